@@ -87,6 +87,8 @@ FP32_PEAK_TFLOPS = 157.3          # MI355X_MICROARCH.md: fp32 matrix (= vector) 
 HBM_PEAK_BPS = 8.0e12             # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s achievable by a float4 copy)
 BF16_PEAK_TFLOPS = 2516.6         # dense bf16 MFMA: 256 CUs x 4 SIMDs x 1024 FLOP/clk x 2.4 GHz (16x the fp32 rate)
 METRIC = "CT slices/sec/node (fwd+bwd) UNet 256×256 bs=32; Dice vs ref"
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000   # --dump-outputs: every .npy file together, headers included
+DUMP_SEED = 2026                       # the fixed sample of an array larger than its share of the budget
 
 
 def make_args(bs, num_gpus, size):
@@ -102,6 +104,59 @@ def make_args(bs, num_gpus, size):
 
 YML = dict(init_channels=64, num_down_samples=4, ret_prob=False, ret_pred=True, build_metrics=True,
            build_summaries=False)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: `arrays` (name -> tensor or host number) written as out_dir/<name>.npy -- float64 for float64
+    tensors and host numbers, float32 for everything else -- DUMP_BUDGET_BYTES in all.  Smallest first, each array may
+    take an equal share of what is left; one larger than its share is replaced by a fixed sample of its flattened elements
+    (numpy default_rng(DUMP_SEED), without replacement, in index order): the same elements on every run and every build.
+    Returns {name: {"shape", "elements"}} for the result line."""
+    import re
+
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    items = []
+    for name, v in arrays.items():
+        if torch.is_tensor(v):
+            t = v.detach()
+            t = t if t.dtype in (torch.float32, torch.float64) else t.to(torch.float32)
+        else:
+            t = torch.tensor(float(v), dtype=torch.float64)
+        items.append((t.numel() * t.element_size(), re.sub(r"[^A-Za-z0-9_.-]", "_", name), t))
+    items.sort(key=lambda x: (x[0], x[1]))
+    header = 4096                                      # room for each file's .npy header
+    left, info = DUMP_BUDGET_BYTES - header * len(items), {}
+    for i, (nbytes, name, t) in enumerate(items):
+        share = left // (len(items) - i)
+        flat = t.reshape(-1)
+        if nbytes > share:
+            k = share // t.element_size()
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.numel(), k, replace=False, shuffle=False))
+            arr = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+        else:
+            arr = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        left -= arr.nbytes
+        info[name] = {"shape": list(t.shape), "elements": int(arr.size)}
+    return info
+
+
+def step_outputs(model, loss):
+    """What a caller of one training step holds afterwards: the loss, the logits, predictions and metrics, the variables
+    after the update and the gradients the update used."""
+    out = {"loss": loss}
+    if torch.is_tensor(model.layers.get("logits")):
+        out["logits"] = model.layers["logits"]
+    for k, v in model.predictions.items():
+        out["pred_" + k] = v
+    for k, v in model.metrics_dict.items():
+        out["metric_" + k] = v
+    for g in sorted(model.params.flat):
+        out["param_" + g] = model.params.flat[g]
+    for g in sorted(model.params.grad):
+        out["grad_" + g] = model.params.grad[g]
+    return out
 
 
 def _cpu_oracle_steps(size, n_classes, bs, warm, timed):
@@ -221,14 +276,17 @@ def infer_main(a, args, model, inputs_of, data, gflop_unit, workload_name, rank,
         feats.append(inp)
     n_fwd = 1 + len(evaluator.mirror_variants)
     slabs = []
+    last = {}                                                   # --dump-outputs: the newest slab probability and case segmentation
 
     def one_step(i):
         slabs.append(evaluator._slab_probability(model, feats[i % 2]))
+        last["slab_probability"] = slabs[-1]
         if len(slabs) == a.case_slabs:
             volume = torch.cat(slabs)
             amax, _ = ops.head_predict(volume.contiguous(), volume.shape[-1], want_preds=False)
             host = amax.view(volume.shape[:-1]).cpu()           # the case's segmentation: one uint8 copy (a host sync per case)
             del slabs[:]
+            last["case_segmentation"] = host
             return host
         return None
 
@@ -238,6 +296,7 @@ def infer_main(a, args, model, inputs_of, data, gflop_unit, workload_name, rank,
     for j in range(a.warmup):
         one_step(j)
     del slabs[:]
+    last.clear()
     if prof_list is not None:
         ops.profile_begin(4096 * n_ev_steps)
     torch.cuda.synchronize()
@@ -250,6 +309,7 @@ def infer_main(a, args, model, inputs_of, data, gflop_unit, workload_name, rank,
     elapsed = time.perf_counter() - t0
     ops.profile_on(None)
     trace_ms, trace_names = ops.profile_read() if prof_list is not None else ([], [])
+    dumped = dump_outputs(a.dump_outputs, last) if a.dump_outputs and rank == 0 else None
     ms = elapsed / a.steps * 1e3
     slices = a.batch * a.steps / elapsed
     fwd_gflop = gflop_unit / 3.0                               # fwd + dgrad + wgrad are three equal contractions
@@ -267,6 +327,8 @@ def infer_main(a, args, model, inputs_of, data, gflop_unit, workload_name, rank,
            "forward_tflops": round(tfl, 2), "forward_frac_of_fp32_peak": round(tfl / FP32_PEAK_TFLOPS, 4),
            "forward_frac_of_dtype_peak": round(tfl / (FP32_PEAK_TFLOPS if a.dtype == "fp32" else BF16_PEAK_TFLOPS), 4),
            "fused_eval_epilogue": bool(ops.FUSE_EVAL)}
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
     if prof_list:
         agg, hbm = {}, {}
         for tag, flops, i0, i1, nbytes in prof_list:
@@ -331,7 +393,16 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="self-test of the multi-rank launch only (no kernels, no GPU needed): every rank joins the process "
                          "group, rank 0 prints the ranks it saw as a `launch-check` line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (train: loss, logits, predictions, metrics, "
+                         "updated variables, gradients; infer: slab probabilities, last case's segmentation) as DIR/<name>.npy, "
+                         "64 MB in all (a fixed seeded sample of larger arrays); the settle phase is skipped so that the state "
+                         "the timed steps start from is the same on every run")
     a = ap.parse_args()
+    if a.steps < 1:
+        raise SystemExit("bench.py --steps must be at least 1")
+    if a.dump_outputs:
+        a.settle_seconds = 0.0          # settle runs a varying number of steps: the dumped state would differ run to run
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -519,6 +590,7 @@ def main():
     ops.profile_on(None)
     ops.side_streams_pause(one_stream)
     loss_val = float(loss.detach())
+    dumped = dump_outputs(a.dump_outputs, step_outputs(model, loss)) if a.dump_outputs and rank == 0 else None
     trace_ms, trace_names = ops.profile_read() if prof is not None else ([], [])
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps)]
     rank_ms, n_ranks_seen = [own / a.steps * 1e3], 1
@@ -729,6 +801,8 @@ def main():
                         " (rocprofv3 --pmc, FETCH_SIZE x2 + WRITE_SIZE)"
             except (OSError, KeyError, ValueError, IndexError):
                 pass
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
         if not a.no_cpu_baseline and world == 1 and a.model == "UNet":
             out["cpu_baseline"] = cpu_baseline(a.size)
             if a.dtype == "fp32":

@@ -14,6 +14,8 @@ import argparse
 import io
 import json
 import os
+import re
+import shlex
 import sys
 import tempfile
 from contextlib import redirect_stdout
@@ -173,7 +175,9 @@ def main():
     with open(os.path.join(HERE, "ref_save_metrics.json"), "w") as f:
         json.dump({"rows": rows, "file": table}, f, indent=1, sort_keys=True)
     write_meta_excerpt()
-    print("wrote ref_config_surface.json, ref_surface.npz, ref_k_folds.json, ref_save_metrics.json, ref_meta_excerpt.json")
+    write_run_scripts()
+    print("wrote ref_config_surface.json, ref_surface.npz, ref_k_folds.json, ref_save_metrics.json, ref_meta_excerpt.json, "
+          "ref_run_scripts.json")
 
 
 def write_meta_excerpt(pids=(3, 5, 32, 4)):
@@ -187,6 +191,37 @@ def write_meta_excerpt(pids=(3, 5, 32, 4)):
     with open(os.path.join(HERE, "ref_meta_excerpt.json"), "w") as f:
         json.dump({"source": "DataLoader/Liver/prepare/meta.json (131 cases), cases " + ", ".join(str(p) for p in sorted(pids)),
                    "n_cases_in_file": len(meta), "cases": pick}, f, sort_keys=True)
+
+
+RUN_SCRIPT_DIRS = ("run_scripts/template", "scripts", "threed_script")
+
+
+def _script_invocations(path):
+    """[(entry script, [argv after it])] of every `python ./entry/<x>.py ...` command in a reference run script, with the
+    shell substitutions the scripts use resolved (tag from the script name, one GPU)."""
+    text = open(path).read()
+    base = os.path.basename(path)[:-3]
+    out = []
+    for m in re.finditer(r"python\s+\./entry/(\w+)\.py\s+(.*?)\$@", text, re.S):
+        body = m.group(2).replace("\\\n", " ")
+        body = body.replace('${BASE_NAME%".sh"}', base).replace("${#GPU_IDS[@]}", "1")
+        out.append([m.group(1), shlex.split(body)])
+    return out
+
+
+def write_run_scripts():
+    """6. The command lines of every shipped run script (run_scripts/template, scripts, threed_script): for each `python
+    ./entry/<x>.py ... $@` the entry script and its argv, split as the shell would split it.  tests/test_entry_host.py parses
+    them with boxsegliver_amd.entry.main.get_arguments."""
+    scripts = {}
+    for d in RUN_SCRIPT_DIRS:
+        for name in sorted(os.listdir(os.path.join(REF, d))):
+            if name.endswith(".sh"):
+                scripts[d + "/" + name] = _script_invocations(os.path.join(REF, d, name))
+    with open(os.path.join(HERE, "ref_run_scripts.json"), "w") as f:
+        json.dump({"source": "the reference's run scripts under " + ", ".join(RUN_SCRIPT_DIRS) + ": entry script and argv of "
+                             "each `python ./entry/<x>.py ... $@` (tag = script name, one GPU)", "scripts": scripts},
+                  f, indent=1, sort_keys=True)
 
 
 if __name__ == "__main__":

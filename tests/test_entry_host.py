@@ -1,31 +1,17 @@
 """CPU: the command-line entry points (boxsegliver_amd.entry.main / main_g; reference entry/main.py:45-85,122-208 and
-entry/main_g.py): sub-command dispatch, the merged flag surface, and -- where the reference tree is present (build container)
--- the flag lists of its shipped run scripts parsed VERBATIM."""
+entry/main_g.py): sub-command dispatch, the merged flag surface, and the flag lists of the reference's shipped run scripts
+parsed VERBATIM (tests/golden/ref_run_scripts.json, written by tests/golden/make_ref_fixtures.py)."""
+import json
 import os
-import re
-import shlex
 
 import pytest
 
 from boxsegliver_amd.entry import main as entry
 
-REF = "/root/reference"
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_run_scripts.json")) as _f:
+    RUN_SCRIPTS = json.load(_f)["scripts"]          # "<dir>/<name>.sh" -> [[entry script, argv], ...]
 
 
-def _script_invocations(path):
-    """[(entry script, [argv after it])] of every `python ./entry/<x>.py ...` command in a reference run script, with the
-    shell substitutions the scripts use resolved (tag from the script name, one GPU)."""
-    text = open(path).read()
-    base = os.path.basename(path)[:-3]
-    out = []
-    for m in re.finditer(r"python\s+\./entry/(\w+)\.py\s+(.*?)\$@", text, re.S):
-        body = m.group(2).replace("\\\n", " ")
-        body = body.replace('${BASE_NAME%".sh"}', base).replace("${#GPU_IDS[@]}", "1")
-        out.append((m.group(1), shlex.split(body)))
-    return out
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference tree (build container only)")
 @pytest.mark.parametrize("script,expect", [
     ("run_scripts/template/001_unet.sh", dict(model="UNet", classes=["Liver", "Tumor"], batch_size=8, learning_policy="plateau",
                                               loss_numeric_w=[0.2, 0.4, 4.4], primary_metric="Tumor/Dice")),
@@ -35,7 +21,7 @@ def _script_invocations(path):
                                           random_flip=7, log_step=125)),
 ])
 def test_reference_run_scripts_parse_verbatim(script, expect):
-    calls = _script_invocations(os.path.join(REF, script))
+    calls = RUN_SCRIPTS[script]
     assert calls, script
     parsed = 0
     for which, argv in calls:
@@ -51,17 +37,14 @@ def test_reference_run_scripts_parse_verbatim(script, expect):
     assert parsed >= 1
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference tree (build container only)")
 def test_every_shipped_script_that_uses_main_or_main_g_parses():
     n = 0
-    for d in ("run_scripts/template", "scripts", "threed_script"):
-        for name in sorted(os.listdir(os.path.join(REF, d))):
-            if not name.endswith(".sh"):
-                continue
-            for which, argv in _script_invocations(os.path.join(REF, d, name)):
-                if which in ("main", "main_g") and argv and argv[0] in entry.SUBCOMMANDS[which == "main_g"]:
-                    entry.get_arguments(argv, guided=(which == "main_g"))
-                    n += 1
+    assert len(RUN_SCRIPTS) == 68                               # every .sh of run_scripts/template, scripts, threed_script
+    for script in sorted(RUN_SCRIPTS):
+        for which, argv in RUN_SCRIPTS[script]:
+            if which in ("main", "main_g") and argv and argv[0] in entry.SUBCOMMANDS[which == "main_g"]:
+                entry.get_arguments(argv, guided=(which == "main_g"))
+                n += 1
     assert n >= 20
 
 
