@@ -9,6 +9,11 @@ MI355X decisions: NDHWC fp32; every conv3d is a composition of the 2-D fp32-MFMA
 plane views (csrc/conv3d.hip); variables are channel-padded to the 32-wide MFMA tile on the device
 (30->32, 60->64, 120->128, 240->256) while checkpoints keep the TF shapes (NetworksV2/padded.py);
 zero-copy concat as in the 2-D nets.
+
+--compute_dtype bf16c (UNETK_BF16: bf16 matrix-core operands, fp32 tensors, statistics, master weights and optimiser): the
+convs the fixed layer rule of include/unetk.h admits (stride 1, Cin % 32 == 0, Cout % 32 == 0, kd in {1, 3}) and the
+transposed convs run on the bf16 pipe; the first conv (Cin = 1) and the four strided convs stay exact fp32 (ops.conv3d_precision).
+--compute_dtype bf16 (bf16 storage) is not built for this net.
 """
 import torch
 
@@ -130,7 +135,8 @@ class UNet3D(base.BaseNet):
         spec = self._spec()
         ns = scope + ("/BatchNorm" if spec.kind == "batch_norm" else "/InstanceNorm")
         z = ops.Conv3dNormRelu.apply(x, p[scope + "/weights"], p[ns + "/gamma"], p[ns + "/beta"],
-                                     p.get(ns + "/moving_mean"), p.get(ns + "/moving_variance"), spec, stride, out)
+                                     p.get(ns + "/moving_mean"), p.get(ns + "/moving_variance"), spec, stride, out,
+                                     self.compute_bf16)
         if self._taps is not None:
             self._taps[scope] = z
         return z
@@ -145,8 +151,9 @@ class UNet3D(base.BaseNet):
             raise ops._abi.UnetkError("UNet3D runs on the GPU only: move `images` to cuda (no CPU path)")
         if images.dim() != 5 or images.shape[4] != self.channel:
             raise ValueError("images must be [bs, D, H, W, {}], got {}".format(self.channel, tuple(images.shape)))
-        if self.compute_bf16:
-            raise NotImplementedError("--compute_dtype bf16 is built for the 2-D nets (UNet, GUNet); UNet3D runs fp32")
+        if self.compute_bf16 not in (0, 1):
+            raise NotImplementedError("--compute_dtype bf16 (bf16 storage) is built for the 2-D nets (UNet, GUNet); "
+                                      "UNet3D runs fp32 or bf16c (bf16 matrix-core operands, fp32 storage)")
         if getattr(self.args, "img_grad", False):
             # reference UNet3D.py:138-140 unpacks three values from tf.image.image_gradients on a 5-D tensor; that op
             # takes 4-D input and returns (dy, dx), so the reference's own path raises at graph build
@@ -192,7 +199,7 @@ class UNet3D(base.BaseNet):
                     for lname, _, stride in layers:
                         scope = "{}/{}/{}".format(nm, block, lname)
                         if lname == "up":
-                            x = ops.Deconv3dConcat.apply(x, p[scope + "/weights"], enc["x"], enc["cat"])
+                            x = ops.Deconv3dConcat.apply(x, p[scope + "/weights"], enc["x"], enc["cat"], self.compute_bf16)
                         else:
                             x = self._unit(x, scope, stride)
 

@@ -95,6 +95,12 @@ _SIGNATURES = {
     "unetk_conv3d_fwd": (c_int, [POINTER(Conv3dDesc), P, P, P, P, P, c_size_t, P]),
     "unetk_conv3d_dgrad": (c_int, [POINTER(Conv3dDesc), P, P, P, P, c_size_t, P]),
     "unetk_conv3d_wgrad": (c_int, [POINTER(Conv3dDesc), P, P, P, P, c_size_t, P]),
+    "unetk_conv3d_pack_bf16": (c_int, [P, c_int, c_int, c_int, P, P, P]),
+    "unetk_conv3d_stat_rows_bf16": (c_int, [POINTER(Conv3dDesc)]),
+    "unetk_conv3d_ws_bytes_bf16": (c_size_t, [POINTER(Conv3dDesc)]),
+    "unetk_conv3d_fwd_bf16": (c_int, [POINTER(Conv3dDesc), P, P, P, P, P, c_size_t, P]),
+    "unetk_conv3d_dgrad_bf16": (c_int, [POINTER(Conv3dDesc), P, P, P, P, c_size_t, P]),
+    "unetk_conv3d_wgrad_bf16": (c_int, [POINTER(Conv3dDesc), P, P, P, P, c_size_t, P]),
     "unetk_norm_finalize_ws_bytes": (c_size_t, [POINTER(NormDesc), c_int]),
     "unetk_norm_finalize": (c_int, [POINTER(NormDesc), P, c_int, P, P, c_float, c_float, c_int, P, P, P, P, P, P,
                                     P, c_size_t, P]),

@@ -268,6 +268,7 @@ struct WgParams {
 // conv_wgrad.hip: dw[9][Cin][Cout] = filter gradient of one 2-D tap plane; ws layout as unetk_conv3x3_wgrad
 size_t unetk_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout, int kd = 1);
 int unetk_wgrad_run(WgParams p, float* dw, void* ws, size_t ws_bytes, hipStream_t st);
+size_t unetk_wgrad_bf16_ws_bytes(int N, int H, int W, int Cin, int Cout, int kd);   // p.bf16 with p.kd fused depth taps
 // conv_wgrad_bf16s.hip: UNETK_BF16S -- x and dy are bf16 in memory (x fp32 for the first layer, 9 * Cin <= 32)
 size_t unetk_wgrad_bf16s_ws_bytes(int N, int H, int W, int Cin, int Cout);
 int unetk_wgrad_bf16s_run(WgParams p, float* dw, void* ws, size_t ws_bytes, hipStream_t st);

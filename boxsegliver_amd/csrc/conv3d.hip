@@ -623,3 +623,108 @@ extern "C" int unetk_conv3d_wgrad(const unetk_conv3d_desc* d, const float* x, co
   }
   return UNETK_OK;
 }
+
+// ---------------------------------------------------------------- UNETK_BF16: the stride-1 3-D convs on the bf16 matrix cores
+// (include/unetk.h: the layer rule).  Forward / input gradient: ONE launch of conv3x3_igemm_bf16_kernel per conv, the kd depth
+// taps fused into its K loop (FT); filter gradient: ONE launch of the bf16 conv3x3_wgrad_kernel with WgParams::kd = kd, fixed
+// splits + fixed-order slab reduction.
+namespace {
+bool bf16_rule_ok(const unetk_conv3d_desc* d) {
+  return d->sd == 1 && d->shw == 1 && (d->kd == 1 || d->kd == 3) && d->Cin % 32 == 0 && d->Cout % 32 == 0;
+}
+// every bf16 entry point takes the workspace of unetk_conv3d_ws_bytes_bf16 and refuses a missing, misaligned or short one
+int bf16_ws_check(const unetk_conv3d_desc* d, const void* ws, size_t ws_bytes) {
+  if (!ws || !unetk_aligned16(ws)) return UNETK_E_BADARG;
+  if (ws_bytes < unetk_conv3d_ws_bytes_bf16(d)) return UNETK_E_WORKSPACE;
+  return UNETK_OK;
+}
+}  // namespace
+
+extern "C" int unetk_conv3d_pack_bf16(const float* w, int kd, int Cin, int Cout, void* wp_fwd, void* wp_dgrad, void* stream) {
+  UNETK_REQUIRE(w && (kd == 1 || kd == 3) && Cin > 0 && Cout > 0 && (wp_fwd || wp_dgrad));
+  if (Cin % 32 != 0 || Cout % 32 != 0) return UNETK_E_UNSUPPORTED;
+  UNETK_REQUIRE((!wp_fwd || unetk_aligned16(wp_fwd)) && (!wp_dgrad || unetk_aligned16(wp_dgrad)));
+  for (int dt = 0; dt < kd; ++dt) {
+    const int64_t o = (int64_t)dt * 9 * Cin * Cout;         // elements per depth tap: floats of w, bf16 of the packs
+    const int rc = unetk_conv3x3_pack_bf16(w + o, Cin, Cout, wp_fwd ? (void*)((bf16_t*)wp_fwd + o) : nullptr,
+                                           wp_dgrad ? (void*)((bf16_t*)wp_dgrad + o) : nullptr, stream);
+    if (rc != UNETK_OK) return rc;
+  }
+  return UNETK_OK;
+}
+
+extern "C" int unetk_conv3d_stat_rows_bf16(const unetk_conv3d_desc* d) {
+  if (!desc_ok(d)) return UNETK_E_BADARG;
+  if (!bf16_rule_ok(d)) return UNETK_E_UNSUPPORTED;
+  return unetk_conv_stat_rows_bf16(d->N * d->D, d->H, d->W, d->Cin, d->Cout);
+}
+
+extern "C" size_t unetk_conv3d_ws_bytes_bf16(const unetk_conv3d_desc* d) {
+  if (!desc_ok(d) || !bf16_rule_ok(d)) return 0;
+  const int np = d->N * d->D;
+  const size_t a = unetk_wgrad_bf16_ws_bytes(np, d->H, d->W, d->Cin, d->Cout, d->kd);
+  const size_t b = unetk_wgrad_ws_bytes(np, d->H, d->W, d->Cin, d->Cout);     // the plain (kd = 1) run's check
+  return a > b ? a : b;
+}
+
+extern "C" int unetk_conv3d_fwd_bf16(const unetk_conv3d_desc* d, const float* x, const void* wp_fwd, float* y,
+                                     float* stat_partials, void* ws, size_t ws_bytes, void* stream) {
+  if (!desc_ok(d)) return UNETK_E_BADARG;
+  if (!bf16_rule_ok(d)) return UNETK_E_UNSUPPORTED;
+  UNETK_REQUIRE(x && wp_fwd && y && unetk_aligned16(x) && unetk_aligned16(wp_fwd) && unetk_aligned16(y));
+  UNETK_REQUIRE(d->x_stride % 4 == 0 && d->y_stride % 4 == 0);
+  const int rc = bf16_ws_check(d, ws, ws_bytes);
+  if (rc != UNETK_OK) return rc;
+  const int HWx = d->H * d->W * d->x_stride;
+  ConvParams p{};
+  p.bf16 = UNETK_BF16;
+  p.x = x; p.wp = (const float*)wp_fwd; p.y = y; p.stat = stat_partials;
+  p.N = d->N * d->D; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout;
+  p.xs = d->x_stride; p.ys = d->y_stride;
+  p.xa = planes(HWx, d->D, 1, d->D);
+  p.ya = planes(d->H * d->W * d->y_stride, d->D, 1, d->D);
+  p.spg = d->D;
+  if (d->kd == 3) { p.kd = 3; p.dsd = 1; p.dshift0 = -1; p.dstep = 1; p.din = d->D; p.dplane = HWx; }   // y[o] = sum_dt x[o - 1 + dt] w[dt]
+  return unetk_conv_run_bf16(p, (hipStream_t)stream);
+}
+
+extern "C" int unetk_conv3d_dgrad_bf16(const unetk_conv3d_desc* d, const float* dy, const void* wp_dgrad, float* dx,
+                                       void* ws, size_t ws_bytes, void* stream) {
+  if (!desc_ok(d)) return UNETK_E_BADARG;
+  if (!bf16_rule_ok(d)) return UNETK_E_UNSUPPORTED;
+  UNETK_REQUIRE(dy && wp_dgrad && dx && unetk_aligned16(dy) && unetk_aligned16(wp_dgrad) && unetk_aligned16(dx));
+  UNETK_REQUIRE(d->x_stride % 4 == 0 && d->y_stride % 4 == 0);
+  const int rc = bf16_ws_check(d, ws, ws_bytes);
+  if (rc != UNETK_OK) return rc;
+  const int HWy = d->H * d->W * d->y_stride;
+  ConvParams p{};
+  p.bf16 = UNETK_BF16;
+  p.x = dy; p.wp = (const float*)wp_dgrad; p.y = dx; p.stat = nullptr;
+  p.N = d->N * d->D; p.H = d->H; p.W = d->W; p.Cin = d->Cout; p.Cout = d->Cin;
+  p.xs = d->y_stride; p.ys = d->x_stride;
+  p.xa = planes(HWy, d->D, 1, d->D);
+  p.ya = planes(d->H * d->W * d->x_stride, d->D, 1, d->D);
+  p.spg = d->D;
+  if (d->kd == 3) { p.kd = 3; p.dsd = 1; p.dshift0 = 1; p.dstep = -1; p.din = d->D; p.dplane = HWy; }   // dx[i] = sum_dt dy[i + 1 - dt] w'[dt]
+  return unetk_conv_run_bf16(p, (hipStream_t)stream);
+}
+
+extern "C" int unetk_conv3d_wgrad_bf16(const unetk_conv3d_desc* d, const float* x, const float* dy, float* dw, void* ws,
+                                       size_t ws_bytes, void* stream) {
+  if (!desc_ok(d)) return UNETK_E_BADARG;
+  if (!bf16_rule_ok(d)) return UNETK_E_UNSUPPORTED;
+  UNETK_REQUIRE(x && dy && dw && unetk_aligned16(x) && unetk_aligned16(dy) && unetk_aligned16(dw));
+  UNETK_REQUIRE(d->x_stride % 4 == 0 && d->y_stride % 4 == 0);
+  const int rc = bf16_ws_check(d, ws, ws_bytes);
+  if (rc != UNETK_OK) return rc;
+  const int HWx = d->H * d->W * d->x_stride;
+  WgParams p{};
+  p.x = x; p.dy = dy;
+  p.N = d->N * d->D; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout;
+  p.xs = d->x_stride; p.ys = d->y_stride;
+  p.bf16 = 1;
+  p.xa = planes(HWx, d->D, 1, d->D);
+  p.ya = planes(d->H * d->W * d->y_stride, d->D, 1, d->D);
+  if (d->kd == 3) { p.kd = 3; p.dshift0 = -1; p.dsd = 1; p.din = d->D; p.spg = d->D; p.dplane = HWx; }
+  return unetk_wgrad_run(p, dw, ws, ws_bytes, (hipStream_t)stream);
+}

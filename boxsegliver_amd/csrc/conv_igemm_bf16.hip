@@ -18,6 +18,13 @@
 // (a half-wave then writes 128 contiguous bytes per pixel instead of two 64-byte pieces), the filter pack of this mode
 // (unetk_conv3x3_pack_bf16s) permutes the output channels inside every 64-channel block: MFMA column l of tile tn holds
 // channel 2 l + tn.
+//
+// FT = true is the stride-1 3-D conv of UNETK_BF16 (unetk_conv3d_fwd_bf16 / _dgrad_bf16): the kd depth taps are contracted in
+// ONE launch, K = kd x 9 x Cin.  Image i is output plane dep = i % spg of its sample; tap dt reads the input plane
+// dep * dsd + dshift0 + dt * dstep at xa.off(i) + (dshift0 + dt * dstep) * dplane floats, with the filter panel
+// wp + dt * 9 * Cin * Cout.  One block = one output plane, so a tap whose plane lies outside [0, din) is skipped for the
+// whole block (the chunk range below); the output is written once, no memset and no y += acc passes.  Halo and filter
+// requests are unconditional: an out-of-image halo pixel reads a zero page selected by pointer.
 #include "common.h"
 #include "pack.h"
 
@@ -38,6 +45,7 @@ constexpr int CKB = 32;  // input channels per K-chunk
 constexpr int PSQ = 5;   // LDS pixel stride in 16-B units: 64 B of bf16 + 16 B pad -> conflict-free ds_read_b128
 constexpr int TW = 16;
 constexpr int HWD = TW + 2;
+__device__ float kZeroF8[8] = {};   // what an out-of-image halo pixel of the FT kernels reads (NOT const: see conv_igemm.hip kZeroF4)
 
 __device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {
   uint32_t r;
@@ -47,11 +55,12 @@ __device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {
 
 // NBR: input gradient fused with the producing unit's norm-backward reduction (ConvParams::ny) -- its own instantiation so
 // the plain kernels keep their register budget (see conv_igemm.hip).
-template <int WM, int WN, int TM, int TN, bool BS = false, bool NBR = false>
+template <int WM, int WN, int TM, int TN, bool BS = false, bool NBR = false, bool FT = false>
 __global__ __launch_bounds__(WM* WN * 64) void conv3x3_igemm_bf16_kernel(ConvParams p) {
   constexpr int RING = UNETK_BF16_RING(WM, WN, TM, TN);   // depth of the filter-panel register ring (divides 9)
   static_assert(!BS || (TN == 2 && (WN * TN * 32 == 128 || WN * TN * 32 == 64)), "bf16 storage packs channel pairs (tile 0 / tile 1) into one word");
   static_assert(!NBR || BS, "the fused reduction is built for bf16 storage");
+  static_assert(!FT || !BS, "fused depth taps: fp32 storage (UNETK_BF16)");
   constexpr int NT = WM * WN * 64;
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   constexpr int TH = BM / TW, HH = TH + 2;
@@ -99,8 +108,20 @@ __global__ __launch_bounds__(WM* WN * 64) void conv3x3_igemm_bf16_kernel(ConvPar
 #pragma unroll
   for (int r = 0; r < WR; ++r) {
     const int idx = tid + r * NT;
-    const int q = idx / BN, n = idx - q * BN;
+    const int q = (FT ? min(idx, WB_Q - 1) : idx) / BN;     // FT: threads past a small panel request its last unit again
+    const int n = (FT ? min(idx, WB_Q - 1) : idx) - q * BN;
     woff[r] = q * p.Cout + n0 + n;
+  }
+  // fused depth taps: the chunk index runs over (valid depth tap, 32-channel chunk)
+  const int nchunks = p.Cin / CKB;
+  int c_begin = 0, c_end = nchunks;
+  if constexpr (FT) {
+    const int dep = (n_img % p.spg) * p.dsd + p.dshift0;
+    int lo = 0, hi = p.kd;
+    while (lo < hi && (unsigned)(dep + lo * p.dstep) >= (unsigned)p.din) ++lo;
+    while (hi > lo && (unsigned)(dep + (hi - 1) * p.dstep) >= (unsigned)p.din) --hi;
+    c_begin = lo * nchunks;
+    c_end = hi * nchunks;
   }
 
   float4 hreg[BS ? 1 : HR][2];
@@ -116,6 +137,17 @@ __global__ __launch_bounds__(WM* WN * 64) void conv3x3_igemm_bf16_kernel(ConvPar
     for (int r = 0; r < HR; ++r) hoff[r] = hok[r] ? hoff[r] : 0;
   }
   auto load_halo = [&](int c) {
+    if constexpr (FT) {
+      const int dt = c / nchunks;
+      const int64_t soff = (int64_t)(p.dshift0 + dt * p.dstep) * p.dplane + (c - dt * nchunks) * CKB;
+#pragma unroll
+      for (int r = 0; r < HR; ++r) {
+        const float* src = hok[r] ? p.x + hoff[r] + soff : kZeroF8;
+        hreg[r][0] = ldg4(src);
+        hreg[r][1] = ldg4(src + 4);
+      }
+      return;
+    }
 #pragma unroll
     for (int r = 0; r < HR; ++r) {
       if constexpr (BS) {
@@ -146,6 +178,13 @@ __global__ __launch_bounds__(WM* WN * 64) void conv3x3_igemm_bf16_kernel(ConvPar
       }
   };
   auto load_w = [&](int c, int t) {        // t: compile-time under the unrolled tap loop (register-array index t % RING)
+    if constexpr (FT) {
+      const int dt = c / nchunks;
+      const uint4* base = wq + ((int64_t)(dt * 9 + t) * cin8 + (c - dt * nchunks) * (CKB / 8)) * p.Cout;
+#pragma unroll
+      for (int r = 0; r < WR; ++r) wring[t % RING][r] = *reinterpret_cast<const u32x4*>(base + woff[r]);
+      return;
+    }
     const uint4* base = wq + ((int64_t)t * cin8 + c * (CKB / 8)) * p.Cout;
 #pragma unroll
     for (int r = 0; r < WR; ++r)
@@ -179,23 +218,21 @@ __global__ __launch_bounds__(WM* WN * 64) void conv3x3_igemm_bf16_kernel(ConvPar
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
 
-  const int nchunks = p.Cin / CKB;
-
-  load_halo(0);
+  load_halo(c_begin);
 #pragma unroll
-  for (int t = 0; t < RING; ++t) load_w(0, t);
+  for (int t = 0; t < RING; ++t) load_w(c_begin, t);
   store_halo(0);
   store_w(0, 0);
-  load_w(min(RING / 9, nchunks - 1), RING % 9);            // step RING's panel into the slot just emptied
+  load_w(min(c_begin + RING / 9, c_end - 1), RING % 9);    // step RING's panel into the slot just emptied
   __syncthreads();
 
   // The prefetches are UNCONDITIONAL (the last chunk re-fetches itself / tap 0 into the free buffers, never read): with
   // `if (more_chunks)` guards the compiler peeled the last chunk out of the loop and shuttled accumulators between
   // AGPRs and VGPRs around the peeled copy (tools/asm_lint.py: accumulator reads before the last MFMA).
   int step = 0;
-  for (int c = 0; c < nchunks; ++c) {
-    const uint4* hb = halo + (c & 1) * HALO_Q;
-    const int cn = min(c + 1, nchunks - 1);
+  for (int c = c_begin; c < c_end; ++c) {
+    const uint4* hb = halo + ((c - c_begin) & 1) * HALO_Q;
+    const int cn = min(c + 1, c_end - 1);
 #pragma unroll
     for (int t = 0; t < 9; ++t, ++step) {
       if (t == 0) load_halo(cn);                     // HBM latency >> one tap step: a whole chunk of slack
@@ -218,8 +255,8 @@ __global__ __launch_bounds__(WM* WN * 64) void conv3x3_igemm_bf16_kernel(ConvPar
       }
 
       store_w((t + 1) % 9, (step + 1) & 1);                            // the next step's panel (requested RING - 1 steps ago)
-      load_w(min(c + (t + 1 + RING) / 9, nchunks - 1), (t + 1 + RING) % 9);   // that slot's next use, RING steps from now
-      if (t == 8) store_halo((c + 1) & 1);
+      load_w(min(c + (t + 1 + RING) / 9, c_end - 1), (t + 1 + RING) % 9);   // that slot's next use, RING steps from now
+      if (t == 8) store_halo((c + 1 - c_begin) & 1);
       // NOT __syncthreads(): its fence waits for every outstanding global load (vmcnt(0)), i.e. it would force the halo
       // prefetch of the next chunk -- issued at tap 0 for use at tap 8 -- to land within ONE tap step.  The LDS writes
       // above must be complete (lgkmcnt(0)) before the barrier; the register-staged loads are tracked by the compiler.
@@ -350,14 +387,14 @@ inline BfCfg pick_bf16(int H, int Cin, int Cout, int N = 1 << 20, int W = 1 << 1
   return {4, 16};
 }
 
-template <int WM, int WN, int TM, int TN, bool BS = false, bool NBR = false>
+template <int WM, int WN, int TM, int TN, bool BS = false, bool NBR = false, bool FT = false>
 int launch_bf16(const ConvParams& p, int n_mtiles, hipStream_t st) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   constexpr int TH = BM / TW;
   constexpr size_t lds = (size_t)(2 * (TH + 2) * HWD * PSQ + 2 * (CKB / 8) * BN) * 16;
   static_assert(lds >= 2 * WM * BN * sizeof(float), "stat scratch must fit");
   static_assert(lds <= 160 * 1024, "LDS budget");
-  auto kern = conv3x3_igemm_bf16_kernel<WM, WN, TM, TN, BS, NBR>;
+  auto kern = conv3x3_igemm_bf16_kernel<WM, WN, TM, TN, BS, NBR, FT>;
   static bool attr_done = false;
   if (!attr_done) {
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -389,7 +426,7 @@ int unetk_conv_run_bf16(ConvParams p, hipStream_t st) {
   const BfCfg cfg = pick_bf16(p.H, p.Cin, p.Cout, p.N, p.W);
   if (cfg.id < 0) return UNETK_E_UNSUPPORTED;
   if (p.bf16 == UNETK_BF16S) {   // bf16 storage: 16-B halo pieces of 8 channels, 4-B output words of 2 channels
-    if (cfg.id == 4 || p.accumulate) return UNETK_E_UNSUPPORTED;     // Cout % 64 != 0 / 3-D depth taps: not in this mode
+    if (cfg.id == 4 || p.accumulate || p.kd > 1) return UNETK_E_UNSUPPORTED;     // Cout % 64 != 0 / 3-D depth taps: not in this mode
     if (unetk_conv_bf16s_v3_ok(p.N, p.H, p.W, p.Cin, p.Cout, p.xs, p.ys) && (p.ny == nullptr || (p.Cout % 128 == 0 && p.nys % 8 == 0)))
       return unetk_conv_bf16s_v3_run(p, st);
     if (p.asc != nullptr) return UNETK_E_UNSUPPORTED;      // the inference epilogue lives in the persistent kernel only
@@ -423,6 +460,17 @@ int unetk_conv_run_bf16(ConvParams p, hipStream_t st) {
   p.tiles_w = (p.W + TW - 1) / TW;
   const int n_mtiles = p.N * p.tiles_h * p.tiles_w;
   p.stat_rows = n_mtiles;
+  if (p.kd > 1) {        // a stride-1 3-D conv: all depth taps in one launch (FT)
+    if (p.accumulate || p.asc != nullptr || p.spg < 1 || p.din < 1 || p.dsd < 1 || (p.dstep != 1 && p.dstep != -1))
+      return UNETK_E_UNSUPPORTED;
+    switch (cfg.id) {
+      case 0: p.n_ntiles = p.Cout / 128; return launch_bf16<4, 2, 4, 2, false, false, true>(p, n_mtiles, st);
+      case 1: p.n_ntiles = p.Cout / 128; return launch_bf16<2, 2, 2, 2, false, false, true>(p, n_mtiles, st);
+      case 2: p.n_ntiles = p.Cout / 64; return launch_bf16<4, 1, 2, 2, false, false, true>(p, n_mtiles, st);
+      case 3: p.n_ntiles = p.Cout / 64; return launch_bf16<4, 1, 1, 2, false, false, true>(p, n_mtiles, st);
+      default: p.n_ntiles = p.Cout / 32; return launch_bf16<4, 1, 2, 1, false, false, true>(p, n_mtiles, st);
+    }
+  }
   switch (cfg.id) {
     case 0: p.n_ntiles = p.Cout / 128; return launch_bf16<4, 2, 4, 2>(p, n_mtiles, st);
     case 1: p.n_ntiles = p.Cout / 128; return launch_bf16<2, 2, 2, 2>(p, n_mtiles, st);

@@ -612,6 +612,14 @@ size_t unetk_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout, int kd) {
   return 256 + (size_t)S * 9 * Cin * Cout * sizeof(float);    // 256 B zero page + slabs
 }
 
+// UNETK_BF16 with kd fused depth taps (the stride-1 3-D filter gradient): the bf16 plan's splits x kd slabs
+size_t unetk_wgrad_bf16_ws_bytes(int N, int H, int W, int Cin, int Cout, int kd) {
+  if (kd < 1) kd = 1;
+  const WgPlan pl = wg_plan(N, H, W, Cin, Cout, true, kd);
+  if (pl.mode != 0) return 0;
+  return 256 + (size_t)pl.S * kd * 9 * Cin * Cout * sizeof(float);    // 256 B zero page + slabs
+}
+
 bool unetk_wgrad_strided_ok(int Cin, int Cout) { return wg_strided_ok(Cin, Cout); }
 
 size_t unetk_wgrad_strided_ws_bytes(int N, int Ho, int Wo, int Cin, int Cout, int kd) {
@@ -671,8 +679,11 @@ int unetk_wgrad_run(WgParams p, float* dw, void* ws, size_t ws_bytes, hipStream_
   const int KD = p.kd > 1 ? p.kd : 1;
   const WgPlan pl = wg_plan(p.N, p.H, p.W, p.Cin, p.Cout, p.bf16 != 0, KD);
   if (pl.mode < 0) return UNETK_E_UNSUPPORTED;
-  if (KD > 1 && (p.bf16 || (pl.mode != 0 && pl.mode != 2 && pl.mode != 5))) return UNETK_E_UNSUPPORTED;   // MFMA fp32 kernels only
-  if (ws_bytes < unetk_wgrad_ws_bytes(p.N, p.H, p.W, p.Cin, p.Cout, KD)) return UNETK_E_WORKSPACE;
+  // fused depth taps: the MFMA kernels only (fp32: plain or stacked planes; UNETK_BF16: the plain tiles, BF = true)
+  if (KD > 1 && (p.bf16 ? pl.mode != 0 : (pl.mode != 0 && pl.mode != 2 && pl.mode != 5))) return UNETK_E_UNSUPPORTED;
+  if (ws_bytes < (p.bf16 && KD > 1 ? unetk_wgrad_bf16_ws_bytes(p.N, p.H, p.W, p.Cin, p.Cout, KD)
+                                   : unetk_wgrad_ws_bytes(p.N, p.H, p.W, p.Cin, p.Cout, KD)))
+    return UNETK_E_WORKSPACE;
   p.slab = pl.S == 1 ? dw : (float*)ws + 64;           // a single split writes the gradient in place
   p.tiles_h = pl.tiles_h; p.tiles_w = pl.tiles_w; p.total_tiles = pl.total_tiles;
   p.tiles_per_split = pl.tiles_per_split; p.n_ci_tiles = pl.n_ci_tiles; p.n_co_tiles = pl.n_co_tiles;

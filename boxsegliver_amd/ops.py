@@ -331,13 +331,13 @@ SIDE_WGRAD_FIRST = os.environ.get("UNETK_SIDE_WGRAD_FIRST", "1") == "1"         
 SIDE_WGRAD3D_FIRST = os.environ.get("UNETK_SIDE_WGRAD3D_FIRST", "1") == "1"      # the 3-D units (Conv3dNormRelu.backward)
 
 
-def _wgrad3d_on_side(x, dy, d, out):
+def _wgrad3d_on_side(x, dy, d, out, precision=0):
     if _Side.stream is None:
         _Side.stream = torch.cuda.Stream(device=x.device)
     side = _Side.stream
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
-        dw = conv3d_wgrad(x, dy, d, out=out, ws_pool=_Side.ws)
+        dw = conv3d_wgrad(x, dy, d, out=out, ws_pool=_Side.ws, precision=precision)
     dy.record_stream(side)
     x.record_stream(side)
     if not _Side.pending:
@@ -641,11 +641,37 @@ def conv3d_out_shape(d):
     return (d.N, do.value, ho.value, wo.value, d.Cout)
 
 
-def conv3d_pack(w, want_dgrad=True):
-    """w: TF DHWIO [kd,3,3,Cin,Cout] (Cin % 4 == 0 for the MFMA path)."""
+def conv3d_bf16_ok(d):
+    """The UNETK_BF16 layer rule of the 3-D convs (include/unetk.h): stride 1, Cin % 32 == 0, Cout % 32 == 0, kd in {1, 3}."""
+    return d.sd == 1 and d.shw == 1 and d.kd in (1, 3) and d.Cin % 32 == 0 and d.Cout % 32 == 0
+
+
+def conv3d_precision(d, precision):
+    """The precision a 3-D conv of descriptor d runs at when the net asks for `precision`: UNETK_BF16 only for the layers the
+    rule admits, every other layer stays exact fp32 (the caller need not know which)."""
+    return _abi.BF16 if int(precision or 0) == _abi.BF16 and conv3d_bf16_ok(d) else _abi.FP32
+
+
+def conv3d_pack(w, want_dgrad=True, precision=0):
+    """w: TF DHWIO [kd,3,3,Cin,Cout] (Cin % 4 == 0 for the MFMA path).  precision UNETK_BF16: kd bf16 K8 packs (one per
+    depth tap, the layout of unetk_conv3x3_pack_bf16), Cin % 32 == 0 and Cout % 32 == 0."""
     _require_cuda(w)
     kd, kh, kw, cin, cout = w.shape
     assert kh == 3 and kw == 3
+    prec = int(precision or 0)
+    if prec not in (_abi.FP32, _abi.BF16):
+        raise _abi.UnetkError("conv3d_pack: precision {} is not built for the 3-D convs".format(prec))
+    if prec == _abi.BF16:
+        def build_bf16():
+            wp_f = torch.empty(kd * 9 * cin * cout, dtype=torch.bfloat16, device=w.device)
+            wp_d = torch.empty_like(wp_f) if want_dgrad else None
+            check(_abi.lib().unetk_conv3d_pack_bf16(ptr(w), kd, cin, cout, ptr(wp_f), ptr(wp_d), stream_ptr()),
+                  "conv3d_pack_bf16")
+            src, tap = 9 * cin * cout * 4, 9 * cin * cout * 2        # bytes per depth tap: fp32 source, bf16 packs
+            items = [(PK_CONV_BF16, 0, cin, cout, w.data_ptr() + a * src, wp_f.data_ptr() + a * tap,
+                      (wp_d.data_ptr() + a * tap) if want_dgrad else None) for a in range(kd)]
+            return wp_f, wp_d, items
+        return PACKS.get(w, ("c3d", prec, bool(want_dgrad)), build_bf16)
 
     def build():
         wp_f = torch.empty(kd * 9 * cin * cout, dtype=torch.float32, device=w.device)
@@ -658,51 +684,65 @@ def conv3d_pack(w, want_dgrad=True):
     return PACKS.get(w, ("c3d", 0, bool(want_dgrad)), build)
 
 
-def _ws3d(d, device):
-    nbytes = _abi.lib().unetk_conv3d_ws_bytes(ctypes.byref(d))
-    return WORKSPACE.get(nbytes, device), nbytes
+def _bf16_3d(d, precision):
+    """True when the call runs the UNETK_BF16 entry points; a bf16 request for a layer outside the rule is an error here
+    (Conv3dNormRelu picks the layer's precision with conv3d_precision)."""
+    if int(precision or 0) == _abi.FP32:
+        return False
+    if int(precision) != _abi.BF16 or not conv3d_bf16_ok(d):
+        raise _abi.UnetkError("conv3d: precision {} is not built for kd={} stride=({},{}) Cin={} Cout={}".format(
+            int(precision), d.kd, d.sd, d.shw, d.Cin, d.Cout))
+    return True
 
 
-def conv3d_fwd(x, w, d, want_stats=True):
-    """x [N,D,H,W,Cin] dense; w = packed filter when conv_uses_mfma(Cin, Cout) else raw DHWIO (kd == 1)."""
+def _ws3d(d, device, bf16=False, pool=None):
+    nbytes = (_abi.lib().unetk_conv3d_ws_bytes_bf16 if bf16 else _abi.lib().unetk_conv3d_ws_bytes)(ctypes.byref(d))
+    return (pool or WORKSPACE).get(nbytes, device), nbytes
+
+
+def conv3d_fwd(x, w, d, want_stats=True, precision=0):
+    """x [N,D,H,W,Cin] dense; w = packed filter when conv_uses_mfma(Cin, Cout) else raw DHWIO (kd == 1).
+    precision UNETK_BF16: bf16 matrix-core operands (w from conv3d_pack(..., precision=UNETK_BF16)), fp32 tensors."""
     _require_cuda(x, w)
     assert x.stride(-1) == 1 and x.stride(-2) == d.x_stride        # dense, or a channel slice of a concat buffer
+    bf16 = _bf16_3d(d, precision)
     y = torch.empty(conv3d_out_shape(d), dtype=torch.float32, device=x.device)
     stats, rows = None, 0
     if want_stats:
-        rows = _abi.lib().unetk_conv3d_stat_rows(ctypes.byref(d))
+        rows = (_abi.lib().unetk_conv3d_stat_rows_bf16 if bf16 else _abi.lib().unetk_conv3d_stat_rows)(ctypes.byref(d))
         if rows <= 0:
             check(rows, "conv3d_stat_rows")
         stats = torch.empty((2, rows, d.Cout), dtype=torch.float32, device=x.device)
-    ws, nbytes = _ws3d(d, x.device)
+    ws, nbytes = _ws3d(d, x.device, bf16)
     flops = 2.0 * y.numel() / d.Cout * d.kd * 9 * d.Cin * d.Cout
-    with _Timed("conv3d_fwd", flops, "k{}s{}{} {}".format(d.kd, d.sd, d.shw, tuple(x.shape))):
-        check(_abi.lib().unetk_conv3d_fwd(ctypes.byref(d), ptr(x), ptr(w), ptr(y), ptr(stats), ptr(ws), nbytes,
-                                          stream_ptr()), "conv3d_fwd")
+    fn = _abi.lib().unetk_conv3d_fwd_bf16 if bf16 else _abi.lib().unetk_conv3d_fwd
+    with _Timed("conv3d_fwd<bf16>" if bf16 else "conv3d_fwd", flops, "k{}s{}{} {}".format(d.kd, d.sd, d.shw, tuple(x.shape))):
+        check(fn(ctypes.byref(d), ptr(x), ptr(w), ptr(y), ptr(stats), ptr(ws), nbytes, stream_ptr()), "conv3d_fwd")
     return y, stats, rows
 
 
-def conv3d_dgrad(dy, wp_dgrad, d):
+def conv3d_dgrad(dy, wp_dgrad, d, precision=0):
     assert dy.is_contiguous()
+    bf16 = _bf16_3d(d, precision)
     dx = torch.empty((d.N, d.D, d.H, d.W, d.Cin), dtype=torch.float32, device=dy.device)
-    ws, nbytes = _ws3d(d, dy.device)
+    ws, nbytes = _ws3d(d, dy.device, bf16)
     flops = 2.0 * dy.numel() / d.Cout * d.kd * 9 * d.Cin * d.Cout
-    with _Timed("conv3d_dgrad", flops, "k{}s{}{} {}".format(d.kd, d.sd, d.shw, tuple(dx.shape))):
-        check(_abi.lib().unetk_conv3d_dgrad(ctypes.byref(d), ptr(dy), ptr(wp_dgrad), ptr(dx), ptr(ws), nbytes,
-                                            stream_ptr()), "conv3d_dgrad")
+    fn = _abi.lib().unetk_conv3d_dgrad_bf16 if bf16 else _abi.lib().unetk_conv3d_dgrad
+    with _Timed("conv3d_dgrad<bf16>" if bf16 else "conv3d_dgrad", flops, "k{}s{}{} {}".format(d.kd, d.sd, d.shw, tuple(dx.shape))):
+        check(fn(ctypes.byref(d), ptr(dy), ptr(wp_dgrad), ptr(dx), ptr(ws), nbytes, stream_ptr()), "conv3d_dgrad")
     return dx
 
 
-def conv3d_wgrad(x, dy, d, out=None, ws_pool=None):
+def conv3d_wgrad(x, dy, d, out=None, ws_pool=None, precision=0):
     assert x.stride(-2) == d.x_stride and dy.is_contiguous()
+    bf16 = _bf16_3d(d, precision)
     dw = out if out is not None else torch.empty((d.kd, 3, 3, d.Cin, d.Cout), dtype=torch.float32, device=x.device)
     assert tuple(dw.shape) == (d.kd, 3, 3, d.Cin, d.Cout) and dw.is_contiguous()
-    nbytes = _abi.lib().unetk_conv3d_ws_bytes(ctypes.byref(d))
-    ws = (ws_pool or WORKSPACE).get(nbytes, x.device)
+    ws, nbytes = _ws3d(d, x.device, bf16, ws_pool)
     flops = 2.0 * dy.numel() / d.Cout * d.kd * 9 * d.Cin * d.Cout
-    with _Timed("conv3d_wgrad", flops, "k{}s{}{} {}".format(d.kd, d.sd, d.shw, tuple(x.shape))):
-        check(_abi.lib().unetk_conv3d_wgrad(ctypes.byref(d), ptr(x), ptr(dy), ptr(dw), ptr(ws), nbytes, stream_ptr()),
-              "conv3d_wgrad")
+    fn = _abi.lib().unetk_conv3d_wgrad_bf16 if bf16 else _abi.lib().unetk_conv3d_wgrad
+    with _Timed("conv3d_wgrad<bf16>" if bf16 else "conv3d_wgrad", flops, "k{}s{}{} {}".format(d.kd, d.sd, d.shw, tuple(x.shape))):
+        check(fn(ctypes.byref(d), ptr(x), ptr(dy), ptr(dw), ptr(ws), nbytes, stream_ptr()), "conv3d_wgrad")
     return dw
 
 
@@ -966,11 +1006,25 @@ def deconv2x2_bwd(x, wp_dgrad, cat, dcat, coff, cout, bf16=False, out_w=None, ou
     return dx, dw, db
 
 
-def deconv3d_pack(w):
-    """w: TF [kd,2,2,Cout,Cin] with kd in {1, 2}."""
+def deconv3d_pack(w, precision=0):
+    """w: TF [kd,2,2,Cout,Cin] with kd in {1, 2}.  precision UNETK_BF16: the bf16 packs (Cin % 32 == 0 and Cout % 32 == 0)."""
     _require_cuda(w)
     kd, kh, kw, cout, cin = w.shape
     assert kh == 2 and kw == 2 and kd in (1, 2)
+    prec = int(precision or 0)
+    if prec not in (_abi.FP32, _abi.BF16):
+        raise _abi.UnetkError("deconv3d_pack: precision {} is not built for the 3-D transposed convs".format(prec))
+    if prec == _abi.BF16:
+        def build_bf16():
+            wp_f = torch.empty(kd * 4 * cin * cout, dtype=torch.bfloat16, device=w.device)
+            wp_d = torch.empty_like(wp_f)
+            check(_abi.lib().unetk_deconv3d_pack_bf16(ptr(w), kd, cin, cout, ptr(wp_f), ptr(wp_d), stream_ptr()),
+                  "deconv3d_pack_bf16")
+            src, tap = 4 * cin * cout * 4, 4 * cin * cout * 2
+            items = [(PK_DECONV_BF16, 0, cin, cout, w.data_ptr() + a * src, wp_f.data_ptr() + a * tap,
+                      wp_d.data_ptr() + a * tap) for a in range(kd)]
+            return wp_f, wp_d, items
+        return PACKS.get(w, ("d3d", prec, True), build_bf16)
 
     def build():
         wp_f = torch.empty(kd * 4 * cin * cout, dtype=torch.float32, device=w.device)
@@ -989,19 +1043,19 @@ def _pix_stride_nd(t):
     return t.stride(-2)
 
 
-def deconv3d_fwd(x, wp_fwd, bias, cat, coff, cout, kd):
+def deconv3d_fwd(x, wp_fwd, bias, cat, coff, cout, kd, precision=0):
     n, dd, h, w, cin = x.shape
     assert x.is_contiguous()
-    d = Deconv3dDesc(n, dd, h, w, cin, cout, kd, _pix_stride_nd(cat), coff)
+    d = Deconv3dDesc(n, dd, h, w, cin, cout, kd, _pix_stride_nd(cat), coff, int(precision or 0))
     with _Timed("deconv3d_fwd", 8.0 * kd * n * dd * h * w * cin * cout, "kd{} {}".format(kd, tuple(x.shape))):
         check(_abi.lib().unetk_deconv3d_fwd(ctypes.byref(d), ptr(x), ptr(wp_fwd), ptr(bias), ptr(cat), stream_ptr()),
               "deconv3d_fwd")
     return cat
 
 
-def deconv3d_bwd(x, wp_dgrad, cat, dcat, coff, cout, kd, want_dbias, out_w=None):
+def deconv3d_bwd(x, wp_dgrad, cat, dcat, coff, cout, kd, want_dbias, out_w=None, precision=0):
     n, dd, h, w, cin = x.shape
-    d = Deconv3dDesc(n, dd, h, w, cin, cout, kd, _pix_stride_nd(cat), coff)
+    d = Deconv3dDesc(n, dd, h, w, cin, cout, kd, _pix_stride_nd(cat), coff, int(precision or 0))
     assert _pix_stride_nd(dcat) == _pix_stride_nd(cat)
     nbytes = _abi.lib().unetk_deconv3d_bwd_ws_bytes(ctypes.byref(d))
     if nbytes == 0:
@@ -1592,14 +1646,19 @@ class Conv3dNormRelu(_Op):
     (1,3,3) or (3,3,3), stride 1 / (1,2,2) / (2,2,2), SAME, no bias, instance or batch norm, ReLU."""
 
     @staticmethod
-    def forward(ctx, x, w, gamma, beta, moving_mean, moving_var, spec, stride, out):
+    def forward(ctx, x, w, gamma, beta, moving_mean, moving_var, spec, stride, out, precision=0):
+        """precision: UNETK_FP32, or UNETK_BF16 (--compute_dtype bf16c) -- applied when the layer meets the rule of
+        conv3d_bf16_ok, else the layer runs exact fp32."""
         _require_cuda(x, w)
         kd, cin, cout = w.shape[0], w.shape[3], w.shape[4]
         mfma = conv_uses_mfma(cin, cout)
         need_dx = ctx.needs_input_grad[0]
         live8 = getattr(w, "unetk_live8", None)      # set on channel-padded filters by PaddedParamStore
         d = conv3d_desc(x.shape, cout, kd, stride, x_stride=_pix_stride_nd(x), live8=live8)
-        if mfma:
+        prec = conv3d_precision(d, precision)
+        if prec:
+            wp_f, wp_d = conv3d_pack(w, want_dgrad=need_dx, precision=prec)
+        elif mfma:
             wp_f, wp_d = conv3d_pack(w, want_dgrad=need_dx)
         else:
             if kd != 1 or need_dx:
@@ -1607,7 +1666,7 @@ class Conv3dNormRelu(_Op):
             wp_f, wp_d = w, None
         plain = spec.kind == "none"                # --without_norm: z = relu(y + bias); `beta` carries the conv bias
         use_batch_stats = (spec.training or spec.per_sample) and not plain
-        y, stats, rows = conv3d_fwd(x, wp_f, d, want_stats=use_batch_stats)
+        y, stats, rows = conv3d_fwd(x, wp_f, d, want_stats=use_batch_stats, precision=prec)
         z = out if out is not None else torch.empty_like(y)
         nd = norm_desc(y.shape, spec.per_sample, _pix_stride_nd(z))
         if plain:
@@ -1620,7 +1679,7 @@ class Conv3dNormRelu(_Op):
         norm_apply_relu(nd, y, aff, z)
         if spec.training:
             ctx.save_for_backward(x, y, aff)
-            ctx.wp_d, ctx.need_dx, ctx.d, ctx.nd, ctx.live8 = wp_d, need_dx, d, nd, live8
+            ctx.wp_d, ctx.need_dx, ctx.d, ctx.nd, ctx.live8, ctx.prec = wp_d, need_dx, d, nd, live8, prec
             ctx.has = (gamma is not None, beta is not None)
             ctx.sinks = (grad_sink(w, ctx), grad_sink(gamma, ctx), grad_sink(beta, ctx) if not plain else None)
             ctx.dbg = (w.detach(), gamma, beta, stride, z.detach()) if DEBUG_CAPTURE is not None else None
@@ -1636,19 +1695,20 @@ class Conv3dNormRelu(_Op):
         dy, dgamma, dbeta, _, _ = norm_relu_bwd_nd(ctx.nd, y, dz, aff, ctx.has[0], ctx.has[1], out_gamma=sg, out_beta=sb)
         voxels = dy.numel() // dy.shape[-1]
         on_side = (not debug) and sw is not None and ctx.need_dx and 0 < voxels <= SIDE_WGRAD3D_VOXELS and not _Side.paused
+        prec = ctx.prec
         if not on_side:
-            dw = conv3d_wgrad(x, dy, ctx.d, out=sw)
+            dw = conv3d_wgrad(x, dy, ctx.d, out=sw, precision=prec)
         elif SIDE_WGRAD3D_FIRST:
-            dw = _wgrad3d_on_side(x, dy, ctx.d, sw)      # queued behind dy only: runs BESIDE this layer's input gradient
+            dw = _wgrad3d_on_side(x, dy, ctx.d, sw, prec)      # queued behind dy only: runs BESIDE this layer's input gradient
         dense = conv3d_desc(x.shape, ctx.d.Cout, ctx.d.kd, (ctx.d.sd, ctx.d.shw, ctx.d.shw), live8=ctx.live8)   # dx is dense
-        dx = conv3d_dgrad(dy, ctx.wp_d, dense) if ctx.need_dx else None
+        dx = conv3d_dgrad(dy, ctx.wp_d, dense, precision=prec) if ctx.need_dx else None
         if on_side and not SIDE_WGRAD3D_FIRST:
-            dw = _wgrad3d_on_side(x, dy, ctx.d, sw)      # queued behind the input gradient: runs beside the NEXT unit's norm backward
+            dw = _wgrad3d_on_side(x, dy, ctx.d, sw, prec)      # queued behind the input gradient: runs beside the NEXT unit's norm backward
         if DEBUG_CAPTURE is not None:
             DEBUG_CAPTURE.append(dict(kind="conv3d", x=x, y=y, w=ctx.dbg[0], gamma=ctx.dbg[1], beta=ctx.dbg[2],
                                       stride=ctx.dbg[3], z=ctx.dbg[4], dz=dz, dy=dy, dw=dw, dx=dx, dgamma=dgamma, dbeta=dbeta,
                                       per_sample=bool(ctx.nd.per_sample), plain=bool(ctx.nd.affine_only)))
-        return dx, _ret(dw, sw), _ret(dgamma, sg), _ret(dbeta, sb), None, None, None, None, None
+        return dx, _ret(dw, sw), _ret(dgamma, sg), _ret(dbeta, sb), None, None, None, None, None, None
 
 
 class Deconv3dConcat(_Op):
@@ -1656,15 +1716,18 @@ class Deconv3dConcat(_Op):
     `skip` already lives in cat[..., :C], the kernel fills cat[..., C:]."""
 
     @staticmethod
-    def forward(ctx, x, w, skip, cat):
+    def forward(ctx, x, w, skip, cat, precision=0):
+        """precision: UNETK_FP32, or UNETK_BF16 (bf16 matrix-core operands; Cin % 32 == 0 and Cout % 32 == 0, else fp32)."""
         _require_cuda(x, w, cat)
         kd, cout = w.shape[0], w.shape[3]
+        cin = w.shape[4]
         coff = cat.shape[-1] - cout
         assert skip.data_ptr() == cat.data_ptr() and skip.shape[-1] == coff
-        wp_f, wp_d = deconv3d_pack(w)
-        deconv3d_fwd(x, wp_f, None, cat, coff, cout, kd)
+        prec = _abi.BF16 if int(precision or 0) == _abi.BF16 and cin % 32 == 0 and cout % 32 == 0 else _abi.FP32
+        wp_f, wp_d = deconv3d_pack(w, precision=prec)
+        deconv3d_fwd(x, wp_f, None, cat, coff, cout, kd, precision=prec)
         ctx.save_for_backward(x, cat)
-        ctx.wp_d, ctx.cout, ctx.coff, ctx.kd = wp_d, cout, coff, kd
+        ctx.wp_d, ctx.cout, ctx.coff, ctx.kd, ctx.prec = wp_d, cout, coff, kd, prec
         ctx.sink = grad_sink(w, ctx)
         ctx.w_dbg = w.detach() if DEBUG_CAPTURE is not None else None
         return alias(cat)
@@ -1674,11 +1737,12 @@ class Deconv3dConcat(_Op):
         x, cat = ctx.saved_tensors
         dcat = dcat.contiguous()
         sw = None if DEBUG_CAPTURE is not None else _take(ctx.sink)
-        dx, dw, _ = deconv3d_bwd(x, ctx.wp_d, cat, dcat, ctx.coff, ctx.cout, ctx.kd, want_dbias=False, out_w=sw)
+        dx, dw, _ = deconv3d_bwd(x, ctx.wp_d, cat, dcat, ctx.coff, ctx.cout, ctx.kd, want_dbias=False, out_w=sw,
+                                 precision=ctx.prec)
         if DEBUG_CAPTURE is not None:
             DEBUG_CAPTURE.append(dict(kind="deconv3d", x=x, w=ctx.w_dbg, cat=cat.clone(), dcat=dcat, dx=dx, dw=dw,
                                       coff=ctx.coff, kd=ctx.kd))
-        return dx, _ret(dw, sw), dcat[..., :ctx.coff], None
+        return dx, _ret(dw, sw), dcat[..., :ctx.coff], None, None
 
 
 class MaxPool2x2(_Op):

@@ -65,7 +65,9 @@ typedef struct unetk_conv_desc {
  * UNETK_BF16 (BASELINE.json configs[2], "bf16"): both operands rounded to bf16 (RNE) on their way into the
  * matrix cores (v_mfma_f32_32x32x16_bf16), fp32 accumulation, fp32 tensors in memory, fp32 statistics, master
  * weights and optimiser.  Needs Cin % 32 == 0 and Cout % 32 == 0 (else UNETK_E_UNSUPPORTED: use UNETK_FP32 for
- * that layer) and filters packed by unetk_conv3x3_pack_bf16. */
+ * that layer) and filters packed by unetk_conv3x3_pack_bf16.  The 3-D convs have the same contract through the
+ * unetk_conv3d_*_bf16 entry points; their layer rule (stride 1, Cin % 32 == 0, Cout % 32 == 0, kd in {1, 3}) is
+ * stated with them below. */
 #define UNETK_FP32 0
 #define UNETK_BF16 1
 /* UNETK_BF16S = UNETK_BF16 arithmetic + bf16 STORAGE of activations and activation gradients (BASELINE.json
@@ -205,6 +207,28 @@ int unetk_conv3d_dgrad(const unetk_conv3d_desc* d, const float* dy, const float*
                        void* ws, size_t ws_bytes, void* stream);
 int unetk_conv3d_wgrad(const unetk_conv3d_desc* d, const float* x, const float* dy, float* dw,
                        void* ws, size_t ws_bytes, void* stream);
+
+/* UNETK_BF16 for the 3-D convs (UNet3D --compute_dtype bf16c): the arithmetic contract of UNETK_BF16 above -- both operands
+ * of every contraction rounded to bf16 (RNE) on their way into the matrix cores, fp32 accumulation, every tensor in memory
+ * fp32, statistics, master weights, weight gradients and the optimiser fp32.  The entry points below imply it.
+ * Layer rule (fixed): a conv runs on the bf16 pipe when it has stride 1 in all three axes, Cin % 32 == 0 and Cout % 32 == 0
+ * (padded channels: 30 -> 32 qualifies) and kd in {1, 3}.  Every other descriptor gets UNETK_E_UNSUPPORTED and keeps the
+ * exact fp32 entry points: in UNet3D the first conv (Cin = 1) and the four strided convs (about 11 % of the FLOPs).
+ * Forward and input gradient contract K = kd x 9 x Cin (resp. Cout) in ONE launch, the depth taps fused; the filter gradient
+ * is ONE launch over all kd taps with a fixed split and a fixed-order slab reduction (bit-reproducible, no atomics).
+ * Filters: kd per-depth-tap bf16 K8 packs, each the layout of unetk_conv3x3_pack_bf16 (perm 0); the cin_live8 / cout_live8
+ * promise is accepted and not needed (the padded rows are zero in the packs and contract to exactly 0).
+ * ws / ws_bytes: at least unetk_conv3d_ws_bytes_bf16 bytes, 16-byte aligned, for all three calls: a NULL or misaligned ws
+ * is UNETK_E_BADARG, a short one UNETK_E_WORKSPACE. */
+int unetk_conv3d_pack_bf16(const float* w, int kd, int Cin, int Cout, void* wp_fwd, void* wp_dgrad, void* stream);
+int unetk_conv3d_stat_rows_bf16(const unetk_conv3d_desc* d);
+size_t unetk_conv3d_ws_bytes_bf16(const unetk_conv3d_desc* d);   /* 0 outside the rule */
+int unetk_conv3d_fwd_bf16(const unetk_conv3d_desc* d, const float* x, const void* wp_fwd, float* y,
+                          float* stat_partials, void* ws, size_t ws_bytes, void* stream);
+int unetk_conv3d_dgrad_bf16(const unetk_conv3d_desc* d, const float* dy, const void* wp_dgrad, float* dx,
+                            void* ws, size_t ws_bytes, void* stream);
+int unetk_conv3d_wgrad_bf16(const unetk_conv3d_desc* d, const float* x, const float* dy, float* dw,
+                            void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------- normalisation + ReLU after each 3x3 conv
  * slim.batch_norm   NetworksV2/base.py:153-162 -- TF defaults eps 1e-3, decay .999 (GUNet encoder .99,
