@@ -60,6 +60,28 @@ bool desc_ok(const unetk_conv3d_desc* d) {
          !(d->kd == 1 && d->sd != 1) && d->x_stride >= d->Cin && d->y_stride >= d->Cout;
 }
 
+// zero the C channels of npix pixels at pixel stride `stride`: an output that is a channel slice of a concat buffer must leave
+// the channels beside it alone (a dense output is one memset)
+__global__ __launch_bounds__(256) void zero_slice_kernel(float* __restrict__ p, int64_t npix, int C, int stride) {
+  const int64_t total = npix * C;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t px = i / C;
+    p[px * stride + (i - px * C)] = 0.f;
+  }
+}
+
+int zero_pixels(float* p, int64_t npix, int C, int stride, hipStream_t st) {
+  if (stride == C) {
+    const hipError_t e = hipMemsetAsync(p, 0, (size_t)npix * C * sizeof(float), st);
+    return e == hipSuccess ? UNETK_OK : (int)e;
+  }
+  int64_t grid = (npix * C + 255) / 256;
+  if (grid > 8192) grid = 8192;
+  UNETK_LAUNCH(zero_slice_kernel, dim3((int)grid), dim3(256), 0, st, p, npix, C, stride);
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
 // y[n, do, ho, wo, :] = t[n, do, 2ho+off_h, 2wo+off_w, :]; statistic partials per block, blocks grouped per sample
 __global__ __launch_bounds__(256) void subsample2_stats_kernel(const float* __restrict__ t, float* __restrict__ y,
                                                                float* __restrict__ stat, int planes_per_sample, int H,
@@ -268,9 +290,13 @@ extern "C" int unetk_conv3d_fwd(const unetk_conv3d_desc* d, const float* x, cons
     if (ws && unetk_aligned16(ws)) { p.sk_slab = (float*)ws; p.sk_slab_bytes = ws_bytes; }
     return unetk_conv_run(p, st);
   }
-  if (s2lin_ok(d, g) && ws && unetk_aligned16(ws) && ws_bytes >= unetk_conv3d_ws_bytes(d)) {
+  if (s2lin_ok(d, g)) {
     // small OUTPUT planes (UNet3D's 24^2 / 12^2 / 6^2 levels behind a stride-2 layer): space-to-depth copy of x, then ONE
-    // launch of the linear-pixel kernel over kd x 4 tap groups (K = kd x 9 x Cin, every MFMA row an output pixel, stream-K)
+    // launch of the linear-pixel kernel over kd x 4 tap groups (K = kd x 9 x Cin, every MFMA row an output pixel, stream-K).
+    // The copy lives in ws, and unetk_conv3d_stat_rows counts this kernel's rows: no silent fall-back to the tiled kernel
+    // (it writes more rows) when ws is missing or short
+    UNETK_REQUIRE(ws && unetk_aligned16(ws) && d->x_stride % 4 == 0);
+    if (ws_bytes < unetk_conv3d_ws_bytes(d)) return UNETK_E_WORKSPACE;
     float* XS = (float*)ws;
     const int ncls = d->sd == 2 ? 8 : 4;
     const int64_t npix_out = (int64_t)d->N * g.Do * g.Ho * g.Wo;
@@ -336,8 +362,8 @@ extern "C" int unetk_conv3d_fwd(const unetk_conv3d_desc* d, const float* x, cons
     if (dt != full) order[n_taps++] = dt;
   order[n_taps++] = full;
   if (d->kd > 1) {
-    hipError_t e = hipMemsetAsync(T, 0, (size_t)d->N * g.Do * HWt * sizeof(float), st);
-    if (e != hipSuccess) return (int)e;
+    const int zr = zero_pixels(T, (int64_t)d->N * g.Do * (HWt / ts), d->Cout, ts, st);
+    if (zr != UNETK_OK) return zr;
   }
   for (int i = 0; i < n_taps; ++i) {
     const int dt = order[i];
@@ -449,8 +475,8 @@ extern "C" int unetk_conv3d_dgrad(const unetk_conv3d_desc* d, const float* dy, c
     }
     const bool multi = !fuse_d && (d->kd > 1 || d->sd > 1);
     if (multi) {
-      hipError_t e = hipMemsetAsync(dx, 0, (size_t)d->N * d->D * HWx * sizeof(float), st);
-      if (e != hipSuccess) return (int)e;
+      const int zr = zero_pixels(dx, (int64_t)d->N * d->D * d->H * d->W, d->Cin, d->x_stride, st);
+      if (zr != UNETK_OK) return zr;
     }
     for (int dt = 0; dt < (fuse_d ? 1 : d->kd); ++dt) {
       int lo, hi;
@@ -512,8 +538,8 @@ extern "C" int unetk_conv3d_dgrad(const unetk_conv3d_desc* d, const float* dy, c
   const int HWx = d->H * d->W * d->x_stride, HWz = d->H * d->W * zs;
   const bool multi = d->kd > 1 || d->sd > 1;
   if (multi) {
-    hipError_t e = hipMemsetAsync(dx, 0, (size_t)d->N * d->D * HWx * sizeof(float), st);
-    if (e != hipSuccess) return (int)e;
+    const int zr = zero_pixels(dx, (int64_t)d->N * d->D * d->H * d->W, d->Cin, d->x_stride, st);
+    if (zr != UNETK_OK) return zr;
   }
   for (int dt = 0; dt < d->kd; ++dt) {
     int lo, hi;

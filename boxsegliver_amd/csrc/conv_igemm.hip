@@ -29,7 +29,7 @@
 
 namespace {
 
-__device__ float kZeroF4[4] = {};        // NOT const: a const array lives in the constant address space and selecting between it and a global pointer makes the load a FLAT load (lgkmcnt: every LDS read then waits for it)      // what an out-of-image halo pixel reads (see load_halo)
+__device__ __attribute__((aligned(16))) float kZeroF4[4] = {};        // NOT const: a const array lives in the constant address space and selecting between it and a global pointer makes the load a FLAT load (lgkmcnt: every LDS read then waits for it)      // what an out-of-image halo pixel reads (see load_halo)
 
 constexpr int CK = 16;   // input channels per K-chunk
 // tap steps at which the next chunk's halo is requested from HBM / written to LDS (registers in between)

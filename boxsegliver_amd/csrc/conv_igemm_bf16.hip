@@ -45,7 +45,7 @@ constexpr int CKB = 32;  // input channels per K-chunk
 constexpr int PSQ = 5;   // LDS pixel stride in 16-B units: 64 B of bf16 + 16 B pad -> conflict-free ds_read_b128
 constexpr int TW = 16;
 constexpr int HWD = TW + 2;
-__device__ float kZeroF8[8] = {};   // what an out-of-image halo pixel of the FT kernels reads (NOT const: see conv_igemm.hip kZeroF4)
+__device__ __attribute__((aligned(16))) float kZeroF8[8] = {};   // what an out-of-image halo pixel of the FT kernels reads (NOT const: see conv_igemm.hip kZeroF4)
 
 __device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {
   uint32_t r;

@@ -19,7 +19,7 @@
 
 namespace {
 
-__device__ float kZeroF4[4] = {};        // NOT const: a const array lives in the constant address space and selecting between it and a global pointer makes the load a FLAT load (lgkmcnt: every LDS read then waits for it)      // what a pad pixel of the halo reads
+__device__ __attribute__((aligned(16))) float kZeroF4[4] = {};        // NOT const: a const array lives in the constant address space and selecting between it and a global pointer makes the load a FLAT load (lgkmcnt: every LDS read then waits for it)      // what a pad pixel of the halo reads
 
 constexpr int CK = 16;
 constexpr int PS = 20;

@@ -15,7 +15,7 @@
 
 namespace {
 
-__device__ float kZeroF4[4] = {};        // what a row past M reads in the bf16c pw_gemm (NOT const: see conv_igemm.hip)
+__device__ __attribute__((aligned(16))) float kZeroF4[4] = {};        // what a row past M reads in the bf16c pw_gemm (NOT const: see conv_igemm.hip)
 
 constexpr int CK = 16, PS = 20;
 

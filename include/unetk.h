@@ -199,8 +199,12 @@ typedef struct unetk_conv3d_desc {
 int unetk_conv3d_pack(const float* w, int kd, int Cin, int Cout, float* wp_fwd, float* wp_dgrad,
                       void* stream);
 int unetk_conv3d_out_dims(const unetk_conv3d_desc* d, int* Do, int* Ho, int* Wo);
-int unetk_conv3d_stat_rows(const unetk_conv3d_desc* d);      /* rows of the statistic partials */
+int unetk_conv3d_stat_rows(const unetk_conv3d_desc* d);      /* rows of the statistic partials the forward writes */
 size_t unetk_conv3d_ws_bytes(const unetk_conv3d_desc* d);    /* one size serves fwd / dgrad / wgrad */
+/* Forward workspace: an H/W-strided conv (shw == 2) takes ws of at least unetk_conv3d_ws_bytes bytes, 16-byte aligned, and on
+ * every path that uses it (stride-1 conv + subsample; space-to-depth copy for small output planes) a NULL or misaligned ws is
+ * UNETK_E_BADARG and a short one UNETK_E_WORKSPACE -- the forward never falls back to a kernel that writes another number of
+ * statistic rows than unetk_conv3d_stat_rows.  The space-to-depth path also needs x_stride % 4 == 0.  Stride 1 accepts ws = NULL. */
 int unetk_conv3d_fwd(const unetk_conv3d_desc* d, const float* x, const float* wp_fwd, float* y,
                      float* stat_partials, void* ws, size_t ws_bytes, void* stream);
 int unetk_conv3d_dgrad(const unetk_conv3d_desc* d, const float* dy, const float* wp_dgrad, float* dx,
