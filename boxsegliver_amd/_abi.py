@@ -6,7 +6,7 @@ op in boxsegliver_amd.ops goes through this module.
 """
 import ctypes
 import os
-from ctypes import (POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t,
+from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t,
                     c_void_p)
 
 _LIB = None
@@ -155,6 +155,16 @@ _SIGNATURES = {
     "unetk_sumsq": (c_int, [P, c_int64, P, P, c_size_t, P]),
     "unetk_boundary_weights_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "unetk_boundary_weights": (c_int, [P, c_int, c_int, c_int, P, P, c_size_t, P]),
+    "unetk_largest_component_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "unetk_largest_component": (c_int, [P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
+    "unetk_component_mask": (c_int, [P, c_int, c_int, c_int, c_int32, P, P]),
+    "unetk_mask_counts_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "unetk_mask_counts": (c_int, [P, P, c_int, c_int, c_int, P, P, c_size_t, P]),
+    "unetk_surface3d": (c_int, [P, c_int, c_int, c_int, P, P, c_int, P]),
+    "unetk_edt3d_sq_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "unetk_edt3d_sq": (c_int, [P, c_int, c_int, c_int, P, c_double, c_double, c_double, P, P, c_size_t, P]),
+    "unetk_surface_dist_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "unetk_surface_dist": (c_int, [P, P, c_int, c_int, c_int, P, P, c_size_t, P]),
 }
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))

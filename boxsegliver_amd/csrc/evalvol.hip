@@ -1,0 +1,510 @@
+// Volume evaluation on the device (evaluators/evaluator_liver.py _postprocess / _run_actual, loss_metrics.metric_3d):
+// largest 6-connected component, the confusion counts, the 18-neighbourhood surface, the exact squared Euclidean distance
+// transform and the surface-distance sums.  Masks are dense C-order uint8 [D,H,W], non-zero = object; D*H*W < 2^31, so a
+// linear voxel index fits an int32.  Every reduction runs in a fixed order: results are bit-reproducible run to run.
+#include "common.h"
+
+namespace {
+
+constexpr int EV_BLOCK = 256;
+constexpr int EV_MAX_BLOCKS = 1024;          // fixed-grid reductions: partial rows per call (a function of the size only)
+
+static inline int ev_blocks(int64_t n) { return (int)min((int64_t)EV_MAX_BLOCKS, max((int64_t)1, (n + EV_BLOCK * 8 - 1) / (EV_BLOCK * 8))); }
+static inline int ev_grid1(int64_t n) { return (int)((n + EV_BLOCK - 1) / EV_BLOCK); }
+
+static inline int ev_dims(int D, int H, int W) {
+  if (D <= 0 || H <= 0 || W <= 0) return UNETK_E_BADARG;
+  if ((int64_t)D * H * W >= ((int64_t)1 << 31)) return UNETK_E_UNSUPPORTED;
+  return UNETK_OK;
+}
+static inline size_t ev_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// Labels only ever decrease and every value a voxel has held names a member of its own set, so a stale read (an older
+// parent, or a "root" that has since been linked) is still an ancestor: the union below stays correct and terminates, and
+// the reads may come from the CU's own cache (workgroup scope) instead of all hitting the one L2 line of a big root.
+__device__ __forceinline__ int ld_label(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+
+// ---------------------------------------------------------------- largest 6-connected component (union-find)
+// label[i] = -1 (background) or a voxel index <= i of the same component; roots have label[i] == i.  A union links the
+// larger root under the smaller one with atomicMin (Playne & Hawick's lock-free union), so each tree's root is the minimum
+// linear index of its component whatever order the atomics run in.
+__global__ __launch_bounds__(EV_BLOCK) void lc_init_kernel(const uint8_t* __restrict__ mask, int n, int* __restrict__ label,
+                                                           int* __restrict__ cnt, unsigned long long* __restrict__ best,
+                                                           int32_t* __restrict__ info) {
+  const int i = blockIdx.x * EV_BLOCK + threadIdx.x;
+  if (i == 0) *best = 0ull;
+  if (i < 4) info[i] = 0;
+  if (i >= n) return;
+  label[i] = mask[i] ? i : -1;
+  cnt[i] = 0;
+}
+
+__device__ __forceinline__ int lc_find(const int* label, int p) {
+  int q = ld_label(label + p);
+  while (q != p) {
+    p = q;
+    q = ld_label(label + p);
+  }
+  return p;
+}
+
+__device__ __forceinline__ void lc_union(int* label, int a, int b) {
+  for (;;) {
+    a = lc_find(label, a);
+    b = lc_find(label, b);
+    if (a == b) return;
+    if (a < b) {
+      const int old = atomicMin(label + b, a);
+      if (old == b) return;
+      b = old;
+    } else {
+      const int old = atomicMin(label + a, b);
+      if (old == a) return;
+      a = old;
+    }
+  }
+}
+
+__global__ __launch_bounds__(EV_BLOCK) void lc_merge_kernel(const uint8_t* __restrict__ mask, int D, int H, int W,
+                                                            int* __restrict__ label) {
+  const int n = D * H * W;
+  const int i = blockIdx.x * EV_BLOCK + threadIdx.x;
+  if (i >= n || !mask[i]) return;
+  const int x = i % W, y = (i / W) % H, z = i / (H * W);
+  if (x > 0 && mask[i - 1]) lc_union(label, i, i - 1);
+  if (y > 0 && mask[i - W]) lc_union(label, i, i - W);
+  if (z > 0 && mask[i - H * W]) lc_union(label, i, i - H * W);
+}
+
+// every voxel points straight at its root; component sizes by integer atomics at the root's slot, one per wave for the
+// lanes that share the wave's first root (the big component would otherwise take one atomic per voxel on one address)
+__global__ __launch_bounds__(EV_BLOCK) void lc_flatten_kernel(int n, int* __restrict__ label, int* __restrict__ cnt) {
+  const int i = blockIdx.x * EV_BLOCK + threadIdx.x;
+  int r = -1;
+  if (i < n) {
+    const int l = label[i];
+    if (l >= 0) {
+      r = lc_find(label, l);
+      label[i] = r;
+    }
+  }
+  const int lead = __builtin_amdgcn_readfirstlane(r >= 0 ? r : 0x7fffffff);
+  const unsigned long long same = __ballot(r == lead);
+  if (r < 0) return;
+  if (r != lead)
+    atomicAdd(cnt + r, 1);
+  else if ((int)__lane_id() == __ffsll((long long)same) - 1)
+    atomicAdd(cnt + r, __popcll(same));
+}
+
+// best = max over roots of (size << 32 | root): the largest component, the larger root (= scipy's larger label id) on ties
+__global__ __launch_bounds__(EV_BLOCK) void lc_pick_kernel(int n, const int* __restrict__ label, const int* __restrict__ cnt,
+                                                           unsigned long long* __restrict__ best) {
+  __shared__ unsigned long long red[EV_BLOCK / 64];
+  const int i = blockIdx.x * EV_BLOCK + threadIdx.x;
+  unsigned long long key = 0ull;
+  if (i < n && label[i] == i) key = ((unsigned long long)(unsigned)cnt[i] << 32) | (unsigned)i;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long other = __shfl_xor(key, o);
+    key = other > key ? other : key;
+  }
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = key;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long m = red[0];
+#pragma unroll
+    for (int j = 1; j < EV_BLOCK / 64; ++j) m = red[j] > m ? red[j] : m;
+    if (m) atomicMax(best, m);
+  }
+}
+
+// info[2] = number of components of the largest size, info[3] = number of components (wave-aggregated integer atomics)
+__global__ __launch_bounds__(EV_BLOCK) void lc_ties_kernel(int n, const int* __restrict__ label, const int* __restrict__ cnt,
+                                                           const unsigned long long* __restrict__ best,
+                                                           int32_t* __restrict__ info) {
+  const int i = blockIdx.x * EV_BLOCK + threadIdx.x;
+  const int top = (int)(*best >> 32);
+  const bool root = i < n && label[i] == i;
+  const unsigned long long roots = __ballot(root), ties = __ballot(root && cnt[i] == top);
+  if ((threadIdx.x & 63) == 0) {
+    if (roots) atomicAdd(info + 3, __popcll(roots));
+    if (ties) atomicAdd(info + 2, __popcll(ties));
+  }
+}
+
+// out = (label == root); root < 0 = the packed best's root (none for an empty mask); info[0..1] = {root, size}
+__global__ __launch_bounds__(EV_BLOCK) void lc_write_kernel(int n, const int* __restrict__ label, const int* __restrict__ cnt,
+                                                            const unsigned long long* __restrict__ best, int root,
+                                                            uint8_t* __restrict__ out, int32_t* __restrict__ info) {
+  const int i = blockIdx.x * EV_BLOCK + threadIdx.x;
+  if (root < 0) {
+    const unsigned long long b = *best;
+    root = b != 0ull ? (int)(unsigned)(b & 0xffffffffull) : -2;
+  }
+  if (i == 0 && info) {
+    info[0] = root >= 0 ? root : -1;
+    info[1] = root >= 0 ? cnt[root] : 0;
+  }
+  if (i >= n) return;
+  out[i] = label[i] == root ? 1 : 0;
+}
+
+// ---------------------------------------------------------------- counts |A|, |B|, |A and B|, |A or B|
+__global__ __launch_bounds__(EV_BLOCK) void counts_partial_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
+                                                                  int n, long long* __restrict__ part) {
+  __shared__ long long red[4][EV_BLOCK];
+  int ca = 0, cb = 0, ci = 0, cu = 0;
+  for (int i = blockIdx.x * EV_BLOCK + threadIdx.x; i < n; i += gridDim.x * EV_BLOCK) {
+    const int va = a[i] != 0, vb = b[i] != 0;
+    ca += va; cb += vb; ci += va & vb; cu += va | vb;
+  }
+  red[0][threadIdx.x] = ca; red[1][threadIdx.x] = cb; red[2][threadIdx.x] = ci; red[3][threadIdx.x] = cu;
+  __syncthreads();
+  for (int s = EV_BLOCK / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x < 4) part[(int64_t)blockIdx.x * 4 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+__global__ __launch_bounds__(EV_BLOCK) void counts_final_kernel(const long long* __restrict__ part, int rows,
+                                                                long long* __restrict__ out) {
+  __shared__ long long red[4][EV_BLOCK];
+  long long s[4] = {0, 0, 0, 0};
+  for (int r = threadIdx.x; r < rows; r += EV_BLOCK)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[k] += part[(int64_t)r * 4 + k];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) red[k][threadIdx.x] = s[k];
+  __syncthreads();
+  for (int h = EV_BLOCK / 2; h > 0; h >>= 1) {
+    if (threadIdx.x < h)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x < 4) out[threadIdx.x] = red[threadIdx.x][0];
+}
+
+// ---------------------------------------------------------------- surface  A xor erode(A, 18-neighbourhood)
+// box: {z0, y0, x0, z1, y1, x1}, half-open; atomicMin / atomicMax of per-block extents (order-free)
+__global__ void box_init_kernel(int32_t* __restrict__ box) {
+  if (threadIdx.x < 3) box[threadIdx.x] = 0x7fffffff;
+  else if (threadIdx.x < 6) box[threadIdx.x] = 0;
+}
+
+__global__ __launch_bounds__(EV_BLOCK) void surface_kernel(const uint8_t* __restrict__ mask, int D, int H, int W,
+                                                           uint8_t* __restrict__ edge, int32_t* __restrict__ box) {
+  __shared__ int red[6][EV_BLOCK];
+  const int n = D * H * W, HW = H * W;
+  int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {0, 0, 0};
+  for (int i = blockIdx.x * EV_BLOCK + threadIdx.x; i < n; i += gridDim.x * EV_BLOCK) {
+    uint8_t e = 0;
+    if (mask[i]) {
+      const int x = i % W, y = (i / W) % H, z = i / HW;
+      bool inner = x > 0 && x < W - 1 && y > 0 && y < H - 1 && z > 0 && z < D - 1;   // the border counts as background
+      if (inner) {
+        // 6 faces + 12 edges (generate_binary_structure(3, 2) without the centre)
+#pragma unroll
+        for (int dz = -1; dz <= 1; ++dz)
+#pragma unroll
+          for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+              const int m = (dz != 0) + (dy != 0) + (dx != 0);
+              if (m == 1 || m == 2) inner = inner && mask[i + dz * HW + dy * W + dx] != 0;
+            }
+      }
+      if (!inner) {
+        e = 1;
+        lo[0] = min(lo[0], z); lo[1] = min(lo[1], y); lo[2] = min(lo[2], x);
+        hi[0] = max(hi[0], z + 1); hi[1] = max(hi[1], y + 1); hi[2] = max(hi[2], x + 1);
+      }
+    }
+    edge[i] = e;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { red[k][threadIdx.x] = lo[k]; red[3 + k][threadIdx.x] = hi[k]; }
+  __syncthreads();
+  for (int s = EV_BLOCK / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        red[k][threadIdx.x] = min(red[k][threadIdx.x], red[k][threadIdx.x + s]);
+        red[3 + k][threadIdx.x] = max(red[3 + k][threadIdx.x], red[3 + k][threadIdx.x + s]);
+      }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && red[3][0] > 0) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { atomicMin(box + k, red[k][0]); atomicMax(box + 3 + k, red[3 + k][0]); }
+  }
+}
+
+// ---------------------------------------------------------------- exact squared EDT, one 1-D pass per launch
+// One line per thread: f_out(q) = min_p f_in(p) + ((q - p) s)^2 over the line's part inside the box, by the lower envelope
+// of parabolas (Felzenszwalb & Huttenlocher 2012).  Sites with f_in = +inf are left out; a line without a site is +inf.
+// AXIS 2 (x) reads the feature mask (feature -> 0, else +inf), AXIS 1 / 0 the previous pass.  The envelope's site and
+// boundary stacks live in the workspace at [k * nlines + line], so neighbouring threads touch neighbouring words.
+template <int AXIS>
+__global__ __launch_bounds__(EV_BLOCK) void edt_pass_kernel(const uint8_t* __restrict__ feat, const double* __restrict__ fin,
+                                                            double* __restrict__ fout, int D, int H, int W,
+                                                            const int32_t* __restrict__ box, double s,
+                                                            int* __restrict__ vst, double* __restrict__ zst) {
+  const int L = blockIdx.x * EV_BLOCK + threadIdx.x;
+  const int nlines = AXIS == 2 ? D * H : (AXIS == 1 ? D * W : H * W);
+  if (L >= nlines) return;
+  const int z0 = max(box[0], 0), y0 = max(box[1], 0), x0 = max(box[2], 0);          // clamped: a box past the volume
+  const int z1 = min(box[3], D), y1 = min(box[4], H), x1 = min(box[5], W);           // only shrinks to it
+  int base, stride, lo, hi;
+  if (AXIS == 2) {
+    const int z = L / H, y = L % H;
+    if (z < z0 || z >= z1 || y < y0 || y >= y1) return;
+    base = (z * H + y) * W; stride = 1; lo = x0; hi = x1;
+  } else if (AXIS == 1) {
+    const int z = L / W, x = L % W;
+    if (z < z0 || z >= z1 || x < x0 || x >= x1) return;
+    base = z * H * W + x; stride = W; lo = y0; hi = y1;
+  } else {
+    const int y = L / W, x = L % W;
+    if (y < y0 || y >= y1 || x < x0 || x >= x1) return;
+    base = L; stride = H * W; lo = z0; hi = z1;
+  }
+  const double INF = __builtin_huge_val();
+  const double ss2 = 2.0 * s * s;
+  int k = -1;
+  for (int q = lo; q < hi; ++q) {
+    const int iq = base + q * stride;
+    const double fq = AXIS == 2 ? (feat[iq] ? 0.0 : INF) : fin[iq];
+    if (fq == INF) continue;
+    const double cq = (double)(q - lo) * s;
+    double zq = -INF;
+    while (k >= 0) {
+      const int p = vst[(int64_t)k * nlines + L];
+      const double fp = AXIS == 2 ? 0.0 : fin[base + p * stride];
+      const double cp = (double)(p - lo) * s;
+      const double sx = ((fq + cq * cq) - (fp + cp * cp)) / (ss2 * (double)(q - p));   // intersection, in index units - lo
+      if (sx <= zst[(int64_t)k * nlines + L]) {
+        --k;
+      } else {
+        zq = sx;
+        break;
+      }
+    }
+    ++k;
+    vst[(int64_t)k * nlines + L] = q;
+    zst[(int64_t)k * nlines + L] = zq;
+  }
+  if (k < 0) {
+    for (int q = lo; q < hi; ++q) fout[base + q * stride] = INF;
+    return;
+  }
+  const int kmax = k;
+  k = 0;
+  int p = vst[L];
+  double fp = AXIS == 2 ? 0.0 : fin[base + p * stride];
+  for (int q = lo; q < hi; ++q) {
+    while (k < kmax && zst[(int64_t)(k + 1) * nlines + L] < (double)(q - lo)) {
+      ++k;
+      p = vst[(int64_t)k * nlines + L];
+      fp = AXIS == 2 ? 0.0 : fin[base + p * stride];
+    }
+    const double d = (double)(q - p) * s;
+    fout[base + q * stride] = d * d + fp;
+  }
+}
+
+// ---------------------------------------------------------------- surface distance sums
+// over the voxels of `surf`: d = sqrt(dist2); sum d, sum d*d, max d, count -- fixed-order per-block partials, one final block
+__global__ __launch_bounds__(EV_BLOCK) void sdist_partial_kernel(const uint8_t* __restrict__ surf, const double* __restrict__ dist2,
+                                                                 int n, double* __restrict__ part) {
+  __shared__ double red[4][EV_BLOCK];
+  double s1 = 0.0, s2 = 0.0, mx = 0.0;
+  int c = 0;
+  for (int i = blockIdx.x * EV_BLOCK + threadIdx.x; i < n; i += gridDim.x * EV_BLOCK) {
+    if (surf[i]) {
+      const double d = sqrt(dist2[i]);
+      s1 += d; s2 += d * d; mx = fmax(mx, d); ++c;
+    }
+  }
+  red[0][threadIdx.x] = s1; red[1][threadIdx.x] = s2; red[2][threadIdx.x] = mx; red[3][threadIdx.x] = (double)c;
+  __syncthreads();
+  for (int h = EV_BLOCK / 2; h > 0; h >>= 1) {
+    if (threadIdx.x < h) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + h];
+      red[1][threadIdx.x] += red[1][threadIdx.x + h];
+      red[2][threadIdx.x] = fmax(red[2][threadIdx.x], red[2][threadIdx.x + h]);
+      red[3][threadIdx.x] += red[3][threadIdx.x + h];                 // integers < 2^31: exact in fp64
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 4) part[(int64_t)blockIdx.x * 4 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+__global__ __launch_bounds__(EV_BLOCK) void sdist_final_kernel(const double* __restrict__ part, int rows, double* __restrict__ out) {
+  __shared__ double red[4][EV_BLOCK];
+  double s1 = 0.0, s2 = 0.0, mx = 0.0, c = 0.0;
+  for (int r = threadIdx.x; r < rows; r += EV_BLOCK) {
+    s1 += part[(int64_t)r * 4 + 0];
+    s2 += part[(int64_t)r * 4 + 1];
+    mx = fmax(mx, part[(int64_t)r * 4 + 2]);
+    c += part[(int64_t)r * 4 + 3];
+  }
+  red[0][threadIdx.x] = s1; red[1][threadIdx.x] = s2; red[2][threadIdx.x] = mx; red[3][threadIdx.x] = c;
+  __syncthreads();
+  for (int h = EV_BLOCK / 2; h > 0; h >>= 1) {
+    if (threadIdx.x < h) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + h];
+      red[1][threadIdx.x] += red[1][threadIdx.x + h];
+      red[2][threadIdx.x] = fmax(red[2][threadIdx.x], red[2][threadIdx.x + h]);
+      red[3][threadIdx.x] += red[3][threadIdx.x + h];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    out[0] = red[0][0];
+    out[1] = red[1][0];
+    out[2] = red[2][0];
+    reinterpret_cast<long long*>(out)[3] = (long long)red[3][0];
+  }
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------- C ABI
+extern "C" size_t unetk_largest_component_ws_bytes(int D, int H, int W) {
+  if (ev_dims(D, H, W) != UNETK_OK) return 0;
+  return 2 * ev_align((size_t)D * H * W * 4) + 256;
+}
+
+extern "C" int unetk_largest_component(const uint8_t* mask, int D, int H, int W, uint8_t* out, int32_t* info, void* ws,
+                                       size_t ws_bytes, void* stream) {
+  const int dims = ev_dims(D, H, W);
+  if (dims != UNETK_OK) return dims;
+  UNETK_REQUIRE(mask && out && info && ws && unetk_aligned16(ws) && (((uintptr_t)info) & 3u) == 0);
+  if (ws_bytes < unetk_largest_component_ws_bytes(D, H, W)) return UNETK_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int n = D * H * W;
+  int* label = (int*)ws;
+  int* cnt = (int*)((char*)ws + ev_align((size_t)n * 4));
+  unsigned long long* best = (unsigned long long*)((char*)ws + 2 * ev_align((size_t)n * 4));
+  const int g = ev_grid1(n);
+  UNETK_LAUNCH(lc_init_kernel, dim3(g), dim3(EV_BLOCK), 0, st, mask, n, label, cnt, best, info);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(lc_merge_kernel, dim3(g), dim3(EV_BLOCK), 0, st, mask, D, H, W, label);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(lc_flatten_kernel, dim3(g), dim3(EV_BLOCK), 0, st, n, label, cnt);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(lc_pick_kernel, dim3(g), dim3(EV_BLOCK), 0, st, n, (const int*)label, (const int*)cnt, best);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(lc_ties_kernel, dim3(g), dim3(EV_BLOCK), 0, st, n, (const int*)label, (const int*)cnt,
+               (const unsigned long long*)best, info);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(lc_write_kernel, dim3(g), dim3(EV_BLOCK), 0, st, n, (const int*)label, (const int*)cnt,
+               (const unsigned long long*)best, -1, out, info);
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
+extern "C" int unetk_component_mask(const void* ws, int D, int H, int W, int32_t root, uint8_t* out, void* stream) {
+  const int dims = ev_dims(D, H, W);
+  if (dims != UNETK_OK) return dims;
+  UNETK_REQUIRE(ws && out && unetk_aligned16(ws) && root >= 0 && (int64_t)root < (int64_t)D * H * W);
+  hipStream_t st = (hipStream_t)stream;
+  const int n = D * H * W;
+  const int* label = (const int*)ws;
+  const int* cnt = (const int*)((const char*)ws + ev_align((size_t)n * 4));
+  UNETK_LAUNCH(lc_write_kernel, dim3(ev_grid1(n)), dim3(EV_BLOCK), 0, st, n, label, cnt, (const unsigned long long*)nullptr, root,
+               out, (int32_t*)nullptr);
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
+extern "C" size_t unetk_mask_counts_ws_bytes(int D, int H, int W) {
+  if (ev_dims(D, H, W) != UNETK_OK) return 0;
+  return (size_t)ev_blocks((int64_t)D * H * W) * 4 * 8;
+}
+
+extern "C" int unetk_mask_counts(const uint8_t* a, const uint8_t* b, int D, int H, int W, int64_t* counts, void* ws,
+                                 size_t ws_bytes, void* stream) {
+  const int dims = ev_dims(D, H, W);
+  if (dims != UNETK_OK) return dims;
+  UNETK_REQUIRE(a && b && counts && ws && unetk_aligned16(ws) && unetk_aligned8(counts));
+  if (ws_bytes < unetk_mask_counts_ws_bytes(D, H, W)) return UNETK_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int n = D * H * W, rows = ev_blocks(n);
+  UNETK_LAUNCH(counts_partial_kernel, dim3(rows), dim3(EV_BLOCK), 0, st, a, b, n, (long long*)ws);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(counts_final_kernel, dim3(1), dim3(EV_BLOCK), 0, st, (const long long*)ws, rows, (long long*)counts);
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
+extern "C" int unetk_surface3d(const uint8_t* mask, int D, int H, int W, uint8_t* edge, int32_t* box, int accumulate_box,
+                               void* stream) {
+  const int dims = ev_dims(D, H, W);
+  if (dims != UNETK_OK) return dims;
+  UNETK_REQUIRE(mask && edge && box && (((uintptr_t)box) & 3u) == 0);
+  hipStream_t st = (hipStream_t)stream;
+  if (!accumulate_box) {
+    UNETK_LAUNCH(box_init_kernel, dim3(1), dim3(64), 0, st, box);
+    UNETK_LAUNCH_CHECK();
+  }
+  const int n = D * H * W;
+  UNETK_LAUNCH(surface_kernel, dim3(ev_blocks(n)), dim3(EV_BLOCK), 0, st, mask, D, H, W, edge, box);
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
+extern "C" size_t unetk_edt3d_sq_ws_bytes(int D, int H, int W) {
+  if (ev_dims(D, H, W) != UNETK_OK) return 0;
+  const size_t n = (size_t)D * H * W;
+  return 2 * ev_align(n * 8) + ev_align(n * 4);
+}
+
+extern "C" int unetk_edt3d_sq(const uint8_t* feature, int D, int H, int W, const int32_t* box, double sz, double sy, double sx,
+                              double* dist2, void* ws, size_t ws_bytes, void* stream) {
+  const int dims = ev_dims(D, H, W);
+  if (dims != UNETK_OK) return dims;
+  UNETK_REQUIRE(feature && box && dist2 && ws && unetk_aligned16(ws) && unetk_aligned8(dist2) && (((uintptr_t)box) & 3u) == 0);
+  UNETK_REQUIRE(sz > 0.0 && sy > 0.0 && sx > 0.0);
+  if (ws_bytes < unetk_edt3d_sq_ws_bytes(D, H, W)) return UNETK_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t n = (size_t)D * H * W;
+  double* tmp = (double*)ws;
+  double* zst = (double*)((char*)ws + ev_align(n * 8));
+  int* vst = (int*)((char*)ws + 2 * ev_align(n * 8));
+  UNETK_LAUNCH(edt_pass_kernel<2>, dim3(ev_grid1((int64_t)D * H)), dim3(EV_BLOCK), 0, st, feature, (const double*)nullptr, dist2,
+               D, H, W, box, sx, vst, zst);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(edt_pass_kernel<1>, dim3(ev_grid1((int64_t)D * W)), dim3(EV_BLOCK), 0, st, feature, (const double*)dist2, tmp,
+               D, H, W, box, sy, vst, zst);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(edt_pass_kernel<0>, dim3(ev_grid1((int64_t)H * W)), dim3(EV_BLOCK), 0, st, feature, (const double*)tmp, dist2,
+               D, H, W, box, sz, vst, zst);
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
+extern "C" size_t unetk_surface_dist_ws_bytes(int D, int H, int W) {
+  if (ev_dims(D, H, W) != UNETK_OK) return 0;
+  return (size_t)ev_blocks((int64_t)D * H * W) * 4 * 8;
+}
+
+extern "C" int unetk_surface_dist(const uint8_t* surf, const double* dist2, int D, int H, int W, double* out, void* ws,
+                                  size_t ws_bytes, void* stream) {
+  const int dims = ev_dims(D, H, W);
+  if (dims != UNETK_OK) return dims;
+  UNETK_REQUIRE(surf && dist2 && out && ws && unetk_aligned16(ws) && unetk_aligned8(out) && unetk_aligned8(dist2));
+  if (ws_bytes < unetk_surface_dist_ws_bytes(D, H, W)) return UNETK_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int n = D * H * W, rows = ev_blocks(n);
+  UNETK_LAUNCH(sdist_partial_kernel, dim3(rows), dim3(EV_BLOCK), 0, st, surf, dist2, n, (double*)ws);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(sdist_final_kernel, dim3(1), dim3(EV_BLOCK), 0, st, (const double*)ws, rows, out);
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}

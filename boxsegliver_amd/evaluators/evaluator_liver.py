@@ -7,8 +7,11 @@ What runs where (MI355X-first):
     `/ mirror_div` accumulation of the class probabilities: `unetk_flip_axpy`; the reference does this with np.flip
     on the host, :648-655), the concatenation of a case's slabs, and the final `np.argmax(volume, -1)` (:663,
     `unetk_head_predict`, lowest index on ties like numpy).  One device->host copy per case (uint8 mask).
-  * HOST, as in the reference: zoom back to the original shape (scipy.ndimage.zoom), merge tumor into liver, largest
-    connected component, the per-case volume metrics (loss_metrics.metric_3d) and the global Dice accumulators.
+  * HOST: zoom back to the original shape (scipy.ndimage.zoom, inside _predict_case).
+  * DEVICE again (metrics_on="device", the default): the case's argmax volume and its labels are uploaded once each,
+    then class split, merge tumor into liver, largest connected component (_postprocess_device), the per-case volume
+    metrics (loss_metrics.metric_3d_device) and the global Dice counts run in csrc/evalvol.hip.  metrics_on="host" keeps
+    the reference's host path (_postprocess, loss_metrics.metric_3d, ConfusionMatrix).
 
 The input contract is the reference's eval generator (DataLoader/Liver/input_pipeline_li.py:398-456): a stream of
 `(features, None)` slabs -- features["images"] [bs,H,W,C], features["names"], optional features["mirror"] in {0,1,2,3}
@@ -57,10 +60,10 @@ def add_arguments(parser):
 
 
 def get_evaluator(evaluator, estimator=None, model_dir=None, params=None, merge_tumor_to_liver=True, largest=True,
-                  use_sg_reduce_fp=False):
+                  use_sg_reduce_fp=False, metrics_on="device"):
     if evaluator == "Volume":
         return EvaluateVolume(estimator, model_dir=model_dir, params=params, merge_tumor_to_liver=merge_tumor_to_liver,
-                              largest=largest, use_sg_reduce_fp=use_sg_reduce_fp)
+                              largest=largest, use_sg_reduce_fp=use_sg_reduce_fp, metrics_on=metrics_on)
     raise ValueError("Unsupported evaluator: {}. Must be [Volume, ]".format(evaluator))
 
 
@@ -90,8 +93,11 @@ class EvaluateVolume(EvaluateBase):
     """Evaluate a model case by case (volume by volume)."""
 
     def __init__(self, estimator=None, model_dir=None, params=None, merge_tumor_to_liver=True, largest=True,
-                 use_sg_reduce_fp=False):
+                 use_sg_reduce_fp=False, metrics_on="device"):
         super(EvaluateVolume, self).__init__()
+        if metrics_on not in ("device", "host"):
+            raise ValueError("metrics_on must be 'device' or 'host', got {!r}".format(metrics_on))
+        self.metrics_on = metrics_on
         self.estimator = estimator
         self.model_dir = model_dir or (estimator.model_dir if estimator is not None else None)
         self.params = params or estimator.params
@@ -240,6 +246,21 @@ class EvaluateVolume(EvaluateBase):
                     decouple_volume["Liver"].astype(decouple_volume["Tumor"].dtype)
         return decouple_volume
 
+    def _postprocess_device(self, volume, is_label=False):
+        """_postprocess on the device: `volume` is a device tensor of class ids (or a dict class -> device mask); returns
+        class -> uint8 device mask, with tumor merged into liver and the liver reduced to its largest component."""
+        if not isinstance(volume, dict):
+            decouple_volume = {cls: (volume == i + 1).view(torch.uint8) for i, cls in enumerate(self.classes)}
+        else:
+            decouple_volume = dict(volume)
+        if self.merge_tumor_to_liver and "Tumor" in decouple_volume and "Liver" in decouple_volume:
+            decouple_volume["Liver"] = decouple_volume["Liver"] | decouple_volume["Tumor"]
+        if self.largest and "Liver" in decouple_volume and not is_label:
+            decouple_volume["Liver"] = ops.largest_component3d(decouple_volume["Liver"])
+            if self.merge_tumor_to_liver and "Tumor" in decouple_volume:
+                decouple_volume["Tumor"] = decouple_volume["Tumor"] & decouple_volume["Liver"]
+        return decouple_volume
+
     def run_with_session(self, session=None):
         """evaluator_liver.py:164-169,286-330 (2-D): evaluate on the `eval_online` batches from inside training, with
         the live variables and moving statistics -- the mean of the in-graph "<Class>/<Metric>" values per batch, or
@@ -290,6 +311,8 @@ class EvaluateVolume(EvaluateBase):
             vol = {cls: torch.cat(preds[cls], dim=0) for cls in self.classes}
             lab = torch.cat(labels, dim=0)
             n_real = depths.get(case, lab.shape[0])                    # drop the padding slices of the last batch
+            if self.metrics_on == "device":
+                return finish_device(vol, lab[:n_real], n_real)
             lab = lab[:n_real].cpu().numpy()
             results = {}
             for i, cls in enumerate(self.classes):
@@ -303,6 +326,22 @@ class EvaluateVolume(EvaluateBase):
                     acc[cls + "_tp"] += conf.tp
                 else:
                     for met, value in metric_ops.metric_3d(pred, ref, required=self.metrics_str).items():
+                        results["{}/{}".format(cls, met)] = value
+            if not use_global:
+                self.append_metrics(results)
+
+        def finish_device(vol, lab, n_real):
+            results = {}
+            for i, cls in enumerate(self.classes):
+                pred = vol[cls][:n_real].to(torch.uint8)
+                ref = (lab == i + 1).view(torch.uint8)
+                if use_global:
+                    conf = ops.mask_counts(pred, ref)
+                    acc[cls + "_fn"] += conf["fn"]
+                    acc[cls + "_fp"] += conf["fp"]
+                    acc[cls + "_tp"] += conf["tp"]
+                else:
+                    for met, value in metric_ops.metric_3d_device(pred, ref, required=self.metrics_str).items():
                         results["{}/{}".format(cls, met)] = value
             if not use_global:
                 self.append_metrics(results)
@@ -375,7 +414,9 @@ class EvaluateVolume(EvaluateBase):
                                                                    dtype=getattr(self.config, "pred_type", "pred"),
                                                                    save_path=save_path, **run_kwargs):
             results = {}
-            if do_eval:
+            if do_eval and self.metrics_on == "device":
+                self._score_case_device(volume, labels, post_processed, accumulator, use_global)
+            elif do_eval:
                 if not post_processed:
                     volume = self._postprocess(volume)
                 labels = self._postprocess(labels, is_label=True)
@@ -409,6 +450,28 @@ class EvaluateVolume(EvaluateBase):
             with (save_path / "results.json").open("w") as f:
                 json.dump(results, f)
         return results
+
+    def _score_case_device(self, volume, labels, post_processed, accumulator, use_global):
+        """One case of _run_actual on the device: one upload of the volume and one of the labels, then post-processing,
+        the global Dice counts and metric_3d_device per class."""
+        def upload(x):
+            return torch.from_numpy(np.ascontiguousarray(x)).cuda()
+        if post_processed:
+            volume = {cls: upload(v) for cls, v in volume.items()}
+        else:
+            volume = self._postprocess_device(upload(volume))
+        labels = self._postprocess_device(upload(labels), is_label=True)
+        results = {}
+        for cls in self.classes:
+            conf = ops.mask_counts(volume[cls], labels[cls])
+            accumulator[cls + "_fn"] += conf["fn"]
+            accumulator[cls + "_fp"] += conf["fp"]
+            accumulator[cls + "_tp"] += conf["tp"]
+        if not use_global:
+            for cls in self.classes:
+                for met, value in metric_ops.metric_3d_device(volume[cls], labels[cls], required=self.metrics_str).items():
+                    results["{}/{}".format(cls, met)] = value
+            self.append_metrics(results)
 
     def compare(self, *args_, **kwargs):
         return _compare(*args_, **kwargs)

@@ -161,6 +161,61 @@ def metric_3d(logits3d, labels3d, required=None, **kwargs):
     return out
 
 
+def metric_3d_device(pred, ref, required=None, sampling=(1, 1, 1)):
+    """metric_3d on the device (csrc/evalvol.hip): the same keys, Python types and edge behaviour.  pred / ref are
+    same-shape masks, torch device tensors (numpy arrays are uploaded once).  Dice / VOE / RVD come from the same integer
+    counts through the same expressions, so they are the same floats; ASSD / RMSD / MSD sum the exact distance transform
+    in float64 in a fixed order (equal to the host's up to rounding).  At most two device-to-host reads."""
+    import math
+
+    import numpy as np
+    metrics = ["Dice", "VOE", "RVD", "ASSD", "RMSD", "MSD"]
+    if required is None:
+        required = list(metrics)
+    elif isinstance(required, str):
+        required = [required]
+    else:
+        required = list(required)
+    for req in required:
+        if req not in metrics:
+            raise ValueError("Not supported metric: %s" % req)
+    need_dist_map = any(req in metrics[3:] for req in required)
+    pred, ref = (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (pred, ref))
+    if pred.dim() > 3:
+        pred = pred.squeeze()
+    if ref.dim() > 3:
+        ref = ref.squeeze()
+    assert pred.shape == ref.shape, ("Shape mismatch of logits3D and labels3D. \n"
+                                     "Logits3D has shape %r while labels3D has "
+                                     "shape %r" % (tuple(pred.shape), tuple(ref.shape)))
+    c = ops.mask_counts(pred, ref)
+    na, nb, inter = c["na"], c["nb"], c["inter"]
+    out = {}
+    if need_dist_map:
+        if na == 0 or nb == 0:
+            out["ASSD"] = 0
+            out["MSD"] = 0
+        else:
+            (s_ab, q_ab, m_ab, n_ab), (s_ba, q_ba, m_ba, n_ba) = ops.surface_distances(pred, ref, sampling)
+            n = n_ab + n_ba
+            if "ASSD" in required:
+                out["ASSD"] = 1.0 / n * (s_ab + s_ba)
+            if "MSD" in required:
+                out["MSD"] = np.float64(max(m_ab, m_ba))
+            if "RMSD" in required:
+                out["RMSD"] = math.sqrt(1.0 / n) * math.sqrt(q_ab + q_ba)
+    if "Dice" in required:
+        out["Dice"] = 2.0 * inter / float(na + nb) if na + nb > 0 else 0.0
+    if "VOE" in required:
+        union = c["union"]
+        out["VOE"] = 1.0 - (inter / float(union) if union > 0 else float("nan"))
+    if "RVD" in required:
+        if nb == 0:
+            raise RuntimeError("The second supplied array does not contain any binary object.")
+        out["RVD"] = abs((na - nb) / float(nb))
+    return out
+
+
 class ConfusionMatrix(object):
     """loss_metrics.py:506-580: tp / fp / tn / fn counts of a test volume against a reference volume."""
 

@@ -1141,6 +1141,96 @@ def boundary_weights(labels):
     return wmap
 
 
+# ----------------------------------------------------------------------------- volume evaluation (csrc/evalvol.hip)
+def _mask3d(t):
+    """A [D, H, W] device mask as a dense uint8 tensor (non-zero = object)."""
+    _require_cuda(t)
+    if t.dim() != 3:
+        raise ValueError("a 3-D [D, H, W] mask expected, got shape {}".format(tuple(t.shape)))
+    if t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    elif t.dtype != torch.uint8:
+        t = t != 0
+        t = t.view(torch.uint8)
+    return t.contiguous()
+
+
+def largest_component3d(mask):
+    """utils/array_kits.get_largest_component(mask, rank=3) on the device: the largest 6-connected component as a 0/1
+    uint8 mask, zeros for an empty mask.  One device-to-host read (the size of the largest component and how many share
+    it).  When several share it, the host's rule -- the last index of np.argsort(areas) over the components in scipy's
+    label order, which np.argsort's unstable sort decides for long arrays -- is applied to the component sizes the
+    kernel left in its workspace, exactly as the host computes it."""
+    import numpy as np
+    m = _mask3d(mask)
+    d, h, w = m.shape
+    n = d * h * w
+    out = torch.empty_like(m)
+    info = torch.empty(4, dtype=torch.int32, device=m.device)
+    lib = _abi.lib()
+    nbytes = lib.unetk_largest_component_ws_bytes(d, h, w)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=m.device)
+    check(lib.unetk_largest_component(ptr(m), d, h, w, ptr(out), ptr(info), ptr(ws), nbytes, stream_ptr()),
+          "largest_component3d")
+    _, _, ties, _ = info.tolist()
+    if ties > 1:
+        off = (4 * n + 255) & ~255
+        sizes = ws[off:off + 4 * n].view(torch.int32)
+        roots = torch.nonzero(sizes).flatten()                     # ascending = scipy's label order
+        areas = sizes[roots].cpu().numpy().astype(np.int64)
+        root = int(roots[int(np.argsort(areas)[-1])])
+        check(lib.unetk_component_mask(ptr(ws), d, h, w, root, ptr(out), stream_ptr()), "component_mask")
+    return out
+
+
+def mask_counts_async(a, b):
+    """int64 device tensor {|A|, |B|, |A and B|, |A or B|} of two same-shape masks (no host read)."""
+    a, b = _mask3d(a), _mask3d(b)
+    if a.shape != b.shape:
+        raise ValueError("shape mismatch: {} and {}".format(tuple(a.shape), tuple(b.shape)))
+    d, h, w = a.shape
+    counts = torch.empty(4, dtype=torch.int64, device=a.device)
+    nbytes = _abi.lib().unetk_mask_counts_ws_bytes(d, h, w)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=a.device)
+    check(_abi.lib().unetk_mask_counts(ptr(a), ptr(b), d, h, w, ptr(counts), ptr(ws), nbytes, stream_ptr()), "mask_counts")
+    return counts
+
+
+def mask_counts(a, b):
+    """Confusion counts of a test mask `a` against a reference mask `b` (loss_metrics.ConfusionMatrix): a dict of Python
+    ints na, nb, inter, union, tp, fp, fn.  One device-to-host read."""
+    na, nb, inter, union = (int(v) for v in mask_counts_async(a, b).tolist())
+    return {"na": na, "nb": nb, "inter": inter, "union": union, "tp": inter, "fp": na - inter, "fn": nb - inter}
+
+
+def surface_distances(a, b, sampling=(1.0, 1.0, 1.0)):
+    """Surface distances between two non-empty masks (utils/surface.Surface): ((sum d, sum d^2, max d, n) of the surface
+    voxels of `a` to the surface of `b`, the same of `b` to `a`), d in the units of `sampling` (per axis of the array).
+    The distance transforms run over the union bounding box of the two surfaces.  One device-to-host read."""
+    a, b = _mask3d(a), _mask3d(b)
+    if a.shape != b.shape:
+        raise ValueError("shape mismatch: {} and {}".format(tuple(a.shape), tuple(b.shape)))
+    sz, sy, sx = (float(v) for v in sampling)
+    d, h, w = a.shape
+    lib, st, dev = _abi.lib(), stream_ptr(), a.device
+    edges = torch.empty((2, d, h, w), dtype=torch.uint8, device=dev)
+    box = torch.empty(6, dtype=torch.int32, device=dev)
+    check(lib.unetk_surface3d(ptr(a), d, h, w, ptr(edges[0]), ptr(box), 0, st), "surface3d")
+    check(lib.unetk_surface3d(ptr(b), d, h, w, ptr(edges[1]), ptr(box), 1, st), "surface3d")
+    dist2 = torch.empty((d, h, w), dtype=torch.float64, device=dev)
+    n_edt = lib.unetk_edt3d_sq_ws_bytes(d, h, w)
+    n_sum = lib.unetk_surface_dist_ws_bytes(d, h, w)
+    ws = torch.empty(max(n_edt, n_sum, 16), dtype=torch.uint8, device=dev)
+    res = torch.empty((2, 4), dtype=torch.float64, device=dev)
+    for k, (src, dst) in enumerate(((0, 1), (1, 0))):     # k = 0: a's surface against b's transform
+        check(lib.unetk_edt3d_sq(ptr(edges[dst]), d, h, w, ptr(box), sz, sy, sx, ptr(dist2), ptr(ws), n_edt, st), "edt3d_sq")
+        check(lib.unetk_surface_dist(ptr(edges[src]), ptr(dist2), d, h, w, ptr(res[k]), ptr(ws), n_sum, st), "surface_dist")
+    host = res.cpu()
+    n = host.view(torch.int64)[:, 3].tolist()
+    vals = host.tolist()
+    return tuple((vals[k][0], vals[k][1], vals[k][2], int(n[k])) for k in range(2))
+
+
 def lits_batch(slices, seg_slices, sample_tab, clip, out_hw, channels, lab_scale=64, noise_scale=0.0, seed=0):
     """One training batch from device-resident decoded slices (input_pipeline.py:243-284): slices uint16 / seg_slices
     uint8 [n, src_h, src_w] (stored as int16 / uint8 tensors), sample_tab int32 [N, C+7], clip f32 [N, 2]."""

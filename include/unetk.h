@@ -511,6 +511,49 @@ size_t unetk_boundary_weights_ws_bytes(int N, int H, int W);
 int unetk_boundary_weights(const int32_t* labels, int N, int H, int W, float* wmap, void* ws,
                            size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- volume evaluation
+ * evaluators/evaluator_liver.py:680-702,906-996 (_postprocess, _run_actual) and loss_metrics.py:342-452 (metric_3d), which
+ * the reference runs on the host with scipy.  Masks are dense C-order uint8 [D,H,W], non-zero = object.  D, H, W > 0
+ * (else UNETK_E_BADARG) and D*H*W < 2^31 (else UNETK_E_UNSUPPORTED; the *_ws_bytes queries then return 0).  Workspaces are
+ * 16-byte aligned, of at least the queried size; every reduction runs in a fixed order, so results are bit-reproducible.
+ *
+ * unetk_largest_component: out = the largest 6-connected component of mask (0/1), the one with the larger root (minimum
+ *   linear index of the component) on ties -- utils/array_kits.py:357-384 get_largest_component(x, rank=3), whose scipy
+ *   labels number components in raster order of their roots and whose tie rule is "the last of np.argsort(areas)".  An
+ *   empty mask gives zeros.  Union-find with integer atomicMin (each voxel ends at the minimum index of its component),
+ *   sizes by integer atomics, one packed 64-bit (size, root) max.  info int32[4] = {root (-1 if empty), its size, number
+ *   of components of that size, number of components}.  The workspace then holds the component table: int32 label[n] at
+ *   offset 0 (the root of each voxel, -1 = background) and int32 size[n] at offset (4n + 255) & ~255 (each component's
+ *   size at its root, 0 elsewhere), n = D*H*W.  np.argsort is stable only for short arrays, so when info[2] > 1 a caller
+ *   that must match the host exactly runs the host's argsort over the sizes in root order and passes its pick to
+ *   unetk_component_mask, which rewrites out = (label == root) from that table.
+ * unetk_mask_counts: counts int64[4] = {|A|, |B|, |A and B|, |A or B|} (tp = [2], fp = [0] - [2], fn = [1] - [2]).
+ * unetk_surface3d: edge = A xor erode(A, 18-neighbourhood), the volume border counting as background (utils/surface.py
+ *   Surface.compute_contour).  box int32[6] = {z0, y0, x0, z1, y1, x1} (half-open) receives the bounding box of the edge
+ *   voxels: reset first unless accumulate_box (then widened: two calls give the union box of two surfaces); it stays empty
+ *   (z1 = 0) for an empty edge.
+ * unetk_edt3d_sq: dist2 f64 [D,H,W] = squared Euclidean distance, with voxel spacing (sz, sy, sx) > 0, from each voxel
+ *   inside the device box to the nearest non-zero voxel of `feature` -- scipy.ndimage.distance_transform_edt(~feature,
+ *   sampling)^2.  Exact when the box holds every feature voxel; voxels outside the box are not written.  Three separable
+ *   1-D passes (lower envelope of parabolas), one line per thread.
+ * unetk_surface_dist: over the non-zero voxels of surf, d = sqrt(dist2): out = {sum d, sum d^2, max d} as f64 and the
+ *   count as int64 in the fourth 8-byte slot; zeros for an empty surf.  ASSD / RMSD / MSD follow on the host. */
+size_t unetk_largest_component_ws_bytes(int D, int H, int W);
+int unetk_largest_component(const uint8_t* mask, int D, int H, int W, uint8_t* out, int32_t* info, void* ws,
+                            size_t ws_bytes, void* stream);
+int unetk_component_mask(const void* ws, int D, int H, int W, int32_t root, uint8_t* out, void* stream);
+size_t unetk_mask_counts_ws_bytes(int D, int H, int W);
+int unetk_mask_counts(const uint8_t* a, const uint8_t* b, int D, int H, int W, int64_t* counts, void* ws,
+                      size_t ws_bytes, void* stream);
+int unetk_surface3d(const uint8_t* mask, int D, int H, int W, uint8_t* edge, int32_t* box, int accumulate_box,
+                    void* stream);
+size_t unetk_edt3d_sq_ws_bytes(int D, int H, int W);
+int unetk_edt3d_sq(const uint8_t* feature, int D, int H, int W, const int32_t* box, double sz, double sy, double sx,
+                   double* dist2, void* ws, size_t ws_bytes, void* stream);
+size_t unetk_surface_dist_ws_bytes(int D, int H, int W);
+int unetk_surface_dist(const uint8_t* surf, const double* dist2, int D, int H, int W, double* out, void* ws,
+                       size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- LiTS training batch  
  * DataLoader/Liver/input_pipeline.py:243-284 `data_processing_train` for a whole batch, gathering from decoded slices
  * that are RESIDENT in device memory: per sample crop_to_bounding_box -> resize_bilinear(align_corners) -> window clip
