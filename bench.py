@@ -9,8 +9,11 @@ Liver+Tumor, 256x256x3, bs 32 per GPU, fp32 (BASELINE.json configs[1]) on synthe
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events around every launch of
-the conv kernels during the timed region; `cpu_baseline` times the CPU oracle (a restatement, not
-the TensorFlow reference -- TF 1.13 cannot run here) on a bounded sample of the same workload.
+the conv kernels during the timed region.  A plain run does only what the headline figure needs: set-up,
+settle + warm-up, the K timed steps, --dump-outputs, the line.  `--full` adds what takes runs of its own:
+`cpu_baseline` times the CPU oracle (a restatement, not the TensorFlow reference -- TF 1.13 cannot run
+here) on a bounded sample of the same workload, `dice_vs_oracle` trains against the oracle, and with data
+parallelism the timed steps are run again without the all-reduce (`data_parallel`).
 """
 import argparse
 import json
@@ -190,8 +193,7 @@ def cpu_baseline(size, full=True):
     configs[1]-shaped workload at bs 2 (3 classes; median of 2 timed steps after one warm-up) = `value`, and BASELINE.json
     configs[0] (Liver only = 2 classes, bs 2; one timed step after one warm-up), and the configs[1] shape at bs 8 (SURVEY.md 8d
     "bs 2 and bs 8") -- ~15 s of CPU work in all since the thread pool follows the CPUs the process may use (round 5: 16 threads
-    on a 16-core grant run the bs-2 step in 0.93 s; the 128 throttled threads before took 5.2 s), so the default run is not
-    mostly oracle."""
+    on a 16-core grant run the bs-2 step in 0.93 s; the 128 throttled threads before took 5.2 s).  Runs with --full only."""
     threads = torch.get_num_threads()
     bs = 2
     t_start = time.perf_counter()
@@ -214,8 +216,8 @@ def cpu_baseline(size, full=True):
 
 
 def dice_vs_oracle(steps=120, size=64, bs=8):
-    """BASELINE.json metric "... Dice vs ref": part of the cpu_baseline leg (the only place bench.py touches the oracle), outside
-    the timed region.  The headline network (UNet.yml sizes, 3 classes, batch norm, numerical loss weights) is trained for `steps`
+    """BASELINE.json metric "... Dice vs ref": part of the cpu_baseline leg of --full (the only place bench.py touches the oracle),
+    outside the timed region.  The headline network (UNet.yml sizes, 3 classes, batch norm, numerical loss weights) is trained for `steps`
     TF-Adam steps at size x size, bs `bs`, from identical variables on the same learnable synthetic stream, once on the HIP path
     (fp32) and once on the oracle in float64 (on the device: the oracle is a torch restatement; as the CHECKER only); then
     Liver/Dice and Tumor/Dice (loss_metrics.py:261-301) on held-out batches.  `max_abs_diff` is what north_star bounds by 1e-3;
@@ -363,12 +365,16 @@ def main():
     ap.add_argument("--depth", type=int, default=0,
                     help="UNet3D: patch depth (default = --size, i.e. a cube); the reference's own 3-D script trains "
                          "--depth 10 --size 256 --batch 4 (threed_script/201_unet_v1.sh:26)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-baseline-full", action="store_true", help="kept for old command lines: the bs 8 leg is part of the default since round 5")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: cpu_baseline and dice_vs_oracle (UNet, "
+                         "one rank) and, with data parallelism, the timed steps again without the all-reduce "
+                         "(data_parallel.compute_only_ms_per_step, dp_again_ms_per_step and the efficiencies)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline and dice_vs_oracle")
+    ap.add_argument("--cpu-baseline-full", action="store_true", help="kept for old command lines: the bs 8 leg is part of --full's cpu_baseline")
     ap.add_argument("--no-kernel-events", action="store_true", help="skip per-launch HIP-event timing")
-    ap.add_argument("--settle-seconds", type=float, default=45.0,
+    ap.add_argument("--settle-seconds", type=float, default=None,
                     help="upper bound of the untimed settle phase in front of the warm-up (blocks of ten steps until two in a "
-                         "row show no one-step hiccup of the box); 0 = none")
+                         "row show no one-step hiccup of the box); default 15, 45 with --full; 0 = none")
     ap.add_argument("--single-stream", action="store_true",
                     help="every step on ONE stream (filter gradients otherwise run beside input gradients on a second stream): "
                          "what the traced steps do anyway; for rocprofv3 runs whose per-kernel averages are compared with the line's")
@@ -401,6 +407,9 @@ def main():
     a = ap.parse_args()
     if a.steps < 1:
         raise SystemExit("bench.py --steps must be at least 1")
+    if a.settle_seconds is None:
+        # 1.5 s on a quiet box; the bound only matters on a box whose gaps go on, and keeps a plain run's set-up short
+        a.settle_seconds = 45.0 if a.full else 15.0
     if a.dump_outputs:
         a.settle_seconds = 0.0          # settle runs a varying number of steps: the dumped state would differ run to run
 
@@ -605,8 +614,8 @@ def main():
         dist.all_gather(every, mine)
         rank_ms = [float(v.item()) for v in every]
 
-    # ---- data-parallel diagnostics (N > 1): what the buckets did, how long the compute stream waited for them, and this
-    # rank's step WITHOUT the all-reduce (3 extra untimed-by-the-metric steps, replicas may drift afterwards: the run is over)
+    # ---- data-parallel diagnostics (N > 1): what the buckets did and how long the compute stream waited for them; with --full
+    # also this rank's step WITHOUT the all-reduce (extra steps untimed by the metric, replicas may drift afterwards: the run is over)
     dp_diag = None
     if dp_on:
         bk = getattr(solver, "_buckets", None)
@@ -615,7 +624,8 @@ def main():
                    "bucket_launch_progress": bk.last["launch_progress"] if bk is not None and bk.last else None,
                    "bucket_bytes": bk.last["bucket_bytes"] if bk is not None and bk.last else None,
                    "allreduce_exposed_ms": round(bk.exposed_ms(), 4) if bk is not None and bk.exposed_ms() is not None else None,
-                   "allreduce_bytes": int(sum(g.numel() for g in model.params.grad.values()) * 4)}
+                   "allreduce_bytes": int(sum(g.numel() for g in model.params.grad.values()) * 4), "backend": backend}
+    if dp_diag is not None and a.full:
         solver.strategy = None
         if bk is not None:
             bk.remove()
@@ -635,7 +645,6 @@ def main():
         dp_diag["compute_only_ms_per_step"] = round((time.perf_counter() - tc) / a.steps * 1e3, 3)
         ops.profile_on(None)
         ops.side_streams_pause(one_stream)
-        dp_diag["backend"] = backend
         dist.barrier()
         # ... and the data-parallel region once more BEHIND it (not part of the metric): DP / compute-only / DP -- the mean of the
         # two DP timings against the compute-only one in between cancels the drift of a clock-governed step over the run (the bf16
@@ -700,7 +709,8 @@ def main():
             "traced_steps_single_stream": True,
         }
         if dp_diag is not None:
-            dp_diag["dp_efficiency_vs_compute_only"] = round(dp_diag["compute_only_ms_per_step"] / ms, 4)
+            if "compute_only_ms_per_step" in dp_diag:
+                dp_diag["dp_efficiency_vs_compute_only"] = round(dp_diag["compute_only_ms_per_step"] / ms, 4)
             if dp_diag.get("dp_again_ms_per_step"):      # drift-cancelled: compute-only against the mean of the DP regions around it
                 dp_diag["dp_efficiency_drift_cancelled"] = round(
                     dp_diag["compute_only_ms_per_step"] / (0.5 * (ms + dp_diag["dp_again_ms_per_step"])), 4)
@@ -803,7 +813,7 @@ def main():
                 pass
         if dumped is not None:
             out["dump_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
-        if not a.no_cpu_baseline and world == 1 and a.model == "UNet":
+        if a.full and not a.no_cpu_baseline and world == 1 and a.model == "UNet":
             out["cpu_baseline"] = cpu_baseline(a.size)
             if a.dtype == "fp32":
                 out["dice_vs_oracle"] = dice_vs_oracle()

@@ -69,14 +69,18 @@ def test_bench_two_ranks_from_a_plain_shell_gloo_rehearsal():
     assert out["config"]["global_batch"] == 4 and out["config"]["parallelism"] == "dp2" and out["scaling"] == "weak"
     assert out["value"] > 0 and out["rank_ms_per_step_min"] <= out["rank_ms_per_step_max"] <= out["ms_per_step"] * 1.5
     assert "roofline" in out and out["roofline"]["achieved"] > 0
+    # a plain run (no --full) measures the timed steps only: no re-run without the all-reduce, no oracle legs
+    assert out["data_parallel"]["buckets"] >= 1 and "compute_only_ms_per_step" not in out["data_parallel"]
+    assert "cpu_baseline" not in out and "dice_vs_oracle" not in out
 
 
 @pytest.mark.gpu
 def test_bench_runs_the_rccl_data_parallel_path_in_a_world_of_one():
     """the production data-parallel path -- process group on RCCL ("nccl"), GradBuckets launched from backward
     hooks, finish() joining the compute stream, 1/N in the optimiser kernel -- driven through bench.py itself on the one GPU
-    of the test box; the line carries the diagnostics an 8-GPU run will be read with."""
-    r = _run(["--gpus", "1", "--dp-rehearsal", "--steps", "3", "--warmup", "1", "--batch", "4", "--size", "64", "--no-cpu-baseline"])
+    of the test box; the line carries the diagnostics an 8-GPU run will be read with (the compute-only re-run: --full)."""
+    r = _run(["--gpus", "1", "--dp-rehearsal", "--full", "--steps", "3", "--warmup", "1", "--batch", "4", "--size", "64",
+              "--no-cpu-baseline"])
     assert r.returncode == 0, r.stderr[-3000:]
     out = _line(r.stdout)
     dp = out["data_parallel"]

@@ -12,7 +12,7 @@ T="timeout -k 10 300"
 PART="${1:-all}"        # bench | prof | all  (one gpurun call is at most 1200 s: run the two parts in two calls)
 if [[ "$PART" != "prof" ]]; then
 
-$T python bench.py --steps 20 --warmup 5 > "$OUT/bench_n1.json"            # the driver's own command line
+$T python bench.py --steps 20 --warmup 5 --full > "$OUT/bench_n1.json"     # the headline command + cpu_baseline, dice_vs_oracle
 echo "bench_n1 done"
 $T python bench.py --steps 20 --warmup 5 --no-kernel-events --no-cpu-baseline > "$OUT/bench_n1_noevents.json"
 $T python bench.py --steps 10 --warmup 3 --detail --no-cpu-baseline > "$OUT/bench_n1_by_layer.json"
@@ -33,8 +33,8 @@ $T python bench.py --dtype bf16 --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/
 $T python bench.py --dtype bf16 --size 512 --batch 8 --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench_bf16_512_bs8.json"
 $T python bench.py --dtype bf16 --model GUNet --batch 8 --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench_bf16_gunet_bs8.json"
 $T python bench.py --dtype bf16c --size 512 --batch 8 --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench_bf16c_512_bs8.json"
-$T python bench.py --dp-rehearsal --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench_n1_dp_rehearsal.json"
-$T python bench.py --dp-rehearsal --dtype bf16 --size 512 --batch 8 --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench_bf16_512_bs8_dp_rehearsal.json"
+$T python bench.py --dp-rehearsal --full --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench_n1_dp_rehearsal.json"
+$T python bench.py --dp-rehearsal --full --dtype bf16 --size 512 --batch 8 --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench_bf16_512_bs8_dp_rehearsal.json"
 $T python bench.py --dtype bf16 --model GUNet --batch 8 --steps 10 --warmup 3 --no-cpu-baseline --no-kernel-events > "$OUT/bench_bf16_gunet_bs8_noevents.json"
 echo "bf16 benches done"
 # inference: the volume evaluator's slab loop, fused conv + affine + ReLU [+ pool] epilogue vs the two-pass path
