@@ -59,9 +59,15 @@ class LitsDesc(Structure):
                 ("src_w", c_int32), ("lab_scale", c_int32), ("seed", ctypes.c_uint32), ("noise_scale", c_float)]
 
 
+class LitsGuideDesc(Structure):
+    _fields_ = [("N", c_int32), ("H", c_int32), ("W", c_int32), ("C", c_int32), ("src_h", c_int32), ("src_w", c_int32),
+                ("n_obj", c_int32), ("min_std", c_float)]
+
+
 P = c_void_p
 _SIGNATURES = {
     "unetk_lits_batch": (c_int, [POINTER(LitsDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "unetk_lits_spatial_guide": (c_int, [POINTER(LitsGuideDesc), P, P, P, P, P]),
     "unetk_abi_version": (c_int, []),
     "unetk_nan_watch": (c_int, [P, P, c_int32, P]),
     "unetk_png_unfilter": (c_int, [P, c_int64, c_int, c_int, c_int, c_int, P, c_int64, P, P]),

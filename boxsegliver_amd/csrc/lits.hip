@@ -74,6 +74,59 @@ __global__ __launch_bounds__(256) void lits_batch_kernel(unetk_lits_desc d, cons
   }
 }
 
+// Spatial guide of the guided pipeline (input_pipeline_g.py:382-412): the reference renders
+// create_spatial_guide_2d(crop size, centres, max(stddevs, min_std)) per sample, resize_bilinear(align_corners) to the
+// network size, then g / 2 + 0.5.  A bilinear resize of a rendered guide reads it at 4 integer corners, so each output pixel
+// evaluates the Gaussians at exactly those corners -- the same arithmetic without the crop-resolution intermediate.  Sample
+// geometry (crop clamp, flips, corners, weights) is lits_batch_kernel's, so guide and image line up pixel for pixel.
+//   obj_ptr int32 [N + 1] (CSR into obj), obj float4 [n_obj] = (cy, cx, sy, sx), centres relative to the crop.
+__device__ __forceinline__ float guide_at(float py, float px, const float4* __restrict__ o, int k0, int k1, float min_std) {
+  float g = 0.f;                               // every term is >= 0: a max from 0 is create_spatial_guide_2d's reduce_max
+  for (int k = k0; k < k1; ++k) {
+    const float4 b = o[k];
+    const float sy = fmaxf(b.z, min_std), sx = fmaxf(b.w, min_std);
+    const float dy = py - b.x, dx = px - b.y;
+    // (coords - center)^2 / (2 * s * s), summed y then x, full-precision exp (image_ops.py:396-434)
+    g = fmaxf(g, expf(-(dy * dy / (2.f * sy * sy) + dx * dx / (2.f * sx * sx))));
+  }
+  return g;
+}
+
+__global__ __launch_bounds__(256) void lits_guide_kernel(unetk_lits_guide_desc d, const int32_t* __restrict__ tab,
+                                                         const int32_t* __restrict__ obj_ptr, const float4* __restrict__ obj,
+                                                         float* __restrict__ guide) {
+  const int64_t total = (int64_t)d.N * d.H * d.W;
+  const int TW = d.C + 7;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int x = (int)(i % d.W);
+    const int y = (int)((i / d.W) % d.H);
+    const int n = (int)(i / ((int64_t)d.W * d.H));
+    // the CSR row is clamped into [0, n_obj]: a malformed pointer table cannot become an out-of-bounds read
+    const int k0 = min(max(obj_ptr[n], 0), d.n_obj), k1 = min(max(obj_ptr[n + 1], k0), d.n_obj);
+    if (k1 == k0) {              // no object on this sample: the reference's false_fn, exactly 0.5
+      guide[i] = 0.5f;
+      continue;
+    }
+    const int32_t* t = tab + (int64_t)n * TW;
+    const int off_y = min(max(t[d.C + 1], 0), d.src_h - 1), off_x = min(max(t[d.C + 2], 0), d.src_w - 1);
+    const int ch = min(max(t[d.C + 3], 1), d.src_h - off_y), cw = min(max(t[d.C + 4], 1), d.src_w - off_x);
+    const int sx = t[d.C + 5] ? d.W - 1 - x : x;
+    const int sy = t[d.C + 6] ? d.H - 1 - y : y;
+    const float hs = d.H > 1 ? (float)(ch - 1) / (float)(d.H - 1) : 0.f;
+    const float ws = d.W > 1 ? (float)(cw - 1) / (float)(d.W - 1) : 0.f;
+    const float in_y = sy * hs, in_x = sx * ws;
+    const int y0 = (int)floorf(in_y), x0 = (int)floorf(in_x);
+    const int y1 = min(y0 + 1, ch - 1), x1 = min(x0 + 1, cw - 1);
+    const float ly = in_y - y0, lx = in_x - x0;
+    const float tl = guide_at((float)y0, (float)x0, obj, k0, k1, d.min_std);
+    const float tr = guide_at((float)y0, (float)x1, obj, k0, k1, d.min_std);
+    const float bl = guide_at((float)y1, (float)x0, obj, k0, k1, d.min_std);
+    const float br = guide_at((float)y1, (float)x1, obj, k0, k1, d.min_std);
+    const float top = tl + (tr - tl) * lx, bot = bl + (br - bl) * lx;     // tf resize_bilinear's lerp order
+    guide[i] = (top + (bot - top) * ly) / 2.f + 0.5f;
+  }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -176,6 +229,21 @@ extern "C" int unetk_lits_batch(const unetk_lits_desc* d, const uint16_t* slices
   if (grid > 65536) grid = 65536;
   UNETK_LAUNCH(lits_batch_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, *d, slices, seg_slices,
                      sample_tab, clip, images, labels);
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
+extern "C" int unetk_lits_spatial_guide(const unetk_lits_guide_desc* d, const int32_t* sample_tab, const int32_t* obj_ptr,
+                                        const float* obj, float* guide, void* stream) {
+  UNETK_REQUIRE(d && sample_tab && obj_ptr && guide && (obj || d->n_obj == 0));
+  UNETK_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->C > 0 && d->C <= 8 && d->src_h > 0 && d->src_w > 0 && d->n_obj >= 0);
+  UNETK_REQUIRE(d->min_std > 0.f);                    // a zero stddev would divide by zero (image_ops.py: "must not contain zero")
+  UNETK_REQUIRE(d->n_obj == 0 || (((uintptr_t)obj) & 15u) == 0);       // float4 rows
+  const int64_t total = (int64_t)d->N * d->H * d->W;
+  int64_t grid = (total + 255) / 256;
+  if (grid > 65536) grid = 65536;
+  UNETK_LAUNCH(lits_guide_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, *d, sample_tab, obj_ptr,
+               reinterpret_cast<const float4*>(obj), guide);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }

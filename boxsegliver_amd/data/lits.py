@@ -327,10 +327,13 @@ class TrainSampler(object):
         object box (shrunk by 5 px) inside the crop when that range is more than 20 px wide, else in
         [box start - 20, a point between the box's start and its centre] clipped to the image (:337-352);
       * neighbouring slices fill the other channels, -1 (zeros) outside the volume; window level uniform in
-        [10, 50] / [500, 540] HU-units x IM_SCALE when random_window_level else fixed 50 / 500; independent flip coins."""
+        [10, 50] / [500, 540] HU-units x IM_SCALE when random_window_level else fixed 50 / 500; independent flip coins.
+
+    `guide` (a GuidePolicy) adds the spatial-guide objects of the guided pipeline (`guide_objects`); their draws come from
+    a generator of their own, so a guided run draws the same slices, crops, windows and flips as an unguided one."""
 
     def __init__(self, data_list, batch_size, config, liver_percent=0., tumor_percent=0., random_scale=(1., 1.),
-                 random_window_level=False, random_flip=0, seed=None):
+                 random_window_level=False, random_flip=0, seed=None, guide=None):
         self.bs, self.c = int(batch_size), int(config.im_channel)
         self.target = np.array([config.im_height, config.im_width], dtype=np.float64)
         self.scale = (float(random_scale[0]), float(random_scale[1]))
@@ -352,6 +355,10 @@ class TrainSampler(object):
         self.n_liver = max(int(math.ceil(self.bs * liver_percent)), self.n_tumor)          # tumor samples count as liver
         if self.n_tumor and len(self.tumor_cases) == 0:
             raise ValueError("tumor_percent > 0 needs at least one case with tumors")
+        self.guide = guide
+        if guide is not None:
+            self.guide_rng = np.random.default_rng(np.random.SeedSequence(seed).spawn(1)[0])
+            self.moments = ObjectMoments(d, n_slices, self.slice_z, self.box_ptr)
 
     def _randint(self, lo, hi):
         """Uniform integers in [lo, hi] (inclusive, element-wise)."""
@@ -404,11 +411,11 @@ class TrainSampler(object):
         return dict(case=case, pid=self.pid[case], z=z, chans=chans, box=np.concatenate([off, crop], axis=1), clip=clip,
                     flips=flips.astype(np.int32), kind=kind)
 
-    def table(self, slice_offset):
+    def table(self, slice_offset, b=None):
         """The batch as `unetk_lits_batch` takes it: int32 [bs, C + 7] = (resident-store indices of the C channel slices, of
         the label slice, off_y, off_x, crop_h, crop_w, flip_lr, flip_ud), float32 [bs, 2] windows, int64 [bs] case ids.
-        slice_offset: {pid: index of the case's first slice in the resident store}."""
-        b = self.draw()
+        slice_offset: {pid: index of the case's first slice in the resident store}; b: a draw() (default: a new one)."""
+        b = self.draw() if b is None else b
         base = np.array([slice_offset[int(p)] for p in b["pid"]], dtype=np.int64)
         tab = np.empty((self.bs, self.c + 7), dtype=np.int32)
         tab[:, :self.c] = np.where(b["chans"] >= 0, base[:, None] + b["chans"], -1)
@@ -417,37 +424,154 @@ class TrainSampler(object):
         tab[:, self.c + 5:] = b["flips"]
         return tab, b["clip"], b["pid"]
 
+    def guide_objects(self, b):
+        """The spatial-guide objects of the batch `b` (a draw()), gen_train_batch's policy (input_pipeline_g.py:527-599):
+        a sample whose coin falls below spatial_random and whose slice is a tumour slice of its case keeps the tumours whose
+        centre lies in the drawn crop (off <= c < off + crop on both axes); under inner_random a uniformly random non-empty
+        subset of them of size randint(1, n) (the reference raises when none is in the box; that sample gets no guide
+        here); then c' = c - off + s U(-r_c, r_c), s' = max(s U(1 / (1 + r_s), 1 + r_s), min_std), in float64 as the
+        reference computes them.  Vectorised over the batch; the draws come from `guide_rng` alone.
+        Returns (obj_ptr int32 [bs + 1], obj float32 [M, 4] = (cy, cx, sy, sx)), centres relative to the crop."""
+        g, rng, bs = self.guide, self.guide_rng, self.bs
+        coin = rng.random(bs) < g.spatial_random
+        ind = np.where(coin, self.moments.slice_index(b["case"], b["z"]), -1)
+        ptr, c, s = self.moments.gather(ind)
+        sample = np.repeat(np.arange(bs), np.diff(ptr))
+        off, crop = b["box"][sample, :2], b["box"][sample, 2:]
+        keep = np.all((off <= c) & (c < off + crop), axis=1)
+        if g.inner_random:
+            n_in = np.bincount(sample[keep], minlength=bs)
+            k = 1 + np.floor(rng.random(bs) * n_in).astype(np.int64)                # randint(1, n_in); n_in = 0 keeps none
+            key = np.where(keep, rng.random(len(sample)), np.inf)                  # a uniform order of each sample's in-box tumours
+            order = np.lexsort((key, sample))
+            rank = np.empty(len(sample), dtype=np.int64)
+            rank[order] = np.arange(len(sample)) - ptr[sample[order]]
+            keep &= rank < k[sample]
+        sample, c, s, off = sample[keep], c[keep].astype(np.float64), s[keep].astype(np.float64), off[keep]
+        rc, rs = float(g.center_ratio), float(g.stddev_ratio)
+        c = s * rng.uniform(-rc, rc, c.shape) + (c - off)
+        s = np.maximum(s * rng.uniform(1. / (1 + rs), 1. + rs, s.shape), float(g.min_std))
+        obj_ptr = np.concatenate(([0], np.cumsum(np.bincount(sample, minlength=bs)))).astype(np.int32)
+        return obj_ptr, np.concatenate([c, s], axis=1).astype(np.float32).reshape(-1, 4)
 
-def batches(store, data_list, config, training, seed=1234, liver_percent=0., tumor_percent=0., random_scale=(1., 1.)):
+
+class GuidePolicy(object):
+    """The spatial-guide knobs of gen_train_batch (input_pipeline_g.py:527-599): --spatial_random, --spatial_inner_random,
+    --center_random_ratio, --stddev_random_ratio, --min_std (the sampler's stddev floor; the render floor is RENDER_MIN_STD)."""
+
+    def __init__(self, spatial_random=1., inner_random=False, center_ratio=0.2, stddev_ratio=0.4, min_std=2.):
+        self.spatial_random, self.inner_random = float(spatial_random), bool(inner_random)
+        self.center_ratio, self.stddev_ratio, self.min_std = float(center_ratio), float(stddev_ratio), float(min_std)
+
+    @classmethod
+    def from_args(cls, args, spatial_random, inner_random):
+        return cls(spatial_random, inner_random, getattr(args, "center_random_ratio", 0.2),
+                   getattr(args, "stddev_random_ratio", 0.4), getattr(args, "min_std", 2.))
+
+
+class ObjectMoments(object):
+    """The tumours' centres (y, x) and stddevs of a case list as flat float32 tables in CSR over the tumour slices (the
+    order of TrainSampler.boxes), and the reference's `tumor_slices_index.index(z)` as one searchsorted over (case, z)
+    keys."""
+
+    def __init__(self, cases, n_slices=None, slice_z=None, box_ptr=None):
+        cases = list(cases)
+        if n_slices is None:
+            n_slices = np.array([len(c["slices"]) for c in cases], dtype=np.int64)
+            slice_z = np.array([z for c in cases for z in c["tumor_slices_index"]], dtype=np.int64)
+            n_boxes = np.array([len(bx) for c in cases for bx in c["slices"]], dtype=np.int64)
+            box_ptr = np.concatenate(([0], np.cumsum(n_boxes)))
+        self.box_ptr = box_ptr
+        self.centers = np.array([p for c in cases for cs in c["centers"] for p in cs], dtype=np.float32).reshape(-1, 2)
+        self.stddevs = np.array([p for c in cases for ss in c["stddevs"] for p in ss], dtype=np.float32).reshape(-1, 2)
+        if not len(self.centers) == len(self.stddevs) == int(box_ptr[-1]):
+            raise ValueError("tumour centres / stddevs do not match the tumour boxes of the cases")
+        depth = max([int(c["size"][0]) for c in cases] + [int(slice_z.max(initial=-1)) + 1])
+        self.span = depth + 1
+        key = np.repeat(np.arange(len(cases)), n_slices) * self.span + slice_z
+        self.order = np.argsort(key, kind="stable")            # sorted and unique in the shipped meta.json; first match wins
+        self.key = key[self.order]
+
+    def slice_index(self, case, z):
+        """Tumour-slice index (into box_ptr) of slice z of case `case`, element-wise; -1 where z is no tumour slice."""
+        case, z = np.asarray(case, dtype=np.int64), np.asarray(z, dtype=np.int64)
+        if len(self.key) == 0:
+            return np.full(case.shape, -1, dtype=np.int64)
+        q = case * self.span + z
+        pos = np.minimum(np.searchsorted(self.key, q), len(self.key) - 1)
+        hit = (z >= 0) & (z < self.span) & (self.key[pos] == q)
+        return np.where(hit, self.order[pos], -1)
+
+    def gather(self, ind):
+        """The tumours of the tumour slices `ind` (-1 = none): (ptr int64 [len(ind) + 1], centres, stddevs)."""
+        ind = np.asarray(ind, dtype=np.int64)
+        ind = np.where(ind < len(self.box_ptr) - 1, ind, -1)
+        safe = np.maximum(ind, 0)
+        bp = np.append(self.box_ptr, self.box_ptr[-1])                   # safe + 1 stays inside with no tumour slice at all
+        cnt = np.where(ind >= 0, bp[safe + 1] - bp[safe], 0)
+        ptr = np.concatenate(([0], np.cumsum(cnt))).astype(np.int64)
+        idx = np.repeat(bp[safe] - ptr[:-1], cnt) + np.arange(ptr[-1])
+        return ptr, self.centers[idx], self.stddevs[idx]
+
+
+RENDER_MIN_STD = 1.0       # data_processing_train's kwargs.get("min_std", 1.): the flag never reaches it (input_pipeline_g.py:383)
+
+
+def render_guide(tab, obj_ptr, obj, config, channels, src_hw):
+    """sp_guide f32 [bs, H, W, 1] of a batch whose table `tab` is already on the device: obj_ptr / obj travel in ONE
+    non-blocking copy from pinned memory (no host sync), then unetk_lits_spatial_guide on the current stream."""
+    m = len(obj)
+    host = torch.empty(4 * m + len(obj_ptr), dtype=torch.float32, pin_memory=True)
+    host[:4 * m] = torch.from_numpy(obj.reshape(-1))
+    host[4 * m:].view(torch.int32)[:] = torch.from_numpy(obj_ptr)
+    dev = host.to(tab.device, non_blocking=True)
+    return ops.lits_spatial_guide(tab, dev[4 * m:].view(torch.int32), dev[:4 * m].view(m, 4), (config.im_height, config.im_width),
+                                  channels, src_hw, RENDER_MIN_STD)
+
+
+def batches(store, data_list, config, training, seed=1234, liver_percent=0., tumor_percent=0., random_scale=(1., 1.),
+            guide=None):
     """The tf.data pipelines get_dataset_for_train / get_dataset_for_eval_online (:381-430) as a generator of
-    (features, labels) device batches: one vectorised sampler draw on the host, everything else in `unetk_lits_batch`."""
+    (features, labels) device batches: one vectorised sampler draw on the host, everything else in `unetk_lits_batch`.
+    guide (a GuidePolicy): also features["sp_guide"] [bs, H, W, 1] (input_pipeline_g.py:382-412), rendered by
+    `unetk_lits_spatial_guide` from the same device table, so it follows the image's crop and flips."""
     bs = distribution_utils.per_device_batch_size(config.batch_size, config.num_gpus)
     c = config.im_channel
     sampler = TrainSampler(data_list, bs, config, liver_percent, tumor_percent, random_scale if training else (1., 1.),
                            random_window_level=training, random_flip=(getattr(config, "random_flip", 0) if training else 0),
-                           seed=seed)
+                           seed=seed, guide=guide)
     step = 0
     while True:
-        tab, clip, names = sampler.table(store.offset)
-        images, labels = ops.lits_batch(store.im, store.lb, torch.from_numpy(tab).to(store.device),
+        b = sampler.draw()
+        tab, clip, names = sampler.table(store.offset, b)
+        tab_d = torch.from_numpy(tab).to(store.device)
+        images, labels = ops.lits_batch(store.im, store.lb, tab_d,
                                         torch.from_numpy(clip).to(store.device), (config.im_height, config.im_width), c,
                                         LB_SCALE, float(config.noise_scale) if training else 0.0, seed * 7919 + step)
         step += 1
-        yield {"images": images, "names": torch.from_numpy(names)}, labels
+        feats = {"images": images, "names": torch.from_numpy(names)}
+        if guide is not None:
+            obj_ptr, obj = sampler.guide_objects(b)
+            feats["sp_guide"] = render_guide(tab_d, obj_ptr, obj, config, c, store.im.shape[1:])
+        yield feats, labels
 
 
-def batches_eval_3d(store, data_list, config):
+def batches_eval_3d(store, data_list, config, guide=None):
     """--eval_3d online evaluation (input_pipeline_g.py:602-700 `gen_eval_3d_online_batch` + :796-833): every validation
     case is served ONCE, as consecutive batch_size-slice batches over the liver's z range [z1, z2) -- the last batch padded
     with empty slices (index -1: zero image, zero label) -- each slice cropped to the liver box (y1, x1, y2 - y1, x2 - x1) and
     resized to the network size, fixed window, no noise, no flips; `names` carries the case id of the batch.
-    The whole table of a case is laid out in one vectorised step; the gather kernel does the rest."""
+    The whole table of a case is laid out in one vectorised step; the gather kernel does the rest.
+    guide (a GuidePolicy; only its min_std is used): also features["sp_guide"] with EVERY tumour of a tumour slice, centres
+    relative to the liver box, stddevs max(s, min_std) -- no coin, no in-box filter, no perturbation (:679-690); 0.5 on
+    the other slices and on padding."""
     bs = distribution_utils.per_device_batch_size(config.batch_size, config.num_gpus)
     c = config.im_channel
     left = (c - 1) // 2
     ctx = np.arange(-left, c - left)[None, :]
     clip_row = np.array([[50., 500.]], dtype=np.float32) * IM_SCALE
-    for case in data_list:
+    moments = ObjectMoments(data_list) if guide is not None else None
+    for ci, case in enumerate(data_list):
         z1, y1, x1, z2, y2, x2 = case["bbox"]
         depth, pid = case["size"][0], int(case["PID"])
         z = np.concatenate((np.arange(z1, z2), np.full((-(z2 - z1)) % bs, -100)))          # -100: padding (as the reference)
@@ -458,11 +582,19 @@ def batches_eval_3d(store, data_list, config):
         tab[:, :c] = np.where(ok, off + chans, -1)
         tab[:, c] = np.where(z >= 0, off + z, -1)
         tab[:, c + 1:c + 5] = [y1, x1, y2 - y1, x2 - x1]
+        if moments is not None:
+            ptr, centers, stddevs = moments.gather(moments.slice_index(np.full(len(z), ci), z))
+            obj = np.concatenate([centers - np.array([y1, x1], dtype=np.float32),
+                                  np.maximum(stddevs, np.float32(guide.min_std))], axis=1).astype(np.float32)
         for b0 in range(0, len(z), bs):
             t = torch.from_numpy(np.ascontiguousarray(tab[b0:b0 + bs])).to(store.device)
             clip = torch.from_numpy(np.repeat(clip_row, bs, axis=0)).to(store.device)
             images, labels = ops.lits_batch(store.im, store.lb, t, clip, (config.im_height, config.im_width), c, LB_SCALE, 0.0, 0)
-            yield {"images": images, "names": torch.full((bs,), pid, dtype=torch.int64)}, labels
+            feats = {"images": images, "names": torch.full((bs,), pid, dtype=torch.int64)}
+            if moments is not None:
+                p = ptr[b0:b0 + bs + 1]
+                feats["sp_guide"] = render_guide(t, (p - p[0]).astype(np.int32), obj[p[0]:p[-1]], config, c, store.im.shape[1:])
+            yield feats, labels
 
 
 def input_fn(mode, params):
@@ -482,15 +614,26 @@ def input_fn(mode, params):
     rs = tuple(getattr(args, "zoom_scale", (1., 1.)))                        # --zoom_scale (input_pipeline.py:62)
     base_seed = int(getattr(args, "seed", 1234) or 1234)
     seed = base_seed + 1000 * int(params.get("rank", 0))                     # training: every replica its own shard of the stream
+    guided = bool(getattr(args, "use_spatial", False))
+    if guided:
+        # the guided pipeline (input_pipeline_g.py:282-301): the module's own forced shares, one guide channel
+        if int(getattr(args, "guide_channel", 1)) != 1:
+            raise ValueError("the LiTS spatial guide has one channel, got --guide_channel {}".format(args.guide_channel))
+        liver_percent, tumor_percent = LIVER_PERCENT, TUMOR_PERCENT
+        sr = float(getattr(args, "spatial_random", 1.))
+        train_guide = GuidePolicy.from_args(args, sr, getattr(args, "spatial_inner_random", False))
+        eval_guide = GuidePolicy.from_args(args, 0. if sr < 1. else sr, False)
+    else:
+        liver_percent, tumor_percent = getattr(args, "liver_percent", 0.), getattr(args, "tumor_percent", 0.)
+        train_guide = eval_guide = None
     if mode == "train":
-        return batches(store, cases, args, True, seed, getattr(args, "liver_percent", 0.), getattr(args, "tumor_percent", 0.), rs)
+        return batches(store, cases, args, True, seed, liver_percent, tumor_percent, rs, guide=train_guide)
     if mode == "eval_online" and getattr(args, "eval_3d", False):
-        return batches_eval_3d(store, cases, args)
+        return batches_eval_3d(store, cases, args, guide=eval_guide)
     if mode == "eval_online":
         # rank-INDEPENDENT stream: the reference (one process) evaluates one sample, and the evaluator hooks let rank 0 alone
         # decide / save -- every replica must see the same validation data so their best-result state stays identical
-        gen = batches(store, cases, args, False, base_seed + 500, getattr(args, "liver_percent", 0.),
-                      getattr(args, "tumor_percent", 0.))
+        gen = batches(store, cases, args, False, base_seed + 500, liver_percent, tumor_percent, guide=eval_guide)
         n = int(getattr(args, "eval_num_batches_per_epoch", 100))
         return (next(gen) for _ in range(n))
     raise ValueError("lits.input_fn handles the modes `train` and `eval_online`, got {}".format(mode))

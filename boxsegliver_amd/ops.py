@@ -1250,6 +1250,26 @@ def lits_batch(slices, seg_slices, sample_tab, clip, out_hw, channels, lab_scale
     return images, labels
 
 
+def lits_spatial_guide(tab, obj_ptr, obj, out_hw, channels, src_hw, min_std=1.0):
+    """The spatial guide f32 [N, H, W, 1] of a batch (input_pipeline_g.py:382-412, unetk_lits_spatial_guide): tab = the
+    batch's int32 [N, C+7] table of lits_batch (crop boxes and flips), obj_ptr int32 [N + 1] CSR into obj f32 [M, 4] =
+    (cy, cx, sy, sx), centres relative to the crop; stddevs floored at min_std.  Runs on the current stream."""
+    _require_cuda(tab, obj_ptr)
+    n = tab.shape[0]
+    h, w = out_hw
+    assert tab.dtype == torch.int32 and tab.dim() == 2 and tab.shape[1] == channels + 7 and tab.is_contiguous()
+    assert obj_ptr.dtype == torch.int32 and tuple(obj_ptr.shape) == (n + 1,) and obj_ptr.is_contiguous()
+    assert obj.dtype == torch.float32 and obj.dim() == 2 and obj.shape[1] == 4 and obj.is_contiguous()
+    m = obj.shape[0]
+    if m:
+        _require_cuda(obj)
+    d = _abi.LitsGuideDesc(n, h, w, channels, int(src_hw[0]), int(src_hw[1]), m, float(min_std))
+    guide = torch.empty((n, h, w, 1), dtype=torch.float32, device=tab.device)
+    check(_abi.lib().unetk_lits_spatial_guide(ctypes.byref(d), ptr(tab), ptr(obj_ptr), ptr(obj) if m else None, ptr(guide),
+                                              stream_ptr()), "lits_spatial_guide")
+    return guide
+
+
 def adam_step(p, g, m, v, lr_t, beta1, beta2, eps, gscale=1.0, l2=0.0, decoupled_wd=0.0):
     with _timed_hbm("adam_step", p, 7):            # reads p, g, m, v; writes p, m, v
         check(_abi.lib().unetk_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr_t, beta1, beta2, eps, gscale, l2,

@@ -581,6 +581,22 @@ int unetk_png_unfilter(const uint8_t* filtered, int64_t image_stride_bytes, int 
 int unetk_lits_batch(const unetk_lits_desc* d, const uint16_t* slices, const uint8_t* seg_slices,
                      const int32_t* sample_tab, const float* clip, float* images, int32_t* labels,
                      void* stream);
+/* Spatial guide of the guided LiTS pipeline (DataLoader/Liver/input_pipeline_g.py:382-412, utils/image_ops.py:396-434) for
+ * a whole batch: per sample create_spatial_guide_2d(crop size, centres, max(stddevs, min_std)) -> resize_bilinear
+ * (align_corners) to H x W -> g / 2 + 0.5, without rendering the crop-resolution guide: every output pixel evaluates
+ * max_k exp(-((py - cy)^2 / (2 sy^2) + (px - cx)^2 / (2 sx^2))) at its 4 bilinear corners and lerps.  sample_tab is the
+ * batch's unetk_lits_batch table (its crop box and flip columns are used, with the same clamp and flips, so guide and
+ * image line up); obj_ptr int32 [N + 1] (CSR, entries clamped into [0, n_obj]); obj float [n_obj][4] = (cy, cx, sy, sx),
+ * centres relative to the crop, in source pixels, 16-byte aligned (may be NULL when n_obj = 0); guide f32 [N, H, W, 1].
+ * A sample without objects is exactly 0.5 (the reference's false_fn).  min_std > 0. */
+typedef struct unetk_lits_guide_desc {
+  int32_t N, H, W, C; /* C: image channels of sample_tab (rows of C + 7) */
+  int32_t src_h, src_w;
+  int32_t n_obj;
+  float min_std; /* render-time stddev floor (1.0 in the reference) */
+} unetk_lits_guide_desc;
+int unetk_lits_spatial_guide(const unetk_lits_guide_desc* d, const int32_t* sample_tab, const int32_t* obj_ptr,
+                             const float* obj, float* guide, void* stream);
 
 /* ---------------------------------------------------------------- optimiser  core/solver.py:204-243
  * tf.train.AdamOptimizer on a flat parameter buffer.  g' = g*gscale + l2*p  (slim.l2_regularizer
