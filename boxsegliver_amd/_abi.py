@@ -68,6 +68,7 @@ P = c_void_p
 _SIGNATURES = {
     "unetk_lits_batch": (c_int, [POINTER(LitsDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "unetk_lits_spatial_guide": (c_int, [POINTER(LitsGuideDesc), P, P, P, P, P]),
+    "unetk_lits_context": (c_int, [P, c_int64, c_int, P, c_int, c_int, P, P, P, P]),
     "unetk_abi_version": (c_int, []),
     "unetk_nan_watch": (c_int, [P, P, c_int32, P]),
     "unetk_png_unfilter": (c_int, [P, c_int64, c_int, c_int, c_int, c_int, P, c_int64, P, P]),
@@ -166,6 +167,8 @@ _SIGNATURES = {
     "unetk_component_mask": (c_int, [P, c_int, c_int, c_int, c_int32, P, P]),
     "unetk_mask_counts_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "unetk_mask_counts": (c_int, [P, P, c_int, c_int, c_int, P, P, c_size_t, P]),
+    "unetk_slice_hist_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "unetk_slice_hist": (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, c_int, P, P, c_size_t, P]),
     "unetk_surface3d": (c_int, [P, c_int, c_int, c_int, P, P, c_int, P]),
     "unetk_edt3d_sq_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "unetk_edt3d_sq": (c_int, [P, c_int, c_int, c_int, P, c_double, c_double, c_double, P, P, c_size_t, P]),

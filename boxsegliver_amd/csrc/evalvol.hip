@@ -372,6 +372,160 @@ __global__ __launch_bounds__(EV_BLOCK) void sdist_final_kernel(const double* __r
   }
 }
 
+// ---------------------------------------------------------------- per-slice HU histograms (the context guide's feature rows)
+// Every count is an integer atomic (LDS per block, then global), so the counts do not depend on the order the atomics run
+// in; the densities are then one correctly rounded fp64 division chain per bin, as numpy computes them.
+constexpr int SH_MAX_BINS = 1024;
+
+// bin of an HU value through the host's lookup table (numpy's edge rule already applied); -1 = not counted
+__device__ __forceinline__ int sh_bin(int v, const int32_t* __restrict__ lut, int lut_lo, int lut_n) {
+  const int d = v - lut_lo;
+  return (unsigned)d < (unsigned)lut_n ? lut[d] : -1;
+}
+
+__global__ __launch_bounds__(EV_BLOCK) void sh_zero_kernel(int32_t* __restrict__ p, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * EV_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * EV_BLOCK) p[i] = 0;
+}
+
+// grid (blocks per slice, D): counts[k][0, bins) over labels >= 1; with TRAIN also counts[k][bins, 2 bins) over labels == 2
+template <bool TRAIN>
+__global__ __launch_bounds__(EV_BLOCK) void sh_slice_kernel(const int16_t* __restrict__ vol, const uint8_t* __restrict__ lab,
+                                                            int HW, const int32_t* __restrict__ lut, int lut_lo, int lut_n,
+                                                            int bins, int32_t* __restrict__ counts) {
+  extern __shared__ int sh_hist[];
+  const int nh = TRAIN ? 2 * bins : bins;
+  for (int j = threadIdx.x; j < nh; j += EV_BLOCK) sh_hist[j] = 0;
+  __syncthreads();
+  const int64_t base = (int64_t)blockIdx.y * HW;
+  for (int i = blockIdx.x * EV_BLOCK + threadIdx.x; i < HW; i += gridDim.x * EV_BLOCK) {
+    const int l = lab[base + i];
+    if (l == 0) continue;
+    const int b = sh_bin(vol[base + i], lut, lut_lo, lut_n);
+    if (b < 0) continue;
+    atomicAdd(sh_hist + b, 1);
+    if (TRAIN && l == 2) atomicAdd(sh_hist + bins + b, 1);
+  }
+  __syncthreads();
+  int32_t* row = counts + (int64_t)blockIdx.y * 2 * bins;
+  for (int j = threadIdx.x; j < nh; j += EV_BLOCK)
+    if (sh_hist[j]) atomicAdd(row + j, sh_hist[j]);
+}
+
+// eval mode: the tumour voxels (label == 2) as union-find roots of their own; zmax = last slice of a root's component
+__global__ __launch_bounds__(EV_BLOCK) void sh_label_init_kernel(const uint8_t* __restrict__ lab, int n, int* __restrict__ label,
+                                                                 int* __restrict__ zmax) {
+  const int i = blockIdx.x * EV_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  label[i] = lab[i] == 2 ? i : -1;
+  zmax[i] = -1;
+}
+
+// 18-connectivity (ndi.generate_binary_structure(3, 2)): the 9 face and edge neighbours that precede a voxel in linear
+// order; the other 9 are covered from their side
+__global__ __launch_bounds__(EV_BLOCK) void sh_merge18_kernel(const uint8_t* __restrict__ lab, int D, int H, int W,
+                                                              int* __restrict__ label) {
+  const int n = D * H * W, HW = H * W;
+  const int i = blockIdx.x * EV_BLOCK + threadIdx.x;
+  if (i >= n || lab[i] != 2) return;
+  const int x = i % W, y = (i / W) % H, z = i / HW;
+  if (x > 0 && lab[i - 1] == 2) lc_union(label, i, i - 1);
+  if (y > 0) {
+    if (lab[i - W] == 2) lc_union(label, i, i - W);
+    if (x > 0 && lab[i - W - 1] == 2) lc_union(label, i, i - W - 1);
+    if (x < W - 1 && lab[i - W + 1] == 2) lc_union(label, i, i - W + 1);
+  }
+  if (z > 0) {
+    const int j = i - HW;
+    if (lab[j] == 2) lc_union(label, i, j);
+    if (y > 0 && lab[j - W] == 2) lc_union(label, i, j - W);
+    if (y < H - 1 && lab[j + W] == 2) lc_union(label, i, j + W);
+    if (x > 0 && lab[j - 1] == 2) lc_union(label, i, j - 1);
+    if (x < W - 1 && lab[j + 1] == 2) lc_union(label, i, j + 1);
+  }
+}
+
+// every voxel points straight at its root (the component's minimum linear index, so its first slice is root / HW); the
+// last slice by atomicMax at the root, one per wave for the lanes that share the wave's first root (their highest lane
+// holds their largest z: consecutive lanes are consecutive voxels)
+__global__ __launch_bounds__(EV_BLOCK) void sh_flatten_kernel(int n, int HW, int* __restrict__ label, int* __restrict__ zmax) {
+  const int i = blockIdx.x * EV_BLOCK + threadIdx.x;
+  int r = -1;
+  if (i < n) {
+    const int l = label[i];
+    if (l >= 0) {
+      r = lc_find(label, l);
+      label[i] = r;
+    }
+  }
+  const int lead = __builtin_amdgcn_readfirstlane(r >= 0 ? r : 0x7fffffff);
+  const unsigned long long same = __ballot(r == lead);
+  if (r < 0) return;
+  if (r != lead)
+    atomicMax(zmax + r, i / HW);
+  else if ((int)__lane_id() == 63 - __clzll((long long)same))
+    atomicMax(zmax + r, i / HW);
+}
+
+// array_kits.guide_pixel_list(middle, tile_guide): the voxels of component c on its middle slice m add their bins to
+// every row of c's extent [z0, z1) -- as a difference array over z: +1 at z0, -1 at z1 (diff has D + 1 rows)
+__global__ __launch_bounds__(EV_BLOCK) void sh_mid_kernel(const int16_t* __restrict__ vol, int n, int HW,
+                                                          const int* __restrict__ label, const int* __restrict__ zmax,
+                                                          const int32_t* __restrict__ lut, int lut_lo, int lut_n, int bins,
+                                                          int32_t* __restrict__ diff) {
+  const int i = blockIdx.x * EV_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const int r = label[i];
+  if (r < 0) return;
+  const int z0 = r / HW, z1 = zmax[r] + 1;
+  if (i / HW != (z1 - z0 - 1) / 2 + z0) return;
+  const int b = sh_bin(vol[i], lut, lut_lo, lut_n);
+  if (b < 0) return;
+  atomicAdd(diff + (int64_t)z0 * bins + b, 1);
+  atomicAdd(diff + (int64_t)z1 * bins + b, -1);
+}
+
+// counts[k][bins + b] = prefix sum of diff[0..k][b]: one thread per bin, rows in order
+__global__ __launch_bounds__(EV_BLOCK) void sh_prefix_kernel(const int32_t* __restrict__ diff, int D, int bins,
+                                                             int32_t* __restrict__ counts) {
+  const int b = blockIdx.x * EV_BLOCK + threadIdx.x;
+  if (b >= bins) return;
+  int run = 0;
+  for (int k = 0; k < D; ++k) {
+    run += diff[(int64_t)k * bins + b];
+    counts[(int64_t)k * 2 * bins + bins + b] = run;
+  }
+}
+
+// one block per row: np.histogram(density=True) = (count / db) / total in fp64, rounded to fp32; an empty half is 0
+// (nan_to_num of 0 / 0)
+__global__ __launch_bounds__(EV_BLOCK) void sh_density_kernel(const int32_t* __restrict__ counts, const double* __restrict__ db,
+                                                              int bins, float* __restrict__ out) {
+  __shared__ long long red[2][EV_BLOCK];
+  const int32_t* row = counts + (int64_t)blockIdx.x * 2 * bins;
+  long long s0 = 0, s1 = 0;
+  for (int j = threadIdx.x; j < bins; j += EV_BLOCK) {
+    s0 += row[j];
+    s1 += row[bins + j];
+  }
+  red[0][threadIdx.x] = s0;
+  red[1][threadIdx.x] = s1;
+  __syncthreads();
+  for (int h = EV_BLOCK / 2; h > 0; h >>= 1) {
+    if (threadIdx.x < h) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + h];
+      red[1][threadIdx.x] += red[1][threadIdx.x + h];
+    }
+    __syncthreads();
+  }
+  const long long t0 = red[0][0], t1 = red[1][0];
+  float* o = out + (int64_t)blockIdx.x * 2 * bins;
+  for (int j = threadIdx.x; j < 2 * bins; j += EV_BLOCK) {
+    const long long t = j < bins ? t0 : t1;
+    const int b = j < bins ? j : j - bins;
+    o[j] = t > 0 ? (float)(((double)row[j] / db[b]) / (double)t) : 0.f;
+  }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- C ABI
@@ -505,6 +659,63 @@ extern "C" int unetk_surface_dist(const uint8_t* surf, const double* dist2, int 
   UNETK_LAUNCH(sdist_partial_kernel, dim3(rows), dim3(EV_BLOCK), 0, st, surf, dist2, n, (double*)ws);
   UNETK_LAUNCH_CHECK();
   UNETK_LAUNCH(sdist_final_kernel, dim3(1), dim3(EV_BLOCK), 0, st, (const double*)ws, rows, out);
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
+static inline size_t sh_counts_bytes(int D, int bins) { return ev_align((size_t)D * 2 * bins * 4); }
+
+extern "C" size_t unetk_slice_hist_ws_bytes(int D, int H, int W, int bins, int mode) {
+  if (ev_dims(D, H, W) != UNETK_OK || bins <= 0 || bins > SH_MAX_BINS || (mode != 0 && mode != 1)) return 0;
+  size_t b = sh_counts_bytes(D, bins);
+  if (mode == 1) b += 2 * ev_align((size_t)D * H * W * 4) + ev_align((size_t)(D + 1) * bins * 4);
+  return b;
+}
+
+extern "C" int unetk_slice_hist(const int16_t* vol, const uint8_t* lab, int D, int H, int W, int mode, const int32_t* lut,
+                                int lut_lo, int lut_n, const double* db, int bins, float* out, void* ws, size_t ws_bytes,
+                                void* stream) {
+  const int dims = ev_dims(D, H, W);
+  if (dims != UNETK_OK) return dims;
+  UNETK_REQUIRE(vol && lab && lut && db && out && ws && unetk_aligned16(ws) && unetk_aligned8(db));
+  UNETK_REQUIRE((((uintptr_t)vol) & 1u) == 0 && (((uintptr_t)lut) & 3u) == 0 && (((uintptr_t)out) & 3u) == 0);
+  UNETK_REQUIRE((mode == 0 || mode == 1) && bins > 0 && bins <= SH_MAX_BINS && lut_n > 0);
+  if (ws_bytes < unetk_slice_hist_ws_bytes(D, H, W, bins, mode)) return UNETK_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int n = D * H * W, HW = H * W;
+  int32_t* counts = (int32_t*)ws;
+  const int64_t ncounts = (int64_t)D * 2 * bins;
+  UNETK_LAUNCH(sh_zero_kernel, dim3(ev_blocks(ncounts)), dim3(EV_BLOCK), 0, st, counts, ncounts);
+  UNETK_LAUNCH_CHECK();
+  const dim3 sgrid((unsigned)min(64, max(1, (HW + EV_BLOCK * 16 - 1) / (EV_BLOCK * 16))), (unsigned)D);
+  if (mode == 0) {
+    UNETK_LAUNCH(sh_slice_kernel<true>, sgrid, dim3(EV_BLOCK), 2 * bins * 4, st, vol, lab, HW, lut, lut_lo, lut_n, bins, counts);
+    UNETK_LAUNCH_CHECK();
+  } else {
+    char* p = (char*)ws + sh_counts_bytes(D, bins);
+    int* label = (int*)p;
+    int* zmax = (int*)(p + ev_align((size_t)n * 4));
+    int32_t* diff = (int32_t*)(p + 2 * ev_align((size_t)n * 4));
+    const int64_t ndiff = (int64_t)(D + 1) * bins;
+    const int g = ev_grid1(n);
+    UNETK_LAUNCH(sh_slice_kernel<false>, sgrid, dim3(EV_BLOCK), bins * 4, st, vol, lab, HW, lut, lut_lo, lut_n, bins, counts);
+    UNETK_LAUNCH_CHECK();
+    UNETK_LAUNCH(sh_zero_kernel, dim3(ev_blocks(ndiff)), dim3(EV_BLOCK), 0, st, diff, ndiff);
+    UNETK_LAUNCH_CHECK();
+    UNETK_LAUNCH(sh_label_init_kernel, dim3(g), dim3(EV_BLOCK), 0, st, lab, n, label, zmax);
+    UNETK_LAUNCH_CHECK();
+    UNETK_LAUNCH(sh_merge18_kernel, dim3(g), dim3(EV_BLOCK), 0, st, lab, D, H, W, label);
+    UNETK_LAUNCH_CHECK();
+    UNETK_LAUNCH(sh_flatten_kernel, dim3(g), dim3(EV_BLOCK), 0, st, n, HW, label, zmax);
+    UNETK_LAUNCH_CHECK();
+    UNETK_LAUNCH(sh_mid_kernel, dim3(g), dim3(EV_BLOCK), 0, st, vol, n, HW, (const int*)label, (const int*)zmax, lut, lut_lo,
+                 lut_n, bins, diff);
+    UNETK_LAUNCH_CHECK();
+    UNETK_LAUNCH(sh_prefix_kernel, dim3((bins + EV_BLOCK - 1) / EV_BLOCK), dim3(EV_BLOCK), 0, st, (const int32_t*)diff, D, bins,
+                 counts);
+    UNETK_LAUNCH_CHECK();
+  }
+  UNETK_LAUNCH(sh_density_kernel, dim3(D), dim3(EV_BLOCK), 0, st, (const int32_t*)counts, db, bins, out);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }

@@ -127,6 +127,32 @@ __global__ __launch_bounds__(256) void lits_guide_kernel(unetk_lits_guide_desc d
   }
 }
 
+// Context rows of a batch (input_pipeline_g.py:527-550, :672-680): sample s reads the resident row of its label slice
+// (column C of the batch table); a failed coin or a padding slice (-1) gives zeros.  With noise (--hist_noise) the row is
+// updated IN PLACE first, row = f32(f64(row) + noise[s]) -- the reference adds the noise into a view of its cached table --
+// so the noise builds up over the run.  One thread per column walks the samples in order: a slice drawn twice in one
+// batch takes both updates, the second sample sees the first one's result.
+__global__ __launch_bounds__(256) void lits_context_kernel(float* __restrict__ table, int64_t n_rows, int F,
+                                                           const int32_t* __restrict__ tab, int N, int C,
+                                                           const int32_t* __restrict__ take, const double* __restrict__ noise,
+                                                           float* __restrict__ out) {
+  const int f = blockIdx.x * 256 + threadIdx.x;
+  if (f >= F) return;
+  for (int s = 0; s < N; ++s) {
+    const int32_t idx = tab[(int64_t)s * (C + 7) + C];
+    float v = 0.f;
+    if (take[s] && idx >= 0 && idx < n_rows) {
+      float* p = table + (int64_t)idx * F + f;
+      v = *p;
+      if (noise) {
+        v = (float)((double)v + noise[(int64_t)s * F + f]);
+        *p = v;
+      }
+    }
+    out[(int64_t)s * F + f] = v;
+  }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -244,6 +270,16 @@ extern "C" int unetk_lits_spatial_guide(const unetk_lits_guide_desc* d, const in
   if (grid > 65536) grid = 65536;
   UNETK_LAUNCH(lits_guide_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, *d, sample_tab, obj_ptr,
                reinterpret_cast<const float4*>(obj), guide);
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
+extern "C" int unetk_lits_context(float* table, int64_t n_rows, int F, const int32_t* sample_tab, int N, int C,
+                                  const int32_t* take, const double* noise, float* out, void* stream) {
+  UNETK_REQUIRE(table && sample_tab && take && out && n_rows > 0 && F > 0 && N > 0 && C > 0 && C <= 8);
+  UNETK_REQUIRE(noise == nullptr || (((uintptr_t)noise) & 7u) == 0);
+  UNETK_LAUNCH(lits_context_kernel, dim3((F + 255) / 256), dim3(256), 0, (hipStream_t)stream, table, n_rows, F, sample_tab, N, C,
+               take, noise, out);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }

@@ -91,3 +91,65 @@ def nii_3d_to_png(in_path, out_path, only_meta=False):
     with (dst / "meta.json").open("w") as f:
         json.dump(metas, f)
     return metas
+
+
+HIST_RANGE = (-200, 250)        # extract.py's (GRAY_MIN + 50, GRAY_MAX - 50) of its own GRAY_MIN / GRAY_MAX = -250 / 300
+
+
+def dump_hist_feature(in_path, out_path, mode, bins=100, xrng=HIST_RANGE, device=None):
+    """extract.py:237-375 (`dump_hist_feature` for mode "train", `dump_hist_feature_v2` for mode "eval", as
+    `run_dump_hist_feature` calls them): for every volume-<PID>.nii[.gz] of in_path (labels next to it as segmentation-<PID>)
+    the per-slice histogram rows float32 [depth, 2 bins] -> <out_path>/hist/<mode>/<PID:03d>.npy, the files the guided
+    pipeline reads with --use_context --context_list hist 200.  The rows are computed on the device (ops.slice_hist,
+    bit-identical to the reference's numpy loop); reading the NIfTI files stays on the host.  Returns the written paths."""
+    import torch
+
+    from .. import ops
+    if mode not in ("train", "eval"):
+        raise ValueError("mode must be `train` or `eval`, got {}".format(mode))
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    src = Path(in_path)
+    dst = Path(out_path) / "hist" / mode
+    dst.mkdir(parents=True, exist_ok=True)
+    files = sorted(list(src.glob("volume-*.nii")) + list(src.glob("volume-*.nii.gz")),
+                   key=lambda x: int(x.name.split(".")[0].split("-")[-1]))
+    written = []
+    for vol_case in files:
+        pid = int(vol_case.name.split(".")[0].split("-")[-1])
+        _, volume = nii_kits.read_lits(pid, "vol", vol_case)
+        _, labels = nii_kits.read_lits(pid, "lab", vol_case.parent / vol_case.name.replace("volume", "segmentation"))
+        assert volume.shape == labels.shape, "Vol{} vs Lab{}".format(volume.shape, labels.shape)
+        vol_d = torch.from_numpy(np.ascontiguousarray(volume, dtype=np.int16)).to(device)
+        lab_d = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.uint8)).to(device)
+        rows = ops.slice_hist(vol_d, lab_d, mode, bins, xrng).cpu().numpy()
+        out = dst / "{:03d}.npy".format(pid)
+        np.save(out, rows)
+        written.append(out)
+    return written
+
+
+def main(argv=None):
+    """python -m boxsegliver_amd.data.extract png <nii_dir> <lits_root>/png
+       python -m boxsegliver_amd.data.extract hist <nii_dir> <lits_root>/feat [--mode train eval]"""
+    import argparse
+    parser = argparse.ArgumentParser(prog="python -m boxsegliver_amd.data.extract", description=__doc__.split("\n")[0])
+    sub = parser.add_subparsers(dest="cmd", required=True)
+    p = sub.add_parser("png", help="NIfTI volumes -> PNG slices + meta.json")
+    p.add_argument("nii_dir")
+    p.add_argument("out_dir")
+    p.add_argument("--only_meta", action="store_true")
+    h = sub.add_parser("hist", help="NIfTI volumes -> per-slice histogram context features <out>/hist/<mode>/<PID>.npy")
+    h.add_argument("nii_dir")
+    h.add_argument("feat_dir")
+    h.add_argument("--mode", nargs="+", choices=("train", "eval"), default=["train", "eval"])
+    a = parser.parse_args(argv)
+    if a.cmd == "png":
+        nii_3d_to_png(a.nii_dir, a.out_dir, a.only_meta)
+    else:
+        for mode in a.mode:
+            for path in dump_hist_feature(a.nii_dir, a.feat_dir, mode):
+                print(path)
+
+
+if __name__ == "__main__":
+    main()

@@ -330,10 +330,12 @@ class TrainSampler(object):
         [10, 50] / [500, 540] HU-units x IM_SCALE when random_window_level else fixed 50 / 500; independent flip coins.
 
     `guide` (a GuidePolicy) adds the spatial-guide objects of the guided pipeline (`guide_objects`); their draws come from
-    a generator of their own, so a guided run draws the same slices, crops, windows and flips as an unguided one."""
+    a generator of their own, so a guided run draws the same slices, crops, windows and flips as an unguided one.
+    `context` (bool): the context guide's coin (`guide_coin`) comes from that same generator, its --hist_noise normals from
+    `noise_rng`, a sibling spawned from the same seed."""
 
     def __init__(self, data_list, batch_size, config, liver_percent=0., tumor_percent=0., random_scale=(1., 1.),
-                 random_window_level=False, random_flip=0, seed=None, guide=None):
+                 random_window_level=False, random_flip=0, seed=None, guide=None, context=False):
         self.bs, self.c = int(batch_size), int(config.im_channel)
         self.target = np.array([config.im_height, config.im_width], dtype=np.float64)
         self.scale = (float(random_scale[0]), float(random_scale[1]))
@@ -356,8 +358,11 @@ class TrainSampler(object):
         if self.n_tumor and len(self.tumor_cases) == 0:
             raise ValueError("tumor_percent > 0 needs at least one case with tumors")
         self.guide = guide
-        if guide is not None:
+        if guide is not None or context:
             self.guide_rng = np.random.default_rng(np.random.SeedSequence(seed).spawn(1)[0])
+        if context:     # --hist_noise normals: a sibling of the guide generator, so the noise leaves the guides' draws alone
+            self.noise_rng = np.random.default_rng(np.random.SeedSequence(seed).spawn(2)[1])
+        if guide is not None:
             self.moments = ObjectMoments(d, n_slices, self.slice_z, self.box_ptr)
 
     def _randint(self, lo, hi):
@@ -424,16 +429,23 @@ class TrainSampler(object):
         tab[:, self.c + 5:] = b["flips"]
         return tab, b["clip"], b["pid"]
 
-    def guide_objects(self, b):
+    def guide_coin(self, spatial_random):
+        """One guide coin per sample, random() < spatial_random (input_pipeline_g.py:528-529): the spatial guide and the
+        context of a sample read the SAME coin, the first draw of the batch from `guide_rng`."""
+        return self.guide_rng.random(self.bs) < spatial_random
+
+    def guide_objects(self, b, coin=None):
         """The spatial-guide objects of the batch `b` (a draw()), gen_train_batch's policy (input_pipeline_g.py:527-599):
         a sample whose coin falls below spatial_random and whose slice is a tumour slice of its case keeps the tumours whose
         centre lies in the drawn crop (off <= c < off + crop on both axes); under inner_random a uniformly random non-empty
         subset of them of size randint(1, n) (the reference raises when none is in the box; that sample gets no guide
         here); then c' = c - off + s U(-r_c, r_c), s' = max(s U(1 / (1 + r_s), 1 + r_s), min_std), in float64 as the
-        reference computes them.  Vectorised over the batch; the draws come from `guide_rng` alone.
+        reference computes them.  Vectorised over the batch; the draws come from `guide_rng` alone.  coin: the batch's
+        `guide_coin` when the context guide shares it (default: drawn here, the same first draw).
         Returns (obj_ptr int32 [bs + 1], obj float32 [M, 4] = (cy, cx, sy, sx)), centres relative to the crop."""
         g, rng, bs = self.guide, self.guide_rng, self.bs
-        coin = rng.random(bs) < g.spatial_random
+        if coin is None:
+            coin = self.guide_coin(g.spatial_random)
         ind = np.where(coin, self.moments.slice_index(b["case"], b["z"]), -1)
         ptr, c, s = self.moments.gather(ind)
         sample = np.repeat(np.arange(bs), np.diff(ptr))
@@ -529,17 +541,111 @@ def render_guide(tab, obj_ptr, obj, config, channels, src_hw):
                                   channels, src_hw, RENDER_MIN_STD)
 
 
+CONTEXT_FEATURES = ("hist",)           # glcm / ct_conv contexts are not built
+
+
+def parse_context_list(context_list):
+    """--context_list name length [name length ...] -> [(name, length)] (input_pipeline_g.py:264-271)."""
+    items = list(context_list or [])
+    if not items:
+        raise ValueError("--use_context needs --context_list, e.g. --context_list hist 200")
+    if len(items) % 2 != 0:
+        raise ValueError("context_list is not paired: {}".format(items))
+    pairs = [(str(items[2 * i]), int(items[2 * i + 1])) for i in range(len(items) // 2)]
+    for name, _ in pairs:
+        if name not in CONTEXT_FEATURES:
+            raise ValueError("context feature `{}` is not supported; the LiTS pipeline builds {}".format(
+                name, ", ".join(CONTEXT_FEATURES)))
+    return pairs
+
+
+def hist_preprocess(feat, hist_scale):
+    """feature_ops.hist_preprocess: feat *= hist_scale (a float32 table times a Python float stays float32)."""
+    return (feat * hist_scale).astype(np.float32)
+
+
+def load_context_rows(lits_root, cases, offset, n_rows, context_list, mode_dir, hist_scale):
+    """The host copy of the resident context table: float32 [n_rows, F] in SliceStore order (row offset[pid] + z), each
+    case's <lits_root>/feat/<name>/<mode_dir>/<PID:03d>.npy preprocessed and concatenated over the context list
+    (input_pipeline_g.py:531-543)."""
+    feat_root = Path(lits_root) / "feat"
+    width = sum(n for _, n in context_list)
+    rows = np.zeros((n_rows, width), dtype=np.float32)
+    for case in cases:
+        pid, depth = int(case["PID"]), int(case["size"][0])
+        col = 0
+        for name, f_len in context_list:
+            path = feat_root / name / mode_dir / "{:03d}.npy".format(pid)
+            if not path.exists():
+                raise FileNotFoundError("missing context features {}; make them with `python -m boxsegliver_amd.data.extract "
+                                        "{} <dir of volume-*.nii> {}`".format(path, name, feat_root))
+            feat = np.load(path, allow_pickle=False)
+            if feat.ndim != 2 or feat.shape[1] != f_len:
+                raise ValueError("{}: feature length mismatch {} vs {}".format(path, feat.shape[1:], f_len))
+            if feat.shape[0] != depth:
+                raise ValueError("{}: {} rows for a case of {} slices".format(path, feat.shape[0], depth))
+            rows[offset[pid]:offset[pid] + depth, col:col + f_len] = hist_preprocess(feat, hist_scale)
+            col += f_len
+    return rows
+
+
+class ContextGuide(object):
+    """The context guide of one pipeline: the host copy of its table (load_context_rows), the coin's spatial_random and,
+    in training with --hist_noise, the noise scale.  `fresh(device)` uploads a new resident table -- one per generator,
+    as the reference caches per generator -- which `unetk_lits_context` reads and, under noise, updates in place."""
+
+    def __init__(self, rows, spatial_random=1., noise_scale=None):
+        self.rows, self.spatial_random = rows, float(spatial_random)
+        self.noise_scale = None if noise_scale is None else float(noise_scale)
+
+    def fresh(self, device):
+        return torch.from_numpy(self.rows).to(device)
+
+
+def upload_pinned(parts, device):
+    """Numpy arrays -> device tensors in ONE non-blocking copy from pinned memory (no host sync); each part 16-byte aligned."""
+    sizes, off = [], 0
+    for a in parts:
+        sizes.append(off)
+        off += (a.nbytes + 15) & ~15
+    host = torch.empty(max(off, 16), dtype=torch.uint8, pin_memory=True)
+    hv = host.numpy()
+    for a, o in zip(parts, sizes):
+        hv[o:o + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+    dev = host.to(device, non_blocking=True)
+    return [dev[o:o + a.nbytes].view(torch.from_numpy(a[:0]).dtype).view(a.shape) for a, o in zip(parts, sizes)]
+
+
+def guides(tab_d, take, obj_ptr, obj, noise, table, config, channels, src_hw):
+    """The guided batch's device work after one upload: (sp_guide or None, context)."""
+    parts = [take.astype(np.int32)] + ([noise] if noise is not None else []) + \
+        ([obj.reshape(-1, 4), obj_ptr] if obj is not None else [])
+    dev = upload_pinned(parts, tab_d.device)
+    take_d, rest = dev[0], dev[1:]
+    noise_d = rest.pop(0) if noise is not None else None
+    sp = None
+    if obj is not None:
+        sp = ops.lits_spatial_guide(tab_d, rest[1], rest[0], (config.im_height, config.im_width), channels, src_hw,
+                                    RENDER_MIN_STD)
+    return sp, ops.lits_context(table, tab_d, channels, take_d, noise_d)
+
+
 def batches(store, data_list, config, training, seed=1234, liver_percent=0., tumor_percent=0., random_scale=(1., 1.),
-            guide=None):
+            guide=None, context=None):
     """The tf.data pipelines get_dataset_for_train / get_dataset_for_eval_online (:381-430) as a generator of
     (features, labels) device batches: one vectorised sampler draw on the host, everything else in `unetk_lits_batch`.
     guide (a GuidePolicy): also features["sp_guide"] [bs, H, W, 1] (input_pipeline_g.py:382-412), rendered by
-    `unetk_lits_spatial_guide` from the same device table, so it follows the image's crop and flips."""
+    `unetk_lits_spatial_guide` from the same device table, so it follows the image's crop and flips.
+    context (a ContextGuide): also features["context"] [bs, F] (input_pipeline_g.py:527-550): the row of each sample's
+    slice where its guide coin (shared with the spatial guide) succeeds, zeros elsewhere; with a noise scale, N(0, 1) x
+    scale is added into the resident row first, so the noise builds up as in the reference.  Coin, guide objects and
+    normals go up in one pinned copy."""
     bs = distribution_utils.per_device_batch_size(config.batch_size, config.num_gpus)
     c = config.im_channel
     sampler = TrainSampler(data_list, bs, config, liver_percent, tumor_percent, random_scale if training else (1., 1.),
                            random_window_level=training, random_flip=(getattr(config, "random_flip", 0) if training else 0),
-                           seed=seed, guide=guide)
+                           seed=seed, guide=guide, context=context is not None)
+    table = context.fresh(store.device) if context is not None else None
     step = 0
     while True:
         b = sampler.draw()
@@ -550,13 +656,22 @@ def batches(store, data_list, config, training, seed=1234, liver_percent=0., tum
                                         LB_SCALE, float(config.noise_scale) if training else 0.0, seed * 7919 + step)
         step += 1
         feats = {"images": images, "names": torch.from_numpy(names)}
-        if guide is not None:
+        if context is not None:
+            coin = sampler.guide_coin(context.spatial_random)
+            obj_ptr, obj = sampler.guide_objects(b, coin) if guide is not None else (None, None)
+            noise = None
+            if training and context.noise_scale is not None:
+                noise = sampler.noise_rng.normal(0., 1., (bs, table.shape[1])) * context.noise_scale
+            sp, feats["context"] = guides(tab_d, coin, obj_ptr, obj, noise, table, config, c, store.im.shape[1:])
+            if sp is not None:
+                feats["sp_guide"] = sp
+        elif guide is not None:
             obj_ptr, obj = sampler.guide_objects(b)
             feats["sp_guide"] = render_guide(tab_d, obj_ptr, obj, config, c, store.im.shape[1:])
         yield feats, labels
 
 
-def batches_eval_3d(store, data_list, config, guide=None):
+def batches_eval_3d(store, data_list, config, guide=None, context=None):
     """--eval_3d online evaluation (input_pipeline_g.py:602-700 `gen_eval_3d_online_batch` + :796-833): every validation
     case is served ONCE, as consecutive batch_size-slice batches over the liver's z range [z1, z2) -- the last batch padded
     with empty slices (index -1: zero image, zero label) -- each slice cropped to the liver box (y1, x1, y2 - y1, x2 - x1) and
@@ -564,13 +679,15 @@ def batches_eval_3d(store, data_list, config, guide=None):
     The whole table of a case is laid out in one vectorised step; the gather kernel does the rest.
     guide (a GuidePolicy; only its min_std is used): also features["sp_guide"] with EVERY tumour of a tumour slice, centres
     relative to the liver box, stddevs max(s, min_std) -- no coin, no in-box filter, no perturbation (:679-690); 0.5 on
-    the other slices and on padding."""
+    the other slices and on padding.
+    context (a ContextGuide of eval rows): also features["context"], the row of every slice, zeros on padding (:672-680)."""
     bs = distribution_utils.per_device_batch_size(config.batch_size, config.num_gpus)
     c = config.im_channel
     left = (c - 1) // 2
     ctx = np.arange(-left, c - left)[None, :]
     clip_row = np.array([[50., 500.]], dtype=np.float32) * IM_SCALE
     moments = ObjectMoments(data_list) if guide is not None else None
+    table = context.fresh(store.device) if context is not None else None
     for ci, case in enumerate(data_list):
         z1, y1, x1, z2, y2, x2 = case["bbox"]
         depth, pid = case["size"][0], int(case["PID"])
@@ -591,7 +708,14 @@ def batches_eval_3d(store, data_list, config, guide=None):
             clip = torch.from_numpy(np.repeat(clip_row, bs, axis=0)).to(store.device)
             images, labels = ops.lits_batch(store.im, store.lb, t, clip, (config.im_height, config.im_width), c, LB_SCALE, 0.0, 0)
             feats = {"images": images, "names": torch.full((bs,), pid, dtype=torch.int64)}
-            if moments is not None:
+            if context is not None:
+                p = ptr[b0:b0 + bs + 1] if moments is not None else None
+                sp, feats["context"] = guides(t, np.ones(bs, dtype=np.int32), None if p is None else (p - p[0]).astype(np.int32),
+                                              None if p is None else obj[p[0]:p[-1]], None, table, config, c,
+                                              store.im.shape[1:])
+                if sp is not None:
+                    feats["sp_guide"] = sp
+            elif moments is not None:
                 p = ptr[b0:b0 + bs + 1]
                 feats["sp_guide"] = render_guide(t, (p - p[0]).astype(np.int32), obj[p[0]:p[-1]], config, c, store.im.shape[1:])
             yield feats, labels
@@ -615,25 +739,44 @@ def input_fn(mode, params):
     base_seed = int(getattr(args, "seed", 1234) or 1234)
     seed = base_seed + 1000 * int(params.get("rank", 0))                     # training: every replica its own shard of the stream
     guided = bool(getattr(args, "use_spatial", False))
+    use_context = bool(getattr(args, "use_context", False))
+    sr = float(getattr(args, "spatial_random", 1.))
     if guided:
         # the guided pipeline (input_pipeline_g.py:282-301): the module's own forced shares, one guide channel
         if int(getattr(args, "guide_channel", 1)) != 1:
             raise ValueError("the LiTS spatial guide has one channel, got --guide_channel {}".format(args.guide_channel))
-        liver_percent, tumor_percent = LIVER_PERCENT, TUMOR_PERCENT
-        sr = float(getattr(args, "spatial_random", 1.))
         train_guide = GuidePolicy.from_args(args, sr, getattr(args, "spatial_inner_random", False))
         eval_guide = GuidePolicy.from_args(args, 0. if sr < 1. else sr, False)
     else:
-        liver_percent, tumor_percent = getattr(args, "liver_percent", 0.), getattr(args, "tumor_percent", 0.)
         train_guide = eval_guide = None
+    if guided or use_context:
+        liver_percent, tumor_percent = LIVER_PERCENT, TUMOR_PERCENT
+    else:
+        liver_percent, tumor_percent = getattr(args, "liver_percent", 0.), getattr(args, "tumor_percent", 0.)
+    context = None
+    if use_context:
+        # the context table: train rows for training, eval rows for both eval_online modes (input_pipeline_g.py:734, :815)
+        context_list = parse_context_list(getattr(args, "context_list", None))
+        hist_scale = float(getattr(args, "hist_scale", 20.))
+        ckey = ("lits_context", mode == "train", tuple(context_list), hist_scale)
+        if ckey not in params:
+            params[ckey] = load_context_rows(root, cases, store.offset, store.im.shape[0], context_list,
+                                             "train" if mode == "train" else "eval", hist_scale)
+        rows = params[ckey]
+        if mode == "train":
+            noise = float(getattr(args, "hist_noise_scale", 0.002)) if getattr(args, "hist_noise", False) else None
+            context = ContextGuide(rows, sr, noise)
+        else:
+            context = ContextGuide(rows, 0. if sr < 1. else sr)
     if mode == "train":
-        return batches(store, cases, args, True, seed, liver_percent, tumor_percent, rs, guide=train_guide)
+        return batches(store, cases, args, True, seed, liver_percent, tumor_percent, rs, guide=train_guide, context=context)
     if mode == "eval_online" and getattr(args, "eval_3d", False):
-        return batches_eval_3d(store, cases, args, guide=eval_guide)
+        return batches_eval_3d(store, cases, args, guide=eval_guide, context=context)
     if mode == "eval_online":
         # rank-INDEPENDENT stream: the reference (one process) evaluates one sample, and the evaluator hooks let rank 0 alone
         # decide / save -- every replica must see the same validation data so their best-result state stays identical
-        gen = batches(store, cases, args, False, base_seed + 500, liver_percent, tumor_percent, guide=eval_guide)
+        gen = batches(store, cases, args, False, base_seed + 500, liver_percent, tumor_percent, guide=eval_guide,
+                      context=context)
         n = int(getattr(args, "eval_num_batches_per_epoch", 100))
         return (next(gen) for _ in range(n))
     raise ValueError("lits.input_fn handles the modes `train` and `eval_online`, got {}".format(mode))
@@ -641,19 +784,49 @@ def input_fn(mode, params):
 
 def input_fn_eval(mode, params):
     """input_pipeline.py:228-234 for ModeKeys.EVAL / PREDICT: a python generator over the NIfTI volumes of the validation
-    fold (paths in meta.json's vol_case / lab_case, relative to params["proj_root"]).  No device work here: the
-    evaluator uploads each slab and does mirroring / accumulation / argmax on the GPU (evaluators/evaluator_liver.py)."""
+    fold (paths in meta.json's vol_case / lab_case, relative to params["proj_root"]).  The evaluator uploads each slab and
+    does mirroring / accumulation / argmax on the GPU (evaluators/evaluator_liver.py); with --use_context (without
+    --use_spatial) each case's eval context rows are uploaded once here and the slabs carry device views of them."""
     args = params["args"]
     cases = collect_datasets(params["lits_root"], args.test_fold, mode, filter_tumor_size=getattr(args, "filter_size", 0),
                              filter_only_liver_in_val=params.get("filter_only_liver_in_val", True))
     if len(cases) == 0:
         raise ValueError("No valid dataset found!")
     proj_root = params.get("proj_root", ".")
+    context = None
+    if getattr(args, "use_context", False) and not getattr(args, "use_spatial", False):
+        # input_pipeline_g.py:910-980 (get_dataset_for_eval_image): every slab carries its slices' eval context rows
+        context = EvalContext(params["lits_root"], parse_context_list(getattr(args, "context_list", None)),
+                              float(getattr(args, "hist_scale", 20.)), params.get("device"))
     if getattr(args, "eval_in_patches", False):
+        if context is not None:
+            raise ValueError("--eval_in_patches does not serve the context guide")
         return get_dataset_for_eval_patches(cases, config=args, proj_root=proj_root)
     if params.get("whole_slices", False):
-        return get_dataset_for_eval_image(cases, args, proj_root)
-    return get_dataset_for_eval_image_v2(cases, args, proj_root)
+        return get_dataset_for_eval_image(cases, args, proj_root, context=context)
+    return get_dataset_for_eval_image_v2(cases, args, proj_root, context=context)
+
+
+class EvalContext(object):
+    """The eval context rows of the offline evaluators: `case(case, pads)` loads a case's rows (load_context_rows,
+    <lits_root>/feat/<name>/eval/), appends `pads` zero rows at the end of the whole volume as the reference does, and
+    uploads them ONCE; the slabs then carry device views of it."""
+
+    def __init__(self, lits_root, context_list, hist_scale, device=None):
+        self.root, self.context_list, self.hist_scale = lits_root, context_list, hist_scale
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+
+    def case(self, case, pads):
+        depth = int(case["size"][0])
+        rows = load_context_rows(self.root, [case], {int(case["PID"]): 0}, depth, self.context_list, "eval", self.hist_scale)
+        rows = np.concatenate((rows, np.zeros((pads, rows.shape[1]), rows.dtype)), axis=0)
+        return torch.from_numpy(rows).to(self.device)
+
+
+def slab_context_rows(z0, n, batch_size):
+    """input_pipeline_g.py:966-969: the slab starting at centre slice z0 + idx reads context_val[sid:sid + batch_size] with
+    sid = z0 + idx, for idx = 0, batch_size, ... < n (z0: the first evaluated slice of the volume)."""
+    return [(z0 + idx, z0 + idx + batch_size) for idx in range(0, n, batch_size)]
 
 
 # ------------------------------------------------------------------------------------------------- offline evaluation
@@ -772,23 +945,29 @@ def _mirrored(eval_batch, config):
             yield dict(eval_batch, images=np.flip(eval_batch["images"], axis=axes), mirror=variant), None
 
 
-def _slabs(volume, batch_size, lhc, rhc, head, config):
+def _slabs(volume, batch_size, lhc, rhc, head, config, context=None, z0=0):
     """Serve a (y, x, z) volume as batch_size-slice slabs with (lhc, rhc) context slices per sample, each followed by its
-    mirrored copies.  `head` = the constant entries of every slab's feature dict."""
+    mirrored copies.  `head` = the constant entries of every slab's feature dict.  context (a device tensor of the case's
+    rows): every slab -- and its mirrored copies, unflipped -- also carries context[sid:sid + batch_size] of
+    slab_context_rows(z0, ...)."""
     n = volume.shape[-1] - lhc - rhc
     assert n % batch_size == 0, "Wrong padding"
     win = np.lib.stride_tricks.sliding_window_view(volume, lhc + rhc + 1, axis=-1)      # [y, x, n, c] without copying
-    for idx in range(0, n, batch_size):
+    rows = slab_context_rows(z0, n, batch_size)
+    for k, idx in enumerate(range(0, n, batch_size)):
         slab = dict(head, images=np.ascontiguousarray(np.moveaxis(win[:, :, idx:idx + batch_size], 2, 0)), mirror=0)
+        if context is not None:
+            slab["context"] = context[rows[k][0]:rows[k][1]]
         yield slab, None
         for item in _mirrored(slab, config):
             yield item
 
 
-def get_dataset_for_eval_image_v2(data_list, config, proj_root="."):
+def get_dataset_for_eval_image_v2(data_list, config, proj_root=".", context=None):
     """input_pipeline.py:615-668: per case the liver box is cut from the NIfTI volume, padded in z to whole batches,
     resized to the network size, and served as batch_size-slice slabs (each followed by its mirrored copies under
-    --eval_mirror); a case ends with (None, (segmentation, vol_path, pads, bbox, resize))."""
+    --eval_mirror); a case ends with (None, (segmentation, vol_path, pads, bbox, resize)).  context (an EvalContext):
+    every slab also carries its slices' eval context rows as a device tensor (input_pipeline_g.py:910-980)."""
     align = 16 if getattr(config, "model", "UNet") != "DenseUNet" else 32
     padding, padding_z = 25, 0
     batch_size = config.batch_size
@@ -804,13 +983,14 @@ def get_dataset_for_eval_image_v2(data_list, config, proj_root="."):
         volume = np.pad(volume, ((0, 0), (0, 0), (0, pads)))
         if resize:
             volume = cv2_resize_linear(volume, pshape)      # dsize = (im_height, im_width), as the reference passes it
-        for item in _slabs(volume, batch_size, lhc, rhc, {"names": pid}, config):
+        ctx = context.case(case, pads) if context is not None else None
+        for item in _slabs(volume, batch_size, lhc, rhc, {"names": pid}, config, ctx, bbox[2]):
             yield item
         yield None, (segmentation, vol_path, pads, bbox, resize)
 
 
-def get_dataset_for_eval_image(data_list, config, proj_root=".", test_data=False):
-    """input_pipeline_li.py:398-456: whole slices (no liver crop)."""
+def get_dataset_for_eval_image(data_list, config, proj_root=".", test_data=False, context=None):
+    """input_pipeline_li.py:398-456: whole slices (no liver crop); context as in get_dataset_for_eval_image_v2."""
     from . import nii_kits
     batch_size = config.batch_size
     c = config.im_channel
@@ -832,7 +1012,8 @@ def get_dataset_for_eval_image(data_list, config, proj_root=".", test_data=False
         volume = np.pad(volume, ((0, 0), (0, 0), (lhc, pads + rhc)))       # context + the zero slices of the last slab
         if resize:
             volume = cv2_resize_linear(volume, pshape)
-        for item in _slabs(volume, batch_size, lhc, rhc, {"names": case["PID"]}, config):
+        ctx = context.case(case, pads) if context is not None else None
+        for item in _slabs(volume, batch_size, lhc, rhc, {"names": case["PID"]}, config, ctx, 0):
             yield item
         yield None, (segmentation, seg_path, pads, (0, 0, 0, w - 1, h - 1, ori_d - 1), resize)
 

@@ -1183,6 +1183,56 @@ def largest_component3d(mask):
     return out
 
 
+_HIST_TABLES = {}
+
+
+def hist_bin_table(bins=100, xrng=(-200, 250)):
+    """The host side of unetk_slice_hist for integer HU values: (lut int32 [n], lut_lo, db float64 [bins]).  lut[v - lut_lo]
+    is the bin np.histogram(v, bins, range=xrng) puts the integer v in (asked of numpy itself, value by value, so its edge
+    rule and closed last bin hold exactly), -1 where it counts nothing; db = np.diff of its float64 edges."""
+    import math
+    import numpy as np
+    key = (int(bins), float(xrng[0]), float(xrng[1]))
+    if key not in _HIST_TABLES:
+        lo, hi = int(math.ceil(key[1])), int(math.floor(key[2]))
+        if hi < lo:
+            raise ValueError("the range {} holds no integer value".format(xrng))
+        lut = np.full(hi - lo + 1, -1, dtype=np.int32)
+        for v in range(lo, hi + 1):
+            h, edges = np.histogram(np.array([v], dtype=np.int16), bins=key[0], range=key[1:])
+            if h.any():
+                lut[v - lo] = int(np.argmax(h))
+        _HIST_TABLES[key] = (lut, lo, np.diff(edges).astype(np.float64))
+    return _HIST_TABLES[key]
+
+
+def slice_hist(vol, lab, mode, bins=100, xrng=(-200, 250)):
+    """float32 [D, 2 bins] per-slice density histograms of a case (unetk_slice_hist): vol int16 [D, H, W] HU, lab uint8
+    [D, H, W] on the device; mode "train" (second half: lab == 2 of the slice) or "eval" (second half: the middle slices of
+    the 18-connected tumours covering the slice) -- extract.py dump_hist_feature / dump_hist_feature_v2, bit for bit."""
+    import numpy as np
+    _require_cuda(vol, lab)
+    if mode not in ("train", "eval"):
+        raise ValueError("mode must be `train` or `eval`, got {}".format(mode))
+    if vol.dtype != torch.int16 or lab.dtype != torch.uint8 or vol.dim() != 3 or vol.shape != lab.shape:
+        raise ValueError("int16 volume and uint8 labels of one [D, H, W] shape expected, got {} {} and {} {}".format(
+            vol.dtype, tuple(vol.shape), lab.dtype, tuple(lab.shape)))
+    vol, lab = vol.contiguous(), lab.contiguous()
+    d, h, w = vol.shape
+    lut, lut_lo, db = hist_bin_table(bins, xrng)
+    tabs = torch.from_numpy(np.concatenate([db.view(np.int32), lut])).to(vol.device)     # one upload: db (8-aligned), lut
+    m = 0 if mode == "train" else 1
+    out = torch.empty((d, 2 * bins), dtype=torch.float32, device=vol.device)
+    lib = _abi.lib()
+    nbytes = lib.unetk_slice_hist_ws_bytes(d, h, w, int(bins), m)
+    if nbytes == 0:
+        raise ValueError("unsupported slice_hist shape {} / bins {}".format(tuple(vol.shape), bins))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=vol.device)
+    check(lib.unetk_slice_hist(ptr(vol), ptr(lab), d, h, w, m, ptr(tabs[2 * bins:]), lut_lo, len(lut), ptr(tabs), int(bins),
+                               ptr(out), ptr(ws), nbytes, stream_ptr()), "slice_hist")
+    return out
+
+
 def mask_counts_async(a, b):
     """int64 device tensor {|A|, |B|, |A and B|, |A or B|} of two same-shape masks (no host read)."""
     a, b = _mask3d(a), _mask3d(b)
@@ -1268,6 +1318,25 @@ def lits_spatial_guide(tab, obj_ptr, obj, out_hw, channels, src_hw, min_std=1.0)
     check(_abi.lib().unetk_lits_spatial_guide(ctypes.byref(d), ptr(tab), ptr(obj_ptr), ptr(obj) if m else None, ptr(guide),
                                               stream_ptr()), "lits_spatial_guide")
     return guide
+
+
+def lits_context(table, tab, channels, take, noise=None):
+    """The context rows f32 [N, F] of a batch (unetk_lits_context): row s = table[tab[s, channels]] where take[s] != 0 and
+    the index is a row of `table`, else zeros.  noise f64 [N, F]: the table rows are first updated in place,
+    row = f32(f64(row) + noise[s]), samples in order.  All on the device; runs on the current stream."""
+    _require_cuda(table, tab, take)
+    n = tab.shape[0]
+    assert table.dtype == torch.float32 and table.dim() == 2 and table.is_contiguous()
+    assert tab.dtype == torch.int32 and tab.dim() == 2 and tab.shape[1] == channels + 7 and tab.is_contiguous()
+    assert take.dtype == torch.int32 and tuple(take.shape) == (n,) and take.is_contiguous()
+    f = table.shape[1]
+    if noise is not None:
+        _require_cuda(noise)
+        assert noise.dtype == torch.float64 and tuple(noise.shape) == (n, f) and noise.is_contiguous()
+    out = torch.empty((n, f), dtype=torch.float32, device=tab.device)
+    check(_abi.lib().unetk_lits_context(ptr(table), table.shape[0], f, ptr(tab), n, channels, ptr(take),
+                                        ptr(noise) if noise is not None else None, ptr(out), stream_ptr()), "lits_context")
+    return out
 
 
 def adam_step(p, g, m, v, lr_t, beta1, beta2, eps, gscale=1.0, l2=0.0, decoupled_wd=0.0):

@@ -553,6 +553,20 @@ int unetk_edt3d_sq(const uint8_t* feature, int D, int H, int W, const int32_t* b
 size_t unetk_surface_dist_ws_bytes(int D, int H, int W);
 int unetk_surface_dist(const uint8_t* surf, const double* dist2, int D, int H, int W, double* out, void* ws,
                        size_t ws_bytes, void* stream);
+/* Per-slice HU histograms of a case, the context guide's feature rows (DataLoader/Liver/extract.py:237-375,
+ * dump_hist_feature / dump_hist_feature_v2).  vol int16 [D,H,W] HU, lab uint8 [D,H,W]; out f32 [D, 2 bins]:
+ *   columns [0, bins): the values of slice k where lab >= 1;
+ *   columns [bins, 2 bins): mode 0 (train) the values of slice k where lab == 2; mode 1 (eval) the values of every
+ *   18-connected tumour component c (lab == 2) whose z-extent [z0, z1) covers k, taken on c's middle slice
+ *   m = (z1 - z0 - 1) / 2 + z0 (array_kits.guide_pixel_list(middle, tile_guide)).
+ * Bins through the host's table: value v counts in bin lut[v - lut_lo] when 0 <= v - lut_lo < lut_n and that entry is >= 0
+ * (the host applies np.histogram's edge rule); each half-row is np.histogram(density=True) = (count / db[b]) / total in
+ * fp64 with db f64 [bins] the bin widths, rounded to f32, and 0 when the half is empty.  Counts are integer atomics, so the
+ * rows are bit-reproducible.  bins <= 1024; ws 16-byte aligned, at least unetk_slice_hist_ws_bytes (mode 1 holds two int32
+ * per voxel for the union-find). */
+size_t unetk_slice_hist_ws_bytes(int D, int H, int W, int bins, int mode);
+int unetk_slice_hist(const int16_t* vol, const uint8_t* lab, int D, int H, int W, int mode, const int32_t* lut, int lut_lo,
+                     int lut_n, const double* db, int bins, float* out, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------- LiTS training batch  
  * DataLoader/Liver/input_pipeline.py:243-284 `data_processing_train` for a whole batch, gathering from decoded slices
@@ -597,6 +611,13 @@ typedef struct unetk_lits_guide_desc {
 } unetk_lits_guide_desc;
 int unetk_lits_spatial_guide(const unetk_lits_guide_desc* d, const int32_t* sample_tab, const int32_t* obj_ptr,
                              const float* obj, float* guide, void* stream);
+/* Context rows of a batch of the guided LiTS pipeline (DataLoader/Liver/input_pipeline_g.py:527-550, :672-680):
+ * out f32 [N, F] row s = table[sample_tab[s][C]] (the label-slice column of the unetk_lits_batch table), zeros where
+ * take[s] == 0 (the guide coin failed) or the index is outside [0, n_rows) (padding, -1).  noise f64 [N, F] (NULL = none):
+ * the resident row is first updated in place, row = f32(f64(row) + noise[s]), samples in order (the reference's noise
+ * accumulates in its cached table).  table f32 [n_rows, F]. */
+int unetk_lits_context(float* table, int64_t n_rows, int F, const int32_t* sample_tab, int N, int C, const int32_t* take,
+                       const double* noise, float* out, void* stream);
 
 /* ---------------------------------------------------------------- optimiser  core/solver.py:204-243
  * tf.train.AdamOptimizer on a flat parameter buffer.  g' = g*gscale + l2*p  (slim.l2_regularizer
