@@ -169,6 +169,9 @@ _SIGNATURES = {
     "unetk_mask_counts": (c_int, [P, P, c_int, c_int, c_int, P, P, c_size_t, P]),
     "unetk_slice_hist_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "unetk_slice_hist": (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, c_int, P, P, c_size_t, P]),
+    "unetk_guide_components_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "unetk_guide_components": (c_int, [P, P, c_int, c_int, c_int, P, P, c_size_t, P]),
+    "unetk_guide_render": (c_int, [P, c_int, c_int, c_int, c_float, P, P]),
     "unetk_surface3d": (c_int, [P, c_int, c_int, c_int, P, P, c_int, P]),
     "unetk_edt3d_sq_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "unetk_edt3d_sq": (c_int, [P, c_int, c_int, c_int, P, c_double, c_double, c_double, P, P, c_size_t, P]),

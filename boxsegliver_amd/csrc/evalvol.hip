@@ -526,6 +526,194 @@ __global__ __launch_bounds__(EV_BLOCK) void sh_density_kernel(const int32_t* __r
   }
 }
 
+// ---------------------------------------------------------------- guide propagation: tumour components of one slice
+// (DataLoader/Liver/input_pipeline_g.py:1246-1318, the `last_pred` setter of EvalImage3DLoader).  The tumour mask is
+// argmax(acc) == 2 (lowest index on ties, as head_predict_kernel); its 4-connected components are the labels of
+// lc_init / lc_merge / lc_flatten run with D = 1.  Roots are numbered in increasing linear index (scipy's label order) by
+// one block; per component integer atomics fill a row and a column histogram and a packed (guide value, -index) max; one
+// thread per component then reads its box, the exact medians and the median absolute deviations off the histograms.
+constexpr int GC_ROW = 12;            // int32 words per table row (include/unetk.h)
+constexpr int GC_ENUM = 1024;         // threads of the numbering block
+
+__global__ __launch_bounds__(EV_BLOCK) void gc_mask_kernel(const float* __restrict__ acc, int n, uint8_t* __restrict__ mask) {
+  const int i = blockIdx.x * EV_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const float a0 = acc[3 * (int64_t)i], a1 = acc[3 * (int64_t)i + 1], a2 = acc[3 * (int64_t)i + 2];
+  const float b = a1 > a0 ? a1 : a0;          // strict comparisons: the first index wins ties (np.argmax)
+  mask[i] = a2 > b ? 1 : 0;
+}
+
+// cid[root] = rank of the root among all roots (scipy's label - 1); rows [0, cap) get {root, area}; head = {count, overflow}.
+// One block walks the image in tiles of GC_ENUM consecutive pixels (coalesced reads): a ballot per wave, the waves' counts
+// in LDS, so each root's rank is the roots before its tile + before its wave + before its lane -- increasing linear order.
+__global__ __launch_bounds__(GC_ENUM) void gc_enum_kernel(int n, const int* __restrict__ label, const int* __restrict__ cnt,
+                                                          int cap, int* __restrict__ cid, int32_t* __restrict__ table) {
+  __shared__ int wsum[GC_ENUM / 64];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  int base = 0;                                  // roots in the tiles before this one (the same in every thread)
+  for (int i0 = 0; i0 < n; i0 += GC_ENUM) {
+    const int i = i0 + t;
+    const bool root = i < n && label[i] == i;
+    const unsigned long long b = __ballot(root);
+    if (lane == 0) wsum[wv] = __popcll(b);
+    __syncthreads();
+    int before = base, total = base;
+    for (int j = 0; j < GC_ENUM / 64; ++j) {
+      const int c = wsum[j];
+      before += j < wv ? c : 0;
+      total += c;
+    }
+    __syncthreads();                             // wsum is rewritten by the next tile
+    if (root) {
+      const int k = before + __popcll(b & ((1ull << lane) - 1ull));
+      cid[i] = k;
+      if (k < cap) {
+        table[4 + (int64_t)k * GC_ROW] = i;
+        table[4 + (int64_t)k * GC_ROW + 1] = cnt[i];
+      }
+    }
+    base = total;
+  }
+  if (t == 0) {
+    table[0] = base;
+    table[1] = base > cap ? 1 : 0;
+    table[2] = 0;
+    table[3] = 0;
+  }
+}
+
+// zero the histograms and the peak key of the components that exist: a fixed grid strides over min(count, cap)
+constexpr int GC_ZERO_BLOCKS = 256;
+__global__ __launch_bounds__(EV_BLOCK) void gc_zero_kernel(const int32_t* __restrict__ table, int cap, int H, int W,
+                                                           int* __restrict__ hrow, int* __restrict__ hcol,
+                                                           unsigned long long* __restrict__ peak) {
+  const int count = min(table[0], cap);
+  for (int k = blockIdx.x; k < count; k += gridDim.x) {
+    for (int j = threadIdx.x; j < H; j += EV_BLOCK) hrow[(int64_t)k * H + j] = 0;
+    for (int j = threadIdx.x; j < W; j += EV_BLOCK) hcol[(int64_t)k * W + j] = 0;
+    if (threadIdx.x == 0) peak[k] = 0ull;
+  }
+}
+
+__device__ __forceinline__ unsigned int gc_order_bits(float g) {     // float -> unsigned key with the same order
+  const unsigned int u = __float_as_uint(g);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ float gc_order_float(unsigned int k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// per pixel of a component: row / column histogram counts and the packed max (guide value, then the smaller index); the
+// lanes that share the wave's first (component, row) add once for all of them, as lc_flatten does for the sizes
+__global__ __launch_bounds__(EV_BLOCK) void gc_accum_kernel(int n, int H, int W, const int* __restrict__ label,
+                                                            const int* __restrict__ cid, const float* __restrict__ guide,
+                                                            int cap, int* __restrict__ hrow, int* __restrict__ hcol,
+                                                            unsigned long long* __restrict__ peak) {
+  const int i = blockIdx.x * EV_BLOCK + threadIdx.x;
+  int k = -1, y = 0, x = 0;
+  unsigned long long key = 0ull;
+  if (i < n) {
+    const int r = label[i];
+    if (r >= 0) {
+      const int c = cid[r];
+      if (c < cap) {
+        k = c;
+        y = i / W;
+        x = i - y * W;
+        key = ((unsigned long long)gc_order_bits(guide[i]) << 32) | (unsigned long long)(0xffffffffu - (unsigned int)i);
+      }
+    }
+  }
+  const int ry = k >= 0 ? k * H + y : 0x7fffffff;   // < cap * H < 2^31 (unetk_guide_components checks it)
+  const int lead = __builtin_amdgcn_readfirstlane(ry);
+  const unsigned long long same = __ballot(k >= 0 && ry == lead);
+  const int kl = __builtin_amdgcn_readfirstlane(k >= 0 ? k : 0x7fffffff);
+  const bool in_lead = k >= 0 && k == kl;
+  unsigned long long m = in_lead ? key : 0ull;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long other = __shfl_xor(m, o);
+    m = other > m ? other : m;
+  }
+  const int first = __ffsll((long long)__ballot(in_lead)) - 1;
+  if (k < 0) return;
+  if (ry != lead)
+    atomicAdd(hrow + ry, 1);
+  else if ((int)__lane_id() == __ffsll((long long)same) - 1)
+    atomicAdd(hrow + ry, __popcll(same));
+  atomicAdd(hcol + (int64_t)k * W + x, 1);
+  if (!in_lead)
+    atomicMax(peak + k, key);
+  else if ((int)__lane_id() == first)
+    atomicMax(peak + k, m);
+}
+
+// the bin of the p-th smallest value (0-based) of a histogram over [lo, hi]
+__device__ __forceinline__ int gc_select(const int* __restrict__ h, int lo, int hi, int p) {
+  int acc = 0;
+  for (int r = lo; r <= hi; ++r) {
+    acc += h[r];
+    if (acc > p) return r;
+  }
+  return hi;
+}
+
+// median and 1.4826 x median absolute deviation of the values a histogram holds, as array_kits.compute_robust_moments
+// computes them in float32: twice the median c2 is an integer, and so is twice each distance |2 r - c2| / 2, walked outward
+__device__ __forceinline__ void gc_moments(const int* __restrict__ h, int lo, int hi, int cnt, float* ctr, float* std) {
+  const int c2 = gc_select(h, lo, hi, (cnt - 1) / 2) + gc_select(h, lo, hi, cnt / 2);
+  const int pa = (cnt - 1) / 2, pb = cnt / 2;
+  int da = -1, db = -1, acc = 0;
+  for (int d2 = c2 & 1; db < 0; d2 += 2) {
+    const int ra = (c2 - d2) / 2, rb = (c2 + d2) / 2;
+    int c = 0;
+    if (ra >= lo && ra <= hi) c += h[ra];
+    if (d2 > 0 && rb >= lo && rb <= hi) c += h[rb];
+    if (da < 0 && acc + c > pa) da = d2;
+    if (acc + c > pb) db = d2;
+    acc += c;
+    if (d2 > 2 * (hi - lo) + 2) {            // cannot happen for a consistent histogram; keeps the loop finite
+      if (da < 0) da = d2;
+      db = d2;
+    }
+  }
+  *ctr = (float)c2 * 0.5f;
+  const float mad = ((float)da * 0.5f + (float)db * 0.5f) / 2.f;
+  *std = 1.4826f * mad;
+}
+
+__global__ __launch_bounds__(EV_BLOCK) void gc_final_kernel(int H, int W, int cap, const int* __restrict__ hrow,
+                                                            const int* __restrict__ hcol,
+                                                            const unsigned long long* __restrict__ peak,
+                                                            int32_t* __restrict__ table) {
+  const int k = blockIdx.x * EV_BLOCK + threadIdx.x;
+  if (k >= min(table[0], cap)) return;
+  int32_t* row = table + 4 + (int64_t)k * GC_ROW;
+  const int area = row[1];
+  const int* hr = hrow + (int64_t)k * H;
+  const int* hc = hcol + (int64_t)k * W;
+  int y0 = 0, y1 = H - 1, x0 = 0, x1 = W - 1;
+  while (y0 < H - 1 && hr[y0] == 0) ++y0;
+  while (y1 > y0 && hr[y1] == 0) --y1;
+  while (x0 < W - 1 && hc[x0] == 0) ++x0;
+  while (x1 > x0 && hc[x1] == 0) --x1;
+  float cy, cx, sy, sx;
+  gc_moments(hr, y0, y1, area, &cy, &sy);
+  gc_moments(hc, x0, x1, area, &cx, &sx);
+  const unsigned long long p = peak[k];
+  row[2] = y0;
+  row[3] = x0;
+  row[4] = y1;
+  row[5] = x1;
+  row[6] = (int32_t)(0xffffffffu - (unsigned int)(p & 0xffffffffull));
+  row[7] = __float_as_int(gc_order_float((unsigned int)(p >> 32)));
+  row[8] = __float_as_int(cy);
+  row[9] = __float_as_int(cx);
+  row[10] = __float_as_int(sy);
+  row[11] = __float_as_int(sx);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- C ABI
@@ -716,6 +904,62 @@ extern "C" int unetk_slice_hist(const int16_t* vol, const uint8_t* lab, int D, i
     UNETK_LAUNCH_CHECK();
   }
   UNETK_LAUNCH(sh_density_kernel, dim3(D), dim3(EV_BLOCK), 0, st, (const int32_t*)counts, db, bins, out);
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
+// ---------------------------------------------------------------- guide propagation
+static inline size_t gc_n_bytes(int H, int W) { return ev_align((size_t)H * W * 4); }
+
+extern "C" size_t unetk_guide_components_ws_bytes(int H, int W, int cap) {
+  if (ev_dims(1, H, W) != UNETK_OK || cap <= 0 || cap > (1 << 16)) return 0;
+  if ((int64_t)cap * H >= ((int64_t)1 << 31) || (int64_t)cap * W >= ((int64_t)1 << 31)) return 0;
+  const size_t nb = gc_n_bytes(H, W);
+  return 3 * nb + ev_align((size_t)H * W) + 256 + ev_align((size_t)cap * H * 4) + ev_align((size_t)cap * W * 4) +
+         ev_align((size_t)cap * 8);
+}
+
+extern "C" int unetk_guide_components(const float* acc, const float* guide, int H, int W, int cap, int32_t* table, void* ws,
+                                      size_t ws_bytes, void* stream) {
+  const int dims = ev_dims(1, H, W);
+  if (dims != UNETK_OK) return dims;
+  UNETK_REQUIRE(acc && guide && table && ws && unetk_aligned16(ws) && cap > 0 && cap <= (1 << 16));
+  UNETK_REQUIRE((int64_t)cap * H < ((int64_t)1 << 31) && (int64_t)cap * W < ((int64_t)1 << 31));    // int histogram indices
+  UNETK_REQUIRE((((uintptr_t)table) & 3u) == 0 && (((uintptr_t)acc) & 3u) == 0 && (((uintptr_t)guide) & 3u) == 0);
+  if (ws_bytes < unetk_guide_components_ws_bytes(H, W, cap)) return UNETK_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int n = H * W;
+  const size_t nb = gc_n_bytes(H, W);
+  char* p = (char*)ws;
+  int* label = (int*)p;                                   // the layout of unetk_largest_component: label, then size
+  int* cnt = (int*)(p + nb);
+  int* cid = (int*)(p + 2 * nb);
+  uint8_t* mask = (uint8_t*)(p + 3 * nb);
+  char* q = p + 3 * nb + ev_align((size_t)n);
+  unsigned long long* best = (unsigned long long*)q;      // lc_init's scalars, unused here
+  int32_t* info = (int32_t*)(q + 16);
+  int* hrow = (int*)(q + 256);
+  int* hcol = (int*)(q + 256 + ev_align((size_t)cap * H * 4));
+  unsigned long long* peak = (unsigned long long*)(q + 256 + ev_align((size_t)cap * H * 4) + ev_align((size_t)cap * W * 4));
+  const int g = ev_grid1(n);
+  UNETK_LAUNCH(gc_mask_kernel, dim3(g), dim3(EV_BLOCK), 0, st, acc, n, mask);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(lc_init_kernel, dim3(g), dim3(EV_BLOCK), 0, st, (const uint8_t*)mask, n, label, cnt, best, info);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(lc_merge_kernel, dim3(g), dim3(EV_BLOCK), 0, st, (const uint8_t*)mask, 1, H, W, label);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(lc_flatten_kernel, dim3(g), dim3(EV_BLOCK), 0, st, n, label, cnt);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(gc_enum_kernel, dim3(1), dim3(GC_ENUM), 0, st, n, (const int*)label, (const int*)cnt, cap, cid, table);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(gc_zero_kernel, dim3(min(cap, GC_ZERO_BLOCKS)), dim3(EV_BLOCK), 0, st, (const int32_t*)table, cap, H, W, hrow,
+               hcol, peak);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(gc_accum_kernel, dim3(g), dim3(EV_BLOCK), 0, st, n, H, W, (const int*)label, (const int*)cid, guide, cap, hrow,
+               hcol, peak);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(gc_final_kernel, dim3((cap + EV_BLOCK - 1) / EV_BLOCK), dim3(EV_BLOCK), 0, st, H, W, cap, (const int*)hrow,
+               (const int*)hcol, (const unsigned long long*)peak, table);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }

@@ -127,6 +127,22 @@ __global__ __launch_bounds__(256) void lits_guide_kernel(unetk_lits_guide_desc d
   }
 }
 
+// Guide of one slice of the propagation loop (input_pipeline_g.py:1427-1440): create_gaussian_distribution_v2 over the
+// network-size image, times the discount, then / 2 + 0.5 -- guide_at's exp without the resize, stddevs taken as given (the
+// host floors them at min_std).  No object: exactly 0.5.
+__global__ __launch_bounds__(256) void guide_render_kernel(const float4* __restrict__ obj, int n_obj, int H, int W,
+                                                           float discount, float* __restrict__ guide) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= H * W) return;
+  if (n_obj == 0) {
+    guide[i] = 0.5f;
+    return;
+  }
+  const int y = i / W, x = i - (i / W) * W;
+  const float g = guide_at((float)y, (float)x, obj, 0, n_obj, 0.f) * discount;
+  guide[i] = g / 2.f + 0.5f;
+}
+
 // Context rows of a batch (input_pipeline_g.py:527-550, :672-680): sample s reads the resident row of its label slice
 // (column C of the batch table); a failed coin or a padding slice (-1) gives zeros.  With noise (--hist_noise) the row is
 // updated IN PLACE first, row = f32(f64(row) + noise[s]) -- the reference adds the noise into a view of its cached table --
@@ -280,6 +296,16 @@ extern "C" int unetk_lits_context(float* table, int64_t n_rows, int F, const int
   UNETK_REQUIRE(noise == nullptr || (((uintptr_t)noise) & 7u) == 0);
   UNETK_LAUNCH(lits_context_kernel, dim3((F + 255) / 256), dim3(256), 0, (hipStream_t)stream, table, n_rows, F, sample_tab, N, C,
                take, noise, out);
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
+extern "C" int unetk_guide_render(const float* obj, int n_obj, int H, int W, float discount, float* guide, void* stream) {
+  UNETK_REQUIRE(guide && H > 0 && W > 0 && (int64_t)H * W < ((int64_t)1 << 31) && n_obj >= 0 && (obj || n_obj == 0));
+  UNETK_REQUIRE(n_obj == 0 || (((uintptr_t)obj) & 15u) == 0);
+  const int64_t total = (int64_t)H * W;
+  UNETK_LAUNCH(guide_render_kernel, dim3((int)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+               reinterpret_cast<const float4*>(obj), n_obj, H, W, discount, guide);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }

@@ -128,9 +128,45 @@ def dump_hist_feature(in_path, out_path, mode, bins=100, xrng=HIST_RANGE, device
     return written
 
 
+def simulate_user_prior(meta):
+    """extract.py:664-717 `simulate_user_prior` on a list of meta.json records: for every 3-D tumour (z1, y1, x1, z2, y2,
+    x2) its middle slice (z2 - z1 - 1) // 2 + z1 receives {"z": [z1, z2], "center", "stddev"} of that tumour's 2-D record
+    on that slice.  Keys: string PIDs, then string slice ids (what json.dump makes of the reference's int keys)."""
+    from .lits import _maybe_json
+    prior = {}
+    for case in meta:
+        tumors = _maybe_json(case["tumors"])
+        index = _maybe_json(case["tumor_slices_index"])
+        from_to = _maybe_json(case["tumor_slices_from_to"])
+        tids = _maybe_json(case["tumor_slices_tid"])
+        centers = _maybe_json(case["tumor_slices_centers"])
+        stddevs = _maybe_json(case["tumor_slices_stddevs"])
+        slices = {}
+        for tid, (z1, _, _, z2, _, _) in enumerate(tumors):
+            middle = (z2 - z1 - 1) // 2 + z1
+            ind = index.index(middle)
+            for j in range(from_to[ind], from_to[ind + 1]):
+                if tids[j] == tid:
+                    slices.setdefault(str(middle), []).append({"z": [z1, z2], "center": centers[j], "stddev": stddevs[j]})
+        prior[str(case["PID"])] = slices
+    return prior
+
+
+def write_user_prior(lits_root):
+    """<lits_root>/meta.json -> <lits_root>/prior.json (simulate_user_prior); returns the path."""
+    root = Path(lits_root)
+    with (root / "meta.json").open() as f:
+        meta = json.load(f)
+    out = root / "prior.json"
+    with out.open("w") as f:
+        json.dump(simulate_user_prior(meta), f)
+    return out
+
+
 def main(argv=None):
     """python -m boxsegliver_amd.data.extract png <nii_dir> <lits_root>/png
-       python -m boxsegliver_amd.data.extract hist <nii_dir> <lits_root>/feat [--mode train eval]"""
+       python -m boxsegliver_amd.data.extract hist <nii_dir> <lits_root>/feat [--mode train eval]
+       python -m boxsegliver_amd.data.extract prior <lits_root>"""
     import argparse
     parser = argparse.ArgumentParser(prog="python -m boxsegliver_amd.data.extract", description=__doc__.split("\n")[0])
     sub = parser.add_subparsers(dest="cmd", required=True)
@@ -142,9 +178,14 @@ def main(argv=None):
     h.add_argument("nii_dir")
     h.add_argument("feat_dir")
     h.add_argument("--mode", nargs="+", choices=("train", "eval"), default=["train", "eval"])
+    r = sub.add_parser("prior", help="<lits_root>/meta.json -> <lits_root>/prior.json, the simulated user prior of the "
+                                     "propagated evaluation")
+    r.add_argument("lits_root")
     a = parser.parse_args(argv)
     if a.cmd == "png":
         nii_3d_to_png(a.nii_dir, a.out_dir, a.only_meta)
+    elif a.cmd == "prior":
+        print(write_user_prior(a.lits_root))
     else:
         for mode in a.mode:
             for path in dump_hist_feature(a.nii_dir, a.feat_dir, mode):

@@ -798,13 +798,36 @@ def input_fn_eval(mode, params):
         # input_pipeline_g.py:910-980 (get_dataset_for_eval_image): every slab carries its slices' eval context rows
         context = EvalContext(params["lits_root"], parse_context_list(getattr(args, "context_list", None)),
                               float(getattr(args, "hist_scale", 20.)), params.get("device"))
+    fixed = None
+    if getattr(args, "use_spatial", False) and getattr(args, "eval_no_sp", False):
+        fixed = eval_no_sp_features(args, params.get("device"))
     if getattr(args, "eval_in_patches", False):
-        if context is not None:
-            raise ValueError("--eval_in_patches does not serve the context guide")
+        if context is not None or fixed is not None:
+            raise ValueError("--eval_in_patches does not serve the context or spatial guide")
         return get_dataset_for_eval_patches(cases, config=args, proj_root=proj_root)
     if params.get("whole_slices", False):
-        return get_dataset_for_eval_image(cases, args, proj_root, context=context)
-    return get_dataset_for_eval_image_v2(cases, args, proj_root, context=context)
+        return get_dataset_for_eval_image(cases, args, proj_root, context=context, fixed=fixed)
+    return get_dataset_for_eval_image_v2(cases, args, proj_root, context=context, fixed=fixed)
+
+
+def eval_no_sp_features(args, device=None):
+    """--use_spatial --eval_no_sp (input_pipeline_g.py:982-1050, get_dataset_for_eval_image_sp): every slab carries
+    sp_guide = 0.5 everywhere and, with --use_context, a context of zeros -- constant device tensors made once.  The
+    reference's --real_sp meta guides in these slabs, --save_sp_guide and --mode infer are not supported."""
+    if getattr(args, "real_sp", None):
+        raise NotImplementedError("--real_sp guides in the --eval_no_sp slabs are not supported")
+    if getattr(args, "save_sp_guide", False):
+        raise NotImplementedError("--save_sp_guide is not supported with --eval_no_sp")
+    if getattr(args, "mode", "eval") == "infer":
+        raise NotImplementedError("--mode infer with --use_spatial --eval_no_sp is not supported")
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    bs = int(args.batch_size)
+    fixed = {"sp_guide": torch.full((bs, int(args.im_height), int(args.im_width), 1), 0.5, dtype=torch.float32,
+                                    device=device)}
+    if getattr(args, "use_context", False):
+        width = sum(n for _, n in parse_context_list(getattr(args, "context_list", None)))
+        fixed["context"] = torch.zeros((bs, width), dtype=torch.float32, device=device)
+    return fixed
 
 
 class EvalContext(object):
@@ -963,11 +986,12 @@ def _slabs(volume, batch_size, lhc, rhc, head, config, context=None, z0=0):
             yield item
 
 
-def get_dataset_for_eval_image_v2(data_list, config, proj_root=".", context=None):
+def get_dataset_for_eval_image_v2(data_list, config, proj_root=".", context=None, fixed=None):
     """input_pipeline.py:615-668: per case the liver box is cut from the NIfTI volume, padded in z to whole batches,
     resized to the network size, and served as batch_size-slice slabs (each followed by its mirrored copies under
     --eval_mirror); a case ends with (None, (segmentation, vol_path, pads, bbox, resize)).  context (an EvalContext):
-    every slab also carries its slices' eval context rows as a device tensor (input_pipeline_g.py:910-980)."""
+    every slab also carries its slices' eval context rows as a device tensor (input_pipeline_g.py:910-980).  fixed: entries
+    every slab carries unchanged (eval_no_sp_features)."""
     align = 16 if getattr(config, "model", "UNet") != "DenseUNet" else 32
     padding, padding_z = 25, 0
     batch_size = config.batch_size
@@ -984,13 +1008,13 @@ def get_dataset_for_eval_image_v2(data_list, config, proj_root=".", context=None
         if resize:
             volume = cv2_resize_linear(volume, pshape)      # dsize = (im_height, im_width), as the reference passes it
         ctx = context.case(case, pads) if context is not None else None
-        for item in _slabs(volume, batch_size, lhc, rhc, {"names": pid}, config, ctx, bbox[2]):
+        for item in _slabs(volume, batch_size, lhc, rhc, dict(fixed or {}, names=pid), config, ctx, bbox[2]):
             yield item
         yield None, (segmentation, vol_path, pads, bbox, resize)
 
 
-def get_dataset_for_eval_image(data_list, config, proj_root=".", test_data=False, context=None):
-    """input_pipeline_li.py:398-456: whole slices (no liver crop); context as in get_dataset_for_eval_image_v2."""
+def get_dataset_for_eval_image(data_list, config, proj_root=".", test_data=False, context=None, fixed=None):
+    """input_pipeline_li.py:398-456: whole slices (no liver crop); context and fixed as in get_dataset_for_eval_image_v2."""
     from . import nii_kits
     batch_size = config.batch_size
     c = config.im_channel
@@ -1013,7 +1037,7 @@ def get_dataset_for_eval_image(data_list, config, proj_root=".", test_data=False
         if resize:
             volume = cv2_resize_linear(volume, pshape)
         ctx = context.case(case, pads) if context is not None else None
-        for item in _slabs(volume, batch_size, lhc, rhc, {"names": case["PID"]}, config, ctx, 0):
+        for item in _slabs(volume, batch_size, lhc, rhc, dict(fixed or {}, names=case["PID"]), config, ctx, 0):
             yield item
         yield None, (segmentation, seg_path, pads, (0, 0, 0, w - 1, h - 1, ori_d - 1), resize)
 

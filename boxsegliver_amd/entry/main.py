@@ -154,10 +154,19 @@ def run(args, sub, pipe, guided=False, dataset_params=None):
         estimator = estimator_lib.CustomEstimator(models.model_fn, args.model_dir,
                                                   estimator_lib.RunConfig(model_dir=args.model_dir), params)
         evaluator = evaluator_lib.get_evaluator(args.evaluator, estimator=estimator, model_dir=args.model_dir, params=params)
+        spatial = guided and sub == "liver" and getattr(args, "use_spatial", False)
+        if spatial and args.mode == ModeKeys.PREDICT:
+            raise NotImplementedError("--mode infer with --use_spatial is not supported (with or without --eval_no_sp); "
+                                      "evaluate with --mode eval")
+        if spatial and getattr(args, "save_sp_guide", False):
+            raise NotImplementedError("--save_sp_guide is not supported (with or without --eval_no_sp)")
+        propagated = spatial and not getattr(args, "eval_no_sp", False)
         ckpt = estimator.checkpoint_path(args.ckpt_path, args.load_status_file if not args.eval_final else None)
         if not ckpt:
             raise FileNotFoundError("Missing checkpoint file in {} with status_file {}".format(
                 args.model_dir, args.load_status_file if not args.eval_final else None))
+        if propagated:                                   # entry/main_g.py:218-228: guide propagation (EvaluateVolume.run_g)
+            return evaluator.run_g(input_fn_eval, checkpoint_path=ckpt, save=args.save_predict)
         return evaluator.run(input_fn_eval, checkpoint_path=ckpt, save=args.save_predict)
 
     raise ValueError("--mode {} is not built (TF-Serving export is out of scope, SURVEY.md 2 row 15)".format(args.mode))

@@ -18,6 +18,9 @@ The input contract is the reference's eval generator (DataLoader/Liver/input_pip
 -- closed per case by `(None, (segmentation, vol_path, pads, bbox, resize))`.  When --eval_mirror is set and the
 pipeline does NOT emit mirrored copies (no "mirror" key), the evaluator mirrors on the device itself, which saves the
 host flips and three host->device copies per slab.
+
+With --use_spatial, `run_g` (evaluator_liver.py:768-917) evaluates by guide propagation instead: data/propagate.py holds the
+state machine, `_GuidedLoop` the per-slice device work (one forward, unetk_guide_components, one table copy, unetk_guide_render).
 """
 import json
 import time
@@ -398,6 +401,71 @@ class EvaluateVolume(EvaluateBase):
         resize = getattr(self.config, "im_height", 0) > 0 and getattr(self.config, "im_width", 0) > 0
         return self._run_actual(self._predict_case, run_pred, save, cases=n_cases, resize=resize)
 
+    # ------------------------------------------------------------------ spatial-guide propagation
+    def run_g(self, input_fn=None, checkpoint_path=None, latest_filename=None, save=False, cases=None, timing=None,
+              trace=None):
+        """evaluator_liver.py:818-917 with --use_spatial: every case of the validation fold is walked slice by slice up and
+        then down, each slice guided by the prior and by the tumours predicted on the previous one (data/propagate.py).
+        Per slice on the device: one forward over the image, its mirrors and the guide's mirrors, the mirror-averaged
+        probabilities written into the case's resident slot of the sweep, `unetk_guide_components`, one small table copied
+        to pinned host memory (the slice's only sync; the head and 256 rows, the rest only for a slice with more components),
+        the host's matching, and `unetk_guide_render` for the next slice.
+        The two sweeps' volumes are combined as max(forward, flip_z(backward)) on the device, then argmax, zoom back to the
+        box (order 0) and the usual post-processing and metrics.  timing (a dict): per-phase seconds, measured with a device
+        sync between phases (for measurements only).  trace (a list): receives per slice (direction, sid, objects,
+        components at or above the threshold, their decisions, number of components below it)."""
+        from ..data import lits, propagate
+        cfg = self.config
+        if getattr(cfg, "save_sp_guide", False):
+            raise NotImplementedError("--save_sp_guide is not supported by the propagated evaluation")
+        if getattr(cfg, "mode", ModeKeys.EVAL) == ModeKeys.PREDICT:
+            raise NotImplementedError("--mode predict with --use_spatial is not supported (the evaluation needs labels)")
+        if checkpoint_path and not tf_checkpoint.checkpoint_exists(checkpoint_path):
+            raise FileNotFoundError("Missing checkpoint file {} (status_file {})".format(checkpoint_path, latest_filename))
+        root = self.params["lits_root"]
+        data = lits.collect_datasets(root, cfg.test_fold, "eval", filter_tumor_size=getattr(cfg, "filter_size", 0),
+                                     filter_only_liver_in_val=self.params.get("filter_only_liver_in_val", True))
+        if len(data) == 0:
+            raise ValueError("No valid dataset found!")
+        context = None
+        if getattr(cfg, "use_context", False):
+            context = lits.EvalContext(root, lits.parse_context_list(getattr(cfg, "context_list", None)),
+                                       float(getattr(cfg, "hist_scale", 20.)), self.params.get("device"))
+        prior = propagate.load_prior(root, getattr(cfg, "real_sp", None))
+        state = propagate.Propagation(prior, float(getattr(cfg, "min_std", 2.)), float(getattr(cfg, "eval_discount", 0.85)),
+                                      (cfg.im_height, cfg.im_width))
+        source = propagate.EvalCases(data, cfg, self.params.get("proj_root", "."), root, context)
+        model = self._model()
+
+        def run_pred():
+            loop = _GuidedLoop(self, model, state, checkpoint_path, timing, trace)
+            for item in source:
+                yield item, loop.case(item)
+
+        n_cases = cases if cases is not None else -1
+        return self._run_actual(self._predict_case_g, run_pred, save, cases=n_cases)
+
+    def _predict_case_g(self, predicts, cases=-1, dtype="pred", save_path=None):
+        """evaluator_liver.py:768-816: the combined probability volume of a case (already max(forward, flip_z(backward)) on
+        the device) -> argmax (or the probabilities with --pred_type prob) -> zoom back to the box."""
+        counter = 0
+        for item, volume in predicts:
+            if dtype == "pred":
+                amax, _ = ops.head_predict(volume.view(-1, volume.shape[-1]), volume.shape[-1], want_preds=False)
+                volume = amax.view(volume.shape[:-1]).cpu().numpy()
+            else:
+                volume = volume.cpu().numpy()
+            ori_shape = (volume.shape[0],) + arr_ops.bbox_to_shape(item["bbox"])[1:]
+            if volume.ndim == 4:
+                ori_shape = ori_shape + (volume.shape[-1],)
+            scales = np.array(ori_shape) / np.array(volume.shape)
+            if np.any(scales != 1):
+                volume = ndi.zoom(volume, scales, order=0 if dtype == "pred" else 1)
+            yield str(item["pid"]), item["segmentation"], volume, False
+            counter += 1
+            if 0 < cases <= counter:
+                break
+
     def _run_actual(self, predict_fn, run_fn, save, cases=-1, **run_kwargs):
         """evaluator_liver.py:906-996; returns the averaged results (the reference only logs them)."""
         do_eval = getattr(self.config, "mode", ModeKeys.EVAL) != "predict"
@@ -475,6 +543,116 @@ class EvaluateVolume(EvaluateBase):
 
     def compare(self, *args_, **kwargs):
         return _compare(*args_, **kwargs)
+
+
+GUIDE_TABLE_CAP = 16384         # components per slice the device table holds (more raise): an early checkpoint can predict
+#                                 thousands of specks
+GUIDE_TABLE_FIRST = 256         # rows copied with the head every slice (12 KB); more are fetched only when a slice has more
+
+
+class _GuidedLoop(object):
+    """The device side of EvaluateVolume.run_g: buffers that live across slices and cases, and one case at a time."""
+
+    def __init__(self, evaluator, model, state, checkpoint_path, timing=None, trace=None):
+        from ..data import propagate
+        self.ev, self.model, self.state, self.ckpt = evaluator, model, state, checkpoint_path
+        self.propagate = propagate
+        self.timing, self.trace = timing, trace
+        cfg = evaluator.config
+        self.h, self.w, self.c = int(cfg.im_height), int(cfg.im_width), int(cfg.im_channel)
+        self.variants = list(evaluator.mirror_variants)
+        self.scale = 1.0 / evaluator.mirror_div
+        self.dev = torch.device("cuda", torch.cuda.current_device())
+        b = 1 + len(self.variants)
+        self.images = torch.empty((b, self.h, self.w, self.c), dtype=torch.float32, device=self.dev)
+        self.sp = torch.empty((b, self.h, self.w, 1), dtype=torch.float32, device=self.dev)
+        self.guide = torch.empty((self.h, self.w), dtype=torch.float32, device=self.dev)
+        self.table = torch.empty(4 + GUIDE_TABLE_CAP * ops.GUIDE_ROW, dtype=torch.int32, device=self.dev)
+        self.table_host = torch.empty(self.table.shape, dtype=torch.int32, pin_memory=True)
+        self.obj_host = torch.empty((64, 4), dtype=torch.float32, pin_memory=True)
+        self.obj = torch.empty((64, 4), dtype=torch.float32, device=self.dev)
+        self.ws = ops.guide_components_ws(self.h, self.w, GUIDE_TABLE_CAP, self.dev)
+        self.restored = False
+        self._tic = None
+
+    def _mark(self, phase):
+        """timing only: charge the time since the previous mark to `phase`, with the device idle at both ends."""
+        if self.timing is None:
+            return
+        torch.cuda.synchronize()
+        now = time.perf_counter()
+        if phase is not None and self._tic is not None:
+            self.timing[phase] = self.timing.get(phase, 0.0) + now - self._tic
+        self._tic = now
+
+    def _render(self, objects):
+        n = len(objects)
+        if n > self.obj.shape[0]:
+            cap = max(n, 2 * self.obj.shape[0])
+            self.obj_host = torch.empty((cap, 4), dtype=torch.float32, pin_memory=True)
+            self.obj = torch.empty((cap, 4), dtype=torch.float32, device=self.dev)
+        if n:
+            self.obj_host[:n].numpy()[:] = objects
+            self.obj[:n].copy_(self.obj_host[:n], non_blocking=True)       # the previous slice's sync freed obj_host
+        ops.guide_render(self.obj[:n] if n else None, (self.h, self.w), self.state.discount, out=self.guide)
+
+    def _forward(self, feats):
+        if not self.restored:
+            self.restored = True
+            if self.model.params is None:
+                self.ev._forward(self.model, feats)                            # creates the variables
+            if self.ckpt and self.ev.estimator is not None:
+                self.ev.estimator._restore(self.ckpt, self.model, None)
+        return self.ev._forward(self.model, feats)
+
+    def case(self, item):
+        """The combined class probabilities [d, H, W, 3] of one case on the device."""
+        cshape, lhc, rhc, bbox = item["cshape"], item["lhc"], item["rhc"], item["bbox"]
+        depth = cshape[0] - lhc - rhc
+        vol = torch.from_numpy(np.ascontiguousarray(np.moveaxis(item["volume"], -1, 0))).to(self.dev)    # [z, H, W]
+        ctx = item["context"]
+        fwd = torch.empty((depth, self.h, self.w, 3), dtype=torch.float32, device=self.dev)
+        bwd = torch.empty_like(fwd)
+        for direction, idx in self.propagate.sweeps(cshape, lhc, rhc):
+            zz1 = idx - lhc
+            sid = zz1 + bbox[2]
+            self._mark(None)
+            objects = self.state.start_slice(item["pid"], sid, bbox, cshape)
+            self._render(objects)
+            self._mark("render")
+            self.images[0].copy_(vol[zz1:zz1 + self.c].permute(1, 2, 0))
+            self.sp[0, :, :, 0].copy_(self.guide)
+            for j, m in enumerate(self.variants):
+                fh, fw = _FLIPS[m]
+                ops.flip_axpy(self.images[0:1], self.images[j + 1:j + 2], fh, fw)
+                ops.flip_axpy(self.sp[0:1], self.sp[j + 1:j + 2], fh, fw)
+            feats = {"images": self.images, "sp_guide": self.sp}
+            if ctx is not None:
+                feats["context"] = ctx[sid:sid + 1].expand(self.images.shape[0], -1).contiguous()
+            prob = self._forward(feats)
+            slot = (fwd if direction == "Forward" else bwd)[zz1:zz1 + 1]       # backward slices land flipped back in z
+            ops.flip_axpy(prob[0:1], slot, False, False, self.scale, accumulate=False)
+            for j, m in enumerate(self.variants):
+                fh, fw = _FLIPS[m]
+                ops.flip_axpy(prob[j + 1:j + 2], slot, fh, fw, self.scale, accumulate=True)
+            self._mark("forward")
+            ops.guide_components(slot[0], self.guide, GUIDE_TABLE_CAP, table=self.table, ws=self.ws)
+            self._mark("components")
+            head = 4 + GUIDE_TABLE_FIRST * ops.GUIDE_ROW
+            self.table_host[:head].copy_(self.table[:head], non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            count = int(self.table_host[0])
+            if GUIDE_TABLE_FIRST < count <= GUIDE_TABLE_CAP:          # a speckled slice: the rest of its rows
+                end = 4 + count * ops.GUIDE_ROW
+                self.table_host[head:end].copy_(self.table[head:end], non_blocking=True)
+                torch.cuda.current_stream().synchronize()
+            comps, n_low = self.propagate.parse_table(self.table_host.numpy(), self.w, skip_low=True)
+            decisions = self.state.finish_slice(sid, comps, lambda: self.guide.cpu().numpy(), n_low)
+            self._mark("sync_match")
+            if self.trace is not None:
+                self.trace.append((direction, sid, objects, comps, decisions, n_low))
+        torch.maximum(fwd, bwd, out=fwd)
+        return fwd
 
 
 def _compare(cur_result, ori_result, primary_metric=None, secondary_metric=None):

@@ -1281,6 +1281,54 @@ def surface_distances(a, b, sampling=(1.0, 1.0, 1.0)):
     return tuple((vals[k][0], vals[k][1], vals[k][2], int(n[k])) for k in range(2))
 
 
+GUIDE_ROW = 12            # int32 words per component row of unetk_guide_components
+
+
+def guide_components_ws(h, w, cap, device):
+    """A workspace for guide_components at [h, w] with table capacity cap (one per loop: it is reused every slice)."""
+    nbytes = _abi.lib().unetk_guide_components_ws_bytes(int(h), int(w), int(cap))
+    if nbytes == 0:
+        raise ValueError("unsupported guide_components shape {}x{} / capacity {}".format(h, w, cap))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def guide_components(acc, guide, cap=1024, table=None, ws=None):
+    """The tumour components of one slice of the guide propagation (unetk_guide_components): acc f32 [H, W, 3] the
+    mirror-averaged probabilities, guide f32 [H, W] the guide the slice was given.  Returns the int32 device table
+    [4 + cap * GUIDE_ROW]: head {count, overflow, 0, 0}, then per component in root order {root, area, y0, x0, y1, x1, peak
+    index, peak value, cy, cx, sy, sx} (the last five are float32 bits).  No host read; runs on the current stream."""
+    _require_cuda(acc, guide)
+    h, w = int(acc.shape[0]), int(acc.shape[1])
+    assert acc.dtype == torch.float32 and tuple(acc.shape) == (h, w, 3) and acc.is_contiguous()
+    assert guide.dtype == torch.float32 and guide.numel() == h * w and guide.is_contiguous()
+    if table is None:
+        table = torch.empty(4 + cap * GUIDE_ROW, dtype=torch.int32, device=acc.device)
+    assert table.dtype == torch.int32 and table.numel() >= 4 + cap * GUIDE_ROW and table.is_contiguous()
+    nbytes = _abi.lib().unetk_guide_components_ws_bytes(h, w, int(cap))
+    if ws is None:
+        ws = guide_components_ws(h, w, cap, acc.device)
+    assert ws.numel() >= nbytes
+    check(_abi.lib().unetk_guide_components(ptr(acc), ptr(guide), h, w, int(cap), ptr(table), ptr(ws), nbytes, stream_ptr()),
+          "guide_components")
+    return table
+
+
+def guide_render(obj, out_hw, discount, out=None):
+    """The guide f32 [H, W] of one propagation slice (unetk_guide_render): obj f32 [n, 4] = (cy, cx, sy, sx) on the device
+    (16-byte aligned rows), max of the Gaussians x discount / 2 + 0.5; exactly 0.5 without objects."""
+    h, w = int(out_hw[0]), int(out_hw[1])
+    n = 0 if obj is None else int(obj.shape[0])
+    if n:
+        _require_cuda(obj)
+        assert obj.dtype == torch.float32 and obj.dim() == 2 and obj.shape[1] == 4 and obj.is_contiguous()
+    if out is None:
+        out = torch.empty((h, w), dtype=torch.float32, device=obj.device if n else torch.device("cuda", torch.cuda.current_device()))
+    assert out.dtype == torch.float32 and out.numel() == h * w and out.is_contiguous()
+    check(_abi.lib().unetk_guide_render(ptr(obj) if n else None, n, h, w, float(discount), ptr(out), stream_ptr()),
+          "guide_render")
+    return out
+
+
 def lits_batch(slices, seg_slices, sample_tab, clip, out_hw, channels, lab_scale=64, noise_scale=0.0, seed=0):
     """One training batch from device-resident decoded slices (input_pipeline.py:243-284): slices uint16 / seg_slices
     uint8 [n, src_h, src_w] (stored as int16 / uint8 tensors), sample_tab int32 [N, C+7], clip f32 [N, 2]."""

@@ -1,5 +1,7 @@
 """Array helpers the volume evaluator needs -- host-side mirror of the reference's utils/array_kits.py
 (`get_largest_component` :357-384, `merge_labels`, `bbox_to_shape`)."""
+import math
+
 import numpy as np
 from scipy import ndimage as ndi
 
@@ -88,3 +90,33 @@ def compute_robust_moments(binary_image, isotropic=False, indexing="ij", min_std
     if indexing == "ij":
         return center, std_dev
     raise ValueError("Valid values for `indexing` are 'xy' and 'ij'.")
+
+
+def xiaolinwu_line(x0, y0, x1, y1):
+    """utils/array_kits.py `xiaolinwu_line`: the pixels (xs, ys) of Xiaolin Wu's line from (x0, y0) to (x1, y1), one per step
+    along the major axis (the first pixel of each anti-aliased pair), ordered from the end with the smaller major
+    coordinate; `forward` is False when that end is (x1, y1).  The same float64 arithmetic as the reference, so the
+    floors fall on the same pixels."""
+    if x0 == x1 and y0 == y1:
+        raise ValueError("Must be different points, but the same ({}) vs ({})".format(x0, y0))
+    steep = abs(y1 - y0) > abs(x1 - x0)
+    if steep:                                   # walk along y: swap the roles of the axes
+        x0, y0, x1, y1 = y0, x0, y1, x1
+    forward = not x0 > x1
+    if not forward:
+        x0, y0, x1, y1 = x1, y1, x0, y0
+    dx, dy = x1 - x0, y1 - y0
+    gradient = 1. if dx == 0 else 1. * dy / dx
+    a_major = round(x0)
+    intery = y0 + gradient * (a_major - x0)
+    majors, minors = [a_major], [math.floor(intery)]
+    intery += gradient
+    b_major = round(x1)
+    b_minor = math.floor(y1 + gradient * (b_major - x1))
+    for m in range(a_major + 1, b_major):
+        majors.append(m)
+        minors.append(math.floor(intery))
+        intery += gradient
+    majors.append(b_major)
+    minors.append(b_minor)
+    return (minors, majors, forward) if steep else (majors, minors, forward)

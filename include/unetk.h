@@ -568,6 +568,26 @@ size_t unetk_slice_hist_ws_bytes(int D, int H, int W, int bins, int mode);
 int unetk_slice_hist(const int16_t* vol, const uint8_t* lab, int D, int H, int W, int mode, const int32_t* lut, int lut_lo,
                      int lut_n, const double* db, int bins, float* out, void* ws, size_t ws_bytes, void* stream);
 
+/* Spatial-guide propagation of the guided volume evaluation (DataLoader/Liver/input_pipeline_g.py:1179-1513,
+ * EvalImage3DLoader), one slice at a time; the matching itself stays on the host.
+ * unetk_guide_components: acc f32 [H,W,3] the slice's mirror-averaged class probabilities, guide f32 [H,W] the guide the
+ *   slice was given.  Tumour mask = argmax(acc) == 2 (lowest index on ties); its 4-connected components (the labels of
+ *   unetk_largest_component with D = 1, numbered in increasing root = minimum linear index, scipy's order).  table int32
+ *   [4 + cap * 12]: head {count, overflow (count > cap), 0, 0}, then per component k < min(count, cap) the row
+ *   {root, area, y0, x0, y1, x1 (inclusive box), peak index, peak value (f32 bits), cy, cx, sy, sx (f32 bits)}: the peak
+ *   is the maximum of guide over the component at its first raster position, (cy, cx) the medians of its rows and columns
+ *   (mean of the two middle values for even counts) and (sy, sx) = 1.4826f * the median absolute deviations in float32 --
+ *   array_kits.compute_robust_moments without the min_std floor.  Exact: integer histograms, then one thread per component.
+ *   H * W < 2^31, 0 < cap <= 65536, cap * H < 2^31 and cap * W < 2^31 (else UNETK_E_BADARG and a zero ws query);
+ *   ws 16-byte aligned, at least unetk_guide_components_ws_bytes.
+ * unetk_guide_render: guide f32 [H,W] = max_k exp(-((y - cy)^2 / (2 sy^2) + (x - cx)^2 / (2 sx^2))) * discount / 2 + 0.5
+ *   over obj float4 [n_obj] = (cy, cx, sy, sx), 16-byte aligned (array_kits.create_gaussian_distribution_v2 in float32);
+ *   exactly 0.5 when n_obj = 0. */
+size_t unetk_guide_components_ws_bytes(int H, int W, int cap);
+int unetk_guide_components(const float* acc, const float* guide, int H, int W, int cap, int32_t* table, void* ws,
+                           size_t ws_bytes, void* stream);
+int unetk_guide_render(const float* obj, int n_obj, int H, int W, float discount, float* guide, void* stream);
+
 /* ---------------------------------------------------------------- LiTS training batch  
  * DataLoader/Liver/input_pipeline.py:243-284 `data_processing_train` for a whole batch, gathering from decoded slices
  * that are RESIDENT in device memory: per sample crop_to_bounding_box -> resize_bilinear(align_corners) -> window clip
