@@ -111,6 +111,8 @@ _SIGNATURES = {
     "unetk_norm_finalize_ws_bytes": (c_size_t, [POINTER(NormDesc), c_int]),
     "unetk_norm_finalize": (c_int, [POINTER(NormDesc), P, c_int, P, P, c_float, c_float, c_int, P, P, P, P, P, P,
                                     P, c_size_t, P]),
+    "unetk_norm_finalize_y": (c_int, [POINTER(NormDesc), P, c_int, P, P, P, c_float, c_float, c_int, P, P, P, P, P, P,
+                                      P, c_size_t, P]),
     "unetk_norm_apply_relu": (c_int, [POINTER(NormDesc), P, P, P, P, P, P, P, P, P]),
     "unetk_norm_bwd_ws_bytes": (c_size_t, [POINTER(NormDesc)]),
     "unetk_norm_relu_bwd": (c_int, [POINTER(NormDesc), P, P, c_int, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P,

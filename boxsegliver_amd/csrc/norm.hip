@@ -63,14 +63,58 @@ NormGeom geom(const unetk_norm_desc* d, bool density) {
   return g;
 }
 
+// The batch statistics come in one pass, var = E[y^2] - E[y]^2 from fp32 partials: three fp32 roundings (the epilogue's row
+// partials, the first-level row sums, the rounding of the sums below) each cost about 2^-24 (var + mean^2) of the
+// variance, so its relative error grows with (mean / std)^2.  A channel is ill-conditioned when
+// mean^2 > NORM_REFINE_T (var + eps); given the activations, its statistics are recomputed from them in a second, shifted
+// pass (norm_refine_kernel).  T is derived in tests/test_norm_stats_host.py: the channels the one-pass path keeps stay
+// well inside the 1e-5 relative rstd / variance bound of tests/test_gpu_norm_stats.py.  A flagged channel's recomputed
+// statistics replace the one-pass ones only where these are off by more than that bound allows: 2^-16 (var + eps) of the
+// variance (2^-17 of rstd), also 2^-17 of the variance where the moving variance is updated, 2^-23 |mean| + 2^-21 std of
+// the mean.  A one-pass result within them stays, bit for bit.
+constexpr double NORM_REFINE_T = 16.0;
+constexpr int NORM_REFINE_PB = 64;         // at most this many pixel blocks per (group, 16 channels)
+constexpr int64_t NORM_REFINE_PIX = 4096;  // pixels per pixel block, at least
+
+int refine_blocks(int64_t Ps) {
+  const int64_t b = (Ps + NORM_REFINE_PIX - 1) / NORM_REFINE_PIX;
+  return (int)(b < 1 ? 1 : (b > NORM_REFINE_PB ? NORM_REFINE_PB : b));
+}
+
+// mean / var (float64) of one (group, channel) -> the moving statistics, mean / rstd / scale / shift
+__device__ __forceinline__ void norm_finish(double m, double v, int c, int i, double count, const float* __restrict__ gamma,
+                                            const float* __restrict__ beta, float eps, float decay, int update_moving,
+                                            float* __restrict__ moving_mean, float* __restrict__ moving_var,
+                                            float* __restrict__ mean_out, float* __restrict__ rstd_out,
+                                            float* __restrict__ scale_out, float* __restrict__ shift_out) {
+  const float mean = (float)m, var = (float)v;
+  if (update_moving) {   // batch norm only (Ns == 1)
+    const double unbiased = count > 1.0 ? v * (count / (count - 1.0)) : v;
+    moving_mean[c] = moving_mean[c] * decay + mean * (1.f - decay);
+    moving_var[c] = moving_var[c] * decay + (float)unbiased * (1.f - decay);
+  }
+  const float rstd = 1.0f / sqrtf(var + eps);
+  const float g = gamma ? gamma[c] : 1.f;
+  const float b = beta ? beta[c] : 0.f;
+  const float scale = g * rstd;
+  mean_out[i] = mean;
+  rstd_out[i] = rstd;
+  scale_out[i] = scale;
+  shift_out[i] = b - mean * scale;
+}
+
 // Last level of the statistics reduction fused with the finalisation: src[2][Ns][rows][C] (rows <= 256: the conv
 // epilogue's partials, or their first-level sums) -> mean / rstd / scale / shift.  Block = 16 channels x 16 row lanes of
 // one group; fp64 row sums in a fixed order, rounded to fp32 exactly as unetk_rows_reduce + norm_finalize_kernel did.
+// flags != null (the activations were given): flags[g][c] = the channel is ill-conditioned; such a channel keeps its
+// float64 one-pass mean / variance in one[g][c][2] and leaves its moving statistics to norm_refine_kernel, and the
+// (group, 16-channel block)'s arrival counter is zeroed for it.
 __global__ __launch_bounds__(256) void norm_reduce_finalize_kernel(
     const float* __restrict__ src, int rows, int Ns, int C, double count, const float* __restrict__ gamma,
     const float* __restrict__ beta, float eps, float decay, int update_moving, float* __restrict__ moving_mean,
     float* __restrict__ moving_var, float* __restrict__ mean_out, float* __restrict__ rstd_out,
-    float* __restrict__ scale_out, float* __restrict__ shift_out) {
+    float* __restrict__ scale_out, float* __restrict__ shift_out, int* __restrict__ flags, unsigned* __restrict__ counters,
+    double* __restrict__ one) {
   __shared__ double red[2][16][17];
   const int cblocks = (C + 15) / 16;
   const int cb = blockIdx.x % cblocks, gi = blockIdx.x / cblocks;
@@ -95,21 +139,109 @@ __global__ __launch_bounds__(256) void norm_reduce_finalize_kernel(
   const double m = (double)(float)t0 / count;
   double v = (double)(float)t1 / count - m * m;
   if (v < 0.0) v = 0.0;
-  const float mean = (float)m, var = (float)v;
-  if (update_moving) {   // batch norm only (Ns == 1)
-    const double unbiased = count > 1.0 ? v * (count / (count - 1.0)) : v;
-    moving_mean[c] = moving_mean[c] * decay + mean * (1.f - decay);
-    moving_var[c] = moving_var[c] * decay + (float)unbiased * (1.f - decay);
-  }
-  const float rstd = 1.0f / sqrtf(var + eps);
-  const float g = gamma ? gamma[c] : 1.f;
-  const float b = beta ? beta[c] : 0.f;
-  const float scale = g * rstd;
   const int i = gi * C + c;
-  mean_out[i] = mean;
-  rstd_out[i] = rstd;
-  scale_out[i] = scale;
-  shift_out[i] = b - mean * scale;
+  int refine = 0;
+  if (flags) {
+    refine = m * m > NORM_REFINE_T * (v + (double)eps) ? 1 : 0;
+    flags[i] = refine;
+    if (refine) {
+      one[2 * i] = m;
+      one[2 * i + 1] = v;
+    }
+    if (cl == 0) counters[gi * cblocks + cb] = 0u;
+  }
+  norm_finish(m, v, c, i, count, gamma, beta, eps, decay, update_moving && !refine, moving_mean, moving_var, mean_out,
+              rstd_out, scale_out, shift_out);
+}
+
+// The second pass of the flagged channels.  Grid = (group, 16-channel block, pixel block PB): a block whose 16 channels are
+// all unflagged returns at once.  Block = four float4 channel lanes x 64 pixel lanes over one contiguous pixel range of
+// the group; fp64 sums of d = y - p and d^2 with p = the one-pass fp32 mean (mean_out), in a fixed order (pixel lane ->
+// groups of four lanes -> sixteen groups), into part[g][cb][PB][2][16].  The last block of a (group, channel block) to
+// arrive sums the PB partials in block order,
+//   mean = p + S1 / n,   var = S2 / n - (S1 / n)^2,
+// and finishes the channel (mean / rstd / scale / shift, moving statistics) from these, or from the one-pass mean and
+// variance in one[] where those are within the tolerances above.
+// A constant channel has d = a few ulps of p at every pixel: every partial sum is exact and var is exactly 0.
+__global__ __launch_bounds__(256) void norm_refine_kernel(
+    const float* __restrict__ y, int64_t Ps, int Ns, int C, int PB, double count, const float* __restrict__ gamma,
+    const float* __restrict__ beta, float eps, float decay, int update_moving, float* __restrict__ moving_mean,
+    float* __restrict__ moving_var, float* __restrict__ mean_out, float* __restrict__ rstd_out,
+    float* __restrict__ scale_out, float* __restrict__ shift_out, const int* __restrict__ flags,
+    unsigned* __restrict__ counters, double* __restrict__ part, const double* __restrict__ one) {
+  __shared__ double red[2][64][17];
+  __shared__ double red2[2][16][17];
+  __shared__ int last;
+  const int cblocks = (C + 15) / 16;
+  const int pb = blockIdx.x % PB;
+  const int cb = (blockIdx.x / PB) % cblocks, gi = blockIdx.x / (PB * cblocks);
+  const int fc = cb * 16 + (int)threadIdx.x;
+  const int f = (threadIdx.x < 16 && fc < C) ? flags[gi * C + fc] : 0;
+  if (!__syncthreads_or(f)) return;
+  const int q = threadIdx.x & 3, rl = threadIdx.x >> 2;
+  const int c0 = cb * 16 + q * 4;
+  double s0[4] = {0.0, 0.0, 0.0, 0.0}, s1[4] = {0.0, 0.0, 0.0, 0.0};
+  if (c0 < C) {   // C % 4 == 0
+    const float4 p = ldg4(mean_out + (int64_t)gi * C + c0);
+    const int64_t chunk = (Ps + PB - 1) / PB;
+    const int64_t r0 = pb * chunk, r1 = r0 + chunk < Ps ? r0 + chunk : Ps;
+    const float* yg = y + (int64_t)gi * Ps * C + c0;
+    for (int64_t r = r0 + rl; r < r1; r += 64) {
+      const float4 v = ldg4(yg + r * C);
+      const double d0 = (double)v.x - (double)p.x, d1 = (double)v.y - (double)p.y;
+      const double d2 = (double)v.z - (double)p.z, d3 = (double)v.w - (double)p.w;
+      s0[0] += d0; s1[0] += d0 * d0;
+      s0[1] += d1; s1[1] += d1 * d1;
+      s0[2] += d2; s1[2] += d2 * d2;
+      s0[3] += d3; s1[3] += d3 * d3;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    red[0][rl][q * 4 + k] = s0[k];
+    red[1][rl][q * 4 + k] = s1[k];
+  }
+  __syncthreads();
+  {
+    const int cl = threadIdx.x & 15, j = threadIdx.x >> 4;
+    red2[0][j][cl] = (red[0][4 * j][cl] + red[0][4 * j + 1][cl]) + (red[0][4 * j + 2][cl] + red[0][4 * j + 3][cl]);
+    red2[1][j][cl] = (red[1][4 * j][cl] + red[1][4 * j + 1][cl]) + (red[1][4 * j + 2][cl] + red[1][4 * j + 3][cl]);
+  }
+  __syncthreads();
+  double* pp = part + (((int64_t)gi * cblocks + cb) * PB + pb) * 32;
+  if (threadIdx.x < 16) {
+    double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      t0 += red2[0][j][threadIdx.x];
+      t1 += red2[1][j][threadIdx.x];
+    }
+    pp[threadIdx.x] = t0;
+    pp[16 + threadIdx.x] = t1;
+    __threadfence();
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) last = atomicAdd(counters + gi * cblocks + cb, 1u) == (unsigned)(PB - 1);
+  __syncthreads();
+  if (!last || threadIdx.x >= 16 || fc >= C || !f) return;
+  __threadfence();
+  const double* pc = part + ((int64_t)gi * cblocks + cb) * PB * 32 + threadIdx.x;
+  double S0 = 0.0, S1 = 0.0;
+  for (int b = 0; b < PB; ++b) {
+    S0 += __hip_atomic_load(pc + b * 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    S1 += __hip_atomic_load(pc + b * 32 + 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  const int i = gi * C + fc;
+  const double dm = S0 / count;
+  double v = S1 / count - dm * dm;
+  if (v < 0.0) v = 0.0;
+  const double m = (double)mean_out[i] + dm;
+  const double m1 = one[2 * i], v1 = one[2 * i + 1];
+  const double dv = fabs(v1 - v);
+  const bool keep = dv <= 0x1p-16 * (v + (double)eps) && (!update_moving || dv <= 0x1p-17 * v) &&
+                    fabs(m1 - m) <= 0x1p-23 * fabs(m) + 0x1p-21 * sqrt(v);
+  norm_finish(keep ? m1 : m, keep ? v1 : v, fc, i, count, gamma, beta, eps, decay, update_moving, moving_mean, moving_var,
+              mean_out, rstd_out, scale_out, shift_out);
 }
 
 // sums[0][g][c] = sum y, sums[1][g][c] = sum y^2 over `count` elements of group g
@@ -866,17 +998,34 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_pool_kernel(BwdArgs a, Poo
 
 }  // namespace
 
+// bytes of the first part of the workspace (sums, first-level row sums), rounded up to 16: the refinement scratch follows
+size_t finalize_ws_base(const unetk_norm_desc* d, const NormGeom& g, int stat_rows) {
+  const size_t f = 2 * (size_t)g.Ns * d->C + unetk_rows_reduce_tmp_floats(2 * g.Ns, stat_rows / g.Ns, d->C);
+  return (f * sizeof(float) + 15) / 16 * 16;
+}
+
 extern "C" size_t unetk_norm_finalize_ws_bytes(const unetk_norm_desc* d, int stat_rows) {
   if (!norm_desc_ok(d) || stat_rows <= 0) return 0;
   const NormGeom g = geom(d, false);
-  const int rows_per_group = stat_rows / g.Ns;
-  return (2 * (size_t)g.Ns * d->C + unetk_rows_reduce_tmp_floats(2 * g.Ns, rows_per_group, d->C)) * sizeof(float);
+  const size_t cblocks = (d->C + 15) / 16;
+  // refinement (unetk_norm_finalize_y): part[Ns][cblocks][PB][2][16] and one[Ns][C][2] doubles, flags[Ns][C],
+  // counters[Ns][cblocks]
+  return finalize_ws_base(d, g, stat_rows) + (size_t)g.Ns * cblocks * refine_blocks(g.Ps) * 32 * sizeof(double) +
+         (size_t)g.Ns * d->C * 2 * sizeof(double) + (size_t)g.Ns * d->C * sizeof(int) + (size_t)g.Ns * cblocks * sizeof(unsigned);
 }
 
 extern "C" int unetk_norm_finalize(const unetk_norm_desc* d, const float* stat_partials, int stat_rows,
                                    const float* gamma, const float* beta, float eps, float decay, int training,
                                    float* moving_mean, float* moving_var, float* mean_out, float* rstd_out,
                                    float* scale_out, float* shift_out, void* ws, size_t ws_bytes, void* stream) {
+  return unetk_norm_finalize_y(d, stat_partials, stat_rows, nullptr, gamma, beta, eps, decay, training, moving_mean,
+                               moving_var, mean_out, rstd_out, scale_out, shift_out, ws, ws_bytes, stream);
+}
+
+extern "C" int unetk_norm_finalize_y(const unetk_norm_desc* d, const float* stat_partials, int stat_rows, const float* y,
+                                     const float* gamma, const float* beta, float eps, float decay, int training,
+                                     float* moving_mean, float* moving_var, float* mean_out, float* rstd_out,
+                                     float* scale_out, float* shift_out, void* ws, size_t ws_bytes, void* stream) {
   UNETK_REQUIRE(norm_desc_ok(d) && mean_out && rstd_out && scale_out && shift_out);
   hipStream_t st = (hipStream_t)stream;
   const NormGeom g = geom(d, false);
@@ -884,6 +1033,7 @@ extern "C" int unetk_norm_finalize(const unetk_norm_desc* d, const float* stat_p
   float* sums = nullptr;
   if (!use_moving) {
     UNETK_REQUIRE(stat_partials && stat_rows > 0 && ws && stat_rows % g.Ns == 0);
+    UNETK_REQUIRE(!y || (d->storage == UNETK_FP32 && norm_supported(d) && unetk_aligned16(y) && unetk_aligned16(mean_out)));
     if (ws_bytes < unetk_norm_finalize_ws_bytes(d, stat_rows)) return UNETK_E_WORKSPACE;
     sums = (float*)ws;
     // partials are [2][stat_rows][C] with each image's tiles contiguous -> [2*Ns][rows_per_group][C]
@@ -896,10 +1046,21 @@ extern "C" int unetk_norm_finalize(const unetk_norm_desc* d, const float* stat_p
       rows = 64;
     }
     const int update_moving = (!d->per_sample && training && moving_mean && moving_var) ? 1 : 0;
-    UNETK_LAUNCH(norm_reduce_finalize_kernel, dim3(((d->C + 15) / 16) * g.Ns), dim3(256), 0, st, src, rows, g.Ns, d->C,
+    const int cblocks = (d->C + 15) / 16, PB = refine_blocks(g.Ps);
+    double* part = (double*)((char*)ws + finalize_ws_base(d, g, stat_rows));
+    double* one = part + (size_t)g.Ns * cblocks * PB * 32;
+    int* flags = y ? (int*)(one + (size_t)g.Ns * d->C * 2) : nullptr;
+    unsigned* counters = y ? (unsigned*)(flags + (size_t)g.Ns * d->C) : nullptr;
+    UNETK_LAUNCH(norm_reduce_finalize_kernel, dim3(cblocks * g.Ns), dim3(256), 0, st, src, rows, g.Ns, d->C,
                        (double)g.Ps, gamma, beta, eps, decay, update_moving, moving_mean, moving_var, mean_out, rstd_out,
-                       scale_out, shift_out);
+                       scale_out, shift_out, flags, counters, one);
     UNETK_LAUNCH_CHECK();
+    if (y) {
+      UNETK_LAUNCH(norm_refine_kernel, dim3(PB * cblocks * g.Ns), dim3(256), 0, st, y, g.Ps, g.Ns, d->C, PB, (double)g.Ps,
+                   gamma, beta, eps, decay, update_moving, moving_mean, moving_var, mean_out, rstd_out, scale_out,
+                   shift_out, flags, counters, part, one);
+      UNETK_LAUNCH_CHECK();
+    }
     return UNETK_OK;
   } else {
     UNETK_REQUIRE(moving_mean && moving_var);

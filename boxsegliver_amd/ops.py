@@ -755,14 +755,21 @@ def norm_desc(y_shape, per_sample, z_stride=None, guide_ch=0, gw_stride=0, gw_co
                     gw_stride, gw_coff)
 
 
-def norm_finalize(d, stats, rows, gamma, beta, eps, decay, training, moving_mean, moving_var, device):
+def norm_finalize(d, stats, rows, gamma, beta, eps, decay, training, moving_mean, moving_var, device, y=None):
+    """y: the fp32 activations the partials were taken of; given, the ill-conditioned channels (mean^2 > 16 (var + eps))
+    get their statistics from a second, shifted pass over y (unetk_norm_finalize_y).  bf16 storage passes none."""
     groups = d.N if d.per_sample else 1
     out = torch.empty((4, groups, d.C), dtype=torch.float32, device=device)   # mean, rstd, scale, shift
     nbytes = _abi.lib().unetk_norm_finalize_ws_bytes(ctypes.byref(d), max(rows, groups))
     ws = WORKSPACE.get(nbytes, device)
-    check(_abi.lib().unetk_norm_finalize(ctypes.byref(d), ptr(stats), rows, ptr(gamma), ptr(beta), eps, decay,
-                                         1 if training else 0, ptr(moving_mean), ptr(moving_var), ptr(out[0]),
-                                         ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(ws), nbytes, stream_ptr()),
+    if y is not None:
+        if y.dtype != torch.float32:
+            y = None
+        else:
+            assert y.is_contiguous() and y.numel() == d.N * d.HW * d.C, (tuple(y.shape), d.N, d.HW, d.C)
+    check(_abi.lib().unetk_norm_finalize_y(ctypes.byref(d), ptr(stats), rows, ptr(y), ptr(gamma), ptr(beta), eps, decay,
+                                           1 if training else 0, ptr(moving_mean), ptr(moving_var), ptr(out[0]),
+                                           ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(ws), nbytes, stream_ptr()),
           "norm_finalize")
     return out
 
@@ -1570,7 +1577,7 @@ class Conv3x3NormRelu(_Op):
             aff = torch.stack([zero, one, one, beta.detach()]).reshape(4, 1, cout).contiguous()
         else:
             aff = norm_finalize(d, stats, rows, gamma, beta, spec.eps, spec.decay, spec.training, moving_mean,
-                                moving_var, y.device)
+                                moving_var, y.device, y=y)
         se_graph = None
         if se is not None:
             # GUNet.py:192-201: gains = sigmoid(fc(relu(fc(concat(mean_hw(net), context))))).  mean_hw(net)[b, c] =
@@ -1902,7 +1909,7 @@ class Conv3dNormRelu(_Op):
             aff = torch.stack([zero, one, one, beta.detach()]).reshape(4, 1, cout).contiguous()
         else:
             aff = norm_finalize(nd, stats, rows, gamma, beta, spec.eps, spec.decay, spec.training, moving_mean, moving_var,
-                                y.device)
+                                y.device, y=y)
         norm_apply_relu(nd, y, aff, z)
         if spec.training:
             ctx.save_for_backward(x, y, aff)

@@ -280,6 +280,16 @@ int unetk_norm_finalize(const unetk_norm_desc* d, const float* stat_partials, in
                         const float* gamma, const float* beta, float eps, float decay, int training,
                         float* moving_mean, float* moving_var, float* mean_out, float* rstd_out,
                         float* scale_out, float* shift_out, void* ws, size_t ws_bytes, void* stream);
+/* The same, given also the activations y [N, HW, C] the partials were taken of (fp32, dense, C % 4 == 0; NULL = exactly
+ * unetk_norm_finalize).  A channel whose one-pass variance E[y^2] - E[y]^2 is ill-conditioned (mean^2 > 16 (var + eps))
+ * gets its statistics recomputed on the device from y, shifted by the one-pass mean, in a fixed order; they replace the
+ * one-pass ones where those are off by more than 2^-17 of rstd (2^-17 of the variance where the moving variance is
+ * updated) or 2^-23 |mean| + 2^-21 std of the mean.  Every other channel's results are bit-identical to those of
+ * unetk_norm_finalize.  Same workspace. */
+int unetk_norm_finalize_y(const unetk_norm_desc* d, const float* stat_partials, int stat_rows, const float* y,
+                          const float* gamma, const float* beta, float eps, float decay, int training,
+                          float* moving_mean, float* moving_var, float* mean_out, float* rstd_out,
+                          float* scale_out, float* shift_out, void* ws, size_t ws_bytes, void* stream);
 
 /* z = relu((y*scale + shift) [* den[n][c]] [+ guide modulation]); z has pixel stride d->z_stride.
  * den (nullable, [N][C]) is GUNet's density modulation `conditional_normalization` (GUNet.py:119-133,203-206):

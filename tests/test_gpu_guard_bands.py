@@ -833,6 +833,67 @@ def test_norm_finalize_edges(ops):
     run_checked(launch, outs, g_in, ws, verify, inout=inout, kernels=("norm_reduce_finalize_kernel(",))
 
 
+@pytest.mark.parametrize("flagged", [False, True], ids=["one_pass", "refined"])
+def test_norm_finalize_y_edges(ops, flagged):
+    """unetk_norm_finalize_y: y = NULL is unetk_norm_finalize bit for bit; y of channels at mean / std about 27 takes the
+    second pass over y (the one-pass variance is off by more than the keep tolerance there)."""
+    u = _Unit()
+    n, c = u.n, u.c
+    d = _norm_desc(n, u.h * u.w, c, c)
+    rows = 6
+    y = u.y + 40.0 if flagged else u.y
+    yr = y.reshape(rows, -1, c)
+    stats = torch.stack((yr.sum(1), (yr * yr).sum(1)))
+    g_in = {k: guarded_input(t) for k, t in (("stats", stats), ("gamma", u.gamma), ("beta", u.beta))}
+    if flagged:
+        g_in["y"] = guarded_input(y)
+    mm0 = torch.randn(c, device="cuda", generator=_gen(1))
+    mv0 = torch.rand(c, device="cuda", generator=_gen(2)) + 0.5
+    inout = {"moving_mean": guarded_input(mm0), "moving_var": guarded_input(mv0)}
+    outs = {k: guarded((1, c)) for k in ("mean", "rstd", "scale", "shift")}
+    ws = lib().unetk_norm_finalize_ws_bytes(ctypes.byref(d), rows)
+    decay = 0.999
+    m = y.numel() // c
+    y64 = y.double()
+    mean = y64.mean((0, 1, 2))
+    var = y64.var((0, 1, 2), unbiased=False)
+    rstd = 1.0 / torch.sqrt(var + 1e-3)
+    scale = u.gamma.double() * rstd
+    shift = u.beta.double() - mean * scale
+
+    def args(fn, wsp, nb, yp):
+        head = (ctypes.byref(d), P(g_in["stats"]), rows) + ((yp,) if fn == "y" else ())
+        return head + (P(g_in["gamma"]), P(g_in["beta"]), ctypes.c_float(1e-3), ctypes.c_float(decay), 1,
+                       P(inout["moving_mean"]), P(inout["moving_var"]), P(outs["mean"]), P(outs["rstd"]),
+                       P(outs["scale"]), P(outs["shift"]), wsp, nb, stream())
+
+    def launch(wsp, nb):
+        return lib().unetk_norm_finalize_y(*args("y", wsp, nb, P(g_in.get("y"))))
+
+    def verify(o):
+        for k, ref in (("mean", mean), ("rstd", rstd), ("scale", scale), ("shift", shift)):
+            torch.testing.assert_close(o[k][0].double(), ref, rtol=1e-5, atol=1e-6)
+        torch.testing.assert_close(inout["moving_mean"].view.double(), mm0.double() * decay + mean * (1 - decay),
+                                   rtol=1e-5, atol=1e-6)
+        torch.testing.assert_close(inout["moving_var"].view.double(),
+                                   mv0.double() * decay + var * m / (m - 1) * (1 - decay), rtol=1e-5, atol=1e-6)
+
+    run_checked(launch, outs, g_in, ws, verify, inout=inout,
+                kernels=("norm_reduce_finalize_kernel(",) + (("norm_refine_kernel(",) if flagged else ()),
+                absent=() if flagged else ("norm_refine_kernel(",))
+    if not flagged:      # NULL activations: the results of unetk_norm_finalize, bit for bit
+        wsb = GuardedWorkspace(ws)
+        got = {}
+        for fn in ("y", "plain"):
+            for o in list(outs.values()) + list(inout.values()):
+                o.reset()
+            f = lib().unetk_norm_finalize_y if fn == "y" else lib().unetk_norm_finalize
+            assert f(*args(fn, P(wsb.ptr()), wsb.nbytes, None)) == 0
+            torch.cuda.synchronize()
+            got[fn] = [_bits(o.view.clone()) for o in list(outs.values()) + list(inout.values())]
+        assert all(torch.equal(a, b) for a, b in zip(got["y"], got["plain"]))
+
+
 def test_norm_apply_relu_strided_and_pooled_edges(ops):
     u = _Unit()
     n, h, w, c = u.n, u.h, u.w, u.c
