@@ -240,53 +240,73 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(unetk_head_desc d, const 
         red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-// one thread per sample; then thread 0 combines in sample order
-__global__ void head_finalize_kernel(unetk_head_desc d, const float* __restrict__ part, int bps, int nq,
+// The finalisation's LDS: per sample of a pass, 3 + nq doubles and nq * L slice sums.  A pass takes as many samples as fit
+// the 64 KiB a block may ask for (with L = 1: 431 samples for 2 classes, 264 for 3, 90 for 8); a batch beyond that takes
+// several passes.  L is the kernel's own choice for a block of `threads`.
+constexpr int FIN_THREADS = 1024;
+constexpr int FIN_LDS_DOUBLES = 64 * 1024 / (int)sizeof(double);
+inline int head_fin_samples(int N, int nq) {
+  const int fit = FIN_LDS_DOUBLES / (3 + 2 * nq);
+  return N < fit ? N : fit;
+}
+__host__ __device__ inline int head_fin_slices(int nb, int nq, int threads) {
+  int L = 1;
+  while (L < 64 && 2 * L * nb * nq <= threads) L *= 2;
+  return L;
+}
+
+// one thread per sample; then thread 0 combines in sample order.  nb samples per pass (all of them where they fit).
+__global__ void head_finalize_kernel(unetk_head_desc d, const float* __restrict__ part, int bps, int nq, int nb,
                                      float* __restrict__ result) {
-  extern __shared__ double sh[];  // [N][3]: ce_sum, present, dice_term; [N][nq] column sums; [N * nq][L] slice sums
+  extern __shared__ double sh[];  // [nb][3]: ce_sum, present, dice_term; [nb][nq] column sums; [nb * nq][L] slice sums
   const int ncls = d.ncls;
-  double* colsum = sh + (int64_t)d.N * 3;
-  double* slice = colsum + (int64_t)d.N * nq;
+  double* colsum = sh + (int64_t)nb * 3;
+  double* slice = colsum + (int64_t)nb * nq;
   // L threads per (sample, quantity), each a fixed-order sum over every L-th partial row, combined in slice order: one
   // thread walking all bps rows (864 of them for a 96^3 patch) made this single-block kernel 90 us of serial loads
-  const int P = d.N * nq;
-  int L = 1;
-  while (L < 64 && 2 * L * P <= (int)blockDim.x) L *= 2;
-  for (int t = threadIdx.x; t < P * L; t += blockDim.x) {
-    const int pq = t / L, sl = t - pq * L;
-    const int b = pq / nq, i = pq - b * nq;
-    double a = 0.0;
-    for (int j = sl; j < bps; j += L) a += (double)part[((int64_t)b * bps + j) * nq + i];
-    slice[t] = a;
-  }
-  __syncthreads();
-  for (int t = threadIdx.x; t < P; t += blockDim.x) {
-    double a = 0.0;
-    for (int k = 0; k < L; ++k) a += slice[t * L + k];
-    colsum[t] = a;
-  }
-  __syncthreads();
-  for (int b = threadIdx.x; b < d.N; b += blockDim.x) {
-    const double* acc = colsum + (int64_t)b * nq;
-    double I = 0.0, U = 0.0;
-    for (int c = 1; c < ncls; ++c) {
-      const double* qq = &acc[2 + (c - 1) * 6];
-      float* r = result + 3 + ((int64_t)b * (ncls - 1) + (c - 1)) * 4;
-      r[0] = (float)qq[0]; r[1] = (float)qq[1]; r[2] = (float)qq[2]; r[3] = (float)qq[3];
-      I += qq[4];
-      U += qq[5];
+  const int L = head_fin_slices(nb, nq, (int)blockDim.x);
+  double ce = 0.0, np = 0.0, dm = 0.0;      // thread 0: running sums over the samples, in sample order
+  for (int b0 = 0; b0 < d.N; b0 += nb) {
+    const int nbc = min(nb, d.N - b0);
+    const int P = nbc * nq;
+    for (int t = threadIdx.x; t < P * L; t += blockDim.x) {
+      const int pq = t / L, sl = t - pq * L;
+      const int b = b0 + pq / nq, i = pq % nq;
+      double a = 0.0;
+      for (int j = sl; j < bps; j += L) a += (double)part[((int64_t)b * bps + j) * nq + i];
+      slice[t] = a;
     }
-    float* iu = result + 3 + (int64_t)d.N * (ncls - 1) * 4 + b * 2;
-    iu[0] = (float)I;
-    iu[1] = (float)U;
-    sh[b * 3 + 0] = acc[0];
-    sh[b * 3 + 1] = acc[1];
-    sh[b * 3 + 2] = 2.0 * (double)(float)I / ((double)(float)U + 1e-8);
+    __syncthreads();
+    for (int t = threadIdx.x; t < P; t += blockDim.x) {
+      double a = 0.0;
+      for (int k = 0; k < L; ++k) a += slice[t * L + k];
+      colsum[t] = a;
+    }
+    __syncthreads();
+    for (int bl = threadIdx.x; bl < nbc; bl += blockDim.x) {
+      const int b = b0 + bl;
+      const double* acc = colsum + (int64_t)bl * nq;
+      double I = 0.0, U = 0.0;
+      for (int c = 1; c < ncls; ++c) {
+        const double* qq = &acc[2 + (c - 1) * 6];
+        float* r = result + 3 + ((int64_t)b * (ncls - 1) + (c - 1)) * 4;
+        r[0] = (float)qq[0]; r[1] = (float)qq[1]; r[2] = (float)qq[2]; r[3] = (float)qq[3];
+        I += qq[4];
+        U += qq[5];
+      }
+      float* iu = result + 3 + (int64_t)d.N * (ncls - 1) * 4 + b * 2;
+      iu[0] = (float)I;
+      iu[1] = (float)U;
+      sh[bl * 3 + 0] = acc[0];
+      sh[bl * 3 + 1] = acc[1];
+      sh[bl * 3 + 2] = 2.0 * (double)(float)I / ((double)(float)U + 1e-8);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int bl = 0; bl < nbc; ++bl) { ce += sh[bl * 3]; np += sh[bl * 3 + 1]; dm += sh[bl * 3 + 2]; }
+    __syncthreads();                        // the next pass overwrites sh
   }
-  __syncthreads();
   if (threadIdx.x == 0) {
-    double ce = 0.0, np = 0.0, dm = 0.0;
-    for (int b = 0; b < d.N; ++b) { ce += sh[b * 3]; np += sh[b * 3 + 1]; dm += sh[b * 3 + 2]; }
     result[0] = np > 0.0 ? (float)(ce / np) : 0.f;
     result[1] = (float)(1.0 - dm / (double)d.N);
     result[2] = (float)np;
@@ -495,11 +515,11 @@ extern "C" int unetk_head_fwd(const unetk_head_desc* d, const void* z, const flo
   UNETK_LAUNCH_CHECK();
   if (labels) {
     {
-      const int P = d->N * L.nq;
-      int Ls = 1;
-      while (Ls < 64 && 2 * Ls * P <= 1024) Ls *= 2;        // the kernel's own choice for 1024 threads
-      UNETK_LAUNCH(head_finalize_kernel, dim3(1), dim3(1024),
-                         ((size_t)d->N * (3 + L.nq) + (size_t)P * Ls) * sizeof(double), st, *d, part, bps, L.nq, result);
+      const int nb = head_fin_samples(d->N, L.nq);
+      const int Ls = head_fin_slices(nb, L.nq, FIN_THREADS);
+      UNETK_LAUNCH(head_finalize_kernel, dim3(1), dim3(FIN_THREADS),
+                         ((size_t)nb * (3 + L.nq) + (size_t)nb * L.nq * Ls) * sizeof(double), st, *d, part, bps, L.nq, nb,
+                         result);
     }
     UNETK_LAUNCH_CHECK();
   }

@@ -1003,3 +1003,107 @@ def test_norm_relu_bwd_pool_edges(ops):
 
     run_checked(launch, outs, dict(par, y=gy, dskip=gds, dp=gdp), ws, verify,
                 kernels=("norm_bwd_reduce_pool_kernel<float>", "norm_bwd_apply_pool_kernel<float>"))
+
+
+# ------------------------------------------------------------------------------------------------ loss head
+HEAD_ROWS = [
+    # name, N, HW, C, ncls, weight mode
+    ("c64_k3", 2, 1025, 64, 3, "numerical"),
+    ("c32_k2", 3, 255, 32, 2, "pixelmap"),
+    ("c8_k8_ragged", 2, 7, 8, 8, "proportion"),              # HW not a multiple of the 2 lanes per pixel
+    ("c8_k3_tmp", 2, 140000, 8, 3, "none"),                  # 1094 backward blocks: dw and db both go through `tmp`
+]
+
+
+@pytest.mark.parametrize("storage", ["fp32", "bf16s"])
+@pytest.mark.parametrize("row", HEAD_ROWS, ids=[r[0] for r in HEAD_ROWS])
+def test_head_fwd_bwd_edges(ops, row, storage):
+    """unetk_head_fwd + unetk_head_bwd on one shared workspace of exactly unetk_head_ws_bytes (hist, wn, part, pw, pb, tmp);
+    result holds exactly unetk_head_result_floats; one byte less of workspace is refused before anything is written."""
+    import test_gpu_head as th
+    from boxsegliver_amd import _abi
+    _, n, hw, c, ncls, mode = row
+    bf = storage == "bf16s"
+    sdt = torch.bfloat16 if bf else torch.float32
+    case = th._case("guard_" + row[0], n, hw, c, ncls, mode, None, storage="bf16" if bf else "fp32")
+    z, w, b, labels, pixel_w = th.make_inputs(case)
+    ref = th.ref_of(case, (z, w, b, labels, pixel_w))
+    d = th.desc_of(ops, case)
+    d.storage = _abi.BF16S if bf else _abi.FP32
+    npix = n * hw
+    nres, nws = lib().unetk_head_result_floats(ctypes.byref(d)), lib().unetk_head_ws_bytes(ctypes.byref(d))
+    assert nres == 3 + n * (ncls - 1) * 4 + n * 2 and nws == th.head_paths(n, hw, c, ncls)["ws_bytes"]
+    assert (th.head_paths(n, hw, c, ncls)["nblk"] > 1024) == (row[0] == "c8_k3_tmp")
+    ins = {"z": guarded_input(z.reshape(npix, c).cuda(), dtype=sdt), "w": guarded_input(w.cuda()),
+           "b": guarded_input(b.cuda()), "labels": guarded_input(labels.reshape(npix, 1).cuda().view(torch.float32))}
+    if pixel_w is not None:
+        ins["pixel_w"] = guarded_input(pixel_w.reshape(npix, 1).cuda())
+    outs = {"logits": guarded((npix, ncls)), "probs": guarded((npix, ncls)), "result": guarded((nres,)),
+            "dz": guarded((npix, c), sdt), "dw": guarded((c, ncls)), "db": guarded((ncls,))}
+    scales = torch.tensor([0.5, 2.0], device="cuda")
+    xs, ds = 0.7, 0.3
+
+    def fwd(wsp, nb):
+        return lib().unetk_head_fwd(ctypes.byref(d), P(ins["z"]), P(ins["w"]), P(ins["b"]), P(ins["labels"]),
+                                    P(ins.get("pixel_w")), P(outs["logits"]), P(outs["probs"]), P(outs["result"]), wsp, nb,
+                                    stream())
+
+    def bwd(wsp, nb):
+        return lib().unetk_head_bwd(ctypes.byref(d), P(ins["z"]), P(ins["w"]), P(ins["labels"]), P(ins.get("pixel_w")),
+                                    P(outs["logits"]), P(outs["result"]), xs, ds, P(scales), P(outs["dz"]), P(outs["dw"]),
+                                    P(outs["db"]), wsp, nb, stream())
+
+    def launch(wsp, nb):
+        return fwd(wsp, nb) or bwd(wsp, nb)
+
+    exp = [xs * 0.5 * (gx if gx is not None else 0.0) + ds * 2.0 * gd for gx, gd in zip(ref["gx"], ref["gd"])]
+
+    def verify(o):
+        res = o["result"].double().cpu()
+        head3, sums, iu = th.split_result(res, n, ncls)
+        assert rel(o["logits"].reshape(n, hw, ncls), ref["logits"].to("cuda")) < 3e-6
+        assert (o["probs"].reshape(n, hw, ncls).double() - ref["probs"].to("cuda")).abs().max().item() < 2e-6
+        assert abs(head3[0].item() - ref["xent"]) < 2e-5 * max(1.0, abs(ref["xent"]))
+        assert abs(head3[1].item() - ref["dice"]) < 2e-5
+        assert head3[2].item() == ref["present"]
+        assert ((iu - ref["iu"].cpu()).abs() / ref["iu"].cpu().abs().clamp_min(1.0)).max().item() < 2e-5
+        th.check_counts(sums, ref)
+        if bf:
+            _stored_ok(o["dz"].reshape(n, hw, c), exp[0].to("cuda"), flips=5e-3)
+        else:
+            assert rel(o["dz"].reshape(n, hw, c), exp[0].to("cuda")) < 2e-5
+        assert rel(o["dw"], exp[1].to("cuda")) < 2e-5
+        assert rel(o["db"], exp[2].to("cuda")) < 2e-5
+
+    kernels = ("head_fwd_kernel", "head_finalize_kernel", "head_bwd_kernel")
+    run_checked(launch, outs, ins, nws, verify, kernels=kernels + (("rows_reduce_l1_kernel",) if row[0] == "c8_k3_tmp" else ()))
+    # one byte less: UNETK_E_WORKSPACE from both entry points, nothing written anywhere
+    short = GuardedWorkspace(nws - 1)
+    short.fill(0x5F)
+    before = short.buf.clone()
+    for o in outs.values():
+        o.reset()
+    for call in (fwd, bwd):
+        rc = call(P(short.ptr()), short.nbytes)
+        torch.cuda.synchronize()
+        assert rc == E_WORKSPACE, rc
+        assert all(o.changed_anywhere() == 0 for o in outs.values()) and torch.equal(short.buf, before)
+    assert all(i.changed_anywhere() == 0 for i in ins.values())
+
+
+@pytest.mark.parametrize("npix", [1000, 4096 * 256 + 77], ids=["ragged_block", "past_grid_cap"])
+def test_head_predict_edges(ops, npix):
+    """unetk_head_predict: argmax and the thresholded masks (uint8; 0xA5 is no valid value of either) inside guards."""
+    ncls, guard = 3, 256 << 10
+    probs = torch.softmax(2.0 * torch.randn((npix, ncls), generator=_gen(npix % 97), device="cuda"), -1)
+    gp = guarded_input(probs)
+    bufs = {"argmax": torch.full((2 * guard + npix,), 0xA5, dtype=torch.uint8, device="cuda"),
+            "preds": torch.full((2 * guard + (ncls - 1) * npix,), 0xA5, dtype=torch.uint8, device="cuda")}
+    rc = lib().unetk_head_predict(P(gp), npix, ncls, P(bufs["argmax"].data_ptr() + guard), P(bufs["preds"].data_ptr() + guard),
+                                  stream())
+    torch.cuda.synchronize()
+    assert rc == 0 and gp.changed_anywhere() == 0
+    for name, t in bufs.items():
+        assert bool((t[:guard] == 0xA5).all()) and bool((t[-guard:] == 0xA5).all()), name
+    assert torch.equal(bufs["argmax"][guard:-guard], probs.argmax(-1).to(torch.uint8))
+    assert torch.equal(bufs["preds"][guard:-guard].reshape(ncls - 1, npix), (probs[:, 1:] > 0.5).t().to(torch.uint8))

@@ -402,18 +402,21 @@ def test_head_forward_backward(ops, w_type, nw, decay, ncls, loss_type):
     assert np.abs(probs.cpu().numpy().reshape(pref.shape) - pref).max() < 2e-6
     got_loss = res[0] if loss_type == "xentropy" else res[1]
     assert abs(got_loss - lref.item()) < 2e-5 * max(1.0, abs(lref.item()))
-    # metrics on thresholded predictions (bit-exact counts where prob is not within 1e-6 of 0.5)
-    preds = olosses.threshold_pred(torch.tensor(pref))
+    # metrics on thresholded predictions: a pixel whose float64 probability lies within 1e-5 of 0.5 may fall either way, so
+    # each count must lie between the reference count with those pixels off and with them on (exact where there are none)
+    amb_all = np.abs(pref[..., 1:] - 0.5) <= 1e-5
+    assert amb_all.mean() <= 1e-3
     for ci in range(1, ncls):
         lab = (labels == ci).unsqueeze(-1)
         sums = res[3:3 + n * (ncls - 1) * 4].reshape(n, ncls - 1, 4)[:, ci - 1]
-        pr = preds[ci - 1].numpy().astype(np.float64)
         lb = lab.numpy().astype(np.float64)
-        if np.abs(pref[..., ci] - 0.5).min() > 1e-5:
-            np.testing.assert_array_equal(sums[:, 0], (pr * lb).sum((1, 2, 3)))
-            np.testing.assert_array_equal(sums[:, 1], pr.sum((1, 2, 3)))
-            np.testing.assert_array_equal(sums[:, 2], lb.sum((1, 2, 3)))
-            np.testing.assert_array_equal(sums[:, 3], np.clip(pr + lb, 0, 1).sum((1, 2, 3)))
+        amb = amb_all[..., ci - 1:ci]
+        on = pref[..., ci:ci + 1] > 0.5
+        bounds = []
+        for pr in ((on & ~amb).astype(np.float64), (on | amb).astype(np.float64)):
+            bounds.append(np.stack([(pr * lb).sum((1, 2, 3)), pr.sum((1, 2, 3)), lb.sum((1, 2, 3)),
+                                    np.clip(pr + lb, 0, 1).sum((1, 2, 3))], -1))
+        assert np.all(sums >= bounds[0]) and np.all(sums <= bounds[1]), (sums, bounds)
     xs, ds = (1.0, 0.0) if loss_type == "xentropy" else (0.0, 1.0)
     scales = torch.tensor([1.0, 1.0], device="cuda")
     dz, dw, db = ops.head_bwd(d, zd, wd, ld, None, lg, result, ws, xs, ds, scales)
