@@ -34,20 +34,20 @@ def rel_err(got, ref):
 
 
 CONV_SHAPES = [
-    # N, H, W, Cin, Cout
-    (2, 16, 32, 16, 64),       # 128x64 tile path
-    (1, 8, 16, 64, 128),       # 128x128 tile path
-    (2, 24, 20, 32, 128),      # H, W not multiples of the 8x16 tile (masked edges)
-    (1, 16, 16, 128, 64),
-    (3, 8, 48, 64, 64),
-    (1, 4, 4, 32, 256),        # image smaller than a tile
-    (2, 16, 32, 32, 32),       # 256x32 tile path (UNet3D's 30-channel levels padded to 32)
-    (1, 24, 20, 64, 32),
-    # small planes -> linear-pixel kernel (conv_igemm_lin.hip): blocks span rows and planes
-    (5, 12, 12, 64, 128),      # UNet3D e3 shape; 720 pixels = 5.6 blocks, plane boundaries inside blocks
-    (9, 6, 6, 32, 64),         # bridge shape: a block covers 3.6 planes
-    (2, 24, 24, 48, 128),      # 24 wide: 75 % fill in the tiled kernel
-    (3, 11, 13, 16, 64),       # odd sizes, last block partial
+    # N, H, W, Cin, Cout          the forward kernel the launch trace shows (tests/test_gpu_conv_paths.py pins every path by name)
+    (2, 16, 32, 16, 64),       # 128x64 tile: conv3x3_igemm_kernel<4,1,1,2>
+    (1, 8, 16, 64, 128),       # two tiled blocks starve the chip: linear-pixel kernel, 64-pixel blocks (lin<2,2,1,2>)
+    (2, 24, 20, 32, 128),      # W = 20 fills 16-wide tiles to 62 %: linear-pixel kernel (lin<2,2,1,2>), blocks cross rows
+    (1, 16, 16, 128, 64),      # 128x64 tile <4,1,1,2>
+    (3, 8, 48, 64, 64),        # 128x64 tile <4,1,1,2>
+    (1, 4, 4, 32, 256),        # image smaller than a tile; 4-row small-grid tile <2,2,1,2>
+    (2, 16, 32, 32, 32),       # 256x32 tile <4,1,2,1> (UNet3D's 30-channel levels padded to 32)
+    (1, 24, 20, 64, 32),       # 256x32 tile <4,1,2,1>, masked edges
+    # small planes: as 2-D images these stay in the tiled kernel unless it leaves > 10 % of its MFMA rows empty
+    (5, 12, 12, 64, 128),      # UNet3D e3 plane as a 2-D image: 4-row small-grid tile <2,2,1,2> (linear-pixel only through the 3-D API)
+    (9, 6, 6, 32, 64),         # bridge plane as a 2-D image: 128x64 tile <4,1,1,2>
+    (2, 24, 24, 48, 128),      # 24 wide: 75 % fill in the tiled kernel -> linear-pixel kernel (lin<2,2,1,2>)
+    (3, 11, 13, 16, 64),       # odd sizes: 128x64 tile <4,1,1,2>, masked edges
 ]
 
 

@@ -137,6 +137,143 @@ def test_conv3d_live_channel_masks(ops, case):
     assert rel_err(dw.cpu().numpy(), wt.grad.numpy()) < 5e-6
 
 
+def _trace(ops, fn):
+    ops.profile_begin(0)
+    ops.profile_on([])
+    try:
+        out = fn()
+    finally:
+        ops.profile_on(None)
+    torch.cuda.synchronize()
+    launches = []
+    for name in ops.profile_read()[1]:
+        name = name.replace(" ", "").replace("(anonymousnamespace)::", "").split("(")[0]
+        if name.startswith("void"):
+            name = name[4:]
+        if "pack_" not in name:
+            launches.append(name)
+    return out, launches           # every launch, in order: a doubled or reordered launch shows
+
+
+def exact_case(ops, case, live=None):
+    """One case with inputs for which fp32 arithmetic is exact in any summation order (x integers in [-4, 4], w eighths in
+    [-2/8, 2/8], dy integers in [-2, 2]: tests/test_gpu_conv_paths.py): y, dx, dw must equal float64 bit for bit whatever
+    stride-2 tile, depth-tap accumulation, grouped taps, four-class scatter, half chunk or fused depth tap computes them.
+    Returns the traced launches (forward, input gradient, filter gradient), in order."""
+    n, dd, h, w, cin, cout, kd, stride = case
+    g = torch.Generator().manual_seed(n * 1000 + dd * 100 + h + cin + cout + kd)
+    x = torch.randint(-4, 5, (n, dd, h, w, cin), generator=g).double()
+    wt = torch.randint(-2, 3, (kd, 3, 3, cin, cout), generator=g).double() / 8
+    live8 = None
+    if live is not None:
+        ci, co = torch.zeros(cin, dtype=torch.bool), torch.zeros(cout, dtype=torch.bool)
+        for lo, hi in live[0]:
+            ci[lo:hi] = True
+        for lo, hi in live[1]:
+            co[lo:hi] = True
+        x = x * ci
+        wt = wt * ci[:, None] * co[None, :]
+        live8 = (_mask8(live[0]), _mask8(live[1]))
+    x.requires_grad_(True)
+    wt.requires_grad_(True)
+    y_ref = tf_ops.conv_nd_same(x, wt, stride=stride)
+    dy = torch.randint(-2, 3, tuple(y_ref.shape), generator=g).double()
+    if live is not None:
+        dy = dy * co
+    y_ref.backward(dy)
+    # the exact regime, from this case's own inputs
+    with torch.no_grad():
+        assert tf_ops.conv_nd_same(x.abs(), wt.abs(), stride=stride).max().item() * 8 < 2 ** 24
+    assert 9 * kd * cout * 2 * 0.25 * 8 < 2 ** 24 and 8 * dy.numel() // cout < 2 ** 24
+    d = ops.conv3d_desc(x.shape, cout, kd, stride, live8=live8)
+    xd, dyd = x.detach().float().cuda(), dy.float().cuda()
+    wp_f, wp_d = ops.conv3d_pack(wt.detach().float().cuda())
+    (y, stats, rows), t_f = _trace(ops, lambda: ops.conv3d_fwd(xd, wp_f, d, want_stats=True))
+    assert torch.equal(y.double().cpu(), y_ref.detach())
+    dx, t_d = _trace(ops, lambda: ops.conv3d_dgrad(dyd, wp_d, d))
+    assert torch.equal(dx.double().cpu(), x.grad)
+    dw, t_w = _trace(ops, lambda: ops.conv3d_wgrad(xd, dyd, d))
+    assert torch.equal(dw.double().cpu(), wt.grad)
+    assert torch.equal(dw, ops.conv3d_wgrad(xd, dyd, d))
+    return t_f, t_d, t_w
+
+
+# the launches of each case (forward, input gradient, filter gradient) in order, recorded from the launch trace: a case that
+# lands elsewhere after a dispatch change fails here instead of quietly testing something else
+EXACT_TRACES = {
+    0: (['conv3x3_igemm_kernel<4,1,2,1,1,1,0>'],
+        ['conv3x3_igemm_kernel<4,1,2,1,1,1,0>'],
+        ['conv3x3_wgrad_kernel<32,32,false,8,16,false,1,1>', 'slab_reduce_kernel<4>']),
+    1: (['conv3x3_igemm_kernel<4,1,1,2,2,1,0>'],
+        ['conv3x3_igemm_lin_kernel<4,1,1,1,true,true,false,false,false,false>'],
+        ['conv3x3_wgrad_kernel<32,64,false,4,16,false,2,1>', 'slab_reduce_kernel<4>']),
+    2: (['conv3x3_igemm_kernel<4,1,1,2,2,1,0>'],
+        ['conv3x3_igemm_lin_kernel<4,1,1,1,true,true,false,false,false,false>'],
+        ['conv3x3_wgrad_kernel<32,64,false,4,16,false,2,1>', 'slab_reduce_kernel<1>']),
+    3: (['conv3x3_igemm_kernel<4,1,1,2,1,1,1>', 'conv3x3_igemm_kernel<4,1,1,2,1,1,1>', 'conv3x3_igemm_kernel<4,1,1,2,1,1,1>'],
+        ['conv3x3_igemm_kernel<4,1,1,2,1,1,1>', 'conv3x3_igemm_kernel<4,1,1,2,1,1,1>', 'conv3x3_igemm_kernel<4,1,1,2,1,1,1>'],
+        ['conv3x3_wgrad_kernel<64,64,false,8,16,false,1,1>', 'slab_reduce_kernel<4>']),
+    4: (['s2d_kernel', 'conv3x3_igemm_lin_kernel<2,2,2,2,false,false,false,false,true,false>'],
+        ['conv3x3_igemm_lin_kernel<4,1,1,2,true,true,false,false,false,false>'],
+        ['conv3x3_wgrad_kernel<32,64,false,4,16,false,2,1>', 'slab_reduce_kernel<1>']),
+    5: (['s2d_kernel', 'conv3x3_igemm_lin_kernel<4,1,1,2,false,false,false,false,true,false>'],
+        ['conv3x3_igemm_lin_kernel<4,1,1,2,true,true,false,false,false,false>'],
+        ['conv3x3_wgrad_kernel<32,64,false,4,16,false,2,1>', 'slab_reduce_kernel<1>']),
+    6: (['conv3x3_igemm_kernel<4,1,1,2,2,1,0>'],
+        ['conv3x3_igemm_lin_kernel<4,1,1,2,true,true,false,false,false,false>', 'conv3x3_igemm_lin_kernel<4,1,1,2,true,true,false,false,false,false>', 'conv3x3_igemm_lin_kernel<4,1,1,2,true,true,false,false,false,false>'],
+        ['conv3x3_wgrad_kernel<32,64,false,4,16,false,2,1>', 'slab_reduce_kernel<1>']),
+    7: (['conv3x3_igemm_kernel<4,1,2,1,1,1,0>'],
+        ['conv3x3_igemm_lin_kernel<2,2,2,2,false,false,false,false,false,false>'],
+        ['conv3x3_wgrad_kernel<64,32,false,8,16,false,1,1>', 'slab_reduce_kernel<1>']),
+    8: (['conv3x3_igemm_lin_kernel<2,2,2,2,false,false,true,false,false,false>', 'lin_sk_fixup_kernel<128,128>'],
+        ['conv3x3_igemm_lin_kernel<4,1,1,2,false,false,true,false,false,false>', 'lin_sk_fixup_kernel<128,64>'],
+        ['conv3x3_wgrad_kernel<64,64,false,10,12,true,1,1>', 'slab_reduce_kernel<4>']),
+    9: (['conv3x3_igemm_lin_kernel<4,1,1,2,false,false,false,false,false,false>'],
+        ['conv3x3_igemm_lin_kernel<4,1,1,2,false,false,false,false,false,false>'],
+        ['conv3x3_wgrad_kernel<64,64,false,20,6,true,1,1>', 'slab_reduce_kernel<1>']),
+    10: (['conv3x3_igemm_lin_kernel<4,1,1,2,false,false,true,false,false,false>', 'lin_sk_fixup_kernel<128,64>'],
+        ['conv3x3_igemm_kernel<4,1,2,1,1,1,1>', 'conv3x3_igemm_kernel<4,1,2,1,1,1,1>', 'conv3x3_igemm_kernel<4,1,2,1,1,1,1>'],
+        ['conv3x3_wgrad_kernel<32,64,false,8,16,false,1,1>', 'slab_reduce_kernel<4>']),
+    11: (['conv3x3_igemm_lin_kernel<4,1,1,2,false,false,false,false,false,false>'],
+        ['conv3x3_igemm_kernel<4,1,2,1,1,1,0>'],
+        ['conv3x3_wgrad_kernel<32,64,false,8,16,false,1,1>', 'slab_reduce_kernel<4>']),
+}
+EXACT_LIVE_TRACES = {
+    0: (['conv3x3_igemm_lin_kernel<2,2,2,2,false,false,true,false,false,false>', 'lin_sk_fixup_kernel<128,128>'],
+        ['conv3x3_igemm_lin_kernel<2,2,2,2,false,false,true,false,false,false>', 'lin_sk_fixup_kernel<128,128>'],
+        ['conv3x3_wgrad_kernel<64,64,false,10,12,true,1,1>', 'slab_reduce_kernel<1>']),
+    1: (['conv3x3_igemm_lin_kernel<2,2,2,2,false,false,true,false,false,true>', 'lin_sk_fixup_kernel<128,128>'],
+        ['conv3x3_igemm_lin_kernel<2,2,2,2,false,false,true,false,false,true>', 'lin_sk_fixup_kernel<128,128>'],
+        ['conv3x3_wgrad_kernel<64,64,false,10,12,true,1,1>', 'slab_reduce_kernel<4>']),
+    2: (['conv3x3_igemm_lin_kernel<2,2,2,2,false,false,true,false,false,false>', 'lin_sk_fixup_kernel<128,128>'],
+        ['conv3x3_igemm_lin_kernel<2,2,2,2,false,false,true,false,false,false>', 'lin_sk_fixup_kernel<128,128>'],
+        ['conv3x3_wgrad_kernel<64,64,false,10,12,true,1,1>', 'slab_reduce_kernel<1>']),
+    3: (['conv3x3_igemm_lin_kernel<2,2,2,2,false,false,true,false,false,true>', 'lin_sk_fixup_kernel<128,128>'],
+        ['conv3x3_igemm_lin_kernel<2,2,2,2,false,false,true,false,false,true>', 'lin_sk_fixup_kernel<128,128>'],
+        ['conv3x3_wgrad_kernel<64,64,false,10,12,true,1,1>', 'slab_reduce_kernel<4>']),
+    4: (['s2d_kernel', 'conv3x3_igemm_lin_kernel<2,2,2,2,false,false,true,false,true,false>', 'lin_sk_fixup_kernel<128,128>'],
+        ['conv3x3_igemm_lin_kernel<2,2,1,1,true,true,false,false,false,false>'],
+        ['conv3x3_wgrad_kernel<32,64,false,4,12,false,2,1>', 'slab_reduce_kernel<4>']),
+    5: (['s2d_kernel', 'conv3x3_igemm_lin_kernel<4,1,1,2,false,false,true,false,true,false>', 'lin_sk_fixup_kernel<128,64>'],
+        ['conv3x3_igemm_lin_kernel<2,2,1,1,true,true,false,false,false,false>'],
+        ['conv3x3_wgrad_kernel<32,64,false,4,6,false,2,1>', 'slab_reduce_kernel<1>']),
+    6: (['conv3x3_igemm_lin_kernel<2,2,2,2,false,false,true,false,false,false>', 'lin_sk_fixup_kernel<128,128>'],
+        ['conv3x3_igemm_lin_kernel<2,2,2,2,false,false,true,false,false,false>', 'lin_sk_fixup_kernel<128,128>'],
+        ['conv3x3_wgrad_kernel<64,64,false,10,12,true,1,1>', 'slab_reduce_kernel<1>']),
+}
+
+
+@pytest.mark.parametrize("i", range(len(CASES)))
+def test_conv3d_exact_inputs(ops, i):
+    assert exact_case(ops, CASES[i]) == EXACT_TRACES[i]
+
+
+@pytest.mark.parametrize("i", range(len(LIVE_CASES)))
+def test_conv3d_live_exact_inputs(ops, i):
+    n, dd, h, w, cin, cin_live, cout, cout_live, kd, stride = LIVE_CASES[i]
+    assert exact_case(ops, (n, dd, h, w, cin, cout, kd, stride), live=(cin_live, cout_live)) == EXACT_LIVE_TRACES[i]
+
+
 DECONV_CASES = [
     # N, D, H, W, Cin, Cout, kd
     (1, 3, 4, 8, 128, 64, 1),      # conv_d1/up: (1,2,2)
