@@ -508,9 +508,11 @@ __device__ __forceinline__ bf16x8 pack8(const float* v) {
 // BF is a template parameter, not a run-time branch: with both MFMA loops in one kernel the compiler shuttled the
 // accumulator between VGPRs and AGPRs once per tile and read a15 back ten wait-states after the last 16-pass MFMA of
 // the loop -- too early (rows 27 / 31 of each 32-row panel lost the final k-step, non-reproducibly).  One loop per
-// instantiation keeps the accumulator in place for the whole split.
+// instantiation keeps the accumulator in place for the whole split.  Only BF = true is instantiated: the fp32 filter gradient
+// is deconv_wgrad4_kernel, and the one-sub-pixel fp32 loop this kernel used to carry had no caller left.
 template <bool BF>
 __global__ __launch_bounds__(256) void deconv_wgrad_kernel(DwParams p) {
+  static_assert(BF, "the fp32 filter gradient is deconv_wgrad4_kernel");
   constexpr int KT = 128, CT = 64;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* at = smem;             // [KT][CT]  dpre rows (co)
@@ -572,24 +574,15 @@ __global__ __launch_bounds__(256) void deconv_wgrad_kernel(DwParams p) {
     }
     __syncthreads();
     if (mt + KT < me) load_tile(mt + KT);
-    if constexpr (BF) {
 #pragma unroll 2
-      for (int s = 0; s < KT / 16; ++s) {
-        float av[8], bv[8];
+    for (int s = 0; s < KT / 16; ++s) {
+      float av[8], bv[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          av[j] = at[(16 * s + 8 * h + j) * CT + wco * 32 + l31];
-          bv[j] = bt[(16 * s + 8 * h + j) * CT + wci * 32 + l31];
-        }
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pack8(av), pack8(bv), acc, 0, 0, 0);
+      for (int j = 0; j < 8; ++j) {
+        av[j] = at[(16 * s + 8 * h + j) * CT + wco * 32 + l31];
+        bv[j] = bt[(16 * s + 8 * h + j) * CT + wci * 32 + l31];
       }
-      continue;
-    }
-#pragma unroll 8
-    for (int s = 0; s < KT / 2; ++s) {
-      const float a = at[(2 * s + h) * CT + wco * 32 + l31];
-      const float b = bt[(2 * s + h) * CT + wci * 32 + l31];
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pack8(av), pack8(bv), acc, 0, 0, 0);
     }
   }
   float* out = p.slab + ((int64_t)split * 4 + ab) * p.Cout * p.Cin;
@@ -960,7 +953,16 @@ __global__ __launch_bounds__(256) void deconv_wgrad4_kernel(DwParams p) {
 
 bool deconv_desc_ok(const unetk_deconv3d_desc* d) {
   return d && d->N > 0 && d->D > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && (d->kd == 1 || d->kd == 2) &&
-         d->out_coff >= 0 && d->out_stride >= d->out_coff + d->Cout;
+         d->out_coff >= 0 && d->out_stride >= d->out_coff + d->Cout &&
+         (d->precision == UNETK_FP32 || d->precision == UNETK_BF16 || d->precision == UNETK_BF16S);
+}
+
+// The backward's shape rules (UNETK_E_UNSUPPORTED / a zero workspace query).  Cout <= 1024: relu_bwd_bias_kernel maps a block's
+// 256 threads to Cout / 4 channel quads (unetk_colmap), and dw_plan divides by the rows that leaves per block -- none beyond.
+bool deconv_bwd_ok(const unetk_deconv3d_desc* d) {
+  if (d->Cin % 64 != 0 || d->Cout % 32 != 0 || d->Cout > 1024 || d->out_stride % 4 != 0 || d->out_coff % 4 != 0) return false;
+  if (d->precision == UNETK_BF16S && (d->kd != 1 || d->Cout % 64 != 0)) return false;
+  return true;
 }
 
 struct DwPlan {
@@ -1096,7 +1098,7 @@ extern "C" int unetk_deconv3d_fwd(const unetk_deconv3d_desc* d, const void* xv, 
 }
 
 extern "C" size_t unetk_deconv3d_bwd_ws_bytes(const unetk_deconv3d_desc* d) {
-  if (!deconv_desc_ok(d) || d->Cin % 64 != 0 || d->Cout % 32 != 0) return 0;
+  if (!deconv_desc_ok(d) || !deconv_bwd_ok(d)) return 0;
   const DwPlan pl = dw_plan(d);
   const size_t M = (size_t)d->N * d->D * d->H * d->W;
   size_t f = 4 * d->kd * M * d->Cout;                       // dpre
@@ -1128,9 +1130,7 @@ extern "C" int unetk_deconv3d_bwd_parts(const unetk_deconv3d_desc* d, const void
   float* dx = (float*)dxv;
   UNETK_REQUIRE(deconv_desc_ok(d) && x && wp_dgrad && cat && dcat && dx && dw && ws && parts >= 1 && parts <= 3);
   const bool bs = d->precision == UNETK_BF16S;
-  if (bs && (d->kd != 1 || d->Cout % 64 != 0 || d->out_stride % 4 != 0)) return UNETK_E_UNSUPPORTED;
-  if (d->Cin % 64 != 0 || d->Cout % 32 != 0 || d->out_stride % 4 != 0 || d->out_coff % 4 != 0)
-    return UNETK_E_UNSUPPORTED;
+  if (!deconv_bwd_ok(d)) return UNETK_E_UNSUPPORTED;
   UNETK_REQUIRE(unetk_aligned16(x) && unetk_aligned16(wp_dgrad) && unetk_aligned16(cat) && unetk_aligned16(dcat) &&
                 unetk_aligned16(dx) && unetk_aligned16(dw) && unetk_aligned16(ws));
   if (ws_bytes < unetk_deconv3d_bwd_ws_bytes(d)) return UNETK_E_WORKSPACE;
@@ -1194,11 +1194,8 @@ extern "C" int unetk_deconv3d_bwd_parts(const unetk_deconv3d_desc* d, const void
     }
     static bool attr_done = false;
     if (!attr_done) {
-      hipError_t e = hipFuncSetAttribute((const void*)deconv_wgrad_kernel<false>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 128 * 64 * (int)sizeof(float));
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)deconv_wgrad_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                2 * 128 * 64 * (int)sizeof(float));
+      hipError_t e = hipFuncSetAttribute((const void*)deconv_wgrad_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         2 * 128 * 64 * (int)sizeof(float));
       if (e != hipSuccess) return (int)e;
       attr_done = true;
     }
@@ -1213,10 +1210,8 @@ extern "C" int unetk_deconv3d_bwd_parts(const unetk_deconv3d_desc* d, const void
       UNETK_LAUNCH(deconv_wgrad_bf16s4_kernel, dim3(pl.S * q.n_co_tiles * q.n_ci_tiles), dim3(512), (size_t)6 * 64 * 128, st, q);
     } else if (bs)
       UNETK_LAUNCH(deconv_wgrad_bf16s_kernel, dim3(grid), dim3(256), (size_t)2 * 128 * 128, st, q);
-    else if (q.bf16)
+    else      // UNETK_BF16 (deconv_desc_ok admits no fourth precision)
       UNETK_LAUNCH(deconv_wgrad_kernel<true>, dim3(grid), dim3(256), (size_t)2 * 128 * 64 * sizeof(float), st, q);
-    else
-      UNETK_LAUNCH(deconv_wgrad_kernel<false>, dim3(grid), dim3(256), (size_t)2 * 128 * 64 * sizeof(float), st, q);
     UNETK_LAUNCH_CHECK();
     rc = unetk_launch_slab_reduce(slab, pl.S, (int64_t)4 * d->Cin * d->Cout, dw + (int64_t)a * 4 * d->Cin * d->Cout, st);
     if (rc != UNETK_OK) return rc;

@@ -439,7 +439,8 @@ int unetk_deconv2x2_pack_bf16s(const float* w, int Cin, int Cout, void* wp_fwd, 
 int unetk_deconv2x2_fwd(const unetk_deconv_desc* d, const void* x, const void* wp_fwd,
                         const float* bias, void* out, void* stream);
 /* Backward.  dcat/cat: gradient and forward value of the concat buffer (same strides/offset as
- * `out`).  Produces dx [N,H,W,Cin], dw [2,2,Cout,Cin], dbias [Cout]. */
+ * `out`).  Produces dx [N,H,W,Cin], dw [2,2,Cout,Cin], dbias [Cout].  Needs Cin % 64 == 0, Cout % 32 == 0 (UNETK_BF16S:
+ * % 64), Cout <= 1024, out_stride % 4 == 0 and out_coff % 4 == 0; otherwise UNETK_E_UNSUPPORTED and a zero *_ws_bytes. */
 size_t unetk_deconv2x2_bwd_ws_bytes(const unetk_deconv_desc* d);
 int unetk_deconv2x2_bwd(const unetk_deconv_desc* d, const void* x, const void* wp_dgrad,
                         const void* cat, const void* dcat, void* dx, float* dw, float* dbias,
