@@ -111,7 +111,81 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_kernel(WgParams p) {
     }
   }
 
-  auto issue_tile = [&](int tile, int stage) {
+  const int t_begin = split * p.tiles_per_split;
+  const int t_end = min(t_begin + p.tiles_per_split, p.total_tiles);
+
+  // STEPPED: a split's tiles are requested in order, so the position of the next one -- (image, tile row, tile column), the
+  // image's x / dy offsets -- is carried along in scalar registers and stepped, and a piece's offset from its tile's origin
+  // (roff) is computed once per block: a tile costs a wave one 64-bit add, two range checks and the zero-page select per piece.
+  // The per-tile form (issue_general: four run-time divisions per tile and ((int64)gh * pw + gw) * stride per lane and piece,
+  // 42 quarter-rate integer multiplies per wave and tile) is hoisted by the compiler in FRONT of the tile's barrier on all eight
+  // waves, the matrix pipe idle meanwhile: DESIGN.md section 4, "staging addresses".
+  // Compiled into the instantiation it was measured on -- the 64 x 64 fp32 panel of plain 8 x 16 tiles, i.e. every filter
+  // gradient of the headline net; the arithmetic holds for any plain tile (S, DIL below), but the others keep the per-tile form
+  // until they have an A/B of their own.
+  constexpr bool STEPPED = !STK && !BF && S == 1 && DIL == 1 && CIT == 64 && COT == 64 && TH_ == TH && TW_ == TW;
+  int64_t roff[G::IPW];
+  int nx_tw = 0, nx_th = 0, nx_n = 0;
+  int64_t nx_ximg = 0, nx_yimg = 0;
+  bool nx_xok = true;                                       // fused depth taps: the tap's input plane exists
+  auto nx_plane = [&]() {
+    nx_ximg = p.xa.off(nx_n) + x_dt;
+    nx_yimg = p.ya.off(nx_n);
+    if (KD > 1) {
+      const int din_i = (nx_n % p.spg) * p.dsd + p.dshift0 + dt;
+      nx_xok = din_i >= 0 && din_i < p.din;
+    }
+  };
+  if constexpr (STEPPED) {
+#pragma unroll
+    for (int i = 0; i < G::IPW; ++i) {
+      const int j = wave + 8 * i;
+      const bool dummy = rel_h[i] >= (1 << 20);
+      if (j < G::NI_X) roff[i] = dummy ? 0 : ((int64_t)rel_h[i] * (S != 1 ? p.Win : p.W) + rel_w[i]) * p.xs + ci0 + qx * 4;
+      else roff[i] = ((int64_t)rel_h[i] * p.W + rel_w[i]) * p.ys + co0 + qy * 4;
+    }
+    nx_tw = t_begin % p.tiles_w;
+    nx_th = (t_begin / p.tiles_w) % p.tiles_h;
+    nx_n = t_begin / (p.tiles_w * p.tiles_h);
+    nx_plane();
+  }
+
+  // Plain tiles: request the NEXT tile of the split (nx_*) into `stage` and step the position.  No tile index comes in: the
+  // position is the lambda's own state, first t_begin, then one tile further per call.
+  auto issue_plain = [&](int stage) {
+    const int h0 = nx_th * TH_, w0 = nx_tw * TW_;
+    const int pwx = S != 1 ? p.Win : p.W, phx = S != 1 ? p.Hin : p.H;
+    const int hx = S * h0 - p.pbh, wx = S * w0 - p.pbw;                       // halo origin in the input plane (may be < 0)
+    // wave-uniform tile origins.  On border tiles xb points in FRONT of the image (hx, wx < 0): it is only ever dereferenced
+    // at xb + roff of a piece that passed the range check, which lies inside the image; every other lane reads the zero page.
+    const float* xb = p.x + nx_ximg + ((int64_t)hx * pwx + wx) * p.xs;
+    const float* yb = p.dy + nx_yimg + ((int64_t)h0 * p.W + w0) * p.ys;
+#pragma unroll
+    for (int i = 0; i < G::IPW; ++i) {
+      const int j = wave + 8 * i;
+      if (j < G::NI) {   // wave-uniform
+        const bool is_x = j < G::NI_X;
+        const int gh = (is_x ? hx : h0) + rel_h[i], gw = (is_x ? wx : w0) + rel_w[i];   // a dummy's rel_h fails the range check
+        const bool ok = (unsigned)gh < (unsigned)(is_x ? phx : p.H) && (unsigned)gw < (unsigned)(is_x ? pwx : p.W) &&
+                        (!is_x || nx_xok);
+        const float* src = (is_x ? xb : yb) + roff[i];
+        if (!ok) src = kZeroPage + (lane & 15) * 4;
+        float* dst = smem + stage * G::STAGE_F + j * 256;   // wave-uniform; lanes land at dst + lane*16 B
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                         (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+      }
+    }
+    if (++nx_tw == p.tiles_w) {
+      nx_tw = 0;
+      if (++nx_th == p.tiles_h) {
+        nx_th = 0;
+        ++nx_n;
+        nx_plane();      // (behind the last tile of the last image this is image N's offset: computed, never used)
+      }
+    }
+  };
+  // Every other instantiation (stacked planes, stride 2, atrous, bf16, narrower panels): the position from the tile index.
+  auto issue_general = [&](int tile, int stage) {
     const int tw_i = tile % p.tiles_w;
     const int th_i = STK ? tile / p.tiles_w : (tile / p.tiles_w) % p.tiles_h;
     const int n_tile = STK ? 0 : tile / (p.tiles_w * p.tiles_h);
@@ -172,11 +246,12 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_kernel(WgParams p) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 
-  const int t_begin = split * p.tiles_per_split;
-  const int t_end = min(t_begin + p.tiles_per_split, p.total_tiles);
   const int a_lane = wci * 32 + l31, b_lane = wco * 32 + l31;
 
-  if (t_begin < t_end) issue_tile(t_begin, 0);
+  if (t_begin < t_end) {
+    if constexpr (!STEPPED) issue_general(t_begin, 0);
+    else issue_plain(0);
+  }
   int stage = 0;
   for (int tile = t_begin; tile < t_end; ++tile, stage ^= 1) {
     // every wave: its own pieces of this tile have landed; barrier: everybody's have, and all reads of the
@@ -195,7 +270,10 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_kernel(WgParams p) {
     // ahead -- 250 VGPRs, 131 instead of 133 TF: the LDS latency at the top of a row is not what this kernel waits for.)
 #pragma unroll 1
     for (int rr = 0; rr < G::RPW; ++rr) {
-      if (rr == issue_rr && tile + 1 < t_end) issue_tile(tile + 1, stage ^ 1);
+      if (rr == issue_rr && tile + 1 < t_end) {
+        if constexpr (!STEPPED) issue_general(tile + 1, stage ^ 1);
+        else issue_plain(stage ^ 1);
+      }
       const int r = ks * G::RPW + rr;
       if constexpr (BF) {
         float bv[8];

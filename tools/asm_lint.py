@@ -9,6 +9,10 @@ Checks, per kernel:
 2. **The matrix kernels really are MFMA kernels of the intended shape**: fp32 kernels contain `v_mfma_f32_32x32x2_f32`
    (exact fp32), bf16 kernels `v_mfma_f32_32x32x16_bf16`; a template change that silently falls back to VALU FMAs (or to
    another MFMA shape with different rounding) is caught here, not by a slow benchmark.
+   The check is positional: it takes "before the last MFMA" in LAYOUT order over the whole function (up to `.Lfunc_end`, not up
+   to the first `s_endpgm`: block placement may put an early exit in front of the K loop).  Should the compiler ever lay an
+   epilogue that reads AGPRs out in front of its K loop, this check would report it although control flow is fine; none of
+   the kernels does today (the ones with such a layout keep their accumulators in VGPRs).
 3. **No scratch**: `.private_segment_fixed_size` == 0 and no `scratch_` instructions (a register spill in a hot loop).
 
 Usage: python tools/asm_lint.py      (exits 1 on a finding).  `tests/test_asm_lint.py` runs the same checks under pytest.
@@ -99,8 +103,10 @@ def lint(jobs=4):
         private = {m.group(1): int(m.group(2)) for m in re.finditer(
             r"\.amdhsa_kernel (\w+)\b.*?\.amdhsa_private_segment_fixed_size (\d+)", txt, re.S)}
         for m in re.finditer(r"^(_Z\w+):[^\n]*\n", txt, re.M):
-            end = txt.find("s_endpgm", m.end())
-            if end < 0:
+            # the whole function, not the text up to its first s_endpgm: block placement may put an early exit (and the
+            # epilogue) in FRONT of the K loop -- conv3x3_wgrad_kernel<32,32,..> has its tile loop behind the slab store
+            end = txt.find(".Lfunc_end", m.end())
+            if end < 0 or txt.find("s_endpgm", m.end(), end) < 0:
                 continue
             body = txt[m.end():end]
             sym = m.group(1)
