@@ -786,7 +786,9 @@ def input_fn_eval(mode, params):
     """input_pipeline.py:228-234 for ModeKeys.EVAL / PREDICT: a python generator over the NIfTI volumes of the validation
     fold (paths in meta.json's vol_case / lab_case, relative to params["proj_root"]).  The evaluator uploads each slab and
     does mirroring / accumulation / argmax on the GPU (evaluators/evaluator_liver.py); with --use_context (without
-    --use_spatial) each case's eval context rows are uploaded once here and the slabs carry device views of them."""
+    --use_spatial) each case's eval context rows are uploaded once here and the slabs carry device views of them.
+    params["volumes_on"] == "device": each case's raw crop is uploaded once and the slabs are built on the device
+    (_device_slabs); --eval_in_patches keeps the host generator."""
     args = params["args"]
     cases = collect_datasets(params["lits_root"], args.test_fold, mode, filter_tumor_size=getattr(args, "filter_size", 0),
                              filter_only_liver_in_val=params.get("filter_only_liver_in_val", True))
@@ -805,9 +807,12 @@ def input_fn_eval(mode, params):
         if context is not None or fixed is not None:
             raise ValueError("--eval_in_patches does not serve the context or spatial guide")
         return get_dataset_for_eval_patches(cases, config=args, proj_root=proj_root)
+    device = None
+    if params.get("volumes_on") == "device":
+        device = params.get("device") or torch.device("cuda", torch.cuda.current_device())
     if params.get("whole_slices", False):
-        return get_dataset_for_eval_image(cases, args, proj_root, context=context, fixed=fixed)
-    return get_dataset_for_eval_image_v2(cases, args, proj_root, context=context, fixed=fixed)
+        return get_dataset_for_eval_image(cases, args, proj_root, context=context, fixed=fixed, device=device)
+    return get_dataset_for_eval_image_v2(cases, args, proj_root, context=context, fixed=fixed, device=device)
 
 
 def eval_no_sp_features(args, device=None):
@@ -856,27 +861,29 @@ def slab_context_rows(z0, n, batch_size):
 GRAY_MIN, GRAY_MAX = -200, 250       # input_pipeline.py:45-46
 
 
+def cv2_linear_taps(dst_n, src_n):
+    """One axis of cv2_resize_linear: (i0, i1, f) per destination sample -- it reads src[i0] * (1 - f) + src[i1] * f.
+    (Also the tap arrays of the device slab builder, ops.eval_slab.)"""
+    s = (np.arange(dst_n, dtype=np.float64) + 0.5) * (src_n / float(dst_n)) - 0.5
+    i0 = np.floor(s).astype(np.int64)
+    f = (s - i0).astype(np.float32)
+    lo = i0 < 0
+    i0[lo], f[lo] = 0, 0.0
+    hi = i0 >= src_n - 1
+    i0[hi], f[hi] = src_n - 1, 0.0
+    return i0, np.minimum(i0 + 1, src_n - 1), f
+
+
 def cv2_resize_linear(img, dsize):
     """cv2.resize(img, dsize, interpolation=cv2.INTER_LINEAR) for float arrays [H, W] or [H, W, C]; dsize = (width, height).
     OpenCV's rule: source coordinate (dst + 0.5) * (src / dst) - 0.5, taps clamped to the image (border replicate)."""
     dw, dh = int(dsize[0]), int(dsize[1])
     img = np.asarray(img, np.float32)
     sh, sw = img.shape[:2]
-
-    def taps(dst_n, src_n):
-        s = (np.arange(dst_n, dtype=np.float64) + 0.5) * (src_n / float(dst_n)) - 0.5
-        i0 = np.floor(s).astype(np.int64)
-        f = (s - i0).astype(np.float32)
-        lo = i0 < 0
-        i0[lo], f[lo] = 0, 0.0
-        hi = i0 >= src_n - 1
-        i0[hi], f[hi] = src_n - 1, 0.0
-        return i0, np.minimum(i0 + 1, src_n - 1), f
-
     if (sh, sw) == (dh, dw):
         return img.copy()
-    y0, y1, fy = taps(dh, sh)
-    x0, x1, fx = taps(dw, sw)
+    y0, y1, fy = cv2_linear_taps(dh, sh)
+    x0, x1, fx = cv2_linear_taps(dw, sw)
     ex = (Ellipsis,) if img.ndim == 2 else (Ellipsis, None)
     rows = img[y0] * (1.0 - fy)[(slice(None), None) + ((None,) if img.ndim == 3 else ())] + \
         img[y1] * fy[(slice(None), None) + ((None,) if img.ndim == 3 else ())]
@@ -932,9 +939,9 @@ def _window_normalise(volume):
     return volume.transpose((1, 2, 0)).astype(np.float32)
 
 
-def parse_case_eval(case, align, padding, padding_z, im_channel, parse_label=True, test_data=False, proj_root="."):
-    """input_pipeline.py:556-612: the liver box (+ padding, sides rounded up to `align`) of one NIfTI case ->
-    normalised float32 volume (y, x, z) with the half-channel context slices, cropped uint8 segmentation (z, y, x)."""
+def _case_eval_crop(case, align, padding, padding_z, im_channel, parse_label=True, test_data=False, proj_root="."):
+    """The raw part of parse_case_eval: the int16 HU crop [z, y, x] of the liver box with the context slices the volume
+    has, and (before, after) = the context slices beyond it, which parse_case_eval pads with HU 0 before the window."""
     from . import nii_kits
     d, h, w = case["size"]
     z1, z2 = max(case["bbox"][0] - padding_z, 0), min(case["bbox"][3] + padding_z, d)
@@ -944,16 +951,25 @@ def parse_case_eval(case, align, padding, padding_z, im_channel, parse_label=Tru
     lhc = (im_channel - 1) // 2                       # context slices before / after the centre slice of a sample
     rhc = im_channel - 1 - lhc
     lo, hi = z1 - lhc, z2 + rhc                       # zero slices stand in for context beyond the volume
-    volume = np.pad(volume[max(lo, 0):min(hi, d), y1:y2, x1:x2], ((max(-lo, 0), max(hi - d, 0)), (0, 0), (0, 0)))
-    cshape = list(volume.shape)
-    volume = _window_normalise(volume)
+    crop = volume[max(lo, 0):min(hi, d), y1:y2, x1:x2]
     segmentation, lab_case = None, None
     if parse_label:
         _, segmentation = nii_kits.read_lits(obj_num, "lab", root / case["lab_case"])
         segmentation = segmentation.astype(np.uint8)[z1:z2, y1:y2, x1:x2]
         lab_case = case["lab_case"]
     bbox = [x1, y1, z1, x2 - 1, y2 - 1, z2 - 1]
-    return case["PID"], case["vol_case"], lab_case, bbox, [d, h, w], cshape, lhc, rhc, volume, segmentation
+    return case["PID"], case["vol_case"], lab_case, bbox, [d, h, w], lhc, rhc, crop, (max(-lo, 0), max(hi - d, 0)), segmentation
+
+
+def parse_case_eval(case, align, padding, padding_z, im_channel, parse_label=True, test_data=False, proj_root="."):
+    """input_pipeline.py:556-612: the liver box (+ padding, sides rounded up to `align`) of one NIfTI case ->
+    normalised float32 volume (y, x, z) with the half-channel context slices, cropped uint8 segmentation (z, y, x)."""
+    pid, vol_case, lab_case, bbox, size, lhc, rhc, crop, beyond, segmentation = _case_eval_crop(
+        case, align, padding, padding_z, im_channel, parse_label, test_data, proj_root)
+    volume = np.pad(crop, (beyond, (0, 0), (0, 0)))
+    cshape = list(volume.shape)
+    volume = _window_normalise(volume)
+    return pid, vol_case, lab_case, bbox, size, cshape, lhc, rhc, volume, segmentation
 
 
 def _mirrored(eval_batch, config):
@@ -986,21 +1002,74 @@ def _slabs(volume, batch_size, lhc, rhc, head, config, context=None, z0=0):
             yield item
 
 
-def get_dataset_for_eval_image_v2(data_list, config, proj_root=".", context=None, fixed=None):
+def window_table():
+    """f32 [GRAY_MAX - GRAY_MIN + 1]: _window_normalise of every integer HU value of the window, by the host's own
+    expression -- the device slab builder (ops.eval_slab) clamps into the window and reads this table."""
+    return _window_normalise(np.arange(GRAY_MIN, GRAY_MAX + 1).reshape(-1, 1, 1)).reshape(-1)
+
+
+def _device_slabs(crop, planes, out_hw, batch_size, c, head, device, context=None, z0=0):
+    """_slabs on the device: `crop` (raw int16 HU [z, y, x]) is uploaded once, and every slab's images are built there by
+    ops.eval_slab -- window, bilinear resize to out_hw = (rows, columns) and the channel window in one launch, bit-equal to
+    the host's _window_normalise / cv2_resize_linear / _slabs.  planes int32 [n + c - 1]: what the host's padded volume
+    holds at each z: a slice of `crop`, -1 = zeros added after the window, -2 = HU 0 padded before it.  One more small
+    upload carries every table of the case.  No mirrored copies and no "mirror" key: the evaluator mirrors on the device."""
+    if crop.dtype != np.int16:
+        raise ValueError("the device slab builder takes int16 HU volumes, got {}".format(crop.dtype))
+    n = len(planes) - (c - 1)
+    assert n % batch_size == 0, "Wrong padding"
+    zsrc = np.lib.stride_tricks.sliding_window_view(np.asarray(planes, np.int32), c)          # [n, c]
+    taps_y, taps_x = cv2_linear_taps(out_hw[0], crop.shape[1]), cv2_linear_taps(out_hw[1], crop.shape[2])
+    ints = [zsrc.reshape(-1), taps_y[0], taps_y[1], taps_x[0], taps_x[1]]
+    floats = [taps_y[2], taps_x[2], window_table()]
+    parts = [np.asarray(a, np.int32) for a in ints] + [np.asarray(a, np.float32).view(np.int32) for a in floats]
+    packed = torch.from_numpy(np.concatenate(parts)).to(device)                                # one upload: every table
+    views, pos = [], 0
+    for a in parts:
+        views.append(packed[pos:pos + a.size])
+        pos += a.size
+    zs, y0, y1, x0, x1 = views[:5]
+    fy, fx, lut = (v.view(torch.float32) for v in views[5:])
+    vol = torch.from_numpy(np.ascontiguousarray(crop)).to(device)                              # one upload: the HU crop
+    rows = slab_context_rows(z0, n, batch_size)
+    for k, idx in enumerate(range(0, n, batch_size)):
+        images = ops.eval_slab(vol, zs[idx * c:(idx + batch_size) * c].view(batch_size, c), (y0, y1, fy), (x0, x1, fx), lut,
+                               out_hw, c, window=(GRAY_MIN, GRAY_MAX))
+        slab = dict(head, images=images)
+        if context is not None:
+            slab["context"] = context[rows[k][0]:rows[k][1]]
+        yield slab, None
+
+
+def get_dataset_for_eval_image_v2(data_list, config, proj_root=".", context=None, fixed=None, device=None):
     """input_pipeline.py:615-668: per case the liver box is cut from the NIfTI volume, padded in z to whole batches,
     resized to the network size, and served as batch_size-slice slabs (each followed by its mirrored copies under
     --eval_mirror); a case ends with (None, (segmentation, vol_path, pads, bbox, resize)).  context (an EvalContext):
     every slab also carries its slices' eval context rows as a device tensor (input_pipeline_g.py:910-980).  fixed: entries
-    every slab carries unchanged (eval_no_sp_features)."""
+    every slab carries unchanged (eval_no_sp_features).  device (a torch device): the raw crop is uploaded once per case and
+    the slabs' images are device tensors built there (_device_slabs), without mirrored copies; the rest of the stream is
+    the same."""
     align = 16 if getattr(config, "model", "UNet") != "DenseUNet" else 32
     padding, padding_z = 25, 0
     batch_size = config.batch_size
     c = config.im_channel
     pshape = config.im_height, config.im_width
     resize = not (config.im_height <= 0 or config.im_width <= 0)
+    parse_label = getattr(config, "mode", "eval") != "infer"
     for case in data_list[getattr(config, "eval_skip_num", 0):]:
+        if device is not None:
+            pid, vol_path, _, bbox, _, lhc, rhc, crop, beyond, segmentation = _case_eval_crop(
+                case, align, padding, padding_z, c, parse_label=parse_label, proj_root=proj_root)
+            pads = -(bbox[5] - bbox[2] + 1) % batch_size
+            planes = [-2] * beyond[0] + list(range(crop.shape[0])) + [-2] * beyond[1] + [-1] * pads
+            out_hw = (pshape[1], pshape[0]) if resize else crop.shape[1:]     # cv2's dsize is (width, height)
+            ctx = context.case(case, pads) if context is not None else None
+            for item in _device_slabs(crop, planes, out_hw, batch_size, c, dict(fixed or {}, names=pid), device, ctx, bbox[2]):
+                yield item
+            yield None, (segmentation, vol_path, pads, bbox, resize)
+            continue
         pid, vol_path, _, bbox, _, cshape, lhc, rhc, volume, segmentation = parse_case_eval(
-            case, align, padding, padding_z, c, parse_label=getattr(config, "mode", "eval") != "infer", proj_root=proj_root)
+            case, align, padding, padding_z, c, parse_label=parse_label, proj_root=proj_root)
         if not resize:
             pshape = tuple(cshape[1:])
         pads = -(bbox[5] - bbox[2] + 1) % batch_size          # zero slices that complete the last slab
@@ -1013,8 +1082,9 @@ def get_dataset_for_eval_image_v2(data_list, config, proj_root=".", context=None
         yield None, (segmentation, vol_path, pads, bbox, resize)
 
 
-def get_dataset_for_eval_image(data_list, config, proj_root=".", test_data=False, context=None, fixed=None):
-    """input_pipeline_li.py:398-456: whole slices (no liver crop); context and fixed as in get_dataset_for_eval_image_v2."""
+def get_dataset_for_eval_image(data_list, config, proj_root=".", test_data=False, context=None, fixed=None, device=None):
+    """input_pipeline_li.py:398-456: whole slices (no liver crop); context, fixed and device as in
+    get_dataset_for_eval_image_v2."""
     from . import nii_kits
     batch_size = config.batch_size
     c = config.im_channel
@@ -1026,19 +1096,28 @@ def get_dataset_for_eval_image(data_list, config, proj_root=".", test_data=False
     rhc = c - 1 - lhc
     for case in data_list[getattr(config, "eval_skip_num", 0):]:
         obj_num, volume = _load_lits_volume(case, root, test_data)
-        volume = _window_normalise(volume)
+        raw = volume
+        if device is None:
+            volume = _window_normalise(volume)
         segmentation, seg_path = None, None
         if parse_label:
             _, segmentation = nii_kits.read_lits(obj_num, "lab", root / case["lab_case"])
             segmentation, seg_path = segmentation.astype(np.uint8), case["lab_case"]
-        h, w, ori_d = volume.shape
+        ori_d, h, w = raw.shape
         pads = -ori_d % batch_size
-        volume = np.pad(volume, ((0, 0), (0, 0), (lhc, pads + rhc)))       # context + the zero slices of the last slab
-        if resize:
-            volume = cv2_resize_linear(volume, pshape)
         ctx = context.case(case, pads) if context is not None else None
-        for item in _slabs(volume, batch_size, lhc, rhc, dict(fixed or {}, names=case["PID"]), config, ctx, 0):
-            yield item
+        head = dict(fixed or {}, names=case["PID"])
+        if device is not None:
+            planes = [-1] * lhc + list(range(ori_d)) + [-1] * (pads + rhc)
+            out_hw = (pshape[1], pshape[0]) if resize else (h, w)
+            for item in _device_slabs(raw, planes, out_hw, batch_size, c, head, device, ctx, 0):
+                yield item
+        else:
+            volume = np.pad(volume, ((0, 0), (0, 0), (lhc, pads + rhc)))       # context + the zero slices of the last slab
+            if resize:
+                volume = cv2_resize_linear(volume, pshape)
+            for item in _slabs(volume, batch_size, lhc, rhc, head, config, ctx, 0):
+                yield item
         yield None, (segmentation, seg_path, pads, (0, 0, 0, w - 1, h - 1, ori_d - 1), resize)
 
 

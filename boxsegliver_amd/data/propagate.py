@@ -216,7 +216,9 @@ class Propagation(object):
 # ------------------------------------------------------------------------------------------------ the cases
 class EvalCases(object):
     """prepare_next_case / gen_next_batch of EvalImage3DLoader without the model: per case the normalised volume resized
-    to the network size (y, x, z with the context slices), its labels, its box, and the slice order of the two sweeps."""
+    to the network size (y, x, z with the context slices), its labels, its box, and the slice order of the two sweeps.
+    This input side stays on the host (window and resize in numpy, one upload per case) whatever the evaluator's
+    volumes_on says; only the zoom back of run_g follows that switch."""
 
     def __init__(self, data_list, config, proj_root=".", lits_root=None, context=None):
         self.data_list = list(data_list)[int(getattr(config, "eval_skip_num", 0)):]

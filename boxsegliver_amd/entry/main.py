@@ -153,7 +153,11 @@ def run(args, sub, pipe, guided=False, dataset_params=None):
         params.update(models.get_model_params(args))
         estimator = estimator_lib.CustomEstimator(models.model_fn, args.model_dir,
                                                   estimator_lib.RunConfig(model_dir=args.model_dir), params)
-        evaluator = evaluator_lib.get_evaluator(args.evaluator, estimator=estimator, model_dir=args.model_dir, params=params)
+        # volumes_on="device": a case's volumes stay on the GPU from the raw crop to the metrics; same results as "host".
+        # main_g keeps "host": its evaluation hands every case's volume to the scoring step as a host array, and callers
+        # that look at it there (tests/test_gpu_propagation.py) read it as one.
+        evaluator = evaluator_lib.get_evaluator(args.evaluator, estimator=estimator, model_dir=args.model_dir, params=params,
+                                                volumes_on="host" if guided else "device")
         spatial = guided and sub == "liver" and getattr(args, "use_spatial", False)
         if spatial and args.mode == ModeKeys.PREDICT:
             raise NotImplementedError("--mode infer with --use_spatial is not supported (with or without --eval_no_sp); "

@@ -3,15 +3,21 @@ evaluators/evaluator_liver.py (`EvaluateVolume`: run :704-766, _predict_case :61
 _run_actual :906-996, _compare :1193-1227) on the libunetk HIP kernels.
 
 What runs where (MI355X-first):
+  * HOST or DEVICE (volumes_on): the network's input slabs.  volumes_on="host" (the default) takes the reference's host
+    generator: window, bilinear resize and the slabs in numpy, one upload per slab (data/lits.py).  volumes_on="device"
+    (what entry/main.py asks for; main_g keeps "host") uploads a case's raw int16 crop once and builds every slab there: `unetk_eval_slab`,
+    bit-equal to the host pipeline.
   * DEVICE: the forward passes of every slab, the mirror test-time augmentation (flip of the input slab, un-flip and
     `/ mirror_div` accumulation of the class probabilities: `unetk_flip_axpy`; the reference does this with np.flip
     on the host, :648-655), the concatenation of a case's slabs, and the final `np.argmax(volume, -1)` (:663,
-    `unetk_head_predict`, lowest index on ties like numpy).  One device->host copy per case (uint8 mask).
-  * HOST: zoom back to the original shape (scipy.ndimage.zoom, inside _predict_case).
-  * DEVICE again (metrics_on="device", the default): the case's argmax volume and its labels are uploaded once each,
-    then class split, merge tumor into liver, largest connected component (_postprocess_device), the per-case volume
-    metrics (loss_metrics.metric_3d_device) and the global Dice counts run in csrc/evalvol.hip.  metrics_on="host" keeps
-    the reference's host path (_postprocess, loss_metrics.metric_3d, ConfusionMatrix).
+    `unetk_head_predict`, lowest index on ties like numpy).
+  * HOST or DEVICE (volumes_on): zoom back to the original shape.  "host": one device->host copy per case (uint8 mask)
+    and scipy.ndimage.zoom inside _predict_case.  "device": `unetk_zoom_nearest3d` with index tables asked of scipy itself
+    (ops.zoom_tables), so scipy's zero samples just outside the input are reproduced; the prediction stays on the device.
+  * DEVICE again (metrics_on="device", the default): the case's labels are uploaded once (and, with volumes_on="host", its
+    argmax volume again), then class split, merge tumor into liver, largest connected component (_postprocess_device),
+    the per-case volume metrics (loss_metrics.metric_3d_device) and the global Dice counts run in csrc/evalvol.hip.
+    metrics_on="host" keeps the reference's host path (_postprocess, loss_metrics.metric_3d, ConfusionMatrix).
 
 The input contract is the reference's eval generator (DataLoader/Liver/input_pipeline_li.py:398-456): a stream of
 `(features, None)` slabs -- features["images"] [bs,H,W,C], features["names"], optional features["mirror"] in {0,1,2,3}
@@ -63,10 +69,11 @@ def add_arguments(parser):
 
 
 def get_evaluator(evaluator, estimator=None, model_dir=None, params=None, merge_tumor_to_liver=True, largest=True,
-                  use_sg_reduce_fp=False, metrics_on="device"):
+                  use_sg_reduce_fp=False, metrics_on="device", volumes_on="host"):
     if evaluator == "Volume":
         return EvaluateVolume(estimator, model_dir=model_dir, params=params, merge_tumor_to_liver=merge_tumor_to_liver,
-                              largest=largest, use_sg_reduce_fp=use_sg_reduce_fp, metrics_on=metrics_on)
+                              largest=largest, use_sg_reduce_fp=use_sg_reduce_fp, metrics_on=metrics_on,
+                              volumes_on=volumes_on)
     raise ValueError("Unsupported evaluator: {}. Must be [Volume, ]".format(evaluator))
 
 
@@ -93,14 +100,21 @@ _FLIPS = {0: (False, False), 1: (False, True), 2: (True, False), 3: (True, True)
 
 
 class EvaluateVolume(EvaluateBase):
-    """Evaluate a model case by case (volume by volume)."""
+    """Evaluate a model case by case (volume by volume).
+
+    volumes_on="device" keeps a case's volumes on the device from the raw crop to the metrics (see the module docstring);
+    results are identical to "host".  It applies to --pred_type pred without --eval_in_patches: with --pred_type prob (an
+    order-1 zoom of float volumes) or patches the evaluator silently takes the host path."""
 
     def __init__(self, estimator=None, model_dir=None, params=None, merge_tumor_to_liver=True, largest=True,
-                 use_sg_reduce_fp=False, metrics_on="device"):
+                 use_sg_reduce_fp=False, metrics_on="device", volumes_on="host"):
         super(EvaluateVolume, self).__init__()
         if metrics_on not in ("device", "host"):
             raise ValueError("metrics_on must be 'device' or 'host', got {!r}".format(metrics_on))
+        if volumes_on not in ("device", "host"):
+            raise ValueError("volumes_on must be 'device' or 'host', got {!r}".format(volumes_on))
         self.metrics_on = metrics_on
+        self.volumes_on = volumes_on
         self.estimator = estimator
         self.model_dir = model_dir or (estimator.model_dir if estimator is not None else None)
         self.params = params or estimator.params
@@ -120,6 +134,21 @@ class EvaluateVolume(EvaluateBase):
     @property
     def metrics_str(self):
         return list(getattr(self.config, "metrics_eval", ["Dice"]))
+
+    def _device_volumes(self, dtype=None):
+        """Does this run keep its volumes on the device?  (volumes_on="device", class predictions, no patches.)"""
+        dtype = dtype or getattr(self.config, "pred_type", "pred")
+        return self.volumes_on == "device" and dtype == "pred" and not getattr(self.config, "eval_in_patches", False)
+
+    def _zoom_back(self, volume, ori_shape, dtype):
+        """Zoom a case's volume to ori_shape as the reference does (scipy.ndimage.zoom, order 0 for predictions and 1 for
+        probabilities): a device tensor is zoomed on the device (predictions only), a numpy array on the host."""
+        scales = np.array(ori_shape) / np.array(volume.shape)
+        if not np.any(scales != 1):
+            return volume
+        if torch.is_tensor(volume):
+            return ops.zoom_nearest3d(volume, ori_shape, ops.zoom_tables(tuple(volume.shape), ori_shape))
+        return ndi.zoom(volume, scales, order=0 if dtype == "pred" else 1)
 
     # ------------------------------------------------------------------ device side
     def _model(self):
@@ -151,7 +180,9 @@ class EvaluateVolume(EvaluateBase):
 
     def _predict_case(self, predicts, cases=-1, dtype="pred", resize=False, save_path=None):
         """evaluator_liver.py:616-678 with the accumulation on the device.  Yields
-        (case, segmentation, volume, post_processed)."""
+        (case, segmentation, volume, post_processed); volume is a numpy array, or with _device_volumes a uint8 device
+        tensor that was zoomed back on the device."""
+        on_device = self._device_volumes(dtype)
         slabs = []
         cur_case = None
         counter = 0
@@ -174,16 +205,16 @@ class EvaluateVolume(EvaluateBase):
                     volume = volume[:-pads]
                 if dtype == "pred":
                     amax, _ = ops.head_predict(volume.contiguous(), volume.shape[-1], want_preds=False)
-                    volume = amax.view(volume.shape[:-1]).cpu().numpy()  # np.argmax(volume, -1).astype(uint8)
+                    volume = amax.view(volume.shape[:-1])               # np.argmax(volume, -1).astype(uint8)
+                    if not on_device:
+                        volume = volume.cpu().numpy()
                 else:
                     volume = volume.cpu().numpy()
                 if resize and reshape_ori:
                     ori_shape = (volume.shape[0],) + arr_ops.bbox_to_shape(bbox)[1:]
                     if volume.ndim == 4:
                         ori_shape = ori_shape + (volume.shape[-1],)
-                    scales = np.array(ori_shape) / np.array(volume.shape)
-                    if np.any(scales != 1):
-                        volume = ndi.zoom(volume, scales, order=0 if dtype == "pred" else 1)
+                    volume = self._zoom_back(volume, ori_shape, dtype)
                 yield cur_case, segmentation, volume, False
                 slabs.clear()
                 cur_case = None
@@ -377,8 +408,10 @@ class EvaluateVolume(EvaluateBase):
         mode = getattr(self.config, "mode", ModeKeys.EVAL)
         patches = bool(getattr(self.config, "eval_in_patches", False))
 
+        params = dict(self.params, volumes_on="device") if self._device_volumes() else self.params
+
         def run_pred():
-            for features, labels in input_fn(mode, self.params):
+            for features, labels in input_fn(mode, params):
                 if features:
                     # host generators (the reference's contract: numpy slabs, data/lits.input_fn_eval) -> one upload per slab
                     features = {k: (torch.from_numpy(np.ascontiguousarray(v)).cuda() if isinstance(v, np.ndarray) else v)
@@ -447,20 +480,22 @@ class EvaluateVolume(EvaluateBase):
 
     def _predict_case_g(self, predicts, cases=-1, dtype="pred", save_path=None):
         """evaluator_liver.py:768-816: the combined probability volume of a case (already max(forward, flip_z(backward)) on
-        the device) -> argmax (or the probabilities with --pred_type prob) -> zoom back to the box."""
+        the device) -> argmax (or the probabilities with --pred_type prob) -> zoom back to the box (on the device with
+        _device_volumes, like _predict_case)."""
+        on_device = self._device_volumes(dtype)
         counter = 0
         for item, volume in predicts:
             if dtype == "pred":
                 amax, _ = ops.head_predict(volume.view(-1, volume.shape[-1]), volume.shape[-1], want_preds=False)
-                volume = amax.view(volume.shape[:-1]).cpu().numpy()
+                volume = amax.view(volume.shape[:-1])
+                if not on_device:
+                    volume = volume.cpu().numpy()
             else:
                 volume = volume.cpu().numpy()
             ori_shape = (volume.shape[0],) + arr_ops.bbox_to_shape(item["bbox"])[1:]
             if volume.ndim == 4:
                 ori_shape = ori_shape + (volume.shape[-1],)
-            scales = np.array(ori_shape) / np.array(volume.shape)
-            if np.any(scales != 1):
-                volume = ndi.zoom(volume, scales, order=0 if dtype == "pred" else 1)
+            volume = self._zoom_back(volume, ori_shape, dtype)
             yield str(item["pid"]), item["segmentation"], volume, False
             counter += 1
             if 0 < cases <= counter:
@@ -485,6 +520,8 @@ class EvaluateVolume(EvaluateBase):
             if do_eval and self.metrics_on == "device":
                 self._score_case_device(volume, labels, post_processed, accumulator, use_global)
             elif do_eval:
+                if torch.is_tensor(volume):                             # volumes_on="device" with the host metrics
+                    volume = volume.cpu().numpy()
                 if not post_processed:
                     volume = self._postprocess(volume)
                 labels = self._postprocess(labels, is_label=True)
@@ -520,10 +557,11 @@ class EvaluateVolume(EvaluateBase):
         return results
 
     def _score_case_device(self, volume, labels, post_processed, accumulator, use_global):
-        """One case of _run_actual on the device: one upload of the volume and one of the labels, then post-processing,
-        the global Dice counts and metric_3d_device per class."""
+        """One case of _run_actual on the device: one upload of the volume (none when it is a device tensor already:
+        volumes_on="device") and one of the labels, then post-processing, the global Dice counts and metric_3d_device per
+        class."""
         def upload(x):
-            return torch.from_numpy(np.ascontiguousarray(x)).cuda()
+            return x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x)).cuda()
         if post_processed:
             volume = {cls: upload(v) for cls, v in volume.items()}
         else:

@@ -1288,6 +1288,116 @@ def surface_distances(a, b, sampling=(1.0, 1.0, 1.0)):
     return tuple((vals[k][0], vals[k][1], vals[k][2], int(n[k])) for k in range(2))
 
 
+# ----------------------------------------------------------------------------- offline evaluation I/O (csrc/evalio.hip)
+def _device_table(t, dtype, n, device, what):
+    """A host array or a device tensor as a dense device tensor of `n` elements of `dtype` (one upload for a host array)."""
+    import numpy as np
+    if not torch.is_tensor(t):
+        t = torch.from_numpy(np.ascontiguousarray(t, dtype={torch.int32: np.int32, torch.float32: np.float32}[dtype])).to(device)
+    _require_cuda(t)
+    if t.dtype != dtype or t.numel() != n or not t.is_contiguous():
+        raise ValueError("{}: {} dense elements of {} expected, got {} of {}".format(what, n, dtype, tuple(t.shape), t.dtype))
+    return t
+
+
+def eval_slab(vol, zsrc, taps_y, taps_x, lut, out_hw, channels, window=(-200, 250), out=None):
+    """One network input slab f32 [N, H, W, C] from a case's resident raw crop (unetk_eval_slab): vol int16 [d, h, w] on the
+    device; zsrc int32 [N, C] the source slice of every sample and channel (-1: a plane of 0.0, -2: a plane of HU 0 passed
+    through the window); taps_y = (y0, y1, fy) of H entries and taps_x = (x0, x1, fx) of W entries, the bilinear taps of
+    data/lits.cv2_linear_taps; lut f32 [hi - lo + 1] the host's normalisation of every HU value of window = (lo, hi).
+    Tables may be host arrays (uploaded here) or device tensors (a caller serving many slabs uploads them once).  Bit-equal
+    to the host pipeline (window, then cv2_resize_linear).  out: a dense f32 [N, H, W, C] device tensor to write into."""
+    _require_cuda(vol)
+    if vol.dtype != torch.int16 or vol.dim() != 3 or not vol.is_contiguous():
+        raise ValueError("a dense int16 [d, h, w] volume expected, got {} {}".format(vol.dtype, tuple(vol.shape)))
+    h, w = int(out_hw[0]), int(out_hw[1])
+    c = int(channels)
+    lo, hi = int(window[0]), int(window[1])
+    dev = vol.device
+    n = int(zsrc.shape[0])
+    if tuple(zsrc.shape) != (n, c):
+        raise ValueError("zsrc must be [N, {}], got {}".format(c, tuple(zsrc.shape)))
+    zsrc = _device_table(zsrc, torch.int32, n * c, dev, "zsrc")
+    y0, y1 = (_device_table(t, torch.int32, h, dev, "taps_y") for t in taps_y[:2])
+    x0, x1 = (_device_table(t, torch.int32, w, dev, "taps_x") for t in taps_x[:2])
+    fy = _device_table(taps_y[2], torch.float32, h, dev, "taps_y")
+    fx = _device_table(taps_x[2], torch.float32, w, dev, "taps_x")
+    lut = _device_table(lut, torch.float32, int(lut.shape[0]) if hasattr(lut, "shape") else len(lut), dev, "lut")
+    if out is None:
+        out = torch.empty((n, h, w, c), dtype=torch.float32, device=dev)
+    _require_cuda(out)
+    if out.dtype != torch.float32 or tuple(out.shape) != (n, h, w, c) or not out.is_contiguous():
+        raise ValueError("out must be a dense f32 {} tensor".format((n, h, w, c)))
+    d, sh, sw = (int(s) for s in vol.shape)
+    with _timed_hbm("eval_slab", out, 1, 2 * 4 * out.numel()):           # the store + four int16 taps per element
+        check(_abi.lib().unetk_eval_slab(ptr(vol), d, sh, sw, ptr(zsrc), n, c, ptr(y0), ptr(y1), ptr(fy), h, ptr(x0), ptr(x1),
+                                         ptr(fx), w, ptr(lut), lut.numel(), lo, hi, ptr(out), stream_ptr()), "eval_slab")
+    return out
+
+
+_ZOOM_TABLES = {}
+
+
+def zoom_tables(in_shape, out_shape):
+    """Host side of zoom_nearest3d: per axis the int32 source index of every output sample of
+    scipy.ndimage.zoom(volume, np.array(out_shape) / np.array(in_shape), order=0), -1 where scipy's sample lands just
+    outside the input and becomes cval = 0 (the last sample of an axis for many size pairs: 32 -> 16, 64 -> 93, ...).
+    The order-0 zoom is separable, so the tables are asked of the installed scipy itself, axis by axis: the zoom of
+    1 .. n_in."""
+    import numpy as np
+    import scipy.ndimage as ndi
+    in_shape, out_shape = tuple(int(s) for s in in_shape), tuple(int(s) for s in out_shape)
+    if len(in_shape) != len(out_shape) or min(in_shape + out_shape) <= 0:
+        raise ValueError("zoom_tables: positive shapes of one rank expected, got {} and {}".format(in_shape, out_shape))
+    key = (in_shape, out_shape)
+    if key not in _ZOOM_TABLES:
+        scales = np.array(out_shape) / np.array(in_shape)                  # the evaluator's own expression
+        tables = []
+        for n_in, n_out, s in zip(in_shape, out_shape, scales):
+            t = np.rint(ndi.zoom(np.arange(1, n_in + 1, dtype=np.float64), s, order=0)).astype(np.int32) - 1
+            assert t.shape == (n_out,), (n_in, n_out, t.shape)
+            assert t.min() >= -1 and t.max() < n_in, (n_in, n_out)
+            tables.append(t)
+        if len(_ZOOM_TABLES) >= 256:
+            _ZOOM_TABLES.clear()
+        _ZOOM_TABLES[key] = tuple(tables)
+    return _ZOOM_TABLES[key]
+
+
+def zoom_nearest3d(vol_u8, out_shape, tables=None, out=None):
+    """scipy.ndimage.zoom(volume, out_shape / volume.shape, order=0) of a uint8 [d, h, w] device volume on the device
+    (unetk_zoom_nearest3d), voxel for voxel including scipy's zero samples just outside the input.  tables: the three host
+    index tables of zoom_tables (built when None); they are validated here and uploaded in one copy.  out: a dense uint8
+    device tensor of out_shape to write into."""
+    import numpy as np
+    _require_cuda(vol_u8)
+    if vol_u8.dtype != torch.uint8 or vol_u8.dim() != 3:
+        raise ValueError("a uint8 [d, h, w] volume expected, got {} {}".format(vol_u8.dtype, tuple(vol_u8.shape)))
+    vol_u8 = vol_u8.contiguous()
+    in_shape = tuple(int(s) for s in vol_u8.shape)
+    out_shape = tuple(int(s) for s in out_shape)
+    if tables is None:
+        tables = zoom_tables(in_shape, out_shape)
+    tables = [np.ascontiguousarray(t, dtype=np.int32) for t in tables]
+    if len(tables) != 3 or len(out_shape) != 3:
+        raise ValueError("three tables and a 3-D output shape expected")
+    for t, n_in, n_out in zip(tables, in_shape, out_shape):
+        if t.shape != (n_out,) or t.min() < -1 or t.max() >= n_in:
+            raise ValueError("zoom table of {} entries in [-1, {}) expected, got {} in [{}, {}]".format(
+                n_out, n_in, t.shape, t.min() if t.size else None, t.max() if t.size else None))
+    tabs = torch.from_numpy(np.concatenate(tables)).to(vol_u8.device)
+    dd, hh, ww = out_shape
+    if out is None:
+        out = torch.empty(out_shape, dtype=torch.uint8, device=vol_u8.device)
+    _require_cuda(out)
+    if out.dtype != torch.uint8 or tuple(out.shape) != out_shape or not out.is_contiguous():
+        raise ValueError("out must be a dense uint8 {} tensor".format(out_shape))
+    with _timed_hbm("zoom_nearest3d", out, 2):                          # one gathered read and one store per output voxel
+        check(_abi.lib().unetk_zoom_nearest3d(ptr(vol_u8), in_shape[0], in_shape[1], in_shape[2], ptr(tabs), ptr(tabs[dd:]),
+                                              ptr(tabs[dd + hh:]), dd, hh, ww, ptr(out), stream_ptr()), "zoom_nearest3d")
+    return out
+
+
 GUIDE_ROW = 12            # int32 words per component row of unetk_guide_components
 
 

@@ -599,6 +599,29 @@ int unetk_guide_components(const float* acc, const float* guide, int H, int W, i
                            size_t ws_bytes, void* stream);
 int unetk_guide_render(const float* obj, int n_obj, int H, int W, float discount, float* guide, void* stream);
 
+/* ---------------------------------------------------------------- offline evaluation: slabs in, zoom back
+ * The input and the output side of evaluators/evaluator_liver.py on the device (csrc/evalio.hip); both are gathers that
+ * write every output element once: no atomics, no workspace.
+ *
+ * Slab building (DataLoader/Liver/input_pipeline.py:556-668, input_pipeline_li.py:398-456): images f32 [N,H,W,C] dense =
+ * window-normalised, bilinearly resized planes of the resident raw crop vol int16 [src_d,src_h,src_w].  zsrc int32 [N,C]:
+ * the plane of every sample and channel: >= 0 a slice of vol, -1 a plane of exactly 0.0f, -2 a plane of HU 0 passed
+ * through the window (context padded before normalisation).  Window: HU is clamped into [lo, hi] and read from
+ * lut f32 [lut_n >= hi - lo + 1], lut[v - lo] = the host's normalisation of v (-32768 <= lo <= hi <= 32767, at most
+ * 16384 entries).  Resize: the host's six tap arrays y0, y1 int32 [H], fy f32 [H], x0, x1 int32 [W], fx f32 [W] (taps
+ * are clamped into the plane); rows first, r = a[y0] * (1 - fy) + a[y1] * fy, then columns r[x0] * (1 - fx) + r[x1] * fx,
+ * every product, sum and difference rounded to f32 on its own (no FMA): bit-equal to numpy's float32 arithmetic.
+ * src_d * src_h * src_w < 2^31 and N * H * W * C < 2^31; images 4-byte aligned (16-byte aligned: 16-byte stores). */
+int unetk_eval_slab(const int16_t* vol, int src_d, int src_h, int src_w, const int32_t* zsrc, int N, int C,
+                    const int32_t* y0, const int32_t* y1, const float* fy, int H, const int32_t* x0, const int32_t* x1,
+                    const float* fx, int W, const float* lut, int lut_n, int lo, int hi, float* images, void* stream);
+/* Zoom back (evaluator_liver.py:670-676, scipy.ndimage.zoom with order 0, separable): dst uint8 [D,H,W] dense,
+ * dst[z][y][x] = src[tz[z]][ty[y]][tx[x]] with src uint8 [d,h,w], tz int32 [D], ty int32 [H], tx int32 [W]; an index of
+ * -1 (any index outside its axis) writes 0: scipy's samples that land just outside the input.  d * h * w < 2^31 and
+ * D * H * W < 2^31. */
+int unetk_zoom_nearest3d(const uint8_t* src, int d, int h, int w, const int32_t* tz, const int32_t* ty, const int32_t* tx,
+                         int D, int H, int W, uint8_t* dst, void* stream);
+
 /* ---------------------------------------------------------------- LiTS training batch  
  * DataLoader/Liver/input_pipeline.py:243-284 `data_processing_train` for a whole batch, gathering from decoded slices
  * that are RESIDENT in device memory: per sample crop_to_bounding_box -> resize_bilinear(align_corners) -> window clip
