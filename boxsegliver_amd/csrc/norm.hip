@@ -1138,6 +1138,10 @@ extern "C" int unetk_norm_apply_relu_pool(const unetk_norm_desc* d, int W, const
 
 extern "C" size_t unetk_norm_bwd_ws_bytes(const unetk_norm_desc* d) {
   if (!norm_desc_ok(d) || !norm_supported(d)) return 0;
+  // what the backward refuses on the descriptor alone has no workspace either
+  if (d->storage != UNETK_FP32 && d->storage != UNETK_BF16S) return 0;
+  if (d->dropout_keep < 0.f || d->dropout_keep > 1.f) return 0;
+  if (d->guide_leaky != 0 && d->guide_ch < 1) return 0;
   // sized for the density variant (K + 2 rows, N launch groups): a superset of every other case
   const NormGeom g = geom(d, true);
   const int K = 5 + d->guide_ch;          // density + leaky guide + post-shift row: the largest variant

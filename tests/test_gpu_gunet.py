@@ -9,6 +9,7 @@ import torch
 
 from oracle import gunet2d
 from test_gpu_unet import check_deconv_backward, check_unit_backward, rel
+from unetk_rng import fc_uniform_host, unit_mask_host          # shared with test_gpu_norm_paths.py
 
 pytestmark = pytest.mark.gpu
 
@@ -149,15 +150,6 @@ def test_gunet_trains_and_checkpoint_names():
 
 
 # ----------------------------------------------------------------------------- context (density) branch, GUNet.py:31-60
-def fc_uniform_host(seed, idx):
-    """The counter RNG of unetk_fc_fwd's dropout mask (csrc/fc.hip), restated in numpy."""
-    h = (idx.astype(np.uint64) * 0x9E3779B1 + seed) & 0xFFFFFFFF
-    h ^= h >> 16
-    h = (h * 0x85EBCA6B) & 0xFFFFFFFF
-    h ^= h >> 13
-    h = (h * 0xC2B2AE35) & 0xFFFFFFFF
-    h ^= h >> 16
-    return (h >> 8).astype(np.float32) * np.float32(1.0 / 16777216.0)
 
 
 @pytest.mark.parametrize("bsz,k,n,relu,keep", [(2, 10, 256, True, None), (8, 256, 1000, True, 0.5), (3, 256, 3968, False, None),
@@ -584,13 +576,6 @@ def test_unetinter_matches_oracle_and_trains(normalizer, mid_cat):
 
 
 # ----------------------------------------------------------------------------- --dropout / --fix / --use_se (GUNet.py:189-201,299-304)
-def unit_mask_host(seed, shape, keep):
-    """The 0 | 1/keep mask the norm kernels regenerate: unetk_uniform(seed, flat NHWC element index) < keep."""
-    idx = np.arange(int(np.prod(shape)), dtype=np.uint64)
-    u = fc_uniform_host(seed & 0xFFFFFFFF, idx).reshape(shape)
-    return np.where(u < np.float32(keep), np.float32(1.0 / keep), np.float32(0.0)).astype(np.float32)
-
-
 @pytest.mark.parametrize("per_sample,g_ch,with_den,leaky", [(True, 0, False, False), (False, 1, False, False), (True, 2, True, False),
                                                             (False, 0, True, False), (True, 1, False, True)])
 def test_norm_dropout_forward_backward(per_sample, g_ch, with_den, leaky):
