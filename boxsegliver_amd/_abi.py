@@ -64,8 +64,18 @@ class LitsGuideDesc(Structure):
                 ("n_obj", c_int32), ("min_std", c_float)]
 
 
+class Lits3dDesc(Structure):
+    _fields_ = [("N", c_int32), ("D", c_int32), ("H", c_int32), ("W", c_int32), ("n_slices", c_int32), ("src_h", c_int32),
+                ("src_w", c_int32), ("im_scale", c_int32), ("lab_scale", c_int32), ("lab_max", c_int32), ("training", c_int32)]
+
+
+LITS3D_TAB_COLS = 16        # UNETK_LITS3D_TAB_COLS
+
 P = c_void_p
 _SIGNATURES = {
+    "unetk_lits_pick_voxel": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P]),
+    "unetk_lits_patch3d_ws_bytes": (c_size_t, [POINTER(Lits3dDesc)]),
+    "unetk_lits_patch3d": (c_int, [POINTER(Lits3dDesc), P, P, P, P, P, P, c_size_t, P]),
     "unetk_lits_batch": (c_int, [POINTER(LitsDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "unetk_lits_spatial_guide": (c_int, [POINTER(LitsGuideDesc), P, P, P, P, P]),
     "unetk_lits_context": (c_int, [P, c_int64, c_int, P, c_int, c_int, P, P, P, P]),

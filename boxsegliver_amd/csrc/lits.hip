@@ -11,6 +11,7 @@
 //   clip row (float):         [window lo, window hi]          (IM_SCALE units, input_pipeline.py:370-373)
 // HBM-bound and tiny: reads <= 4 source pixels per output value.
 #include "common.h"
+#include "lits_geom.h"
 
 namespace {
 
@@ -40,13 +41,11 @@ __global__ __launch_bounds__(256) void lits_batch_kernel(unetk_lits_desc d, cons
     // random flips act on the finished sample: output (y, x) shows source position (sy, sx)
     const int sx = t[d.C + 5] ? d.W - 1 - x : x;
     const int sy = t[d.C + 6] ? d.H - 1 - y : y;
-    // align_corners: in = out * (in_size - 1) / (out_size - 1)
-    const float hs = d.H > 1 ? (float)(ch - 1) / (float)(d.H - 1) : 0.f;
-    const float ws = d.W > 1 ? (float)(cw - 1) / (float)(d.W - 1) : 0.f;
-    const float in_y = sy * hs, in_x = sx * ws;
-    const int y0 = (int)floorf(in_y), x0 = (int)floorf(in_x);
-    const int y1 = min(y0 + 1, ch - 1), x1 = min(x0 + 1, cw - 1);
-    const float ly = in_y - y0, lx = in_x - x0;
+    // align_corners source coordinate and taps: lits_geom.h (shared with the 3-D patch kernel)
+    const float in_y = sy * lits_ac_scale(ch, d.H), in_x = sx * lits_ac_scale(cw, d.W);
+    const LitsTaps ty = lits_ac_taps(in_y, ch), tx = lits_ac_taps(in_x, cw);
+    const int y0 = ty.i0, y1 = ty.i1, x0 = tx.i0, x1 = tx.i1;
+    const float ly = ty.f, lx = tx.f;
     const float lo = clip[2 * n], hi = clip[2 * n + 1];
     const int64_t plane = (int64_t)d.src_h * d.src_w;
     for (int c = 0; c < d.C; ++c) {
@@ -56,8 +55,7 @@ __global__ __launch_bounds__(256) void lits_batch_kernel(unetk_lits_desc d, cons
         const uint16_t* p = slices + s * plane + (int64_t)off_y * d.src_w + off_x;
         const float tl = p[(int64_t)y0 * d.src_w + x0], tr = p[(int64_t)y0 * d.src_w + x1];
         const float bl = p[(int64_t)y1 * d.src_w + x0], br = p[(int64_t)y1 * d.src_w + x1];
-        const float top = tl + (tr - tl) * lx, bot = bl + (br - bl) * lx;     // tf resize_bilinear's lerp order
-        v = top + (bot - top) * ly;
+        v = lits_bilerp(tl, tr, bl, br, lx, ly);                              // tf resize_bilinear's lerp order
         v = (fminf(fmaxf(v, lo), hi) - lo) / (hi - lo);
         if (d.noise_scale > 0.f)   // noise is drawn per FINAL pixel (after the flip in the reference too)
           v += (2.f * u01(d.seed, ((uint64_t)i * d.C + c)) - 1.f) * d.noise_scale;
@@ -67,7 +65,7 @@ __global__ __launch_bounds__(256) void lits_batch_kernel(unetk_lits_desc d, cons
     int lab = 0;
     const int ls = t[d.C];
     if (ls >= 0 && ls < d.n_slices) {
-      const int ny = min((int)roundf(in_y), ch - 1), nx = min((int)roundf(in_x), cw - 1);   // nearest, align_corners
+      const int ny = lits_ac_nearest(in_y, ch), nx = lits_ac_nearest(in_x, cw);
       lab = segs[ls * plane + (int64_t)(off_y + ny) * d.src_w + off_x + nx] / d.lab_scale;
     }
     labels[i] = lab;
@@ -112,18 +110,15 @@ __global__ __launch_bounds__(256) void lits_guide_kernel(unetk_lits_guide_desc d
     const int ch = min(max(t[d.C + 3], 1), d.src_h - off_y), cw = min(max(t[d.C + 4], 1), d.src_w - off_x);
     const int sx = t[d.C + 5] ? d.W - 1 - x : x;
     const int sy = t[d.C + 6] ? d.H - 1 - y : y;
-    const float hs = d.H > 1 ? (float)(ch - 1) / (float)(d.H - 1) : 0.f;
-    const float ws = d.W > 1 ? (float)(cw - 1) / (float)(d.W - 1) : 0.f;
-    const float in_y = sy * hs, in_x = sx * ws;
-    const int y0 = (int)floorf(in_y), x0 = (int)floorf(in_x);
-    const int y1 = min(y0 + 1, ch - 1), x1 = min(x0 + 1, cw - 1);
-    const float ly = in_y - y0, lx = in_x - x0;
+    const float in_y = sy * lits_ac_scale(ch, d.H), in_x = sx * lits_ac_scale(cw, d.W);
+    const LitsTaps ty = lits_ac_taps(in_y, ch), tx = lits_ac_taps(in_x, cw);
+    const int y0 = ty.i0, y1 = ty.i1, x0 = tx.i0, x1 = tx.i1;
+    const float ly = ty.f, lx = tx.f;
     const float tl = guide_at((float)y0, (float)x0, obj, k0, k1, d.min_std);
     const float tr = guide_at((float)y0, (float)x1, obj, k0, k1, d.min_std);
     const float bl = guide_at((float)y1, (float)x0, obj, k0, k1, d.min_std);
     const float br = guide_at((float)y1, (float)x1, obj, k0, k1, d.min_std);
-    const float top = tl + (tr - tl) * lx, bot = bl + (br - bl) * lx;     // tf resize_bilinear's lerp order
-    guide[i] = (top + (bot - top) * ly) / 2.f + 0.5f;
+    guide[i] = lits_bilerp(tl, tr, bl, br, lx, ly) / 2.f + 0.5f;         // tf resize_bilinear's lerp order
   }
 }
 

@@ -1,0 +1,383 @@
+// 3-D training patches for UNet3D, cropped and normalised on the device from the resident LiTS slice store.
+//
+// The reference has no LiTS 3-D pipeline; the semantics are those of its 3-D pipeline for the NF data
+// (DataLoader/NF/input_pipeline_3d.py:544-604 gen_batch, :352-407 data_processing; DataLoader/misc.py:132-143 volume_crop;
+// utils/image_ops.py:241 random_flip, :339-354 augment_gamma), the volumes are the cases of data/lits.SliceStore:
+//   crop D x ch x cw around a centre -> z-score over the crop's non-zero voxels -> resize_bilinear(align_corners) to H x W per
+//   slice -> flips -> (training) gamma with retain_stats; labels nearest.
+// Everything per-sample arrives in ONE int32 table (include/unetk.h: UNETK_LITS3D_TAB_COLS); the forced-class centres are
+// picked on the device (unetk_lits_pick_voxel) straight into that table, so a batch never synchronises the host.
+//
+// All kernels are HBM-bound passes over a few MB per sample.  The reductions (mask moments, patch moments, min / max) go
+// through fp64 per-block partials in the workspace and a finalising block that walks them by index: no floating-point
+// atomics, identical bits on every call.
+//   workspace: double sums[N][P][3], float minmax[N][P][2] (the blocks' partials: see "block reductions"), then
+//              float stat[N][8] = {m, s, mn, sd, min, range, new_mn, new_sd}
+#include "common.h"
+#include "lits_geom.h"
+
+namespace {
+
+constexpr int TW = UNETK_LITS3D_TAB_COLS;
+constexpr int P3D_MAX_BLOCKS = 256;      // partial blocks per sample
+constexpr int P3D_VOX_PER_BLOCK = 4096;
+enum { ST_M = 0, ST_S, ST_MN, ST_SD, ST_MIN, ST_RNG, ST_NMN, ST_NSD, ST_N };
+
+inline int p3d_blocks(const unetk_lits3d_desc* d) {
+  const int64_t vox = (int64_t)d->D * d->H * d->W;
+  const int64_t p = (vox + P3D_VOX_PER_BLOCK - 1) / P3D_VOX_PER_BLOCK;
+  return (int)(p < 1 ? 1 : (p > P3D_MAX_BLOCKS ? P3D_MAX_BLOCKS : p));
+}
+
+// ------------------------------------------------------------------------------------------------ forced-class centre
+// One block per sample; thread t owns the contiguous pixels [t L, (t + 1) L) of the slice, so a block-wide exclusive
+// prefix of the per-thread counts orders the forced-class pixels row-major.
+__global__ __launch_bounds__(1024) void lits_pick_voxel_kernel(const uint8_t* __restrict__ segs, int n_slices, int src_h, int src_w,
+                                                              int thr, int32_t* __restrict__ tab, int32_t* __restrict__ status) {
+  __shared__ int wtot[16];
+  int32_t* t = tab + (int64_t)blockIdx.x * TW;
+  if (t[11] == 0) return;                                    // uniform sample: keeps the (cy, cx) the host drew
+  const int64_t s = (int64_t)t[0] + t[2];
+  const int k = t[12];
+  const bool ok = s >= 0 && s < n_slices && k >= 0;          // block-uniform
+  const int hw = src_h * src_w;
+  const int L = (hw + 1023) / 1024;
+  const int lo = min((int)threadIdx.x * L, hw), hi = min(lo + L, hw);
+  const uint8_t* p = segs + (ok ? s : 0) * (int64_t)hw;
+  int cnt = 0;
+  if (ok)
+    for (int i = lo; i < hi; ++i) cnt += p[i] >= thr ? 1 : 0;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int incl = cnt;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(incl, o);
+    if (lane >= o) incl += v;
+  }
+  if (lane == 63) wtot[wave] = incl;
+  __syncthreads();
+  int woff = 0, total = 0;
+  for (int w = 0; w < 16; ++w) {
+    if (w < wave) woff += wtot[w];
+    total += wtot[w];
+  }
+  const int excl = woff + incl - cnt;
+  if (ok && k >= excl && k < excl + cnt) {                   // exactly one thread when k < total
+    int r = k - excl;
+    for (int i = lo; i < hi; ++i) {
+      if (p[i] >= thr) {
+        if (r == 0) {
+          t[3] = i / src_w;
+          t[4] = i - (i / src_w) * src_w;
+          break;
+        }
+        --r;
+      }
+    }
+  }
+  if (threadIdx.x == 0 && (!ok || k >= total)) {             // a caller bug: flagged, and a centre that is always valid
+    t[3] = 0;
+    t[4] = 0;
+    atomicOr(status, 1);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ crop box
+struct Box3 {
+  int64_t base;
+  int depth, z1, y1, x1, ch, cw;
+};
+// DataLoader/misc.py:132-143 volume_crop, with the crop clamped to the slice and a case shallower than D starting at 0
+__device__ __forceinline__ Box3 p3d_box(const int32_t* __restrict__ t, const unetk_lits3d_desc& d) {
+  Box3 b;
+  b.base = t[0];
+  b.depth = max(t[1], 0);
+  b.ch = min(max(t[5], 1), d.src_h);
+  b.cw = min(max(t[6], 1), d.src_w);
+  b.z1 = min(max(t[2] - d.D / 2, 0), max(b.depth - d.D, 0));
+  b.y1 = min(max(t[3] - b.ch / 2, 0), d.src_h - b.ch);
+  b.x1 = min(max(t[4] - b.cw / 2, 0), d.src_w - b.cw);
+  return b;
+}
+// store index of crop slice z, or -1 where the crop leaves the case (or the store): zeros, label 0
+__device__ __forceinline__ int64_t p3d_slice(const Box3& b, int z, const unetk_lits3d_desc& d) {
+  const int zs = b.z1 + z;
+  const int64_t s = b.base + zs;
+  return (zs < b.depth && s >= 0 && s < d.n_slices) ? s : -1;
+}
+
+// ------------------------------------------------------------------------------------------------ block reductions
+// Partials of one block, the same layout in every pass (workspace: sums[N][P][3] doubles, then minmax[N][P][2] floats):
+//   sums   = {number of values, their sum, their sum of squares}
+//   minmax = {min, max}                       (written by the patch pass only)
+// Each is reduced in a fixed order: an xor butterfly inside the wave, then the four waves by index.
+__device__ __forceinline__ void block_sum3(double cnt, double sum, double sq, double* __restrict__ dst) {
+  __shared__ double sh[4][3];
+  cnt = wave_sum_d(cnt);
+  sum = wave_sum_d(sum);
+  sq = wave_sum_d(sq);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    sh[wave][0] = cnt;
+    sh[wave][1] = sum;
+    sh[wave][2] = sq;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double r0 = 0., r1 = 0., r2 = 0.;
+    for (int w = 0; w < 4; ++w) {
+      r0 += sh[w][0];
+      r1 += sh[w][1];
+      r2 += sh[w][2];
+    }
+    dst[0] = r0;
+    dst[1] = r1;
+    dst[2] = r2;
+  }
+  __syncthreads();
+}
+__device__ __forceinline__ void block_minmax(float lo, float hi, float* __restrict__ dst) {
+  __shared__ float sh[4][2];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    lo = fminf(lo, __shfl_xor(lo, o));
+    hi = fmaxf(hi, __shfl_xor(hi, o));
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    sh[wave][0] = lo;
+    sh[wave][1] = hi;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) {
+      lo = fminf(lo, sh[w][0]);
+      hi = fmaxf(hi, sh[w][1]);
+    }
+    dst[0] = lo;
+    dst[1] = hi;
+  }
+  __syncthreads();
+}
+
+// ------------------------------------------------------------------------------------------------ pass 1: mask moments
+// data_processing :354-357: moments over the crop's voxels with v > 0, at SOURCE resolution.  v = stored / im_scale is an
+// integer multiple of 1 / im_scale, so the fp64 sums are exact.
+__global__ __launch_bounds__(256) void p3d_mask_stats_kernel(unetk_lits3d_desc d, const uint16_t* __restrict__ slices,
+                                                             const int32_t* __restrict__ tab, double* __restrict__ part) {
+  const int n = blockIdx.y, P = gridDim.x;
+  const Box3 b = p3d_box(tab + (int64_t)n * TW, d);
+  const int64_t plane = (int64_t)d.src_h * d.src_w;
+  const int area = b.ch * b.cw;
+  const int total = d.D * area;                              // < 2^31: checked by the entry point
+  const float scale = (float)d.im_scale;
+  double cnt = 0., sum = 0., sq = 0.;
+  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < total; i += P * 256) {
+    const int z = (int)(i / area), r = (int)(i - (int64_t)z * area);
+    const int y = r / b.cw, x = r - y * b.cw;
+    const int64_t s = p3d_slice(b, z, d);
+    if (s < 0) continue;
+    const float v = (float)slices[s * plane + (int64_t)(b.y1 + y) * d.src_w + b.x1 + x] / scale;
+    if (v > 0.f) {
+      cnt += 1.;
+      sum += (double)v;
+      sq += (double)v * (double)v;
+    }
+  }
+  block_sum3(cnt, sum, sq, part + ((int64_t)n * P + blockIdx.x) * 3);
+}
+
+// ------------------------------------------------------------------------------------------------ finalising block
+// One wave per sample walks the P partials by index (lane l takes l, l + 64, ...; then a fixed butterfly): mean and
+// standard deviation of the values the pass counted, and in stage 1 their min and range.
+//   stage 0 (mask moments)  -> m, s                    (empty mask: 0, 0)
+//   stage 1 (patch)         -> mn, sd, min, range      of the normalised patch
+//   stage 2 (gamma)         -> new_mn, new_sd          of the gamma-mapped patch
+__global__ __launch_bounds__(64) void p3d_finalize_kernel(int stage, int P, const double* __restrict__ part,
+                                                          const float* __restrict__ minmax, float* __restrict__ stat) {
+  const int n = blockIdx.x, lane = threadIdx.x;
+  const double* p = part + (int64_t)n * P * 3;
+  const float* mm = minmax + (int64_t)n * P * 2;
+  double cnt = 0., sum = 0., sq = 0.;
+  float lo = INFINITY, hi = -INFINITY;
+  for (int i = lane; i < P; i += 64) {
+    cnt += p[i * 3 + 0];
+    sum += p[i * 3 + 1];
+    sq += p[i * 3 + 2];
+    if (stage == 1) {
+      lo = fminf(lo, mm[i * 2 + 0]);
+      hi = fmaxf(hi, mm[i * 2 + 1]);
+    }
+  }
+  cnt = wave_sum_d(cnt);
+  sum = wave_sum_d(sum);
+  sq = wave_sum_d(sq);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    lo = fminf(lo, __shfl_xor(lo, o));
+    hi = fmaxf(hi, __shfl_xor(hi, o));
+  }
+  if (lane != 0) return;
+  double m = 0., var = 0.;
+  if (cnt > 0.) {
+    m = sum / cnt;
+    var = fmax(sq / cnt - m * m, 0.);
+  }
+  float* st = stat + (int64_t)n * ST_N;
+  if (stage == 0) {
+    st[ST_M] = (float)m;
+    st[ST_S] = (float)sqrt(var);
+  } else if (stage == 1) {
+    st[ST_MN] = (float)m;
+    st[ST_SD] = (float)sqrt(var);
+    st[ST_MIN] = lo;
+    st[ST_RNG] = hi - lo;
+  } else {
+    st[ST_NMN] = (float)m;
+    st[ST_NSD] = (float)sqrt(var);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ pass 2: the patch
+// Voxel (z, y, x) of the resized, un-flipped patch; the flips are its write address.
+__global__ __launch_bounds__(256) void p3d_patch_kernel(unetk_lits3d_desc d, const uint16_t* __restrict__ slices,
+                                                        const uint8_t* __restrict__ segs, const int32_t* __restrict__ tab,
+                                                        const float* __restrict__ stat, float* __restrict__ images,
+                                                        int32_t* __restrict__ labels, double* __restrict__ part,
+                                                        float* __restrict__ minmax) {
+  const int n = blockIdx.y, P = gridDim.x;
+  const int32_t* t = tab + (int64_t)n * TW;
+  const Box3 b = p3d_box(t, d);
+  const bool flr = t[7] != 0, fud = t[8] != 0, ffb = t[9] != 0;
+  const float m = stat[(int64_t)n * ST_N + ST_M], den = stat[(int64_t)n * ST_N + ST_S] + 1e-8f;
+  const float scale = (float)d.im_scale;
+  const float hs = lits_ac_scale(b.ch, d.H), ws = lits_ac_scale(b.cw, d.W);
+  const int64_t plane = (int64_t)d.src_h * d.src_w;
+  const int area = d.H * d.W;
+  const int total = d.D * area;                              // < 2^31: checked by the entry point
+  float* img = images + (int64_t)n * total;
+  int32_t* lab = labels + (int64_t)n * total;
+  double cnt = 0., sum = 0., sq = 0.;
+  float lo = INFINITY, hi = -INFINITY;
+  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < total; i += P * 256) {
+    const int z = (int)(i / area), r = (int)(i - (int64_t)z * area);
+    const int y = r / d.W, x = r - y * d.W;
+    const float in_y = y * hs, in_x = x * ws;
+    float v = 0.f;
+    int l = 0;
+    const int64_t s = p3d_slice(b, z, d);
+    if (s >= 0) {
+      const LitsTaps ty = lits_ac_taps(in_y, b.ch), tx = lits_ac_taps(in_x, b.cw);
+      const uint16_t* p = slices + s * plane + (int64_t)b.y1 * d.src_w + b.x1;
+      // z-score of each corner, then the lerp (data_processing :359 before :381): (img - region mean) / (region sd + 1e-8)
+      float c[4] = {(float)p[(int64_t)ty.i0 * d.src_w + tx.i0], (float)p[(int64_t)ty.i0 * d.src_w + tx.i1],
+                    (float)p[(int64_t)ty.i1 * d.src_w + tx.i0], (float)p[(int64_t)ty.i1 * d.src_w + tx.i1]};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float cv = c[j] / scale;
+        c[j] = cv > 0.f ? (cv - m) / den : 0.f;
+      }
+      v = lits_bilerp(c[0], c[1], c[2], c[3], tx.f, ty.f);
+      const int ny = lits_ac_nearest(in_y, b.ch), nx = lits_ac_nearest(in_x, b.cw);
+      l = min((int)segs[s * plane + (int64_t)(b.y1 + ny) * d.src_w + b.x1 + nx] / d.lab_scale, d.lab_max);
+    }
+    const int zo = ffb ? d.D - 1 - z : z, yo = fud ? d.H - 1 - y : y, xo = flr ? d.W - 1 - x : x;
+    const int o = (zo * d.H + yo) * d.W + xo;
+    img[o] = v;
+    lab[o] = l;
+    cnt += 1.;
+    sum += (double)v;
+    sq += (double)v * (double)v;
+    lo = fminf(lo, v);
+    hi = fmaxf(hi, v);
+  }
+  if (d.training) {
+    block_sum3(cnt, sum, sq, part + ((int64_t)n * P + blockIdx.x) * 3);
+    block_minmax(lo, hi, minmax + ((int64_t)n * P + blockIdx.x) * 2);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ passes 3, 4: gamma
+// augment_gamma (image_ops.py:339-354), retain_stats=True, in float32 as the reference: the accurate powf.
+__global__ __launch_bounds__(256) void p3d_gamma_kernel(unetk_lits3d_desc d, const int32_t* __restrict__ tab,
+                                                        const float* __restrict__ stat, float* __restrict__ images,
+                                                        double* __restrict__ part) {
+  const int n = blockIdx.y, P = gridDim.x;
+  const float gamma = __int_as_float(tab[(int64_t)n * TW + 10]);
+  const float* st = stat + (int64_t)n * ST_N;
+  const float minm = st[ST_MIN], rnge = st[ST_RNG];
+  const int total = d.D * d.H * d.W;
+  float* img = images + (int64_t)n * total;
+  double cnt = 0., sum = 0., sq = 0.;
+  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < total; i += P * 256) {
+    const float y = powf((img[i] - minm) / (rnge + 1e-7f), gamma) * rnge + minm;
+    img[i] = y;
+    cnt += 1.;
+    sum += (double)y;
+    sq += (double)y * (double)y;
+  }
+  block_sum3(cnt, sum, sq, part + ((int64_t)n * P + blockIdx.x) * 3);
+}
+
+__global__ __launch_bounds__(256) void p3d_retain_kernel(unetk_lits3d_desc d, const float* __restrict__ stat,
+                                                         float* __restrict__ images) {
+  const int n = blockIdx.y, P = gridDim.x;
+  const float* st = stat + (int64_t)n * ST_N;
+  const float mn = st[ST_MN], sd = st[ST_SD], nmn = st[ST_NMN], nden = st[ST_NSD] + 1e-8f;
+  const int total = d.D * d.H * d.W;
+  float* img = images + (int64_t)n * total;
+  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < total; i += P * 256) img[i] = (img[i] - nmn + mn) / nden * sd;
+}
+
+bool p3d_supported(const unetk_lits3d_desc* d) {
+  return (int64_t)d->D * d->H * d->W < ((int64_t)1 << 31) && (int64_t)d->D * d->src_h * d->src_w < ((int64_t)1 << 31);
+}
+bool p3d_valid(const unetk_lits3d_desc* d) {
+  return d && d->N > 0 && d->N <= 65535 && d->D > 0 && d->H > 0 && d->W > 0 && d->n_slices > 0 && d->src_h > 0 && d->src_w > 0 &&
+         d->im_scale > 0 && d->lab_scale > 0 && d->lab_max > 0;
+}
+
+}  // namespace
+
+extern "C" int unetk_lits_pick_voxel(const uint8_t* seg_slices, int n_slices, int src_h, int src_w, int lab_scale, int fg_label,
+                                     int32_t* sample_tab, int N, int32_t* status, void* stream) {
+  UNETK_REQUIRE(seg_slices && sample_tab && status && n_slices > 0 && src_h > 0 && src_w > 0 && N > 0 && lab_scale > 0 && fg_label > 0);
+  UNETK_REQUIRE((int64_t)src_h * src_w < ((int64_t)1 << 30) && (int64_t)lab_scale * fg_label < ((int64_t)1 << 31));
+  UNETK_REQUIRE(((((uintptr_t)sample_tab) | ((uintptr_t)status)) & 3u) == 0);
+  UNETK_LAUNCH(lits_pick_voxel_kernel, dim3(N), dim3(1024), 0, (hipStream_t)stream, seg_slices, n_slices, src_h, src_w,
+               lab_scale * fg_label, sample_tab, status);      // seg / lab_scale >= fg  <=>  seg >= fg * lab_scale
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
+extern "C" size_t unetk_lits_patch3d_ws_bytes(const unetk_lits3d_desc* d) {
+  if (!p3d_valid(d) || !p3d_supported(d)) return 0;
+  return (size_t)d->N * p3d_blocks(d) * (3 * sizeof(double) + 2 * sizeof(float)) + (size_t)d->N * ST_N * sizeof(float);
+}
+
+extern "C" int unetk_lits_patch3d(const unetk_lits3d_desc* d, const uint16_t* slices, const uint8_t* seg_slices,
+                                  const int32_t* sample_tab, float* images, int32_t* labels, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  UNETK_REQUIRE(p3d_valid(d) && slices && seg_slices && sample_tab && images && labels && ws);
+  UNETK_REQUIRE((((uintptr_t)slices) & 1u) == 0 && ((((uintptr_t)sample_tab) | ((uintptr_t)images) | ((uintptr_t)labels)) & 3u) == 0);
+  UNETK_REQUIRE(unetk_aligned16(ws));
+  if (!p3d_supported(d)) return UNETK_E_UNSUPPORTED;
+  if (ws_bytes < unetk_lits_patch3d_ws_bytes(d)) return UNETK_E_WORKSPACE;
+  const int P = p3d_blocks(d);
+  double* part = static_cast<double*>(ws);
+  float* minmax = reinterpret_cast<float*>(part + (size_t)d->N * P * 3);
+  float* stat = minmax + (size_t)d->N * P * 2;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(P, d->N), fin(d->N);
+  UNETK_LAUNCH(p3d_mask_stats_kernel, grid, dim3(256), 0, st, *d, slices, sample_tab, part);
+  UNETK_LAUNCH(p3d_finalize_kernel, fin, dim3(64), 0, st, 0, P, (const double*)part, (const float*)minmax, stat);
+  UNETK_LAUNCH(p3d_patch_kernel, grid, dim3(256), 0, st, *d, slices, seg_slices, sample_tab, (const float*)stat, images, labels, part, minmax);
+  if (d->training) {
+    UNETK_LAUNCH(p3d_finalize_kernel, fin, dim3(64), 0, st, 1, P, (const double*)part, (const float*)minmax, stat);
+    UNETK_LAUNCH(p3d_gamma_kernel, grid, dim3(256), 0, st, *d, sample_tab, (const float*)stat, images, part);
+    UNETK_LAUNCH(p3d_finalize_kernel, fin, dim3(64), 0, st, 2, P, (const double*)part, (const float*)minmax, stat);
+    UNETK_LAUNCH(p3d_retain_kernel, grid, dim3(256), 0, st, *d, (const float*)stat, images);
+  }
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}

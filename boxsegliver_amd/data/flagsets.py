@@ -110,6 +110,9 @@ PIPELINES = {
                "--sample_neg", "--use_cascade", "--cascade_binary", "--use_2d", "--downsampling", "--model_2d",
                "--model_2d_config", "--ckpt_2d"],
               {"--im_channel": 1, "--zoom_scale": (1.0, 1.25), "--stddev": [1, 3., 3.]}),
+    # UNet3D on LiTS (data/lits3d.py): the flags of DataLoader/NF/input_pipeline_3d.py:53-67 that apply, its defaults
+    "liver_3d": (["--test_fold", "--im_depth", "--im_height", "--im_width", "--im_channel", "--zoom_scale", "--random_flip",
+                  "--eval_num_batches_per_epoch", "--tumor_percent"], {"--im_channel": 1, "--zoom_scale": (1.0, 1.25)}),
 }
 
 

@@ -1,0 +1,245 @@
+"""LiTS training input pipeline for UNet3D: 3-D patches cropped, z-scored, resized, flipped and gamma-augmented on the
+device from the resident slice store.
+
+The reference has no LiTS 3-D training pipeline (only DataLoader/Liver/preprocess_3d.py, a one-off resampler).  The
+semantics here are those of its 3-D pipeline for the NF data, the volumes are the LiTS cases of `data/lits.SliceStore`:
+  * DataLoader/NF/input_pipeline_3d.py:544-604 `gen_batch` -> `PatchSampler` (which cases, which centres, zoom, and the
+    draws the reference leaves to TensorFlow: flip coins and gamma);
+  * :352-407 `data_processing` (without the use_spatial / cascade branches), DataLoader/misc.py:132-143 `volume_crop`,
+    utils/image_ops.py:241 `random_flip`, :339-354 `augment_gamma` -> `unetk_lits_patch3d` (csrc/lits3d.hip).
+TensorFlow does not run here: the arithmetic is pinned by the float64 restatement in tests/lits3d_ref.py, which cites the
+same lines ("parity unpinned").
+
+A batch costs the host one vectorised sampler draw and ONE pinned upload of the int32 sample table; the centre of a
+forced-class sample is picked on the device (`unetk_lits_pick_voxel`) from a (slice, rank) pair, so no voxel position
+table exists anywhere and nothing synchronises the host with the device.
+
+Two deviations from the literal reference arithmetic: a case shallower than --im_depth is cropped from slice 0 and padded
+with zero slices (the reference would index with a negative start), and a patch without a single non-zero voxel is all
+zeros (TensorFlow's moments of an empty tensor are NaN)."""
+import math
+
+import numpy as np
+import torch
+
+from .. import _abi, ops
+from ..utils import distribution_utils
+from . import flagsets, lits
+
+EVAL_ZOOM = 1.125                  # gen_batch(train=False): zoom = (1.125, 1.125)   (input_pipeline_3d.py:570-572)
+GAMMA_RANGE = (0.7, 1.5)           # data_processing :405
+GAMMA_P = 0.3
+LABEL_MAPS = (("Liver",), ("Liver", "Tumor"))
+(COL_BASE, COL_DEPTH, COL_CZ, COL_CY, COL_CX, COL_CH, COL_CW, COL_FLIP_LR, COL_FLIP_UD, COL_FLIP_FB, COL_GAMMA, COL_FORCED,
+ COL_K) = range(13)
+
+
+def add_arguments(parser):
+    """The flags of DataLoader/NF/input_pipeline_3d.py:53-67 that apply (names / defaults verbatim, data/flagsets.py) +
+    --lits_root and --seed as the 2-D LiTS sub-commands add them."""
+    flagsets.add_arguments(parser, "liver_3d")
+    parser.add_argument("--lits_root", type=str, default="data/LiTS", help="where png/, meta.json and k_folds.txt live")
+    parser.add_argument("--seed", type=int, default=1234)
+
+
+def check_args(args):
+    if int(getattr(args, "im_channel", 1)) != 1:
+        raise ValueError("the LiTS 3-D patches have one channel, got --im_channel {}".format(args.im_channel))
+    return label_map(args.classes)
+
+
+def label_map(classes):
+    """--classes -> (lab_max, fg_label), as the 2-D LiTS pipelines map them: `Liver Tumor` keeps the stored labels
+    {0, 1, 2} (input_pipeline.py), `Liver` alone clips them to {0, 1}, tumour counting as liver (input_pipeline_li.py:230).
+    fg_label is the forced class of the sampler: the tumour when it is a class, else the liver."""
+    classes = tuple(classes)
+    if classes not in LABEL_MAPS:
+        raise ValueError("the LiTS labels serve --classes Liver or --classes Liver Tumor, got {}".format(" ".join(classes)))
+    return len(classes), 2 if "Tumor" in classes else 1
+
+
+def forced_counts(store, fg_label):
+    """Forced-class pixels of every slice of the store, int64 [n_slices]: counted on the device, ONE transfer."""
+    thr = int(fg_label) * lits.LB_SCALE                  # seg // LB_SCALE >= fg  <=>  seg >= fg * LB_SCALE
+    n = store.lb.shape[0]
+    if thr > 255:
+        return np.zeros(n, dtype=np.int64)
+    parts = [(store.lb[c0:c0 + 1024] >= thr).sum(dim=(1, 2)) for c0 in range(0, n, 1024)]
+    return torch.cat(parts).cpu().numpy().astype(np.int64)
+
+
+def crop_shape(target_hw, zoom):
+    """gen_batch :589: (float32 target * python floats).astype(int32) -- a float64 product, truncated."""
+    return (np.asarray(target_hw, dtype=np.float32).astype(np.float64) * np.asarray(zoom, dtype=np.float64)).astype(np.int32)
+
+
+class PatchSampler(object):
+    """Which cases, centres, crops, flips and gammas make up a batch -- `gen_batch` (input_pipeline_3d.py:544-604) as one
+    vectorised draw per batch on a `numpy.random.Generator` of its own:
+      * force = ceil(bs * tumor_percent) cases, without replacement, from the cases that hold forced-class voxels (:565,
+        :575), each centred on a uniformly chosen forced-class voxel of the case (:592-593);
+      * the other bs - force, without replacement, from the cases not chosen above (:582-583), each centred on a uniform
+        (pz, py, px) (:598-600);
+      * per sample two zoom factors U(zoom_scale) for y and x, crop = int32(target * zoom) (:589); evaluation: 1.125;
+      * training: a coin per flip axis enabled in random_flip (image_ops.py:309-314) and gamma -- with probability 0.3 from
+        U(0.7, 1), else from U(1, 1.5) (image_ops.py:344-346 as data_processing :405 calls it).
+    A forced-class voxel is chosen WITHOUT a position table: `slice_counts` (forced-class pixels of every store slice, see
+    forced_counts) is cumulated once; a rank below the case's total is drawn, searchsorted on the cumulative counts gives
+    the slice z and the rank k inside it, and `unetk_lits_pick_voxel` turns (z, k) into (py, px) on the device."""
+
+    def __init__(self, cases, offset, slice_counts, batch_size, shape, src_hw, tumor_percent=0.5, zoom_scale=(1.0, 1.25),
+                 random_flip=0, training=True, seed=None):
+        self.bs = int(batch_size)
+        self.depth_out, self.h, self.w = (int(v) for v in shape)
+        self.src_h, self.src_w = int(src_hw[0]), int(src_hw[1])
+        self.training = bool(training)
+        self.zoom = (float(zoom_scale[0]), float(zoom_scale[1])) if training else (EVAL_ZOOM, EVAL_ZOOM)
+        self.flip = int(random_flip or 0) if training else 0
+        self.rng = np.random.default_rng(seed)
+        cases = list(cases)
+        self.pid = np.array([int(c["PID"]) for c in cases], dtype=np.int64)
+        self.depth = np.array([int(c["size"][0]) for c in cases], dtype=np.int64)
+        self.base = np.array([int(offset[int(p)]) for p in self.pid], dtype=np.int64)
+        counts = np.asarray(slice_counts, dtype=np.int64)
+        self.cum = np.concatenate(([0], np.cumsum(counts)))                     # cum[s] = forced-class pixels before store slice s
+        self.case_total = self.cum[self.base + self.depth] - self.cum[self.base]
+        self.fg_cases = np.flatnonzero(self.case_total > 0)
+        self.force = int(math.ceil(self.bs * float(tumor_percent)))
+        if self.force > len(self.fg_cases):
+            raise ValueError("too few cases with forced-class voxels: ceil(batch_size * tumor_percent) = {} are drawn without "
+                             "replacement, {} of the {} cases have any".format(self.force, len(self.fg_cases), len(cases)))
+        if self.bs - self.force > len(cases) - self.force:
+            raise ValueError("too few cases: the {} samples beside the forced ones are drawn without replacement from the "
+                             "{} other cases".format(self.bs - self.force, len(cases) - self.force))
+
+    def locate(self, case, rank):
+        """Rank `rank` (< case_total) among the forced-class voxels of case index `case` -> (z within the case, k within
+        slice z), element-wise, through the cumulative slice counts."""
+        case, rank = np.asarray(case, dtype=np.int64), np.asarray(rank, dtype=np.int64)
+        target = self.cum[self.base[case]] + rank
+        s = np.searchsorted(self.cum, target, side="right") - 1                 # the store slice holding that voxel
+        return s - self.base[case], target - self.cum[s]
+
+    def draw(self):
+        """One batch: dict(case [bs] index into the case list, pid, forced [bs] bool, center [bs, 3] = (z, y, x) with (y, x)
+        undefined (0) on forced samples, k [bs], crop [bs, 2], flips [bs, 3] = (left/right, up/down, front/back), gamma [bs])."""
+        bs, rng, force = self.bs, self.rng, self.force
+        nf = rng.choice(self.fg_cases, size=force, replace=False) if force else np.zeros(0, dtype=np.int64)
+        others = np.setdiff1d(np.arange(len(self.pid)), nf)
+        rem = rng.choice(others, size=bs - force, replace=False) if bs > force else np.zeros(0, dtype=np.int64)
+        case = np.concatenate([nf, rem]).astype(np.int64)
+        forced = np.arange(bs) < force
+        crop = crop_shape([self.h, self.w], rng.uniform(self.zoom[0], self.zoom[1], (bs, 2)))
+        center = np.zeros((bs, 3), dtype=np.int64)
+        k = np.zeros(bs, dtype=np.int64)
+        if force:
+            center[:force, 0], k[:force] = self.locate(nf, rng.integers(0, self.case_total[nf]))
+        u = rng.random((bs, 3))
+        uniform = np.floor(u * np.stack([self.depth[case], np.full(bs, self.src_h), np.full(bs, self.src_w)], axis=1)).astype(np.int64)
+        center[~forced] = uniform[~forced]
+        coins = rng.random((bs, 3)) >= 0.5
+        flips = coins & np.array([bool(self.flip & 1), bool(self.flip & 2), bool(self.flip & 4)])[None, :]
+        low = rng.random(bs) < GAMMA_P
+        gamma = np.where(low, rng.uniform(GAMMA_RANGE[0], 1.0, bs), rng.uniform(1.0, GAMMA_RANGE[1], bs))
+        if not self.training:
+            gamma = np.ones(bs)
+        return dict(case=case, pid=self.pid[case], forced=forced, center=center, k=k, crop=crop, flips=flips,
+                    gamma=gamma.astype(np.float32))
+
+    def table(self, b=None):
+        """The batch as `unetk_lits_patch3d` takes it: int32 [bs, 16] (include/unetk.h), gamma as float bits."""
+        b = self.draw() if b is None else b
+        tab = np.zeros((self.bs, _abi.LITS3D_TAB_COLS), dtype=np.int32)
+        tab[:, COL_BASE] = self.base[b["case"]]
+        tab[:, COL_DEPTH] = self.depth[b["case"]]
+        tab[:, COL_CZ:COL_CX + 1] = b["center"]
+        tab[:, COL_CH:COL_CW + 1] = b["crop"]
+        tab[:, COL_FLIP_LR:COL_FLIP_FB + 1] = b["flips"]
+        tab[:, COL_GAMMA] = np.ascontiguousarray(b["gamma"], dtype=np.float32).view(np.int32)
+        tab[:, COL_FORCED] = b["forced"]
+        tab[:, COL_K] = b["k"]
+        return tab
+
+
+def check_status(status, what):
+    """Read the pick kernel's status word (one small device -> host copy: call it where the host synchronises anyway) and
+    raise if a forced sample's rank lay beyond its slice's count -- per-slice counts that do not match the store.  Such a
+    sample is centred on (0, 0), so without this check the bug would only show as a run that never sees its forced class."""
+    if int(status.item()) != 0:
+        raise RuntimeError("unetk_lits_pick_voxel: a forced sample's rank was beyond the forced-class count of its slice ({}); "
+                           "the per-slice counts do not match the resident store".format(what))
+
+
+def batches(store, sampler, shape, lab_max, fg_label, status=None):
+    """(features, labels) device batches for ever: features["images"] f32 [bs, D, H, W, 1], features["names"] the case ids,
+    labels int32 [bs, D, H, W].  Per batch: one sampler draw, one pinned upload, then `unetk_lits_pick_voxel` (forced
+    samples' centres, in the device table) and `unetk_lits_patch3d` on the current stream -- no host synchronisation.
+    status: int32 [1] device word that collects the pick kernel's out-of-range bit; it is NOT read here (that would
+    synchronise): the owner reads it with `check_status` at a point that synchronises anyway (input_fn: every evaluation)."""
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=store.device)
+    while True:
+        b = sampler.draw()
+        (tab,) = lits.upload_pinned([sampler.table(b)], store.device)
+        if sampler.force:
+            ops.lits_pick_voxels(store.lb, tab, fg_label, status, lits.LB_SCALE)
+        images, labels = ops.lits_patch3d(store.im, store.lb, tab, shape, sampler.training, lab_max, lits.IM_SCALE, lits.LB_SCALE)
+        yield {"images": images, "names": torch.from_numpy(b["pid"])}, labels
+
+
+def input_fn(mode, params):
+    """input_pipeline_3d.py:336-343 for the modes train / eval_online on LiTS; the resident store, the k-fold split and the
+    `params` cache keys are `lits.input_fn`'s.  Training: generator seeded seed + 1000 * rank.  eval_online: zoom 1.125, no
+    flips, no gamma, and a rank-independent generator seeded seed + 500 that is re-created for every evaluation, so each
+    epoch scores the same --eval_num_batches_per_epoch batches (the reference reseeds with 1234 when it builds the
+    generator, :571).  params[("lits3d_status", mode == "train")] is the pick kernel's status word of that stream; every
+    evaluation checks both (check_status), a trainer without online evaluation can check the training one itself."""
+    args = params["args"]
+    if mode not in ("train", "eval_online"):
+        raise ValueError("lits3d.input_fn handles the modes `train` and `eval_online`, got {}".format(mode))
+    lab_max, fg_label = check_args(args)
+    root = params["lits_root"]
+    device = params.get("device", torch.device("cuda", torch.cuda.current_device()))
+    key = ("lits_store", mode == "train")
+    if key not in params:
+        cases = lits.collect_datasets(root, args.test_fold, "train" if mode == "train" else "val",
+                                      filter_tumor_size=getattr(args, "filter_size", 0))
+        params[key] = (lits.SliceStore(root, cases, device, strategy=params.get("strategy")), cases)
+    store, cases = params[key]
+    if len(cases) == 0:
+        raise ValueError("No valid dataset found!")
+    ckey = ("lits3d_counts", mode == "train", fg_label)
+    if ckey not in params:
+        params[ckey] = forced_counts(store, fg_label)
+    bs = distribution_utils.per_device_batch_size(args.batch_size, args.num_gpus)
+    shape = (int(args.im_depth), int(args.im_height), int(args.im_width))
+    base_seed = int(getattr(args, "seed", 1234) or 1234)
+    training = mode == "train"
+    seed = base_seed + 1000 * int(params.get("rank", 0)) if training else base_seed + 500
+    sampler = PatchSampler(cases, store.offset, params[ckey], bs, shape, store.im.shape[1:],
+                           tumor_percent=getattr(args, "tumor_percent", 0.5), zoom_scale=getattr(args, "zoom_scale", (1., 1.25)),
+                           random_flip=getattr(args, "random_flip", 0), training=training, seed=seed)
+    # the pick kernel's status words live in `params` (one per mode) so that they outlast the generators: params[("lits3d_status",
+    # True)] is the training stream's.  An evaluation synchronises anyway, so both are read there: the training word when
+    # the evaluation starts, the evaluation's own after its last batch.
+    skey = ("lits3d_status", training)
+    if skey not in params:
+        params[skey] = torch.zeros(1, dtype=torch.int32, device=store.device)
+    gen = batches(store, sampler, shape, lab_max, fg_label, params[skey])
+    if training:
+        return gen
+    n = int(getattr(args, "eval_num_batches_per_epoch", 100))
+
+    def evaluation():
+        if ("lits3d_status", True) in params:
+            check_status(params[("lits3d_status", True)], "training batches")
+        for _ in range(n):
+            yield next(gen)
+        check_status(params[skey], "eval_online batches")
+    return evaluation()
+
+
+def input_fn_eval(mode, params):
+    """Offline evaluation (--mode eval / infer): not built."""
+    raise NotImplementedError("whole-volume 3-D evaluation of UNet3D on LiTS is not built (a sliding-window evaluator over "
+                              "the case volumes); `liver_3d` serves --mode train, with --eval_per_epoch for online evaluation")

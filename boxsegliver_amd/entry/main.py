@@ -4,7 +4,8 @@ entry/main_g.py, entry/main_g.py (GUNet):
     python -m boxsegliver_amd.entry.main <subcommand> --mode train --tag NAME --model UNet --classes Liver Tumor ...
 
 The first positional argument selects the dataset pipeline and evaluator exactly as in the reference (entry/main.py:53-77:
-only_liver | liver | nf | nf_inter | nf_3d; entry/main_g.py:55-73: liver | nf | nf2 | nf_inter); every flag of the six
+only_liver | liver | nf | nf_inter | nf_3d; entry/main_g.py:55-73: liver | nf | nf2 | nf_inter; plus `liver_3d`, UNet3D on
+LiTS, which the reference does not have: data/lits3d.py); every flag of the six
 argument groups the reference merges (config, core.models, core.solver, loss_metrics, <pipeline>, <evaluator>) is accepted
 with the same name and default, so the shipped run scripts' flag lists parse unchanged (tests/test_entry_host.py does that
 with run_scripts/template/001_unet.sh, scripts/102_gnet_v1.sh and threed_script/201_unet_v1.sh's lists).
@@ -32,6 +33,9 @@ KEEP_CHECKPOINT_MAX = 1                     # entry/main.py:42
 def _liver(pipeline):
     from ..data import flagsets, lits
     from ..evaluators import evaluator_liver
+    if pipeline == "liver_3d":                          # UNet3D on LiTS: 3-D patches from the same resident store
+        from ..data import lits3d
+        return lits3d.add_arguments, lits3d.input_fn, lits3d.input_fn_eval, evaluator_liver
 
     def add(parser):
         flagsets.add_arguments(parser, pipeline)
@@ -49,7 +53,7 @@ def _nf(pipeline):
 # sub-command -> pipeline: entry/main.py:53-77 and entry/main_g.py:55-73
 SUBCOMMANDS = {
     False: {"only_liver": lambda: _liver("liver_li"), "liver": lambda: _liver("liver"), "nf": lambda: _nf("nf"),
-            "nf_inter": lambda: _nf("nf_g_simply"), "nf_3d": lambda: _nf("nf_3d")},
+            "nf_inter": lambda: _nf("nf_g_simply"), "nf_3d": lambda: _nf("nf_3d"), "liver_3d": lambda: _liver("liver_3d")},
     True: {"liver": lambda: _liver("liver_g"), "nf": lambda: _nf("nf_g"), "nf2": lambda: _nf("nf_iin"),
            "nf_inter": lambda: _nf("nf_g_simply")},
 }

@@ -1504,6 +1504,54 @@ def lits_context(table, tab, channels, take, noise=None):
     return out
 
 
+def lits_pick_voxels(seg_slices, sample_tab, fg_label, status, lab_scale=64):
+    """The forced-class centres of a 3-D batch (unetk_lits_pick_voxel): every row of sample_tab int32 [N, 16] with
+    forced != 0 gets (cy, cx) = np.argwhere(seg_slices[base + cz] / lab_scale >= fg_label)[k], written IN PLACE on the
+    device; status int32 [1] (zeroed by the caller) gets bit 0 for a k beyond the slice's count.  Current stream."""
+    _require_cuda(seg_slices, sample_tab, status)
+    assert seg_slices.dtype == torch.uint8 and seg_slices.dim() == 3 and seg_slices.is_contiguous()
+    assert sample_tab.dtype == torch.int32 and sample_tab.dim() == 2 and sample_tab.shape[1] == _abi.LITS3D_TAB_COLS
+    assert sample_tab.is_contiguous() and status.dtype == torch.int32 and status.numel() >= 1
+    with _timed_hbm("lits_pick_voxels", seg_slices[0], sample_tab.shape[0]):          # at most one label slice per sample
+        check(_abi.lib().unetk_lits_pick_voxel(ptr(seg_slices), seg_slices.shape[0], seg_slices.shape[1], seg_slices.shape[2],
+                                               int(lab_scale), int(fg_label), ptr(sample_tab), sample_tab.shape[0], ptr(status),
+                                               stream_ptr()), "lits_pick_voxels")
+    return sample_tab
+
+
+def lits3d_desc(slices, n, shape, training, lab_max=2, im_scale=64, lab_scale=64):
+    d, h, w = (int(v) for v in shape)
+    return _abi.Lits3dDesc(int(n), d, h, w, slices.shape[0], slices.shape[1], slices.shape[2], int(im_scale), int(lab_scale),
+                           int(lab_max), 1 if training else 0)
+
+
+def lits_patch3d(slices, seg_slices, sample_tab, shape, training, lab_max=2, im_scale=64, lab_scale=64):
+    """One UNet3D batch from the device-resident slice store (unetk_lits_patch3d; include/unetk.h has the table layout):
+    slices uint16 / seg_slices uint8 [n, src_h, src_w] (stored as int16 / uint8 tensors), sample_tab int32 [N, 16],
+    shape = (D, H, W).  Returns images f32 [N, D, H, W, 1], labels int32 [N, D, H, W].  training: gamma augmentation with
+    the table's per-sample gamma.  Current stream; no host synchronisation."""
+    _require_cuda(slices, seg_slices, sample_tab)
+    assert slices.dtype in (torch.int16, torch.uint16) and seg_slices.dtype == torch.uint8
+    assert slices.is_contiguous() and seg_slices.is_contiguous() and slices.shape == seg_slices.shape and slices.dim() == 3
+    assert sample_tab.dtype == torch.int32 and sample_tab.dim() == 2 and sample_tab.shape[1] == _abi.LITS3D_TAB_COLS
+    assert sample_tab.is_contiguous()
+    n = sample_tab.shape[0]
+    desc = lits3d_desc(slices, n, shape, training, lab_max, im_scale, lab_scale)
+    nbytes = int(_abi.lib().unetk_lits_patch3d_ws_bytes(ctypes.byref(desc)))
+    if nbytes == 0:
+        raise _abi.UnetkError("lits_patch3d: unsupported shape {} from {} x {} slices".format(tuple(shape), slices.shape[1],
+                                                                                              slices.shape[2]))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=slices.device)
+    images = torch.empty((n, desc.D, desc.H, desc.W, 1), dtype=torch.float32, device=slices.device)
+    labels = torch.empty((n, desc.D, desc.H, desc.W), dtype=torch.int32, device=slices.device)
+    # algorithmic bytes: the image written once (training: + the two gamma passes' read and write) and the labels; the crop
+    # reads depend on the table's zoom and are left out
+    with _timed_hbm("lits_patch3d", images, 5 if training else 1, labels.numel() * 4):
+        check(_abi.lib().unetk_lits_patch3d(ctypes.byref(desc), ptr(slices), ptr(seg_slices), ptr(sample_tab), ptr(images),
+                                            ptr(labels), ptr(ws), nbytes, stream_ptr()), "lits_patch3d")
+    return images, labels
+
+
 def adam_step(p, g, m, v, lr_t, beta1, beta2, eps, gscale=1.0, l2=0.0, decoupled_wd=0.0):
     with _timed_hbm("adam_step", p, 7):            # reads p, g, m, v; writes p, m, v
         check(_abi.lib().unetk_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr_t, beta1, beta2, eps, gscale, l2,

@@ -673,6 +673,54 @@ int unetk_lits_spatial_guide(const unetk_lits_guide_desc* d, const int32_t* samp
 int unetk_lits_context(float* table, int64_t n_rows, int F, const int32_t* sample_tab, int N, int C, const int32_t* take,
                        const double* noise, float* out, void* stream);
 
+/* ---------------------------------------------------------------- LiTS 3-D training patches  
+ * UNet3D batches cropped from the resident slice store: the semantics of the reference's 3-D pipeline
+ * (DataLoader/NF/input_pipeline_3d.py:544-604 gen_batch, :352-407 data_processing; DataLoader/misc.py:132-143 volume_crop;
+ * utils/image_ops.py:241 random_flip, :339-354 augment_gamma) on LiTS volumes.
+ *
+ * sample_tab int32 [N][UNETK_LITS3D_TAB_COLS], one row per sample:
+ *   0 base   store index of the case's first slice      8  flip_up_down
+ *   1 depth  slices of the case                          9  flip_front_back
+ *   2 cz     centre slice (within the case)              10 gamma (float bits; training only)
+ *   3 cy     centre row                                  11 forced: 1 = (cy, cx) come from unetk_lits_pick_voxel
+ *   4 cx     centre column                               12 k: rank of the forced-class pixel in slice cz
+ *   5 ch     crop rows    = int32(H * zoom_y)            13..15 reserved (0)
+ *   6 cw     crop columns = int32(W * zoom_x)
+ *   7 flip_left_right
+ *
+ * unetk_lits_pick_voxel: for every row with forced != 0, (cy, cx) <- the k-th pixel, in row-major order, of slice
+ *   base + cz with seg / lab_scale >= fg_label -- np.argwhere(lab[cz] >= fg_label)[k], exactly -- written into the table on
+ *   the device.  Rows with forced == 0 are left alone.  A k outside [0, count) or a slice outside the store writes (0, 0)
+ *   and sets status[0] |= 1 (the caller zeroes it); nothing is read out of bounds.  One block per sample.
+ *
+ * unetk_lits_patch3d: images f32 [N,D,H,W,1], labels int32 [N,D,H,W].  Per sample:
+ *   crop box (volume_crop): ch, cw clamped into [1, src_h] x [1, src_w]; z1 = min(max(cz - D/2, 0), max(depth - D, 0)),
+ *     y1 = min(max(cy - ch/2, 0), src_h - ch), x1 likewise; crop slices at or beyond `depth` (a case shallower than D)
+ *     read as zeros with label 0;
+ *   mask statistics over the crop at source resolution, v = stored / im_scale: mean m and standard deviation s over the
+ *     voxels with v > 0 (fp64 partials per block, summed by index: bit-reproducible); an empty mask gives m = s = 0;
+ *   image: every bilinear corner c is normalised on the fly, c > 0 ? (c - m) / (s + 1e-8) : 0, then resize_bilinear
+ *     (align_corners) to H x W per slice -- normalise, then resize, as the reference;
+ *   labels: resize_nearest_neighbor(align_corners), min(seg / lab_scale, lab_max);
+ *   flips of image and label alike, by the write address;
+ *   training != 0: augment_gamma(retain_stats=True) with the row's gamma: mn, sd, min, range of the patch,
+ *     y = powf((x - min) / (range + 1e-7), gamma) * range + min, out = (y - mean(y) + mn) / (sd(y) + 1e-8) * sd.
+ * D*H*W < 2^31 and D*src_h*src_w < 2^31 (else UNETK_E_UNSUPPORTED and a zero ws query); N <= 65535; ws 16-byte aligned, at
+ * least unetk_lits_patch3d_ws_bytes (the partials and the per-sample statistics only). */
+#define UNETK_LITS3D_TAB_COLS 16
+typedef struct unetk_lits3d_desc {
+  int32_t N, D, H, W;
+  int32_t n_slices, src_h, src_w; /* extent of the resident store */
+  int32_t im_scale, lab_scale;    /* IM_SCALE = LB_SCALE = 64 */
+  int32_t lab_max;                /* labels are min(seg / lab_scale, lab_max): the number of foreground classes */
+  int32_t training;               /* != 0: gamma augmentation */
+} unetk_lits3d_desc;
+int unetk_lits_pick_voxel(const uint8_t* seg_slices, int n_slices, int src_h, int src_w, int lab_scale, int fg_label,
+                          int32_t* sample_tab, int N, int32_t* status, void* stream);
+size_t unetk_lits_patch3d_ws_bytes(const unetk_lits3d_desc* d);
+int unetk_lits_patch3d(const unetk_lits3d_desc* d, const uint16_t* slices, const uint8_t* seg_slices,
+                       const int32_t* sample_tab, float* images, int32_t* labels, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- optimiser  core/solver.py:204-243
  * tf.train.AdamOptimizer on a flat parameter buffer.  g' = g*gscale + l2*p  (slim.l2_regularizer
  * gradient, base.py:128-135);  m += (1-b1)(g'-m);  v += (1-b2)(g'^2-v);
