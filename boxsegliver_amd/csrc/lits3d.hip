@@ -337,7 +337,87 @@ bool p3d_valid(const unetk_lits3d_desc* d) {
          d->im_scale > 0 && d->lab_scale > 0 && d->lab_max > 0;
 }
 
+// ------------------------------------------------------------------------------------------------ evaluation: the way back
+// Whole-volume evaluation in windows: the class probabilities of the windows p3d_patch_kernel cut are
+// resized back from H x W to the rows' ch x cw crops and added into the case's accumulator at source resolution.  A
+// gather: one thread per voxel of the rows' union box, x fastest; it walks the rows IN ORDER (the table row is
+// wave-uniform: scalar loads), so every (voxel, class) has one writer and a fixed summation order -- no atomics.  A wave
+// reads and writes 64 * C consecutive floats of acc; the probs taps of neighbouring threads are neighbours too.
+struct EvalBox {
+  int z0, y0, x0, bd, bh, bw;
+};
+template <int C>
+__global__ __launch_bounds__(256) void eval3d_accumulate_kernel(unetk_lits3d_desc d, const int32_t* __restrict__ tab,
+                                                                const float* __restrict__ probs, int64_t case_base,
+                                                                int case_depth, EvalBox e, float* __restrict__ acc,
+                                                                int32_t* __restrict__ cnt) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t area = (int64_t)e.bh * e.bw;
+  if (i >= area * e.bd) return;
+  const int zb = (int)(i / area), r = (int)(i - zb * area);
+  const int yb = r / e.bw;
+  const int z = e.z0 + zb, y = e.y0 + yb, x = e.x0 + (r - yb * e.bw);
+  const int64_t vox = ((int64_t)z * d.src_h + y) * d.src_w + x;
+  float* a = acc + vox * C;
+  float sum[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) sum[c] = a[c];
+  int hits = 0;
+  const int win = d.D * d.H * d.W * C;                       // < 2^31: checked by the entry point
+  for (int n = 0; n < d.N; ++n) {
+    const int32_t* t = tab + (int64_t)n * TW;
+    const Box3 b = p3d_box(t, d);
+    if (b.base != case_base || b.depth != case_depth) continue;          // not this case's row: rejected on the host
+    const int zw = z - b.z1, yw = y - b.y1, xw = x - b.x1;
+    if (zw < 0 || zw >= d.D || yw < 0 || yw >= b.ch || xw < 0 || xw >= b.cw) continue;
+    if (p3d_slice(b, zw, d) < 0) continue;                               // the window's zero slices below a shallow case
+    // the inverse resize: H x W -> ch x cw, taps in the un-flipped window; the flips are the read address
+    const LitsTaps ty = lits_ac_taps(yw * lits_ac_scale(d.H, b.ch), d.H), tx = lits_ac_taps(xw * lits_ac_scale(d.W, b.cw), d.W);
+    const bool flr = t[7] != 0, fud = t[8] != 0, ffb = t[9] != 0;
+    const int y0 = min(ty.i0, d.H - 1), x0 = min(tx.i0, d.W - 1);
+    const int zr = ffb ? d.D - 1 - zw : zw;
+    const int ya = fud ? d.H - 1 - y0 : y0, yb2 = fud ? d.H - 1 - ty.i1 : ty.i1;
+    const int xa = flr ? d.W - 1 - x0 : x0, xb = flr ? d.W - 1 - tx.i1 : tx.i1;
+    const float* p = probs + (int64_t)n * win;
+    const int ra = (zr * d.H + ya) * d.W, rb = (zr * d.H + yb2) * d.W;
+    const float *tl = p + (ra + xa) * C, *tr = p + (ra + xb) * C, *bl = p + (rb + xa) * C, *br = p + (rb + xb) * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) sum[c] += lits_bilerp(tl[c], tr[c], bl[c], br[c], tx.f, ty.f);
+    ++hits;
+  }
+  if (hits == 0) return;
+#pragma unroll
+  for (int c = 0; c < C; ++c) a[c] = sum[c];
+  cnt[vox] += hits;
+}
+
 }  // namespace
+
+extern "C" int unetk_eval3d_accumulate(const unetk_lits3d_desc* d, const int32_t* sample_tab, const float* probs, int C,
+                                       int64_t case_base, int case_depth, const int32_t box[6], float* acc, int32_t* cnt,
+                                       void* stream) {
+  UNETK_REQUIRE(p3d_valid(d) && sample_tab && probs && box && acc && cnt && C >= 1 && C <= 8);
+  UNETK_REQUIRE(((((uintptr_t)sample_tab) | ((uintptr_t)probs) | ((uintptr_t)acc) | ((uintptr_t)cnt)) & 3u) == 0);
+  UNETK_REQUIRE(case_base >= 0 && case_depth > 0 && case_base + case_depth <= d->n_slices);
+  UNETK_REQUIRE(0 <= box[0] && box[0] < box[1] && box[1] <= case_depth && 0 <= box[2] && box[2] < box[3] && box[3] <= d->src_h &&
+                0 <= box[4] && box[4] < box[5] && box[5] <= d->src_w);
+  if (!p3d_supported(d) || (int64_t)d->D * d->H * d->W * C >= ((int64_t)1 << 31)) return UNETK_E_UNSUPPORTED;
+  const EvalBox e = {box[0], box[2], box[4], box[1] - box[0], box[3] - box[2], box[5] - box[4]};
+  const int64_t blocks = ((int64_t)e.bd * e.bh * e.bw + 255) / 256;
+  if (blocks >= ((int64_t)1 << 31)) return UNETK_E_UNSUPPORTED;
+  const dim3 grid((unsigned)blocks);
+  hipStream_t st = (hipStream_t)stream;
+#define EVAL3D_CASE(c)                                                                                                      \
+  case c:                                                                                                                   \
+    UNETK_LAUNCH(eval3d_accumulate_kernel<c>, grid, dim3(256), 0, st, *d, sample_tab, probs, case_base, case_depth, e, acc, cnt); \
+    break;
+  switch (C) {
+    EVAL3D_CASE(1) EVAL3D_CASE(2) EVAL3D_CASE(3) EVAL3D_CASE(4) EVAL3D_CASE(5) EVAL3D_CASE(6) EVAL3D_CASE(7) EVAL3D_CASE(8)
+  }
+#undef EVAL3D_CASE
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
 
 extern "C" int unetk_lits_pick_voxel(const uint8_t* seg_slices, int n_slices, int src_h, int src_w, int lab_scale, int fg_label,
                                      int32_t* sample_tab, int N, int32_t* status, void* stream) {

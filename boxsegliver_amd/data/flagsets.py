@@ -112,7 +112,8 @@ PIPELINES = {
               {"--im_channel": 1, "--zoom_scale": (1.0, 1.25), "--stddev": [1, 3., 3.]}),
     # UNet3D on LiTS (data/lits3d.py): the flags of DataLoader/NF/input_pipeline_3d.py:53-67 that apply, its defaults
     "liver_3d": (["--test_fold", "--im_depth", "--im_height", "--im_width", "--im_channel", "--zoom_scale", "--random_flip",
-                  "--eval_num_batches_per_epoch", "--tumor_percent"], {"--im_channel": 1, "--zoom_scale": (1.0, 1.25)}),
+                  "--eval_in_patches", "--eval_num_batches_per_epoch", "--eval_mirror", "--tumor_percent"],
+                 {"--im_channel": 1, "--zoom_scale": (1.0, 1.25)}),
 }
 
 

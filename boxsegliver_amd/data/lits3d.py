@@ -16,7 +16,10 @@ table exists anywhere and nothing synchronises the host with the device.
 
 Two deviations from the literal reference arithmetic: a case shallower than --im_depth is cropped from slice 0 and padded
 with zero slices (the reference would index with a negative start), and a patch without a single non-zero voxel is all
-zeros (TensorFlow's moments of an empty tensor are NaN)."""
+zeros (TensorFlow's moments of an empty tensor are NaN).
+
+Offline, `input_fn_eval` tiles every case of the validation fold with windows cut as `eval_online` cuts them (window_starts,
+eval_tables) for the sliding-window evaluator, `EvaluateVolume.run_3d` (--eval_in_patches)."""
 import math
 
 import numpy as np
@@ -40,11 +43,16 @@ def add_arguments(parser):
     flagsets.add_arguments(parser, "liver_3d")
     parser.add_argument("--lits_root", type=str, default="data/LiTS", help="where png/, meta.json and k_folds.txt live")
     parser.add_argument("--seed", type=int, default=1234)
+    parser.add_argument("--eval_overlap", type=float, default=0.5,
+                        help="--mode eval --eval_in_patches: overlap of neighbouring windows as a share of the window, in [0, 1)")
 
 
 def check_args(args):
     if int(getattr(args, "im_channel", 1)) != 1:
         raise ValueError("the LiTS 3-D patches have one channel, got --im_channel {}".format(args.im_channel))
+    overlap = float(getattr(args, "eval_overlap", 0.5))
+    if not 0.0 <= overlap < 1.0:                          # also refuses NaN
+        raise ValueError("--eval_overlap must satisfy 0 <= v < 1, got {}".format(overlap))
     return label_map(args.classes)
 
 
@@ -239,7 +247,115 @@ def input_fn(mode, params):
     return evaluation()
 
 
+# ------------------------------------------------------------------------------------------------- whole-volume evaluation
+def window_starts(extent, window, overlap):
+    """Where the windows of one axis start (evaluators/evaluator_nf.py:194-257 walks its patches the same way): every
+    step = max(int(window * (1 - overlap)), 1) while the window fits, plus one window aligned with the end when the last one
+    stops short of it; an axis no longer than the window has the one start 0."""
+    extent, window = int(extent), int(window)
+    if extent <= window:
+        return [0]
+    step = max(int(window * (1 - float(overlap))), 1)
+    starts = list(range(0, extent - window + 1, step))
+    if starts[-1] + window != extent:
+        starts.append(extent - window)
+    return starts
+
+
+def mirror_variants(args):
+    """The flip sets (left/right, up/down, front/back) of the mirror test-time augmentation, entry/main_eval_3d.py:246-287
+    literally: the plain window, and with --eval_mirror every m in 1..7 with (random_flip & m) > 0, bit 0 = left/right,
+    bit 1 = up/down, bit 2 = front/back -- so `--random_flip 1` also runs m = 3, 5, 7, a quirk kept as
+    evaluator_liver.mirror_plan keeps the 2-D one."""
+    variants = [0]
+    if getattr(args, "eval_mirror", False):
+        rf = int(getattr(args, "random_flip", 0) or 0)
+        variants += [m for m in range(1, 8) if (rf & m) > 0]
+    return [(m & 1, (m >> 1) & 1, (m >> 2) & 1) for m in variants]
+
+
+def eval_windows(src_hw, shape):
+    """(D, ch, cw): a window's extent in the case -- im_depth slices (fewer exist in a shallower case) and the
+    `eval_online` crop int32((H, W) * EVAL_ZOOM) clamped to the slice, as the kernels' crop box clamps it."""
+    ch, cw = (int(v) for v in crop_shape(shape[1:], (EVAL_ZOOM, EVAL_ZOOM)))
+    return int(shape[0]), min(max(ch, 1), int(src_hw[0])), min(max(cw, 1), int(src_hw[1]))
+
+
+def eval_tables(case, store, shape, overlap, variants, batch_size):
+    """The sample tables (PatchSampler.table's layout, int32 [n, 16]) that tile ONE case with windows, in batches of
+    `batch_size` rows, the last one short.  Windows are cut as `eval_online` cuts them (zoom EVAL_ZOOM, no gamma, not
+    forced) and cover the whole volume -- not the ground-truth liver box: no label information enters the prediction.
+    A window that starts at `a` is centred on a + window // 2, from which the kernels' volume_crop clamp gives back `a`.
+    Every window is followed by its mirror variants: the same row with the flip columns set."""
+    pid, depth = int(case["PID"]), int(case["size"][0])
+    src_h, src_w = int(store.im.shape[1]), int(store.im.shape[2])
+    d, ch, cw = eval_windows((src_h, src_w), shape)
+    rows = []
+    for z in window_starts(depth, d, overlap):
+        for y in window_starts(src_h, ch, overlap):
+            for x in window_starts(src_w, cw, overlap):
+                for flips in variants:
+                    row = np.zeros(_abi.LITS3D_TAB_COLS, dtype=np.int32)
+                    row[COL_BASE], row[COL_DEPTH] = int(store.offset[pid]), depth
+                    row[COL_CZ:COL_CX + 1] = z + d // 2, y + ch // 2, x + cw // 2
+                    row[COL_CH:COL_CW + 1] = ch, cw
+                    row[COL_FLIP_LR:COL_FLIP_FB + 1] = flips
+                    row[COL_GAMMA] = np.array([1.0], dtype=np.float32).view(np.int32)[0]
+                    rows.append(row)
+    tab = np.stack(rows)
+    bs = max(int(batch_size), 1)
+    for i in range(0, len(tab), bs):
+        yield tab[i:i + bs]
+
+
+def table_box(tab, shape, depth, src_hw):
+    """(z0, z1, y0, y1, x0, x1): the union box of a table's crop boxes inside the case (the voxels
+    `unetk_eval3d_accumulate` visits), computed as the kernels' crop box (p3d_box, csrc/lits3d.hip) computes them."""
+    tab = np.asarray(tab).astype(np.int64)
+    d, depth = int(shape[0]), int(depth)
+    ch = np.clip(tab[:, COL_CH], 1, int(src_hw[0]))
+    cw = np.clip(tab[:, COL_CW], 1, int(src_hw[1]))
+    z1 = np.minimum(np.maximum(tab[:, COL_CZ] - d // 2, 0), max(depth - d, 0))
+    y1 = np.minimum(np.maximum(tab[:, COL_CY] - ch // 2, 0), int(src_hw[0]) - ch)
+    x1 = np.minimum(np.maximum(tab[:, COL_CX] - cw // 2, 0), int(src_hw[1]) - cw)
+    return (int(z1.min()), int(min((z1 + d).max(), depth)), int(y1.min()), int((y1 + ch).max()), int(x1.min()),
+            int((x1 + cw).max()))
+
+
 def input_fn_eval(mode, params):
-    """Offline evaluation (--mode eval / infer): not built."""
-    raise NotImplementedError("whole-volume 3-D evaluation of UNet3D on LiTS is not built (a sliding-window evaluator over "
-                              "the case volumes); `liver_3d` serves --mode train, with --eval_per_epoch for online evaluation")
+    """Offline evaluation (--mode eval) in sliding windows, --eval_in_patches.  The validation fold is
+    loaded into the resident store exactly as input_fn("eval_online") loads it (same cache key).  Per case the generator
+    yields its window tables (host int32 [n, 16], eval_tables) and then one end-of-case item
+    (None, dict(case, base, depth, store)).  Labels never leave the device: the evaluator takes them from store.lb.
+    Without the flag: the reference's other way, one forward over the whole case (entry/main_eval_3d.py), which is not built."""
+    args = params["args"]
+    if not getattr(args, "eval_in_patches", False):
+        raise NotImplementedError("whole-volume 3-D evaluation of UNet3D on LiTS in ONE forward is not built; pass "
+                                  "--eval_in_patches for the sliding-window evaluator")
+    if mode != "eval":
+        raise NotImplementedError("`liver_3d` serves --mode train and --mode eval --eval_in_patches, got --mode {}".format(mode))
+    check_args(args)
+    return _eval_cases(args, params)
+
+
+def _eval_cases(args, params):
+    root = params["lits_root"]
+    key = ("lits_store", False)
+    if key not in params:
+        device = params.get("device") or torch.device("cuda", torch.cuda.current_device())
+        cases = lits.collect_datasets(root, args.test_fold, "val", filter_tumor_size=getattr(args, "filter_size", 0))
+        params[key] = (lits.SliceStore(root, cases, device, strategy=params.get("strategy")), cases)
+    store, cases = params[key]
+    if len(cases) == 0:
+        raise ValueError("No valid dataset found!")
+    cases = cases[int(getattr(args, "eval_skip_num", 0) or 0):]
+    if int(getattr(args, "eval_num", -1)) > 0:
+        cases = cases[:int(args.eval_num)]
+    bs = distribution_utils.per_device_batch_size(args.batch_size, args.num_gpus)
+    shape = (int(args.im_depth), int(args.im_height), int(args.im_width))
+    variants = mirror_variants(args)
+    for case in cases:
+        for tab in eval_tables(case, store, shape, float(getattr(args, "eval_overlap", 0.5)), variants, bs):
+            yield tab, None
+        pid = int(case["PID"])
+        yield None, dict(case=str(pid), base=int(store.offset[pid]), depth=int(case["size"][0]), store=store)

@@ -175,6 +175,8 @@ def run(args, sub, pipe, guided=False, dataset_params=None):
                 args.model_dir, args.load_status_file if not args.eval_final else None))
         if propagated:                                   # entry/main_g.py:218-228: guide propagation (EvaluateVolume.run_g)
             return evaluator.run_g(input_fn_eval, checkpoint_path=ckpt, save=args.save_predict)
+        if sub == "liver_3d" and args.mode == ModeKeys.EVAL:      # UNet3D on LiTS: sliding windows (EvaluateVolume.run_3d)
+            return evaluator.run_3d(input_fn_eval, checkpoint_path=ckpt, save=args.save_predict)
         return evaluator.run(input_fn_eval, checkpoint_path=ckpt, save=args.save_predict)
 
     raise ValueError("--mode {} is not built (TF-Serving export is out of scope, SURVEY.md 2 row 15)".format(args.mode))

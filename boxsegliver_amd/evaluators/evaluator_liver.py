@@ -27,6 +27,9 @@ host flips and three host->device copies per slab.
 
 With --use_spatial, `run_g` (evaluator_liver.py:768-917) evaluates by guide propagation instead: data/propagate.py holds the
 state machine, `_GuidedLoop` the per-slice device work (one forward, unetk_guide_components, one table copy, unetk_guide_render).
+
+UNet3D on LiTS (`liver_3d --eval_in_patches`) is scored by `run_3d`: sliding windows from data/lits3d.input_fn_eval, one forward per
+batch, `unetk_eval3d_accumulate` into the case at source resolution, then the same scoring.
 """
 import json
 import time
@@ -433,6 +436,75 @@ class EvaluateVolume(EvaluateBase):
             return self._run_actual(self._predict_case_patches, run_pred, save, cases=n_cases)
         resize = getattr(self.config, "im_height", 0) > 0 and getattr(self.config, "im_width", 0) > 0
         return self._run_actual(self._predict_case, run_pred, save, cases=n_cases, resize=resize)
+
+    # ------------------------------------------------------------------ UNet3D in sliding windows
+    def run_3d(self, input_fn, checkpoint_path=None, save=False, cases=None):
+        """Whole LiTS cases scored by UNet3D in sliding windows (`liver_3d --mode eval --eval_in_patches`; the reference's
+        evaluators/evaluator_nf.py:194-257 `_evaluate_patches`).  input_fn: data/lits3d.input_fn_eval --
+        per case the host tables of its windows, then an end-of-case item.  Per table: one pinned upload, the windows cut by
+        `unetk_lits_patch3d` as `eval_online` cuts them, one forward, and `unetk_eval3d_accumulate`, which resizes the window
+        probabilities back to their crops and ADDS them into the case's accumulator at source resolution (the reference
+        assigns but counts: its last window is divided by the coverage).  At the end of a case: argmax over the sums (the
+        division by a positive count does not change it), labels from the resident store, and the usual post-processing
+        and metrics on the device.  Nothing inside a case synchronises the host; the coverage count is read once per case."""
+        from ..data import lits, lits3d
+        cfg = self.config
+        model = self._model()
+        if checkpoint_path and not tf_checkpoint.checkpoint_exists(checkpoint_path):
+            raise FileNotFoundError("Missing checkpoint file {} (status_file None)".format(checkpoint_path))
+        mode = getattr(cfg, "mode", ModeKeys.EVAL)
+        shape = (int(cfg.im_depth), int(cfg.im_height), int(cfg.im_width))
+        lab_max, _ = lits3d.label_map(cfg.classes)
+        params = self.params
+
+        def run_pred():
+            restored = False
+            acc = cnt = None
+            for tab, end in input_fn(mode, params):
+                store = params[("lits_store", False)][0]            # input_fn_eval made it resident before its first item
+                if tab is not None:
+                    (dtab,) = lits.upload_pinned([tab], store.device)
+                    images, _ = ops.lits_patch3d(store.im, store.lb, dtab, shape, False, lab_max, lits.IM_SCALE, lits.LB_SCALE)
+                    features = {"images": images}
+                    if not restored:
+                        restored = True
+                        if model.params is None:
+                            self._forward(model, features)              # creates the variables
+                        if checkpoint_path and self.estimator is not None:
+                            self.estimator._restore(checkpoint_path, model, None)
+                    prob = self._forward(model, features).contiguous()  # [n, D, H, W, C]
+                    base, depth = int(tab[0, lits3d.COL_BASE]), int(tab[0, lits3d.COL_DEPTH])
+                    src_hw = tuple(store.im.shape[1:])
+                    if acc is None:
+                        acc = torch.zeros((depth,) + src_hw + (prob.shape[-1],), dtype=torch.float32, device=store.device)
+                        cnt = torch.zeros((depth,) + src_hw, dtype=torch.int32, device=store.device)
+                    ops.eval3d_accumulate(prob, dtab, shape, base, depth, lits3d.table_box(tab, shape, depth, src_hw), acc, cnt,
+                                          store.im, host_tab=tab)
+                else:
+                    if acc is None or end["depth"] != acc.shape[0]:
+                        raise RuntimeError("case {} ended without windows of its own".format(end["case"]))
+                    amax, _ = ops.head_predict(acc.view(-1, acc.shape[-1]), acc.shape[-1], want_preds=False)
+                    lb = end["store"].lb[end["base"]:end["base"] + end["depth"]]
+                    labels = torch.clamp(torch.div(lb, lits.LB_SCALE, rounding_mode="floor"), max=lab_max).to(torch.uint8)
+                    yield end["case"], labels, amax.view(cnt.shape), cnt
+                    acc = cnt = None
+
+        n_cases = cases if cases is not None else getattr(cfg, "eval_num", -1)
+        return self._run_actual(self._predict_case_3d, run_pred, save, cases=n_cases)
+
+    def _predict_case_3d(self, predicts, cases=-1, dtype="pred", save_path=None):
+        """A case of run_3d for _run_actual: (case, device labels, device class volume uint8 [depth, src_h, src_w], False).
+        The coverage is read here, where the scoring that follows synchronises anyway."""
+        if dtype != "pred":
+            raise NotImplementedError("the sliding-window 3-D evaluation scores class predictions (--pred_type pred)")
+        counter = 0
+        for case, labels, volume, cnt in predicts:
+            if int(cnt.min().item()) <= 0:
+                raise RuntimeError("--eval_in_patches: windows do not cover every voxel of case {}".format(case))
+            yield case, labels, volume, False
+            counter += 1
+            if 0 < cases <= counter:
+                break
 
     # ------------------------------------------------------------------ spatial-guide propagation
     def run_g(self, input_fn=None, checkpoint_path=None, latest_filename=None, save=False, cases=None, timing=None,

@@ -1552,6 +1552,41 @@ def lits_patch3d(slices, seg_slices, sample_tab, shape, training, lab_max=2, im_
     return images, labels
 
 
+def eval3d_accumulate(probs, sample_tab, shape, case_base, case_depth, box, acc, cnt, slices, host_tab=None):
+    """Window probabilities back into ONE case at source resolution (unetk_eval3d_accumulate): probs f32
+    [N, D, H, W, C] of the windows `lits_patch3d(..., training=False)` cut for sample_tab int32 [N, 16]; acc f32
+    [depth, src_h, src_w, C] and cnt int32 [depth, src_h, src_w] are updated IN PLACE (the caller zeroes them before the
+    case's first batch); box = (z0, z1, y0, y1, x0, x1), the union of the rows' crop boxes; slices: the resident store the
+    windows were cut from (its extent enters the crop box).  host_tab: the table's host copy, when the caller has it -- the
+    rows' (base, depth) are then checked against the case here (a device table is not read back).  Current stream; no
+    host synchronisation."""
+    _require_cuda(probs, sample_tab, acc, cnt, slices)
+    d, h, w = (int(v) for v in shape)
+    assert sample_tab.dtype == torch.int32 and sample_tab.dim() == 2 and sample_tab.shape[1] == _abi.LITS3D_TAB_COLS
+    assert sample_tab.is_contiguous()
+    n = sample_tab.shape[0]
+    assert probs.dtype == torch.float32 and probs.dim() == 5 and tuple(probs.shape[:4]) == (n, d, h, w) and probs.is_contiguous()
+    c = int(probs.shape[4])
+    assert slices.dim() == 3
+    vol = (int(case_depth), int(slices.shape[1]), int(slices.shape[2]))
+    assert acc.dtype == torch.float32 and tuple(acc.shape) == vol + (c,) and acc.is_contiguous()
+    assert cnt.dtype == torch.int32 and tuple(cnt.shape) == vol and cnt.is_contiguous()
+    if host_tab is not None:
+        rows = torch.as_tensor(host_tab)
+        if tuple(rows.shape) != (n, _abi.LITS3D_TAB_COLS) or bool((rows[:, 0] != int(case_base)).any()) or \
+                bool((rows[:, 1] != int(case_depth)).any()):
+            raise _abi.UnetkError("eval3d_accumulate: every row must carry the case's (base, depth) = ({}, {})".format(
+                int(case_base), int(case_depth)))
+    desc = lits3d_desc(slices, n, shape, False)
+    cbox = (ctypes.c_int32 * 6)(*(int(v) for v in box))
+    # algorithmic bytes: the windows read once, the box of acc read and written, the box of cnt read and written
+    nvox = (cbox[1] - cbox[0]) * (cbox[3] - cbox[2]) * (cbox[5] - cbox[4])
+    with _timed_hbm("eval3d_accumulate", probs, 1, nvox * 8 * (c + 1)):
+        check(_abi.lib().unetk_eval3d_accumulate(ctypes.byref(desc), ptr(sample_tab), ptr(probs), c, int(case_base),
+                                                 int(case_depth), cbox, ptr(acc), ptr(cnt), stream_ptr()), "eval3d_accumulate")
+    return acc, cnt
+
+
 def adam_step(p, g, m, v, lr_t, beta1, beta2, eps, gscale=1.0, l2=0.0, decoupled_wd=0.0):
     with _timed_hbm("adam_step", p, 7):            # reads p, g, m, v; writes p, m, v
         check(_abi.lib().unetk_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr_t, beta1, beta2, eps, gscale, l2,

@@ -721,6 +721,21 @@ size_t unetk_lits_patch3d_ws_bytes(const unetk_lits3d_desc* d);
 int unetk_lits_patch3d(const unetk_lits3d_desc* d, const uint16_t* slices, const uint8_t* seg_slices,
                        const int32_t* sample_tab, float* images, int32_t* labels, void* ws, size_t ws_bytes, void* stream);
 
+/* Whole-volume evaluation in windows.  probs f32 [N,D,H,W,C]: the class probabilities of the N windows that
+ * unetk_lits_patch3d(training = 0) cut for sample_tab (same desc, same table, flips included).  acc f32 [depth,src_h,src_w,C],
+ * cnt int32 [depth,src_h,src_w]: ONE case, zeroed by the caller before its first batch.  All rows must carry this case's
+ * (base, depth).  For every voxel (z,y,x) of the case and every row n = 0..N-1 IN ORDER whose crop box holds it:
+ *   acc[z,y,x,c] += resize_bilinear(align_corners) of probs[n,z - z1,:,:,c] from H x W to ch x cw, at (y - y1, x - x1),
+ *   read through the row's flips;   cnt[z,y,x] += 1.
+ * A gather: every (voxel, class) is written by one thread, rows are added in index order -- no atomics, two calls give
+ * identical bits.  [z0,z1) x [y0,y1) x [x0,x1): the union box of the rows (the host knows it), the only voxels visited.
+ * box = {z0, z1, y0, y1, x0, x1} (host memory), inside [0,depth) x [0,src_h) x [0,src_w) and not empty; 1 <= C <= 8; a row
+ * whose (base, depth) differ from (case_base, case_depth) is rejected when the caller passes the table's host copy to the
+ * wrapper (the entry point sees a device pointer), and contributes nothing on the device.  Window slices at or beyond
+ * case_depth contribute nothing.  The size limits of unetk_lits_patch3d apply, and D*H*W*C < 2^31 (UNETK_E_UNSUPPORTED). */
+int unetk_eval3d_accumulate(const unetk_lits3d_desc* d, const int32_t* sample_tab, const float* probs, int C,
+                            int64_t case_base, int case_depth, const int32_t box[6], float* acc, int32_t* cnt, void* stream);
+
 /* ---------------------------------------------------------------- optimiser  core/solver.py:204-243
  * tf.train.AdamOptimizer on a flat parameter buffer.  g' = g*gscale + l2*p  (slim.l2_regularizer
  * gradient, base.py:128-135);  m += (1-b1)(g'-m);  v += (1-b2)(g'^2-v);
