@@ -42,6 +42,9 @@ CASES = [
     (2, 7, 6, 6, 64, 64, 3, (1, 1, 1)),        # bridge shape: 252 pixels per sample (last block partial)
     (1, 5, 24, 24, 32, 64, 3, (1, 1, 1)),      # conv_e2 shape
     (3, 4, 11, 13, 32, 64, 1, (1, 1, 1)),      # odd plane, three samples, (1,3,3)
+    # D = 1: depth taps 0 and 2 have no input plane (forward / input gradient: the middle tap alone; dw[0] = dw[2] = 0)
+    (1, 1, 8, 16, 64, 64, 3, (1, 1, 1)),       # one filter-gradient tile: one split, dw written in place
+    (3, 1, 6, 6, 64, 64, 3, (1, 1, 1)),        # three one-plane samples side by side, stacked-plane filter gradient
 ]
 
 
@@ -237,6 +240,12 @@ EXACT_TRACES = {
     11: (['conv3x3_igemm_lin_kernel<4,1,1,2,false,false,false,false,false,false>'],
         ['conv3x3_igemm_kernel<4,1,2,1,1,1,0>'],
         ['conv3x3_wgrad_kernel<32,64,false,8,16,false,1,1>', 'slab_reduce_kernel<4>']),
+    12: (['conv3x3_igemm_kernel<4,1,1,2,1,1,1>'],
+        ['conv3x3_igemm_kernel<4,1,1,2,1,1,1>'],
+        ['conv3x3_wgrad_kernel<64,64,false,8,16,false,1,1>']),
+    13: (['conv3x3_igemm_kernel<4,1,1,2,1,1,1>'],
+        ['conv3x3_igemm_kernel<4,1,1,2,1,1,1>'],
+        ['conv3x3_wgrad_kernel<64,64,false,20,6,true,1,1>', 'slab_reduce_kernel<1>']),
 }
 EXACT_LIVE_TRACES = {
     0: (['conv3x3_igemm_lin_kernel<2,2,2,2,false,false,true,false,false,false>', 'lin_sk_fixup_kernel<128,128>'],
