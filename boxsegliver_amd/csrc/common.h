@@ -220,25 +220,47 @@ inline void unetk_set_klive(ConvParams& p, const uint32_t live8[2], int K, bool 
   if (n == 0 || (n == K / 16 && half == 0)) return;
   p.nlive = n; p.khalf = half;
 }
+// ---- one decision per 3x3 conv launch.  ConvShape is what a launch is known by (no pointers); unetk_conv_plan (conv_igemm.hip,
+// pure host arithmetic, no HIP calls) derives from it everything the launch, the statistic-row query and the workspace query
+// need, so the three cannot disagree.  Each family's arithmetic lives in the file that owns its constants.
+enum ConvFamily {
+  CONV_TILED, CONV_TILED_S2, CONV_ATROUS,      // conv_igemm.hip: cfg = ConvTile
+  CONV_LIN, CONV_LIN_SK,                       // conv_igemm_lin.hip (SK: stream-K launch + fix-up), bm = pixels per block
+  CONV_BF16,                                   // conv_igemm_bf16.hip: cfg = 0..4 (pick_bf16)
+  CONV_BF16S_V3,                               // conv_igemm_bf16s.hip: cfg = NT8 (8 / 4)
+  CONV_C3_MFMA, CONV_DIRECT                    // conv_igemm.hip first layers
+};
+struct ConvShape {
+  int N, H, W, Cin, Cout, xs, ys, spg;         // as ConvParams
+  int bf16, ybf16, stride, dil;
+  int klive;                                   // live channels of the contraction axis (0 = all of Cin)
+  int kd, ng;                                  // fused depth taps / tap groups (ConvParams::kd, ::ng)
+  int nbr, nys;                                // fused norm-backward reduction, the producer's pixel stride
+  int affine, pool, accumulate, khalf, stat;   // mode flags (stat: statistic partials are wanted)
+  size_t ws_bytes;                             // stream-K scratch on offer
+};
+struct ConvPlan {
+  int rc;                                      // UNETK_OK, or why the combination is refused (the geometry is filled regardless)
+  int family, cfg, mode, th, bm;               // mode: the tiled kernel's MODE template argument
+  int spg, tiles_h, tiles_w, n_ntiles, stat_rows, lin_pix;
+  int sk_G, sk_whole, sk_tiles, sk_nc, sk_maxp;
+  size_t ws_bytes;                             // stream-K scratch the shape wants (family CONV_LIN_SK when the offer covers it)
+  size_t lds;                                  // direct kernel: dynamic LDS bytes
+};
+ConvPlan unetk_conv_plan(const ConvShape& s);
+int unetk_conv_run(ConvParams p, hipStream_t st);          // conv_igemm.hip: validate, plan, launch
+bool unetk_conv_stride2_ok(int Cin, int Cout);
+bool unetk_conv_bf16_ok(int Cin, int Cout);
+// the family files: `plan` fills the plan when the family takes the shape, `launch` instantiates what the plan says
+bool unetk_conv_plan_lin(const ConvShape& s, ConvPlan& pl);          // conv_igemm_lin.hip: planes narrower than 32 pixels
+int unetk_conv_launch_lin(const ConvPlan& pl, ConvParams p, hipStream_t st);
+void unetk_conv_plan_bf16(const ConvShape& s, ConvPlan& pl);         // conv_igemm_bf16.hip: UNETK_BF16 / UNETK_BF16S
+int unetk_conv_launch_bf16(const ConvPlan& pl, ConvParams p, hipStream_t st);
+bool unetk_conv_plan_bf16s_v3(const ConvShape& s, ConvPlan& pl);     // conv_igemm_bf16s.hip: persistent 512 x 128 / 512 x 64 tiles
+int unetk_conv_launch_bf16s_v3(const ConvPlan& pl, ConvParams p, hipStream_t st);
+// conv_igemm_lin.hip GEN variant (input gradient of a stride-2 conv)
 bool unetk_conv_lin_gen_ok(int H, int W, int Cin, int Cout);
 int unetk_conv_run_lin_gen(ConvParams p, hipStream_t st);
-int unetk_conv_run(ConvParams p, hipStream_t st);          // conv_igemm.hip: picks the tile configuration
-int unetk_conv_stat_rows(int N, int H, int W, int Cin, int Cout, int spg = 1, int stride = 1, int dil = 1);
-bool unetk_conv_stride2_ok(int Cin, int Cout);
-// conv_igemm_lin.hip: linear-pixel variant for planes narrower than 32 pixels (same packed filters)
-bool unetk_conv_lin_ok(int N, int H, int W, int Cin, int Cout, int spg);
-int unetk_conv_stat_rows_lin(int N, int H, int W, int spg, int Cout = 0);   // Cout picks the block height (64 / 128 pixels)
-int unetk_conv_run_lin(ConvParams p, hipStream_t st);
-size_t unetk_conv_lin_sk_bytes(int N, int H, int W, int Cin, int Cout, int spg, int kd);   // 0 = stream-K not used for this shape
-// conv_igemm_bf16.hip
-bool unetk_conv_bf16_ok(int Cin, int Cout);
-int unetk_conv_run_bf16(ConvParams p, hipStream_t st);
-int unetk_conv_stat_rows_bf16(int N, int H, int W, int Cin, int Cout);
-int unetk_conv_stat_rows_bf16s(int N, int H, int W, int Cin, int Cout, int xs, int ys);   // UNETK_BF16S: round-3 kernel where it applies
-// conv_igemm_bf16s.hip: UNETK_BF16S round-3 kernel (persistent 512 x 128 / 512 x 64 tiles, LDS-DMA staging, 16x16x32 MFMA)
-bool unetk_conv_bf16s_v3_ok(int N, int H, int W, int Cin, int Cout, int xs, int ys);
-int unetk_conv_bf16s_v3_stat_rows(int N, int H, int W);
-int unetk_conv_bf16s_v3_run(ConvParams p, hipStream_t st);
 
 struct WgParams {
   const float* x;

@@ -167,6 +167,17 @@ inline ImgAddr planes(int HW_floats, int group, int step, int planes_total) {
 
 const int SUB_BPS = 64;   // subsample blocks per sample
 
+// The plan of the 2-D launch over a 3-D layer's planes: `np` images of H x W in samples of spg planes; klive = live channels of
+// the contraction axis, kd / ng = fused depth taps / tap groups (they size the stream-K cut).
+ConvPlan plane_plan(int np, int H, int W, int Cin, int Cout, int spg, int klive = 0, int kd = 0, int ng = 0, int stride = 1,
+                    int bf16 = 0) {
+  ConvShape s{};
+  s.N = np; s.H = H; s.W = W; s.Cin = Cin; s.Cout = Cout; s.xs = Cin; s.ys = Cout; s.spg = spg;
+  s.klive = klive; s.kd = kd; s.ng = ng; s.stride = stride; s.bf16 = bf16;
+  return unetk_conv_plan(s);
+}
+bool is_lin(const ConvPlan& pl) { return pl.family == CONV_LIN || pl.family == CONV_LIN_SK; }
+
 // A strided conv whose OUTPUT planes are small (W < 32: the linear-pixel kernel's range) and whose input extents are even
 // (SAME padding then puts the one pad row / column / plane behind the data): forward = space-to-depth + grouped taps.
 // UNETK_S2LIN=0 (measurement): the tiled stride-2 kernel as before.
@@ -175,7 +186,7 @@ bool s2lin_ok(const unetk_conv3d_desc* d, const Geo3& g) {
   if (on < 0) { const char* e = getenv("UNETK_S2LIN"); on = e ? atoi(e) : 1; }
   if (!on || d->shw != 2 || (d->H & 1) || (d->W & 1) || d->Cin % 16 != 0) return false;
   if (d->sd == 2 && ((d->D & 1) || d->kd != 3)) return false;
-  return unetk_conv_lin_ok(d->N * g.Do, g.Ho, g.Wo, d->Cin, d->Cout, g.Do);
+  return is_lin(plane_plan(d->N * g.Do, g.Ho, g.Wo, d->Cin, d->Cout, g.Do));
 }
 inline size_t s2lin_xs_floats(const unetk_conv3d_desc* d, const Geo3& g) {
   return ((size_t)d->N * g.Do * g.Ho * g.Wo * (d->sd == 2 ? 8 : 4) * d->Cin + 63) & ~(size_t)63;
@@ -207,11 +218,11 @@ extern "C" int unetk_conv3d_stat_rows(const unetk_conv3d_desc* d) {
   if (!desc_ok(d)) return UNETK_E_BADARG;
   const Geo3 g = geo3(d);
   if (d->shw == 2) {
-    if (s2lin_ok(d, g)) return unetk_conv_stat_rows_lin(d->N * g.Do, g.Ho, g.Wo, g.Do, d->Cout);
-    if (unetk_conv_stride2_ok(d->Cin, d->Cout)) return unetk_conv_stat_rows(d->N * g.Do, g.Ho, g.Wo, d->Cin, d->Cout, g.Do, 2);
+    if (s2lin_ok(d, g)) return plane_plan(d->N * g.Do, g.Ho, g.Wo, d->Cin, d->Cout, g.Do).stat_rows;
+    if (unetk_conv_stride2_ok(d->Cin, d->Cout)) return plane_plan(d->N * g.Do, g.Ho, g.Wo, d->Cin, d->Cout, g.Do, 0, 0, 0, 2).stat_rows;
     return d->N * SUB_BPS;
   }
-  return unetk_conv_stat_rows(d->N * g.Do, d->H, d->W, d->Cin, d->Cout, g.Do);
+  return plane_plan(d->N * g.Do, d->H, d->W, d->Cin, d->Cout, g.Do).stat_rows;
 }
 
 // UNETK_KSKIP (measurement; read once): bit 0 = skip the dead 16-channel chunks of a channel-padded contraction axis
@@ -245,12 +256,12 @@ extern "C" size_t unetk_conv3d_ws_bytes(const unetk_conv3d_desc* d) {
   }
   if (s2lin_ok(d, g)) {              // space-to-depth copy of x + the stream-K slab of the grouped-tap forward
     const size_t sb = s2lin_xs_floats(d, g) * sizeof(float) +
-                      unetk_conv_lin_sk_bytes(d->N * g.Do, g.Ho, g.Wo, live_k(d->cin_live8, d->Cin), d->Cout, g.Do, d->kd * 4);
+                      plane_plan(d->N * g.Do, g.Ho, g.Wo, d->Cin, d->Cout, g.Do, live_k(d->cin_live8, d->Cin), 0, d->kd * 4).ws_bytes;
     if (sb > bytes) bytes = sb;
   }
   if (d->shw == 1 && d->sd == 1) {   // stream-K slabs of the small-plane kernel, forward and input gradient
-    const size_t kf = unetk_conv_lin_sk_bytes(d->N * d->D, d->H, d->W, live_k(d->cin_live8, d->Cin), d->Cout, d->D, d->kd);
-    const size_t kb = unetk_conv_lin_sk_bytes(d->N * d->D, d->H, d->W, live_k(d->cout_live8, d->Cout), d->Cin, d->D, d->kd);
+    const size_t kf = plane_plan(d->N * d->D, d->H, d->W, d->Cin, d->Cout, d->D, live_k(d->cin_live8, d->Cin), d->kd).ws_bytes;
+    const size_t kb = plane_plan(d->N * d->D, d->H, d->W, d->Cout, d->Cin, d->D, live_k(d->cout_live8, d->Cout), d->kd).ws_bytes;
     if (kf > bytes) bytes = kf;
     if (kb > bytes) bytes = kb;
   }
@@ -275,7 +286,7 @@ extern "C" int unetk_conv3d_fwd(const unetk_conv3d_desc* d, const float* x, cons
     ts = d->Cout;
   }
   const int HWx = d->H * d->W * d->x_stride, HWt = (native ? g.Ho * g.Wo : d->H * d->W) * ts;
-  if (d->kd == 3 && d->sd == 1 && d->shw == 1 && unetk_conv_lin_ok(d->N * d->D, d->H, d->W, d->Cin, d->Cout, d->D)) {
+  if (d->kd == 3 && d->sd == 1 && d->shw == 1 && is_lin(plane_plan(d->N * d->D, d->H, d->W, d->Cin, d->Cout, d->D))) {
     // small planes, depth stride 1 (UNet3D's 24^2 / 12^2 / 6^2 levels): the three depth taps are contracted inside ONE
     // launch of the linear-pixel kernel (K = 27 Cin) -- no memset, no read-modify-write of y per tap
     ConvParams p{};
@@ -333,7 +344,7 @@ extern "C" int unetk_conv3d_fwd(const unetk_conv3d_desc* d, const float* x, cons
     set_live(p, d->cin_live8, d->Cin);
     const size_t xsb = s2lin_xs_floats(d, g) * sizeof(float);
     p.sk_slab = (float*)((char*)ws + xsb); p.sk_slab_bytes = ws_bytes - xsb;
-    return unetk_conv_run_lin(p, st);
+    return unetk_conv_run(p, st);
   }
   if (native && d->kd == 3) {
     // natively strided (3,3,3) conv (UNet3D's (1,2,2) and (2,2,2) down-sampling layers): the three depth taps are contracted
@@ -517,7 +528,7 @@ extern "C" int unetk_conv3d_dgrad(const unetk_conv3d_desc* d, const float* dy, c
     UNETK_REQUIRE(ws && unetk_aligned16(ws));
     if (ws_bytes < unetk_conv3d_ws_bytes(d)) return UNETK_E_WORKSPACE;
   }
-  if (d->kd == 3 && d->sd == 1 && d->shw == 1 && unetk_conv_lin_ok(d->N * d->D, d->H, d->W, d->Cout, d->Cin, d->D)) {
+  if (d->kd == 3 && d->sd == 1 && d->shw == 1 && is_lin(plane_plan(d->N * d->D, d->H, d->W, d->Cout, d->Cin, d->D))) {
     // fused depth taps (see unetk_conv3d_fwd): dx[di] = sum_dt dy[di + pb - dt] * w[dt]
     ConvParams p{};
     p.x = dy; p.wp = wp_dgrad; p.y = dx; p.stat = nullptr;
@@ -682,7 +693,8 @@ extern "C" int unetk_conv3d_pack_bf16(const float* w, int kd, int Cin, int Cout,
 extern "C" int unetk_conv3d_stat_rows_bf16(const unetk_conv3d_desc* d) {
   if (!desc_ok(d)) return UNETK_E_BADARG;
   if (!bf16_rule_ok(d)) return UNETK_E_UNSUPPORTED;
-  return unetk_conv_stat_rows_bf16(d->N * d->D, d->H, d->W, d->Cin, d->Cout);
+  const ConvPlan pl = plane_plan(d->N * d->D, d->H, d->W, d->Cin, d->Cout, d->D, 0, 0, 0, 1, UNETK_BF16);
+  return pl.stat_rows > 0 ? pl.stat_rows : pl.rc;
 }
 
 extern "C" size_t unetk_conv3d_ws_bytes_bf16(const unetk_conv3d_desc* d) {
@@ -711,7 +723,7 @@ extern "C" int unetk_conv3d_fwd_bf16(const unetk_conv3d_desc* d, const float* x,
   p.ya = planes(d->H * d->W * d->y_stride, d->D, 1, d->D);
   p.spg = d->D;
   if (d->kd == 3) { p.kd = 3; p.dsd = 1; p.dshift0 = -1; p.dstep = 1; p.din = d->D; p.dplane = HWx; }   // y[o] = sum_dt x[o - 1 + dt] w[dt]
-  return unetk_conv_run_bf16(p, (hipStream_t)stream);
+  return unetk_conv_run(p, (hipStream_t)stream);
 }
 
 extern "C" int unetk_conv3d_dgrad_bf16(const unetk_conv3d_desc* d, const float* dy, const void* wp_dgrad, float* dx,
@@ -732,7 +744,7 @@ extern "C" int unetk_conv3d_dgrad_bf16(const unetk_conv3d_desc* d, const float* 
   p.ya = planes(d->H * d->W * d->x_stride, d->D, 1, d->D);
   p.spg = d->D;
   if (d->kd == 3) { p.kd = 3; p.dsd = 1; p.dshift0 = 1; p.dstep = -1; p.din = d->D; p.dplane = HWy; }   // dx[i] = sum_dt dy[i + 1 - dt] w'[dt]
-  return unetk_conv_run_bf16(p, (hipStream_t)stream);
+  return unetk_conv_run(p, (hipStream_t)stream);
 }
 
 extern "C" int unetk_conv3d_wgrad_bf16(const unetk_conv3d_desc* d, const float* x, const float* dy, float* dw, void* ws,

@@ -614,14 +614,13 @@ __global__ void pack_conv3x3_kernel(const float* __restrict__ w, int Cin, int Co
     unetk_pack::conv3x3_f32(w, Cin, Cout, wp_fwd, wp_dgrad, i);      // csrc/pack.h
 }
 
-struct ConvCfg {
-  int id;  // 0: 128x128 tile, 1: 128x64 tile, 2: 256x32 tile (UNet3D's 30-channel levels, padded to 32), -1: direct
-  int th;
-};
+// Tile configurations of the tiled kernel: <WM, WN, TM, TN> = 128x128, 64x128 (4-row), 256x128 (16-row), 128x64, 256x64
+// (16-row), 256x32 (UNet3D's 30-channel levels, padded to 32)
+enum ConvTile { T_2222, T_2212, T_2242, T_4112, T_4122, T_4121 };
 
 // Small grids (deep levels at small batch: 8 x 32^2 pixels x 512 couts = 256 blocks of 128 x 128) leave CUs idle or
 // at one block each: halve the pixel tile (4-row tiles, <2,2,1,2>) when the 128 x 128 grid has fewer than 1.5 blocks
-// per CU.  The statistic rows follow the tile height, so both users go through this one predicate.
+// per CU.
 inline bool small_grid(int N, int H, int W, int Cout) {
   if (Cout % 128 != 0) return false;
   const int64_t blocks = (int64_t)N * ((H + 7) / 8) * ((W + TW - 1) / TW) * (Cout / 128);
@@ -642,23 +641,14 @@ inline bool big_grid(int N, int H, int W, int Cin, int Cout, int spg, bool nbr) 
   return blocks >= 512;
 }
 
-inline ConvCfg pick_cfg(int Cin, int Cout) {
-  if (Cin % CK == 0 && Cout % 128 == 0) return {0, 8};
-  if (Cin % CK == 0 && Cout % 64 == 0) return {1, 8};
-  if (Cin % CK == 0 && Cout % 32 == 0) return {2, 16};
-  return {-1, 8};
+// output-channel tile width of the MFMA kernels for these channel counts: 128 / 64 / 32, 0 = first layers (direct kernels)
+inline int tiled_bn(int Cin, int Cout) {
+  if (Cin % CK != 0) return 0;
+  return Cout % 128 == 0 ? 128 : Cout % 64 == 0 ? 64 : Cout % 32 == 0 ? 32 : 0;
 }
 
-// rows of the pixel tile the stride-1 tiled kernel takes for this shape (one statistic row per tile)
-inline int tile_rows(int N, int H, int W, int Cin, int Cout, int spg, bool nbr) {
-  const ConvCfg cfg = pick_cfg(Cin, Cout);
-  if (cfg.id == 0 && small_grid(N, H, W, Cout)) return 4;
-  if ((cfg.id == 0 || cfg.id == 1) && big_grid(N, H, W, Cin, Cout, spg, nbr)) return 16;
-  return cfg.th;
-}
-
-template <int WM, int WN, int TM, int TN, int S = 1, int DIL = 1, int MODE = 0>
-int launch_igemm_mode(const ConvParams& p, int n_mtiles, hipStream_t st) {
+template <int WM, int WN, int TM, int TN, int S, int DIL, int MODE>
+int launch_igemm_mode(const ConvParams& p, hipStream_t st) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   constexpr int TH = BM / TW;
   constexpr size_t lds = (2 * (S * TH + 2 * DIL) * halo_row_f(S, DIL) + 2 * CK * BN) * sizeof(float);
@@ -671,160 +661,176 @@ int launch_igemm_mode(const ConvParams& p, int n_mtiles, hipStream_t st) {
     if (e != hipSuccess) return (int)e;
     attr_done = true;
   }
-  const int grid = n_mtiles * p.n_ntiles;
-  UNETK_LAUNCH(kern, dim3(grid), dim3(WM * WN * 64), lds, st, p);
+  UNETK_LAUNCH(kern, dim3(p.stat_rows * p.n_ntiles), dim3(WM * WN * 64), lds, st, p);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }
 
-template <int WM, int WN, int TM, int TN, int S = 1, int DIL = 1, bool NBR = false>
-int launch_igemm(const ConvParams& p, int n_mtiles, hipStream_t st) {
-  if constexpr (NBR) return launch_igemm_mode<WM, WN, TM, TN, S, DIL, 2>(p, n_mtiles, st);
-  if (p.asc != nullptr) {       // inference epilogue: (scale, shift) + ReLU [+ 2 x 2 max-pool]
-    if constexpr (S == 1 && DIL == 1) {
-      if (p.accumulate || p.stat != nullptr) return UNETK_E_UNSUPPORTED;
-      return p.pool != nullptr ? launch_igemm_mode<WM, WN, TM, TN, 1, 1, 4>(p, n_mtiles, st)
-                               : launch_igemm_mode<WM, WN, TM, TN, 1, 1, 3>(p, n_mtiles, st);
-    } else {
-      return UNETK_E_UNSUPPORTED;
+// MODE 0 plain, 1 accumulate, 2 norm-backward reduction (128-wide dense tiles), 3 / 4 inference epilogue without / with the
+// 2 x 2 max-pool (dense tiles)
+template <int WM, int WN, int TM, int TN, int S = 1, int DIL = 1>
+int launch_igemm(int mode, const ConvParams& p, hipStream_t st) {
+  if constexpr (S == 1 && DIL == 1) {
+    if constexpr (WN == 2) {
+      if (mode == 2) return launch_igemm_mode<WM, WN, TM, TN, 1, 1, 2>(p, st);
     }
+    if (mode == 3) return launch_igemm_mode<WM, WN, TM, TN, 1, 1, 3>(p, st);
+    if (mode == 4) return launch_igemm_mode<WM, WN, TM, TN, 1, 1, 4>(p, st);
   }
-  if (p.accumulate) return launch_igemm_mode<WM, WN, TM, TN, S, DIL, 1>(p, n_mtiles, st);
-  return launch_igemm_mode<WM, WN, TM, TN, S, DIL, 0>(p, n_mtiles, st);
+  if (mode == 1) return launch_igemm_mode<WM, WN, TM, TN, S, DIL, 1>(p, st);
+  if (mode == 0) return launch_igemm_mode<WM, WN, TM, TN, S, DIL, 0>(p, st);
+  return UNETK_E_UNSUPPORTED;
+}
+
+void plan_tiles(const ConvShape& s, ConvPlan& pl, int th, int bn) {
+  pl.th = th;
+  pl.tiles_h = (s.H + th - 1) / th;
+  pl.tiles_w = (s.W + TW - 1) / TW;
+  pl.stat_rows = s.N * pl.tiles_h * pl.tiles_w;
+  pl.n_ntiles = s.Cout / bn;
+}
+
+// stride-1, dense, fp32: linear-pixel kernel on small planes, else the tiled kernel, else the first-layer kernels
+void plan_dense(const ConvShape& s0, ConvPlan& pl) {
+  ConvShape s = s0;
+  if (s.spg < 1) s.spg = 1;
+  pl.spg = s.spg;
+  if (unetk_conv_plan_lin(s, pl)) return;
+  const bool nbr = s.nbr != 0;
+  const int bn = tiled_bn(s.Cin, s.Cout);
+  if (bn > 0) {
+    pl.family = CONV_TILED;
+    if (bn == 128 && small_grid(s.N, s.H, s.W, s.Cout)) { pl.cfg = T_2212; plan_tiles(s, pl, 4, 128); }
+    else if (bn >= 64 && big_grid(s.N, s.H, s.W, s.Cin, s.Cout, s.spg, nbr)) { pl.cfg = bn == 128 ? T_2242 : T_4122; plan_tiles(s, pl, 16, bn); }
+    else if (bn == 32) { pl.cfg = T_4121; plan_tiles(s, pl, 16, 32); }
+    else { pl.cfg = bn == 128 ? T_2222 : T_4112; plan_tiles(s, pl, 8, bn); }
+    pl.mode = nbr ? 2 : s.affine ? (s.pool ? 4 : 3) : s.accumulate ? 1 : 0;
+    if (s.ybf16 || (nbr && bn != 128)) pl.rc = UNETK_E_UNSUPPORTED;      // the fused reduction exists for the 128-wide tiles
+    if (s.affine && (s.accumulate || s.stat)) pl.rc = UNETK_E_UNSUPPORTED;
+    return;
+  }
+  plan_tiles(s, pl, 8, 1);      // one block per 8 x 16 pixel tile, every output channel
+  pl.n_ntiles = 0;
+  pl.family = (s.Cout == 64 && s.Cin >= 1 && s.Cin <= 5) ? CONV_C3_MFMA : CONV_DIRECT;      // first layers: the matrix-pipe variant
+  pl.rc = UNETK_E_UNSUPPORTED;
+  if (s.Cout % 4 != 0 || s.Cout > 1024 || nbr) return;
+  const int PL = 256 / (s.Cout / 4);
+  pl.lds = s.stat ? (size_t)2 * PL * s.Cout * sizeof(float) : 0;
+  const size_t halo = (size_t)180 * s.Cin * sizeof(float);
+  if (halo > pl.lds) pl.lds = halo;
+  if (pl.lds > 64 * 1024) return;
+  if (s.ybf16 && s.accumulate) return;      // UNETK_BF16S first layer: fp32 image in, bf16 out
+  if (pl.family == CONV_C3_MFMA) {
+    if (s.affine && (s.pool || s.accumulate || s.stat)) return;
+    pl.lds = ((size_t)((180 * s.Cin + 3) & ~3) + 2 * 4 * 64) * sizeof(float);
+  } else if (s.affine) {
+    return;                                 // the generic direct kernel has no inference epilogue
+  }
+  pl.rc = UNETK_OK;
+}
+
+int launch_tiled(const ConvPlan& pl, const ConvParams& p, hipStream_t st) {
+  if (pl.family == CONV_TILED_S2)
+    return pl.cfg == T_2212 ? launch_igemm<2, 2, 1, 2, 2>(pl.mode, p, st) : launch_igemm<4, 1, 1, 2, 2>(pl.mode, p, st);
+  if (pl.family == CONV_ATROUS)
+    return pl.cfg == T_2222 ? launch_igemm<2, 2, 2, 2, 1, 2>(pl.mode, p, st) : launch_igemm<4, 1, 1, 2, 1, 2>(pl.mode, p, st);
+  switch (pl.cfg) {
+    case T_2212: return launch_igemm<2, 2, 1, 2>(pl.mode, p, st);
+    case T_2222: return launch_igemm<2, 2, 2, 2>(pl.mode, p, st);
+    case T_2242: return launch_igemm<2, 2, 4, 2>(pl.mode, p, st);
+    case T_4112: return launch_igemm<4, 1, 1, 2>(pl.mode, p, st);
+    case T_4122: return launch_igemm<4, 1, 2, 2>(pl.mode, p, st);
+    default: return launch_igemm<4, 1, 2, 1>(pl.mode, p, st);
+  }
+}
+
+template <typename TY>
+int launch_direct(const ConvParams& p, size_t lds, hipStream_t st) {
+  const dim3 grid(p.stat_rows), block(256);
+  switch (p.Cin) {
+    case 1: UNETK_LAUNCH((conv3x3_direct_kernel<1, TY>), grid, block, lds, st, p); break;
+    case 2: UNETK_LAUNCH((conv3x3_direct_kernel<2, TY>), grid, block, lds, st, p); break;
+    case 3: UNETK_LAUNCH((conv3x3_direct_kernel<3, TY>), grid, block, lds, st, p); break;
+    case 4: UNETK_LAUNCH((conv3x3_direct_kernel<4, TY>), grid, block, lds, st, p); break;
+    case 5: UNETK_LAUNCH((conv3x3_direct_kernel<5, TY>), grid, block, lds, st, p); break;
+    default: UNETK_LAUNCH((conv3x3_direct_kernel<0, TY>), grid, block, lds, st, p); break;
+  }
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
+template <typename TY, bool AFF>
+int launch_c3(const ConvParams& p, size_t lds, hipStream_t st) {
+  const dim3 grid(p.stat_rows < 256 * 6 ? p.stat_rows : 256 * 6), block(256);      // persistent: six resident blocks per CU walk the tiles
+  switch (p.Cin) {
+    case 1: UNETK_LAUNCH((conv3x3_c3_mfma_kernel<1, TY, AFF>), grid, block, lds, st, p); break;
+    case 2: UNETK_LAUNCH((conv3x3_c3_mfma_kernel<2, TY, AFF>), grid, block, lds, st, p); break;
+    case 3: UNETK_LAUNCH((conv3x3_c3_mfma_kernel<3, TY, AFF>), grid, block, lds, st, p); break;
+    case 4: UNETK_LAUNCH((conv3x3_c3_mfma_kernel<4, TY, AFF>), grid, block, lds, st, p); break;
+    default: UNETK_LAUNCH((conv3x3_c3_mfma_kernel<5, TY, AFF>), grid, block, lds, st, p); break;
+  }
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
 }
 
 }  // namespace
 
-// H, W = OUTPUT extent; stride 2 always takes the tiled kernel.  Cout % 128 == 0: 4-row tiles -- the stride-2 halo of an
-// 8-row tile (18 x 34 pixels, 98 KB double-buffered) leaves one block per CU, the 10 x 34 halo of a 4-row tile two
-// (53 -> 69 TFLOP/s on UNet3D's (1,2,2) layers); the 64-wide configuration is better off with 8 rows (measured).
-static int s2_th(int Cout) { return Cout % 128 == 0 ? 4 : 8; }
-int unetk_conv_stat_rows(int N, int H, int W, int Cin, int Cout, int spg, int stride, int dil) {
-  if (dil == 2) return N * ((H + 7) / 8) * ((W + TW - 1) / TW);
-  if (stride == 2) return N * ((H + s2_th(Cout) - 1) / s2_th(Cout)) * ((W + TW - 1) / TW);
-  if (unetk_conv_lin_ok(N, H, W, Cin, Cout, spg)) return unetk_conv_stat_rows_lin(N, H, W, spg, Cout);
-  const int th = tile_rows(N, H, W, Cin, Cout, spg, false);
-  return N * ((H + th - 1) / th) * ((W + TW - 1) / TW);
-}
-
 bool unetk_conv_stride2_ok(int Cin, int Cout) { return Cin % CK == 0 && Cout % 64 == 0; }
 
+ConvPlan unetk_conv_plan(const ConvShape& s) {
+  ConvPlan pl{};
+  pl.spg = s.spg;
+  pl.rc = UNETK_OK;
+  if (((s.nbr || s.affine) && (s.stride == 2 || s.dil == 2)) || (s.pool && ((s.H | s.W) & 1))) {
+    pl.rc = UNETK_E_UNSUPPORTED;
+    return pl;
+  }
+  if (s.stride == 2 || s.dil == 2) {
+    // stride 2 (H, W = OUTPUT extent) always takes the tiled kernel.  Cout % 128 == 0: 4-row tiles -- the stride-2 halo of an
+    // 8-row tile (18 x 34 pixels, 98 KB double-buffered) leaves one block per CU, the 10 x 34 halo of a 4-row tile two
+    // (53 -> 69 TFLOP/s on UNet3D's (1,2,2) layers); the 64-wide configuration is better off with 8 rows (measured).
+    // Atrous: tiled fp32 kernel only, 8-row tiles (SmallUNet's two 32 x 32 levels).
+    const bool s2 = s.stride == 2, wide = s.Cout % 128 == 0;
+    pl.family = s2 ? CONV_TILED_S2 : CONV_ATROUS;
+    pl.cfg = !wide ? T_4112 : s2 ? T_2212 : T_2222;
+    plan_tiles(s, pl, s2 && wide ? 4 : 8, wide ? 128 : 64);
+    pl.mode = s.accumulate ? 1 : 0;
+    if (s.bf16 || s.ybf16 || !unetk_conv_stride2_ok(s.Cin, s.Cout) || s.xs % 4 != 0) pl.rc = UNETK_E_UNSUPPORTED;
+    return pl;
+  }
+  if (s.bf16) {
+    unetk_conv_plan_bf16(s, pl);
+  } else {
+    plan_dense(s, pl);
+  }
+  if (s.dil > 2 || s.dil < 0) pl.rc = UNETK_E_UNSUPPORTED;
+  return pl;
+}
+
 int unetk_conv_run(ConvParams p, hipStream_t st) {
-  if ((p.ny != nullptr || p.asc != nullptr) && (p.stride == 2 || p.dil == 2)) return UNETK_E_UNSUPPORTED;
-  if (p.stride == 2) {   // p.H x p.W = output extent, p.Hin x p.Win = input extent
-    if (p.bf16 || !unetk_conv_stride2_ok(p.Cin, p.Cout) || p.xs % 4 != 0) return UNETK_E_UNSUPPORTED;
-    p.tiles_h = (p.H + s2_th(p.Cout) - 1) / s2_th(p.Cout);
-    p.tiles_w = (p.W + TW - 1) / TW;
-    const int n_mt = p.N * p.tiles_h * p.tiles_w;
-    p.stat_rows = n_mt;
-    if (p.Cout % 128 == 0) {
-      p.n_ntiles = p.Cout / 128;
-      return launch_igemm<2, 2, 1, 2, 2>(p, n_mt, st);
-    }
-    p.n_ntiles = p.Cout / 64;
-    return launch_igemm<4, 1, 1, 2, 2>(p, n_mt, st);
+  ConvShape s{};
+  s.N = p.N; s.H = p.H; s.W = p.W; s.Cin = p.Cin; s.Cout = p.Cout; s.xs = p.xs; s.ys = p.ys; s.spg = p.spg;
+  s.bf16 = p.bf16; s.ybf16 = p.ybf16; s.stride = p.stride; s.dil = p.dil;
+  s.klive = p.nlive * CK; s.kd = p.kd; s.ng = p.ng;
+  s.nbr = p.ny != nullptr; s.nys = p.nys;
+  s.affine = p.asc != nullptr; s.pool = p.pool != nullptr; s.accumulate = p.accumulate; s.khalf = p.khalf != 0;
+  s.stat = p.stat != nullptr;
+  s.ws_bytes = (p.sk_slab != nullptr && unetk_aligned16(p.sk_slab)) ? p.sk_slab_bytes : 0;
+  const ConvPlan pl = unetk_conv_plan(s);
+  if (pl.rc != UNETK_OK) return pl.rc;
+  p.spg = pl.spg;
+  p.tiles_h = pl.tiles_h; p.tiles_w = pl.tiles_w; p.n_ntiles = pl.n_ntiles; p.stat_rows = pl.stat_rows; p.lin_pix = pl.lin_pix;
+  switch (pl.family) {
+    case CONV_LIN:
+    case CONV_LIN_SK: return unetk_conv_launch_lin(pl, p, st);
+    case CONV_BF16: return unetk_conv_launch_bf16(pl, p, st);
+    case CONV_BF16S_V3: return unetk_conv_launch_bf16s_v3(pl, p, st);
+    case CONV_C3_MFMA:
+      if (p.asc != nullptr) return p.ybf16 ? launch_c3<bf16_t, true>(p, pl.lds, st) : launch_c3<float, true>(p, pl.lds, st);
+      return p.ybf16 ? launch_c3<bf16_t, false>(p, pl.lds, st) : launch_c3<float, false>(p, pl.lds, st);
+    case CONV_DIRECT: return p.ybf16 ? launch_direct<bf16_t>(p, pl.lds, st) : launch_direct<float>(p, pl.lds, st);
+    default: return launch_tiled(pl, p, st);
   }
-  if (p.dil == 2) {      // atrous: tiled fp32 kernel only (SmallUNet's two 32 x 32 levels)
-    if (p.bf16 || p.Cin % CK != 0 || p.Cout % 64 != 0 || p.xs % 4 != 0) return UNETK_E_UNSUPPORTED;
-    p.tiles_h = (p.H + 7) / 8;
-    p.tiles_w = (p.W + TW - 1) / TW;
-    const int n_mt = p.N * p.tiles_h * p.tiles_w;
-    p.stat_rows = n_mt;
-    if (p.Cout % 128 == 0) {
-      p.n_ntiles = p.Cout / 128;
-      return launch_igemm<2, 2, 2, 2, 1, 2>(p, n_mt, st);
-    }
-    p.n_ntiles = p.Cout / 64;
-    return launch_igemm<4, 1, 1, 2, 1, 2>(p, n_mt, st);
-  }
-  if (p.dil > 2 || p.dil < 0) return UNETK_E_UNSUPPORTED;
-  if (p.bf16) return (p.asc != nullptr && p.bf16 != UNETK_BF16S) ? UNETK_E_UNSUPPORTED : unetk_conv_run_bf16(p, st);
-  if (p.spg < 1) p.spg = 1;
-  if (unetk_conv_lin_ok(p.N, p.H, p.W, p.Cin, p.Cout, p.spg))                                     // small planes: linear M
-    return (p.asc != nullptr && (p.pool != nullptr || p.accumulate || p.kd > 1)) ? UNETK_E_UNSUPPORTED : unetk_conv_run_lin(p, st);
-  const ConvCfg cfg = pick_cfg(p.Cin, p.Cout);
-  const int th = tile_rows(p.N, p.H, p.W, p.Cin, p.Cout, p.spg, p.ny != nullptr);
-  const bool small = cfg.id == 0 && th == 4, big = cfg.id <= 1 && th == 16;
-  p.tiles_h = (p.H + th - 1) / th;
-  p.tiles_w = (p.W + TW - 1) / TW;
-  const int n_mtiles = p.N * p.tiles_h * p.tiles_w;
-  p.stat_rows = n_mtiles;
-  if (p.ny != nullptr && cfg.id != 0) return UNETK_E_UNSUPPORTED;   // the fused reduction exists for the 128-wide tiles
-  if (small) {
-    p.n_ntiles = p.Cout / 128;
-    if (p.ny != nullptr) return launch_igemm<2, 2, 1, 2, 1, 1, true>(p, n_mtiles, st);
-    return launch_igemm<2, 2, 1, 2>(p, n_mtiles, st);
-  }
-  if (big && cfg.id == 1) {
-    p.n_ntiles = p.Cout / 64;
-    return launch_igemm<4, 1, 2, 2>(p, n_mtiles, st);
-  }
-  if (big) {
-    p.n_ntiles = p.Cout / 128;
-    if (p.ny != nullptr) return launch_igemm<2, 2, 4, 2, 1, 1, true>(p, n_mtiles, st);
-    return launch_igemm<2, 2, 4, 2>(p, n_mtiles, st);
-  }
-  if (cfg.id == 0) {
-    p.n_ntiles = p.Cout / 128;
-    if (p.ny != nullptr) return launch_igemm<2, 2, 2, 2, 1, 1, true>(p, n_mtiles, st);
-    return launch_igemm<2, 2, 2, 2>(p, n_mtiles, st);
-  }
-  if (cfg.id == 1) {
-    p.n_ntiles = p.Cout / 64;
-    return launch_igemm<4, 1, 1, 2>(p, n_mtiles, st);
-  }
-  if (cfg.id == 2) {
-    p.n_ntiles = p.Cout / 32;
-    return launch_igemm<4, 1, 2, 1>(p, n_mtiles, st);
-  }
-  if (p.Cout % 4 != 0 || p.Cout > 1024) return UNETK_E_UNSUPPORTED;
-  const int PL = 256 / (p.Cout / 4);
-  size_t lds = p.stat ? (size_t)2 * PL * p.Cout * sizeof(float) : 0;
-  const size_t halo = (size_t)180 * p.Cin * sizeof(float);
-  if (halo > lds) lds = halo;
-  if (lds > 64 * 1024) return UNETK_E_UNSUPPORTED;
-  if (p.Cout == 64 && p.Cin >= 1 && p.Cin <= 5) {      // first layers: the matrix-pipe variant
-    const size_t l3 = ((size_t)((180 * p.Cin + 3) & ~3) + 2 * 4 * 64) * sizeof(float);
-    const int c3_grid = n_mtiles < 256 * 6 ? n_mtiles : 256 * 6;      // persistent: six resident blocks per CU walk the tiles
-#define C3_LAUNCH(CI)                                                                                              \
-  case CI:                                                                                                         \
-    if (p.asc != nullptr) {                                                                                        \
-      if (p.ybf16) UNETK_LAUNCH((conv3x3_c3_mfma_kernel<CI, bf16_t, true>), dim3(c3_grid), dim3(256), l3, st, p);  \
-      else UNETK_LAUNCH((conv3x3_c3_mfma_kernel<CI, float, true>), dim3(c3_grid), dim3(256), l3, st, p);           \
-    } else if (p.ybf16) UNETK_LAUNCH((conv3x3_c3_mfma_kernel<CI, bf16_t>), dim3(c3_grid), dim3(256), l3, st, p);   \
-    else UNETK_LAUNCH((conv3x3_c3_mfma_kernel<CI, float>), dim3(c3_grid), dim3(256), l3, st, p);                   \
-    break;
-    if (p.ybf16 && p.accumulate) return UNETK_E_UNSUPPORTED;
-    if (p.asc != nullptr && (p.pool != nullptr || p.accumulate || p.stat != nullptr)) return UNETK_E_UNSUPPORTED;
-    switch (p.Cin) { C3_LAUNCH(1) C3_LAUNCH(2) C3_LAUNCH(3) C3_LAUNCH(4) C3_LAUNCH(5) default: break; }
-#undef C3_LAUNCH
-    UNETK_LAUNCH_CHECK();
-    return UNETK_OK;
-  }
-  if (p.asc != nullptr) return UNETK_E_UNSUPPORTED;      // the generic direct kernel has no inference epilogue
-  if (p.ybf16) {      // UNETK_BF16S first layer: fp32 image in, bf16 out
-    if (p.accumulate) return UNETK_E_UNSUPPORTED;
-    switch (p.Cin) {
-      case 1: UNETK_LAUNCH((conv3x3_direct_kernel<1, bf16_t>), dim3(n_mtiles), dim3(256), lds, st, p); break;
-      case 2: UNETK_LAUNCH((conv3x3_direct_kernel<2, bf16_t>), dim3(n_mtiles), dim3(256), lds, st, p); break;
-      case 3: UNETK_LAUNCH((conv3x3_direct_kernel<3, bf16_t>), dim3(n_mtiles), dim3(256), lds, st, p); break;
-      case 4: UNETK_LAUNCH((conv3x3_direct_kernel<4, bf16_t>), dim3(n_mtiles), dim3(256), lds, st, p); break;
-      case 5: UNETK_LAUNCH((conv3x3_direct_kernel<5, bf16_t>), dim3(n_mtiles), dim3(256), lds, st, p); break;
-      default: UNETK_LAUNCH((conv3x3_direct_kernel<0, bf16_t>), dim3(n_mtiles), dim3(256), lds, st, p); break;
-    }
-    UNETK_LAUNCH_CHECK();
-    return UNETK_OK;
-  }
-  switch (p.Cin) {
-    case 1: UNETK_LAUNCH(conv3x3_direct_kernel<1>, dim3(n_mtiles), dim3(256), lds, st, p); break;
-    case 2: UNETK_LAUNCH(conv3x3_direct_kernel<2>, dim3(n_mtiles), dim3(256), lds, st, p); break;
-    case 3: UNETK_LAUNCH(conv3x3_direct_kernel<3>, dim3(n_mtiles), dim3(256), lds, st, p); break;
-    case 4: UNETK_LAUNCH(conv3x3_direct_kernel<4>, dim3(n_mtiles), dim3(256), lds, st, p); break;
-    case 5: UNETK_LAUNCH(conv3x3_direct_kernel<5>, dim3(n_mtiles), dim3(256), lds, st, p); break;
-    default: UNETK_LAUNCH(conv3x3_direct_kernel<0>, dim3(n_mtiles), dim3(256), lds, st, p); break;
-  }
-  UNETK_LAUNCH_CHECK();
-  return UNETK_OK;
 }
 
 namespace {
@@ -832,6 +838,36 @@ namespace {
 bool conv_desc_ok(const unetk_conv_desc* d) {
   return d && d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && d->x_stride >= d->Cin &&
          d->y_stride >= d->Cout;
+}
+
+// The conv a descriptor stands for -- forward, or transposed (the input gradient: a conv3x3 with Cin <-> Cout on the packed,
+// tap-flipped filters) -- as a plan shape and as the matching fields of ConvParams.
+// Forward UNETK_BF16S: bf16 in, bf16 out on the bf16 matrix cores where they take the channel counts, else the first layer
+// (fp32 image in, bf16 out: ybf16, which only the first-layer kernels have).
+ConvShape desc_shape(const unetk_conv_desc* d, bool transposed) {
+  ConvShape s{};
+  s.N = d->N; s.H = d->H; s.W = d->W; s.dil = d->dilation;
+  if (transposed) {
+    s.Cin = d->Cout; s.Cout = d->Cin; s.xs = d->y_stride; s.ys = d->x_stride;
+    s.bf16 = d->precision;
+  } else {
+    s.Cin = d->Cin; s.Cout = d->Cout; s.xs = d->x_stride; s.ys = d->y_stride;
+    s.bf16 = (d->precision == UNETK_BF16S && !unetk_conv_bf16_ok(d->Cin, d->Cout)) ? 0 : d->precision;
+    s.ybf16 = d->precision == UNETK_BF16S && s.bf16 == 0;
+  }
+  return s;
+}
+
+ConvParams desc_params(const unetk_conv_desc* d, bool transposed, const void* x, const void* w, void* y, void* ws, size_t ws_bytes) {
+  const ConvShape s = desc_shape(d, transposed);
+  ConvParams p{};
+  p.x = (const float*)x; p.wp = (const float*)w; p.y = (float*)y;
+  p.bf16 = s.bf16; p.ybf16 = s.ybf16; p.dil = s.dil;
+  p.N = s.N; p.H = s.H; p.W = s.W; p.Cin = s.Cin; p.Cout = s.Cout; p.xs = s.xs; p.ys = s.ys;
+  p.xa = unetk_dense_addr(p.H, p.W, p.xs);
+  p.ya = unetk_dense_addr(p.H, p.W, p.ys);
+  if (ws && unetk_aligned16(ws) && ws_bytes > 0) { p.sk_slab = (float*)ws; p.sk_slab_bytes = ws_bytes; }      // stream-K scratch
+  return p;
 }
 
 }  // namespace
@@ -851,17 +887,13 @@ extern "C" int unetk_conv3x3_pack(const float* w, int Cin, int Cout, float* wp_f
 
 extern "C" int unetk_conv3x3_stat_rows(const unetk_conv_desc* d) {
   if (!conv_desc_ok(d)) return UNETK_E_BADARG;
-  if (d->dilation == 2) return unetk_conv_stat_rows(d->N, d->H, d->W, d->Cin, d->Cout, 1, 1, 2);
-  if (d->precision == UNETK_BF16) return unetk_conv_stat_rows_bf16(d->N, d->H, d->W, d->Cin, d->Cout);
-  if (d->precision == UNETK_BF16S && unetk_conv_bf16_ok(d->Cin, d->Cout))
-    return unetk_conv_stat_rows_bf16s(d->N, d->H, d->W, d->Cin, d->Cout, d->x_stride, d->y_stride);
-  return unetk_conv_stat_rows(d->N, d->H, d->W, d->Cin, d->Cout);
+  const ConvPlan pl = unetk_conv_plan(desc_shape(d, false));
+  return pl.stat_rows > 0 ? pl.stat_rows : pl.rc;
 }
 
 extern "C" size_t unetk_conv3x3_ws_bytes(const unetk_conv_desc* d) {
   if (!conv_desc_ok(d) || d->precision != UNETK_FP32 || d->dilation > 1) return 0;
-  const size_t f = unetk_conv_lin_sk_bytes(d->N, d->H, d->W, d->Cin, d->Cout, 1, 1);
-  const size_t b = unetk_conv_lin_sk_bytes(d->N, d->H, d->W, d->Cout, d->Cin, 1, 1);
+  const size_t f = unetk_conv_plan(desc_shape(d, false)).ws_bytes, b = unetk_conv_plan(desc_shape(d, true)).ws_bytes;
   return f > b ? f : b;
 }
 
@@ -875,38 +907,18 @@ extern "C" int unetk_conv3x3_fwd_ws(const unetk_conv_desc* d, const void* x, con
   UNETK_REQUIRE(conv_desc_ok(d) && x && w && y);
   UNETK_REQUIRE(unetk_aligned16(x) && unetk_aligned16(w) && unetk_aligned16(y));
   UNETK_REQUIRE(d->y_stride % 4 == 0);
-  if (pick_cfg(d->Cin, d->Cout).id >= 0) UNETK_REQUIRE(d->x_stride % 4 == 0);
-  if (d->precision == UNETK_BF16 && !unetk_conv_bf16_ok(d->Cin, d->Cout)) return UNETK_E_UNSUPPORTED;
-  ConvParams p{};
-  p.bf16 = d->precision == UNETK_BF16 ? 1 : 0;
-  if (d->precision == UNETK_BF16S) {
-    if (d->dilation > 1) return UNETK_E_UNSUPPORTED;
-    if (unetk_conv_bf16_ok(d->Cin, d->Cout)) p.bf16 = UNETK_BF16S;         // bf16 in, bf16 out (igemm on the bf16 matrix cores)
-    else if (pick_cfg(d->Cin, d->Cout).id < 0) p.ybf16 = 1;                // first layer: fp32 image in, bf16 out (direct kernel)
-    else return UNETK_E_UNSUPPORTED;
-  }
-  p.x = (const float*)x; p.wp = (const float*)w; p.y = (float*)y; p.stat = stat_partials;
-  p.dil = d->dilation;
-  p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout; p.xs = d->x_stride; p.ys = d->y_stride;
-  p.xa = unetk_dense_addr(p.H, p.W, p.xs);
-  p.ya = unetk_dense_addr(p.H, p.W, p.ys);
-  if (ws && unetk_aligned16(ws) && ws_bytes > 0) { p.sk_slab = (float*)ws; p.sk_slab_bytes = ws_bytes; }
+  if (tiled_bn(d->Cin, d->Cout) > 0) UNETK_REQUIRE(d->x_stride % 4 == 0);
+  ConvParams p = desc_params(d, false, x, w, y, ws, ws_bytes);
+  p.stat = stat_partials;
   return unetk_conv_run(p, (hipStream_t)stream);
 }
 
 // ---- inference: conv + (scale, shift) + ReLU [+ 2 x 2 max-pool] in one pass
 extern "C" int unetk_conv3x3_fwd_affine_ok(const unetk_conv_desc* d, int with_pool) {
-  if (!conv_desc_ok(d) || d->dilation > 1 || d->precision == UNETK_BF16) return 0;
-  if (with_pool && ((d->H | d->W) & 1)) return 0;
-  const bool first = pick_cfg(d->Cin, d->Cout).id < 0 && d->Cout == 64 && d->Cin >= 1 && d->Cin <= 5;   // Encode1/conv1 on the matrix pipe
-  if (d->precision == UNETK_BF16S) {     // the persistent bf16-storage kernel (and the first layer: fp32 image in, bf16 out)
-    if (unetk_conv_bf16_ok(d->Cin, d->Cout))
-      return unetk_conv_bf16s_v3_ok(d->N, d->H, d->W, d->Cin, d->Cout, d->x_stride, d->y_stride) ? 1 : 0;
-    return (first && !with_pool) ? 1 : 0;
-  }
-  if (pick_cfg(d->Cin, d->Cout).id >= 0)       // the small-plane (linear-pixel) kernel has the affine epilogue but no pool
-    return (unetk_conv_lin_ok(d->N, d->H, d->W, d->Cin, d->Cout, 1) && with_pool) ? 0 : 1;
-  return (first && !with_pool) ? 1 : 0;
+  if (!conv_desc_ok(d) || d->dilation > 1) return 0;
+  ConvShape s = desc_shape(d, false);
+  s.affine = 1; s.pool = with_pool != 0;
+  return unetk_conv_plan(s).rc == UNETK_OK ? 1 : 0;
 }
 
 extern "C" int unetk_conv3x3_fwd_affine(const unetk_conv_desc* d, const void* x, const void* w, const float* scale,
@@ -916,19 +928,9 @@ extern "C" int unetk_conv3x3_fwd_affine(const unetk_conv_desc* d, const void* x,
   UNETK_REQUIRE(unetk_aligned16(x) && unetk_aligned16(w) && unetk_aligned16(z));
   UNETK_REQUIRE(d->y_stride % 4 == 0 && (pooled == nullptr || (pooled_stride >= d->Cout && unetk_aligned16(pooled))));
   if (!unetk_conv3x3_fwd_affine_ok(d, pooled != nullptr)) return UNETK_E_UNSUPPORTED;
-  if (pick_cfg(d->Cin, d->Cout).id >= 0) UNETK_REQUIRE(d->x_stride % 4 == 0);
-  ConvParams p{};
-  if (d->precision == UNETK_BF16S) {
-    if (unetk_conv_bf16_ok(d->Cin, d->Cout)) p.bf16 = UNETK_BF16S;      // bf16 in, bf16 out
-    else p.ybf16 = 1;                                                   // first layer: fp32 image in, bf16 out
-  }
-  p.x = (const float*)x; p.wp = (const float*)w; p.y = (float*)z; p.stat = nullptr;
+  if (tiled_bn(d->Cin, d->Cout) > 0) UNETK_REQUIRE(d->x_stride % 4 == 0);
+  ConvParams p = desc_params(d, false, x, w, z, ws, ws_bytes);
   p.asc = scale; p.ash = shift; p.pool = pooled; p.pool_s = pooled_stride;
-  if (ws && unetk_aligned16(ws) && ws_bytes > 0) { p.sk_slab = (float*)ws; p.sk_slab_bytes = ws_bytes; }   // stream-K scratch
-  p.dil = d->dilation;
-  p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout; p.xs = d->x_stride; p.ys = d->y_stride;
-  p.xa = unetk_dense_addr(p.H, p.W, p.xs);
-  p.ya = unetk_dense_addr(p.H, p.W, p.ys);
   return unetk_conv_run(p, (hipStream_t)stream);
 }
 
@@ -941,20 +943,9 @@ extern "C" int unetk_conv3x3_dgrad_ws(const unetk_conv_desc* d, const void* dy, 
                                       size_t ws_bytes, void* stream) {
   UNETK_REQUIRE(conv_desc_ok(d) && dy && w && dx);
   UNETK_REQUIRE(unetk_aligned16(dy) && unetk_aligned16(w) && unetk_aligned16(dx));
-  // dgrad = conv3x3 with Cin <-> Cout on the packed, tap-flipped filters
-  if (pick_cfg(d->Cout, d->Cin).id < 0) return UNETK_E_UNSUPPORTED;
+  if (tiled_bn(d->Cout, d->Cin) == 0) return UNETK_E_UNSUPPORTED;      // no input gradient on the first-layer kernels
   UNETK_REQUIRE(d->x_stride % 4 == 0 && d->y_stride % 4 == 0);
-  if (d->precision != UNETK_FP32 && !unetk_conv_bf16_ok(d->Cout, d->Cin)) return UNETK_E_UNSUPPORTED;
-  if (d->precision == UNETK_BF16S && d->dilation > 1) return UNETK_E_UNSUPPORTED;
-  ConvParams p{};
-  p.bf16 = d->precision;                    // UNETK_FP32 / UNETK_BF16 / UNETK_BF16S (dy and dx are bf16)
-  p.x = (const float*)dy; p.wp = (const float*)w; p.y = (float*)dx; p.stat = nullptr;
-  p.dil = d->dilation;
-  p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = d->Cout; p.Cout = d->Cin; p.xs = d->y_stride; p.ys = d->x_stride;
-  p.xa = unetk_dense_addr(p.H, p.W, p.xs);
-  p.ya = unetk_dense_addr(p.H, p.W, p.ys);
-  if (ws && unetk_aligned16(ws) && ws_bytes > 0) { p.sk_slab = (float*)ws; p.sk_slab_bytes = ws_bytes; }
-  return unetk_conv_run(p, (hipStream_t)stream);
+  return unetk_conv_run(desc_params(d, true, dy, w, dx, ws, ws_bytes), (hipStream_t)stream);
 }
 
 // ---- input gradient fused with the producing unit's norm-backward reduction (ConvParams::ny)
@@ -964,14 +955,11 @@ extern "C" int unetk_conv3x3_dgrad_nbr_rows(const unetk_conv_desc* d) {
   // measured: the extra epilogue work (16 x TN strided loads of prod_y per fragment) costs ~0.03 ms on the deep layers and
   // 0.38 ms on the 64-channel 256^2 level, whose K loop is only 36 steps -- more than the separate reduction pass there
   if (K < 128 || Nc < 128 || Nc % 128 != 0) return 0;
-  if (d->precision == UNETK_BF16S) {
-    if (!unetk_conv_bf16_ok(K, Nc) || K % 64 != 0 || Nc % 64 != 0) return 0;
-    return unetk_conv_stat_rows_bf16s(d->N, d->H, d->W, K, Nc, d->y_stride, d->x_stride);
-  }
-  if (d->precision != UNETK_FP32) return 0;
-  if (pick_cfg(K, Nc).id < 0 || unetk_conv_lin_ok(d->N, d->H, d->W, K, Nc, 1)) return 0;   // tiled fp32 kernel only
-  const int th = tile_rows(d->N, d->H, d->W, K, Nc, 1, true);
-  return d->N * ((d->H + th - 1) / th) * ((d->W + TW - 1) / TW);
+  if (d->precision == UNETK_BF16 || (d->precision == UNETK_BF16S && K % 64 != 0)) return 0;
+  ConvShape s = desc_shape(d, true);
+  s.nbr = 1; s.stat = 1;      // (nys stays 0: the row count does not depend on the producer's stride, unetk_conv_plan_bf16)
+  const ConvPlan pl = unetk_conv_plan(s);
+  return pl.rc == UNETK_OK ? pl.stat_rows : 0;
 }
 
 extern "C" int unetk_conv3x3_dgrad_nbr(const unetk_conv_desc* d, const void* dy, const void* w, void* dx,
@@ -982,13 +970,8 @@ extern "C" int unetk_conv3x3_dgrad_nbr(const unetk_conv_desc* d, const void* dy,
   UNETK_REQUIRE(unetk_aligned16(dy) && unetk_aligned16(w) && unetk_aligned16(dx));
   UNETK_REQUIRE(d->x_stride % 4 == 0 && d->y_stride % 4 == 0 && prod_y_stride >= d->Cin);
   if (unetk_conv3x3_dgrad_nbr_rows(d) <= 0) return UNETK_E_UNSUPPORTED;
-  ConvParams p{};
-  p.bf16 = d->precision;
-  p.x = (const float*)dy; p.wp = (const float*)w; p.y = (float*)dx; p.stat = partials;
-  p.dil = d->dilation;
-  p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = d->Cout; p.Cout = d->Cin; p.xs = d->y_stride; p.ys = d->x_stride;
-  p.xa = unetk_dense_addr(p.H, p.W, p.xs);
-  p.ya = unetk_dense_addr(p.H, p.W, p.ys);
+  ConvParams p = desc_params(d, true, dy, w, dx, nullptr, 0);
+  p.stat = partials;
   p.ny = prod_y; p.nys = prod_y_stride;
   p.nsc = scale; p.nsh = shift; p.nmu = mean; p.nrs = rstd;
   p.nsst = per_sample ? d->Cin : 0;

@@ -410,73 +410,66 @@ int launch_bf16(const ConvParams& p, int n_mtiles, hipStream_t st) {
 
 bool unetk_conv_bf16_ok(int Cin, int Cout) { return Cin % CKB == 0 && Cout % 32 == 0; }
 
-int unetk_conv_stat_rows_bf16(int N, int H, int W, int Cin, int Cout) {
-  const BfCfg cfg = pick_bf16(H, Cin, Cout, N, W);
-  if (cfg.id < 0) return UNETK_E_UNSUPPORTED;
-  return N * ((H + cfg.th - 1) / cfg.th) * ((W + TW - 1) / TW);
-}
-
 // UNETK_BF16S: the round-3 kernel (conv_igemm_bf16s.hip) where its tile grid fills the chip, else the kernels of this file
-int unetk_conv_stat_rows_bf16s(int N, int H, int W, int Cin, int Cout, int xs, int ys) {
-  if (unetk_conv_bf16s_v3_ok(N, H, W, Cin, Cout, xs, ys)) return unetk_conv_bf16s_v3_stat_rows(N, H, W);
-  return unetk_conv_stat_rows_bf16(N, H, W, Cin, Cout);
+void unetk_conv_plan_bf16(const ConvShape& s, ConvPlan& pl) {
+  const BfCfg cfg = pick_bf16(s.H, s.Cin, s.Cout, s.N, s.W);
+  pl.family = CONV_BF16;
+  pl.rc = UNETK_E_UNSUPPORTED;
+  if (cfg.id < 0) return;
+  const bool bs = s.bf16 == UNETK_BF16S;
+  int v3_rows = 0;
+  if (bs && unetk_conv_plan_bf16s_v3(s, pl)) {
+    // the persistent kernel's reduction epilogue exists for its 128-wide tiles and 16-byte rows of the producer's output;
+    // where it cannot run, the tall tile of this file emits the same statistic rows (32-row tiles both)
+    if (!s.nbr || (s.Cout % 128 == 0 && s.nys % 8 == 0)) return;
+    v3_rows = pl.stat_rows;
+    pl.family = CONV_BF16;
+    pl.rc = UNETK_E_UNSUPPORTED;
+  }
+  pl.cfg = cfg.id; pl.th = cfg.th;
+  pl.tiles_h = (s.H + cfg.th - 1) / cfg.th;
+  pl.tiles_w = (s.W + TW - 1) / TW;
+  pl.stat_rows = s.N * pl.tiles_h * pl.tiles_w;
+  pl.n_ntiles = s.Cout / (cfg.id <= 1 ? 128 : cfg.id <= 3 ? 64 : 32);
+  if (bs) {   // bf16 storage: 16-B halo pieces of 8 channels, 4-B output words of 2 channels
+    if (cfg.id == 4 || s.accumulate || s.kd > 1) return;     // Cout % 64 != 0 / 3-D depth taps: not in this mode
+    if (s.affine) return;                                    // the inference epilogue lives in the persistent kernel only
+    if (s.xs % 8 != 0 || s.ys % 2 != 0) { pl.rc = UNETK_E_BADARG; return; }
+    if (s.nbr && (cfg.id > 1 || (v3_rows && v3_rows != pl.stat_rows))) return;
+  } else {
+    if (s.nbr || s.affine) return;
+    if (s.xs % 4 != 0) { pl.rc = UNETK_E_BADARG; return; }
+    if (s.kd > 1 && (s.accumulate || s.spg < 1)) return;     // a stride-1 3-D conv: all depth taps in one launch (FT)
+  }
+  pl.rc = UNETK_OK;
 }
 
-int unetk_conv_run_bf16(ConvParams p, hipStream_t st) {
-  const BfCfg cfg = pick_bf16(p.H, p.Cin, p.Cout, p.N, p.W);
-  if (cfg.id < 0) return UNETK_E_UNSUPPORTED;
-  if (p.bf16 == UNETK_BF16S) {   // bf16 storage: 16-B halo pieces of 8 channels, 4-B output words of 2 channels
-    if (cfg.id == 4 || p.accumulate || p.kd > 1) return UNETK_E_UNSUPPORTED;     // Cout % 64 != 0 / 3-D depth taps: not in this mode
-    if (unetk_conv_bf16s_v3_ok(p.N, p.H, p.W, p.Cin, p.Cout, p.xs, p.ys) && (p.ny == nullptr || (p.Cout % 128 == 0 && p.nys % 8 == 0)))
-      return unetk_conv_bf16s_v3_run(p, st);
-    if (p.asc != nullptr) return UNETK_E_UNSUPPORTED;      // the inference epilogue lives in the persistent kernel only
-    if (p.xs % 8 != 0 || p.ys % 2 != 0) return UNETK_E_BADARG;
-    p.tiles_h = (p.H + cfg.th - 1) / cfg.th;
-    p.tiles_w = (p.W + TW - 1) / TW;
-    const int n_mt = p.N * p.tiles_h * p.tiles_w;
-    p.stat_rows = n_mt;
-    switch (cfg.id) {
-      case 0:
-        p.n_ntiles = p.Cout / 128;
-        if (p.ny != nullptr) return launch_bf16<4, 2, 4, 2, true, true>(p, n_mt, st);
-        return launch_bf16<4, 2, 4, 2, true>(p, n_mt, st);
-      case 1:
-        p.n_ntiles = p.Cout / 128;
-        if (p.ny != nullptr) return launch_bf16<2, 2, 2, 2, true, true>(p, n_mt, st);
-        return launch_bf16<2, 2, 2, 2, true>(p, n_mt, st);
-      case 2:
-        if (p.ny != nullptr) return UNETK_E_UNSUPPORTED;
-        p.n_ntiles = p.Cout / 64;
-        return launch_bf16<4, 1, 2, 2, true>(p, n_mt, st);
-      default:
-        if (p.ny != nullptr) return UNETK_E_UNSUPPORTED;
-        p.n_ntiles = p.Cout / 64;
-        return launch_bf16<4, 1, 1, 2, true>(p, n_mt, st);
+int unetk_conv_launch_bf16(const ConvPlan& pl, ConvParams p, hipStream_t st) {
+  const int n_mt = pl.stat_rows;
+  if (p.bf16 == UNETK_BF16S) {
+    switch (pl.cfg) {
+      case 0: return p.ny != nullptr ? launch_bf16<4, 2, 4, 2, true, true>(p, n_mt, st) : launch_bf16<4, 2, 4, 2, true>(p, n_mt, st);
+      case 1: return p.ny != nullptr ? launch_bf16<2, 2, 2, 2, true, true>(p, n_mt, st) : launch_bf16<2, 2, 2, 2, true>(p, n_mt, st);
+      case 2: return launch_bf16<4, 1, 2, 2, true>(p, n_mt, st);
+      default: return launch_bf16<4, 1, 1, 2, true>(p, n_mt, st);
     }
   }
-  if (p.ny != nullptr) return UNETK_E_UNSUPPORTED;
-  if (p.xs % 4 != 0) return UNETK_E_BADARG;
-  p.tiles_h = (p.H + cfg.th - 1) / cfg.th;
-  p.tiles_w = (p.W + TW - 1) / TW;
-  const int n_mtiles = p.N * p.tiles_h * p.tiles_w;
-  p.stat_rows = n_mtiles;
-  if (p.kd > 1) {        // a stride-1 3-D conv: all depth taps in one launch (FT)
-    if (p.accumulate || p.asc != nullptr || p.spg < 1 || p.din < 1 || p.dsd < 1 || (p.dstep != 1 && p.dstep != -1))
-      return UNETK_E_UNSUPPORTED;
-    switch (cfg.id) {
-      case 0: p.n_ntiles = p.Cout / 128; return launch_bf16<4, 2, 4, 2, false, false, true>(p, n_mtiles, st);
-      case 1: p.n_ntiles = p.Cout / 128; return launch_bf16<2, 2, 2, 2, false, false, true>(p, n_mtiles, st);
-      case 2: p.n_ntiles = p.Cout / 64; return launch_bf16<4, 1, 2, 2, false, false, true>(p, n_mtiles, st);
-      case 3: p.n_ntiles = p.Cout / 64; return launch_bf16<4, 1, 1, 2, false, false, true>(p, n_mtiles, st);
-      default: p.n_ntiles = p.Cout / 32; return launch_bf16<4, 1, 2, 1, false, false, true>(p, n_mtiles, st);
+  if (p.kd > 1) {
+    if (p.din < 1 || p.dsd < 1 || (p.dstep != 1 && p.dstep != -1)) return UNETK_E_UNSUPPORTED;
+    switch (pl.cfg) {
+      case 0: return launch_bf16<4, 2, 4, 2, false, false, true>(p, n_mt, st);
+      case 1: return launch_bf16<2, 2, 2, 2, false, false, true>(p, n_mt, st);
+      case 2: return launch_bf16<4, 1, 2, 2, false, false, true>(p, n_mt, st);
+      case 3: return launch_bf16<4, 1, 1, 2, false, false, true>(p, n_mt, st);
+      default: return launch_bf16<4, 1, 2, 1, false, false, true>(p, n_mt, st);
     }
   }
-  switch (cfg.id) {
-    case 0: p.n_ntiles = p.Cout / 128; return launch_bf16<4, 2, 4, 2>(p, n_mtiles, st);
-    case 1: p.n_ntiles = p.Cout / 128; return launch_bf16<2, 2, 2, 2>(p, n_mtiles, st);
-    case 2: p.n_ntiles = p.Cout / 64; return launch_bf16<4, 1, 2, 2>(p, n_mtiles, st);
-    case 3: p.n_ntiles = p.Cout / 64; return launch_bf16<4, 1, 1, 2>(p, n_mtiles, st);
-    default: p.n_ntiles = p.Cout / 32; return launch_bf16<4, 1, 2, 1>(p, n_mtiles, st);
+  switch (pl.cfg) {
+    case 0: return launch_bf16<4, 2, 4, 2>(p, n_mt, st);
+    case 1: return launch_bf16<2, 2, 2, 2>(p, n_mt, st);
+    case 2: return launch_bf16<4, 1, 2, 2>(p, n_mt, st);
+    case 3: return launch_bf16<4, 1, 1, 2>(p, n_mt, st);
+    default: return launch_bf16<4, 1, 2, 1>(p, n_mt, st);
   }
 }
 

@@ -557,7 +557,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bf16s_kernel(ConvParams p) {
 
 }  // namespace
 
-// ---- host side (called from conv_igemm_bf16.hip's dispatch)
+// ---- host side (its plan part is asked by conv_igemm_bf16.hip's)
 // UNETK_V3_FLAGS (measurement only; read once): bit 0 = no staggered requests, bit 1 = do not use this kernel at all.
 // A build with -DUNETK_V3_PROBE (tools/probe_v3.sh; never the shipped library) adds switches that give WRONG RESULTS and
 // exist to time the parts of the loop: 4 = no staging requests in the main loop, 8 = every halo read hits tile 0 of image 0
@@ -572,17 +572,25 @@ static int v3_flags() {
   return f;
 }
 
-bool unetk_conv_bf16s_v3_ok(int N, int H, int W, int Cin, int Cout, int xs, int ys) {
+bool unetk_conv_plan_bf16s_v3(const ConvShape& s, ConvPlan& pl) {
   if (v3_flags() & 2) return false;
-  if (Cin % 32 != 0 || (Cout % 128 != 0 && Cout != 64)) return false;
-  if (xs % 8 != 0 || ys % 8 != 0) return false;              // 16-byte halo units / output stores
-  if (H < 24 || (int64_t)H * W * xs * 2 >= (int64_t(1) << 31)) return false;      // 32-bit byte offsets inside an image
-  const int bn = Cout % 128 == 0 ? 128 : 64;
-  const int64_t tiles = (int64_t)N * ((H + TH - 1) / TH) * ((W + TW - 1) / TW) * (Cout / bn);
-  return tiles >= 200 && tiles < (1 << 30);
+  if (s.Cin % 32 != 0 || (s.Cout % 128 != 0 && s.Cout != 64)) return false;
+  if (s.xs % 8 != 0 || s.ys % 8 != 0) return false;              // 16-byte halo units / output stores
+  if (s.H < 24 || (int64_t)s.H * s.W * s.xs * 2 >= (int64_t(1) << 31)) return false;      // 32-bit byte offsets inside an image
+  const int bn = s.Cout % 128 == 0 ? 128 : 64;
+  const int64_t tiles = (int64_t)s.N * ((s.H + TH - 1) / TH) * ((s.W + TW - 1) / TW) * (s.Cout / bn);
+  if (tiles < 200 || tiles >= (1 << 30)) return false;
+  pl.family = CONV_BF16S_V3;
+  pl.cfg = bn / 16;
+  pl.th = TH;
+  pl.tiles_h = (s.H + TH - 1) / TH;
+  pl.tiles_w = (s.W + TW - 1) / TW;
+  pl.n_ntiles = s.Cout / bn;
+  pl.stat_rows = s.N * pl.tiles_h * pl.tiles_w;
+  const bool refused = s.accumulate || s.kd > 1 || (s.nbr && s.affine) || (s.affine && s.stat);
+  pl.rc = refused ? UNETK_E_UNSUPPORTED : UNETK_OK;
+  return true;
 }
-
-int unetk_conv_bf16s_v3_stat_rows(int N, int H, int W) { return N * ((H + TH - 1) / TH) * ((W + TW - 1) / TW); }
 
 template <int NT8, bool NBR, int AFF = 0>
 static int launch_v3(const ConvParams& p, hipStream_t st) {
@@ -606,27 +614,17 @@ static int launch_v3(const ConvParams& p, hipStream_t st) {
   return UNETK_OK;
 }
 
-int unetk_conv_bf16s_v3_run(ConvParams p, hipStream_t st) {
-  if (!unetk_conv_bf16s_v3_ok(p.N, p.H, p.W, p.Cin, p.Cout, p.xs, p.ys)) return UNETK_E_UNSUPPORTED;
-  if (p.accumulate) return UNETK_E_UNSUPPORTED;
-  const int bn = p.Cout % 128 == 0 ? 128 : 64;
-  p.tiles_h = (p.H + TH - 1) / TH;
-  p.tiles_w = (p.W + TW - 1) / TW;
-  p.n_ntiles = p.Cout / bn;
-  p.stat_rows = p.N * p.tiles_h * p.tiles_w;
-  p.ptiles = p.stat_rows * p.n_ntiles;
+int unetk_conv_launch_bf16s_v3(const ConvPlan& pl, ConvParams p, hipStream_t st) {
+  p.ptiles = pl.stat_rows * pl.n_ntiles;
   p.dbg = v3_flags();
-  if (p.ny != nullptr) {
-    if (bn != 128 || p.nys % 8 != 0 || p.asc != nullptr) return UNETK_E_UNSUPPORTED;
-    return launch_v3<8, true>(p, st);
-  }
+  const bool wide = pl.cfg == 8;
+  if (p.ny != nullptr) return launch_v3<8, true>(p, st);
   if (p.asc != nullptr) {         // inference epilogue: (scale, shift) + ReLU [+ 2 x 2 max-pool]
-    if (p.stat != nullptr) return UNETK_E_UNSUPPORTED;
     if (p.pool != nullptr) {
-      if (((p.H | p.W) & 1) || p.pool_s % (bn == 128 ? 8 : 4) != 0) return UNETK_E_UNSUPPORTED;
-      return bn == 128 ? launch_v3<8, false, 2>(p, st) : launch_v3<4, false, 2>(p, st);
+      if (p.pool_s % (wide ? 8 : 4) != 0) return UNETK_E_UNSUPPORTED;
+      return wide ? launch_v3<8, false, 2>(p, st) : launch_v3<4, false, 2>(p, st);
     }
-    return bn == 128 ? launch_v3<8, false, 1>(p, st) : launch_v3<4, false, 1>(p, st);
+    return wide ? launch_v3<8, false, 1>(p, st) : launch_v3<4, false, 1>(p, st);
   }
-  return bn == 128 ? launch_v3<8, false>(p, st) : launch_v3<4, false>(p, st);
+  return wide ? launch_v3<8, false>(p, st) : launch_v3<4, false>(p, st);
 }

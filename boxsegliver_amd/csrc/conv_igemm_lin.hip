@@ -714,7 +714,7 @@ static int lin_2d() {
   return v;
 }
 
-bool unetk_conv_lin_ok(int N, int H, int W, int Cin, int Cout, int spg) {
+static bool lin_ok(int N, int H, int W, int Cin, int Cout, int spg) {
   const int wmax = (lin_2d() & 1) && spg == 1 ? 33 : 32;
   if (Cin % CK != 0 || Cout % 64 != 0 || W >= wmax || spg < 1 || N % spg != 0) return false;
   const int64_t gpix = (int64_t)spg * H * W;
@@ -744,7 +744,7 @@ static int lin_tune(int N, int H, int W, int spg) {
     v = e ? atoi(e) : 7;
   }
   if (spg > 1) return v;
-  // 2-D planes: only those the tiled kernel would FILL (they are here because its grid starves the chip, unetk_conv_lin_ok) --
+  // 2-D planes: only those the tiled kernel would FILL (they are here because its grid starves the chip, lin_ok) --
   // with at least 16 blocks of 128 pixels (8 slices of 16 x 16), where the change was measured.  The badly filled small planes
   // (8 x 8, 4 x 4 ...) and the two-slice batches of the end-to-end tests keep the round-2 schedule: same kernel-level error
   // either way (tools/dbg/lin2d_check.py: 0.5-2e-6 of the output's range against float64), but another fp32 summation order
@@ -764,11 +764,6 @@ static int lin_bm(int N, int H, int W, int Cout, int spg) {
   // is what the smaller block costs in filter-panel reuse)
   auto eff = [](int64_t b) { return (double)b / (double)(((b + 255) / 256) * 256); };
   return eff(b64) * 0.95 > eff(b128) ? 64 : LIN_BM;
-}
-
-int unetk_conv_stat_rows_lin(int N, int H, int W, int spg, int Cout) {
-  const int bm = Cout > 0 ? lin_bm(N, H, W, Cout, spg) : LIN_BM;
-  return (N / spg) * (int)(((int64_t)spg * H * W + bm - 1) / bm);
 }
 
 // Padded rows a block of bm linear pixels may touch.  General case: ceil(bm / W) + 1 pixel rows (a block may start mid-row),
@@ -818,7 +813,7 @@ int unetk_conv_run_lin_gen(ConvParams p, hipStream_t st) {
   }
   if (p.Cout % 64 != 0 || p.kd > 1) return UNETK_E_UNSUPPORTED;   // fused depth taps exist in the four-class variant only
   if (lin_rows_bound(p.H, p.W) * (p.W + 2) > LIN_MAXPIX) return UNETK_E_UNSUPPORTED;
-  const int n_mtiles = unetk_conv_stat_rows_lin(p.N, p.H, p.W, p.spg, 0);
+  const int n_mtiles = (p.N / p.spg) * (int)(((int64_t)p.spg * p.H * p.W + LIN_BM - 1) / LIN_BM);
   p.stat_rows = n_mtiles;
   p.lin_pix = lin_rows_bound(p.H, p.W) * (p.W + 2);
   if (p.Cout % 128 == 0) {
@@ -829,50 +824,58 @@ int unetk_conv_run_lin_gen(ConvParams p, hipStream_t st) {
   return launch_lin<4, 1, 1, 2, true>(p, 4 * n_mtiles, st);
 }
 
-namespace {
-
 // Stream-K plan: used when whole tiles quantise badly over the CUs (or do not fill them) and the K loop is long enough to
-// cut.  G = 2 blocks per CU (fewer when the layer has fewer than 4 chunks per block).
-struct SkPlan {
-  bool on;
-  int G, whole, tiles, nc, maxp, bm, bn;     // G = blocks sharing the remainder tiles
-  size_t bytes;
-};
-
-SkPlan sk_plan(int N, int H, int W, int Cin, int Cout, int spg, int kd) {
-  SkPlan s{};
-  const int bm = lin_bm(N, H, W, Cout, spg);
-  const int bn = (bm == 64 || Cout % 128 == 0) ? 128 : 64;
-  const int n_mt = (N / spg) * (int)(((int64_t)spg * H * W + bm - 1) / bm);
-  s.bm = bm; s.bn = bn;
-  s.tiles = n_mt * (Cout / bn);
-  s.nc = (kd > 1 ? kd : 1) * (Cin / CK);
-  const double eff = (double)s.tiles / (double)(((s.tiles + 255) / 256) * 256);
+// cut.  G = 2 blocks per CU (fewer when the layer has fewer than 4 chunks per block).  Fills pl.sk_* and pl.ws_bytes (0 = this
+// shape runs one block per tile); K = live channels of the contraction axis, kd = depth taps or tap groups.
+static void sk_plan(const ConvShape& s, int K, int kd, int bn, ConvPlan& pl) {
+  const int tune = lin_tune(s.N, s.H, s.W, s.spg);
+  const int tiles = pl.stat_rows * (s.Cout / bn), nc = (kd > 1 ? kd : 1) * (K / CK);
+  const double eff = (double)tiles / (double)(((tiles + 255) / 256) * 256);
   // (up to one tile per CU the K range is always split: a lone 4-wave block per CU runs at ~100 TFLOP/s, two half-K blocks
   // at more)
-  if (s.tiles >= 2048 || (s.tiles > 256 && eff >= 0.92)) return s;
-  s.whole = s.tiles <= 256 ? 0 : s.tiles / 256 * 256;    // full rounds run one whole tile per block
-  if ((lin_tune(N, H, W, spg) & 2) && s.tiles <= 1024) s.whole = 0;
-  const int rem = s.tiles - s.whole;
+  if (tiles >= 2048 || (tiles > 256 && eff >= 0.92)) return;
+  int whole = tiles <= 256 ? 0 : tiles / 256 * 256;    // full rounds run one whole tile per block
+  if ((tune & 2) && tiles <= 1024) whole = 0;
+  const int rem = tiles - whole;
   // measured (UNet3D, one patch): a remainder of 176 tiles with K >= 48 chunks gains 10-12 %, 96 tiles or K = 24 chunks
   // do not pay for the slab round trip and the fix-up launch
-  if (s.whole > 0 && (rem < 128 || s.nc < 48)) return s;
-  if (s.whole == 0 && s.tiles > 256 && s.nc < 48 && !(lin_tune(N, H, W, spg) & 4)) return s;
-  const int64_t tot = (int64_t)rem * s.nc;
+  if (whole > 0 && (rem < 128 || nc < 48)) return;
+  if (whole == 0 && tiles > 256 && nc < 48 && !(tune & 4)) return;
+  const int64_t tot = (int64_t)rem * nc;
   int G = 256;
-  if (s.whole == 0 && tot >= 512 * 4) G = 512;           // nothing else resident: two blocks per CU
+  if (whole == 0 && tot >= 512 * 4) G = 512;           // nothing else resident: two blocks per CU
   while (G > 32 && tot < (int64_t)G * 4) G >>= 1;
-  if (tot < (int64_t)G * 4) return s;
-  s.G = G;
+  if (tot < (int64_t)G * 4) return;
   const int64_t minlen = tot / G;
-  s.maxp = (int)((s.nc + minlen - 1) / minlen) + 1;
-  s.bytes = (size_t)rem * s.maxp * bm * bn * sizeof(float);
-  s.on = s.bytes <= ((size_t)1 << 30);
-  return s;
+  const int maxp = (int)((nc + minlen - 1) / minlen) + 1;
+  const size_t bytes = (size_t)rem * maxp * pl.bm * bn * sizeof(float);
+  if (bytes > ((size_t)1 << 30)) return;
+  pl.sk_G = G; pl.sk_whole = whole; pl.sk_tiles = tiles; pl.sk_nc = nc; pl.sk_maxp = maxp;
+  pl.ws_bytes = bytes;
 }
 
+bool unetk_conv_plan_lin(const ConvShape& s, ConvPlan& pl) {
+  if (!lin_ok(s.N, s.H, s.W, s.Cin, s.Cout, s.spg)) return false;
+  pl.bm = lin_bm(s.N, s.H, s.W, s.Cout, s.spg);
+  const int bn = (pl.bm == 64 || s.Cout % 128 == 0) ? 128 : 64;
+  pl.stat_rows = (s.N / s.spg) * (int)(((int64_t)s.spg * s.H * s.W + pl.bm - 1) / pl.bm);
+  pl.tiles_h = pl.tiles_w = 0;
+  pl.n_ntiles = s.Cout / bn;
+  pl.lin_pix = lin_rows_bound(s.H, s.W, pl.bm) * (s.W + 2);
+  sk_plan(s, s.klive ? s.klive : s.Cin, s.ng > 0 ? s.ng : s.kd, bn, pl);
+  pl.family = (pl.ws_bytes > 0 && s.ws_bytes >= pl.ws_bytes && !s.accumulate && s.ys % 4 == 0) ? CONV_LIN_SK : CONV_LIN;
+  // this kernel has the inference epilogue but no pool, and neither the fused reduction nor a bf16 output; grouped taps (a
+  // strided conv over its space-to-depth input, conv3d.hip) come without the other K-sequence variants
+  if (s.nbr || s.ybf16 || (s.affine && (s.pool || s.accumulate || s.kd > 1))) pl.rc = UNETK_E_UNSUPPORTED;
+  else if (s.xs % 4 != 0) pl.rc = UNETK_E_BADARG;
+  else if (s.ng > 0 && (s.ng > 12 || s.accumulate || s.kd > 1 || s.affine)) pl.rc = UNETK_E_UNSUPPORTED;
+  return true;
+}
+
+namespace {
+
 template <int WM, int WN, int TM, int TN, bool GRP = false, bool KHALF = false>
-int launch_lin_sk(const ConvParams& p, const SkPlan& sk, hipStream_t st) {
+int launch_lin_sk(const ConvParams& p, const ConvPlan& pl, hipStream_t st) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   constexpr size_t lds_max = (size_t)(2 * LIN_MAXPIX * PS + 2 * CK * BN) * sizeof(float);
   const size_t lds = (size_t)(2 * p.lin_pix * PS + 2 * CK * BN) * sizeof(float);
@@ -883,77 +886,43 @@ int launch_lin_sk(const ConvParams& p, const SkPlan& sk, hipStream_t st) {
     if (e != hipSuccess) return (int)e;
     attr_done = true;
   }
-  UNETK_LAUNCH(kern, dim3(sk.whole + sk.G), dim3(WM * WN * 64), lds, st, p);
+  UNETK_LAUNCH(kern, dim3(pl.sk_whole + pl.sk_G), dim3(WM * WN * 64), lds, st, p);
   UNETK_LAUNCH_CHECK();
-  UNETK_LAUNCH((lin_sk_fixup_kernel<BM, BN>), dim3(sk.tiles - sk.whole), dim3(256), 0, st, p, sk.G);
+  UNETK_LAUNCH((lin_sk_fixup_kernel<BM, BN>), dim3(pl.sk_tiles - pl.sk_whole), dim3(256), 0, st, p, pl.sk_G);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }
 
 }  // namespace
 
-size_t unetk_conv_lin_sk_bytes(int N, int H, int W, int Cin, int Cout, int spg, int kd) {
-  if (!unetk_conv_lin_ok(N, H, W, Cin, Cout, spg)) return 0;
-  const SkPlan sk = sk_plan(N, H, W, Cin, Cout, spg, kd);
-  return sk.on ? sk.bytes : 0;
-}
-
-int unetk_conv_run_lin(ConvParams p, hipStream_t st) {
-  const int n_mtiles = unetk_conv_stat_rows_lin(p.N, p.H, p.W, p.spg, p.Cout);
-  const int bm = lin_bm(p.N, p.H, p.W, p.Cout, p.spg);
-  p.stat_rows = n_mtiles;
-  p.tiles_h = p.tiles_w = 0;
-  p.lin_pix = lin_rows_bound(p.H, p.W, bm) * (p.W + 2);
-  if (p.xs % 4 != 0) return UNETK_E_BADARG;
-  if (p.ng > 0) {      // grouped taps (a strided conv over its space-to-depth input, conv3d.hip): K sequence = ng x Cin / 16 chunks
-    if (p.ng > 12 || p.accumulate || p.kd > 1 || p.asc != nullptr) return UNETK_E_UNSUPPORTED;
-    for (int g = 0; g < p.ng; ++g)
-      if (p.g_ntaps[g] < 1 || p.g_ntaps[g] > 4) return UNETK_E_BADARG;
-    if (p.sk_slab != nullptr && p.ys % 4 == 0) {
-      const SkPlan sk = sk_plan(p.N, p.H, p.W, p.nlive ? p.nlive * CK : p.Cin, p.Cout, p.spg, p.ng);
-      if (sk.on && p.sk_slab_bytes >= sk.bytes && unetk_aligned16(p.sk_slab)) {
-        p.sk_tiles = sk.tiles; p.sk_nc = sk.nc; p.sk_maxp = sk.maxp; p.sk_whole = sk.whole;
-        p.n_ntiles = p.Cout / sk.bn;
-        if (bm == 64) return launch_lin_sk<2, 2, 1, 2, true>(p, sk, st);
-        if (p.Cout % 128 == 0) return launch_lin_sk<2, 2, 2, 2, true>(p, sk, st);
-        return launch_lin_sk<4, 1, 1, 2, true>(p, sk, st);
-      }
+// tile shape: 64-pixel blocks x 128 couts <2,2,1,2>, 128 x 128 <2,2,2,2>, 128 x 64 <4,1,1,2>
+int unetk_conv_launch_lin(const ConvPlan& pl, ConvParams p, hipStream_t st) {
+  const int n_mtiles = pl.stat_rows;
+  const bool wide = p.Cout % 128 == 0, khalf = p.khalf != 0 && !p.accumulate && p.ng == 0;
+  for (int g = 0; g < p.ng; ++g)
+    if (p.g_ntaps[g] < 1 || p.g_ntaps[g] > 4) return UNETK_E_BADARG;
+  if (pl.family == CONV_LIN_SK) {
+    p.sk_tiles = pl.sk_tiles; p.sk_nc = pl.sk_nc; p.sk_maxp = pl.sk_maxp; p.sk_whole = pl.sk_whole;
+    if (p.ng > 0) {
+      if (pl.bm == 64) return launch_lin_sk<2, 2, 1, 2, true>(p, pl, st);
+      if (wide) return launch_lin_sk<2, 2, 2, 2, true>(p, pl, st);
+      return launch_lin_sk<4, 1, 1, 2, true>(p, pl, st);
     }
-    p.sk_slab = nullptr;
-    if (bm == 64) {
-      p.n_ntiles = p.Cout / 128;
-      return launch_lin<2, 2, 1, 2, false, false, false, true>(p, n_mtiles, st);
-    }
-    if (p.Cout % 128 == 0) {
-      p.n_ntiles = p.Cout / 128;
-      return launch_lin<2, 2, 2, 2, false, false, false, true>(p, n_mtiles, st);
-    }
-    p.n_ntiles = p.Cout / 64;
-    return launch_lin<4, 1, 1, 2, false, false, false, true>(p, n_mtiles, st);
-  }
-  if (p.sk_slab != nullptr && !p.accumulate && p.ys % 4 == 0) {
-    const SkPlan sk = sk_plan(p.N, p.H, p.W, p.nlive ? p.nlive * CK : p.Cin, p.Cout, p.spg, p.kd);
-    if (sk.on && p.sk_slab_bytes >= sk.bytes && unetk_aligned16(p.sk_slab)) {
-      p.sk_tiles = sk.tiles; p.sk_nc = sk.nc; p.sk_maxp = sk.maxp; p.sk_whole = sk.whole;
-      p.n_ntiles = p.Cout / sk.bn;
-      if (p.khalf != 0 && bm == 64) return launch_lin_sk<2, 2, 1, 2, false, true>(p, sk, st);
-      if (p.khalf != 0 && p.Cout % 128 == 0) return launch_lin_sk<2, 2, 2, 2, false, true>(p, sk, st);
-      if (bm == 64) return launch_lin_sk<2, 2, 1, 2>(p, sk, st);
-      if (p.Cout % 128 == 0) return launch_lin_sk<2, 2, 2, 2>(p, sk, st);
-      return launch_lin_sk<4, 1, 1, 2>(p, sk, st);
-    }
+    if (khalf && pl.bm == 64) return launch_lin_sk<2, 2, 1, 2, false, true>(p, pl, st);
+    if (khalf && wide) return launch_lin_sk<2, 2, 2, 2, false, true>(p, pl, st);
+    if (pl.bm == 64) return launch_lin_sk<2, 2, 1, 2>(p, pl, st);
+    if (wide) return launch_lin_sk<2, 2, 2, 2>(p, pl, st);
+    return launch_lin_sk<4, 1, 1, 2>(p, pl, st);
   }
   p.sk_slab = nullptr;
-  if (bm == 64) {
-    p.n_ntiles = p.Cout / 128;
-    if (p.khalf != 0 && !p.accumulate) return launch_lin<2, 2, 1, 2, false, false, false, false, true>(p, n_mtiles, st);
-    return launch_lin<2, 2, 1, 2>(p, n_mtiles, st);
+  if (p.ng > 0) {
+    if (pl.bm == 64) return launch_lin<2, 2, 1, 2, false, false, false, true>(p, n_mtiles, st);
+    if (wide) return launch_lin<2, 2, 2, 2, false, false, false, true>(p, n_mtiles, st);
+    return launch_lin<4, 1, 1, 2, false, false, false, true>(p, n_mtiles, st);
   }
-  if (p.Cout % 128 == 0) {
-    p.n_ntiles = p.Cout / 128;
-    if (p.khalf != 0 && !p.accumulate) return launch_lin<2, 2, 2, 2, false, false, false, false, true>(p, n_mtiles, st);
-    return launch_lin<2, 2, 2, 2>(p, n_mtiles, st);
-  }
-  p.n_ntiles = p.Cout / 64;
+  if (khalf && pl.bm == 64) return launch_lin<2, 2, 1, 2, false, false, false, false, true>(p, n_mtiles, st);
+  if (khalf && wide) return launch_lin<2, 2, 2, 2, false, false, false, false, true>(p, n_mtiles, st);
+  if (pl.bm == 64) return launch_lin<2, 2, 1, 2>(p, n_mtiles, st);
+  if (wide) return launch_lin<2, 2, 2, 2>(p, n_mtiles, st);
   return launch_lin<4, 1, 1, 2>(p, n_mtiles, st);
 }

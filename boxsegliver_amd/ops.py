@@ -151,10 +151,13 @@ class _Timed(object):
     trace records [i0, i1) -- its time is the sum of those kernels' own GPU durations (what rocprofv3 --kernel-trace reports),
     with no host gap inside whatever the stream's queue depth was."""
 
-    def __init__(self, tag, flops, shape=None, nbytes=0):
-        """flops: algorithmic FLOPs of a matrix kernel; nbytes: algorithmic HBM bytes (each operand once) of an HBM-bound pass."""
+    def __init__(self, tag, flops, shape=None, nbytes=0, by_kernel=False):
+        """flops: algorithmic FLOPs of a matrix kernel; nbytes: algorithmic HBM bytes (each operand once) of an HBM-bound pass,
+        or a function of the final tag.  by_kernel: the library picks the kernel (csrc/conv_igemm.hip, unetk_conv_plan), so the
+        tag becomes the name of the first launch inside the bracket, read from the trace when the bracket closes; `tag` is
+        kept only by a bracket that launched nothing."""
         self.on = PROFILE is not None
-        self.tag, self.flops, self.nbytes = (tag if not (PROFILE_SHAPES and shape) else "{} [{}]".format(tag, shape)), flops, nbytes
+        self.tag, self.flops, self.shape, self.nbytes, self.by_kernel = tag, flops, shape, nbytes, by_kernel
 
     def __enter__(self):
         if self.on:
@@ -163,8 +166,21 @@ class _Timed(object):
 
     def __exit__(self, *exc):
         if self.on and exc[0] is None:
-            PROFILE.append((self.tag, self.flops, self.i0, _abi.lib().unetk_prof_mark(), self.nbytes))
+            i1 = _abi.lib().unetk_prof_mark()
+            tag = _kernel_tag(self.i0) if self.by_kernel and i1 > self.i0 else self.tag
+            nbytes = self.nbytes(tag) if callable(self.nbytes) else self.nbytes
+            if PROFILE_SHAPES and self.shape:
+                tag = "{} [{}]".format(tag, self.shape)
+            PROFILE.append((tag, self.flops, self.i0, i1, nbytes))
         return False
+
+
+def _kernel_tag(i):
+    """Name of traced launch i as the tests and bench.py's tables write it: no "void ", no anonymous namespace, no argument
+    list, no blanks -- conv3x3_igemm_kernel<2,2,4,2,1,1,0>."""
+    buf = ctypes.create_string_buffer(512)
+    check(_abi.lib().unetk_prof_name(i, buf, 512), "prof_name")
+    return buf.value.decode().replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0].replace(" ", "")
 
 
 def profile_begin(reserve_launches=0):
@@ -204,12 +220,12 @@ class _NoTimer(object):
 _NO_TIMER = _NoTimer()
 
 
-def _timed(tag_fn, flops, fmt=None, args=(), nbytes_fn=None):
+def _timed(tag_fn, flops, fmt=None, args=(), nbytes_fn=None, by_kernel=False):
     """Timer of a matrix kernel; tag_fn / the shape string / nbytes_fn are evaluated only when bench.py asked for events."""
     if PROFILE is None:
         return _NO_TIMER
     tag = tag_fn() if callable(tag_fn) else tag_fn
-    return _Timed(tag, flops, fmt.format(*args) if fmt else None, nbytes_fn(tag) if nbytes_fn else 0)
+    return _Timed(tag, flops, fmt.format(*args) if fmt else None, nbytes_fn or 0, by_kernel)
 
 
 def _timed_hbm(tag, t, passes, extra=0):
@@ -218,38 +234,6 @@ def _timed_hbm(tag, t, passes, extra=0):
     if PROFILE is None:
         return _NO_TIMER
     return _Timed(tag, 0.0, None, t.numel() * t.element_size() * passes + extra)
-
-
-def _igemm_tag(cin, cout, bf16=False, h=0, n=1 << 20, w=1 << 10, nbr=False):
-    """Kernel name of a conv3x3 forward / input-gradient launch (mirrors the dispatch of conv_igemm*.hip; bench labels)."""
-    def cdiv(a, b):
-        return -(-a // b)
-
-    def big(bn):        # big_grid (conv_igemm.hip): 16 x 16 pixel tiles when they still give two blocks per CU
-        return h % 16 == 0 and not (nbr and cin < 256) and n * (h // 16) * cdiv(w, 16) * (cout // bn) >= 512
-    if bf16 and cin % 32 == 0 and cout % 32 == 0:
-        bs = ",true>" if int(bf16) == _abi.BF16S else ">"          # <..., BS = true>: bf16 storage
-        if int(bf16) == _abi.BF16S and h >= 24 and (cout % 128 == 0 or cout == 64):      # unetk_conv_bf16s_v3_ok (conv_igemm_bf16s.hip)
-            bn = 128 if cout % 128 == 0 else 64
-            if n * cdiv(h, 32) * cdiv(w, 16) * (cout // bn) >= 200:
-                return "conv3x3_bf16s_kernel<{}{}>".format(bn // 16, ",nbr" if nbr else "")
-        if cout % 128 == 0:
-            tall = h >= 24 and n * cdiv(h, 32) * cdiv(w, 16) * (cout // 128) >= 200     # pick_bf16 (conv_igemm_bf16.hip)
-            return ("conv3x3_igemm_bf16_kernel<4,2,4,2" if tall else "conv3x3_igemm_bf16_kernel<2,2,2,2") + bs
-        if cout % 64 == 0:
-            return ("conv3x3_igemm_bf16_kernel<4,1,2,2" if h >= 12 else "conv3x3_igemm_bf16_kernel<4,1,1,2") + bs
-        return "conv3x3_igemm_bf16_kernel<4,1,2,1>"
-    if cin % 16 == 0 and cout % 128 == 0:
-        if n * cdiv(h, 8) * cdiv(w, 16) * (cout // 128) < 384:      # under-filled grid: half-height tiles
-            return "conv3x3_igemm_kernel<2,2,1,2>"
-        return "conv3x3_igemm_kernel<2,2,4,2>" if big(128) else "conv3x3_igemm_kernel<2,2,2,2>"
-    if cin % 16 == 0 and cout % 64 == 0:
-        return "conv3x3_igemm_kernel<4,1,2,2>" if big(64) else "conv3x3_igemm_kernel<4,1,1,2>"
-    if cin % 16 == 0 and cout % 32 == 0:
-        return "conv3x3_igemm_kernel<4,1,2,1>"
-    if cout == 64 and 1 <= cin <= 5:            # first layers on the matrix pipe (conv_igemm.hip)
-        return "conv3x3_c3_mfma_kernel"
-    return "conv3x3_direct_kernel"
 
 
 def alias(t, offset_elems=0, size=None, stride=None):
@@ -533,8 +517,9 @@ def conv3x3_fwd(x, w, cout, want_stats=True, y=None, bf16=False, dilation=1):
     nws = _abi.lib().unetk_conv3x3_ws_bytes(ctypes.byref(d)) if prec == _abi.FP32 else 0     # stream-K scratch (small planes)
     ws = WORKSPACE.get(nws, x.device) if nws else None
     # the first layer's direct kernel is HBM-bound (writes 64 channels per pixel from 3): reported by bytes as well
-    with _timed(lambda: _igemm_tag(cin, cout, bf16, h, n, wd), 18.0 * n * h * wd * cin * cout, "fwd {}x{}x{} {}->{}", (n, h, wd, cin, cout),
-                lambda tag: (x.numel() * x.element_size() + y.numel() * y.element_size()) if tag in ("conv3x3_direct_kernel", "conv3x3_c3_mfma_kernel") else 0):
+    with _timed("conv3x3_fwd", 18.0 * n * h * wd * cin * cout, "fwd {}x{}x{} {}->{}", (n, h, wd, cin, cout),
+                lambda tag: (x.numel() * x.element_size() + y.numel() * y.element_size()) if tag.startswith(("conv3x3_direct_kernel", "conv3x3_c3_mfma_kernel")) else 0,
+                by_kernel=True):
         check(_abi.lib().unetk_conv3x3_fwd_ws(ctypes.byref(d), ptr(x), ptr(w), ptr(y), ptr(stats), ptr(ws), nws,
                                               stream_ptr()), "conv3x3_fwd")
     return y, stats, rows
@@ -577,8 +562,8 @@ def conv3x3_dgrad(dy, wp_dgrad, cin, x_stride=None, dx=None, bf16=False, dilatio
         rows = _abi.lib().unetk_conv3x3_dgrad_nbr_rows(ctypes.byref(d))
         if rows > 0 and py.dtype == dx.dtype and tuple(py.shape) == tuple(dx.shape) and py.is_contiguous():
             part = torch.empty((2, rows, cin), dtype=torch.float32, device=dy.device)
-            with _timed(lambda: _igemm_tag(cout, cin, bf16, h, n, wd, nbr=True), 18.0 * n * h * wd * cin * cout,
-                        "dgrad+nbr {}x{}x{} {}->{}", (n, h, wd, cout, cin)):
+            with _timed("conv3x3_dgrad_nbr", 18.0 * n * h * wd * cin * cout, "dgrad+nbr {}x{}x{} {}->{}", (n, h, wd, cout, cin),
+                        by_kernel=True):
                 check(_abi.lib().unetk_conv3x3_dgrad_nbr(ctypes.byref(d), ptr(dy), ptr(wp_dgrad), ptr(dx), ptr(py), cin,
                                                          ptr(paff[2]), ptr(paff[3]), ptr(paff[0]), ptr(paff[1]),
                                                          1 if per_sample else 0, ptr(part), stream_ptr()),
@@ -590,7 +575,7 @@ def conv3x3_dgrad(dy, wp_dgrad, cin, x_stride=None, dx=None, bf16=False, dilatio
             return dx
     nws = _abi.lib().unetk_conv3x3_ws_bytes(ctypes.byref(d)) if prec == _abi.FP32 else 0
     ws = WORKSPACE.get(nws, dy.device) if nws else None
-    with _timed(lambda: _igemm_tag(cout, cin, bf16, h, n, wd), 18.0 * n * h * wd * cin * cout, "dgrad {}x{}x{} {}->{}", (n, h, wd, cout, cin)):
+    with _timed("conv3x3_dgrad", 18.0 * n * h * wd * cin * cout, "dgrad {}x{}x{} {}->{}", (n, h, wd, cout, cin), by_kernel=True):
         check(_abi.lib().unetk_conv3x3_dgrad_ws(ctypes.byref(d), ptr(dy), ptr(wp_dgrad), ptr(dx), ptr(ws), nws, stream_ptr()),
               "conv3x3_dgrad")
     return dx
@@ -1733,10 +1718,10 @@ class Conv3x3NormRelu(_Op):
                     aff = norm_finalize(nd, None, 0, gamma, beta, spec.eps, spec.decay, False, moving_mean, moving_var, x.device)
                     sc, sh = aff[2], aff[3]
                 pooled = torch.empty((n_, h_ // 2, w_ // 2, cout), dtype=z.dtype, device=x.device) if with_pool else None
-                tag = _igemm_tag(cin, cout, bf16, h_, n_, w_) + ("+affine+relu+pool" if with_pool else "+affine+relu")
                 nws = _abi.lib().unetk_conv3x3_ws_bytes(ctypes.byref(fd))
                 ws = WORKSPACE.get(nws, x.device) if nws else None
-                with _timed(tag, 18.0 * n_ * h_ * w_ * cin * cout, "infer {}x{}x{} {}->{}", (n_, h_, w_, cin, cout)):
+                with _timed("conv3x3_fwd_affine", 18.0 * n_ * h_ * w_ * cin * cout, "infer {}x{}x{} {}->{}", (n_, h_, w_, cin, cout),
+                            by_kernel=True):
                     check(_abi.lib().unetk_conv3x3_fwd_affine(ctypes.byref(fd), ptr(x), ptr(wp_f), ptr(sc), ptr(sh), ptr(z),
                                                               ptr(pooled), cout, ptr(ws), nws, stream_ptr()), "conv3x3_fwd_affine")
                 ctx.pooled = pooled

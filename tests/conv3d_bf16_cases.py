@@ -1,8 +1,8 @@
 """Case table, inputs and float64 reference shared by tests/test_gpu_conv3d_bf16_paths.py (on the device) and
 tests/test_conv3d_bf16_paths_host.py (no GPU).  Nothing here touches the device unless a caller asks for dev="cuda".
 
-Every row was written out by hand from the predicates of csrc/conv_igemm_bf16.hip (pick_bf16, unetk_conv_stat_rows_bf16,
-unetk_conv_run_bf16), csrc/conv_wgrad.hip (wg_plan(..., bf16 = true, kd), unetk_wgrad_run, unetk_launch_slab_reduce) and
+Every row was written out by hand from the predicates of csrc/conv_igemm_bf16.hip (pick_bf16, unetk_conv_plan_bf16,
+unetk_conv_launch_bf16), csrc/conv_wgrad.hip (wg_plan(..., bf16 = true, kd), unetk_wgrad_run, unetk_launch_slab_reduce) and
 csrc/conv3d.hip (unetk_conv3d_{fwd,dgrad,wgrad}_bf16: the forward picks its tile from (N D, H, W, Cin, Cout), the input gradient
 from the same with Cin and Cout swapped).  pick_bf16 / wg_splits below restate those predicates; the host test holds every row
 against them, so that a row and the restatement can only be wrong together, and the device test holds every row against the

@@ -13,7 +13,7 @@ dw[2]), D = 1 and D = 2 with N > 1 (the neighbour plane in memory is another sam
 planes with partial tiles both ways and planes smaller than a tile.
 
 How the table was derived.  Every row names its forward kernel, statistic rows and tile geometry, its input-gradient kernel
-and its filter-gradient launches, written out by hand from pick_bf16, unetk_conv_stat_rows_bf16, wg_plan(..., bf16 = true, kd)
+and its filter-gradient launches, written out by hand from pick_bf16, unetk_conv_plan_bf16, wg_plan(..., bf16 = true, kd)
 and unetk_wgrad_run; tests/test_conv3d_bf16_paths_host.py holds the rows against a restatement of those predicates without a
 device.  Here the library's launch trace of every call must equal the row exactly, so a row that lands elsewhere after a
 dispatch change fails instead of quietly testing something else.
@@ -32,7 +32,7 @@ stay bit-equal, no sentinel may remain inside an output, inputs and packed filte
 workspace is refused.
 
 Limits.  ConvParams::accumulate and the inference epilogue (asc) are refused by the FT dispatch (UNETK_E_UNSUPPORTED in
-unetk_conv_run_bf16) and no 3-D entry point sets them; strided 3-D convs, kd = 3 with depth stride 2 and channel counts that
+unetk_conv_launch_bf16) and no 3-D entry point sets them; strided 3-D convs, kd = 3 with depth stride 2 and channel counts that
 are no multiple of 32 are refused by the entry points (test_refusals) and run exact fp32 in the net.  The live-channel masks of
 the descriptor are not used in this mode.  Small rows take the float64 reference on the CPU, rows marked big on the device.
 """

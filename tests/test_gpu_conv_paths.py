@@ -8,9 +8,9 @@ bounds that keep it in that regime (max(|x| conv |w|) * 8 < 2^24 and 8 * N * H *
 sparse input set (x, w in {-1, 0, 1}, density chosen so that max |y| <= 15) makes the statistic partials exact too.
 
 Each row of CASES names the kernels it exists to reach (forward, input gradient, filter gradient, and the same for UNETK_BF16 /
-UNETK_BF16S where unetk_conv_bf16_ok admits the row), written out by hand from the predicates of csrc/conv_igemm.hip (pick_cfg,
-small_grid, big_grid, unetk_conv_run), csrc/conv_igemm_lin.hip (unetk_conv_lin_ok, lin_bm, sk_plan), csrc/conv_wgrad.hip (wg_plan,
-unetk_wgrad_run), csrc/conv_igemm_bf16.hip (pick_bf16), csrc/conv_igemm_bf16s.hip (unetk_conv_bf16s_v3_ok) and
+UNETK_BF16S where unetk_conv_bf16_ok admits the row), written out by hand from the plan parts of csrc/conv_igemm.hip (tiled_bn,
+small_grid, big_grid, unetk_conv_plan), csrc/conv_igemm_lin.hip (lin_ok, lin_bm, sk_plan), csrc/conv_wgrad.hip (wg_plan,
+unetk_wgrad_run), csrc/conv_igemm_bf16.hip (pick_bf16), csrc/conv_igemm_bf16s.hip (unetk_conv_plan_bf16s_v3) and
 csrc/conv_wgrad_bf16s.hip (plan).  The library's launch trace must show exactly those kernels, so a row that lands elsewhere
 after a dispatch change fails instead of quietly testing something else.  `None` = the entry point refuses the shape (the row
 then skips that op; test_refusals covers the refusals themselves).
@@ -29,7 +29,8 @@ UNETK_BF16 kernels hold 3e-6 on the Cin = 512 .. 1024 rows as well (measured 0.9
 Limits: channel-slice views (xpad / ypad) run in the fp32 and UNETK_BF16 tiers; under UNETK_BF16S the rows run dense, except
 test_bf16s_tall_tile_with_a_4_channel_y_pad, because most pads of the table are not multiples of the 8 channels that mode's
 16-byte units need.  conv3x3_wgrad_bf16s_kernel<false> is reachable only through the UNETK_WGRAD_DEEP measurement switch and
-has no row.  ops._igemm_tag is not compared with the trace: it does not model the linear-pixel kernel.
+has no row.  The bench brackets of ops.py take their tag from this same trace (the first launch inside the bracket):
+test_bench_bracket_tag_is_the_first_traced_kernel.
 
 Small rows take the float64 reference from oracle/tf_ops.conv_nd_same on the CPU, rows marked big=True from the same function
 on the device (it is F.conv2d in float64 there).
@@ -821,7 +822,7 @@ def _cd(a, b):
 
 def sk_plan_bytes(n, h, w, cin, cout):
     """sk_plan's slab size for a 2-D forward (csrc/conv_igemm_lin.hip: lin_tune, lin_bm, sk_plan at their defaults), restated;
-    0 = stream-K off.  Only called for shapes unetk_conv_lin_ok admits.  It exists because the public query is the larger of the
+    0 = stream-K off.  Only called for shapes lin_ok admits.  It exists because the public query is the larger of the
     forward's and the input gradient's need, so "one unit short" of the query need not turn the forward's stream-K off.  A
     mismatch with the library shows as the `(need > 0) == on and query >= need` assertion or the "full" / "short" traces
     failing.  The plan's 1 GiB cap is not mirrored (no row comes near it)."""
@@ -953,6 +954,33 @@ def test_refusals(ops, what, entry, shape, code):
     assert rc == code, (what, rc, code)
     assert names == [], names
     assert bool((out == sent).all()) and bool((out2 == sent).all())
+
+
+@pytest.mark.parametrize("rid", ["t4_ragged", "lin_w3", "sk64"])
+def test_bench_bracket_tag_is_the_first_traced_kernel(ops, rid):
+    """With the profile brackets on, the forward bracket's tag is the name of the first launch inside it -- the tiled kernel,
+    the linear-pixel kernel, and for a stream-K layer the linear kernel, not its fix-up; sk64 checks the input gradient too."""
+    case = BY_ID[rid]
+    x, w, dy, _ = make_inputs(case, "eighths")
+    wp_f, wp_d = ops.conv3x3_pack(w.cuda())
+    xg, dyg = x.cuda(), dy.cuda()
+    expect = [case.fwd] + ([case.dgrad] if rid == "sk64" else [])
+    recs = []
+    ops.profile_begin(0)
+    ops.profile_on(recs)
+    try:
+        ops.conv3x3_fwd(xg, wp_f, case.cout, True)
+        if rid == "sk64":
+            ops.conv3x3_dgrad(dyg, wp_d, case.cin)
+    finally:
+        ops.profile_on(None)
+    torch.cuda.synchronize()
+    names = [_norm(n) for n in ops.profile_read()[1]]
+    assert len(recs) == len(expect), recs
+    for (tag, _, i0, i1, _), kernels in zip(recs, expect):
+        assert i1 - i0 == len(kernels), (tag, i0, i1)
+        first = names[i0][4:] if names[i0].startswith("void") else names[i0]
+        assert tag == first.split("(")[0] == kernels[0], (tag, names[i0], kernels)
 
 
 def _names_of(ops, case, kind="eighths"):
