@@ -970,6 +970,16 @@ extern "C" int unetk_conv3x3_dgrad_nbr(const unetk_conv_desc* d, const void* dy,
   UNETK_REQUIRE(unetk_aligned16(dy) && unetk_aligned16(w) && unetk_aligned16(dx));
   UNETK_REQUIRE(d->x_stride % 4 == 0 && d->y_stride % 4 == 0 && prod_y_stride >= d->Cin);
   if (unetk_conv3x3_dgrad_nbr_rows(d) <= 0) return UNETK_E_UNSUPPORTED;
+  // prod_y is read in the unit of the kernel the plan picks: fp32 scalars (tiled kernel), 4-byte words of two bf16 channels
+  // (the tiles of conv_igemm_bf16.hip) or 16-byte rows of eight (the persistent kernel, which the plan leaves for the tall
+  // tile when prod_y_stride % 8 != 0 -- the base address is not part of the plan, so a base it cannot read is refused here)
+  UNETK_REQUIRE(((uintptr_t)prod_y & 3) == 0);
+  if (d->precision == UNETK_BF16S) {
+    UNETK_REQUIRE(prod_y_stride % 2 == 0);
+    ConvShape s = desc_shape(d, true);
+    s.nbr = 1; s.stat = 1; s.nys = prod_y_stride;
+    if (unetk_conv_plan(s).family == CONV_BF16S_V3) UNETK_REQUIRE(unetk_aligned16(prod_y));
+  }
   ConvParams p = desc_params(d, true, dy, w, dx, nullptr, 0);
   p.stat = partials;
   p.ny = prod_y; p.nys = prod_y_stride;

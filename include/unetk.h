@@ -165,7 +165,12 @@ int unetk_conv3x3_fwd_affine(const unetk_conv_desc* d, const void* x, const void
  * shift > 0), xhat = (prod_y - mean) * rstd; scale / shift / mean / rstd are conv1's unetk_norm_finalize outputs,
  * [N][Cin] when per_sample else [Cin]) into partials [2][rows][Cin] -- the input unetk_norm_relu_bwd_pre takes instead of
  * running its own pass over (dz, y).  unetk_conv3x3_dgrad_nbr_rows = rows, or 0 when the shape has no fused variant
- * (tiled fp32 kernel and bf16-storage kernel only; the caller then uses the two separate calls). */
+ * (tiled fp32 kernel and bf16-storage kernel only; the caller then uses the two separate calls).
+ * Alignment of prod_y (dy, w, dx: 16 bytes, as for unetk_conv3x3_dgrad): the base address a multiple of 4 bytes in both
+ * modes; under UNETK_BF16S prod_y_stride even (two bf16 channels are read as one word), and where the persistent kernel runs
+ * -- H >= 24, at least 200 tiles of 32 x 16 pixels x 128 channels, x_stride / y_stride / prod_y_stride % 8 == 0 -- the base
+ * a multiple of 16 bytes (a stride that is not a multiple of 8 is routed to the tall tile, which reads words).  Anything
+ * else: UNETK_E_BADARG, nothing launched. */
 int unetk_conv3x3_dgrad_nbr_rows(const unetk_conv_desc* d);
 int unetk_conv3x3_dgrad_nbr(const unetk_conv_desc* d, const void* dy, const void* w, void* dx, const void* prod_y,
                             int prod_y_stride, const float* scale, const float* shift, const float* mean,
