@@ -188,6 +188,8 @@ _SIGNATURES = {
     "unetk_eval_slab": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, P, P, c_int, P, P, P, c_int, P, c_int, c_int, c_int,
                                 P, P]),
     "unetk_zoom_nearest3d": (c_int, [P, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, P, P]),
+    "unetk_nii_compose": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  P, P]),
     "unetk_surface3d": (c_int, [P, c_int, c_int, c_int, P, P, c_int, P]),
     "unetk_edt3d_sq_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "unetk_edt3d_sq": (c_int, [P, c_int, c_int, c_int, P, c_double, c_double, c_double, P, P, c_size_t, P]),

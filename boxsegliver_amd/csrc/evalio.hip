@@ -1,7 +1,9 @@
 // Input and output side of the offline volume evaluation (data/lits.py get_dataset_for_eval_image[_v2],
 // evaluators/evaluator_liver.py _predict_case): the network's input slabs are built from a case's resident HU crop, and
-// the argmax volume is zoomed back to the crop's shape, without the volume crossing to the host in between.  Both kernels
-// are gathers: every output element is written exactly once, by plain stores, no atomics and no workspace.
+// the argmax volume is zoomed back to the crop's shape, without the volume crossing to the host in between; with
+// --save_predict the post-processed masks are composed into the whole case in NIfTI file order (unetk_nii_compose), so
+// one copy brings the file's data to the host.  All three kernels are gathers: every output element is written exactly
+// once, by plain stores, no atomics and no workspace.
 //
 // Threads walk the FLAT output (the contiguous axis fastest): a thread owns V consecutive elements = one 16-byte store,
 // decomposes the index of its first element once (32-bit divisions) and steps the coordinates with carries, so 16-byte
@@ -175,6 +177,119 @@ __global__ __launch_bounds__(EIO_BLOCK) void zoom_nearest3d_kernel(ZoomArgs a) {
   }
 }
 
+// ---- predicted volume in NIfTI file order (evaluator_liver.py:998-1026 maybe_save_case + nii_kits.write_nii)
+// Everything is expressed per FILE axis k (0 = fastest): its length n, whether the data index runs backwards along it, and
+// of the data axis it runs along the box origin o, the box extent b and the masks' stride ms.  File index i_k is box
+// coordinate q_k = (flip ? n - 1 - i : i) - o; a voxel is inside the box when every 0 <= q_k < b_k.
+struct NiiArgs {
+  const uint8_t *liver, *tumor;
+  int16_t* dst;
+  int n[3], flip[3], o[3], b[3], ms[3];
+  int total;                                 // n[0] * n[1] * n[2]
+};
+
+__device__ __forceinline__ int nii_q(const NiiArgs& a, int k, int i) { return (a.flip[k] ? a.n[k] - 1 - i : i) - a.o[k]; }
+
+__device__ __forceinline__ int nii_px(const NiiArgs& a, int off) {
+  int v = 0;
+  if (a.liver) v += a.liver[off];
+  if (a.tumor) v += a.tumor[off];
+  return v;
+}
+
+__device__ __forceinline__ int nii_voxel(const NiiArgs& a, int i0, int i1, int i2) {
+  const int q0 = nii_q(a, 0, i0), q1 = nii_q(a, 1, i1), q2 = nii_q(a, 2, i2);
+  if ((unsigned)q0 >= (unsigned)a.b[0] || (unsigned)q1 >= (unsigned)a.b[1] || (unsigned)q2 >= (unsigned)a.b[2]) return 0;
+  return nii_px(a, q0 * a.ms[0] + q1 * a.ms[1] + q2 * a.ms[2]);
+}
+
+// eight consecutive mask bytes from any address (the box origin and width are arbitrary); global loads need no alignment
+__device__ __forceinline__ uint64_t nii_ld8(const uint8_t* p) {
+  uint64_t v;
+  __builtin_memcpy(&v, p, 8);
+  return v;
+}
+
+// File axis 0 runs along data x (ms[0] == 1): a thread owns V consecutive file elements = one 16-byte store.  A group inside
+// one file row whose x run lies inside the box reads 8 bytes of each mask at once; an x flip reverses them in the registers.
+template <int V>
+__global__ __launch_bounds__(EIO_BLOCK) void nii_compose_rows_kernel(NiiArgs a) {
+  const int groups = a.total / V;
+  const unsigned g = blockIdx.x * EIO_BLOCK + threadIdx.x;
+  if (g > (unsigned)groups) return;
+  const int e = (int)g * V;
+  const int count = g < (unsigned)groups ? V : a.total - e;
+  if (count <= 0) return;
+  unsigned t = (unsigned)e;
+  int i0 = (int)(t % (unsigned)a.n[0]);
+  t /= (unsigned)a.n[0];
+  int i1 = (int)(t % (unsigned)a.n[1]);
+  int i2 = (int)(t / (unsigned)a.n[1]);
+  if (V == 8 && count == V && i0 + V <= a.n[0]) {
+    uint32_t word[4] = {0u, 0u, 0u, 0u};
+    const int q1 = nii_q(a, 1, i1), q2 = nii_q(a, 2, i2);
+    const int qlo = (a.flip[0] ? a.n[0] - V - i0 : i0) - a.o[0];          // lowest box x of the group
+    if ((unsigned)q1 < (unsigned)a.b[1] && (unsigned)q2 < (unsigned)a.b[2] && qlo + V > 0 && qlo < a.b[0]) {
+      const int row = q1 * a.ms[1] + q2 * a.ms[2];
+      int v[8];
+      if (qlo >= 0 && qlo + V <= a.b[0]) {
+        const uint64_t l = a.liver ? nii_ld8(a.liver + row + qlo) : 0ull;
+        const uint64_t m = a.tumor ? nii_ld8(a.tumor + row + qlo) : 0ull;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (int)((l >> (8 * j)) & 0xffu) + (int)((m >> (8 * j)) & 0xffu);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (unsigned)(qlo + j) < (unsigned)a.b[0] ? nii_px(a, row + qlo + j) : 0;
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) word[k / 2] |= (uint32_t)(a.flip[0] ? v[7 - k] : v[k]) << (16 * (k % 2));
+    }
+    *reinterpret_cast<uint4*>(a.dst + e) = make_uint4(word[0], word[1], word[2], word[3]);
+  } else {
+    for (int k = 0; k < count; ++k) {
+      a.dst[e + k] = (int16_t)nii_voxel(a, i0, i1, i2);
+      if (++i0 == a.n[0]) {
+        i0 = 0;
+        if (++i1 == a.n[1]) {
+          i1 = 0;
+          ++i2;
+        }
+      }
+    }
+  }
+}
+
+// File axis 0 runs along data y or z, data x along file axis KX (1 or 2): per index of the third axis, a transpose of
+// NII_TILE x NII_TILE tiles through LDS.  Lanes walk data x while reading the masks and file axis 0 while storing, so both
+// sides touch consecutive addresses; a row stride of 33 words keeps the column reads out of each other's LDS banks.
+constexpr int NII_TILE = 64;
+
+template <int KX>
+__global__ __launch_bounds__(EIO_BLOCK) void nii_compose_tr_kernel(NiiArgs a) {
+  __shared__ int16_t tile[NII_TILE][NII_TILE + 2];
+  constexpr int KR = 3 - KX;
+  const int base0 = blockIdx.x * NII_TILE;
+  for (int ir = blockIdx.z; ir < a.n[KR]; ir += gridDim.z) {
+    for (int basex = blockIdx.y * NII_TILE; basex < a.n[KX]; basex += gridDim.y * NII_TILE) {
+      for (int t = threadIdx.x; t < NII_TILE * NII_TILE; t += EIO_BLOCK) {
+        const int xi = t % NII_TILE, ai = t / NII_TILE;
+        const int i0 = base0 + ai, ix = basex + xi;
+        if (i0 < a.n[0] && ix < a.n[KX]) tile[ai][xi] = (int16_t)nii_voxel(a, i0, KX == 1 ? ix : ir, KX == 1 ? ir : ix);
+      }
+      __syncthreads();
+      for (int t = threadIdx.x; t < NII_TILE * NII_TILE; t += EIO_BLOCK) {
+        const int ai = t % NII_TILE, xi = t / NII_TILE;
+        const int i0 = base0 + ai, ix = basex + xi;
+        if (i0 < a.n[0] && ix < a.n[KX]) {
+          const int i1 = KX == 1 ? ix : ir, i2 = KX == 1 ? ir : ix;
+          a.dst[i0 + a.n[0] * (i1 + a.n[1] * i2)] = tile[ai][xi];
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
 static inline bool eio_fits(int a, int b, int c, int d = 1) {
   return a > 0 && b > 0 && c > 0 && d > 0 && (int64_t)a * b * c < ((int64_t)1 << 31) &&
          (int64_t)a * b * c * d < ((int64_t)1 << 31);
@@ -221,6 +336,48 @@ extern "C" int unetk_zoom_nearest3d(const uint8_t* src, int d, int h, int w, con
     UNETK_LAUNCH(zoom_nearest3d_kernel<16>, dim3((groups + EIO_BLOCK - 1) / EIO_BLOCK), dim3(EIO_BLOCK), 0, st, a);
   } else {
     UNETK_LAUNCH(zoom_nearest3d_kernel<1>, dim3((a.total + EIO_BLOCK - 1) / EIO_BLOCK), dim3(EIO_BLOCK), 0, st, a);
+  }
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
+extern "C" int unetk_nii_compose(const uint8_t* liver, const uint8_t* tumor, int bd, int bh, int bw, int z1, int y1, int x1,
+                                 int d, int h, int w, int t0, int t1, int t2, int flips, int16_t* dst, void* stream) {
+  UNETK_REQUIRE((liver || tumor) && dst && (((uintptr_t)dst) & 1u) == 0);
+  UNETK_REQUIRE(d > 0 && h > 0 && w > 0 && bd > 0 && bh > 0 && bw > 0);
+  UNETK_REQUIRE(z1 >= 0 && y1 >= 0 && x1 >= 0 && (int64_t)z1 + bd <= d && (int64_t)y1 + bh <= h && (int64_t)x1 + bw <= w);
+  const int tb[3] = {t0, t1, t2};
+  unsigned seen = 0;
+  for (int k = 0; k < 3; ++k) {
+    UNETK_REQUIRE(tb[k] >= 0 && tb[k] <= 2);
+    seen |= 1u << tb[k];
+  }
+  UNETK_REQUIRE(seen == 7u && (flips & ~7) == 0);
+  if (!eio_fits(d, h, w)) return UNETK_E_UNSUPPORTED;
+  // per data axis (z, y, x): length, box origin, box extent, mask stride, flip bit
+  const int len[3] = {d, h, w}, org[3] = {z1, y1, x1}, ext[3] = {bd, bh, bw}, mst[3] = {bh * bw, bw, 1};
+  const int fbit[3] = {(flips >> 2) & 1, (flips >> 1) & 1, flips & 1};
+  NiiArgs a;
+  a.liver = liver; a.tumor = tumor; a.dst = dst;
+  for (int k = 0; k < 3; ++k) {
+    a.n[k] = len[tb[k]]; a.flip[k] = fbit[tb[k]]; a.o[k] = org[tb[k]]; a.b[k] = ext[tb[k]]; a.ms[k] = mst[tb[k]];
+  }
+  a.total = d * h * w;
+  hipStream_t st = (hipStream_t)stream;
+  if (tb[0] != 2) {
+    const int kx = tb[1] == 2 ? 1 : 2;
+    const int tiles_x = (a.n[kx] + NII_TILE - 1) / NII_TILE;
+    const dim3 grid((a.n[0] + NII_TILE - 1) / NII_TILE, tiles_x < 65535 ? tiles_x : 65535, a.n[3 - kx] < 65535 ? a.n[3 - kx] : 65535);
+    if (kx == 1) {
+      UNETK_LAUNCH(nii_compose_tr_kernel<1>, grid, dim3(EIO_BLOCK), 0, st, a);
+    } else {
+      UNETK_LAUNCH(nii_compose_tr_kernel<2>, grid, dim3(EIO_BLOCK), 0, st, a);
+    }
+  } else if (unetk_aligned16(dst)) {
+    const int groups = a.total / 8 + 1;                        // + 1: the thread that stores the elements past the last group
+    UNETK_LAUNCH(nii_compose_rows_kernel<8>, dim3((groups + EIO_BLOCK - 1) / EIO_BLOCK), dim3(EIO_BLOCK), 0, st, a);
+  } else {
+    UNETK_LAUNCH(nii_compose_rows_kernel<1>, dim3(a.total / EIO_BLOCK + 1), dim3(EIO_BLOCK), 0, st, a);
   }
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;

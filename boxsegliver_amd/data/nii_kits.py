@@ -190,3 +190,132 @@ def write_nii(data, header, out_path, out_dtype=np.int16, special=False, affine=
         zooms = np.abs(affine[:3, :3]).max(axis=0)
         header = Nifti1Header(out_image.shape, out_dtype, zooms, sform=affine[:3, :])
     save(out_image, header, out_path)
+
+
+# ----------------------------------------------------------------------------- saved predictions (--save_predict)
+SAVE_GZIP_LEVEL = 1         # nibabel's default; mtime 0 and no stored file name make two runs write identical bytes
+
+
+def _parse_header(raw, file_name):
+    """The fields of `load` from a file's first 352 bytes."""
+    if len(raw) < 348:
+        raise ValueError("{}: shorter than a NIfTI-1 header".format(file_name))
+    endian = "<"
+    if struct.unpack("<i", raw[:4])[0] != 348:
+        endian = ">"
+        if struct.unpack(">i", raw[:4])[0] != 348:
+            raise ValueError("{}: not a NIfTI-1 file (sizeof_hdr != 348)".format(file_name))
+    if raw[344:348] != b"n+1\0":
+        raise ValueError("{}: bad or unsupported NIfTI-1 magic {!r}".format(file_name, raw[344:348]))
+    dim = struct.unpack(endian + "8h", raw[40:56])
+    ndim = dim[0]
+    if not 1 <= ndim <= 7:
+        raise ValueError("{}: bad dim[0] = {}".format(file_name, ndim))
+    shape = tuple(d for d in dim[1:1 + ndim])
+    while len(shape) > 3 and shape[-1] == 1:
+        shape = shape[:-1]
+    datatype, = struct.unpack(endian + "h", raw[70:72])
+    if datatype not in _DTYPES:
+        raise ValueError("{}: unsupported NIfTI datatype {}".format(file_name, datatype))
+    pixdim = struct.unpack(endian + "8f", raw[76:108])
+    vox_offset, scl_slope, scl_inter = struct.unpack(endian + "3f", raw[108:120])
+    qform_code, sform_code = struct.unpack(endian + "2h", raw[252:256])
+    quatern = struct.unpack(endian + "3f", raw[256:268])
+    qoffset = struct.unpack(endian + "3f", raw[268:280])
+    srow = struct.unpack(endian + "12f", raw[280:328])
+    return Nifti1Header(shape, _DTYPES[datatype], pixdim[1:4], srow if sform_code > 0 else None, qform_code, quatern,
+                        qoffset, -1.0 if pixdim[0] < 0 else 1.0, scl_slope, scl_inter, vox_offset, endian)
+
+
+def load_header(file_name):
+    """The header alone: only the first 352 bytes are read (of a .gz: inflated), where `load` -- and with it
+    read_nii(only_header=True) -- inflates the whole file."""
+    with _open(file_name, "rb") as f:
+        raw = f.read(352)
+    return _parse_header(raw, file_name)
+
+
+def _header_bytes(shape, dtype, header):
+    """The 352 bytes `save` writes in front of an array of `shape` (file order) and `dtype`."""
+    dt = np.dtype(dtype)
+    if dt not in _CODES:
+        raise ValueError("unsupported dtype {}".format(dt))
+    shape = [int(s) for s in shape]
+    h = bytearray(352)
+    struct.pack_into("<i", h, 0, 348)
+    struct.pack_into("<8h", h, 40, *([len(shape)] + shape + [1] * (7 - len(shape))))
+    struct.pack_into("<h", h, 70, _CODES[dt])
+    struct.pack_into("<h", h, 72, dt.itemsize * 8)
+    struct.pack_into("<8f", h, 76, *([header.qfac] + list(header.pixdim[:3]) + [1.0] * 4))
+    struct.pack_into("<3f", h, 108, 352.0, header.scl_slope, header.scl_inter)
+    struct.pack_into("<2h", h, 252, header.qform_code, 1 if header.sform is not None else 0)
+    struct.pack_into("<3f", h, 256, *header.quatern)
+    struct.pack_into("<3f", h, 268, *header.qoffset)
+    if header.sform is not None:
+        struct.pack_into("<12f", h, 280, *np.asarray(header.sform, np.float32).reshape(-1))
+    h[344:348] = b"n+1\0"
+    return bytes(h)
+
+
+def save_flat(flat, shape, header, out_path, level=SAVE_GZIP_LEVEL):
+    """`save` for data that is in file order already: `flat` is a dense 1-D array (file axis 0 fastest) of prod(shape)
+    elements, written with `header`'s geometry behind the same 352 header bytes.  A .gz is written at `level` with mtime 0
+    and no file name in the gzip header, so the bytes depend on the data alone."""
+    flat = np.asarray(flat)
+    if flat.ndim != 1 or not flat.flags.c_contiguous or flat.size != int(np.prod(shape)):
+        raise ValueError("a dense 1-D array of {} elements expected, got shape {}".format(int(np.prod(shape)), flat.shape))
+    if flat.dtype.byteorder == ">":
+        raise ValueError("little-endian (or native) data expected")
+    head = _header_bytes(shape, flat.dtype, header)
+    out_path = str(out_path)
+    with open(out_path, "wb") as raw:
+        if out_path.endswith(".gz"):
+            with gzip.GzipFile(filename="", mode="wb", compresslevel=level, fileobj=raw, mtime=0) as f:
+                f.write(head)
+                f.write(memoryview(flat).cast("B"))
+        else:
+            raw.write(head)
+            raw.write(memoryview(flat).cast("B"))
+
+
+def file_orientation(header, special=False):
+    """What write_nii does to a (z, y, x) array on its way into a file with `header`: (trans_bk, (flip_x, flip_y, flip_z))
+    -- file axis i runs along data axis trans_bk[i], after the flips; `special` (read_lits's x-mirrored cases) toggles the x
+    flip, as two flips of one axis cancel."""
+    affine = np.asarray(header.get_best_affine(), np.float64)
+    if len(np.where(affine[:3, :3].reshape(-1) != 0)[0]) != 3:
+        raise ValueError("an axis-aligned affine expected, got {}".format(affine[:3, :3].tolist()))
+    trans, (flip_x, flip_y, flip_z) = _orient(affine)
+    trans_bk = tuple(int(np.argwhere(np.array(trans[::-1]) == i)[0][0]) for i in range(3))
+    if sorted(trans_bk) != [0, 1, 2]:
+        raise ValueError("the affine {} does not name three different axes".format(affine[:3, :3].tolist()))
+    return trans_bk, (bool(flip_x) != bool(special), bool(flip_y), bool(flip_z))
+
+
+def data_shape(header):
+    """(d, h, w) of the (z, y, x) array read_nii returns for a file with `header`."""
+    trans_bk, _ = file_orientation(header)
+    zyx = [0, 0, 0]
+    for i, axis in enumerate(trans_bk):
+        zyx[axis] = int(header.shape[i])
+    return tuple(zyx)
+
+
+def to_file_order(data, header, special=False, out_dtype=np.int16):
+    """write_nii's flips, transpose and cast without the write: (z, y, x) data -> the flat array save_flat takes."""
+    trans_bk, flips = file_orientation(header, special)
+    for axis, flip in zip((2, 1, 0), flips):
+        if flip:
+            data = np.flip(data, axis=axis)
+    return np.transpose(data, trans_bk).astype(out_dtype).reshape(-1, order="F")
+
+
+def header_from_meta(size, spacing, dtype=np.int16):
+    """A header for a case known only from meta.json (size = [d, h, w], spacing = [z, y, x]): pixdim (sx, sy, sz) and
+    sform diag(-sx, -sy, +sz) with zero offsets -- the orientation read_nii returns unflipped, so the array index of the
+    written file is (x, y, z) of the data."""
+    d, h, w = (int(s) for s in size)
+    sz, sy, sx = (float(s) for s in spacing)
+    sform = np.zeros((3, 4), np.float64)
+    sform[0, 0], sform[1, 1], sform[2, 2] = -sx, -sy, sz
+    return Nifti1Header((w, h, d), dtype, (sx, sy, sz), sform=sform)

@@ -18,6 +18,12 @@ What runs where (MI355X-first):
     argmax volume again), then class split, merge tumor into liver, largest connected component (_postprocess_device),
     the per-case volume metrics (loss_metrics.metric_3d_device) and the global Dice counts run in csrc/evalvol.hip.
     metrics_on="host" keeps the reference's host path (_postprocess, loss_metrics.metric_3d, ConfusionMatrix).
+  * DEVICE, then a HOST THREAD (-s/--save_predict, `maybe_save_case` :998-1026; _CaseSaver below): a case that
+    is on the device and scored there is post-processed once, composed into the whole volume in NIfTI file order by
+    `unetk_nii_compose` and copied once into a pinned buffer on a side stream; utils/volume_writer writes
+    `predict-<case>.nii.gz` (header of the case's volume file, or one built from meta.json) behind the next case.  Host
+    volumes take the reference's np.pad / write_nii steps in that thread; the bytes are the same.  --mode infer writes the
+    files and scores nothing.
 
 The input contract is the reference's eval generator (DataLoader/Liver/input_pipeline_li.py:398-456): a stream of
 `(features, None)` slabs -- features["images"] [bs,H,W,C], features["names"], optional features["mirror"] in {0,1,2,3}
@@ -32,6 +38,7 @@ UNet3D on LiTS (`liver_3d --eval_in_patches`) is scored by `run_3d`: sliding win
 batch, `unetk_eval3d_accumulate` into the case at source resolution, then the same scoring.
 """
 import json
+import logging
 import time
 from collections import defaultdict
 from pathlib import Path
@@ -46,6 +53,8 @@ from ..NetworksV2.base import ModeKeys
 from ..utils import array_kits as arr_ops
 from ..utils import tf_checkpoint
 from .evaluator_base import EvaluateBase
+
+log = logging.getLogger("boxsegliver_amd")
 
 
 def add_arguments(parser):
@@ -129,6 +138,8 @@ class EvaluateVolume(EvaluateBase):
         self.use_sg_reduce_fp = bool(use_sg_reduce_fp and getattr(self.config, "use_spatial", False))
         self.calls = 0
         self.seconds = 0.0
+        self._saver = None                  # the _CaseSaver of a --save_predict run, while it runs
+        self.save_join_each_case = False    # measurements: wait for each case's file instead of writing behind the next case
 
     @property
     def classes(self):
@@ -184,7 +195,8 @@ class EvaluateVolume(EvaluateBase):
     def _predict_case(self, predicts, cases=-1, dtype="pred", resize=False, save_path=None):
         """evaluator_liver.py:616-678 with the accumulation on the device.  Yields
         (case, segmentation, volume, post_processed); volume is a numpy array, or with _device_volumes a uint8 device
-        tensor that was zoomed back on the device."""
+        tensor that was zoomed back on the device.  With save_path (--save_predict) the case is post-processed here, handed
+        to the background writer (_maybe_save_case) and yielded as the post-processed class dict, post_processed = True."""
         on_device = self._device_volumes(dtype)
         slabs = []
         cur_case = None
@@ -218,7 +230,7 @@ class EvaluateVolume(EvaluateBase):
                     if volume.ndim == 4:
                         ori_shape = ori_shape + (volume.shape[-1],)
                     volume = self._zoom_back(volume, ori_shape, dtype)
-                yield cur_case, segmentation, volume, False
+                yield (cur_case, segmentation) + self._maybe_save_case(cur_case, volume, bbox, dtype, save_path)
                 slabs.clear()
                 cur_case = None
                 counter += 1
@@ -255,7 +267,8 @@ class EvaluateVolume(EvaluateBase):
                 volume = amax.view(result.shape[:-1]).cpu().numpy()
             else:
                 volume = result.cpu().numpy()
-            yield str(predict["name"]), segmentation, volume, False
+            yield (str(predict["name"]), segmentation) + self._maybe_save_case(str(predict["name"]), volume, bbox, dtype,
+                                                                               save_path)
             result, covered = None, None
             counter += 1
             if 0 < cases <= counter:
@@ -494,14 +507,17 @@ class EvaluateVolume(EvaluateBase):
 
     def _predict_case_3d(self, predicts, cases=-1, dtype="pred", save_path=None):
         """A case of run_3d for _run_actual: (case, device labels, device class volume uint8 [depth, src_h, src_w], False).
-        The coverage is read here, where the scoring that follows synchronises anyway."""
+        The coverage is read here, where the scoring that follows synchronises anyway.  With save_path the volume is saved as
+        in _predict_case, its box being the whole case at source resolution."""
         if dtype != "pred":
             raise NotImplementedError("the sliding-window 3-D evaluation scores class predictions (--pred_type pred)")
         counter = 0
         for case, labels, volume, cnt in predicts:
             if int(cnt.min().item()) <= 0:
                 raise RuntimeError("--eval_in_patches: windows do not cover every voxel of case {}".format(case))
-            yield case, labels, volume, False
+            depth, src_h, src_w = (int(v) for v in volume.shape)
+            yield (case, labels) + self._maybe_save_case(case, volume, (0, 0, 0, src_w - 1, src_h - 1, depth - 1), dtype,
+                                                         save_path)
             counter += 1
             if 0 < cases <= counter:
                 break
@@ -568,18 +584,39 @@ class EvaluateVolume(EvaluateBase):
             if volume.ndim == 4:
                 ori_shape = ori_shape + (volume.shape[-1],)
             volume = self._zoom_back(volume, ori_shape, dtype)
-            yield str(item["pid"]), item["segmentation"], volume, False
+            yield (str(item["pid"]), item["segmentation"]) + self._maybe_save_case(str(item["pid"]), volume, item["bbox"],
+                                                                                   dtype, save_path)
             counter += 1
             if 0 < cases <= counter:
                 break
 
     def _run_actual(self, predict_fn, run_fn, save, cases=-1, **run_kwargs):
         """evaluator_liver.py:906-996; returns the averaged results (the reference only logs them)."""
-        do_eval = getattr(self.config, "mode", ModeKeys.EVAL) != "predict"
+        do_eval = getattr(self.config, "mode", ModeKeys.EVAL) not in ("predict", ModeKeys.PREDICT)
         save_path = None
         if save:
             save_path = Path(self.model_dir) / (getattr(self.config, "save_path", None) or "prediction")
             save_path.mkdir(parents=True, exist_ok=True)
+            self._saver = _CaseSaver(self, save_path)
+        elif not do_eval:
+            log.warning("--mode infer without --save_predict: the predictions are computed and nothing is written")
+        try:
+            results = self._run_cases(predict_fn, run_fn, save_path, do_eval, cases, **run_kwargs)
+            if self._saver is not None:
+                self._saver.writer.close()                              # every file is complete before results.json says so
+        except BaseException:
+            if self._saver is not None:
+                self._saver.abandon()
+            raise
+        finally:
+            self._saver = None
+        if save_path is not None:
+            with (save_path / "results.json").open("w") as f:
+                json.dump(results, f)
+        return results
+
+    def _run_cases(self, predict_fn, run_fn, save_path, do_eval, cases=-1, **run_kwargs):
+        """The loop of _run_actual over the cases."""
         accumulator = defaultdict(int)
         use_global = bool(getattr(self.config, "use_global_dice", False))
         self.clear_metrics()
@@ -609,9 +646,13 @@ class EvaluateVolume(EvaluateBase):
                         for met, value in pairs.items():
                             results["{}/{}".format(cls, met)] = value
                     self.append_metrics(results)
+            if self._saver is not None and self.save_join_each_case:
+                self._saver.writer.join()
             self.calls += 1
             self.seconds += time.perf_counter() - tic
             tic = time.perf_counter()
+        if not do_eval:
+            return {}
 
         def gdice(cls):
             den = 2 * accumulator[cls + "_tp"] + accumulator[cls + "_fn"] + accumulator[cls + "_fp"]
@@ -623,10 +664,14 @@ class EvaluateVolume(EvaluateBase):
             results = {key: float(np.mean(values)) for key, values in self._metric_values.items()}
             if accumulator:
                 results.update({"G" + cls + "Dice": gdice(cls) for cls in self.classes})
-        if save_path is not None:
-            with (save_path / "results.json").open("w") as f:
-                json.dump(results, f)
         return results
+
+    def _maybe_save_case(self, case, volume, bbox, dtype, save_path):
+        """evaluator_liver.py:998-1026 `maybe_save_case`: -> (volume, post_processed).  Without --save_predict the volume
+        passes through; with it, see _CaseSaver.save."""
+        if save_path is None or self._saver is None:
+            return volume, False
+        return self._saver.save(str(case), volume, bbox, dtype)
 
     def _score_case_device(self, volume, labels, post_processed, accumulator, use_global):
         """One case of _run_actual on the device: one upload of the volume (none when it is a device tensor already:
@@ -653,6 +698,107 @@ class EvaluateVolume(EvaluateBase):
 
     def compare(self, *args_, **kwargs):
         return _compare(*args_, **kwargs)
+
+
+class _CaseSaver(object):
+    """--save_predict for one run of EvaluateVolume: `<save_path>/predict-<case>.nii.gz` holds the post-processed
+    Liver + Tumor mask of the case, padded from its box to the whole volume, with the header of the case's own volume file
+    (evaluator_liver.py:998-1026); --pred_type prob writes `<case>.npz` with the zero-padded 4-D probabilities instead.
+
+    A volume that is on the device and scored there (volumes_on = metrics_on = "device", and run_3d) is post-processed by
+    _postprocess_device, composed in file order by `unetk_nii_compose` and copied once; otherwise the reference's host
+    path (np.pad, write_nii's flips and transpose) runs in the writer thread.  Both write the same bytes.  The files are
+    written by utils/volume_writer.VolumeWriter behind the evaluation of the next case.
+
+    Header: the case's `vol_case` of meta.json under params["proj_root"], read header-only; when the entry or the file is
+    missing (the PNG store of liver_3d needs no NIfTI), nii_kits.header_from_meta of its `size` and `spacing`, logged once.
+    Unlike the reference, which calls write_nii without `special`, the write inverts the read: cases 28..47 are x-mirrored
+    as read_lits("vol") mirrors them, so voxel (i, j, k) of the written file is voxel (i, j, k) of the volume file."""
+
+    def __init__(self, evaluator, save_path):
+        from ..utils.volume_writer import VolumeWriter
+        self.ev, self.save_path = evaluator, Path(save_path)
+        self.writer = VolumeWriter()
+        self._meta = None
+        self._told_fallback = False
+
+    def abandon(self):
+        """The way out of an exception: stop the thread; what it met is second to the exception under way."""
+        try:
+            self.writer.close()
+        except Exception as err:         # noqa: the first exception is the one to report
+            log.error("the volume writer failed as well: %r", err)
+
+    def _case_meta(self, pid):
+        if self._meta is None:
+            root = self.ev.params.get("lits_root")
+            self._meta = {}
+            if root is not None and (Path(root) / "meta.json").exists():
+                with (Path(root) / "meta.json").open() as f:
+                    self._meta = {int(c["PID"]): c for c in json.load(f)}
+        return self._meta.get(pid)
+
+    def header(self, case):
+        """(header, special) of a case; special = the x mirror of read_lits("vol")."""
+        from ..data import nii_kits
+        from ..data.lits import _maybe_json
+        pid = int(case)
+        meta = self._case_meta(pid)
+        if meta is None:
+            raise ValueError("--save_predict: case {} is not in meta.json of {}".format(case, self.ev.params.get("lits_root")))
+        special = 28 <= pid < 48
+        vol_case = meta.get("vol_case")
+        if vol_case:
+            path = Path(self.ev.params.get("proj_root", ".")) / vol_case
+            if path.exists():
+                return nii_kits.load_header(path), special
+        if not self._told_fallback:
+            self._told_fallback = True
+            log.info("--save_predict: no volume file for case %s (vol_case %r); headers are built from meta.json's size and "
+                     "spacing", case, vol_case)
+        return nii_kits.header_from_meta(_maybe_json(meta["size"]), _maybe_json(meta["spacing"])), special
+
+    def save(self, case, volume, bbox, dtype):
+        from ..data import nii_kits
+        header, special = self.header(case)
+        case_shape = nii_kits.data_shape(header)
+        origin = (int(bbox[2]), int(bbox[1]), int(bbox[0]))
+        box = tuple(arr_ops.bbox_to_shape(bbox))
+        if tuple(volume.shape[:3]) != box:
+            raise ValueError("--save_predict: the volume of case {} has shape {}, its box {} (evaluate with the resize back "
+                             "to the box)".format(case, tuple(volume.shape[:3]), box))
+        if any(o < 0 or o + b > n for o, b, n in zip(origin, box, case_shape)):
+            raise ValueError("--save_predict: the box {} at {} of case {} leaves its volume {}".format(
+                box, origin, case, case_shape))
+        pad_with = tuple((o, n - o - b) for o, b, n in zip(origin, box, case_shape))
+        if dtype != "pred":                                           # the 4-D probabilities -> <case>.npz
+            save_file = self.save_path / (case + ".npz")
+            self.writer.submit_call(save_file, lambda: np.savez_compressed(
+                str(save_file), np.pad(volume, pad_with + ((0, 0),), mode="constant", constant_values=0)))
+            return volume, False
+        save_file = self.save_path / "predict-{}.nii.gz".format(case)
+        trans_bk, flips = nii_kits.file_orientation(header, special)
+        file_shape = tuple(case_shape[axis] for axis in trans_bk)
+        if torch.is_tensor(volume) and self.ev.metrics_on == "device":
+            volume = self.ev._postprocess_device(volume)
+            if "Liver" not in volume and "Tumor" not in volume:
+                raise ValueError("Not supported save object!")
+            flat = ops.nii_compose(volume.get("Liver"), volume.get("Tumor"), origin, case_shape, trans_bk, flips)
+            self.writer.submit(save_file, header, file_shape, flat)
+            return volume, True
+        if torch.is_tensor(volume):
+            volume = volume.cpu().numpy()
+        volume = self.ev._postprocess(volume)
+        parts = [np.asarray(volume[cls]).astype(np.uint8) for cls in ("Liver", "Tumor") if cls in volume]
+        if not parts:
+            raise ValueError("Not supported save object!")
+        img_array = parts[0] + parts[1] if len(parts) == 2 else parts[0]
+
+        def write():
+            padded = np.pad(img_array, pad_with, mode="constant", constant_values=0)
+            nii_kits.save_flat(nii_kits.to_file_order(padded, header, special), file_shape, header, save_file)
+        self.writer.submit_call(save_file, write)
+        return volume, True
 
 
 GUIDE_TABLE_CAP = 16384         # components per slice the device table holds (more raise): an early checkpoint can predict

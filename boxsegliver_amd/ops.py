@@ -1383,6 +1383,48 @@ def zoom_nearest3d(vol_u8, out_shape, tables=None, out=None):
     return out
 
 
+def nii_compose(liver, tumor, origin, case_shape, trans_bk=(2, 1, 0), flips=(False, False, False), out=None):
+    """The saved prediction of one case in NIfTI file order (unetk_nii_compose): liver / tumor are the post-processed uint8
+    (or bool) device masks [bd, bh, bw] of the box at origin = (z1, y1, x1) of a case_shape = (d, h, w) volume; either may be
+    None.  trans_bk and flips = (flip_x, flip_y, flip_z) are what nii_kits.write_nii applies (nii_kits.file_orientation).
+    Returns the flat int16 device tensor of d * h * w elements, file axis 0 fastest: liver + tumor inside the box, 0 outside
+    -- np.pad and write_nii's flips, transpose and cast in one pass.  out: a dense int16 tensor of that size to write into."""
+    masks = [None if m is None else _mask_bytes(m) for m in (liver, tumor)]
+    ref = masks[0] if masks[0] is not None else masks[1]
+    if ref is None:
+        raise ValueError("nii_compose needs a liver or a tumor mask")
+    if masks[1] is not None and masks[1].shape != ref.shape:
+        raise ValueError("shape mismatch: {} and {}".format(tuple(ref.shape), tuple(masks[1].shape)))
+    bd, bh, bw = (int(s) for s in ref.shape)
+    z1, y1, x1 = (int(v) for v in origin)
+    d, h, w = (int(v) for v in case_shape)
+    tb = tuple(int(v) for v in trans_bk)
+    if sorted(tb) != [0, 1, 2]:
+        raise ValueError("trans_bk must be a permutation of (0, 1, 2), got {}".format(trans_bk))
+    fx, fy, fz = (bool(f) for f in flips)
+    if out is None:
+        out = torch.empty(d * h * w, dtype=torch.int16, device=ref.device)
+    _require_cuda(out)
+    if out.dtype != torch.int16 or out.numel() != d * h * w or not out.is_contiguous():
+        raise ValueError("out must be a dense int16 tensor of {} elements".format(d * h * w))
+    with _timed_hbm("nii_compose", out, 1, sum(m.numel() for m in masks if m is not None)):
+        check(_abi.lib().unetk_nii_compose(ptr(masks[0]), ptr(masks[1]), bd, bh, bw, z1, y1, x1, d, h, w, tb[0], tb[1], tb[2],
+                                           int(fx) | int(fy) << 1 | int(fz) << 2, ptr(out), stream_ptr()), "nii_compose")
+    return out
+
+
+def _mask_bytes(t):
+    """A [D, H, W] device mask as dense bytes, values kept (bool -> 0 / 1)."""
+    _require_cuda(t)
+    if t.dim() != 3:
+        raise ValueError("a 3-D [D, H, W] mask expected, got shape {}".format(tuple(t.shape)))
+    if t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    elif t.dtype != torch.uint8:
+        raise ValueError("a uint8 or bool mask expected, got {}".format(t.dtype))
+    return t.contiguous()
+
+
 GUIDE_ROW = 12            # int32 words per component row of unetk_guide_components
 
 

@@ -626,6 +626,17 @@ int unetk_eval_slab(const int16_t* vol, int src_d, int src_h, int src_w, const i
  * D * H * W < 2^31. */
 int unetk_zoom_nearest3d(const uint8_t* src, int d, int h, int w, const int32_t* tz, const int32_t* ty, const int32_t* tx,
                          int D, int H, int W, uint8_t* dst, void* stream);
+/* Saved prediction (evaluator_liver.py:998-1026 `maybe_save_case`, nii_kits.py:53-75 `write_nii`): the post-processed class
+ * masks of one case -- liver and / or tumor, uint8 [bd,bh,bw] in (z, y, x) order, either may be NULL -- placed at
+ * (z1, y1, x1) of a [d,h,w] volume of zeros and written as int16 in NIfTI file order: dst[i0 + n0 * (i1 + n1 * i2)] with
+ * file axis k running along data axis t_k (0 = z, 1 = y, 2 = x; n_k its length; (t0, t1, t2) a permutation: write_nii's
+ * `trans_bk`), backwards along the data axes whose bit of `flips` is set (bit 0 = x, 1 = y, 2 = z).  The value is
+ * liver + tumor inside the box and 0 outside; every one of the d * h * w elements is written exactly once; no workspace.
+ * t0 == 2 (every LiTS file): 16-byte stores, 8-byte mask reads (dst not 16-byte aligned: one element per thread);
+ * otherwise a tiled transpose through LDS.  UNETK_E_BADARG: dst or both masks NULL, dst not 2-byte aligned, a
+ * non-positive size, a box outside the case, (t0, t1, t2) not a permutation; UNETK_E_UNSUPPORTED: d * h * w >= 2^31. */
+int unetk_nii_compose(const uint8_t* liver, const uint8_t* tumor, int bd, int bh, int bw, int z1, int y1, int x1, int d, int h,
+                      int w, int t0, int t1, int t2, int flips, int16_t* dst, void* stream);
 
 /* ---------------------------------------------------------------- LiTS training batch  
  * DataLoader/Liver/input_pipeline.py:243-284 `data_processing_train` for a whole batch, gathering from decoded slices
