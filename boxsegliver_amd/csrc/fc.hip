@@ -74,6 +74,7 @@ extern "C" int unetk_fc_fwd(const float* x, const float* w, const float* b, floa
                             int relu, float keep_prob, uint32_t seed, void* stream) {
   UNETK_REQUIRE(x && w && y && B > 0 && k > 0 && n > 0 && B <= 65535);
   UNETK_REQUIRE(!mask || (keep_prob > 0.f && keep_prob <= 1.f));
+  if (relu == 2 && mask) return UNETK_E_UNSUPPORTED;   // the backward has y = s * m only, not the unmasked sigmoid s
   UNETK_LAUNCH(fc_fwd_kernel, dim3((n + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, x, w, b, y, mask, k, n,
                      relu, keep_prob, seed);
   UNETK_LAUNCH_CHECK();
@@ -83,6 +84,7 @@ extern "C" int unetk_fc_fwd(const float* x, const float* w, const float* b, floa
 extern "C" int unetk_fc_bwd(const float* x, const float* w, const float* y, const float* mask, const float* dy, float* dx,
                             float* dw, float* db, float* dpre_ws, int B, int k, int n, int relu, void* stream) {
   UNETK_REQUIRE(x && w && y && dy && dw && dpre_ws && B > 0 && k > 0 && n > 0 && B <= 65535 && k <= 65535);
+  if (relu == 2 && mask) return UNETK_E_UNSUPPORTED;   // d y / d acc = m s (1 - s) needs s; y (1 - y) of the masked y is not it
   hipStream_t st = (hipStream_t)stream;
   UNETK_LAUNCH(fc_bwd_pre_kernel, dim3((n + 255) / 256), dim3(256), 0, st, y, mask, dy, dpre_ws, db, B, n, relu);
   UNETK_LAUNCH_CHECK();

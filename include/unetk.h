@@ -365,7 +365,9 @@ int unetk_norm_se_bwd_add_drop(const unetk_norm_desc* d, const void* y, void* dy
  * hidden layers, 0 for the last (activation_fn=None), 2 = tf.nn.sigmoid (the SE gate of GUNet --use_se, GUNet.py:199).  slim.dropout(keep_prob) in training: mask from a counter
  * RNG keyed by (seed, element), kept entries scaled by 1/keep_prob; `mask` ([B][n] floats, 0 or 1/keep_prob,
  * nullable = no dropout) is written by the forward and read by the backward.
- * Backward: dx[B][k] (nullable), dw[k][n], db[n] from dy[B][n] (gated by y > 0 when relu, times the mask). */
+ * Backward: dx[B][k] (nullable), dw[k][n], db[n] from dy[B][n] (gated by y > 0 when relu, times the mask).
+ * relu == 2 together with a mask returns UNETK_E_UNSUPPORTED from both calls before any launch: the backward sees only the
+ * masked y = sigmoid(acc) * m, from which the derivative m * s * (1 - s) cannot be formed (no model drops out a gate). */
 int unetk_fc_fwd(const float* x, const float* w, const float* b, float* y, float* mask, int B, int k, int n,
                  int relu, float keep_prob, uint32_t seed, void* stream);
 int unetk_fc_bwd(const float* x, const float* w, const float* y, const float* mask, const float* dy, float* dx,
