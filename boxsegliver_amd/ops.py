@@ -286,19 +286,33 @@ def side_join():
         _Side.pending = False
 
 
-def _wgrad_on_side(x, dy, bf16, dilation, out):
+# Tests only (tests/stream_delay.py): called as SIDE_LAUNCH_HOOK(kind, side) on the side stream, after its wait for the main
+# stream and before the side work is queued; kind is "conv2d", "conv3d" or "deconv".  None: nothing is called.
+SIDE_LAUNCH_HOOK = None
+
+
+def _on_side(fn, keep, kind):
+    """Queue fn() on the side stream, ordered behind what the current stream holds now.  `keep`: the tensors fn reads or
+    scribbles on, handed to the caching allocator as in use on the side stream.  Every piece of side-stream work goes through
+    here (tests/test_stream_order_host.py); the main stream joins in side_join()."""
     if _Side.stream is None:
-        _Side.stream = torch.cuda.Stream(device=x.device)
+        _Side.stream = torch.cuda.Stream(device=keep[0].device)
     side = _Side.stream
-    side.wait_stream(torch.cuda.current_stream())          # dy has been queued on the main stream
+    side.wait_stream(torch.cuda.current_stream())          # the operands have been queued on the main stream
     with torch.cuda.stream(side):
-        dw = conv3x3_wgrad(x, dy, bf16=bf16, dilation=dilation, out=out, ws_pool=_Side.ws)
-    dy.record_stream(side)
-    x.record_stream(side)
+        if SIDE_LAUNCH_HOOK is not None:
+            SIDE_LAUNCH_HOOK(kind, side)
+        out = fn()
+    for t in keep:
+        t.record_stream(side)
     if not _Side.pending:
         _Side.pending = True
         torch.autograd.Variable._execution_engine.queue_callback(side_join)
-    return dw
+    return out
+
+
+def _wgrad_on_side(x, dy, bf16, dilation, out):
+    return _on_side(lambda: conv3x3_wgrad(x, dy, bf16=bf16, dilation=dilation, out=out, ws_pool=_Side.ws), (dy, x), "conv2d")
 
 
 # 3-D layers: the filter gradient runs on the side stream BESIDE the input gradient.  UNet3D at one or two patches per GPU is a
@@ -316,18 +330,7 @@ SIDE_WGRAD3D_FIRST = os.environ.get("UNETK_SIDE_WGRAD3D_FIRST", "1") == "1"     
 
 
 def _wgrad3d_on_side(x, dy, d, out, precision=0):
-    if _Side.stream is None:
-        _Side.stream = torch.cuda.Stream(device=x.device)
-    side = _Side.stream
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        dw = conv3d_wgrad(x, dy, d, out=out, ws_pool=_Side.ws, precision=precision)
-    dy.record_stream(side)
-    x.record_stream(side)
-    if not _Side.pending:
-        _Side.pending = True
-        torch.autograd.Variable._execution_engine.queue_callback(side_join)
-    return dw
+    return _on_side(lambda: conv3d_wgrad(x, dy, d, out=out, ws_pool=_Side.ws, precision=precision), (dy, x), "conv3d")
 
 
 # ----------------------------------------------------------------------------- in-place parameter gradients
@@ -963,18 +966,8 @@ def _deconv_bwd_call(fn_parts, fn_whole, d, nbytes, args, side_ok, x, tag, what)
     ws = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=xx.device)
     check(fn_parts(ctypes.byref(d), ptr(xx), ptr(wp), ptr(cat), ptr(dcat), ptr(dx), ptr(dw), ptr(db), ptr(ws), nbytes, 1,
                    stream_ptr()), what)
-    if _Side.stream is None:
-        _Side.stream = torch.cuda.Stream(device=xx.device)
-    side = _Side.stream
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        check(fn_parts(ctypes.byref(d), ptr(xx), ptr(wp), ptr(cat), ptr(dcat), ptr(dx), ptr(dw), ptr(db), ptr(ws), nbytes, 2,
-                       stream_ptr()), what)
-    ws.record_stream(side)
-    xx.record_stream(side)
-    if not _Side.pending:
-        _Side.pending = True
-        torch.autograd.Variable._execution_engine.queue_callback(side_join)
+    _on_side(lambda: check(fn_parts(ctypes.byref(d), ptr(xx), ptr(wp), ptr(cat), ptr(dcat), ptr(dx), ptr(dw), ptr(db), ptr(ws),
+                                    nbytes, 2, stream_ptr()), what), (ws, xx), "deconv")
 
 
 def deconv2x2_bwd(x, wp_dgrad, cat, dcat, coff, cout, bf16=False, out_w=None, out_b=None):
