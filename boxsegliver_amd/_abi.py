@@ -77,6 +77,8 @@ _SIGNATURES = {
     "unetk_lits_patch3d_ws_bytes": (c_size_t, [POINTER(Lits3dDesc)]),
     "unetk_lits_patch3d": (c_int, [POINTER(Lits3dDesc), P, P, P, P, P, P, c_size_t, P]),
     "unetk_eval3d_accumulate": (c_int, [POINTER(Lits3dDesc), P, P, c_int, c_int64, c_int, POINTER(c_int32), P, P, P]),
+    "unetk_eval3d_accumulate_w": (c_int, [POINTER(Lits3dDesc), P, P, c_int, c_int64, c_int, POINTER(c_int32), P, P, P, P, P, P]),
+    "unetk_eval3d_finish": (c_int, [P, c_int, c_int, c_int, c_int, P, P, POINTER(c_int32), P, P, P]),
     "unetk_lits_batch": (c_int, [POINTER(LitsDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "unetk_lits_spatial_guide": (c_int, [POINTER(LitsGuideDesc), P, P, P, P, P]),
     "unetk_lits_context": (c_int, [P, c_int64, c_int, P, c_int, c_int, P, P, P, P]),

@@ -343,14 +343,33 @@ bool p3d_valid(const unetk_lits3d_desc* d) {
 // gather: one thread per voxel of the rows' union box, x fastest; it walks the rows IN ORDER (the table row is
 // wave-uniform: scalar loads), so every (voxel, class) has one writer and a fixed summation order -- no atomics.  A wave
 // reads and writes 64 * C consecutive floats of acc; the probs taps of neighbouring threads are neighbours too.
+//
+// WEIGHTED (unetk_eval3d_accumulate_w): every hit is scaled by a separable window weight gz[zw] * lerp(gy) * lerp(gx), the
+// in-plane factors read at the taps and fractions of the probabilities (un-flipped window), and the float volume wsum
+// collects the weights in place of the hit count.  The three tables (D + H + W floats, 2 KB for a 10 x 256 x 256 window)
+// are read from global memory: gz[zw] is uniform over a wave's row of voxels and the gy / gx taps of neighbouring
+// threads are neighbours, so after the first wave they are hits in the CU's vector L1; staging them in LDS would cost
+// every 256-voxel block D + H + W loads and a barrier to save at most five cached loads per hit.
 struct EvalBox {
   int z0, y0, x0, bd, bh, bw;
 };
-template <int C>
+// The weighted kernel states its fp32 arithmetic operation by operation (contraction off, fused multiply-adds spelled out),
+// and states it as the compiler contracts the unweighted kernel's: the three lerps of lits_bilerp as fused multiply-adds,
+// the fraction along y as the fused yw * scale - y0, the fraction along x as the difference of the rounded product.  Next
+// to the weight's products the compiler would otherwise contract the same source differently (it did: 4 ulp), and
+// all-ones tables would not reproduce unetk_eval3d_accumulate bit for bit (tests/test_gpu_eval3d_weighted.py pins that).
+__device__ __forceinline__ float eval3d_bilerp_fma(float tl, float tr, float bl, float br, float lx, float ly) {
+#pragma clang fp contract(off)
+  const float top = __builtin_fmaf(tr - tl, lx, tl), bot = __builtin_fmaf(br - bl, lx, bl);
+  return __builtin_fmaf(bot - top, ly, top);
+}
+template <int C, bool WEIGHTED>
 __global__ __launch_bounds__(256) void eval3d_accumulate_kernel(unetk_lits3d_desc d, const int32_t* __restrict__ tab,
                                                                 const float* __restrict__ probs, int64_t case_base,
                                                                 int case_depth, EvalBox e, float* __restrict__ acc,
-                                                                int32_t* __restrict__ cnt) {
+                                                                int32_t* __restrict__ cnt, float* __restrict__ wsum,
+                                                                const float* __restrict__ gz, const float* __restrict__ gy,
+                                                                const float* __restrict__ gx) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t area = (int64_t)e.bh * e.bw;
   if (i >= area * e.bd) return;
@@ -363,6 +382,8 @@ __global__ __launch_bounds__(256) void eval3d_accumulate_kernel(unetk_lits3d_des
 #pragma unroll
   for (int c = 0; c < C; ++c) sum[c] = a[c];
   int hits = 0;
+  float wtot = 0.f;
+  if constexpr (WEIGHTED) wtot = wsum[vox];
   const int win = d.D * d.H * d.W * C;                       // < 2^31: checked by the entry point
   for (int n = 0; n < d.N; ++n) {
     const int32_t* t = tab + (int64_t)n * TW;
@@ -381,23 +402,78 @@ __global__ __launch_bounds__(256) void eval3d_accumulate_kernel(unetk_lits3d_des
     const float* p = probs + (int64_t)n * win;
     const int ra = (zr * d.H + ya) * d.W, rb = (zr * d.H + yb2) * d.W;
     const float *tl = p + (ra + xa) * C, *tr = p + (ra + xb) * C, *bl = p + (rb + xa) * C, *br = p + (rb + xb) * C;
+    if constexpr (WEIGHTED) {
+#pragma clang fp contract(off)
+      const float sy = lits_ac_scale(d.H, b.ch), sx = lits_ac_scale(d.W, b.cw);
+      const float fy = __builtin_fmaf((float)yw, sy, -(float)ty.i0), fx = (float)xw * sx - (float)tx.i0;
+      // the weight: lits_bilerp's lerp form a + f (b - a), the tap itself at fraction 0
+      const float wy = gy[y0] + (gy[ty.i1] - gy[y0]) * fy, wx = gx[x0] + (gx[tx.i1] - gx[x0]) * fx;
+      const float w = gz[zw] * wy * wx;
 #pragma unroll
-    for (int c = 0; c < C; ++c) sum[c] += lits_bilerp(tl[c], tr[c], bl[c], br[c], tx.f, ty.f);
+      for (int c = 0; c < C; ++c) sum[c] = __builtin_fmaf(w, eval3d_bilerp_fma(tl[c], tr[c], bl[c], br[c], fx, fy), sum[c]);
+      wtot += w;
+    } else {
+#pragma unroll
+      for (int c = 0; c < C; ++c) sum[c] += lits_bilerp(tl[c], tr[c], bl[c], br[c], tx.f, ty.f);
+    }
     ++hits;
   }
   if (hits == 0) return;
 #pragma unroll
   for (int c = 0; c < C; ++c) a[c] = sum[c];
-  cnt[vox] += hits;
+  if constexpr (WEIGHTED)
+    wsum[vox] = wtot;
+  else
+    cnt[vox] += hits;
+}
+
+// The end of a case (unetk_eval3d_finish): one thread per voxel of the volume.  A voxel is covered when its weight (wsum or
+// cnt) is positive; a covered voxel of the box `e` gets the argmax of its C sums, strict > so that the lowest index wins ties
+// (as head_predict_kernel, csrc/head.hip), every other voxel class 0.  Voxels of `e` without cover are counted: one integer
+// atomic per wave that has any (the idiom of lc_flatten_kernel, csrc/evalvol.hip) -- integer adds commute, the count is
+// reproducible.
+__global__ __launch_bounds__(256) void eval3d_finish_kernel(const float* __restrict__ acc, int C, int64_t nvox, int src_h,
+                                                            int src_w, const float* __restrict__ wsum,
+                                                            const int32_t* __restrict__ cnt, EvalBox e,
+                                                            uint8_t* __restrict__ pred, int32_t* __restrict__ uncovered) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  bool missing = false;
+  if (i < nvox) {
+    const int64_t plane = (int64_t)src_h * src_w;
+    const int z = (int)(i / plane), r = (int)(i - z * plane);
+    const int y = r / src_w, x = r - y * src_w;
+    const bool inside = z >= e.z0 && z < e.z0 + e.bd && y >= e.y0 && y < e.y0 + e.bh && x >= e.x0 && x < e.x0 + e.bw;
+    const bool covered = wsum ? wsum[i] > 0.f : cnt[i] > 0;
+    int bi = 0;
+    if (inside && covered) {
+      const float* a = acc + i * C;
+      float best = a[0];
+      for (int k = 1; k < C; ++k) {
+        const float v = a[k];
+        if (v > best) {
+          best = v;
+          bi = k;
+        }
+      }
+    }
+    missing = inside && !covered;
+    pred[i] = (uint8_t)bi;
+  }
+  const unsigned long long any = __ballot(missing);
+  if (missing && (int)__lane_id() == __ffsll((long long)any) - 1) atomicAdd(uncovered, __popcll(any));
 }
 
 }  // namespace
 
-extern "C" int unetk_eval3d_accumulate(const unetk_lits3d_desc* d, const int32_t* sample_tab, const float* probs, int C,
-                                       int64_t case_base, int case_depth, const int32_t box[6], float* acc, int32_t* cnt,
-                                       void* stream) {
-  UNETK_REQUIRE(p3d_valid(d) && sample_tab && probs && box && acc && cnt && C >= 1 && C <= 8);
+// Both accumulate entry points: cnt for the plain one, wsum and the three tables for the weighted one.
+static int eval3d_accumulate(const unetk_lits3d_desc* d, const int32_t* sample_tab, const float* probs, int C, int64_t case_base,
+                             int case_depth, const int32_t box[6], float* acc, int32_t* cnt, float* wsum, const float* gz,
+                             const float* gy, const float* gx, void* stream) {
+  const bool weighted = cnt == nullptr;
+  UNETK_REQUIRE(p3d_valid(d) && sample_tab && probs && box && acc && C >= 1 && C <= 8);
   UNETK_REQUIRE(((((uintptr_t)sample_tab) | ((uintptr_t)probs) | ((uintptr_t)acc) | ((uintptr_t)cnt)) & 3u) == 0);
+  UNETK_REQUIRE(!weighted || (wsum && gz && gy && gx &&
+                              ((((uintptr_t)wsum) | ((uintptr_t)gz) | ((uintptr_t)gy) | ((uintptr_t)gx)) & 3u) == 0));
   UNETK_REQUIRE(case_base >= 0 && case_depth > 0 && case_base + case_depth <= d->n_slices);
   UNETK_REQUIRE(0 <= box[0] && box[0] < box[1] && box[1] <= case_depth && 0 <= box[2] && box[2] < box[3] && box[3] <= d->src_h &&
                 0 <= box[4] && box[4] < box[5] && box[5] <= d->src_w);
@@ -409,12 +485,48 @@ extern "C" int unetk_eval3d_accumulate(const unetk_lits3d_desc* d, const int32_t
   hipStream_t st = (hipStream_t)stream;
 #define EVAL3D_CASE(c)                                                                                                      \
   case c:                                                                                                                   \
-    UNETK_LAUNCH(eval3d_accumulate_kernel<c>, grid, dim3(256), 0, st, *d, sample_tab, probs, case_base, case_depth, e, acc, cnt); \
+    if (weighted)                                                                                                           \
+      UNETK_LAUNCH((eval3d_accumulate_kernel<c, true>), grid, dim3(256), 0, st, *d, sample_tab, probs, case_base, case_depth, e, \
+                   acc, cnt, wsum, gz, gy, gx);                                                                             \
+    else                                                                                                                    \
+      UNETK_LAUNCH((eval3d_accumulate_kernel<c, false>), grid, dim3(256), 0, st, *d, sample_tab, probs, case_base, case_depth, e, \
+                   acc, cnt, wsum, gz, gy, gx);                                                                             \
     break;
   switch (C) {
     EVAL3D_CASE(1) EVAL3D_CASE(2) EVAL3D_CASE(3) EVAL3D_CASE(4) EVAL3D_CASE(5) EVAL3D_CASE(6) EVAL3D_CASE(7) EVAL3D_CASE(8)
   }
 #undef EVAL3D_CASE
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
+extern "C" int unetk_eval3d_accumulate(const unetk_lits3d_desc* d, const int32_t* sample_tab, const float* probs, int C,
+                                       int64_t case_base, int case_depth, const int32_t box[6], float* acc, int32_t* cnt,
+                                       void* stream) {
+  UNETK_REQUIRE(cnt);
+  return eval3d_accumulate(d, sample_tab, probs, C, case_base, case_depth, box, acc, cnt, nullptr, nullptr, nullptr, nullptr,
+                           stream);
+}
+
+extern "C" int unetk_eval3d_accumulate_w(const unetk_lits3d_desc* d, const int32_t* sample_tab, const float* probs, int C,
+                                         int64_t case_base, int case_depth, const int32_t box[6], const float* gz,
+                                         const float* gy, const float* gx, float* acc, float* wsum, void* stream) {
+  UNETK_REQUIRE(wsum && gz && gy && gx);
+  return eval3d_accumulate(d, sample_tab, probs, C, case_base, case_depth, box, acc, nullptr, wsum, gz, gy, gx, stream);
+}
+
+extern "C" int unetk_eval3d_finish(const float* acc, int C, int depth, int src_h, int src_w, const float* wsum,
+                                   const int32_t* cnt, const int32_t box[6], uint8_t* pred, int32_t* uncovered, void* stream) {
+  UNETK_REQUIRE(acc && box && pred && uncovered && C >= 1 && C <= 8 && depth > 0 && src_h > 0 && src_w > 0);
+  UNETK_REQUIRE((wsum != nullptr) != (cnt != nullptr));                   // exactly one kind of weight
+  UNETK_REQUIRE(((((uintptr_t)acc) | ((uintptr_t)wsum) | ((uintptr_t)cnt) | ((uintptr_t)uncovered)) & 3u) == 0);
+  UNETK_REQUIRE(0 <= box[0] && box[0] < box[1] && box[1] <= depth && 0 <= box[2] && box[2] < box[3] && box[3] <= src_h &&
+                0 <= box[4] && box[4] < box[5] && box[5] <= src_w);
+  const int64_t nvox = (int64_t)depth * src_h * src_w;
+  if (nvox >= ((int64_t)1 << 31)) return UNETK_E_UNSUPPORTED;             // the limit of unetk_eval3d_accumulate's volume
+  const EvalBox e = {box[0], box[2], box[4], box[1] - box[0], box[3] - box[2], box[5] - box[4]};
+  UNETK_LAUNCH(eval3d_finish_kernel, dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, (hipStream_t)stream, acc, C, nvox, src_h,
+               src_w, wsum, cnt, e, pred, uncovered);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }

@@ -19,8 +19,11 @@ with zero slices (the reference would index with a negative start), and a patch 
 zeros (TensorFlow's moments of an empty tensor are NaN).
 
 Offline, `input_fn_eval` tiles every case of the validation fold with windows cut as `eval_online` cuts them (window_starts,
-eval_tables) for the sliding-window evaluator, `EvaluateVolume.run_3d` (--eval_in_patches)."""
+eval_tables) for the sliding-window evaluator, `EvaluateVolume.run_3d` (--eval_in_patches).  Two options
+of that evaluation live here too: the per-axis Gaussian window tables (window_weights, --eval_window_weight gaussian) and
+the box of a saved coarse prediction to which the windows are restricted (prediction_box, --eval_box_from)."""
 import math
+from pathlib import Path
 
 import numpy as np
 import torch
@@ -33,6 +36,9 @@ EVAL_ZOOM = 1.125                  # gen_batch(train=False): zoom = (1.125, 1.12
 GAMMA_RANGE = (0.7, 1.5)           # data_processing :405
 GAMMA_P = 0.3
 LABEL_MAPS = (("Liver",), ("Liver", "Tumor"))
+WINDOW_WEIGHTS = ("uniform", "gaussian")
+MIN_WINDOW_WEIGHT = 1e-30          # the smallest weight of a window, gz[0] * gy[0] * gx[0] in float32, may not fall below this
+DEFAULT_BOX_MARGIN = (0, 25, 25)   # (z, y, x): padding_z / padding of the 2-D --eval_in_patches (lits.get_dataset_for_eval_patches)
 (COL_BASE, COL_DEPTH, COL_CZ, COL_CY, COL_CX, COL_CH, COL_CW, COL_FLIP_LR, COL_FLIP_UD, COL_FLIP_FB, COL_GAMMA, COL_FORCED,
  COL_K) = range(13)
 
@@ -45,6 +51,14 @@ def add_arguments(parser):
     parser.add_argument("--seed", type=int, default=1234)
     parser.add_argument("--eval_overlap", type=float, default=0.5,
                         help="--mode eval --eval_in_patches: overlap of neighbouring windows as a share of the window, in [0, 1)")
+    parser.add_argument("--eval_window_weight", type=str, default="uniform", choices=WINDOW_WEIGHTS,
+                        help="--eval_in_patches: how a window's voxels count in the average; gaussian weights its centre")
+    parser.add_argument("--eval_window_sigma", type=float, default=0.125,
+                        help="gaussian: the standard deviation as a share of the window's extent, per axis")
+    parser.add_argument("--eval_box_from", type=str, default=None, metavar="DIR",
+                        help="--eval_in_patches: tile only the box of predict-<case>.nii.gz in DIR (a --save_predict output)")
+    parser.add_argument("--eval_box_margin", type=int, nargs=3, default=DEFAULT_BOX_MARGIN, metavar=("Z", "Y", "X"),
+                        help="voxels the --eval_box_from box is grown by on each side, per axis")
 
 
 def check_args(args):
@@ -53,6 +67,19 @@ def check_args(args):
     overlap = float(getattr(args, "eval_overlap", 0.5))
     if not 0.0 <= overlap < 1.0:                          # also refuses NaN
         raise ValueError("--eval_overlap must satisfy 0 <= v < 1, got {}".format(overlap))
+    weight = getattr(args, "eval_window_weight", "uniform")
+    if weight not in WINDOW_WEIGHTS:
+        raise ValueError("--eval_window_weight must be one of {}, got {}".format(", ".join(WINDOW_WEIGHTS), weight))
+    sigma = float(getattr(args, "eval_window_sigma", 0.125))
+    if not sigma > 0.0:                                   # also refuses NaN
+        raise ValueError("--eval_window_sigma must be > 0, got {}".format(sigma))
+    if weight == "gaussian":
+        window_weights((int(args.im_depth), int(args.im_height), int(args.im_width)), sigma)     # refuses an underflow
+    margin = getattr(args, "eval_box_margin", DEFAULT_BOX_MARGIN)
+    if len(margin) != 3 or any(int(m) < 0 for m in margin):
+        raise ValueError("--eval_box_margin takes three voxel counts >= 0 (z y x), got {}".format(list(margin)))
+    if margin is not DEFAULT_BOX_MARGIN and getattr(args, "eval_box_from", None) is None:       # argparse keeps the default object
+        raise ValueError("--eval_box_margin grows the box of --eval_box_from, which is not given")
     return label_map(args.classes)
 
 
@@ -281,19 +308,82 @@ def eval_windows(src_hw, shape):
     return int(shape[0]), min(max(ch, 1), int(src_hw[0])), min(max(cw, 1), int(src_hw[1]))
 
 
-def eval_tables(case, store, shape, overlap, variants, batch_size):
+def window_weights(shape, sigma):
+    """--eval_window_weight gaussian: (gz [D], gy [H], gx [W]) float32, the weight of a window's voxel per axis.  Axis of n
+    voxels: exp(-((i - (n - 1) / 2) / (sigma n))^2 / 2) in float64, divided by its maximum, rounded to float32; built as
+    one half and its mirror, so g[i] == g[n - 1 - i] bit for bit.  The smallest weight of a window, gz[0] gy[0] gx[0]
+    formed in float32, must stay >= MIN_WINDOW_WEIGHT: a voxel that only such corners cover would otherwise carry a sum
+    and a weight of 0 (or denormals) and count as not covered."""
+    sigma = float(sigma)
+    if not sigma > 0.0:
+        raise ValueError("--eval_window_sigma must be > 0, got {}".format(sigma))
+    tables = []
+    for n in (int(v) for v in shape):
+        i = np.arange((n + 1) // 2, dtype=np.float64)
+        half = np.exp(-0.5 * ((i - (n - 1) / 2.0) / (sigma * n)) ** 2)
+        half = (half / half.max()).astype(np.float32)
+        tables.append(np.concatenate([half, half[:n // 2][::-1]]))
+    smallest = np.float32(tables[0][0] * tables[1][0]) * tables[2][0]
+    if not smallest >= np.float32(MIN_WINDOW_WEIGHT):
+        raise ValueError("--eval_window_sigma {} is too small for windows of {} x {} x {}: the corner weight {:.3g} underflows "
+                         "(it must be >= {:g})".format(sigma, shape[0], shape[1], shape[2], float(smallest), MIN_WINDOW_WEIGHT))
+    return tuple(tables)
+
+
+def prediction_box(directory, case, depth, src_hw, margin=DEFAULT_BOX_MARGIN):
+    """--eval_box_from: (z0, z1, y0, y1, x0, x1), the box of the foreground of `<directory>/predict-<PID>.nii.gz` (what
+    --save_predict writes, voxel for voxel on the case's volume file), grown by margin = (z, y, x) and clamped to the case.
+    The file is read with the volume's mirror rule (nii_kits.read_lits("vol"): cases 28..47), so the array lines up with
+    the resident store.  A missing file, another shape than (depth, src_h, src_w) or an empty mask raise: there is no
+    fallback to the whole volume."""
+    from . import nii_kits
+    pid = int(case["PID"]) if isinstance(case, dict) else int(case)
+    path = Path(directory) / "predict-{}.nii.gz".format(pid)
+    if not path.exists():
+        raise FileNotFoundError("--eval_box_from: {} does not exist".format(path))
+    _, mask = nii_kits.read_nii(path, out_dtype=np.uint8, special=28 <= pid < 48)
+    want = (int(depth), int(src_hw[0]), int(src_hw[1]))
+    if tuple(mask.shape) != want:
+        raise ValueError("--eval_box_from: {} holds a volume of shape {}, case {} has {}".format(path, tuple(mask.shape), pid, want))
+    box = []
+    for axis, (extent, grow) in enumerate(zip(want, margin)):
+        hit = np.flatnonzero((mask > 0).any(axis=tuple(a for a in range(3) if a != axis)))
+        if len(hit) == 0:
+            raise ValueError("--eval_box_from: {} predicts nothing, case {} has no box".format(path, pid))
+        box += [max(int(hit[0]) - int(grow), 0), min(int(hit[-1]) + 1 + int(grow), extent)]
+    return tuple(box)
+
+
+def box_starts(extent, window, overlap, lo, hi):
+    """window_starts for the part [lo, hi) of an axis: the one start 0 on an axis no longer than the window; a part no
+    longer than the window gets ONE window centred on it and clamped to the axis; else the part is tiled like an axis of
+    its own.  [0, extent) gives window_starts(extent, window, overlap)."""
+    extent, window, lo, hi = int(extent), int(window), int(lo), int(hi)
+    if extent <= window:
+        return [0]
+    if hi - lo <= window:
+        return [min(max(lo - (window - (hi - lo)) // 2, 0), extent - window)]
+    return [lo + s for s in window_starts(hi - lo, window, overlap)]
+
+
+def eval_tables(case, store, shape, overlap, variants, batch_size, box=None):
     """The sample tables (PatchSampler.table's layout, int32 [n, 16]) that tile ONE case with windows, in batches of
     `batch_size` rows, the last one short.  Windows are cut as `eval_online` cuts them (zoom EVAL_ZOOM, no gamma, not
-    forced) and cover the whole volume -- not the ground-truth liver box: no label information enters the prediction.
+    forced) and cover the whole volume -- not the ground-truth liver box: no label information enters the prediction --
+    or, with box = (z0, z1, y0, y1, x0, x1) (prediction_box), that box: box_starts per axis.
     A window that starts at `a` is centred on a + window // 2, from which the kernels' volume_crop clamp gives back `a`.
     Every window is followed by its mirror variants: the same row with the flip columns set."""
     pid, depth = int(case["PID"]), int(case["size"][0])
     src_h, src_w = int(store.im.shape[1]), int(store.im.shape[2])
     d, ch, cw = eval_windows((src_h, src_w), shape)
+    if box is None:
+        box = (0, depth, 0, src_h, 0, src_w)
+    elif not (0 <= box[0] < box[1] <= depth and 0 <= box[2] < box[3] <= src_h and 0 <= box[4] < box[5] <= src_w):
+        raise ValueError("the box {} is empty or leaves case {} ({} x {} x {})".format(tuple(box), pid, depth, src_h, src_w))
     rows = []
-    for z in window_starts(depth, d, overlap):
-        for y in window_starts(src_h, ch, overlap):
-            for x in window_starts(src_w, cw, overlap):
+    for z in box_starts(depth, d, overlap, box[0], box[1]):
+        for y in box_starts(src_h, ch, overlap, box[2], box[3]):
+            for x in box_starts(src_w, cw, overlap, box[4], box[5]):
                 for flips in variants:
                     row = np.zeros(_abi.LITS3D_TAB_COLS, dtype=np.int32)
                     row[COL_BASE], row[COL_DEPTH] = int(store.offset[pid]), depth
@@ -326,7 +416,8 @@ def input_fn_eval(mode, params):
     """Offline evaluation (--mode eval) in sliding windows, --eval_in_patches.  The validation fold is
     loaded into the resident store exactly as input_fn("eval_online") loads it (same cache key).  Per case the generator
     yields its window tables (host int32 [n, 16], eval_tables) and then one end-of-case item
-    (None, dict(case, base, depth, store)).  Labels never leave the device: the evaluator takes them from store.lb.
+    (None, dict(case, base, depth, store)), which with --eval_box_from also carries `box`, the box the windows were
+    restricted to (prediction_box).  Labels never leave the device: the evaluator takes them from store.lb.
     Without the flag: the reference's other way, one forward over the whole case (entry/main_eval_3d.py), which is not built."""
     args = params["args"]
     if not getattr(args, "eval_in_patches", False):
@@ -354,8 +445,13 @@ def _eval_cases(args, params):
     bs = distribution_utils.per_device_batch_size(args.batch_size, args.num_gpus)
     shape = (int(args.im_depth), int(args.im_height), int(args.im_width))
     variants = mirror_variants(args)
+    box_from = getattr(args, "eval_box_from", None)
     for case in cases:
-        for tab in eval_tables(case, store, shape, float(getattr(args, "eval_overlap", 0.5)), variants, bs):
+        pid, depth = int(case["PID"]), int(case["size"][0])
+        end = dict(case=str(pid), base=int(store.offset[pid]), depth=depth, store=store)
+        box = None
+        if box_from is not None:
+            box = end["box"] = prediction_box(box_from, case, depth, store.im.shape[1:], getattr(args, "eval_box_margin", DEFAULT_BOX_MARGIN))
+        for tab in eval_tables(case, store, shape, float(getattr(args, "eval_overlap", 0.5)), variants, bs, box):
             yield tab, None
-        pid = int(case["PID"])
-        yield None, dict(case=str(pid), base=int(store.offset[pid]), depth=int(case["size"][0]), store=store)
+        yield None, end

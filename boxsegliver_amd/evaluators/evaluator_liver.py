@@ -459,7 +459,12 @@ class EvaluateVolume(EvaluateBase):
         probabilities back to their crops and ADDS them into the case's accumulator at source resolution (the reference
         assigns but counts: its last window is divided by the coverage).  At the end of a case: argmax over the sums (the
         division by a positive count does not change it), labels from the resident store, and the usual post-processing
-        and metrics on the device.  Nothing inside a case synchronises the host; the coverage count is read once per case."""
+        and metrics on the device.  Nothing inside a case synchronises the host; the coverage count is read once per case.
+        --eval_window_weight gaussian: the windows are added with the per-axis tables of lits3d.window_weights
+        (`unetk_eval3d_accumulate_w`, a float weight volume for the count).  --eval_box_from: the case's windows tile a box only
+        (the end-of-case item carries it) and everything outside it is class 0.  With either flag `unetk_eval3d_finish` is
+        the argmax inside the box (the whole case without --eval_box_from) and counts the box's voxels without cover; the
+        count is read where the plain path reads cnt.min()."""
         from ..data import lits, lits3d
         cfg = self.config
         model = self._model()
@@ -469,10 +474,13 @@ class EvaluateVolume(EvaluateBase):
         shape = (int(cfg.im_depth), int(cfg.im_height), int(cfg.im_width))
         lab_max, _ = lits3d.label_map(cfg.classes)
         params = self.params
+        gaussian = getattr(cfg, "eval_window_weight", "uniform") == "gaussian"
+        boxed = getattr(cfg, "eval_box_from", None) is not None
+        host_tables = lits3d.window_weights(shape, getattr(cfg, "eval_window_sigma", 0.125)) if gaussian else None
 
         def run_pred():
             restored = False
-            acc = cnt = None
+            acc = cnt = tables = None
             for tab, end in input_fn(mode, params):
                 store = params[("lits_store", False)][0]            # input_fn_eval made it resident before its first item
                 if tab is not None:
@@ -490,16 +498,26 @@ class EvaluateVolume(EvaluateBase):
                     src_hw = tuple(store.im.shape[1:])
                     if acc is None:
                         acc = torch.zeros((depth,) + src_hw + (prob.shape[-1],), dtype=torch.float32, device=store.device)
-                        cnt = torch.zeros((depth,) + src_hw, dtype=torch.int32, device=store.device)
-                    ops.eval3d_accumulate(prob, dtab, shape, base, depth, lits3d.table_box(tab, shape, depth, src_hw), acc, cnt,
-                                          store.im, host_tab=tab)
+                        cnt = torch.zeros((depth,) + src_hw, dtype=torch.float32 if gaussian else torch.int32, device=store.device)
+                    box = lits3d.table_box(tab, shape, depth, src_hw)
+                    if gaussian:
+                        if tables is None:                              # once per run
+                            tables = lits.upload_pinned(list(host_tables), store.device)
+                        ops.eval3d_accumulate_w(prob, dtab, shape, base, depth, box, tables, acc, cnt, store.im, host_tab=tab)
+                    else:
+                        ops.eval3d_accumulate(prob, dtab, shape, base, depth, box, acc, cnt, store.im, host_tab=tab)
                 else:
                     if acc is None or end["depth"] != acc.shape[0]:
                         raise RuntimeError("case {} ended without windows of its own".format(end["case"]))
-                    amax, _ = ops.head_predict(acc.view(-1, acc.shape[-1]), acc.shape[-1], want_preds=False)
                     lb = end["store"].lb[end["base"]:end["base"] + end["depth"]]
                     labels = torch.clamp(torch.div(lb, lits.LB_SCALE, rounding_mode="floor"), max=lab_max).to(torch.uint8)
-                    yield end["case"], labels, amax.view(cnt.shape), cnt
+                    if gaussian or boxed:
+                        uncovered = torch.zeros(1, dtype=torch.int32, device=acc.device)
+                        whole = (0, acc.shape[0], 0, acc.shape[1], 0, acc.shape[2])
+                        yield end["case"], labels, ops.eval3d_finish(acc, cnt, end.get("box", whole), uncovered), uncovered
+                    else:
+                        amax, _ = ops.head_predict(acc.view(-1, acc.shape[-1]), acc.shape[-1], want_preds=False)
+                        yield end["case"], labels, amax.view(cnt.shape), cnt
                     acc = cnt = None
 
         n_cases = cases if cases is not None else getattr(cfg, "eval_num", -1)
@@ -513,7 +531,8 @@ class EvaluateVolume(EvaluateBase):
             raise NotImplementedError("the sliding-window 3-D evaluation scores class predictions (--pred_type pred)")
         counter = 0
         for case, labels, volume, cnt in predicts:
-            if int(cnt.min().item()) <= 0:
+            # cnt: the coverage volume [depth, src_h, src_w] of the plain path, or the word [1] eval3d_finish counted into
+            if (int(cnt.item()) != 0) if cnt.dim() == 1 else (int(cnt.min().item()) <= 0):
                 raise RuntimeError("--eval_in_patches: windows do not cover every voxel of case {}".format(case))
             depth, src_h, src_w = (int(v) for v in volume.shape)
             yield (case, labels) + self._maybe_save_case(case, volume, (0, 0, 0, src_w - 1, src_h - 1, depth - 1), dtype,

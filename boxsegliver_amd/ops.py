@@ -1572,15 +1572,10 @@ def lits_patch3d(slices, seg_slices, sample_tab, shape, training, lab_max=2, im_
     return images, labels
 
 
-def eval3d_accumulate(probs, sample_tab, shape, case_base, case_depth, box, acc, cnt, slices, host_tab=None):
-    """Window probabilities back into ONE case at source resolution (unetk_eval3d_accumulate; DESIGN.md 7.3.4): probs f32
-    [N, D, H, W, C] of the windows `lits_patch3d(..., training=False)` cut for sample_tab int32 [N, 16]; acc f32
-    [depth, src_h, src_w, C] and cnt int32 [depth, src_h, src_w] are updated IN PLACE (the caller zeroes them before the
-    case's first batch); box = (z0, z1, y0, y1, x0, x1), the union of the rows' crop boxes; slices: the resident store the
-    windows were cut from (its extent enters the crop box).  host_tab: the table's host copy, when the caller has it -- the
-    rows' (base, depth) are then checked against the case here (a device table is not read back).  Current stream; no
-    host synchronisation."""
-    _require_cuda(probs, sample_tab, acc, cnt, slices)
+def _eval3d_accumulate_args(name, probs, sample_tab, shape, case_base, case_depth, box, acc, weight, weight_dtype, slices,
+                            host_tab):
+    """The checks the two accumulate wrappers share -> (desc, c, cbox, voxels of the box)."""
+    _require_cuda(probs, sample_tab, acc, weight, slices)
     d, h, w = (int(v) for v in shape)
     assert sample_tab.dtype == torch.int32 and sample_tab.dim() == 2 and sample_tab.shape[1] == _abi.LITS3D_TAB_COLS
     assert sample_tab.is_contiguous()
@@ -1590,21 +1585,73 @@ def eval3d_accumulate(probs, sample_tab, shape, case_base, case_depth, box, acc,
     assert slices.dim() == 3
     vol = (int(case_depth), int(slices.shape[1]), int(slices.shape[2]))
     assert acc.dtype == torch.float32 and tuple(acc.shape) == vol + (c,) and acc.is_contiguous()
-    assert cnt.dtype == torch.int32 and tuple(cnt.shape) == vol and cnt.is_contiguous()
+    assert weight.dtype == weight_dtype and tuple(weight.shape) == vol and weight.is_contiguous()
     if host_tab is not None:
         rows = torch.as_tensor(host_tab)
         if tuple(rows.shape) != (n, _abi.LITS3D_TAB_COLS) or bool((rows[:, 0] != int(case_base)).any()) or \
                 bool((rows[:, 1] != int(case_depth)).any()):
-            raise _abi.UnetkError("eval3d_accumulate: every row must carry the case's (base, depth) = ({}, {})".format(
-                int(case_base), int(case_depth)))
+            raise _abi.UnetkError("{}: every row must carry the case's (base, depth) = ({}, {})".format(
+                name, int(case_base), int(case_depth)))
     desc = lits3d_desc(slices, n, shape, False)
     cbox = (ctypes.c_int32 * 6)(*(int(v) for v in box))
+    return desc, c, cbox, (cbox[1] - cbox[0]) * (cbox[3] - cbox[2]) * (cbox[5] - cbox[4])
+
+
+def eval3d_accumulate(probs, sample_tab, shape, case_base, case_depth, box, acc, cnt, slices, host_tab=None):
+    """Window probabilities back into ONE case at source resolution (unetk_eval3d_accumulate; DESIGN.md 7.3.4): probs f32
+    [N, D, H, W, C] of the windows `lits_patch3d(..., training=False)` cut for sample_tab int32 [N, 16]; acc f32
+    [depth, src_h, src_w, C] and cnt int32 [depth, src_h, src_w] are updated IN PLACE (the caller zeroes them before the
+    case's first batch); box = (z0, z1, y0, y1, x0, x1), the union of the rows' crop boxes; slices: the resident store the
+    windows were cut from (its extent enters the crop box).  host_tab: the table's host copy, when the caller has it -- the
+    rows' (base, depth) are then checked against the case here (a device table is not read back).  Current stream; no
+    host synchronisation."""
+    desc, c, cbox, nvox = _eval3d_accumulate_args("eval3d_accumulate", probs, sample_tab, shape, case_base, case_depth, box, acc,
+                                                  cnt, torch.int32, slices, host_tab)
     # algorithmic bytes: the windows read once, the box of acc read and written, the box of cnt read and written
-    nvox = (cbox[1] - cbox[0]) * (cbox[3] - cbox[2]) * (cbox[5] - cbox[4])
     with _timed_hbm("eval3d_accumulate", probs, 1, nvox * 8 * (c + 1)):
         check(_abi.lib().unetk_eval3d_accumulate(ctypes.byref(desc), ptr(sample_tab), ptr(probs), c, int(case_base),
                                                  int(case_depth), cbox, ptr(acc), ptr(cnt), stream_ptr()), "eval3d_accumulate")
     return acc, cnt
+
+
+def eval3d_accumulate_w(probs, sample_tab, shape, case_base, case_depth, box, tables, acc, wsum, slices, host_tab=None):
+    """eval3d_accumulate with centre-weighted windows (unetk_eval3d_accumulate_w; --eval_window_weight gaussian): tables =
+    (gz f32 [D], gy f32 [H], gx f32 [W]) device vectors (data/lits3d.window_weights); wsum f32 [depth, src_h, src_w] takes
+    the place of cnt and collects the weights.  Everything else as eval3d_accumulate."""
+    desc, c, cbox, nvox = _eval3d_accumulate_args("eval3d_accumulate_w", probs, sample_tab, shape, case_base, case_depth, box, acc,
+                                                  wsum, torch.float32, slices, host_tab)
+    gz, gy, gx = tables
+    _require_cuda(gz, gy, gx)
+    for g, n in zip((gz, gy, gx), shape):
+        assert g.dtype == torch.float32 and tuple(g.shape) == (int(n),) and g.is_contiguous()
+    # algorithmic bytes: as eval3d_accumulate with wsum for cnt, and the three tables once
+    with _timed_hbm("eval3d_accumulate_w", probs, 1, nvox * 8 * (c + 1) + 4 * (gz.numel() + gy.numel() + gx.numel())):
+        check(_abi.lib().unetk_eval3d_accumulate_w(ctypes.byref(desc), ptr(sample_tab), ptr(probs), c, int(case_base),
+                                                   int(case_depth), cbox, ptr(gz), ptr(gy), ptr(gx), ptr(acc), ptr(wsum),
+                                                   stream_ptr()), "eval3d_accumulate_w")
+    return acc, wsum
+
+
+def eval3d_finish(acc, weight, box, uncovered):
+    """The end of a sliding-window case (unetk_eval3d_finish): acc f32 [depth, src_h, src_w, C]; weight: wsum f32 or cnt
+    int32 [depth, src_h, src_w]; box = (z0, z1, y0, y1, x0, x1), the part of the case the windows tiled.  Returns pred uint8
+    [depth, src_h, src_w]: the argmax over the C sums (lowest index on ties, as head_predict) where the weight is positive
+    inside the box, else 0.  uncovered int32 [1] (zeroed by the caller) is raised by the number of voxels of the box
+    without cover; it is NOT read here.  Current stream."""
+    _require_cuda(acc, weight, uncovered)
+    assert acc.dtype == torch.float32 and acc.dim() == 4 and acc.is_contiguous()
+    assert weight.dtype in (torch.float32, torch.int32) and tuple(weight.shape) == tuple(acc.shape[:3]) and weight.is_contiguous()
+    assert uncovered.dtype == torch.int32 and uncovered.numel() >= 1
+    depth, src_h, src_w, c = (int(v) for v in acc.shape)
+    pred = torch.empty((depth, src_h, src_w), dtype=torch.uint8, device=acc.device)
+    cbox = (ctypes.c_int32 * 6)(*(int(v) for v in box))
+    is_w = weight.dtype == torch.float32
+    # algorithmic bytes: acc and the weight read once, pred written
+    with _timed_hbm("eval3d_finish", acc, 1, weight.numel() * 5):
+        check(_abi.lib().unetk_eval3d_finish(ptr(acc), c, depth, src_h, src_w, ptr(weight) if is_w else None,
+                                             None if is_w else ptr(weight), cbox, ptr(pred), ptr(uncovered), stream_ptr()),
+              "eval3d_finish")
+    return pred
 
 
 def adam_step(p, g, m, v, lr_t, beta1, beta2, eps, gscale=1.0, l2=0.0, decoupled_wd=0.0):

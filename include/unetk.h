@@ -754,6 +754,25 @@ int unetk_lits_patch3d(const unetk_lits3d_desc* d, const uint16_t* slices, const
 int unetk_eval3d_accumulate(const unetk_lits3d_desc* d, const int32_t* sample_tab, const float* probs, int C,
                             int64_t case_base, int case_depth, const int32_t box[6], float* acc, int32_t* cnt, void* stream);
 
+/* The same gather with centre-weighted windows (additive to ABI 10).  gz f32 [D], gy f32 [H], gx f32 [W]: the window's weight
+ * per axis, indexed in the UN-FLIPPED window; wsum f32 [depth,src_h,src_w] takes the place of cnt.  Per hit
+ *   w = gz[z - z1] * lerp(gy[y0], gy[y1], fy) * lerp(gx[x0], gx[x1], fx)      (lerp(a, b, f) = a + f (b - a))
+ * with the taps and fractions of the probabilities' resize;  acc[z,y,x,c] += w * (the resized probability);  wsum[z,y,x] += w.
+ * Same order, one writer per (voxel, class), no atomics, same checks and error codes; null or misaligned tables / wsum:
+ * UNETK_E_BADARG.  All-ones tables give the acc of unetk_eval3d_accumulate bit for bit and wsum == cnt. */
+int unetk_eval3d_accumulate_w(const unetk_lits3d_desc* d, const int32_t* sample_tab, const float* probs, int C,
+                              int64_t case_base, int case_depth, const int32_t box[6], const float* gz, const float* gy,
+                              const float* gx, float* acc, float* wsum, void* stream);
+
+/* The end of a case: acc f32 [depth,src_h,src_w,C] and EXACTLY ONE of wsum (f32) / cnt (int32) [depth,src_h,src_w], the other
+ * NULL -> pred uint8 [depth,src_h,src_w].  box = {z0, z1, y0, y1, x0, x1} (host memory, inside the volume, not empty): the part
+ * of the case the windows tiled.  A voxel is covered when its weight is > 0;  pred = covered and inside box ? argmax over the
+ * C sums (lowest index on ties, as unetk_head_predict) : 0 -- windows may reach beyond the box, what they leave there is not a
+ * prediction.  *uncovered (int32, zeroed by the caller) += the voxels of box that are not covered, by integer atomics.
+ * 1 <= C <= 8; depth * src_h * src_w < 2^31 (UNETK_E_UNSUPPORTED). */
+int unetk_eval3d_finish(const float* acc, int C, int depth, int src_h, int src_w, const float* wsum, const int32_t* cnt,
+                        const int32_t box[6], uint8_t* pred, int32_t* uncovered, void* stream);
+
 /* ---------------------------------------------------------------- optimiser  core/solver.py:204-243
  * tf.train.AdamOptimizer on a flat parameter buffer.  g' = g*gscale + l2*p  (slim.l2_regularizer
  * gradient, base.py:128-135);  m += (1-b1)(g'-m);  v += (1-b2)(g'^2-v);
