@@ -270,7 +270,8 @@ struct WgParams {
   int N, H, W, Cin, Cout, xs, ys;
   int tiles_h, tiles_w, total_tiles, tiles_per_split, n_ci_tiles, n_co_tiles;
   ImgAddr xa, ya;
-  int bf16;            // x and dy rounded to bf16 on their way out of LDS, v_mfma_f32_32x32x16_bf16
+  int bf16;            // the precision.  UNETK_BF16: x and dy rounded to bf16 on their way out of LDS, v_mfma_f32_32x32x16_bf16;
+                       // UNETK_BF16S: x and dy are bf16 in memory
   // strided convs (slim.conv3d stride (.,2,2)): H, W are the OUTPUT plane (dy), the input plane is Hin x Win and output
   // pixel (oh, ow) reads input rows stride*oh - pbh + kh.  stride 0 / 1 = plain conv (Hin = H, Win = W, pb = 1).
   int stride, Hin, Win, pbh, pbw;
@@ -287,16 +288,45 @@ struct WgParams {
   // 1 / ya.group, 1 / spg -- unetk_fdiv below
   float rcp_h1, rcp_xg, rcp_yg, rcp_spg;
 };
-// conv_wgrad.hip: dw[9][Cin][Cout] = filter gradient of one 2-D tap plane; ws layout as unetk_conv3x3_wgrad
-size_t unetk_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout, int kd = 1);
+// ---- one decision per 3x3 filter-gradient launch, as ConvShape / ConvPlan above.  WgShape is what a launch is known by (no
+// pointers); unetk_wgrad_plan (conv_wgrad.hip, pure host arithmetic, no HIP calls) derives the kernel family, the tile grid, the
+// pixel splits and the workspace from it, and both unetk_wgrad_run and every workspace query read that one plan.
+enum WgFamily {
+  WG_MFMA, WG_STK12, WG_STK6,                  // conv3x3_wgrad_kernel: plain 8 x 16 tiles; stacked planes, 10 x 12 / 20 x 6 tiles
+  WG_S2W16, WG_S2W12, WG_S2W6,                 // ... stride 2: 4 x 16 / 4 x 12 / 4 x 6 tiles of output pixels
+  WG_ATROUS,                                   // ... rate 2: 6 x 16 tiles
+  WG_C3, WG_SMALLC,                            // first layers: conv3x3_wgrad_c3_kernel (MFMA) / conv3x3_wgrad_smallc_kernel
+  WG_BF16S, WG_BF16S_C3                        // conv_wgrad_bf16s.hip: bf16 storage / its first layer
+};
+struct WgShape {
+  int N, H, W, Cin, Cout;                      // as WgParams (H, W = the OUTPUT plane when strided)
+  int prec, stride, dil, kd;                   // UNETK_FP32 / UNETK_BF16 / UNETK_BF16S; 1 / 2; 1 / 2; fused depth taps (1 = none)
+};
+struct WgPlan {
+  int rc;                                      // UNETK_OK, or UNETK_E_UNSUPPORTED: no kernel takes the shape
+  int family, cit, cot;                        // WgFamily; the ci x co panel of a block
+  int tiles_h, tiles_w, total_tiles, S, tiles_per_split, n_ci_tiles, n_co_tiles;
+  int grid;                                    // blocks: S x kd x panels
+  int64_t slab_elems;                          // kd x 9 x Cin x Cout: one split's partial gradient
+  size_t ws_bytes;                             // 256 + S slabs (the slabs stay unused when S == 1: dw is written in place)
+};
+WgPlan unetk_wgrad_plan(const WgShape& s);
+// dw[kd][9][Cin][Cout] = filter gradient; validates, plans, launches, reduces.  p.bf16 = the precision; ws layout as
+// unetk_conv3x3_wgrad, at least unetk_wgrad_plan(...).ws_bytes
 int unetk_wgrad_run(WgParams p, float* dw, void* ws, size_t ws_bytes, hipStream_t st);
-size_t unetk_wgrad_bf16_ws_bytes(int N, int H, int W, int Cin, int Cout, int kd);   // p.bf16 with p.kd fused depth taps
-// conv_wgrad_bf16s.hip: UNETK_BF16S -- x and dy are bf16 in memory (x fp32 for the first layer, 9 * Cin <= 32)
-size_t unetk_wgrad_bf16s_ws_bytes(int N, int H, int W, int Cin, int Cout);
-int unetk_wgrad_bf16s_run(WgParams p, float* dw, void* ws, size_t ws_bytes, hipStream_t st);
-// stride-2 variant (p.stride == 2; p.H, p.W = output plane): fp32, Cin % 32 == 0 and Cout % 64 == 0
-bool unetk_wgrad_strided_ok(int Cin, int Cout);
-size_t unetk_wgrad_strided_ws_bytes(int N, int Ho, int Wo, int Cin, int Cout, int kd = 1);
+// conv_wgrad_bf16s.hip (UNETK_BF16S: x and dy are bf16 in memory, x fp32 for the first layer, 9 * Cin <= 32): `plan` fills
+// family, panels and *want (the wanted splits) when it takes the shape, `launch` instantiates what the plan says
+bool unetk_wgrad_plan_bf16s(const WgShape& s, WgPlan& pl, int* want);
+int unetk_wgrad_launch_bf16s(const WgPlan& pl, const WgParams& p, hipStream_t st);
+// Split-K over `total` tiles when `want` splits would fill the chip: S <= want splits of `per` tiles each, none of them empty
+// (S is recomputed from per, so it is NOT monotone in total: 576 tiles at want = 512 give 288 splits of 2, 504 tiles 504 of 1).
+struct SplitK { int S, per; };
+inline SplitK unetk_split(int total, int want) {
+  int S = want > total ? total : want;
+  if (S < 1) S = 1;
+  const int per = (total + S - 1) / S;
+  return SplitK{(total + per - 1) / per, per};
+}
 // dst[i] = sum_s slab[s*n + i] in fixed order (n % 4 == 0).
 int unetk_launch_slab_reduce(const float* slab, int S, int64_t n, float* dst, hipStream_t st);
 // dst[k][c] = sum_rows src[k][row][c] (fp64 accumulate).  tmp: K*64*C floats when rows > 256.

@@ -192,6 +192,88 @@ inline size_t s2lin_xs_floats(const unetk_conv3d_desc* d, const Geo3& g) {
   return ((size_t)d->N * g.Do * g.Ho * g.Wo * (d->sd == 2 ? 8 : 4) * d->Cin + 63) & ~(size_t)63;
 }
 
+// The filter-gradient launches of a layer, decided once: the workspace queries size for exactly these (wg_runs_bytes) and the
+// entry points launch them (run_wgrad).  Route: stride-2 tiles straight from dy when that kernel takes the channels -- else dy is
+// zero-dilated into the first zf floats of the workspace and the stride-1 kernels run on it, dW = wgrad_s1(x, dilate(dy)); all
+// three depth taps fused into ONE launch (WgParams::kd) when the plan of that launch takes them -- a third of the splits fills
+// the chip, so every block walks three times the tiles and the slab round trip shrinks accordingly -- else one launch per depth
+// tap over the output planes lo .. hi the tap reaches.  The split count is not monotone in the planes (unetk_split), so a
+// tap's launch is planned at its own plane count.
+struct WgRun {
+  WgShape s;
+  int dt, lo, hi;        // dt < 0: every depth tap in this one launch; hi < lo: the tap reaches no plane (its gradient is zero)
+};
+struct WgRuns {
+  int n;
+  WgRun run[3];
+  bool native;           // stride-2 tiles of OUTPUT pixels: tap (kh, kw) of output (oh, ow) reads input (2 oh - pb + kh, 2 ow - pb + kw)
+  size_t zf;             // floats of the dilated dy in front of the filter gradient's workspace
+};
+WgRuns wg_runs(const unetk_conv3d_desc* d, const Geo3& g, int prec) {
+  WgRuns r{};
+  WgShape s{d->N * g.Do, d->H, d->W, d->Cin, d->Cout, prec, 1, 1, 1};
+  if (d->shw == 2) {
+    WgShape s2 = s;
+    s2.H = g.Ho; s2.W = g.Wo; s2.stride = 2;
+    r.native = unetk_wgrad_plan(s2).rc == UNETK_OK;
+    if (r.native) s = s2;
+    else r.zf = ((size_t)d->N * g.Do * d->H * d->W * d->Cout + 63) & ~(size_t)63;
+  }
+  WgShape sf = s;
+  sf.kd = 3;
+  if (d->kd == 3 && (r.native || d->shw == 1) && unetk_wgrad_plan(sf).rc == UNETK_OK) {
+    r.run[r.n++] = WgRun{sf, -1, 0, g.Do - 1};
+    return r;
+  }
+  for (int dt = 0; dt < d->kd; ++dt) {
+    WgRun& t = r.run[r.n++];
+    t.s = s; t.dt = dt;
+    tap_range(d, g, dt, &t.lo, &t.hi);
+    t.s.N = d->N * (t.hi - t.lo + 1);
+  }
+  return r;
+}
+size_t wg_runs_bytes(const WgRuns& r) {
+  size_t bytes = 0;
+  for (int i = 0; i < r.n; ++i) {
+    if (r.run[i].hi < r.run[i].lo) continue;
+    const WgPlan pl = unetk_wgrad_plan(r.run[i].s);
+    if (pl.rc == UNETK_OK && pl.ws_bytes > bytes) bytes = pl.ws_bytes;
+  }
+  return bytes ? r.zf * sizeof(float) + bytes : 0;
+}
+// Z, zs: dy and its pixel stride (dilated where r.zf); ws: behind the dilated dy
+int run_wgrad(const unetk_conv3d_desc* d, const Geo3& g, const WgRuns& r, const float* x, const float* Z, int zs, float* dw,
+              void* ws, size_t ws_bytes, hipStream_t st) {
+  const int HWx = d->H * d->W * d->x_stride;
+  for (int i = 0; i < r.n; ++i) {
+    const WgRun& t = r.run[i];
+    const int np = t.hi - t.lo + 1, HWz = t.s.H * t.s.W * zs;
+    float* dw_t = dw + (int64_t)(t.dt < 0 ? 0 : t.dt) * 9 * d->Cin * d->Cout;
+    if (np <= 0) {
+      hipError_t e = hipMemsetAsync(dw_t, 0, (size_t)9 * d->Cin * d->Cout * sizeof(float), st);
+      if (e != hipSuccess) return (int)e;
+      continue;
+    }
+    WgParams p{};
+    p.x = x; p.dy = Z + (int64_t)t.lo * HWz;
+    p.N = t.s.N; p.H = t.s.H; p.W = t.s.W; p.Cin = d->Cin; p.Cout = d->Cout;
+    p.xs = d->x_stride; p.ys = zs;
+    p.bf16 = t.s.prec;
+    if (r.native) { p.stride = 2; p.Hin = d->H; p.Win = d->W; p.pbh = same_pb(d->H, 3, 2); p.pbw = same_pb(d->W, 3, 2); }
+    p.xa = planes(HWx, np, d->sd, d->D);
+    p.ya = planes(HWz, np, 1, g.Do);
+    if (t.dt < 0) {      // every dy plane against the x plane each tap reads
+      p.kd = 3; p.dshift0 = -g.pb_d; p.dsd = d->sd; p.din = d->D; p.spg = g.Do; p.dplane = HWx;
+    } else {
+      p.x += (int64_t)(t.lo * d->sd - g.pb_d + t.dt) * HWx;
+    }
+    const int rc = unetk_wgrad_run(p, dw_t, ws, ws_bytes, st);
+    if (rc != UNETK_OK) return rc;
+  }
+  return UNETK_OK;
+}
+
 }  // namespace
 
 extern "C" int unetk_conv3d_pack(const float* w, int kd, int Cin, int Cout, float* wp_fwd, float* wp_dgrad,
@@ -243,17 +325,9 @@ extern "C" size_t unetk_conv3d_ws_bytes(const unetk_conv3d_desc* d) {
   size_t f = 0;
   if (d->shw == 2) f += (size_t)d->N * g.Do * d->H * d->W * d->Cout;          // stride-1 result / dilated dy
   f = (f + 63) & ~(size_t)63;
-  size_t bytes = f * sizeof(float) + unetk_wgrad_ws_bytes(d->N * g.Do, d->H, d->W, d->Cin, d->Cout);
-  if (d->shw == 1 && d->kd > 1) {   // fused depth taps (one launch for the whole (kd,3,3) filter gradient)
-    const size_t fb = unetk_wgrad_ws_bytes(d->N * g.Do, d->H, d->W, d->Cin, d->Cout, d->kd);
-    if (fb > bytes) bytes = fb;
-  }
-  if (d->shw == 2) {
-    size_t sb = unetk_wgrad_strided_ws_bytes(d->N * g.Do, g.Ho, g.Wo, d->Cin, d->Cout);
-    if (sb > bytes) bytes = sb;
-    sb = unetk_wgrad_strided_ws_bytes(d->N * g.Do, g.Ho, g.Wo, d->Cin, d->Cout, d->kd);
-    if (sb > bytes) bytes = sb;
-  }
+  size_t bytes = f * sizeof(float);
+  const size_t wb = wg_runs_bytes(wg_runs(d, g, UNETK_FP32));     // the filter gradient's launches (behind the dilated dy)
+  if (wb > bytes) bytes = wb;
   if (s2lin_ok(d, g)) {              // space-to-depth copy of x + the stream-K slab of the grouped-tap forward
     const size_t sb = s2lin_xs_floats(d, g) * sizeof(float) +
                       plane_plan(d->N * g.Do, g.Ho, g.Wo, d->Cin, d->Cout, g.Do, live_k(d->cin_live8, d->Cin), 0, d->kd * 4).ws_bytes;
@@ -580,85 +654,14 @@ extern "C" int unetk_conv3d_wgrad(const unetk_conv3d_desc* d, const float* x, co
   if (ws_bytes < unetk_conv3d_ws_bytes(d)) return UNETK_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const Geo3 g = geo3(d);
-  if (d->shw == 2 && unetk_wgrad_strided_ok(d->Cin, d->Cout)) {
-    // natively strided filter gradient: tiles of OUTPUT pixels, tap (kh, kw) of output (oh, ow) reads input
-    // (2 oh - pb + kh, 2 ow - pb + kw); no zero-dilated copy of dy, a quarter of the MFMA work
-    const int HWx = d->H * d->W * d->x_stride, HWy = g.Ho * g.Wo * d->y_stride;
-    if (d->kd == 3) {
-      // the three depth taps in ONE launch (WgParams::kd): every dy plane against the x plane each tap reads
-      WgParams p{};
-      p.x = x; p.dy = dy;
-      p.N = d->N * g.Do; p.H = g.Ho; p.W = g.Wo; p.Cin = d->Cin; p.Cout = d->Cout;
-      p.xs = d->x_stride; p.ys = d->y_stride;
-      p.stride = 2; p.Hin = d->H; p.Win = d->W; p.pbh = same_pb(d->H, 3, 2); p.pbw = same_pb(d->W, 3, 2);
-      p.xa = planes(HWx, g.Do, d->sd, d->D);
-      p.ya = planes(HWy, g.Do, 1, g.Do);
-      p.kd = 3; p.dshift0 = -g.pb_d; p.dsd = d->sd; p.din = d->D; p.spg = g.Do; p.dplane = HWx;
-      return unetk_wgrad_run(p, dw, ws, ws_bytes, st);
-    }
-    for (int dt = 0; dt < d->kd; ++dt) {
-      int lo, hi;
-      tap_range(d, g, dt, &lo, &hi);
-      float* dw_t = dw + (int64_t)dt * 9 * d->Cin * d->Cout;
-      if (hi < lo) {
-        hipError_t e = hipMemsetAsync(dw_t, 0, (size_t)9 * d->Cin * d->Cout * sizeof(float), st);
-        if (e != hipSuccess) return (int)e;
-        continue;
-      }
-      WgParams p{};
-      p.x = x + (int64_t)(lo * d->sd - g.pb_d + dt) * HWx;
-      p.dy = dy + (int64_t)lo * HWy;
-      p.N = d->N * (hi - lo + 1); p.H = g.Ho; p.W = g.Wo; p.Cin = d->Cin; p.Cout = d->Cout;
-      p.xs = d->x_stride; p.ys = d->y_stride;
-      p.stride = 2; p.Hin = d->H; p.Win = d->W; p.pbh = same_pb(d->H, 3, 2); p.pbw = same_pb(d->W, 3, 2);
-      p.xa = planes(HWx, hi - lo + 1, d->sd, d->D);
-      p.ya = planes(HWy, hi - lo + 1, 1, g.Do);
-      const int rc = unetk_wgrad_run(p, dw_t, ws, ws_bytes, st);
-      if (rc != UNETK_OK) return rc;
-    }
-    return UNETK_OK;
-  }
-  const float* Z;
-  int zs;
-  int rc = dilated_dy(d, g, dy, ws, st, &Z, &zs);
-  if (rc != UNETK_OK) return rc;
-  size_t zf = d->shw == 2 ? (size_t)d->N * g.Do * d->H * d->W * d->Cout : 0;
-  zf = (zf + 63) & ~(size_t)63;
-  float* wws = (float*)ws + zf;
-  const size_t wws_bytes = ws_bytes - zf * sizeof(float);
-  const int HWx = d->H * d->W * d->x_stride, HWz = d->H * d->W * zs;
-  if (d->kd == 3 && d->shw == 1 && unetk_wgrad_ws_bytes(d->N * g.Do, d->H, d->W, d->Cin, d->Cout, 3) > 0) {
-    // the three depth taps in ONE launch (WgParams::kd): a third of the splits fills the chip, so every block walks three
-    // times the tiles and the slab round trip shrinks accordingly
-    WgParams p{};
-    p.x = x; p.dy = Z;
-    p.N = d->N * g.Do; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout;
-    p.xs = d->x_stride; p.ys = zs;
-    p.xa = planes(HWx, g.Do, d->sd, d->D);
-    p.ya = planes(HWz, g.Do, 1, g.Do);
-    p.kd = 3; p.dshift0 = -g.pb_d; p.dsd = d->sd; p.din = d->D; p.spg = g.Do; p.dplane = HWx;
-    return unetk_wgrad_run(p, dw, wws, wws_bytes, st);
-  }
-  for (int dt = 0; dt < d->kd; ++dt) {
-    int lo, hi;
-    tap_range(d, g, dt, &lo, &hi);
-    float* dw_t = dw + (int64_t)dt * 9 * d->Cin * d->Cout;
-    if (hi < lo) {
-      hipError_t e = hipMemsetAsync(dw_t, 0, (size_t)9 * d->Cin * d->Cout * sizeof(float), st);
-      if (e != hipSuccess) return (int)e;
-      continue;
-    }
-    WgParams p{};
-    p.x = x + (int64_t)(lo * d->sd - g.pb_d + dt) * HWx;
-    p.dy = Z + (int64_t)lo * HWz;
-    p.N = d->N * (hi - lo + 1); p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout;
-    p.xs = d->x_stride; p.ys = zs;
-    p.xa = planes(HWx, hi - lo + 1, d->sd, d->D);
-    p.ya = planes(HWz, hi - lo + 1, 1, g.Do);
-    rc = unetk_wgrad_run(p, dw_t, wws, wws_bytes, st);
+  const WgRuns r = wg_runs(d, g, UNETK_FP32);
+  const float* Z = dy;
+  int zs = d->y_stride;
+  if (r.zf) {
+    const int rc = dilated_dy(d, g, dy, ws, st, &Z, &zs);
     if (rc != UNETK_OK) return rc;
   }
-  return UNETK_OK;
+  return run_wgrad(d, g, r, x, Z, zs, dw, (float*)ws + r.zf, ws_bytes - r.zf * sizeof(float), st);
 }
 
 // ---------------------------------------------------------------- UNETK_BF16: the stride-1 3-D convs on the bf16 matrix cores
@@ -699,10 +702,7 @@ extern "C" int unetk_conv3d_stat_rows_bf16(const unetk_conv3d_desc* d) {
 
 extern "C" size_t unetk_conv3d_ws_bytes_bf16(const unetk_conv3d_desc* d) {
   if (!desc_ok(d) || !bf16_rule_ok(d)) return 0;
-  const int np = d->N * d->D;
-  const size_t a = unetk_wgrad_bf16_ws_bytes(np, d->H, d->W, d->Cin, d->Cout, d->kd);
-  const size_t b = unetk_wgrad_ws_bytes(np, d->H, d->W, d->Cin, d->Cout);     // the plain (kd = 1) run's check
-  return a > b ? a : b;
+  return wg_runs_bytes(wg_runs(d, geo3(d), UNETK_BF16));
 }
 
 extern "C" int unetk_conv3d_fwd_bf16(const unetk_conv3d_desc* d, const float* x, const void* wp_fwd, float* y,
@@ -755,14 +755,6 @@ extern "C" int unetk_conv3d_wgrad_bf16(const unetk_conv3d_desc* d, const float* 
   UNETK_REQUIRE(d->x_stride % 4 == 0 && d->y_stride % 4 == 0);
   const int rc = bf16_ws_check(d, ws, ws_bytes);
   if (rc != UNETK_OK) return rc;
-  const int HWx = d->H * d->W * d->x_stride;
-  WgParams p{};
-  p.x = x; p.dy = dy;
-  p.N = d->N * d->D; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout;
-  p.xs = d->x_stride; p.ys = d->y_stride;
-  p.bf16 = 1;
-  p.xa = planes(HWx, d->D, 1, d->D);
-  p.ya = planes(d->H * d->W * d->y_stride, d->D, 1, d->D);
-  if (d->kd == 3) { p.kd = 3; p.dshift0 = -1; p.dsd = 1; p.din = d->D; p.spg = d->D; p.dplane = HWx; }
-  return unetk_wgrad_run(p, dw, ws, ws_bytes, (hipStream_t)stream);
+  const Geo3 g = geo3(d);
+  return run_wgrad(d, g, wg_runs(d, g, UNETK_BF16), x, dy, d->y_stride, dw, ws, ws_bytes, (hipStream_t)stream);
 }

@@ -573,84 +573,12 @@ int unetk_launch_slab_reduce(const float* slab, int S, int64_t n, float* dst, hi
 namespace {
 
 constexpr int STH = 10, STW = 12;   // stacked-plane tile
-
-struct WgPlan {
-  int mode;  // 0 mfma, 1 small-Cin, 2 mfma on stacked planes, -1 unsupported
-  int cit, cot;
-  int tiles_h, tiles_w, total_tiles, S, tiles_per_split, n_ci_tiles, n_co_tiles;
-};
-
-constexpr int S2TH = 4;             // stride-2 tile: 4 x 16 (or 4 x 12) output pixels, 32-channel ci panels
-
-bool wg_strided_ok(int Cin, int Cout) { return Cin % 32 == 0 && Cout % 64 == 0; }
+constexpr int S2TH = 4;             // stride-2 tile: 4 x 16 (or 4 x 12, 4 x 6) output pixels, 32-channel ci panels
 
 int wg_s2w6() {        // UNETK_WG_S2W6=0: measurement switch for the 6-wide stride-2 tile (read once)
   static int v = -1;
   if (v < 0) { const char* e = getenv("UNETK_WG_S2W6"); v = e ? atoi(e) : 1; }
   return v;
-}
-
-WgPlan wg_plan_strided(int N, int H, int W, int Cin, int Cout, int kd = 1) {   // H, W = output plane
-  WgPlan pl{};
-  // 6-wide output planes (UNet3D's (2,2,2) bridge, round 5): 4 x 6 tiles -- a 4 x 16 tile is 37 % full there (25 TFLOP/s)
-  const int tw = (W % TW != 0 && W % STW == 0) ? STW : ((W == 6 && wg_s2w6()) ? 6 : TW);
-  pl.mode = tw == STW ? 4 : (tw == 6 ? 6 : 3);
-  pl.tiles_h = (H + S2TH - 1) / S2TH;
-  pl.tiles_w = (W + tw - 1) / tw;
-  pl.total_tiles = N * pl.tiles_h * pl.tiles_w;
-  pl.cit = 32; pl.cot = 64;
-  pl.n_ci_tiles = Cin / 32;
-  pl.n_co_tiles = Cout / 64;
-  const int panels = pl.n_ci_tiles * pl.n_co_tiles * (kd > 1 ? kd : 1);      // fused depth taps: kd x the blocks per split
-  int S = panels >= 512 ? 1 : 512 / panels;   // floor: 513 blocks would be three rounds of the one-block-per-CU kernel
-  if (S > pl.total_tiles) S = pl.total_tiles;
-  if (S < 1) S = 1;
-  pl.tiles_per_split = (pl.total_tiles + S - 1) / S;
-  pl.S = (pl.total_tiles + pl.tiles_per_split - 1) / pl.tiles_per_split;
-  return pl;
-}
-
-WgPlan wg_plan(int N, int H, int W, int Cin, int Cout, bool bf16 = false, int kd = 1) {
-  WgPlan pl{};
-  pl.tiles_h = (H + TH - 1) / TH;
-  pl.tiles_w = (W + TW - 1) / TW;
-  pl.total_tiles = N * pl.tiles_h * pl.tiles_w;
-  // small planes whose width 8 x 16 tiles fill badly: 10 x 12 tiles over the stacked planes (fp32, 64 x 64 panels)
-  const bool stk_ok = !bf16 && Cin % 64 == 0 && Cout % 64 == 0 && W % TW != 0 && H <= 64 && (int64_t)N * (H + 1) < (1 << 20);
-  const bool stacked12 = stk_ok && W % STW == 0;
-  const bool stacked6 = stk_ok && !stacked12 && W % 6 == 0;       // 20 x 6 tiles: UNet3D's 6 x 6 bridge planes
-  const bool stacked = stacked12 || stacked6;
-  if (stacked) {
-    const int sth = stacked12 ? STH : 20, stw = stacked12 ? STW : 6;
-    pl.tiles_w = W / stw;
-    pl.tiles_h = (int)(((int64_t)N * (H + 1) + sth - 1) / sth);   // over ALL planes
-    pl.total_tiles = pl.tiles_h * pl.tiles_w;
-  }
-  if (Cin % 32 == 0 && Cout % 32 == 0) {
-    pl.mode = stacked12 ? 2 : (stacked6 ? 5 : 0);
-    pl.cit = Cin % 64 == 0 ? 64 : 32;
-    pl.cot = Cout % 64 == 0 ? 64 : 32;
-    pl.n_ci_tiles = Cin / pl.cit;
-    pl.n_co_tiles = Cout / pl.cot;
-    const int panels = pl.n_ci_tiles * pl.n_co_tiles * (kd > 1 ? kd : 1);
-    int S = panels >= 512 ? 1 : 512 / panels;   // one 512-thread block per CU (154 KB of LDS) x 256 CUs x 2 rounds; floor: 513 blocks would be three
-    // few tiles per block (small layers): one round of 256 blocks halves the per-block epilogue (LDS tree + slab) per tile
-    // (floor, not ceil: 154 KB of LDS = one block per CU, so 257 blocks take two rounds)
-    if (pl.total_tiles / S < 16 && panels <= 256) S = 256 / panels;
-    if (S > pl.total_tiles) S = pl.total_tiles;
-    if (S < 1) S = 1;
-    pl.tiles_per_split = (pl.total_tiles + S - 1) / S;
-    pl.S = (pl.total_tiles + pl.tiles_per_split - 1) / pl.tiles_per_split;
-  } else if ((Cin <= 5 || Cin == 9) && Cout <= 256 && 256 % Cout == 0) {  // 9 = 3 channels x (image, dy, dx): --img_grad; 5 = image + Sobel
-    pl.mode = 1;
-    int S = 512;      // = the resident blocks (two 71 KB blocks per CU): measured 2048 / 1024 / 512 splits -> 0.201 / 0.173 / 0.153 ms
-    if (S > pl.total_tiles) S = pl.total_tiles;
-    pl.tiles_per_split = (pl.total_tiles + S - 1) / S;
-    pl.S = (pl.total_tiles + pl.tiles_per_split - 1) / pl.tiles_per_split;
-  } else {
-    pl.mode = -1;
-  }
-  return pl;
 }
 
 template <int CIT, int COT, bool BF, int TH_ = TH, int TW_ = TW, bool STK = false, int S = 1, int DIL = 1>
@@ -667,169 +595,199 @@ int launch_wgrad(const WgParams& p, int grid, hipStream_t st) {
   return UNETK_OK;
 }
 
+int launch_c3(const WgPlan& pl, const WgParams& p, hipStream_t st) {
+  const size_t lds3 = (size_t)2 * (TH * TW * p.Cout + HALO_PIX * 4) * sizeof(float);      // two tile buffers: 71 KB at Cout = 64
+  static bool attr3 = false;
+  if (!attr3) {
+    hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wgrad_c3_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       2 * (TH * TW * 64 + HALO_PIX * 4) * (int)sizeof(float));
+    if (e != hipSuccess) return (int)e;
+    attr3 = true;
+  }
+  if (p.Cout == 64) UNETK_LAUNCH(conv3x3_wgrad_c3_kernel<64>, dim3(pl.grid), dim3(256), lds3, st, p);
+  else UNETK_LAUNCH(conv3x3_wgrad_c3_kernel<32>, dim3(pl.grid), dim3(256), lds3, st, p);
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
+int launch_smallc(const WgPlan& pl, const WgParams& p, hipStream_t st) {
+  const int PL = 256 / p.Cout;
+  const size_t lds = (size_t)PL * 9 * p.Cin * p.Cout * sizeof(float);
+  if (lds > (p.Cin == 9 ? 150 : 64) * 1024) return UNETK_E_UNSUPPORTED;
+  switch (p.Cin) {
+    case 1: UNETK_LAUNCH(conv3x3_wgrad_smallc_kernel<1>, dim3(pl.grid), dim3(256), lds, st, p); break;
+    case 2: UNETK_LAUNCH(conv3x3_wgrad_smallc_kernel<2>, dim3(pl.grid), dim3(256), lds, st, p); break;
+    case 3: UNETK_LAUNCH(conv3x3_wgrad_smallc_kernel<3>, dim3(pl.grid), dim3(256), lds, st, p); break;
+    case 4: UNETK_LAUNCH(conv3x3_wgrad_smallc_kernel<4>, dim3(pl.grid), dim3(256), lds, st, p); break;
+    case 5: UNETK_LAUNCH(conv3x3_wgrad_smallc_kernel<5>, dim3(pl.grid), dim3(256), lds, st, p); break;
+    case 9: {
+      static bool attr_done = false;
+      if (!attr_done) {
+        hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wgrad_smallc_kernel<9>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        if (e != hipSuccess) return (int)e;
+        attr_done = true;
+      }
+      UNETK_LAUNCH(conv3x3_wgrad_smallc_kernel<9>, dim3(pl.grid), dim3(256), lds, st, p);
+      break;
+    }
+    default: return UNETK_E_UNSUPPORTED;
+  }
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
+// the instantiation the plan names
+int launch_plan(const WgPlan& pl, const WgParams& p, hipStream_t st) {
+  const bool bf = p.bf16 == UNETK_BF16;
+  switch (pl.family) {
+    case WG_MFMA:
+      if (pl.cit == 64 && pl.cot == 64) return bf ? launch_wgrad<64, 64, true>(p, pl.grid, st) : launch_wgrad<64, 64, false>(p, pl.grid, st);
+      if (pl.cit == 64) return bf ? launch_wgrad<64, 32, true>(p, pl.grid, st) : launch_wgrad<64, 32, false>(p, pl.grid, st);
+      if (pl.cot == 64) return bf ? launch_wgrad<32, 64, true>(p, pl.grid, st) : launch_wgrad<32, 64, false>(p, pl.grid, st);
+      return bf ? launch_wgrad<32, 32, true>(p, pl.grid, st) : launch_wgrad<32, 32, false>(p, pl.grid, st);
+    case WG_STK12: return launch_wgrad<64, 64, false, STH, STW, true>(p, pl.grid, st);
+    case WG_STK6: return launch_wgrad<64, 64, false, 20, 6, true>(p, pl.grid, st);
+    case WG_S2W16: return launch_wgrad<32, 64, false, S2TH, TW, false, 2>(p, pl.grid, st);
+    case WG_S2W12: return launch_wgrad<32, 64, false, S2TH, STW, false, 2>(p, pl.grid, st);
+    case WG_S2W6: return launch_wgrad<32, 64, false, S2TH, 6, false, 2>(p, pl.grid, st);
+    case WG_ATROUS: return launch_wgrad<64, 64, false, 6, TW, false, 1, 2>(p, pl.grid, st);
+    case WG_C3:
+      if (p.ys % 4 == 0) return launch_c3(pl, p, st);       // (its dy tile comes by 16-byte loads; same grid and slabs otherwise)
+      return launch_smallc(pl, p, st);
+    case WG_SMALLC: return launch_smallc(pl, p, st);
+    case WG_BF16S:
+    case WG_BF16S_C3: return unetk_wgrad_launch_bf16s(pl, p, st);
+  }
+  return UNETK_E_UNSUPPORTED;
+}
+
 }  // namespace
 
-size_t unetk_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout, int kd) {
-  if (kd > 1) {
-    const WgPlan pk = wg_plan(N, H, W, Cin, Cout, false, kd);
-    if (pk.mode != 0 && pk.mode != 2 && pk.mode != 5) return 0;
-    const size_t fused = 256 + (size_t)pk.S * kd * 9 * Cin * Cout * sizeof(float);
-    const size_t plain = unetk_wgrad_ws_bytes(N, H, W, Cin, Cout, 1);
-    return fused > plain ? fused : plain;
+WgPlan unetk_wgrad_plan(const WgShape& s) {
+  WgPlan pl{};
+  pl.rc = UNETK_E_UNSUPPORTED;
+  const int KD = s.kd > 1 ? s.kd : 1;
+  const bool bf16 = s.prec == UNETK_BF16;
+  int th = TH, tw = TW, want;
+  auto tile_grid = [&]() {
+    pl.tiles_h = (s.H + th - 1) / th;
+    pl.tiles_w = (s.W + tw - 1) / tw;
+    pl.total_tiles = s.N * pl.tiles_h * pl.tiles_w;
+  };
+  pl.cit = pl.cot = 64;
+  pl.n_ci_tiles = pl.n_co_tiles = 1;
+  if (s.dil > 2) return pl;
+  if (s.prec == UNETK_BF16S) {           // stride 1, dense taps only
+    if (s.stride == 2 || s.dil == 2 || KD > 1 || !unetk_wgrad_plan_bf16s(s, pl, &want)) return pl;
+    tile_grid();
+  } else if (s.stride == 2) {            // fp32 only
+    if (bf16 || s.Cin % 32 != 0 || s.Cout % 64 != 0) return pl;
+    // 6-wide output planes (UNet3D's (2,2,2) bridge, round 5): 4 x 6 tiles -- a 4 x 16 tile is 37 % full there (25 TFLOP/s)
+    tw = (s.W % TW != 0 && s.W % STW == 0) ? STW : ((s.W == 6 && wg_s2w6()) ? 6 : TW);
+    th = S2TH;
+    pl.family = tw == STW ? WG_S2W12 : (tw == 6 ? WG_S2W6 : WG_S2W16);
+    tile_grid();
+    pl.cit = 32;
+    pl.n_ci_tiles = s.Cin / 32;
+    pl.n_co_tiles = s.Cout / 64;
+    const int panels = pl.n_ci_tiles * pl.n_co_tiles * KD;      // fused depth taps: kd x the blocks per split
+    want = panels >= 512 ? 1 : 512 / panels;   // floor: 513 blocks would be three rounds of the one-block-per-CU kernel
+  } else if (s.dil == 2) {               // atrous: 6 x 16 tiles (the 10 x 20 halo of two stages fits LDS), 64 x 64 panels, fp32
+    if (bf16 || s.Cin % 64 != 0 || s.Cout % 64 != 0 || KD > 1) return pl;
+    pl.family = WG_ATROUS;
+    th = 6;
+    tile_grid();
+    pl.n_ci_tiles = s.Cin / 64;
+    pl.n_co_tiles = s.Cout / 64;
+    const int panels = pl.n_ci_tiles * pl.n_co_tiles;
+    want = panels >= 512 ? 1 : 512 / panels;   // floor: 513 blocks would be three rounds of the one-block-per-CU kernel
+  } else if (s.Cin % 32 == 0 && s.Cout % 32 == 0) {
+    // small planes whose width 8 x 16 tiles fill badly: 10 x 12 tiles over the stacked planes (fp32, 64 x 64 panels)
+    const bool stk_ok = !bf16 && s.Cin % 64 == 0 && s.Cout % 64 == 0 && s.W % TW != 0 && s.H <= 64 && (int64_t)s.N * (s.H + 1) < (1 << 20);
+    const bool stacked12 = stk_ok && s.W % STW == 0;
+    const bool stacked6 = stk_ok && !stacked12 && s.W % 6 == 0;       // 20 x 6 tiles: UNet3D's 6 x 6 bridge planes
+    pl.family = stacked12 ? WG_STK12 : (stacked6 ? WG_STK6 : WG_MFMA);
+    tile_grid();
+    if (stacked12 || stacked6) {
+      const int sth = stacked12 ? STH : 20, stw = stacked12 ? STW : 6;
+      pl.tiles_w = s.W / stw;
+      pl.tiles_h = (int)(((int64_t)s.N * (s.H + 1) + sth - 1) / sth);   // over ALL planes
+      pl.total_tiles = pl.tiles_h * pl.tiles_w;
+    }
+    pl.cit = s.Cin % 64 == 0 ? 64 : 32;
+    pl.cot = s.Cout % 64 == 0 ? 64 : 32;
+    pl.n_ci_tiles = s.Cin / pl.cit;
+    pl.n_co_tiles = s.Cout / pl.cot;
+    const int panels = pl.n_ci_tiles * pl.n_co_tiles * KD;
+    want = panels >= 512 ? 1 : 512 / panels;   // one 512-thread block per CU (154 KB of LDS) x 256 CUs x 2 rounds; floor: 513 blocks would be three
+    // few tiles per block (small layers): one round of 256 blocks halves the per-block epilogue (LDS tree + slab) per tile
+    // (floor, not ceil: 154 KB of LDS = one block per CU, so 257 blocks take two rounds)
+    if (pl.total_tiles / want < 16 && panels <= 256) want = 256 / panels;
+  } else if ((s.Cin <= 5 || s.Cin == 9) && s.Cout <= 256 && 256 % s.Cout == 0) {  // 9 = 3 channels x (image, dy, dx): --img_grad; 5 = image + Sobel
+    if (KD > 1) return pl;               // fused depth taps: the MFMA kernels only
+    pl.family = 9 * s.Cin <= 32 && (s.Cout == 64 || s.Cout == 32) ? WG_C3 : WG_SMALLC;
+    tile_grid();
+    want = 512;       // = the resident blocks (two 71 KB blocks per CU): measured 2048 / 1024 / 512 splits -> 0.201 / 0.173 / 0.153 ms
+  } else {
+    return pl;
   }
-  const WgPlan pl = wg_plan(N, H, W, Cin, Cout, false), pb = wg_plan(N, H, W, Cin, Cout, true);
-  if (pl.mode < 0) return 0;
-  int S = pl.S > pb.S ? pl.S : pb.S;                           // either precision
-  if (Cin % 64 == 0 && Cout % 64 == 0) {                       // ... or the atrous variant (6-row tiles: more tiles to split)
-    const int panels = (Cin / 64) * (Cout / 64);
-    int sd = (512 + panels - 1) / panels;
-    const int64_t tiles = (int64_t)N * ((H + 5) / 6) * ((W + TW - 1) / TW);
-    if (sd > tiles) sd = (int)tiles;
-    if (sd > S) S = sd;
-  }
-  return 256 + (size_t)S * 9 * Cin * Cout * sizeof(float);    // 256 B zero page + slabs
-}
-
-// UNETK_BF16 with kd fused depth taps (the stride-1 3-D filter gradient): the bf16 plan's splits x kd slabs
-size_t unetk_wgrad_bf16_ws_bytes(int N, int H, int W, int Cin, int Cout, int kd) {
-  if (kd < 1) kd = 1;
-  const WgPlan pl = wg_plan(N, H, W, Cin, Cout, true, kd);
-  if (pl.mode != 0) return 0;
-  return 256 + (size_t)pl.S * kd * 9 * Cin * Cout * sizeof(float);    // 256 B zero page + slabs
-}
-
-bool unetk_wgrad_strided_ok(int Cin, int Cout) { return wg_strided_ok(Cin, Cout); }
-
-size_t unetk_wgrad_strided_ws_bytes(int N, int Ho, int Wo, int Cin, int Cout, int kd) {
-  if (!wg_strided_ok(Cin, Cout)) return 0;
-  const WgPlan pl = wg_plan_strided(N, Ho, Wo, Cin, Cout, kd);
-  return 256 + (size_t)pl.S * (kd > 1 ? kd : 1) * 9 * Cin * Cout * sizeof(float);
+  const SplitK sk = unetk_split(pl.total_tiles, want);
+  pl.S = sk.S;
+  pl.tiles_per_split = sk.per;
+  pl.grid = pl.S * KD * pl.n_ci_tiles * pl.n_co_tiles;
+  pl.slab_elems = (int64_t)KD * 9 * s.Cin * s.Cout;
+  pl.ws_bytes = 256 + (size_t)pl.S * pl.slab_elems * sizeof(float);    // 256 B zero page + slabs
+  pl.rc = UNETK_OK;
+  return pl;
 }
 
 int unetk_wgrad_run(WgParams p, float* dw, void* ws, size_t ws_bytes, hipStream_t st) {
+  const WgShape s{p.N, p.H, p.W, p.Cin, p.Cout, p.bf16, p.stride == 2 ? 2 : 1, p.dil, p.kd > 1 ? p.kd : 1};
+  const WgPlan pl = unetk_wgrad_plan(s);
+  if (pl.rc != UNETK_OK) return pl.rc;
+  if (pl.family == WG_BF16S || pl.family == WG_BF16S_C3) {
+    if (p.ys % 8 != 0 || (pl.family == WG_BF16S && p.xs % 8 != 0)) return UNETK_E_BADARG;       // 16-byte chunks of 8 bf16
+    if ((int64_t)p.H * p.W * (p.xs > p.ys ? p.xs : p.ys) * 2 >= (int64_t(1) << 31)) return UNETK_E_UNSUPPORTED;   // 32-bit offsets inside an image
+  } else if (pl.family <= WG_ATROUS && (p.xs % 4 != 0 || p.ys % 4 != 0)) {
+    return UNETK_E_BADARG;               // the MFMA kernels stage 16-byte pieces
+  }
+  if (s.stride == 2) {                   // H, W = output plane
+    if (p.pbh < 0 || p.pbh > 1 || p.pbw < 0 || p.pbw > 1) return UNETK_E_BADARG;
+    if (p.Hin < 2 * p.H - 1 || p.Hin > 2 * p.H || p.Win < 2 * p.W - 1 || p.Win > 2 * p.W) return UNETK_E_BADARG;
+  } else {
+    p.stride = 1; p.Hin = p.H; p.Win = p.W; p.pbh = p.pbw = s.dil == 2 ? 2 : 1;
+  }
+  if (ws_bytes < pl.ws_bytes) return UNETK_E_WORKSPACE;
   p.rcp_h1 = 1.0f / (float)(p.H + 1);
   p.rcp_xg = 1.0f / (float)(p.xa.group > 0 ? p.xa.group : 1);
   p.rcp_yg = 1.0f / (float)(p.ya.group > 0 ? p.ya.group : 1);
   p.rcp_spg = 1.0f / (float)(p.spg > 0 ? p.spg : 1);
-  if (p.stride == 2) {   // fp32 only: H, W = output plane
-    if (!wg_strided_ok(p.Cin, p.Cout) || p.bf16) return UNETK_E_UNSUPPORTED;
-    if (p.xs % 4 != 0 || p.ys % 4 != 0 || p.pbh < 0 || p.pbh > 1 || p.pbw < 0 || p.pbw > 1) return UNETK_E_BADARG;
-    if (p.Hin < 2 * p.H - 1 || p.Hin > 2 * p.H || p.Win < 2 * p.W - 1 || p.Win > 2 * p.W) return UNETK_E_BADARG;
-    const int KD = p.kd > 1 ? p.kd : 1;
-    const WgPlan pl = wg_plan_strided(p.N, p.H, p.W, p.Cin, p.Cout, KD);
-    if (ws_bytes < unetk_wgrad_strided_ws_bytes(p.N, p.H, p.W, p.Cin, p.Cout, KD)) return UNETK_E_WORKSPACE;
-    p.slab = pl.S == 1 ? dw : (float*)ws + 64;           // a single split writes the gradient in place
-    p.tiles_h = pl.tiles_h; p.tiles_w = pl.tiles_w; p.total_tiles = pl.total_tiles;
-    p.tiles_per_split = pl.tiles_per_split; p.n_ci_tiles = pl.n_ci_tiles; p.n_co_tiles = pl.n_co_tiles;
-    const int grid = pl.S * KD * pl.n_ci_tiles * pl.n_co_tiles;
-    const int rc = pl.mode == 4 ? launch_wgrad<32, 64, false, S2TH, STW, false, 2>(p, grid, st)
-                 : pl.mode == 6 ? launch_wgrad<32, 64, false, S2TH, 6, false, 2>(p, grid, st)
-                                : launch_wgrad<32, 64, false, S2TH, TW, false, 2>(p, grid, st);
-    if (rc != UNETK_OK) return rc;
-    if (pl.S == 1) return UNETK_OK;
-    return unetk_launch_slab_reduce((const float*)ws + 64, pl.S, (int64_t)KD * 9 * p.Cin * p.Cout, dw, st);
-  }
-  if (p.dil == 2) {      // atrous: 6 x 16 tiles (the 10 x 20 halo of two stages fits LDS), 64 x 64 panels, fp32
-    if (p.bf16 || p.Cin % 64 != 0 || p.Cout % 64 != 0 || p.kd > 1) return UNETK_E_UNSUPPORTED;
-    if (p.xs % 4 != 0 || p.ys % 4 != 0) return UNETK_E_BADARG;
-    p.stride = 1; p.Hin = p.H; p.Win = p.W; p.pbh = p.pbw = 2;
-    WgPlan pl{};
-    pl.tiles_h = (p.H + 5) / 6;
-    pl.tiles_w = (p.W + TW - 1) / TW;
-    pl.total_tiles = p.N * pl.tiles_h * pl.tiles_w;
-    pl.n_ci_tiles = p.Cin / 64; pl.n_co_tiles = p.Cout / 64;
-    const int panels = pl.n_ci_tiles * pl.n_co_tiles;
-    int S = panels >= 512 ? 1 : 512 / panels;   // floor: 513 blocks would be three rounds of the one-block-per-CU kernel
-    if (S > pl.total_tiles) S = pl.total_tiles;
-    if (S < 1) S = 1;
-    pl.tiles_per_split = (pl.total_tiles + S - 1) / S;
-    pl.S = (pl.total_tiles + pl.tiles_per_split - 1) / pl.tiles_per_split;
-    if (ws_bytes < 256 + (size_t)pl.S * 9 * p.Cin * p.Cout * sizeof(float)) return UNETK_E_WORKSPACE;
-    p.slab = pl.S == 1 ? dw : (float*)ws + 64;           // a single split writes the gradient in place
-    p.tiles_h = pl.tiles_h; p.tiles_w = pl.tiles_w; p.total_tiles = pl.total_tiles;
-    p.tiles_per_split = pl.tiles_per_split; p.n_ci_tiles = pl.n_ci_tiles; p.n_co_tiles = pl.n_co_tiles;
-    const int rc = launch_wgrad<64, 64, false, 6, TW, false, 1, 2>(p, pl.S * panels, st);
-    if (rc != UNETK_OK) return rc;
-    if (pl.S == 1) return UNETK_OK;
-    return unetk_launch_slab_reduce((const float*)ws + 64, pl.S, (int64_t)9 * p.Cin * p.Cout, dw, st);
-  }
-  p.stride = 1; p.Hin = p.H; p.Win = p.W; p.pbh = p.pbw = 1;
-  const int KD = p.kd > 1 ? p.kd : 1;
-  const WgPlan pl = wg_plan(p.N, p.H, p.W, p.Cin, p.Cout, p.bf16 != 0, KD);
-  if (pl.mode < 0) return UNETK_E_UNSUPPORTED;
-  // fused depth taps: the MFMA kernels only (fp32: plain or stacked planes; UNETK_BF16: the plain tiles, BF = true)
-  if (KD > 1 && (p.bf16 ? pl.mode != 0 : (pl.mode != 0 && pl.mode != 2 && pl.mode != 5))) return UNETK_E_UNSUPPORTED;
-  if (ws_bytes < (p.bf16 && KD > 1 ? unetk_wgrad_bf16_ws_bytes(p.N, p.H, p.W, p.Cin, p.Cout, KD)
-                                   : unetk_wgrad_ws_bytes(p.N, p.H, p.W, p.Cin, p.Cout, KD)))
-    return UNETK_E_WORKSPACE;
   p.slab = pl.S == 1 ? dw : (float*)ws + 64;           // a single split writes the gradient in place
   p.tiles_h = pl.tiles_h; p.tiles_w = pl.tiles_w; p.total_tiles = pl.total_tiles;
   p.tiles_per_split = pl.tiles_per_split; p.n_ci_tiles = pl.n_ci_tiles; p.n_co_tiles = pl.n_co_tiles;
-  int rc = UNETK_OK;
-  if (pl.mode == 2 || pl.mode == 5) {
-    if (p.xs % 4 != 0 || p.ys % 4 != 0) return UNETK_E_BADARG;
-    const int grid = pl.S * KD * pl.n_ci_tiles * pl.n_co_tiles;
-    rc = pl.mode == 2 ? launch_wgrad<64, 64, false, STH, STW, true>(p, grid, st)
-                      : launch_wgrad<64, 64, false, 20, 6, true>(p, grid, st);
-    if (rc != UNETK_OK) return rc;
-  } else if (pl.mode == 0) {
-    if (p.xs % 4 != 0 || p.ys % 4 != 0) return UNETK_E_BADARG;
-    const int grid = pl.S * KD * pl.n_ci_tiles * pl.n_co_tiles;
-    if (p.bf16) {
-      if (pl.cit == 64 && pl.cot == 64) rc = launch_wgrad<64, 64, true>(p, grid, st);
-      else if (pl.cit == 64) rc = launch_wgrad<64, 32, true>(p, grid, st);
-      else if (pl.cot == 64) rc = launch_wgrad<32, 64, true>(p, grid, st);
-      else rc = launch_wgrad<32, 32, true>(p, grid, st);
-    } else if (pl.cit == 64 && pl.cot == 64) rc = launch_wgrad<64, 64, false>(p, grid, st);
-    else if (pl.cit == 64) rc = launch_wgrad<64, 32, false>(p, grid, st);
-    else if (pl.cot == 64) rc = launch_wgrad<32, 64, false>(p, grid, st);
-    else rc = launch_wgrad<32, 32, false>(p, grid, st);
-    if (rc != UNETK_OK) return rc;
-  } else if (9 * p.Cin <= 32 && (p.Cout == 64 || p.Cout == 32) && p.ys % 4 == 0) {
-    const size_t lds3 = (size_t)2 * (TH * TW * p.Cout + HALO_PIX * 4) * sizeof(float);      // two tile buffers: 71 KB at Cout = 64
-    static bool attr3 = false;
-    if (!attr3) {
-      hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wgrad_c3_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         2 * (TH * TW * 64 + HALO_PIX * 4) * (int)sizeof(float));
-      if (e != hipSuccess) return (int)e;
-      attr3 = true;
-    }
-    if (p.Cout == 64) UNETK_LAUNCH(conv3x3_wgrad_c3_kernel<64>, dim3(pl.S), dim3(256), lds3, st, p);
-    else UNETK_LAUNCH(conv3x3_wgrad_c3_kernel<32>, dim3(pl.S), dim3(256), lds3, st, p);
-    UNETK_LAUNCH_CHECK();
-  } else {
-    const int PL = 256 / p.Cout;
-    const size_t lds = (size_t)PL * 9 * p.Cin * p.Cout * sizeof(float);
-    if (lds > (p.Cin == 9 ? 150 : 64) * 1024) return UNETK_E_UNSUPPORTED;
-    switch (p.Cin) {
-      case 1: UNETK_LAUNCH(conv3x3_wgrad_smallc_kernel<1>, dim3(pl.S), dim3(256), lds, st, p); break;
-      case 2: UNETK_LAUNCH(conv3x3_wgrad_smallc_kernel<2>, dim3(pl.S), dim3(256), lds, st, p); break;
-      case 3: UNETK_LAUNCH(conv3x3_wgrad_smallc_kernel<3>, dim3(pl.S), dim3(256), lds, st, p); break;
-      case 4: UNETK_LAUNCH(conv3x3_wgrad_smallc_kernel<4>, dim3(pl.S), dim3(256), lds, st, p); break;
-      case 5: UNETK_LAUNCH(conv3x3_wgrad_smallc_kernel<5>, dim3(pl.S), dim3(256), lds, st, p); break;
-      case 9: {
-        static bool attr_done = false;
-        if (!attr_done) {
-          hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wgrad_smallc_kernel<9>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-          if (e != hipSuccess) return (int)e;
-          attr_done = true;
-        }
-        UNETK_LAUNCH(conv3x3_wgrad_smallc_kernel<9>, dim3(pl.S), dim3(256), lds, st, p);
-        break;
-      }
-      default: return UNETK_E_UNSUPPORTED;
-    }
-    UNETK_LAUNCH_CHECK();
-  }
-  if (pl.S == 1) return UNETK_OK;
-  return unetk_launch_slab_reduce((const float*)ws + 64, pl.S, (int64_t)KD * 9 * p.Cin * p.Cout, dw, st);
+#ifdef UNETK_V3_PROBE
+  // probe build only (tools/probe_v3.sh; WRONG results, timing) of conv3x3_wgrad_bf16s_kernel: 4 = no staging requests, 16 = no
+  // barriers, 32 = no epilogue (LDS exchange, slab store, slab_reduce), 2048 = one request behind each of the first five MFMA
+  // groups instead of five in a row
+  if (pl.family == WG_BF16S || pl.family == WG_BF16S_C3) { const char* e = getenv("UNETK_V3_FLAGS"); p.dbg = e ? atoi(e) : 0; }
+#endif
+  const int rc = launch_plan(pl, p, st);
+  if (rc != UNETK_OK || pl.S == 1) return rc;
+#ifdef UNETK_V3_PROBE
+  if (p.dbg & 32) return UNETK_OK;
+#endif
+  return unetk_launch_slab_reduce((const float*)ws + 64, pl.S, pl.slab_elems, dw, st);
+}
+
+static WgShape desc_shape(const unetk_conv_desc* d) {
+  return WgShape{d->N, d->H, d->W, d->Cin, d->Cout, d->precision, 1, d->dilation, 1};
 }
 
 extern "C" size_t unetk_conv3x3_wgrad_ws_bytes(const unetk_conv_desc* d) {
   if (!d || d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0) return 0;
-  if (d->precision == UNETK_BF16S) return unetk_wgrad_bf16s_ws_bytes(d->N, d->H, d->W, d->Cin, d->Cout);
-  return unetk_wgrad_ws_bytes(d->N, d->H, d->W, d->Cin, d->Cout);
+  const WgPlan pl = unetk_wgrad_plan(desc_shape(d));
+  return pl.rc == UNETK_OK ? pl.ws_bytes : 0;
 }
 
 extern "C" int unetk_conv3x3_wgrad(const unetk_conv_desc* d, const void* xv, const void* dyv, float* dw,
@@ -840,19 +798,10 @@ extern "C" int unetk_conv3x3_wgrad(const unetk_conv_desc* d, const void* xv, con
   UNETK_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0);
   UNETK_REQUIRE(d->x_stride >= d->Cin && d->y_stride >= d->Cout);
   UNETK_REQUIRE(unetk_aligned16(x) && unetk_aligned16(dy) && unetk_aligned16(dw) && unetk_aligned16(ws));
-  if (d->precision == UNETK_BF16S) {        // x and dy are bf16 (x fp32 for the first layer); stride 1, dense taps only
-    if (d->dilation > 1) return UNETK_E_UNSUPPORTED;
-    WgParams q{};
-    q.x = x; q.dy = dy;
-    q.N = d->N; q.H = d->H; q.W = d->W; q.Cin = d->Cin; q.Cout = d->Cout; q.xs = d->x_stride; q.ys = d->y_stride;
-    q.xa = unetk_dense_addr(q.H, q.W, q.xs);
-    q.ya = unetk_dense_addr(q.H, q.W, q.ys);
-    return unetk_wgrad_bf16s_run(q, dw, ws, ws_bytes, (hipStream_t)stream);
-  }
   WgParams p{};
-  p.x = x; p.dy = dy;
+  p.x = x; p.dy = dy;       // UNETK_BF16S: bf16 (x fp32 for the first layer)
   p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout; p.xs = d->x_stride; p.ys = d->y_stride;
-  p.bf16 = d->precision == UNETK_BF16;     // small-Cin layers (first conv) ignore it: they run the fp32 kernels
+  p.bf16 = d->precision;    // small-Cin layers (first conv) ignore UNETK_BF16: they run the fp32 kernels
   p.dil = d->dilation;
   p.xa = unetk_dense_addr(p.H, p.W, p.xs);
   p.ya = unetk_dense_addr(p.H, p.W, p.ys);

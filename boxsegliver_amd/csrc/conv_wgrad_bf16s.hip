@@ -487,83 +487,46 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_c3_bf16s_kernel(WgParams p)
   }
 }
 
-struct Plan {
-  int tiles_h, tiles_w, total_tiles, S, tiles_per_split, n_ci_tiles, n_co_tiles;
-  bool small;   // first-layer kernel
-};
+}  // namespace
 
-bool plan(int N, int H, int W, int Cin, int Cout, Plan* pl) {
-  pl->tiles_h = (H + TH - 1) / TH;
-  pl->tiles_w = (W + TW - 1) / TW;
-  pl->total_tiles = N * pl->tiles_h * pl->tiles_w;
-  int S;
-  if (Cin % CT == 0 && Cout % CT == 0) {
-    pl->small = false;
-    pl->n_ci_tiles = Cin / CT;
-    pl->n_co_tiles = Cout / CT;
-    const int panels = pl->n_ci_tiles * pl->n_co_tiles;
+bool unetk_wgrad_plan_bf16s(const WgShape& s, WgPlan& pl, int* want) {
+  if (s.Cin % CT == 0 && s.Cout % CT == 0) {
+    pl.family = WG_BF16S;
+    pl.n_ci_tiles = s.Cin / CT;
+    pl.n_co_tiles = s.Cout / CT;
+    const int panels = pl.n_ci_tiles * pl.n_co_tiles;
     // ONE round of blocks: 256 CUs x one 512-thread block (160 KB of LDS) -- all blocks do equal work, and every extra
     // split costs a 9 x Cin x Cout slab written and read again (with >= 256 panels there is no split and no reduction)
-    S = panels >= 256 ? 1 : (256 + panels - 1) / panels;
-  } else if (9 * Cin <= 32 && Cout == CT) {
-    pl->small = true;
-    pl->n_ci_tiles = pl->n_co_tiles = 1;
-    S = 1024;         // = the resident blocks (four per CU): measured 2048 / 1024 / 512 splits -> 0.163 / 0.146 / 0.155 ms
+    *want = panels >= 256 ? 1 : (256 + panels - 1) / panels;
+  } else if (9 * s.Cin <= 32 && s.Cout == CT) {
+    pl.family = WG_BF16S_C3;
+    pl.n_ci_tiles = pl.n_co_tiles = 1;
+    *want = 1024;     // = the resident blocks (four per CU): measured 2048 / 1024 / 512 splits -> 0.163 / 0.146 / 0.155 ms
   } else {
     return false;
   }
-  if (S > pl->total_tiles) S = pl->total_tiles;
-  if (S < 1) S = 1;
-  pl->tiles_per_split = (pl->total_tiles + S - 1) / S;
-  pl->S = (pl->total_tiles + pl->tiles_per_split - 1) / pl->tiles_per_split;
   return true;
 }
 
-}  // namespace
-
-size_t unetk_wgrad_bf16s_ws_bytes(int N, int H, int W, int Cin, int Cout) {
-  Plan pl;
-  if (!plan(N, H, W, Cin, Cout, &pl)) return 0;
-  return 256 + (size_t)pl.S * 9 * Cin * Cout * sizeof(float);    // 256 B zero page + slabs
-}
-
-int unetk_wgrad_bf16s_run(WgParams p, float* dw, void* ws, size_t ws_bytes, hipStream_t st) {
-  Plan pl;
-  if (!plan(p.N, p.H, p.W, p.Cin, p.Cout, &pl)) return UNETK_E_UNSUPPORTED;
-  if (ws_bytes < unetk_wgrad_bf16s_ws_bytes(p.N, p.H, p.W, p.Cin, p.Cout)) return UNETK_E_WORKSPACE;
-  if (p.ys % 8 != 0 || (!pl.small && p.xs % 8 != 0)) return UNETK_E_BADARG;       // 16-byte chunks of 8 bf16
-  if ((int64_t)p.H * p.W * (p.xs > p.ys ? p.xs : p.ys) * 2 >= (int64_t(1) << 31)) return UNETK_E_UNSUPPORTED;   // 32-bit offsets inside an image
-  p.zeros = nullptr;
-#ifdef UNETK_V3_PROBE
-  // probe build only (tools/probe_v3.sh; WRONG results, timing): 4 = no staging requests, 16 = no barriers, 32 = no epilogue
-  // (LDS exchange, slab store, slab_reduce), 2048 = one request behind each of the first five MFMA groups instead of five in a row
-  { const char* e = getenv("UNETK_V3_FLAGS"); p.dbg = e ? atoi(e) : 0; }
-#endif
-  p.slab = pl.S == 1 ? dw : (float*)ws + 64;           // a single split writes the gradient in place
-  p.tiles_h = pl.tiles_h; p.tiles_w = pl.tiles_w; p.total_tiles = pl.total_tiles;
-  p.tiles_per_split = pl.tiles_per_split; p.n_ci_tiles = pl.n_ci_tiles; p.n_co_tiles = pl.n_co_tiles;
-  if (pl.small) {
+int unetk_wgrad_launch_bf16s(const WgPlan& pl, const WgParams& p, hipStream_t st) {
+  if (pl.family == WG_BF16S_C3) {
     const size_t lds3 = (size_t)(TH * TW * CT + HALO_PIX * 4) * sizeof(float);
-    UNETK_LAUNCH(conv3x3_wgrad_c3_bf16s_kernel, dim3(pl.S), dim3(256), lds3, st, p);
+    UNETK_LAUNCH(conv3x3_wgrad_c3_bf16s_kernel, dim3(pl.grid), dim3(256), lds3, st, p);
     UNETK_LAUNCH_CHECK();
-  } else {
-    static bool attr_done = false;
-    if (!attr_done) {
-      hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wgrad_bf16s_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B);
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)conv3x3_wgrad_bf16s_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B);
-      if (e != hipSuccess) return (int)e;
-      attr_done = true;
-    }
-    static int deep = -1;          // UNETK_WGRAD_DEEP=1 (measurement): three tiles of load flight, first fragments behind the barrier
-    if (deep < 0) { const char* e = getenv("UNETK_WGRAD_DEEP"); deep = e ? atoi(e) : 0; }
-    if (deep) UNETK_LAUNCH(conv3x3_wgrad_bf16s_kernel<false>, dim3(pl.S * pl.n_ci_tiles * pl.n_co_tiles), dim3(512), LDS_B, st, p);
-    else UNETK_LAUNCH(conv3x3_wgrad_bf16s_kernel<true>, dim3(pl.S * pl.n_ci_tiles * pl.n_co_tiles), dim3(512), LDS_B, st, p);
-    UNETK_LAUNCH_CHECK();
+    return UNETK_OK;
   }
-  if (pl.S == 1) return UNETK_OK;
-#ifdef UNETK_V3_PROBE
-  if (p.dbg & 32) return UNETK_OK;
-#endif
-  return unetk_launch_slab_reduce((const float*)ws + 64, pl.S, (int64_t)9 * p.Cin * p.Cout, dw, st);
+  static bool attr_done = false;
+  if (!attr_done) {
+    hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wgrad_bf16s_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute((const void*)conv3x3_wgrad_bf16s_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B);
+    if (e != hipSuccess) return (int)e;
+    attr_done = true;
+  }
+  static int deep = -1;          // UNETK_WGRAD_DEEP=1 (measurement): three tiles of load flight, first fragments behind the barrier
+  if (deep < 0) { const char* e = getenv("UNETK_WGRAD_DEEP"); deep = e ? atoi(e) : 0; }
+  if (deep) UNETK_LAUNCH(conv3x3_wgrad_bf16s_kernel<false>, dim3(pl.grid), dim3(512), LDS_B, st, p);
+  else UNETK_LAUNCH(conv3x3_wgrad_bf16s_kernel<true>, dim3(pl.grid), dim3(512), LDS_B, st, p);
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
 }

@@ -974,36 +974,43 @@ inline bool dw_bf16s4(const unetk_deconv3d_desc* d) {
 DwPlan dw_plan(const unetk_deconv3d_desc* d) {
   DwPlan pl{};
   const int M = d->N * d->D * d->H * d->W;
-  // fp32: one block takes all four sub-pixels of its (co, ci) panel (deconv_wgrad4_kernel) -- ~768 blocks of 40 KB LDS;
-  // the bf16 kernels take one sub-pixel per block -- ~1024 blocks
-  const bool four = d->precision == UNETK_FP32;
-  if (dw_bf16s4(d)) {     // deconv_wgrad_bf16s4_kernel: 64-pixel tiles, (Cout / 64) x (Cin / 128) panels, one block per CU and more
+  int want, mt;         // wanted splits, pixels per tile
+  if (dw_bf16s4(d)) {   // deconv_wgrad_bf16s4_kernel: 64-pixel tiles, (Cout / 64) x (Cin / 128) panels, one block per CU and more
     const int panels = (d->Cin / 128) * (d->Cout / 64);
-    int S = (256 + panels - 1) / panels;
-    const int mtiles = (M + 63) / 64;
-    if (S > mtiles) S = mtiles;
-    const int tiles_per = (mtiles + S - 1) / S;
-    pl.m_per_split = tiles_per * 64;
-    pl.S = (mtiles + tiles_per - 1) / tiles_per;
-    const ColMap m = unetk_colmap(d->Cout);
-    int64_t g = ((int64_t)4 * d->kd * M + m.rows_per_iter - 1) / m.rows_per_iter;
-    if (g > UNETK_COL_BLOCKS) g = UNETK_COL_BLOCKS;
-    pl.nblk_bias = (int)g;
-    return pl;
+    want = (256 + panels - 1) / panels;
+    mt = 64;
+  } else {
+    // fp32: one block takes all four sub-pixels of its (co, ci) panel (deconv_wgrad4_kernel) -- ~768 blocks of 40 KB LDS;
+    // the bf16 kernels take one sub-pixel per block -- ~1024 blocks
+    const bool four = d->precision == UNETK_FP32;
+    const int panels = (four ? 1 : 4) * (d->Cin / 64) * ((d->Cout + 63) / 64);
+    want = ((four ? 768 : 1024) + panels - 1) / panels;
+    mt = 128;
   }
-  const int panels = (four ? 1 : 4) * (d->Cin / 64) * ((d->Cout + 63) / 64);
-  int S = ((four ? 768 : 1024) + panels - 1) / panels;
-  const int mtiles = (M + 127) / 128;
-  if (S > mtiles) S = mtiles;
-  if (S < 1) S = 1;
-  const int tiles_per = (mtiles + S - 1) / S;
-  pl.m_per_split = tiles_per * 128;
-  pl.S = (mtiles + tiles_per - 1) / tiles_per;
+  const SplitK sk = unetk_split((M + mt - 1) / mt, want);
+  pl.S = sk.S;
+  pl.m_per_split = sk.per * mt;
   const ColMap m = unetk_colmap(d->Cout);
   int64_t g = ((int64_t)4 * d->kd * M + m.rows_per_iter - 1) / m.rows_per_iter;
   if (g > UNETK_COL_BLOCKS) g = UNETK_COL_BLOCKS;
   pl.nblk_bias = (int)g;
   return pl;
+}
+
+// The backward's workspace, in floats from its start: dpre (the masked, re-laid gradient), the bias-gradient partials, the row
+// reduction's scratch, a dbias sink for callers that pass NULL, and -- 4-float aligned -- the filter gradient's slabs.
+struct BwdLayout {
+  size_t bpart, btmp, bsink, slab, total;
+};
+BwdLayout bwd_layout(const unetk_deconv3d_desc* d, const DwPlan& pl) {
+  BwdLayout l;
+  const size_t M = (size_t)d->N * d->D * d->H * d->W;
+  l.bpart = 4 * d->kd * M * d->Cout;
+  l.btmp = l.bpart + (size_t)pl.nblk_bias * d->Cout;
+  l.bsink = l.btmp + unetk_rows_reduce_tmp_floats(1, pl.nblk_bias, d->Cout);
+  l.slab = (l.bsink + (size_t)d->Cout + 3) & ~(size_t)3;
+  l.total = l.slab + (size_t)pl.S * 4 * d->Cin * d->Cout;
+  return l;
 }
 
 unetk_deconv3d_desc from2d(const unetk_deconv_desc* d) {
@@ -1099,15 +1106,7 @@ extern "C" int unetk_deconv3d_fwd(const unetk_deconv3d_desc* d, const void* xv, 
 
 extern "C" size_t unetk_deconv3d_bwd_ws_bytes(const unetk_deconv3d_desc* d) {
   if (!deconv_desc_ok(d) || !deconv_bwd_ok(d)) return 0;
-  const DwPlan pl = dw_plan(d);
-  const size_t M = (size_t)d->N * d->D * d->H * d->W;
-  size_t f = 4 * d->kd * M * d->Cout;                       // dpre
-  f += (size_t)pl.nblk_bias * d->Cout;                      // bias partials
-  f += unetk_rows_reduce_tmp_floats(1, pl.nblk_bias, d->Cout);
-  f += (size_t)d->Cout;                                     // dbias sink when the caller passes NULL
-  f = (f + 3) & ~(size_t)3;
-  f += (size_t)pl.S * 4 * d->Cin * d->Cout;                 // wgrad slabs
-  return f * sizeof(float);
+  return bwd_layout(d, dw_plan(d)).total * sizeof(float);
 }
 
 extern "C" int unetk_deconv3d_bwd(const unetk_deconv3d_desc* d, const void* xv, const void* wpv,
@@ -1137,13 +1136,9 @@ extern "C" int unetk_deconv3d_bwd_parts(const unetk_deconv3d_desc* d, const void
   hipStream_t st = (hipStream_t)stream;
   const DwPlan pl = dw_plan(d);
   const int M = d->N * d->D * d->H * d->W;
+  const BwdLayout lay = bwd_layout(d, pl);
   float* dpre = (float*)ws;
-  float* bpart = dpre + (size_t)4 * d->kd * M * d->Cout;
-  float* btmp = bpart + (size_t)pl.nblk_bias * d->Cout;
-  float* bsink = btmp + unetk_rows_reduce_tmp_floats(1, pl.nblk_bias, d->Cout);
-  size_t off = (size_t)(bsink + d->Cout - dpre);
-  off = (off + 3) & ~(size_t)3;
-  float* slab = dpre + off;
+  float *bpart = dpre + lay.bpart, *btmp = dpre + lay.btmp, *bsink = dpre + lay.bsink, *slab = dpre + lay.slab;
 
   int rc = UNETK_OK;
   if (parts & 1) {

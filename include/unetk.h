@@ -177,7 +177,9 @@ int unetk_conv3x3_dgrad_nbr(const unetk_conv_desc* d, const void* dy, const void
                             const float* rstd, int per_sample, float* partials, void* stream);
 
 /* dw[HWIO] = conv3x3_filter_grad(x, dy).  Split-K over pixel tiles through a workspace of
- * fixed-order partial slabs (bit-reproducible). */
+ * fixed-order partial slabs (bit-reproducible).  The query is exact for the launch the descriptor names, its precision and
+ * dilation included (256 + splits x 9 x Cin x Cout x 4 bytes), and 0 where the launch is refused: ask with the descriptor
+ * you will run. */
 size_t unetk_conv3x3_wgrad_ws_bytes(const unetk_conv_desc* d);
 int unetk_conv3x3_wgrad(const unetk_conv_desc* d, const void* x, const void* dy, float* dw,
                         void* ws, size_t ws_bytes, void* stream);

@@ -2,7 +2,7 @@
 tests/test_conv3d_bf16_paths_host.py (no GPU).  Nothing here touches the device unless a caller asks for dev="cuda".
 
 Every row was written out by hand from the predicates of csrc/conv_igemm_bf16.hip (pick_bf16, unetk_conv_plan_bf16,
-unetk_conv_launch_bf16), csrc/conv_wgrad.hip (wg_plan(..., bf16 = true, kd), unetk_wgrad_run, unetk_launch_slab_reduce) and
+unetk_conv_launch_bf16), csrc/conv_wgrad.hip (unetk_wgrad_plan at UNETK_BF16 with kd, unetk_wgrad_run, unetk_launch_slab_reduce) and
 csrc/conv3d.hip (unetk_conv3d_{fwd,dgrad,wgrad}_bf16: the forward picks its tile from (N D, H, W, Cin, Cout), the input gradient
 from the same with Cin and Cout swapped).  pick_bf16 / wg_splits below restate those predicates; the host test holds every row
 against them, so that a row and the restatement can only be wrong together, and the device test holds every row against the
@@ -113,7 +113,7 @@ def pick_bf16(h, cin, cout, n, w):
 
 
 def wg_splits(n, h, w, cin, cout, kd):
-    """csrc/conv_wgrad.hip wg_plan(N, H, W, Cin, Cout, bf16 = true, kd): (cit, cot, splits S)."""
+    """csrc/conv_wgrad.hip unetk_wgrad_plan at UNETK_BF16 (plain tiles, unetk_split): (cit, cot, splits S)."""
     total = n * _cd(h, WG_TH) * _cd(w, TW)
     cit, cot = (64 if cin % 64 == 0 else 32), (64 if cout % 64 == 0 else 32)
     panels = (cin // cit) * (cout // cot) * (kd if kd > 1 else 1)

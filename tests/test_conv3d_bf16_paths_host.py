@@ -2,7 +2,7 @@
 tell a wrong kernel from a right one.
 
 Every row's hand-written kernel names, statistic rows, tile geometry and filter-gradient splits agree with a Python restatement
-of pick_bf16 / wg_plan / unetk_launch_slab_reduce; the table as a whole names every kernel the device test must reach; both
+of pick_bf16 / unetk_wgrad_plan / unetk_launch_slab_reduce; the table as a whole names every kernel the device test must reach; both
 exact input sets are bf16-representable and stay inside the exact regime (so a table edit cannot leave it silently); and for
 each way a fused-depth-tap kernel can plausibly be wrong -- depth taps leaking across samples, reversed, clamped instead of
 zero-padded, one (tap, 32-channel chunk) step dropped, a missing plane's filter gradient copied from the middle tap -- the wrong

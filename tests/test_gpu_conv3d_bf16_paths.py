@@ -13,7 +13,7 @@ dw[2]), D = 1 and D = 2 with N > 1 (the neighbour plane in memory is another sam
 planes with partial tiles both ways and planes smaller than a tile.
 
 How the table was derived.  Every row names its forward kernel, statistic rows and tile geometry, its input-gradient kernel
-and its filter-gradient launches, written out by hand from pick_bf16, unetk_conv_plan_bf16, wg_plan(..., bf16 = true, kd)
+and its filter-gradient launches, written out by hand from pick_bf16, unetk_conv_plan_bf16, unetk_wgrad_plan (UNETK_BF16, kd)
 and unetk_wgrad_run; tests/test_conv3d_bf16_paths_host.py holds the rows against a restatement of those predicates without a
 device.  Here the library's launch trace of every call must equal the row exactly, so a row that lands elsewhere after a
 dispatch change fails instead of quietly testing something else.

@@ -9,9 +9,9 @@ sparse input set (x, w in {-1, 0, 1}, density chosen so that max |y| <= 15) make
 
 Each row of CASES names the kernels it exists to reach (forward, input gradient, filter gradient, and the same for UNETK_BF16 /
 UNETK_BF16S where unetk_conv_bf16_ok admits the row), written out by hand from the plan parts of csrc/conv_igemm.hip (tiled_bn,
-small_grid, big_grid, unetk_conv_plan), csrc/conv_igemm_lin.hip (lin_ok, lin_bm, sk_plan), csrc/conv_wgrad.hip (wg_plan,
-unetk_wgrad_run), csrc/conv_igemm_bf16.hip (pick_bf16), csrc/conv_igemm_bf16s.hip (unetk_conv_plan_bf16s_v3) and
-csrc/conv_wgrad_bf16s.hip (plan).  The library's launch trace must show exactly those kernels, so a row that lands elsewhere
+small_grid, big_grid, unetk_conv_plan), csrc/conv_igemm_lin.hip (lin_ok, lin_bm, sk_plan), csrc/conv_wgrad.hip (unetk_wgrad_plan,
+launch_plan), csrc/conv_igemm_bf16.hip (pick_bf16), csrc/conv_igemm_bf16s.hip (unetk_conv_plan_bf16s_v3) and
+csrc/conv_wgrad_bf16s.hip (unetk_wgrad_plan_bf16s).  The library's launch trace must show exactly those kernels, so a row that lands elsewhere
 after a dispatch change fails instead of quietly testing something else.  `None` = the entry point refuses the shape (the row
 then skips that op; test_refusals covers the refusals themselves).
 
@@ -393,22 +393,27 @@ REQUIRED = [
     "conv3x3_c3_mfma_kernel<1,unsignedshort,false>", "conv3x3_c3_mfma_kernel<2,unsignedshort,false>",
     "conv3x3_c3_mfma_kernel<3,unsignedshort,false>",
 ]
-# filter-gradient plans (wg_plan): row -> (splits S, what the row is there for).  Where Cin or Cout is not a multiple of 64 the
-# workspace unetk_conv3x3_wgrad_ws_bytes asks for is exactly 256 + S x 9 Cin Cout x 4 bytes, so S is asserted against the library
-# (observable = True).  For 64-multiple channels the query is the largest of this plan, the plain-tile plan of UNETK_BF16 and the
-# 6-row atrous plan, which hides S: those entries are documentation, and only the reducer the trace shows (S >= 64: <16>,
-# 8 .. 63: <4>, 2 .. 7: <1>, 1: none) ties them to the library.
+# filter-gradient plans (unetk_wgrad_plan): row -> (splits S of the fp32 launch, splits of the UNETK_BF16 launch where the row has
+# that tier, what the row is there for).  unetk_conv3x3_wgrad_ws_bytes reads the plan of the launch the descriptor names -- its
+# precision and dilation included -- and asks for exactly 256 + S x 9 Cin Cout x 4 bytes, so every S is asserted against the
+# library, and against the reducer the row's trace names (S >= 64: <16>, 8 .. 63: <4>, 2 .. 7: <1>, 1: none).  UNETK_BF16 has
+# no stacked-plane tiles: on those rows it splits the plain 8 x 16 tiles.
 WG_PLANS = {
-    "t4_b383": (128, True, "one-round branch (256 / 2 panels); 383 tiles = 127 splits of 3 + one of 2: ragged last split"),
-    "t8_big511": (128, True, "one-round branch; 1022 tiles = 127 splits of 8 + one of 6: ragged last split"),
-    "n32_ragged": (18, True, "18 tiles, one each"),
-    "wg_1tile": (1, False, "one tile: S == 1, dw written in place, no reducer in the trace"),
-    "t4_gpix120": (1, False, "one tile"),
-    "wg_s5": (5, False, "five tiles, five splits: slab_reduce_kernel<1>"),
-    "t8_c256": (31, False, "total_tiles / S >= 16: the two-round plan (512 / 16 panels = 32 -> 31 splits of 17 tiles, the last has 10)"),
-    "lin128_24": (10, False, "stacked 10 x 12: N (H + 1) = 50 rows -> 5 tile rows x 2 columns"),
-    "wg_stk12": (18, False, "stacked 10 x 12: N (H + 1) = 175 rows -> 18 tile rows, the last half empty, planes cross tiles"),
-    "wg_stk6": (25, False, "stacked 20 x 6: N (H + 1) = 490 rows -> 25 tile rows, the last half empty"),
+    "t4_b383": (128, 128, "one-round branch (256 / 2 panels); 383 tiles = 127 splits of 3 + one of 2: ragged last split"),
+    "t8_big511": (128, 128, "one-round branch; 1022 tiles = 127 splits of 8 + one of 6: ragged last split"),
+    "n32_ragged": (18, 18, "18 tiles, one each"),
+    "wg_1tile": (1, 1, "one tile: S == 1, dw written in place, no reducer in the trace"),
+    "t4_gpix120": (1, 1, "one tile"),
+    "wg_s5": (5, 5, "five tiles, five splits: slab_reduce_kernel<1>"),
+    "t8_c256": (31, 31, "total_tiles / S >= 16: the two-round plan (512 / 16 panels = 32 -> 31 splits of 17 tiles, the last has 10)"),
+    "lin128_24": (10, 12, "stacked 10 x 12: N (H + 1) = 50 rows -> 5 tile rows x 2 columns; bf16: 2 x 3 x 2 plain tiles"),
+    "wg_stk12": (18, 21, "stacked 10 x 12: N (H + 1) = 175 rows -> 18 tile rows, the last half empty, planes cross tiles; bf16: 7 x 3 x 1"),
+    "wg_stk6": (25, 35, "stacked 20 x 6: N (H + 1) = 490 rows -> 25 tile rows, the last half empty; bf16: 70 plain tiles, "
+                        "one round of 256 / 4 panels = 64 -> 35 splits of 2"),
+    "atrous128": (16, None, "6 x 16 tiles: 2 x 4 x 2 = 16, one each (512 / 2 panels wanted, floor)"),
+    "atrous64": (16, None, "6 x 16 tiles: 16, one each"),
+    "atrous64_1x1": (3, None, "one tile per image"),
+    "atrous128_2x3": (3, None, "one tile per image"),
 }
 
 # forward bound of the Gaussian tier where fp32 arithmetic alone exceeds 2e-6 (see the module docstring): 4 x the CPU float32 error
@@ -612,15 +617,18 @@ def test_table_ids_are_unique_and_plans_are_as_stated():
     L = lib()
     L.unetk_conv3x3_wgrad_ws_bytes.restype = ctypes.c_size_t
     assert len(BY_ID) == len(CASES)
-    for rid, (S, observable, _) in WG_PLANS.items():
+    for rid, (S, S_bf16, _) in WG_PLANS.items():
         c = BY_ID[rid]
-        if observable:
-            d = _desc(c.n, c.h, c.w, c.cin, c.cout)
+        assert (S_bf16 is not None) == (c.bf16 is not None), rid
+        for prec, s_want, names in ((FP32, S, c.wgrad), (BF16, S_bf16, c.bf16[3] if c.bf16 else None)):
+            if s_want is None:
+                continue
+            d = _desc(c.n, c.h, c.w, c.cin, c.cout, prec=prec, dil=c.dil)
             got = (L.unetk_conv3x3_wgrad_ws_bytes(ctypes.byref(d)) - 256) / (9.0 * c.cin * c.cout * 4)
-            assert got == S, (rid, got, S)
-        red = [n for n in c.wgrad if n.startswith("slab_reduce")]
-        want = [] if S == 1 else ["slab_reduce_kernel<{}>".format(16 if S >= 64 else 4 if S >= 8 else 1)]
-        assert red == want, (rid, red, want)
+            assert got == s_want, (rid, prec, got, s_want)
+            red = [n for n in names if n.startswith("slab_reduce")]
+            want = [] if s_want == 1 else ["slab_reduce_kernel<{}>".format(16 if s_want >= 64 else 4 if s_want >= 8 else 1)]
+            assert red == want, (rid, prec, red, want)
 
 
 @pytest.mark.parametrize("kind", ["eighths", "sparse"])

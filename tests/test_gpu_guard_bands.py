@@ -526,6 +526,11 @@ CONV3D_ROWS = [
      ("dilate2_kernel", WG + "32, 32, false, 8, 16, false, 1, 1>")),
     ("first_layer", (2, 4, 16, 40, 1, 32, 3, 1, 1), 0, 32, None, ("zero_slice_kernel", "conv3x3_direct_kernel<1, float>"), None,
      ("conv3x3_wgrad_c3_kernel<32>",)),
+    # the filter gradient runs one launch per depth tap, and taps 0 and 2 reach 7 of the 8 planes: 504 tiles in 504 splits of
+    # one tile, where the 576 tiles of all 8 planes make 288 splits of two (the split count is not monotone in the tiles).
+    # The workspace query has to size the slabs of the launches that run, not of a launch over every plane.
+    ("first_layer_resplit", (1, 8, 96, 96, 1, 32, 3, 1, 1), 0, 0, None, ("conv3x3_direct_kernel<1, float>",), None,
+     ("conv3x3_wgrad_c3_kernel<32>",)),
 ]
 
 
