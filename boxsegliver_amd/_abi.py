@@ -187,6 +187,8 @@ _SIGNATURES = {
     "unetk_guide_components_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "unetk_guide_components": (c_int, [P, P, c_int, c_int, c_int, P, P, c_size_t, P]),
     "unetk_guide_render": (c_int, [P, c_int, c_int, c_int, c_float, P, P]),
+    "unetk_component_overlaps_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "unetk_component_overlaps": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_size_t, P]),
     "unetk_eval_slab": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, P, P, c_int, P, P, P, c_int, P, c_int, c_int, c_int,
                                 P, P]),
     "unetk_zoom_nearest3d": (c_int, [P, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, P, P]),

@@ -714,6 +714,240 @@ __global__ __launch_bounds__(EV_BLOCK) void gc_final_kernel(int H, int W, int ca
   row[11] = __float_as_int(sx);
 }
 
+// ---------------------------------------------------------------- component overlaps of two masks (per-lesion detection)
+// utils/array_kits.py:883-984 distinct_binary_object_correspondences asks, per reference object, which result objects it
+// shares voxels with and how many.  Both masks are labelled by lc_init / lc_merge / lc_flatten; roots are numbered in
+// increasing linear index over tiles of CO_TILE voxels (count, scan, write); the pairs are keyed by their two roots
+// (reference root high, result root low: the order of the keys is the order of the (ref_id, res_id) pairs), made distinct
+// in an open-addressing table of n slots, ranked among themselves, and counted per voxel against the ranked list.  Every
+// value written is an integer that no order of the atomics changes.
+constexpr int CO_TILE = EV_BLOCK * 16;       // voxels per block of the numbering kernels
+constexpr int CO_SCAN = 1024;                // threads of the tile-count scan
+constexpr int CO_MAX_CAP = 1 << 24;          // cap_obj, cap_pair: row indices times the row width stay far inside an int
+constexpr unsigned long long CO_EMPTY = ~0ull;   // no key: roots are < 2^31
+
+static inline int co_tiles(int64_t n) { return (int)((n + CO_TILE - 1) / CO_TILE); }
+
+__global__ __launch_bounds__(EV_BLOCK) void co_fill_kernel(unsigned long long* __restrict__ p, int64_t n, unsigned long long v) {
+  for (int64_t i = (int64_t)blockIdx.x * EV_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * EV_BLOCK) p[i] = v;
+}
+
+// tsum[m * nt + b] = number of roots of mask m (blockIdx.y) in tile b
+__global__ __launch_bounds__(EV_BLOCK) void co_tile_roots_kernel(int n, const int* __restrict__ label0,
+                                                                 const int* __restrict__ label1, int nt, int* __restrict__ tsum) {
+  __shared__ int red[EV_BLOCK / 64];
+  const int* label = blockIdx.y ? label1 : label0;
+  const int64_t base = (int64_t)blockIdx.x * CO_TILE;
+  int c = 0;
+  for (int j = 0; j < CO_TILE / EV_BLOCK; ++j) {
+    const int64_t i = base + j * EV_BLOCK + threadIdx.x;
+    c += (i < n && label[i] == (int)i) ? 1 : 0;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int s = 0;
+#pragma unroll
+    for (int j = 0; j < EV_BLOCK / 64; ++j) s += red[j];
+    tsum[(int64_t)blockIdx.y * nt + blockIdx.x] = s;
+  }
+}
+
+// one block per mask: tsum -> its exclusive prefix sums; head[m] = number of components, head[3] bit m = more than cap_obj
+__global__ __launch_bounds__(CO_SCAN) void co_scan_kernel(int nt, int* __restrict__ tsum, int cap_obj, int32_t* __restrict__ table) {
+  __shared__ int part[CO_SCAN];
+  int* s = tsum + (int64_t)blockIdx.x * nt;
+  const int t = threadIdx.x;
+  const int per = (nt + CO_SCAN - 1) / CO_SCAN;
+  const int lo = min(nt, t * per), hi = min(nt, lo + per);
+  int sum = 0;
+  for (int k = lo; k < hi; ++k) sum += s[k];
+  part[t] = sum;
+  __syncthreads();
+  for (int o = 1; o < CO_SCAN; o <<= 1) {
+    const int v = t >= o ? part[t - o] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  int run = part[t] - sum;
+  for (int k = lo; k < hi; ++k) {
+    const int c = s[k];
+    s[k] = run;
+    run += c;
+  }
+  if (t == CO_SCAN - 1) {
+    table[blockIdx.x] = part[t];
+    if (part[t] > cap_obj) atomicOr(table + 3, 1 << blockIdx.x);
+  }
+}
+
+// rows {root, size} of mask m (blockIdx.y) for the roots of rank < cap_obj: rank = roots in the tiles before (tsum) +
+// before this pass of the tile + before this wave + before this lane, as gc_enum_kernel ranks them
+__global__ __launch_bounds__(EV_BLOCK) void co_rows_kernel(int n, const int* __restrict__ label0, const int* __restrict__ label1,
+                                                           const int* __restrict__ cnt0, const int* __restrict__ cnt1, int nt,
+                                                           const int* __restrict__ tsum, int cap_obj, int32_t* __restrict__ table) {
+  __shared__ int wsum[EV_BLOCK / 64];
+  const int* label = blockIdx.y ? label1 : label0;
+  const int* cnt = blockIdx.y ? cnt1 : cnt0;
+  int32_t* rows = table + 4 + (int64_t)blockIdx.y * 2 * cap_obj;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t first = (int64_t)blockIdx.x * CO_TILE;
+  int base = tsum[(int64_t)blockIdx.y * nt + blockIdx.x];
+  for (int j = 0; j < CO_TILE / EV_BLOCK; ++j) {
+    const int64_t i = first + j * EV_BLOCK + threadIdx.x;
+    const bool root = i < n && label[i] == (int)i;
+    const unsigned long long b = __ballot(root);
+    if (lane == 0) wsum[wv] = __popcll(b);
+    __syncthreads();
+    int before = base, total = base;
+#pragma unroll
+    for (int q = 0; q < EV_BLOCK / 64; ++q) {
+      const int c = wsum[q];
+      before += q < wv ? c : 0;
+      total += c;
+    }
+    __syncthreads();                             // wsum is rewritten by the next pass
+    if (root) {
+      const int k = before + __popcll(b & ((1ull << lane) - 1ull));
+      if (k < cap_obj) {
+        rows[2 * (int64_t)k] = (int)i;
+        rows[2 * (int64_t)k + 1] = cnt[i];
+      }
+    }
+    base = total;
+  }
+}
+
+__device__ __forceinline__ int co_slot(unsigned long long k, int n) {          // murmur3's 64-bit finaliser, then [0, n)
+  k ^= k >> 33;
+  k *= 0xff51afd7ed558ccdull;
+  k ^= k >> 33;
+  k *= 0xc4ceb9fe1a85ec53ull;
+  k ^= k >> 33;
+  return (int)(((k & 0xffffffffull) * (unsigned long long)(unsigned)n) >> 32);
+}
+
+// The key of voxel i, CO_EMPTY outside the overlap.
+__device__ __forceinline__ unsigned long long co_key(int64_t i, int n, const int* __restrict__ lres, const int* __restrict__ lref) {
+  if (i >= n) return CO_EMPTY;
+  const int a = lref[i], b = lres[i];
+  return a >= 0 && b >= 0 ? ((unsigned long long)(unsigned)a << 32) | (unsigned)b : CO_EMPTY;
+}
+
+// Calls f(key, lanes holding it) once per distinct key of the wave, in the first lane that holds it: a whole lesion is one
+// key, so a wave inside it makes one table access, not 64 on one address.  Every lane of the wave must call this.
+template <class F>
+__device__ __forceinline__ void co_per_key(unsigned long long key, F f) {
+  unsigned long long todo = __ballot(key != CO_EMPTY);
+  while (todo) {
+    const int lead = __ffsll((long long)todo) - 1;
+    const unsigned long long k = __shfl(key, lead);
+    const unsigned long long same = __ballot(key == k);
+    if ((int)__lane_id() == lead) f(k, __popcll(same));
+    todo &= ~same;
+  }
+}
+
+// keys -> the table of n slots, each distinct key once.  Two face neighbours of the overlap share both components, so the
+// distinct pairs are at most ceil(n / 2): a free slot is always found; the probe count is bounded all the same.
+__global__ __launch_bounds__(EV_BLOCK) void co_insert_kernel(int n, const int* __restrict__ lres, const int* __restrict__ lref,
+                                                             unsigned long long* __restrict__ slots) {
+  const unsigned long long key = co_key((int64_t)blockIdx.x * EV_BLOCK + threadIdx.x, n, lres, lref);
+  co_per_key(key, [&](unsigned long long k, int) {
+    int s = co_slot(k, n);
+    for (int probe = 0; probe < n; ++probe) {
+      const unsigned long long cur = __hip_atomic_load(slots + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (cur == k) return;
+      if (cur == CO_EMPTY) {
+        const unsigned long long old = atomicCAS(slots + s, CO_EMPTY, k);
+        if (old == CO_EMPTY || old == k) return;
+      }
+      s = s + 1 == n ? 0 : s + 1;
+    }
+  });
+}
+
+// the used slots -> list (any order, the first cap_pair of them); head[2] = their number
+__global__ __launch_bounds__(EV_BLOCK) void co_compact_kernel(int n, const unsigned long long* __restrict__ slots, int cap_pair,
+                                                              unsigned long long* __restrict__ list, int32_t* __restrict__ table) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t i0 = (int64_t)blockIdx.x * EV_BLOCK; i0 < n; i0 += (int64_t)gridDim.x * EV_BLOCK) {
+    const int64_t i = i0 + threadIdx.x;
+    const unsigned long long k = i < n ? slots[i] : CO_EMPTY;
+    const unsigned long long b = __ballot(k != CO_EMPTY);
+    if (b == 0ull) continue;
+    const int lead = __ffsll((long long)b) - 1;
+    int at = 0;
+    if (lane == lead) at = atomicAdd(table + 2, __popcll(b));
+    at = __shfl(at, lead) + __popcll(b & ((1ull << lane) - 1ull));
+    if (k != CO_EMPTY && at < cap_pair) list[at] = k;
+  }
+}
+
+// the pair rows are written only when nothing overflowed: which cap_pair keys the list kept depends on the atomics
+__device__ __forceinline__ int co_listed(const int32_t* __restrict__ table, int cap_obj, int cap_pair) {
+  return table[0] > cap_obj || table[1] > cap_obj || table[2] > cap_pair ? 0 : table[2];
+}
+
+// rows[2 * j] over j in [0, count) ascending: the 1-based rank of `root`
+__device__ __forceinline__ int co_id(const int32_t* __restrict__ rows, int count, int root) {
+  int lo = 0, hi = count;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (rows[2 * (int64_t)mid] < root) lo = mid + 1; else hi = mid;
+  }
+  return lo + 1;
+}
+
+// rank of every listed key among them (keys are distinct): sorted[rank] = key and pair row rank = {ref_id, res_id, 0};
+// head[3] bit 2 = more than cap_pair pairs
+__global__ __launch_bounds__(EV_BLOCK) void co_rank_kernel(const unsigned long long* __restrict__ list, int cap_obj, int cap_pair,
+                                                           unsigned long long* __restrict__ sorted, int32_t* __restrict__ table) {
+  __shared__ unsigned long long tile[EV_BLOCK];
+  if (blockIdx.x == 0 && threadIdx.x == 0 && table[2] > cap_pair) atomicOr(table + 3, 4);
+  const int m = co_listed(table, cap_obj, cap_pair);
+  if ((int64_t)blockIdx.x * EV_BLOCK >= m) return;
+  const int g = blockIdx.x * EV_BLOCK + threadIdx.x;
+  const unsigned long long key = g < m ? list[g] : CO_EMPTY;
+  int rank = 0;
+  for (int t0 = 0; t0 < m; t0 += EV_BLOCK) {
+    const int j = t0 + threadIdx.x;
+    tile[threadIdx.x] = j < m ? list[j] : CO_EMPTY;
+    __syncthreads();
+    const int cnt = min(EV_BLOCK, m - t0);
+    for (int q = 0; q < cnt; ++q) rank += tile[q] < key ? 1 : 0;
+    __syncthreads();
+  }
+  if (g >= m) return;
+  sorted[rank] = key;
+  const int32_t* res_rows = table + 4;
+  const int32_t* ref_rows = table + 4 + 2 * (int64_t)cap_obj;
+  int32_t* row = table + 4 + 4 * (int64_t)cap_obj + 3 * (int64_t)rank;
+  row[0] = co_id(ref_rows, table[1], (int)(key >> 32));
+  row[1] = co_id(res_rows, table[0], (int)(key & 0xffffffffull));
+}
+
+// overlap of every listed pair: one add of the lane count per distinct key of a wave, at the key's place in the sorted list
+__global__ __launch_bounds__(EV_BLOCK) void co_count_kernel(int n, const int* __restrict__ lres, const int* __restrict__ lref,
+                                                            const unsigned long long* __restrict__ sorted, int cap_obj,
+                                                            int cap_pair, int32_t* __restrict__ table) {
+  const int m = co_listed(table, cap_obj, cap_pair);
+  if (m == 0) return;
+  const unsigned long long key = co_key((int64_t)blockIdx.x * EV_BLOCK + threadIdx.x, n, lres, lref);
+  int32_t* pairs = table + 4 + 4 * (int64_t)cap_obj;
+  co_per_key(key, [&](unsigned long long k, int lanes) {
+    int lo = 0, hi = m;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (sorted[mid] < k) lo = mid + 1; else hi = mid;
+    }
+    if (lo < m && sorted[lo] == k) atomicAdd(pairs + 3 * (int64_t)lo + 2, lanes);
+  });
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- C ABI
@@ -960,6 +1194,80 @@ extern "C" int unetk_guide_components(const float* acc, const float* guide, int 
   UNETK_LAUNCH_CHECK();
   UNETK_LAUNCH(gc_final_kernel, dim3((cap + EV_BLOCK - 1) / EV_BLOCK), dim3(EV_BLOCK), 0, st, H, W, cap, (const int*)hrow,
                (const int*)hcol, (const unsigned long long*)peak, table);
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
+// ---------------------------------------------------------------- component overlaps
+static inline bool co_caps_ok(int cap_obj, int cap_pair) {
+  return cap_obj > 0 && cap_pair > 0 && cap_obj <= CO_MAX_CAP && cap_pair <= CO_MAX_CAP;
+}
+
+// workspace: label of res, label of ref, size of res, size of ref (n int32 each; the two size arrays, read into the object
+// rows first, are then the n 64-bit slots of the pair table), lc_init's scalars, the tile sums, the pair list and its sorted copy
+extern "C" size_t unetk_component_overlaps_ws_bytes(int D, int H, int W, int cap_obj, int cap_pair) {
+  if (ev_dims(D, H, W) != UNETK_OK || !co_caps_ok(cap_obj, cap_pair)) return 0;
+  const int64_t n = (int64_t)D * H * W;
+  return 4 * ev_align((size_t)n * 4) + 256 + ev_align((size_t)2 * co_tiles(n) * 4) + 2 * ev_align((size_t)cap_pair * 8);
+}
+
+extern "C" int unetk_component_overlaps(const uint8_t* res, const uint8_t* ref, int D, int H, int W, int cap_obj, int cap_pair,
+                                        int32_t* table, void* ws, size_t ws_bytes, void* stream) {
+  const int dims = ev_dims(D, H, W);
+  if (dims != UNETK_OK) return dims;
+  UNETK_REQUIRE(res && ref && table && ws && unetk_aligned16(ws) && (((uintptr_t)table) & 3u) == 0);
+  UNETK_REQUIRE(co_caps_ok(cap_obj, cap_pair));
+  if (ws_bytes < unetk_component_overlaps_ws_bytes(D, H, W, cap_obj, cap_pair)) return UNETK_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int n = D * H * W, nt = co_tiles(n);
+  const size_t nb = ev_align((size_t)n * 4);
+  char* p = (char*)ws;
+  int* lres = (int*)p;
+  int* lref = (int*)(p + nb);
+  int* cres = (int*)(p + 2 * nb);
+  int* cref = (int*)(p + 3 * nb);
+  unsigned long long* slots = (unsigned long long*)(p + 2 * nb);      // over cres and cref, once the rows hold the sizes
+  char* q = p + 4 * nb;
+  unsigned long long* best = (unsigned long long*)q;                  // lc_init's scalars, unused here
+  int32_t* info = (int32_t*)(q + 16);
+  int* tsum = (int*)(q + 256);
+  unsigned long long* list = (unsigned long long*)(q + 256 + ev_align((size_t)2 * nt * 4));
+  unsigned long long* sorted = list + ev_align((size_t)cap_pair * 8) / 8;
+  const int64_t words = 4 + 4 * (int64_t)cap_obj + 3 * (int64_t)cap_pair;
+  const int g = ev_grid1(n);
+  UNETK_LAUNCH(sh_zero_kernel, dim3(ev_blocks(words)), dim3(EV_BLOCK), 0, st, table, words);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(lc_init_kernel, dim3(g), dim3(EV_BLOCK), 0, st, res, n, lres, cres, best, info);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(lc_merge_kernel, dim3(g), dim3(EV_BLOCK), 0, st, res, D, H, W, lres);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(lc_flatten_kernel, dim3(g), dim3(EV_BLOCK), 0, st, n, lres, cres);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(lc_init_kernel, dim3(g), dim3(EV_BLOCK), 0, st, ref, n, lref, cref, best, info);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(lc_merge_kernel, dim3(g), dim3(EV_BLOCK), 0, st, ref, D, H, W, lref);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(lc_flatten_kernel, dim3(g), dim3(EV_BLOCK), 0, st, n, lref, cref);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(co_tile_roots_kernel, dim3(nt, 2), dim3(EV_BLOCK), 0, st, n, (const int*)lres, (const int*)lref, nt, tsum);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(co_scan_kernel, dim3(2), dim3(CO_SCAN), 0, st, nt, tsum, cap_obj, table);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(co_rows_kernel, dim3(nt, 2), dim3(EV_BLOCK), 0, st, n, (const int*)lres, (const int*)lref, (const int*)cres,
+               (const int*)cref, nt, (const int*)tsum, cap_obj, table);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(co_fill_kernel, dim3(ev_blocks(n)), dim3(EV_BLOCK), 0, st, slots, (int64_t)n, CO_EMPTY);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(co_insert_kernel, dim3(g), dim3(EV_BLOCK), 0, st, n, (const int*)lres, (const int*)lref, slots);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(co_compact_kernel, dim3(ev_blocks(n)), dim3(EV_BLOCK), 0, st, n, (const unsigned long long*)slots, cap_pair, list,
+               table);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(co_rank_kernel, dim3((cap_pair + EV_BLOCK - 1) / EV_BLOCK), dim3(EV_BLOCK), 0, st,
+               (const unsigned long long*)list, cap_obj, cap_pair, sorted, table);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(co_count_kernel, dim3(g), dim3(EV_BLOCK), 0, st, n, (const int*)lres, (const int*)lref,
+               (const unsigned long long*)sorted, cap_obj, cap_pair, table);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }

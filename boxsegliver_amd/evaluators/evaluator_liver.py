@@ -18,6 +18,8 @@ What runs where (MI355X-first):
     argmax volume again), then class split, merge tumor into liver, largest connected component (_postprocess_device),
     the per-case volume metrics (loss_metrics.metric_3d_device) and the global Dice counts run in csrc/evalvol.hip.
     metrics_on="host" keeps the reference's host path (_postprocess, loss_metrics.metric_3d, ConfusionMatrix).
+    --eval_detection adds per-lesion detection of the Tumor class to either path (loss_metrics.tumor_detection_metrics_device:
+    `unetk_component_overlaps`, one table read, the matching on the host; or tumor_detection_metrics).
   * DEVICE, then a HOST THREAD (-s/--save_predict, `maybe_save_case` :998-1026; _CaseSaver below): a case that
     is on the device and scored there is post-processed once, composed into the whole volume in NIfTI file order by
     `unetk_nii_compose` and copied once into a pinned buffer on a side stream; utils/volume_writer writes
@@ -56,6 +58,8 @@ from .evaluator_base import EvaluateBase
 
 log = logging.getLogger("boxsegliver_amd")
 
+DETECTION_CLASS = "Tumor"            # --eval_detection: the class whose objects are lesions
+
 
 def add_arguments(parser):
     """evaluators/evaluator_liver.py:36-71 (names / defaults verbatim)."""
@@ -78,6 +82,12 @@ def add_arguments(parser):
                        help="Generate prediction or probability")
     group.add_argument("--save_path", type=str, default="prediction")
     group.add_argument("--use_global_dice", action="store_true")
+    # project extensions (off by default)
+    group.add_argument("--eval_detection", action="store_true",
+                       help="Also score per-lesion detection of the Tumor class: <Tumor>/DetTP, DetFP, DetPos, Precision, Recall")
+    group.add_argument("--detection_thresh", type=float, default=0.5,
+                       help="--eval_detection: a reference lesion is found when its Dice coefficient with a predicted object "
+                            "(2 overlap / (size + size); the reference code names it iou) reaches this value")
 
 
 def get_evaluator(evaluator, estimator=None, model_dir=None, params=None, merge_tumor_to_liver=True, largest=True,
@@ -136,6 +146,11 @@ class EvaluateVolume(EvaluateBase):
         self.merge_tumor_to_liver = merge_tumor_to_liver
         self.largest = largest
         self.use_sg_reduce_fp = bool(use_sg_reduce_fp and getattr(self.config, "use_spatial", False))
+        self.eval_detection = bool(getattr(self.config, "eval_detection", False))
+        self.detection_thresh = float(getattr(self.config, "detection_thresh", 0.5))
+        if self.eval_detection and DETECTION_CLASS not in list(getattr(self.config, "classes", None) or []):
+            raise ValueError("--eval_detection scores the {} class, which is not among --classes {}".format(
+                DETECTION_CLASS, list(getattr(self.config, "classes", None) or [])))
         self.calls = 0
         self.seconds = 0.0
         self._saver = None                  # the _CaseSaver of a --save_predict run, while it runs
@@ -368,6 +383,8 @@ class EvaluateVolume(EvaluateBase):
             for i, cls in enumerate(self.classes):
                 pred = vol[cls][:n_real].cpu().numpy().astype(np.uint8)
                 ref = (lab == i + 1).astype(np.uint8)
+                if self.eval_detection and cls == DETECTION_CLASS:
+                    self._add_detection(acc, metric_ops.tumor_detection_metrics(pred, ref, self.detection_thresh))
                 if use_global:
                     conf = metric_ops.ConfusionMatrix(pred.astype(int), ref.astype(int))
                     conf.compute()
@@ -385,6 +402,8 @@ class EvaluateVolume(EvaluateBase):
             for i, cls in enumerate(self.classes):
                 pred = vol[cls][:n_real].to(torch.uint8)
                 ref = (lab == i + 1).view(torch.uint8)
+                if self.eval_detection and cls == DETECTION_CLASS:
+                    self._add_detection(acc, metric_ops.tumor_detection_metrics_device(pred, ref, self.detection_thresh))
                 if use_global:
                     conf = ops.mask_counts(pred, ref)
                     acc[cls + "_fn"] += conf["fn"]
@@ -409,9 +428,13 @@ class EvaluateVolume(EvaluateBase):
         if cur is not None:
             finish(cur, preds, labels)
         if use_global:
-            return {cls + "/Dice": 2 * acc[cls + "_tp"] / max(2 * acc[cls + "_tp"] + acc[cls + "_fn"] + acc[cls + "_fp"], 1)
-                    for cls in self.classes}
-        return {k: float(np.mean(v)) for k, v in self.metric_values.items()}
+            results = {cls + "/Dice": 2 * acc[cls + "_tp"] / max(2 * acc[cls + "_tp"] + acc[cls + "_fn"] + acc[cls + "_fp"], 1)
+                       for cls in self.classes}
+        else:
+            results = {k: float(np.mean(v)) for k, v in self.metric_values.items()}
+        if self.eval_detection:                                         # per case, on the volumes as they are scored here
+            results.update(self._detection_results(acc))
+        return results
 
     def run(self, input_fn, checkpoint_path=None, latest_filename=None, save=False, hooks=None, cases=None):
         """evaluator_liver.py:704-766: build the model, restore the checkpoint, stream the cases."""
@@ -659,6 +682,9 @@ class EvaluateVolume(EvaluateBase):
                     accumulator[cls + "_fn"] += conf.fn
                     accumulator[cls + "_fp"] += conf.fp
                     accumulator[cls + "_tp"] += conf.tp
+                if self.eval_detection:
+                    self._add_detection(accumulator, metric_ops.tumor_detection_metrics(
+                        volume[DETECTION_CLASS], labels[DETECTION_CLASS], self.detection_thresh))
                 if not use_global:
                     for cls in self.classes:
                         pairs = metric_ops.metric_3d(volume[cls], labels[cls], required=self.metrics_str)
@@ -683,7 +709,25 @@ class EvaluateVolume(EvaluateBase):
             results = {key: float(np.mean(values)) for key, values in self._metric_values.items()}
             if accumulator:
                 results.update({"G" + cls + "Dice": gdice(cls) for cls in self.classes})
+        if self.eval_detection:
+            results.update(self._detection_results(accumulator))
         return results
+
+    @staticmethod
+    def _add_detection(accumulator, det):
+        """One case's tumor_detection_metrics into the run's counts."""
+        accumulator[DETECTION_CLASS + "_det_tp"] += det["tp"]
+        accumulator[DETECTION_CLASS + "_det_fp"] += det["fp"]
+        accumulator[DETECTION_CLASS + "_det_pos"] += det["pos"]
+
+    @staticmethod
+    def _detection_results(accumulator):
+        """--eval_detection: the counts summed over the cases, and precision / recall of the sums (np.inf where the
+        denominator is 0, as per case)."""
+        tp, fp, pos = (int(accumulator[DETECTION_CLASS + "_det_" + k]) for k in ("tp", "fp", "pos"))
+        scores = metric_ops.detection_scores(tp, tp + fp, pos)
+        return {DETECTION_CLASS + "/DetTP": tp, DETECTION_CLASS + "/DetFP": fp, DETECTION_CLASS + "/DetPos": pos,
+                DETECTION_CLASS + "/Precision": float(scores["precision"]), DETECTION_CLASS + "/Recall": float(scores["recall"])}
 
     def _maybe_save_case(self, case, volume, bbox, dtype, save_path):
         """evaluator_liver.py:998-1026 `maybe_save_case`: -> (volume, post_processed).  Without --save_predict the volume
@@ -709,6 +753,9 @@ class EvaluateVolume(EvaluateBase):
             accumulator[cls + "_fn"] += conf["fn"]
             accumulator[cls + "_fp"] += conf["fp"]
             accumulator[cls + "_tp"] += conf["tp"]
+        if self.eval_detection:
+            self._add_detection(accumulator, metric_ops.tumor_detection_metrics_device(
+                volume[DETECTION_CLASS], labels[DETECTION_CLASS], self.detection_thresh))
         if not use_global:
             for cls in self.classes:
                 for met, value in metric_ops.metric_3d_device(volume[cls], labels[cls], required=self.metrics_str).items():

@@ -216,6 +216,52 @@ def metric_3d_device(pred, ref, required=None, sampling=(1, 1, 1)):
     return out
 
 
+def detection_scores(tp, n_res, n_ref):
+    """loss_metrics.py:478-493: the dict of tumor_detection_metrics from its three counts; precision and recall are
+    np.inf where their denominator is 0."""
+    import numpy as np
+    tp, n_res, n_ref = int(tp), int(n_res), int(n_ref)
+    return {"tp": tp,
+            "fp": n_res - tp,
+            "pos": n_ref,
+            "precision": tp / n_res if n_res != 0 else np.inf,
+            "recall": tp / n_ref if n_ref != 0 else np.inf}
+
+
+def tumor_detection_metrics(result, reference, iou_thresh=0.5, connectivity=1, verbose=False, logger=None, name=""):
+    """loss_metrics.py:455-502 on the host: per-lesion detection of a binary result volume against a binary reference
+    volume.  Objects are 6-connected components; a reference object counts as found when
+    utils/array_kits.distinct_binary_object_correspondences matches it to a result object -- `iou_thresh` is a threshold on
+    the DICE coefficient of the two objects, the reference's name for it notwithstanding.  Returns {"tp", "fp", "pos",
+    "precision", "recall"}."""
+    from .utils import array_kits
+    _, _, n_res, n_ref, mapping = array_kits.distinct_binary_object_correspondences(result, reference, iou_thresh, connectivity)
+    ret = detection_scores(len(mapping), n_res, n_ref)
+    if verbose:
+        info = "{:s} TPs: {:3d} FPs: {:3d} Pos: {:3d} Precision: {:.3f} Recall: {:.3f}".format(
+            name, ret["tp"], ret["fp"], ret["pos"], ret["precision"], ret["recall"])
+        if logger is not None:
+            logger.info(info)
+        else:
+            print(info)
+    return ret
+
+
+def tumor_detection_metrics_device(result, reference, iou_thresh=0.5):
+    """tumor_detection_metrics for masks on the device (numpy arrays are uploaded once): labelling, object sizes and the
+    overlap of every pair of objects come from unetk_component_overlaps (csrc/evalvol.hip) in one table read, the matching
+    rule runs on that table on the host (utils/array_kits.match_components).  The same integers go through the same
+    expressions as on the host, so the dict is equal key for key."""
+    import numpy as np
+
+    from .utils import array_kits
+    result, reference = (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x)).cuda()
+                         for x in (result, reference))
+    res_sizes, ref_sizes, pairs = ops.component_overlaps(result, reference)
+    mapping = array_kits.match_components(res_sizes, ref_sizes, pairs, iou_thresh)
+    return detection_scores(len(mapping), len(res_sizes), len(ref_sizes))
+
+
 class ConfusionMatrix(object):
     """loss_metrics.py:506-580: tp / fp / tn / fn counts of a test volume against a reference volume."""
 

@@ -1168,6 +1168,50 @@ def largest_component3d(mask):
     return out
 
 
+def component_overlaps_table(res, ref, cap_obj=65536, cap_pair=262144, table=None, ws=None):
+    """unetk_component_overlaps as the kernel leaves it: the int32 device table [4 + 4 cap_obj + 3 cap_pair] (include/unetk.h)
+    of the 6-connected components of two same-shape masks and of the pairs that share voxels.  No host read."""
+    res, ref = _mask3d(res), _mask3d(ref)
+    if res.shape != ref.shape:
+        raise ValueError("shape mismatch: {} and {}".format(tuple(res.shape), tuple(ref.shape)))
+    d, h, w = res.shape
+    cap_obj, cap_pair = int(cap_obj), int(cap_pair)
+    lib = _abi.lib()
+    nbytes = lib.unetk_component_overlaps_ws_bytes(d, h, w, cap_obj, cap_pair)
+    if nbytes == 0:
+        raise ValueError("unsupported component_overlaps shape {} / caps {} {}".format(tuple(res.shape), cap_obj, cap_pair))
+    if table is None:
+        table = torch.empty(4 + 4 * cap_obj + 3 * cap_pair, dtype=torch.int32, device=res.device)
+    if ws is None:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=res.device)
+    check(lib.unetk_component_overlaps(ptr(res), ptr(ref), d, h, w, cap_obj, cap_pair, ptr(table), ptr(ws), ws.numel(),
+                                       stream_ptr()), "component_overlaps")
+    return table
+
+
+def component_overlaps(res, ref, cap_obj=65536, cap_pair=262144):
+    """The component tables of per-lesion detection (utils/array_kits.distinct_binary_object_correspondences) from the
+    device: (res_sizes int64 [n_res], ref_sizes int64 [n_ref], pairs int64 [n_pair, 3] rows (ref_id, res_id, overlap) sorted
+    by (ref_id, res_id)) as numpy arrays, ids 1-based in scipy.ndimage.label's order with 6-connectivity.  One
+    device-to-host read of the table.  Raises RuntimeError naming the cap that is too small; never a truncated table."""
+    import numpy as np
+    cap_obj, cap_pair = int(cap_obj), int(cap_pair)
+    table = component_overlaps_table(res, ref, cap_obj, cap_pair).cpu().numpy()
+    n_res, n_ref, n_pair, overflow = (int(v) for v in table[:4])
+    if overflow:
+        over = []
+        if overflow & 1:
+            over.append("cap_obj = {} < {} result components".format(cap_obj, n_res))
+        if overflow & 2:
+            over.append("cap_obj = {} < {} reference components".format(cap_obj, n_ref))
+        if overflow & 4:
+            over.append("cap_pair = {} < {} overlapping pairs".format(cap_pair, n_pair))
+        raise RuntimeError("component_overlaps: " + "; ".join(over))
+    rows = table[4:4 + 4 * cap_obj].reshape(2, cap_obj, 2)
+    pairs = table[4 + 4 * cap_obj:].reshape(cap_pair, 3)[:n_pair]
+    return rows[0, :n_res, 1].astype(np.int64), rows[1, :n_ref, 1].astype(np.int64), pairs.astype(np.int64)
+
+
 _HIST_TABLES = {}
 
 

@@ -34,6 +34,75 @@ def get_largest_component(inputs, rank, connectivity=1):
     return merge_labels(labeled, [-1, int(order[-1]) + 1])
 
 
+def match_components(res_sizes, ref_sizes, pairs, thresh):
+    """The matching rule of utils/array_kits.py:920-984 on component tables: res_sizes [n_res] and ref_sizes [n_ref] the
+    voxel counts of the result and reference objects (object id = index + 1), pairs rows (ref_id, res_id, overlap > 0), one
+    per pair of objects that share voxels.  Returns {ref_id: [res_id, score]}.
+
+    The score of a pair is 2 * overlap / (size_ref + size_res): the reference names it `iou` but computes medpy's Dice
+    coefficient, and so does this.  Reference objects are walked in id order.  One whose candidates are a single result
+    object is decided at once: matched if that object is still unused and scores >= thresh, else unmatched for good.  Those
+    with several candidates wait; then, until none is left: the used result objects leave every waiting set, empty sets are
+    dropped, the rest is stable-sorted by set size, and the first object tries its candidates in decreasing overlap (lowest
+    result id on ties) until one scores >= thresh; it is dropped whether or not one did."""
+    res_sizes, ref_sizes = np.asarray(res_sizes), np.asarray(ref_sizes)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 3)
+    pairs = pairs[np.lexsort((pairs[:, 1], pairs[:, 0]))]                    # by (ref_id, res_id)
+
+    def score(ref_id, res_id, overlap):
+        return 2.0 * overlap / float(int(ref_sizes[ref_id - 1]) + int(res_sizes[res_id - 1]))
+
+    mapping, used, waiting = {}, set(), []
+    starts = np.flatnonzero(np.r_[True, pairs[1:, 0] != pairs[:-1, 0]]) if len(pairs) else []
+    for lo, hi in zip(starts, list(starts[1:]) + [len(pairs)]):
+        ref_id = int(pairs[lo, 0])
+        cands = {int(r): int(o) for _, r, o in pairs[lo:hi]}                 # ascending result id
+        if len(cands) > 1:
+            waiting.append((ref_id, cands))
+            continue
+        (res_id, overlap), = cands.items()
+        if res_id not in used:
+            s = score(ref_id, res_id, overlap)
+            if s >= thresh:
+                mapping[ref_id] = [res_id, s]
+                used.add(res_id)
+    while True:
+        waiting = [(ref_id, {r: o for r, o in cands.items() if r not in used}) for ref_id, cands in waiting]
+        waiting = sorted((w for w in waiting if w[1]), key=lambda w: len(w[1]))
+        if not waiting:
+            break
+        ref_id, cands = waiting[0]
+        for res_id in sorted(cands, key=lambda r: (-cands[r], r)):
+            s = score(ref_id, res_id, cands[res_id])
+            if s >= thresh:
+                mapping[ref_id] = [res_id, s]
+                used.add(res_id)
+                break
+        waiting = waiting[1:]
+    return mapping
+
+
+def distinct_binary_object_correspondences(result, reference, iou_thresh=0.5, connectivity=1):
+    """utils/array_kits.py:883-984: label the objects of two binary volumes and match reference objects to result objects
+    (match_components; `iou_thresh` is a threshold on the Dice coefficient of two objects, as in the reference).  Returns
+    (labeled_res, labeled_ref, n_res, n_ref, mapping), mapping = {ref_id: [res_id, score]}.  Only connectivity 1 (faces)
+    is built."""
+    if connectivity != 1:
+        raise ValueError("only connectivity 1 is supported, got {}".format(connectivity))
+    result = np.atleast_1d(np.asarray(result).astype(bool))
+    reference = np.atleast_1d(np.asarray(reference).astype(bool))
+    assert result.shape == reference.shape
+    struct = ndi.generate_binary_structure(result.ndim, connectivity)
+    labeled_res, n_res = ndi.label(result, struct)
+    labeled_ref, n_ref = ndi.label(reference, struct)
+    both = (labeled_res > 0) & (labeled_ref > 0)
+    keys, overlaps = np.unique(labeled_ref[both].astype(np.int64) * (n_res + 1) + labeled_res[both], return_counts=True)
+    pairs = np.stack([keys // (n_res + 1), keys % (n_res + 1), overlaps], axis=1)
+    mapping = match_components(np.bincount(labeled_res.ravel(), minlength=n_res + 1)[1:],
+                               np.bincount(labeled_ref.ravel(), minlength=n_ref + 1)[1:], pairs, iou_thresh)
+    return labeled_res, labeled_ref, n_res, n_ref, mapping
+
+
 def bbox_to_shape(bbox):
     """(x1, y1, z1, x2, y2, z2) inclusive -> (d, h, w)  (utils/array_kits.py `bbox_to_shape`)."""
     ndim = len(bbox) // 2

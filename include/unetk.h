@@ -608,6 +608,24 @@ int unetk_guide_components(const float* acc, const float* guide, int H, int W, i
                            size_t ws_bytes, void* stream);
 int unetk_guide_render(const float* obj, int n_obj, int H, int W, float discount, float* guide, void* stream);
 
+/* Per-lesion detection (additive to ABI 10): the component tables that utils/array_kits.py:883-984
+ * distinct_binary_object_correspondences builds with scipy.ndimage.label and np.unique; the matching rule itself stays on
+ * the host (utils/array_kits.match_components).  res, ref uint8 [D,H,W], non-zero = object.  Both masks are labelled by the
+ * union-find of unetk_largest_component (6-connected, every voxel ends at the minimum linear index of its component) and
+ * their components numbered 1..n in increasing root: scipy.ndimage.label's ids with generate_binary_structure(3, 1).
+ * table int32 [4 + 4 cap_obj + 3 cap_pair]:
+ *   head {n_res, n_ref, n_pair, overflow}: the true counts whatever the caps; overflow bit 0 = n_res > cap_obj,
+ *     bit 1 = n_ref > cap_obj, bit 2 = n_pair > cap_pair;
+ *   cap_obj rows {root, size} of res, then cap_obj rows {root, size} of ref, row k = the component of id k + 1;
+ *   cap_pair rows {ref_id, res_id, overlap}: one for every pair of components that share a voxel, sorted by
+ *     (ref_id, res_id).  The pair rows are written only when no overflow bit is set.
+ * Rows past the counts are zero.  Integer arithmetic throughout; the pairs are ranked before their rows are written, so the
+ * table is the same bit for bit from run to run.  0 < cap_obj, cap_pair <= 2^24 (else UNETK_E_BADARG and a zero ws query);
+ * table 4-byte, ws 16-byte aligned, at least unetk_component_overlaps_ws_bytes (16 bytes per voxel and 16 per pair row). */
+size_t unetk_component_overlaps_ws_bytes(int D, int H, int W, int cap_obj, int cap_pair);
+int unetk_component_overlaps(const uint8_t* res, const uint8_t* ref, int D, int H, int W, int cap_obj, int cap_pair,
+                             int32_t* table, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- offline evaluation: slabs in, zoom back
  * The input and the output side of evaluators/evaluator_liver.py on the device (csrc/evalio.hip); both are gathers that
  * write every output element once: no atomics, no workspace.
