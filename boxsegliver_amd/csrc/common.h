@@ -62,6 +62,16 @@ __device__ __forceinline__ int unetk_fdiv(int n, int d, float rcp) {
 }
 __device__ __forceinline__ void stg4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
+// ---- NaN-propagating activation helpers (the non-finite contract in unetk.h).  fmaxf(NaN, 0) is 0 (v_max_f32 returns the
+// non-NaN operand), which would turn a poisoned channel into a dead one behind a finite loss; the NaN watch sees the loss only.
+// relu(NaN) = NaN, every other input as fmaxf(v, 0) up to the sign of a zero: one compare and one select.
+__device__ __forceinline__ float unetk_relu(float v) { return v < 0.f ? 0.f : v; }
+// max that returns NaN when either operand is one (F.max_pool2d / F.max_pool1d); finite operands as fmaxf
+__device__ __forceinline__ float unetk_max_nan(float a, float b) { return (a > b || a != a) ? a : b; }
+__device__ __forceinline__ float unetk_max4_nan(float a, float b, float c, float d) {
+  return unetk_max_nan(unetk_max_nan(a, b), unetk_max_nan(c, d));
+}
+
 // ---- bf16 storage (UNETK_BF16S): activations / activation gradients live in HBM as bf16 (uint16_t bit patterns),
 // arithmetic stays fp32.  ld4 / st4 move FOUR consecutive channels: a float4 (16 B) or four bf16 (8 B).
 typedef uint16_t bf16_t;

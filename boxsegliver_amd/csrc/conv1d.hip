@@ -27,7 +27,7 @@ __global__ __launch_bounds__(256) void conv1d_fwd_kernel(const float* __restrict
       const float* wr = w + (int64_t)t * Cin * Cout + co;
       for (int ci = 0; ci < Cin; ++ci) acc = fmaf(xr[ci], wr[(int64_t)ci * Cout], acc);
     }
-    y[i] = relu ? fmaxf(acc, 0.f) : acc;
+    y[i] = relu ? unetk_relu(acc) : acc;
   }
 }
 
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void maxpool1d_fwd_kernel(const float* __restr
     const int64_t r = i / C;
     const int lo = (int)(r % Lo), b = (int)(r / Lo);
     const float a = x[((int64_t)b * L + 2 * lo) * C + c];
-    y[i] = (2 * lo + 1 < L) ? fmaxf(a, x[((int64_t)b * L + 2 * lo + 1) * C + c]) : a;
+    y[i] = (2 * lo + 1 < L) ? unetk_max_nan(a, x[((int64_t)b * L + 2 * lo + 1) * C + c]) : a;
   }
 }
 

@@ -282,7 +282,7 @@ __global__ __launch_bounds__(WM* WN * 64, (TM * TN == 8 ? 2 : 1)) void conv3x3_i
         const int i = mfma32_row(r, h);
         const int gh = h0 + 2 * sub + (i >> 4), gw = w0 + (i & 15);
 #pragma unroll
-        for (int tn = 0; tn < TN; ++tn) acc[tm][tn][r] = fmaxf(fmaf(acc[tm][tn][r], sc[tn], sh[tn]), 0.f);
+        for (int tn = 0; tn < TN; ++tn) acc[tm][tn][r] = unetk_relu(fmaf(acc[tm][tn][r], sc[tn], sh[tn]));
         if (gh < p.H && gw < p.W) {
           float* yp = p.y + yimg + ((int64_t)gh * p.W + gw) * p.ys + n0 + wn * TN * 32 + l31;
 #pragma unroll
@@ -301,8 +301,8 @@ __global__ __launch_bounds__(WM* WN * 64, (TM * TN == 8 ? 2 : 1)) void conv3x3_i
             float* pp = pimg + ((int64_t)(gh >> 1) * Wp + (gw >> 1)) * p.pool_s;
 #pragma unroll
             for (int tn = 0; tn < TN; ++tn)
-              pp[tn * 32] = fmaxf(fmaxf(acc[tm][tn][2 * q], acc[tm][tn][2 * q + 1]),
-                                  fmaxf(acc[tm][tn][8 + 2 * q], acc[tm][tn][9 + 2 * q]));
+              pp[tn * 32] = unetk_max4_nan(acc[tm][tn][2 * q], acc[tm][tn][2 * q + 1], acc[tm][tn][8 + 2 * q],
+                                           acc[tm][tn][9 + 2 * q]);
           }
         }
       }
@@ -570,8 +570,8 @@ __global__ __launch_bounds__(256) void conv3x3_c3_mfma_kernel(ConvParams p) {
       if (gh < p.H && gw < p.W) {
         float v0 = acc0[r], v1 = acc1[r];
         if constexpr (AFF) {
-          v0 = fmaxf(fmaf(v0, asc0, ash0), 0.f);
-          v1 = fmaxf(fmaf(v1, asc1, ash1), 0.f);
+          v0 = unetk_relu(fmaf(v0, asc0, ash0));
+          v1 = unetk_relu(fmaf(v1, asc1, ash1));
         }
         TY* yp = yimg + ((int64_t)gh * p.W + gw) * p.ys;
         if constexpr (std::is_same<TY, float>::value) {

@@ -442,7 +442,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bf16s_kernel(ConvParams p) {
 #pragma unroll
           for (int j = 0; j < NT8; ++j)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc[tm][j][r] = fmaxf(fmaf(acc[tm][j][r], asc[j], ash[j]), 0.f);
+            for (int r = 0; r < 4; ++r) acc[tm][j][r] = unetk_relu(fmaf(acc[tm][j][r], asc[j], ash[j]));
         if constexpr (AFF == 2) {
           const int Hp = p.H >> 1, Wp = p.W >> 1;
           bf16_t* pb = reinterpret_cast<bf16_t*>(p.pool) + (int64_t)cur.n_img * Hp * Wp * p.pool_s + cur.n0 + l15 * NT8;
@@ -456,10 +456,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bf16s_kernel(ConvParams p) {
 #pragma unroll
                 for (int j = 0; j < NT8 / 2; ++j) {
                   // the maximum of the four ROUNDED activations = the rounded maximum (rounding is monotone)
-                  const float m0 = fmaxf(fmaxf(acc[2 * tp][2 * j][2 * rp], acc[2 * tp][2 * j][2 * rp + 1]),
-                                         fmaxf(acc[2 * tp + 1][2 * j][2 * rp], acc[2 * tp + 1][2 * j][2 * rp + 1]));
-                  const float m1 = fmaxf(fmaxf(acc[2 * tp][2 * j + 1][2 * rp], acc[2 * tp][2 * j + 1][2 * rp + 1]),
-                                         fmaxf(acc[2 * tp + 1][2 * j + 1][2 * rp], acc[2 * tp + 1][2 * j + 1][2 * rp + 1]));
+                  const float m0 = unetk_max4_nan(acc[2 * tp][2 * j][2 * rp], acc[2 * tp][2 * j][2 * rp + 1],
+                                                  acc[2 * tp + 1][2 * j][2 * rp], acc[2 * tp + 1][2 * j][2 * rp + 1]);
+                  const float m1 = unetk_max4_nan(acc[2 * tp][2 * j + 1][2 * rp], acc[2 * tp][2 * j + 1][2 * rp + 1],
+                                                  acc[2 * tp + 1][2 * j + 1][2 * rp], acc[2 * tp + 1][2 * j + 1][2 * rp + 1]);
                   pk[j] = unetk_pk_bf16(m0, m1);
                 }
                 bf16_t* pp = pb + ((int64_t)(gh >> 1) * Wp + (gw >> 1)) * p.pool_s;

@@ -544,7 +544,7 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(2))
 #pragma unroll
             for (int tn = 0; tn < TN; ++tn) {
               const int ch = n0 + (wn * TN + tn) * 32 + l31;
-              rp[tn * 32] = fmaxf(fmaf(acc[tm][tn][r], p.asc[ch], p.ash[ch]), 0.f);
+              rp[tn * 32] = unetk_relu(fmaf(acc[tm][tn][r], p.asc[ch], p.ash[ch]));
             }
           } else {
 #pragma unroll
@@ -649,8 +649,8 @@ __global__ __launch_bounds__(256) void lin_sk_fixup_kernel(ConvParams p, int G) 
     const int plane = pix / HW, rem = pix - plane * HW;
     if (p.asc != nullptr) {            // inference epilogue on the summed pieces
       const float4 sc = ldg4(p.asc + n0 + cq * 4), sh = ldg4(p.ash + n0 + cq * 4);
-      v.x = fmaxf(fmaf(v.x, sc.x, sh.x), 0.f); v.y = fmaxf(fmaf(v.y, sc.y, sh.y), 0.f);
-      v.z = fmaxf(fmaf(v.z, sc.z, sh.z), 0.f); v.w = fmaxf(fmaf(v.w, sc.w, sh.w), 0.f);
+      v.x = unetk_relu(fmaf(v.x, sc.x, sh.x)); v.y = unetk_relu(fmaf(v.y, sc.y, sh.y));
+      v.z = unetk_relu(fmaf(v.z, sc.z, sh.z)); v.w = unetk_relu(fmaf(v.w, sc.w, sh.w));
     }
     stg4(p.y + p.ya.off(plane) + (int64_t)rem * p.ys + n0 + cq * 4, v);
     s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;

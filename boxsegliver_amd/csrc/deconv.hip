@@ -74,7 +74,7 @@ __device__ __forceinline__ void pw_epilogue(const PwParams& p, f32x16 (&acc)[TM]
         if (mb + delta >= p.M) break;
         const int64_t ob = img + ((int64_t)(2 * yy) * 2 * p.W + 2 * xx) * p.out_stride;
 #pragma unroll
-        for (int tn = 0; tn < TN; ++tn) p.out[ob + tapoff[tn]] = fmaxf(acc[tm][tn][r] + bv[tn], 0.f);
+        for (int tn = 0; tn < TN; ++tn) p.out[ob + tapoff[tn]] = unetk_relu(acc[tm][tn][r] + bv[tn]);
       }
     }
   } else {
@@ -130,7 +130,7 @@ __device__ __forceinline__ void pw_epilogue_bf16s(const PwParams& p, f32x16 (&ac
         if (mb + delta >= p.M) break;
         const int64_t ob = img + ((int64_t)(2 * yy) * 2 * p.W + 2 * xx) * p.out_stride;
         *reinterpret_cast<uint32_t*>(outb + ob + tapoff) =
-            unetk_pk_bf16(fmaxf(acc[tm][0][r] + b0, 0.f), fmaxf(acc[tm][1][r] + b1, 0.f));
+            unetk_pk_bf16(unetk_relu(acc[tm][0][r] + b0), unetk_relu(acc[tm][1][r] + b1));
       }
     }
   } else {

@@ -19,7 +19,7 @@ __global__ __launch_bounds__(256) void fc_fwd_kernel(const float* __restrict__ x
   const float* xr = x + (int64_t)r * k;
   float acc = b ? b[o] : 0.f;
   for (int i = 0; i < k; ++i) acc = fmaf(xr[i], w[(int64_t)i * n + o], acc);
-  if (relu == 1) acc = fmaxf(acc, 0.f);
+  if (relu == 1) acc = unetk_relu(acc);
   else if (relu == 2) acc = 1.0f / (1.0f + expf(-acc));        // tf.nn.sigmoid (GUNet's SE gate, GUNet.py:199)
   if (mask) {
     const float m = fc_uniform(seed, (uint32_t)(r * n + o)) < keep_prob ? 1.0f / keep_prob : 0.f;

@@ -377,8 +377,8 @@ __global__ __launch_bounds__(256) void norm_apply_relu_kernel(ApplyArgs a) {
       for (int j = 0; j < NP; ++j)
         if (pix + j * a.rpi < a.P) {
           float4 u;
-          u.x = fmaxf(fmaf(v[j].x, sc.x, sh.x), 0.f); u.y = fmaxf(fmaf(v[j].y, sc.y, sh.y), 0.f);
-          u.z = fmaxf(fmaf(v[j].z, sc.z, sh.z), 0.f); u.w = fmaxf(fmaf(v[j].w, sc.w, sh.w), 0.f);
+          u.x = unetk_relu(fmaf(v[j].x, sc.x, sh.x)); u.y = unetk_relu(fmaf(v[j].y, sc.y, sh.y));
+          u.z = unetk_relu(fmaf(v[j].z, sc.z, sh.z)); u.w = unetk_relu(fmaf(v[j].w, sc.w, sh.w));
           st4(az + (base + pix + j * a.rpi) * a.zs + cq * 4, u);
         }
     }
@@ -409,7 +409,7 @@ __global__ __launch_bounds__(256) void norm_apply_relu_kernel(ApplyArgs a) {
         u.x = fmaf(gg, gwv[g].x, u.x); u.y = fmaf(gg, gwv[g].y, u.y); u.z = fmaf(gg, gwv[g].z, u.z); u.w = fmaf(gg, gwv[g].w, u.w);
       }
     }
-    u.x = fmaxf(u.x, 0.f); u.y = fmaxf(u.y, 0.f); u.z = fmaxf(u.z, 0.f); u.w = fmaxf(u.w, 0.f);
+    u.x = unetk_relu(u.x); u.y = unetk_relu(u.y); u.z = unetk_relu(u.z); u.w = unetk_relu(u.w);
     st4(az + (base + pix) * a.zs + cq * 4, u);
   }
 }
@@ -440,13 +440,13 @@ __global__ __launch_bounds__(256) void norm_apply_relu_pool_kernel(ApplyArgs a, 
     for (int i = 0; i < 4; ++i) v[i] = ld4(ay + (pix + off[i]) * a.C + cq * 4);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      u[i].x = fmaxf(fmaf(v[i].x, sc.x, sh.x), 0.f); u[i].y = fmaxf(fmaf(v[i].y, sc.y, sh.y), 0.f);
-      u[i].z = fmaxf(fmaf(v[i].z, sc.z, sh.z), 0.f); u[i].w = fmaxf(fmaf(v[i].w, sc.w, sh.w), 0.f);
+      u[i].x = unetk_relu(fmaf(v[i].x, sc.x, sh.x)); u[i].y = unetk_relu(fmaf(v[i].y, sc.y, sh.y));
+      u[i].z = unetk_relu(fmaf(v[i].z, sc.z, sh.z)); u[i].w = unetk_relu(fmaf(v[i].w, sc.w, sh.w));
       st4(az + (pix + off[i]) * a.zs + cq * 4, u[i]);
     }
     float4 m;          // rounding to the storage type is monotonic: max of the stored values = stored max
-    m.x = fmaxf(fmaxf(u[0].x, u[1].x), fmaxf(u[2].x, u[3].x)); m.y = fmaxf(fmaxf(u[0].y, u[1].y), fmaxf(u[2].y, u[3].y));
-    m.z = fmaxf(fmaxf(u[0].z, u[1].z), fmaxf(u[2].z, u[3].z)); m.w = fmaxf(fmaxf(u[0].w, u[1].w), fmaxf(u[2].w, u[3].w));
+    m.x = unetk_max4_nan(u[0].x, u[1].x, u[2].x, u[3].x); m.y = unetk_max4_nan(u[0].y, u[1].y, u[2].y, u[3].y);
+    m.z = unetk_max4_nan(u[0].z, u[1].z, u[2].z, u[3].z); m.w = unetk_max4_nan(u[0].w, u[1].w, u[2].w, u[3].w);
     st4(ap + (img * per_img + r) * a.C + cq * 4, m);
   }
 }
@@ -915,6 +915,8 @@ __device__ __forceinline__ void pool_window(const BwdArgs& a, const PoolArgs& pa
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     u[i].x = fmaf(v[i].x, sc.x, sh.x); u[i].y = fmaf(v[i].y, sc.y, sh.y); u[i].z = fmaf(v[i].z, sc.z, sh.z); u[i].w = fmaf(v[i].w, sc.w, sh.w);
+    // backward only: fmaxf stays (unetk.h, non-finite contract) -- it decides which pixel of a finite window takes dp, where it
+    // equals unetk_relu, and a NaN forward has refused the step before this runs
     z[i].x = round_as<T>(fmaxf(u[i].x, 0.f)); z[i].y = round_as<T>(fmaxf(u[i].y, 0.f));
     z[i].z = round_as<T>(fmaxf(u[i].z, 0.f)); z[i].w = round_as<T>(fmaxf(u[i].w, 0.f));
   }

@@ -20,10 +20,10 @@ __global__ __launch_bounds__(256) void maxpool2_fwd_kernel(const T* __restrict__
     const T* b = x + (((int64_t)n * H + 2 * ho) * W + 2 * wo) * xs + cq * 4;
     const float4 a0 = ld4(b), a1 = ld4(b + xs), a2 = ld4(b + (int64_t)W * xs), a3 = ld4(b + (int64_t)W * xs + xs);
     float4 o;
-    o.x = fmaxf(fmaxf(a0.x, a1.x), fmaxf(a2.x, a3.x));
-    o.y = fmaxf(fmaxf(a0.y, a1.y), fmaxf(a2.y, a3.y));
-    o.z = fmaxf(fmaxf(a0.z, a1.z), fmaxf(a2.z, a3.z));
-    o.w = fmaxf(fmaxf(a0.w, a1.w), fmaxf(a2.w, a3.w));
+    o.x = unetk_max4_nan(a0.x, a1.x, a2.x, a3.x);   // a window that holds a NaN gives NaN (F.max_pool2d)
+    o.y = unetk_max4_nan(a0.y, a1.y, a2.y, a3.y);
+    o.z = unetk_max4_nan(a0.z, a1.z, a2.z, a3.z);
+    o.w = unetk_max4_nan(a0.w, a1.w, a2.w, a3.w);
     st4(p + i * 4, o);
   }
 }

@@ -18,6 +18,27 @@
  *   - no allocation, no host sync, no global mutable state: caller owns all buffers,
  *     including workspaces sized by the *_ws_bytes() queries  (graph-capturable)
  *   - return 0 on success, else a negative UNETK_E_* or a positive hipError_t
+ *
+ * Non-finite values on the forward path.  Training watches the LOSS only (unetk_nan_watch, as the reference's
+ * NanTensorHook), so a NaN anywhere in front of the head has to reach the loss instead of turning into a finite number:
+ *   1. ReLU: relu(NaN) = NaN.  Every other input, +-Inf included, gives max(v, 0); the sign of a zero result is not
+ *      specified.  (fmaxf(NaN, 0) is 0: the forward kernels use unetk_relu of csrc/common.h, never fmaxf.)
+ *   2. Max-pool (2x2, the fused norm+ReLU+pool and conv+affine+ReLU+pool epilogues, maxpool1d): a window that holds a NaN
+ *      gives NaN, as F.max_pool2d / F.max_pool1d.  Finite windows are unchanged, and so is the backward tie rule (the first
+ *      maximum takes the gradient; a NaN maximum equals no element, so the last element of its window takes it).
+ *   3. Everything else (matrix kernels, statistic partials, norm_finalize, deconv, conv1d, fc, the head): a NaN operand
+ *      reaches every output whose in-image receptive field holds it, by IEEE arithmetic; there is no fast-math flag in
+ *      the build.  Whether a NaN FILTER tap reaches an output whose tap lies in the zero halo is not specified.
+ *   4. Live-channel masks (cin_live8 / cout_live8 of unetk_conv3d_desc): padded channels are skipped, so 0 * NaN from a
+ *      dead channel is NOT formed and a NaN there does not propagate.  The promise that pads are zero makes this
+ *      unobservable; a caller that breaks the promise gets neither the product nor the NaN.
+ * The backward ReLU gates (u > 0 ? d : 0) send a NaN pre-activation's gradient to 0: once the forward is NaN the step is
+ * already refused.  fmaxf / fminf that remain and why they are safe: the softmax shift of the head (head.hip: expf(NaN -
+ * mx) carries the NaN whatever mx is) and its union count fminf(pr + lc, 1) (both operands are 0 or 1); the re-evaluation
+ * of z and of its window maximum in the pool-fused norm BACKWARD (norm.hip pool_window: it only routes dp inside a window,
+ * on finite values it equals the forward's, and it runs after a forward whose NaN has refused the step); the intensity
+ * clamp, min / max reductions and guide renderers of the LiTS loaders (lits.hip, lits3d.hip: their sources are uint16
+ * volumes and host-made tables, not activations).
  */
 #ifndef UNETK_H_
 #define UNETK_H_

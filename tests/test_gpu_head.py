@@ -397,6 +397,8 @@ NAN_CASES = [
     ("proportion_no_decay_all_present", "proportion", "random", False),
     ("numerical_present_classes_weigh_zero", "numerical", "zero_weight_only", True),
     ("numerical_mixed", "numerical", "random", False),
+    ("nan_logit_at_one_pixel", "none", "nan_pixel", True),            # everything in front of the head hands its NaN over as this
+    ("nan_logit_at_one_pixel_weighted", "numerical", "nan_pixel", True),
 ]
 
 
@@ -415,6 +417,9 @@ def test_head_loss_is_nan_exactly_when_the_formulas_give_nan(ops, name, mode, ki
         labels[1][labels[1] == 2] = 0                                # ... but class 2 in sample 1
     elif kind == "zero_weight_only":
         labels[1] = 2                                                # NUMERIC_W[2] == 0
+    elif kind == "nan_pixel":
+        z[1, 37, 5] = float("nan")                                   # one activation: the three logits of that pixel are NaN
+        labels[1, 37] = 1                                            # a class of non-zero weight in both modes
     nw = numeric_w(ncls)
     ref = head_ref(z, w, b, labels, mode, nw, None, None, grads=False)
     assert math.isnan(ref["xent"]) == expect_nan
@@ -424,3 +429,26 @@ def test_head_loss_is_nan_exactly_when_the_formulas_give_nan(ops, name, mode, ki
     assert math.isnan(got) == math.isnan(ref["xent"]), (got, ref["xent"])
     if not expect_nan:
         assert abs(got - ref["xent"]) < 2e-5 * max(1.0, abs(ref["xent"]))
+
+
+def test_head_predict_on_nan_probabilities_follows_the_formulas(ops):
+    """unetk_head_predict on what the softmax of a NaN logit leaves (every class NaN) and on a NaN in class 0 alone: the masks are
+    p > 0.5, false for NaN, and the argmax keeps index 0 -- no class beats a NaN by `>`, and np.argmax names the first NaN too.
+    Evaluated in float64 with numpy; the finite pixels around keep their answers.
+    Deliberately NOT specified: a NaN in class 1 or 2 alone beside a finite class 0.  The kernel's `>` scan (as the reference's
+    tf.argmax) skips it and names the largest finite class, np.argmax names the NaN; a softmax never produces that pixel, and this
+    test does not pin "what argmax gives in float64" for it."""
+    import numpy as np
+    ncls, npix = 3, 1000
+    p = np.random.default_rng(11).random((npix, ncls)).astype(np.float32)
+    p[5] = np.nan                                                    # softmax(NaN logit): all classes
+    p[700, 0] = np.nan                                               # class 0 alone
+    p[701] = [0.1, 0.7, 0.2]
+    amax, preds = ops.head_predict(torch.from_numpy(p).cuda(), ncls)
+    p64 = p.astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        want_preds = (p64[:, 1:] > 0.5).T.astype(np.uint8)
+    want_amax = np.argmax(p64, -1).astype(np.uint8)
+    assert want_amax[5] == 0 and want_amax[700] == 0 and want_amax[701] == 1 and not want_preds[:, 5].any()
+    np.testing.assert_array_equal(amax.cpu().numpy(), want_amax)
+    np.testing.assert_array_equal(preds.cpu().numpy(), want_preds)

@@ -158,16 +158,15 @@ def _trace(ops, fn):
     return out, launches           # every launch, in order: a doubled or reordered launch shows
 
 
-def exact_case(ops, case, live=None):
-    """One case with inputs for which fp32 arithmetic is exact in any summation order (x integers in [-4, 4], w eighths in
-    [-2/8, 2/8], dy integers in [-2, 2]: tests/test_gpu_conv_paths.py): y, dx, dw must equal float64 bit for bit whatever
-    stride-2 tile, depth-tap accumulation, grouped taps, four-class scatter, half chunk or fused depth tap computes them.
-    Returns the traced launches (forward, input gradient, filter gradient), in order."""
+def exact_inputs(case, live=None):
+    """The exact-tier operands of exact_case (also the inputs of the 3-D rows of tests/nonfinite_cases.py): float64 x
+    [N, D, H, W, Cin] integers in [-4, 4] and w [kd, 3, 3, Cin, Cout] eighths in [-2/8, 2/8], masked to the live channels of a
+    channel-padded row.  Returns (x, w, the generator (dy is drawn from it next), the live-Cout mask or None, live8 or None)."""
     n, dd, h, w, cin, cout, kd, stride = case
     g = torch.Generator().manual_seed(n * 1000 + dd * 100 + h + cin + cout + kd)
     x = torch.randint(-4, 5, (n, dd, h, w, cin), generator=g).double()
     wt = torch.randint(-2, 3, (kd, 3, 3, cin, cout), generator=g).double() / 8
-    live8 = None
+    co, live8 = None, None
     if live is not None:
         ci, co = torch.zeros(cin, dtype=torch.bool), torch.zeros(cout, dtype=torch.bool)
         for lo, hi in live[0]:
@@ -177,6 +176,16 @@ def exact_case(ops, case, live=None):
         x = x * ci
         wt = wt * ci[:, None] * co[None, :]
         live8 = (_mask8(live[0]), _mask8(live[1]))
+    return x, wt, g, co, live8
+
+
+def exact_case(ops, case, live=None):
+    """One case with inputs for which fp32 arithmetic is exact in any summation order (x integers in [-4, 4], w eighths in
+    [-2/8, 2/8], dy integers in [-2, 2]: tests/test_gpu_conv_paths.py): y, dx, dw must equal float64 bit for bit whatever
+    stride-2 tile, depth-tap accumulation, grouped taps, four-class scatter, half chunk or fused depth tap computes them.
+    Returns the traced launches (forward, input gradient, filter gradient), in order."""
+    n, dd, h, w, cin, cout, kd, stride = case
+    x, wt, g, co, live8 = exact_inputs(case, live)
     x.requires_grad_(True)
     wt.requires_grad_(True)
     y_ref = tf_ops.conv_nd_same(x, wt, stride=stride)

@@ -112,3 +112,50 @@ def test_nan_loss_between_log_steps_stops_training_before_the_next_checkpoint(tm
     e2.train(synthetic.input_fn, steps=5)
     assert [int(v) for v in e2._nan_flag.tolist()] == [0, 0]
     assert any(f.startswith("model.ckpt-5") for f in os.listdir(str(d2)))
+
+
+def test_nan_beta_without_weight_decay_stops_training_before_the_next_checkpoint(tmp_path):
+    """The same run with weight_decay_rate = 0 and a poisoned norm `beta`: no L2 sum over the variables exists that could carry
+    the NaN, so it reaches the loss through the activations alone (relu(NaN) = NaN, include/unetk.h) -- and the step is refused
+    exactly as above."""
+    import test_gpu_unet as t
+    from boxsegliver_amd.NetworksV2.UNet import UNet
+    from boxsegliver_amd.core import estimator as est
+    from boxsegliver_amd.core import models
+    from boxsegliver_amd.core.solver import Solver
+    from boxsegliver_amd.data import synthetic
+
+    class Poison(object):                       # a hook: after the 2nd step one beta becomes NaN -> step 3's loss is NaN
+        def __init__(self):
+            self.n = 0
+
+        def begin(self):
+            pass
+
+        def after_create_session(self, session):
+            pass
+
+        def before_run(self, ctx):
+            pass
+
+        def after_run(self, ctx, spec):
+            self.n += 1
+            if self.n == 2:
+                spec.model.params["UNet/Encode1/Repeat/convolution2d_1/BatchNorm/beta"].data.view(-1)[0] = float("nan")
+                from boxsegliver_amd import ops
+                ops.PARAM_GEN += 1
+
+        def end(self, session):
+            pass
+
+    args = t.make_args(batch_size=2, im_height=32, im_width=32, model="UNet", noise_scale=0.05, synthetic_batches=2,
+                       log_step=1000, weight_decay_rate=0.0)
+    params = {"args": args, "model": UNet, "model_kwargs": dict(t.YML), "model_args": (), "solver": Solver(args),
+              "solver_kwargs": {}}
+    e = est.CustomEstimator(models.model_fn, str(tmp_path), est.RunConfig(model_dir=str(tmp_path), save_checkpoints_steps=4),
+                            params)
+    with pytest.raises(est.NanLossDuringTrainingError):
+        e.train(synthetic.input_fn, steps=8, hooks=[Poison()])
+    seen, at = (int(v) for v in e._nan_flag.tolist())
+    assert seen == 1 and at == 3
+    assert not [f for f in os.listdir(str(tmp_path)) if f.startswith("model.ckpt")]
