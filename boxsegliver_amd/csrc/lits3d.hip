@@ -15,19 +15,11 @@
 //              float stat[N][8] = {m, s, mn, sd, min, range, new_mn, new_sd}
 #include "common.h"
 #include "lits_geom.h"
+#include "lits_patch.h"      // TW, ST_*, block_sum3 / block_minmax, p3d_finalize_kernel, the two gamma passes
 
 namespace {
 
-constexpr int TW = UNETK_LITS3D_TAB_COLS;
-constexpr int P3D_MAX_BLOCKS = 256;      // partial blocks per sample
-constexpr int P3D_VOX_PER_BLOCK = 4096;
-enum { ST_M = 0, ST_S, ST_MN, ST_SD, ST_MIN, ST_RNG, ST_NMN, ST_NSD, ST_N };
-
-inline int p3d_blocks(const unetk_lits3d_desc* d) {
-  const int64_t vox = (int64_t)d->D * d->H * d->W;
-  const int64_t p = (vox + P3D_VOX_PER_BLOCK - 1) / P3D_VOX_PER_BLOCK;
-  return (int)(p < 1 ? 1 : (p > P3D_MAX_BLOCKS ? P3D_MAX_BLOCKS : p));
-}
+inline int p3d_blocks(const unetk_lits3d_desc* d) { return p3d_blocks_for((int64_t)d->D * d->H * d->W); }
 
 // ------------------------------------------------------------------------------------------------ forced-class centre
 // One block per sample; thread t owns the contiguous pixels [t L, (t + 1) L) of the slice, so a block-wide exclusive
@@ -106,60 +98,6 @@ __device__ __forceinline__ int64_t p3d_slice(const Box3& b, int z, const unetk_l
   return (zs < b.depth && s >= 0 && s < d.n_slices) ? s : -1;
 }
 
-// ------------------------------------------------------------------------------------------------ block reductions
-// Partials of one block, the same layout in every pass (workspace: sums[N][P][3] doubles, then minmax[N][P][2] floats):
-//   sums   = {number of values, their sum, their sum of squares}
-//   minmax = {min, max}                       (written by the patch pass only)
-// Each is reduced in a fixed order: an xor butterfly inside the wave, then the four waves by index.
-__device__ __forceinline__ void block_sum3(double cnt, double sum, double sq, double* __restrict__ dst) {
-  __shared__ double sh[4][3];
-  cnt = wave_sum_d(cnt);
-  sum = wave_sum_d(sum);
-  sq = wave_sum_d(sq);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    sh[wave][0] = cnt;
-    sh[wave][1] = sum;
-    sh[wave][2] = sq;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double r0 = 0., r1 = 0., r2 = 0.;
-    for (int w = 0; w < 4; ++w) {
-      r0 += sh[w][0];
-      r1 += sh[w][1];
-      r2 += sh[w][2];
-    }
-    dst[0] = r0;
-    dst[1] = r1;
-    dst[2] = r2;
-  }
-  __syncthreads();
-}
-__device__ __forceinline__ void block_minmax(float lo, float hi, float* __restrict__ dst) {
-  __shared__ float sh[4][2];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo = fminf(lo, __shfl_xor(lo, o));
-    hi = fmaxf(hi, __shfl_xor(hi, o));
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    sh[wave][0] = lo;
-    sh[wave][1] = hi;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w) {
-      lo = fminf(lo, sh[w][0]);
-      hi = fmaxf(hi, sh[w][1]);
-    }
-    dst[0] = lo;
-    dst[1] = hi;
-  }
-  __syncthreads();
-}
-
 // ------------------------------------------------------------------------------------------------ pass 1: mask moments
 // data_processing :354-357: moments over the crop's voxels with v > 0, at SOURCE resolution.  v = stored / im_scale is an
 // integer multiple of 1 / im_scale, so the fp64 sums are exact.
@@ -185,57 +123,6 @@ __global__ __launch_bounds__(256) void p3d_mask_stats_kernel(unetk_lits3d_desc d
     }
   }
   block_sum3(cnt, sum, sq, part + ((int64_t)n * P + blockIdx.x) * 3);
-}
-
-// ------------------------------------------------------------------------------------------------ finalising block
-// One wave per sample walks the P partials by index (lane l takes l, l + 64, ...; then a fixed butterfly): mean and
-// standard deviation of the values the pass counted, and in stage 1 their min and range.
-//   stage 0 (mask moments)  -> m, s                    (empty mask: 0, 0)
-//   stage 1 (patch)         -> mn, sd, min, range      of the normalised patch
-//   stage 2 (gamma)         -> new_mn, new_sd          of the gamma-mapped patch
-__global__ __launch_bounds__(64) void p3d_finalize_kernel(int stage, int P, const double* __restrict__ part,
-                                                          const float* __restrict__ minmax, float* __restrict__ stat) {
-  const int n = blockIdx.x, lane = threadIdx.x;
-  const double* p = part + (int64_t)n * P * 3;
-  const float* mm = minmax + (int64_t)n * P * 2;
-  double cnt = 0., sum = 0., sq = 0.;
-  float lo = INFINITY, hi = -INFINITY;
-  for (int i = lane; i < P; i += 64) {
-    cnt += p[i * 3 + 0];
-    sum += p[i * 3 + 1];
-    sq += p[i * 3 + 2];
-    if (stage == 1) {
-      lo = fminf(lo, mm[i * 2 + 0]);
-      hi = fmaxf(hi, mm[i * 2 + 1]);
-    }
-  }
-  cnt = wave_sum_d(cnt);
-  sum = wave_sum_d(sum);
-  sq = wave_sum_d(sq);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo = fminf(lo, __shfl_xor(lo, o));
-    hi = fmaxf(hi, __shfl_xor(hi, o));
-  }
-  if (lane != 0) return;
-  double m = 0., var = 0.;
-  if (cnt > 0.) {
-    m = sum / cnt;
-    var = fmax(sq / cnt - m * m, 0.);
-  }
-  float* st = stat + (int64_t)n * ST_N;
-  if (stage == 0) {
-    st[ST_M] = (float)m;
-    st[ST_S] = (float)sqrt(var);
-  } else if (stage == 1) {
-    st[ST_MN] = (float)m;
-    st[ST_SD] = (float)sqrt(var);
-    st[ST_MIN] = lo;
-    st[ST_RNG] = hi - lo;
-  } else {
-    st[ST_NMN] = (float)m;
-    st[ST_NSD] = (float)sqrt(var);
-  }
 }
 
 // ------------------------------------------------------------------------------------------------ pass 2: the patch
@@ -297,38 +184,7 @@ __global__ __launch_bounds__(256) void p3d_patch_kernel(unetk_lits3d_desc d, con
   }
 }
 
-// ------------------------------------------------------------------------------------------------ passes 3, 4: gamma
-// augment_gamma (image_ops.py:339-354), retain_stats=True, in float32 as the reference: the accurate powf.
-__global__ __launch_bounds__(256) void p3d_gamma_kernel(unetk_lits3d_desc d, const int32_t* __restrict__ tab,
-                                                        const float* __restrict__ stat, float* __restrict__ images,
-                                                        double* __restrict__ part) {
-  const int n = blockIdx.y, P = gridDim.x;
-  const float gamma = __int_as_float(tab[(int64_t)n * TW + 10]);
-  const float* st = stat + (int64_t)n * ST_N;
-  const float minm = st[ST_MIN], rnge = st[ST_RNG];
-  const int total = d.D * d.H * d.W;
-  float* img = images + (int64_t)n * total;
-  double cnt = 0., sum = 0., sq = 0.;
-  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < total; i += P * 256) {
-    const float y = powf((img[i] - minm) / (rnge + 1e-7f), gamma) * rnge + minm;
-    img[i] = y;
-    cnt += 1.;
-    sum += (double)y;
-    sq += (double)y * (double)y;
-  }
-  block_sum3(cnt, sum, sq, part + ((int64_t)n * P + blockIdx.x) * 3);
-}
-
-__global__ __launch_bounds__(256) void p3d_retain_kernel(unetk_lits3d_desc d, const float* __restrict__ stat,
-                                                         float* __restrict__ images) {
-  const int n = blockIdx.y, P = gridDim.x;
-  const float* st = stat + (int64_t)n * ST_N;
-  const float mn = st[ST_MN], sd = st[ST_SD], nmn = st[ST_NMN], nden = st[ST_NSD] + 1e-8f;
-  const int total = d.D * d.H * d.W;
-  float* img = images + (int64_t)n * total;
-  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < total; i += P * 256) img[i] = (img[i] - nmn + mn) / nden * sd;
-}
-
+// passes 3, 4 (gamma, retain_stats): lits_patch.h
 bool p3d_supported(const unetk_lits3d_desc* d) {
   return (int64_t)d->D * d->H * d->W < ((int64_t)1 << 31) && (int64_t)d->D * d->src_h * d->src_w < ((int64_t)1 << 31);
 }
@@ -565,10 +421,11 @@ extern "C" int unetk_lits_patch3d(const unetk_lits3d_desc* d, const uint16_t* sl
   UNETK_LAUNCH(p3d_finalize_kernel, fin, dim3(64), 0, st, 0, P, (const double*)part, (const float*)minmax, stat);
   UNETK_LAUNCH(p3d_patch_kernel, grid, dim3(256), 0, st, *d, slices, seg_slices, sample_tab, (const float*)stat, images, labels, part, minmax);
   if (d->training) {
+    const int total = d->D * d->H * d->W;                      // < 2^31: p3d_supported
     UNETK_LAUNCH(p3d_finalize_kernel, fin, dim3(64), 0, st, 1, P, (const double*)part, (const float*)minmax, stat);
-    UNETK_LAUNCH(p3d_gamma_kernel, grid, dim3(256), 0, st, *d, sample_tab, (const float*)stat, images, part);
+    UNETK_LAUNCH(p3d_gamma_kernel, grid, dim3(256), 0, st, total, sample_tab, (const float*)stat, images, part);
     UNETK_LAUNCH(p3d_finalize_kernel, fin, dim3(64), 0, st, 2, P, (const double*)part, (const float*)minmax, stat);
-    UNETK_LAUNCH(p3d_retain_kernel, grid, dim3(256), 0, st, *d, (const float*)stat, images);
+    UNETK_LAUNCH(p3d_retain_kernel, grid, dim3(256), 0, st, total, (const float*)stat, images);
   }
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;

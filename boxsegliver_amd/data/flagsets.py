@@ -115,6 +115,8 @@ PIPELINES = {
                   "--eval_in_patches", "--eval_num_batches_per_epoch", "--eval_mirror", "--tumor_percent"],
                  {"--im_channel": 1, "--zoom_scale": (1.0, 1.25)}),
 }
+# the click-guided nets on LiTS (data/lits_inter.py): the flag group of `nf_inter`, verbatim
+PIPELINES["liver_inter"] = PIPELINES["nf_g_simply"]
 
 
 def add_arguments(parser, pipeline):

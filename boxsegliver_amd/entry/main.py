@@ -5,7 +5,8 @@ entry/main_g.py, entry/main_g.py (GUNet):
 
 The first positional argument selects the dataset pipeline and evaluator exactly as in the reference (entry/main.py:53-77:
 only_liver | liver | nf | nf_inter | nf_3d; entry/main_g.py:55-73: liver | nf | nf2 | nf_inter; plus `liver_3d`, UNet3D on
-LiTS, which the reference does not have: data/lits3d.py); every flag of the six
+LiTS, and `liver_inter`, the click-guided nets on LiTS, which the reference does not have: data/lits3d.py,
+data/lits_inter.py); every flag of the six
 argument groups the reference merges (config, core.models, core.solver, loss_metrics, <pipeline>, <evaluator>) is accepted
 with the same name and default, so the shipped run scripts' flag lists parse unchanged (tests/test_entry_host.py does that
 with run_scripts/template/001_unet.sh, scripts/102_gnet_v1.sh and threed_script/201_unet_v1.sh's lists).
@@ -36,6 +37,9 @@ def _liver(pipeline):
     if pipeline == "liver_3d":                          # UNet3D on LiTS: 3-D patches from the same resident store
         from ..data import lits3d
         return lits3d.add_arguments, lits3d.input_fn, lits3d.input_fn_eval, evaluator_liver
+    if pipeline == "liver_inter":                       # the click-guided nets on LiTS: clicks simulated on the device
+        from ..data import lits_inter
+        return lits_inter.add_arguments, lits_inter.input_fn, lits_inter.input_fn_eval, evaluator_liver
 
     def add(parser):
         flagsets.add_arguments(parser, pipeline)
@@ -53,9 +57,10 @@ def _nf(pipeline):
 # sub-command -> pipeline: entry/main.py:53-77 and entry/main_g.py:55-73
 SUBCOMMANDS = {
     False: {"only_liver": lambda: _liver("liver_li"), "liver": lambda: _liver("liver"), "nf": lambda: _nf("nf"),
-            "nf_inter": lambda: _nf("nf_g_simply"), "nf_3d": lambda: _nf("nf_3d"), "liver_3d": lambda: _liver("liver_3d")},
+            "nf_inter": lambda: _nf("nf_g_simply"), "nf_3d": lambda: _nf("nf_3d"), "liver_3d": lambda: _liver("liver_3d"),
+            "liver_inter": lambda: _liver("liver_inter")},
     True: {"liver": lambda: _liver("liver_g"), "nf": lambda: _nf("nf_g"), "nf2": lambda: _nf("nf_iin"),
-           "nf_inter": lambda: _nf("nf_g_simply")},
+           "nf_inter": lambda: _nf("nf_g_simply"), "liver_inter": lambda: _liver("liver_inter")},
 }
 
 
@@ -95,6 +100,9 @@ def _setup_logging(args):
 
 def run(args, sub, pipe, guided=False, dataset_params=None):
     _, input_fn, input_fn_eval, evaluator_lib = pipe
+    if sub == "liver_inter":                             # refused flags and modes raise before anything is loaded
+        from ..data import lits_inter
+        lits_inter.check_args(args)
     _setup_logging(args)
     log.debug(args)
     if args.num_gpus < 2:

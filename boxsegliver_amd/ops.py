@@ -1698,6 +1698,93 @@ def eval3d_finish(acc, weight, box, uncovered):
     return pred
 
 
+def lits_inter_desc(slices, n, shape, training=False, obj_label=1, im_scale=64, lab_scale=64, noise_scale=0.0, seed=0,
+                    clicks=(3, 10, 40, 5)):
+    """The descriptor of unetk_lits_inter_batch and unetk_lits_clicks (include/unetk.h): shape = (C, H, W), clicks = (margin,
+    step, band, max_clicks) -- the reference's 3, 10, 40, 5 (input_pipeline_g_simply.py:548-560)."""
+    c, h, w = (int(v) for v in shape)
+    margin, step, band, max_clicks = (int(v) for v in clicks)
+    return _abi.LitsInterDesc(N=int(n), H=h, W=w, C=c, n_slices=slices.shape[0], src_h=slices.shape[1], src_w=slices.shape[2],
+                              im_scale=int(im_scale), lab_scale=int(lab_scale), obj_label=int(obj_label),
+                              training=1 if training else 0, seed=int(seed) & 0xffffffff, noise_scale=float(noise_scale),
+                              margin=margin, step=step, band=band, max_clicks=max_clicks, G=2, gaussian=0, stddev=1.0)
+
+
+def _inter_tab(sample_tab):
+    assert sample_tab.dtype == torch.int32 and sample_tab.dim() == 2 and sample_tab.shape[1] == _abi.LITS3D_TAB_COLS
+    assert sample_tab.is_contiguous()
+    return sample_tab.shape[0]
+
+
+def lits_inter_batch(slices, seg_slices, sample_tab, shape, training, status, obj_label=1, noise_scale=0.0, seed=0,
+                     im_scale=64, lab_scale=64):
+    """One click-guided 2-D batch without its guide (unetk_lits_inter_batch): sample_tab int32 [N, 16] (the LiTS 3-D table),
+    shape = (C, H, W).  Returns images f32 [N, H, W, C], labels int32 [N, H, W] in {0, 1} (1 = stored label >= obj_label).
+    training: gamma with the table's per-sample gamma, then -- noise_scale > 0 -- uniform noise keyed by `seed` and the
+    channel mask.  status int32 [1] (zeroed by the caller) collects bit 1; it is NOT read here.  Current stream."""
+    _require_cuda(slices, seg_slices, sample_tab, status)
+    assert slices.dtype in (torch.int16, torch.uint16) and seg_slices.dtype == torch.uint8
+    assert slices.is_contiguous() and seg_slices.is_contiguous() and slices.shape == seg_slices.shape and slices.dim() == 3
+    assert status.dtype == torch.int32 and status.numel() >= 1
+    n = _inter_tab(sample_tab)
+    desc = lits_inter_desc(slices, n, shape, training, obj_label, im_scale, lab_scale, noise_scale, seed)
+    nbytes = int(_abi.lib().unetk_lits_inter_batch_ws_bytes(ctypes.byref(desc)))
+    if nbytes == 0:
+        raise _abi.UnetkError("lits_inter_batch: unsupported shape {} (C odd, <= 7) from {} x {} slices".format(
+            tuple(shape), slices.shape[1], slices.shape[2]))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=slices.device)
+    images = torch.empty((n, desc.H, desc.W, desc.C), dtype=torch.float32, device=slices.device)
+    labels = torch.empty((n, desc.H, desc.W), dtype=torch.int32, device=slices.device)
+    with _timed_hbm("lits_inter_batch", images, 7 if training else 1, labels.numel() * 4):
+        check(_abi.lib().unetk_lits_inter_batch(ctypes.byref(desc), ptr(slices), ptr(seg_slices), ptr(sample_tab), ptr(images),
+                                                ptr(labels), ptr(status), ptr(ws), nbytes, stream_ptr()), "lits_inter_batch")
+    return images, labels
+
+
+def lits_clicks(seg_slices, sample_tab, click_tab, status, obj_label=1, clicks=(3, 10, 40, 5), lab_scale=64):
+    """The simulated clicks of a batch (unetk_lits_clicks; include/unetk.h has the semantics): click_tab uint32-valued int32
+    [N, 12] = the sample's draws.  Returns pts int32 [N, 2, 4, 2] = (kind fg / bg, click, (y, x) in the crop; -1 padding)
+    and cnt int32 [N, 2].  status collects bits 1 and 2; it is NOT read here.  Current stream."""
+    _require_cuda(seg_slices, sample_tab, click_tab, status)
+    assert seg_slices.dtype == torch.uint8 and seg_slices.dim() == 3 and seg_slices.is_contiguous()
+    n = _inter_tab(sample_tab)
+    assert click_tab.dtype == torch.int32 and tuple(click_tab.shape) == (n, _abi.LITS_CLICK_TAB_COLS) and click_tab.is_contiguous()
+    assert status.dtype == torch.int32 and status.numel() >= 1
+    desc = lits_inter_desc(seg_slices, n, (1, 1, 1), obj_label=obj_label, lab_scale=lab_scale, clicks=clicks)
+    nbytes = int(_abi.lib().unetk_lits_clicks_ws_bytes(ctypes.byref(desc)))
+    if nbytes == 0:
+        raise _abi.UnetkError("lits_clicks: unsupported parameters {} on {} x {} slices".format(
+            tuple(clicks), seg_slices.shape[1], seg_slices.shape[2]))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=seg_slices.device)
+    pts = torch.empty((n, 2, _abi.LITS_MAX_CLICKS, 2), dtype=torch.int32, device=seg_slices.device)
+    cnt = torch.empty((n, 2), dtype=torch.int32, device=seg_slices.device)
+    with _timed_hbm("lits_clicks", ws, 3):
+        check(_abi.lib().unetk_lits_clicks(ctypes.byref(desc), ptr(seg_slices), ptr(sample_tab), ptr(click_tab), ptr(pts),
+                                           ptr(cnt), ptr(status), ptr(ws), nbytes, stream_ptr()), "lits_clicks")
+    return pts, cnt
+
+
+def click_guide(sample_tab, pts, cnt, out_hw, src_hw, guide_channel=2, stddev=None):
+    """sp_guide f32 [N, H, W, guide_channel] from clicks (unetk_click_guide): pts int32 [N, 2, 4, 2], cnt int32 [N, 2], in the
+    crop boxes and under the flips of sample_tab.  stddev None: Euclidean distance to the nearest click; a float: the
+    Gaussian of --local_enhance.  guide_channel 2: (fg, bg); 1: fg - bg.  Current stream."""
+    _require_cuda(sample_tab, pts, cnt)
+    n = _inter_tab(sample_tab)
+    assert pts.dtype == torch.int32 and tuple(pts.shape) == (n, 2, _abi.LITS_MAX_CLICKS, 2) and pts.is_contiguous()
+    assert cnt.dtype == torch.int32 and tuple(cnt.shape) == (n, 2) and cnt.is_contiguous()
+    h, w = int(out_hw[0]), int(out_hw[1])
+    # the guide reads the geometry and its own three fields; the store's and the simulator's only have to be valid
+    desc = _abi.LitsInterDesc(N=n, H=h, W=w, C=1, n_slices=1, src_h=int(src_hw[0]), src_w=int(src_hw[1]), im_scale=1, lab_scale=1,
+                              obj_label=1, training=0, seed=0, noise_scale=0.0, margin=1, step=0, band=1, max_clicks=2,
+                              G=int(guide_channel), gaussian=0 if stddev is None else 1,
+                              stddev=0.0 if stddev is None else float(stddev))
+    guide = torch.empty((n, h, w, int(guide_channel)), dtype=torch.float32, device=sample_tab.device)
+    with _timed_hbm("click_guide", guide, 1):
+        check(_abi.lib().unetk_click_guide(ctypes.byref(desc), ptr(sample_tab), ptr(pts), ptr(cnt), ptr(guide), stream_ptr()),
+              "click_guide")
+    return guide
+
+
 def adam_step(p, g, m, v, lr_t, beta1, beta2, eps, gscale=1.0, l2=0.0, decoupled_wd=0.0):
     with _timed_hbm("adam_step", p, 7):            # reads p, g, m, v; writes p, m, v
         check(_abi.lib().unetk_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr_t, beta1, beta2, eps, gscale, l2,

@@ -814,6 +814,86 @@ int unetk_eval3d_accumulate_w(const unetk_lits3d_desc* d, const int32_t* sample_
 int unetk_eval3d_finish(const float* acc, int C, int depth, int src_h, int src_w, const float* wsum, const int32_t* cnt,
                         const int32_t box[6], uint8_t* pred, int32_t* uncovered, void* stream);
 
+/* ---------------------------------------------------------------- LiTS click-guided 2-D batches  
+ * Batches for the nets that take concat(images, sp_guide) (UNetInter, SmallUNet, InterUNet, LGNet), cropped from the resident
+ * slice store with the semantics of the reference's interactive pipeline for the NF data (DataLoader/NF/
+ * input_pipeline_g_simply.py:564-636 gen_batch, :435-527 data_processing, :346-412 inter_simulation as :530-561 gen_kernel
+ * calls it; DataLoader/misc.py:108-129 img_crop; utils/image_ops.py:396-434 create_spatial_guide_2d).  Additive to ABI 10.
+ *
+ * sample_tab is the LiTS 3-D table (UNETK_LITS3D_TAB_COLS, same columns; flip_front_back is ignored), so
+ * unetk_lits_pick_voxel runs on it unchanged.  The (y, x) crop box is unetk_lits_patch3d's: ch, cw clamped into
+ * [1, src_h] x [1, src_w], y1 = min(max(cy - ch/2, 0), src_h - ch), x1 likewise.  Along z there is no clamp (img_crop):
+ * channel c shows slice cz - C/2 + c of the case, zeros where that lies outside [0, depth) or the store (padding).  C odd.
+ * The object is seg / lab_scale >= obj_label on slice cz.  status int32 [1] (zeroed by the caller) collects
+ *   bit 1 (2): a row whose centre slice cz lies outside [0, depth) or the store -- its labels are 0, it has no object;
+ *   bit 2 (4): a click_tab row out of range (n_fg outside [1, max_clicks), n_bg outside [0, max_clicks), a strategy other
+ *              than 1 or 3) -- the value is clamped (strategy: 1).
+ * Nothing is read out of bounds for any table content.
+ *
+ * unetk_lits_inter_batch: images f32 [N,H,W,C], labels int32 [N,H,W] in {0, 1}.  Per sample:
+ *   mask statistics over the whole [C, ch, cw] crop at source resolution, v = stored / im_scale: mean m and standard deviation
+ *     s of the voxels with v > 0 (fp64 partials per block, summed by index); an empty mask gives m = s = 0;
+ *   image: every bilinear corner c is normalised on the fly, c > 0 ? (c - m) / (s + 1e-8) : 0, then resize_bilinear
+ *     (align_corners) to H x W per channel;  labels: slice cz, resize_nearest_neighbor(align_corners), object ? 1 : 0;
+ *   flips (left/right, up/down) of image and label alike, by the write address;
+ *   training != 0: augment_gamma(retain_stats=True) with the row's gamma over the sample's whole [H,W,C] image, the
+ *     arithmetic of unetk_lits_patch3d;  then, if noise_scale > 0:  v <- v + (2 u - 1) * noise_scale  with
+ *     u = the library's counter generator (csrc/common.h, the dropout masks' one) of seed and the element's flat index in
+ *     [N,H,W,C] taken modulo 2^32 (each operation rounded to float32 on its own), and
+ *     every channel is multiplied by (max over (H, W) of that noised channel > 0 ? 1 : 0).
+ *   H*W*C < 2^31, C*src_h*src_w < 2^31, C <= 7 (else UNETK_E_UNSUPPORTED and a zero ws query); N <= 65535; ws 16-byte aligned.
+ *
+ * unetk_lits_clicks: the click simulator.  pts int32 [N][2][UNETK_LITS_MAX_CLICKS][2] = (kind: 0 foreground / 1 background,
+ *   click, (y, x) relative to the crop box; -1 padding), cnt int32 [N][2].  The object mask is the label crop at SOURCE
+ *   resolution.  click_tab uint32 [N][UNETK_LITS_CLICK_TAB_COLS], the sample's draws:
+ *     0 n_fg in [1, max_clicks)   1 n_bg in [0, max_clicks)   2 background strategy (1 or 3)   3 reserved (0)
+ *     4..7 one 32-bit draw per foreground click                8..11 one per background click
+ *   With d1 the city-block distance (binary_erosion's default cross, iterated):
+ *     foreground candidates {p in obj : d1(p, background or outside the crop) > margin}      (border_value = 0)
+ *     background candidates {p : margin < d1(p, obj) <= margin + band}                       (border_value = 1)
+ *   A kind's mask is obj (foreground) / not obj (background).  A mask without a pixel gives no click (deviation: the
+ *   reference would fail converting NaN for an all-object crop; it draws no foreground click without an object either).
+ *   An empty candidate set ("small"): ONE click at (sum y / count, sum x / count) of the mask, integer floor division -- for
+ *   the background without any object in the crop that is the crop's centre.  Otherwise up to n clicks: the first one, and
+ *   every one under strategy 1, is the candidate of rank i = (r * count) >> 32 (64-bit integers, r the click's draw) in
+ *   row-major order; under strategy 3 each later click is the candidate that maximises the minimum squared distance to the
+ *   clicks so far, the first in row-major order on ties.  After a click the candidates with (y-cy)^2 + (x-cx)^2 <= step^2
+ *   are removed; the kind stops early when none are left.  The foreground always uses strategy 1.
+ *   margin, band >= 1, step >= 0, margin + band <= 254, 2 <= max_clicks <= UNETK_LITS_MAX_CLICKS + 1, src_h, src_w <= 1024
+ *   (else UNETK_E_UNSUPPORTED and a zero ws query).  Integer arithmetic only, no atomics on results: two calls give
+ *   identical bits.  ws: three byte fields of src_h * src_w per sample (column distances of both kinds, candidate classes).
+ *
+ * unetk_click_guide: guide f32 [N,H,W,G] from pts / cnt (plain device arrays: real clicks may be fed) and the sample table --
+ *   same crop box and flips, so guide and image line up.  create_spatial_guide_2d at crop resolution, then resize_bilinear
+ *   (align_corners), without the intermediate: every output pixel evaluates the guide at its 4 bilinear corners and lerps.
+ *   gaussian == 0: min_k sqrt(dy^2 + dx^2) (not normalised);  gaussian != 0: max_k exp(-(dy^2 / (2 s^2) + dx^2 / (2 s^2))), s =
+ *   stddev > 0.  A kind without clicks is exactly 0; cnt is clamped into [0, UNETK_LITS_MAX_CLICKS].  G == 2: (fg, bg);
+ *   G == 1: fg - bg. */
+#define UNETK_LITS_MAX_CLICKS 4
+#define UNETK_LITS_CLICK_TAB_COLS 12
+typedef struct unetk_lits_inter_desc {
+  int32_t N, H, W, C;
+  int32_t n_slices, src_h, src_w; /* extent of the resident store */
+  int32_t im_scale, lab_scale;    /* IM_SCALE = LB_SCALE = 64 */
+  int32_t obj_label;              /* object = seg / lab_scale >= obj_label */
+  int32_t training;               /* != 0: gamma, noise, channel mask */
+  uint32_t seed;
+  float noise_scale;              /* 0 = no noise and no channel mask */
+  int32_t margin, step, band, max_clicks; /* unetk_lits_clicks: the reference passes 3, 10, 40, 5 */
+  int32_t G, gaussian;            /* unetk_click_guide */
+  float stddev;
+} unetk_lits_inter_desc;
+size_t unetk_lits_inter_batch_ws_bytes(const unetk_lits_inter_desc* d);
+int unetk_lits_inter_batch(const unetk_lits_inter_desc* d, const uint16_t* slices, const uint8_t* seg_slices,
+                           const int32_t* sample_tab, float* images, int32_t* labels, int32_t* status, void* ws,
+                           size_t ws_bytes, void* stream);
+size_t unetk_lits_clicks_ws_bytes(const unetk_lits_inter_desc* d);
+int unetk_lits_clicks(const unetk_lits_inter_desc* d, const uint8_t* seg_slices, const int32_t* sample_tab,
+                      const uint32_t* click_tab, int32_t* pts, int32_t* cnt, int32_t* status, void* ws, size_t ws_bytes,
+                      void* stream);
+int unetk_click_guide(const unetk_lits_inter_desc* d, const int32_t* sample_tab, const int32_t* pts, const int32_t* cnt,
+                      float* guide, void* stream);
+
 /* ---------------------------------------------------------------- optimiser  core/solver.py:204-243
  * tf.train.AdamOptimizer on a flat parameter buffer.  g' = g*gscale + l2*p  (slim.l2_regularizer
  * gradient, base.py:128-135);  m += (1-b1)(g'-m);  v += (1-b2)(g'^2-v);
