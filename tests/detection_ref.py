@@ -1,7 +1,12 @@
 """Per-lesion detection restated for the tests (no GPU): labelling, pair counting and the matching rule of the reference's
 utils/array_kits.distinct_binary_object_correspondences / loss_metrics.tumor_detection_metrics, written from their
-description and kept apart from boxsegliver_amd.utils.array_kits -- the reference itself cannot run here (it needs medpy
-and np.bool).
+description and kept apart from boxsegliver_amd.utils.array_kits.
+
+The reference function does run in the build container with two shims -- `np.bool` aliased to bool and a stand-in for
+`medpy.metric.dc`, dc(a, b) = 2 |a & b| / (|a| + |b|) -- and tests/golden/make_detection_fixtures.py records what it gives
+in tests/golden/ref_detection.npz (`reference_records` reads it).  test_ref_detection_host.py holds this restatement and
+array_kits to those records, test_gpu_detection.py the device tables.  That pins the matching rule (the labelling, which
+reference object gets which result object, in which order); it does not pin medpy's Dice, which is the stand-in's.
 
 The reference keeps the candidates of a reference object that overlaps several result objects in a container of its own.
 WaitingSet is that container, with its quirks:
@@ -11,6 +16,9 @@ WaitingSet is that container, with its quirks:
     nothing is left;
   * popping does not shrink the length the size sort and the emptiness test see: that length is fixed when the set is built.
 """
+import json
+import os
+
 import numpy as np
 import scipy.ndimage as ndi
 
@@ -120,3 +128,26 @@ def blob(rng, shape, density, sigma=1.0):
     """Thresholded smoothed noise with the given fraction of object voxels."""
     x = ndi.gaussian_filter(rng.random(shape), sigma)
     return x > np.quantile(x, 1.0 - density)
+
+
+def reference_records():
+    """tests/golden/ref_detection.npz as [(name, result bool [D, H, W], reference bool [D, H, W], n_res, n_ref, {thresh: rows})],
+    rows int64 [m, 5] = (reference object's first voxel, result object's first voxel, intersection, reference size, result
+    size) of the matched pairs in the order the reference decided them; first voxels are row-major flat indices."""
+    f = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_detection.npz"))
+    names, off, moff = json.loads(str(f["names"])), f["bit_offsets"], f["match_offsets"]
+    out = []
+    for c, name in enumerate(names):
+        shape = tuple(int(v) for v in f["shapes"][c])
+        n = int(np.prod(shape))
+        vols = [np.unpackbits(f["bits"][off[2 * c + k]:off[2 * c + k + 1]])[:n].reshape(shape).astype(bool) for k in range(2)]
+        rows = {float(t): f["matches"][moff[3 * c + k]:moff[3 * c + k + 1]] for k, t in enumerate(f["thresholds"])}
+        out.append((name, vols[0], vols[1], int(f["counts"][c, 0]), int(f["counts"][c, 1]), rows))
+    return out
+
+
+def first_voxels(labeled, n):
+    """Row-major flat index of the first voxel of objects 1 .. n of a labelled volume."""
+    ids, first = np.unique(labeled.ravel(), return_index=True)
+    assert ids[ids > 0].tolist() == list(range(1, n + 1))
+    return first[ids > 0].astype(np.int64)

@@ -1,8 +1,10 @@
 """Helpers of the click-guided LiTS pipeline tests (test_lits_inter_host.py, test_gpu_lits_inter.py): the float64 / integer
 numpy restatement of what `unetk_lits_inter_batch`, `unetk_lits_clicks` and `unetk_click_guide` compute.
 
-TensorFlow does not run here, so the restatement is builder-written ("parity unpinned"); each step cites the
-reference lines it restates:
+TensorFlow does not run here, so the restatement is builder-written ("parity unpinned"), except `crop_box` and
+`clicks`: the reference's img_crop, gen_kernel and inter_simulation are plain numpy / scipy and do run in the build container,
+and test_ref_clicks_host.py holds both to what they gave (tests/golden/ref_clicks.json).  Each step cites the reference lines
+it restates:
   crop       DataLoader/misc.py:108-129 img_crop: slices cz - C/2 .. cz + C/2, zero padding outside the case (no shift); the
              (y, x) box clamped to the slice
   z-score    DataLoader/NF/input_pipeline_g_simply.py:437-442 (lits3d_ref.zscore; an empty mask gives zeros)

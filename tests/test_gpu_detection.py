@@ -233,6 +233,34 @@ def test_device_metrics_equal_host_metrics_key_for_key(blobs):
         assert dev == host and (math.isinf(dev["precision"]) or math.isinf(dev["recall"]))
 
 
+# ------------------------------------------------------------------------------------------------ the reference's records
+def test_device_tables_through_the_matching_rule_give_the_reference_records():
+    """tests/golden/ref_detection.npz (what the reference's own function matched; make_detection_fixtures.py): the device's
+    roots, sizes and overlaps through array_kits.match_components give the same pairs in the same order, integer for
+    integer; the Dice score is within 2 ulp of the float64 quotient of the recorded integers (one division of exact
+    integers on either side)."""
+    from boxsegliver_amd.utils import array_kits
+    cap_obj, cap_pair = 64, 256
+    matched = 0
+    for name, res, ref, n_res, n_ref, rows in dref.reference_records():
+        t = _run(res, ref, cap_obj, cap_pair)
+        assert t[:2].tolist() == [n_res, n_ref] and t[3] == 0, name
+        obj = t[4:4 + 4 * cap_obj].reshape(2, cap_obj, 2).astype(np.int64)
+        res_rows, ref_rows = obj[0, :n_res], obj[1, :n_ref]                    # (first voxel, size) per object
+        pairs = t[4 + 4 * cap_obj:].reshape(cap_pair, 3)[:t[2]].astype(np.int64)
+        overlap = {(int(j), int(i)): int(o) for j, i, o in pairs}
+        for thresh, want in rows.items():
+            mapping = array_kits.match_components(res_rows[:, 1], ref_rows[:, 1], pairs, thresh)
+            got = [(ref_rows[j - 1, 0], res_rows[i - 1, 0], overlap[(j, i)], ref_rows[j - 1, 1], res_rows[i - 1, 1])
+                   for j, (i, _) in mapping.items()]
+            np.testing.assert_array_equal(np.array(got, np.int64).reshape(-1, 5), want, err_msg="{} {}".format(name, thresh))
+            for (_, score), (_, _, inter, a, b) in zip(mapping.values(), want.tolist()):
+                q = 2.0 * inter / float(a + b)
+                assert abs(score - q) <= 2 * np.spacing(q), (name, thresh, score, q)
+            matched += len(want)
+    assert matched > 100
+
+
 # ------------------------------------------------------------------------------------------------ the evaluator
 def _lits_args(tmp_path, **over):
     import test_gpu_unet as t

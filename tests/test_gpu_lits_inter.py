@@ -13,6 +13,7 @@ import torch
 
 import guardbuf
 import lits_inter_ref as ref
+from click_shapes import rank_draw as _rank_draw
 
 pytestmark = pytest.mark.gpu
 
@@ -55,13 +56,6 @@ def _status():
 
 
 # ------------------------------------------------------------------------------------------------- clicks
-def _rank_draw(rank, count):
-    """A 32-bit draw r with (r * count) >> 32 == rank."""
-    r = ((rank << 32) + count - 1) // count
-    assert (r * count) >> 32 == rank and r < 1 << 32
-    return r
-
-
 def _click_cases(params):
     """(case, centre, crop, obj_label, click_tab row, what the row is there for)."""
     last = 0xFFFFFFFF
