@@ -82,6 +82,15 @@ class LitsInterDesc(Structure):
 LITS_MAX_CLICKS = 4         # UNETK_LITS_MAX_CLICKS
 LITS_CLICK_TAB_COLS = 12    # UNETK_LITS_CLICK_TAB_COLS
 
+
+
+class Lits3dClicksDesc(Structure):
+    _fields_ = [("N", c_int32), ("D", c_int32), ("H", c_int32), ("W", c_int32), ("n_slices", c_int32), ("src_h", c_int32),
+                ("src_w", c_int32), ("lab_scale", c_int32), ("obj_label", c_int32), ("margin", c_int32), ("step", c_int32),
+                ("band", c_int32), ("max_clicks", c_int32), ("G", c_int32), ("gaussian", c_int32), ("stddev", c_float * 3),
+                ("euclid_norm", c_float)]
+
+
 P = c_void_p
 _SIGNATURES = {
     "unetk_lits_pick_voxel": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P]),
@@ -95,6 +104,9 @@ _SIGNATURES = {
     "unetk_lits_clicks_ws_bytes": (c_size_t, [POINTER(LitsInterDesc)]),
     "unetk_lits_clicks": (c_int, [POINTER(LitsInterDesc), P, P, P, P, P, P, P, c_size_t, P]),
     "unetk_click_guide": (c_int, [POINTER(LitsInterDesc), P, P, P, P, P]),
+    "unetk_lits3d_clicks_ws_bytes": (c_size_t, [POINTER(Lits3dClicksDesc)]),
+    "unetk_lits3d_clicks": (c_int, [POINTER(Lits3dClicksDesc), P, P, P, P, P, P, P, c_size_t, P]),
+    "unetk_click_guide3d": (c_int, [POINTER(Lits3dClicksDesc), P, P, P, P, P]),
     "unetk_lits_batch": (c_int, [POINTER(LitsDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "unetk_lits_spatial_guide": (c_int, [POINTER(LitsGuideDesc), P, P, P, P, P]),
     "unetk_lits_context": (c_int, [P, c_int64, c_int, P, c_int, c_int, P, P, P, P]),

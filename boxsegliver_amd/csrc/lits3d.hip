@@ -15,7 +15,7 @@
 //              float stat[N][8] = {m, s, mn, sd, min, range, new_mn, new_sd}
 #include "common.h"
 #include "lits_geom.h"
-#include "lits_patch.h"      // TW, ST_*, block_sum3 / block_minmax, p3d_finalize_kernel, the two gamma passes
+#include "lits_patch.h"      // TW, ST_*, Box3 / p3d_box, block_sum3 / block_minmax, p3d_finalize_kernel, the two gamma passes
 
 namespace {
 
@@ -74,29 +74,7 @@ __global__ __launch_bounds__(1024) void lits_pick_voxel_kernel(const uint8_t* __
   }
 }
 
-// ------------------------------------------------------------------------------------------------ crop box
-struct Box3 {
-  int64_t base;
-  int depth, z1, y1, x1, ch, cw;
-};
-// DataLoader/misc.py:132-143 volume_crop, with the crop clamped to the slice and a case shallower than D starting at 0
-__device__ __forceinline__ Box3 p3d_box(const int32_t* __restrict__ t, const unetk_lits3d_desc& d) {
-  Box3 b;
-  b.base = t[0];
-  b.depth = max(t[1], 0);
-  b.ch = min(max(t[5], 1), d.src_h);
-  b.cw = min(max(t[6], 1), d.src_w);
-  b.z1 = min(max(t[2] - d.D / 2, 0), max(b.depth - d.D, 0));
-  b.y1 = min(max(t[3] - b.ch / 2, 0), d.src_h - b.ch);
-  b.x1 = min(max(t[4] - b.cw / 2, 0), d.src_w - b.cw);
-  return b;
-}
-// store index of crop slice z, or -1 where the crop leaves the case (or the store): zeros, label 0
-__device__ __forceinline__ int64_t p3d_slice(const Box3& b, int z, const unetk_lits3d_desc& d) {
-  const int zs = b.z1 + z;
-  const int64_t s = b.base + zs;
-  return (zs < b.depth && s >= 0 && s < d.n_slices) ? s : -1;
-}
+// crop box: Box3, p3d_box, p3d_slice (lits_patch.h; lits3d_clicks.hip cuts the same box)
 
 // ------------------------------------------------------------------------------------------------ pass 1: mask moments
 // data_processing :354-357: moments over the crop's voxels with v > 0, at SOURCE resolution.  v = stored / im_scale is an

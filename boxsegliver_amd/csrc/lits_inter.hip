@@ -22,17 +22,13 @@
 //                     click is not written back, a candidate is alive while it is farther than `step` from every click so far
 // Everything is integer arithmetic and every reduction has a fixed order (ballots inside a wave, waves by index).
 #include "common.h"
+#include "lits_clicks.h"     // MAXK, CTW, CLS_*, CLK_U, clk_draws, clk_col_sweeps: shared with lits3d_clicks.hip
 #include "lits_geom.h"
 #include "lits_patch.h"
 
 namespace {
 
-constexpr int MAXK = UNETK_LITS_MAX_CLICKS;
-constexpr int CTW = UNETK_LITS_CLICK_TAB_COLS;
 constexpr int IB_MAX_C = 7;              // image channels (odd; the channel-mask partials are 8 floats per block)
-constexpr int CLK_MAX_EXTENT = 1024;     // rows / columns of a slice the simulator takes (its row buffer lives in LDS)
-enum { CLS_FG = 1, CLS_BG = 2, CLS_OBJ = 4 };
-constexpr int CLK_U = 8;                  // pixels a thread loads before it works on them (clk_cols_kernel, clk_select_kernel)
 
 // ------------------------------------------------------------------------------------------------ crop box
 struct Box2 {
@@ -222,46 +218,7 @@ __global__ __launch_bounds__(64) void clk_cols_kernel(unetk_lits_inter_desc d, c
   uint8_t* gf = ws + (int64_t)n * 3 * plane;
   uint8_t* gb = gf + plane;
   const uint8_t* p = segs + (sl < 0 ? 0 : sl) * plane + (int64_t)b.y1 * d.src_w + b.x1 + x;
-  // CLK_U rows per step, their loads issued together: the sweeps are chains of dependent adds, not of dependent loads
-  int df = 0, db = cap;
-  for (int y0 = 0; y0 < b.ch; y0 += CLK_U) {
-    int s[CLK_U];
-#pragma unroll
-    for (int u = 0; u < CLK_U; ++u) s[u] = (sl >= 0 && y0 + u < b.ch) ? (int)p[(int64_t)(y0 + u) * d.src_w] : 0;
-#pragma unroll
-    for (int u = 0; u < CLK_U; ++u) {
-      const int y = y0 + u;
-      if (y < b.ch) {
-        const bool o = s[u] >= thr;
-        df = o ? min(df + 1, cap) : 0;
-        db = o ? 0 : min(db + 1, cap);
-        gf[y * b.cw + x] = (uint8_t)df;
-        gb[y * b.cw + x] = (uint8_t)db;
-      }
-    }
-  }
-  df = 0;
-  db = cap;
-  for (int y0 = b.ch - 1; y0 >= 0; y0 -= CLK_U) {
-    int f[CLK_U], g[CLK_U];
-#pragma unroll
-    for (int u = 0; u < CLK_U; ++u) {
-      const int y = max(y0 - u, 0);
-      f[u] = gf[y * b.cw + x];
-      g[u] = gb[y * b.cw + x];
-    }
-#pragma unroll
-    for (int u = 0; u < CLK_U; ++u) {
-      const int y = y0 - u;
-      if (y >= 0) {
-        const bool o = f[u] > 0;                              // the downward distance is positive exactly on object pixels
-        df = o ? min(df + 1, cap) : 0;
-        db = o ? 0 : min(db + 1, cap);
-        gf[y * b.cw + x] = (uint8_t)min(f[u], df);
-        gb[y * b.cw + x] = (uint8_t)min(g[u], db);
-      }
-    }
-  }
+  clk_col_sweeps(p, sl >= 0, d.src_w, b.ch, b.cw, thr, cap, gf + x, gb + x);
 }
 
 // ------------------------------------------------------------------------------------------------ clicks: row pass, classes
@@ -335,12 +292,9 @@ __global__ __launch_bounds__(1024) void clk_select_kernel(unetk_lits_inter_desc 
   const int bit = kind == 0 ? CLS_FG : CLS_BG, step2 = d.step * d.step;
   // the sample's draws, clamped into their ranges
   const uint32_t* ct = click_tab + (int64_t)n * CTW;
-  const int n_min = kind == 0 ? 1 : 0;
-  const uint32_t want_raw = ct[kind];
-  const int want = (int)min(max(want_raw, (uint32_t)n_min), (uint32_t)(d.max_clicks - 1));
-  const uint32_t strat_raw = kind == 0 ? 1u : ct[2];
-  const int strategy = strat_raw == 3u ? 3 : 1;
-  if (threadIdx.x == 0 && ((uint32_t)want != want_raw || (strat_raw != 1u && strat_raw != 3u))) atomicOr(status, 4);
+  const ClkDraws dr = clk_draws(ct, kind, d.max_clicks);
+  const int want = dr.want, strategy = dr.strategy;
+  if (threadIdx.x == 0 && dr.bad) atomicOr(status, 4);
 
   // pass 0: candidates per wave; the mask's pixel count and coordinate sums
   Clicks c;

@@ -1,7 +1,8 @@
 // Passes shared by the LiTS patch pipelines that z-score a crop and gamma-augment the result (lits3d.hip: 3-D patches,
-// lits_inter.hip: 2-D click-guided batches): the sample table's crop clamp, the block reductions, the finalising block and
-// the two gamma passes.  One copy, so the two pipelines cannot drift; every reduction goes through fp64 per-block partials
-// that a finalising block walks by index -- no floating-point atomics, identical bits on every call.
+// lits_inter.hip: 2-D click-guided batches): the sample table's crop clamp, the 3-D crop box (also lits3d_clicks.hip's), the
+// block reductions, the finalising block and the two gamma passes.  One copy, so the pipelines cannot drift; every reduction
+// goes through fp64 per-block partials that a finalising block walks by index -- no floating-point atomics, identical bits
+// on every call.
 //   workspace: double sums[N][P][3], float minmax[N][P][2] (the blocks' partials: see "block reductions"), then
 //              float stat[N][8] = {m, s, mn, sd, min, range, new_mn, new_sd}
 #pragma once
@@ -17,6 +18,34 @@ enum { ST_M = 0, ST_S, ST_MN, ST_SD, ST_MIN, ST_RNG, ST_NMN, ST_NSD, ST_N };
 inline int p3d_blocks_for(int64_t vox) {
   const int64_t p = (vox + P3D_VOX_PER_BLOCK - 1) / P3D_VOX_PER_BLOCK;
   return (int)(p < 1 ? 1 : (p > P3D_MAX_BLOCKS ? P3D_MAX_BLOCKS : p));
+}
+
+// ------------------------------------------------------------------------------------------------ 3-D crop box
+// The box of one sample-table row, for every descriptor that carries D, src_h, src_w and n_slices (unetk_lits3d_desc,
+// unetk_lits3d_clicks_desc): patches, window accumulation and the 3-D click simulator cut the same voxels.
+struct Box3 {
+  int64_t base;
+  int depth, z1, y1, x1, ch, cw;
+};
+// DataLoader/misc.py:132-143 volume_crop, with the crop clamped to the slice and a case shallower than D starting at 0
+template <class Desc>
+__device__ __forceinline__ Box3 p3d_box(const int32_t* __restrict__ t, const Desc& d) {
+  Box3 b;
+  b.base = t[0];
+  b.depth = max(t[1], 0);
+  b.ch = min(max(t[5], 1), d.src_h);
+  b.cw = min(max(t[6], 1), d.src_w);
+  b.z1 = min(max(t[2] - d.D / 2, 0), max(b.depth - d.D, 0));
+  b.y1 = min(max(t[3] - b.ch / 2, 0), d.src_h - b.ch);
+  b.x1 = min(max(t[4] - b.cw / 2, 0), d.src_w - b.cw);
+  return b;
+}
+// store index of crop slice z, or -1 where the crop leaves the case (or the store): zeros, label 0
+template <class Desc>
+__device__ __forceinline__ int64_t p3d_slice(const Box3& b, int z, const Desc& d) {
+  const int zs = b.z1 + z;
+  const int64_t s = b.base + zs;
+  return (zs < b.depth && s >= 0 && s < d.n_slices) ? s : -1;
 }
 
 // ------------------------------------------------------------------------------------------------ block reductions

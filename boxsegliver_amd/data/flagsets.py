@@ -110,10 +110,12 @@ PIPELINES = {
                "--sample_neg", "--use_cascade", "--cascade_binary", "--use_2d", "--downsampling", "--model_2d",
                "--model_2d_config", "--ckpt_2d"],
               {"--im_channel": 1, "--zoom_scale": (1.0, 1.25), "--stddev": [1, 3., 3.]}),
-    # UNet3D on LiTS (data/lits3d.py): the flags of DataLoader/NF/input_pipeline_3d.py:53-67 that apply, its defaults
+    # UNet3D on LiTS (data/lits3d.py): the flags of DataLoader/NF/input_pipeline_3d.py:53-67 that apply, its defaults; the
+    # click guides (--use_spatial) take nf_3d's four flags, --stddev as its (z, y, x) list
     "liver_3d": (["--test_fold", "--im_depth", "--im_height", "--im_width", "--im_channel", "--zoom_scale", "--random_flip",
-                  "--eval_in_patches", "--eval_num_batches_per_epoch", "--eval_mirror", "--tumor_percent"],
-                 {"--im_channel": 1, "--zoom_scale": (1.0, 1.25)}),
+                  "--eval_in_patches", "--eval_num_batches_per_epoch", "--eval_mirror", "--tumor_percent", "--use_spatial",
+                  "--local_enhance", "--stddev", "--guide_channel"],
+                 {"--im_channel": 1, "--zoom_scale": (1.0, 1.25), "--stddev": [1, 3., 3.]}),
 }
 # the click-guided nets on LiTS (data/lits_inter.py): the flag group of `nf_inter`, verbatim
 PIPELINES["liver_inter"] = PIPELINES["nf_g_simply"]

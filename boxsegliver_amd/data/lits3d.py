@@ -18,6 +18,12 @@ Two deviations from the literal reference arithmetic: a case shallower than --im
 with zero slices (the reference would index with a negative start), and a patch without a single non-zero voxel is all
 zeros (TensorFlow's moments of an empty tensor are NaN).
 
+With --use_spatial the batches carry `sp_guide`: the clicks of :258-324 `inter_simulation` as :474-504
+`gen_kernel` calls it are simulated on the device from per-sample draws made here (`lits_inter.draw_click_tab`, drawn after
+the sampler's draw so that an unguided run consumes its generator exactly as without the feature) -> `unetk_lits3d_clicks`;
+:364-398 with utils/image_ops.py:437-472 `create_spatial_guide_3d` -> `unetk_click_guide3d`.  The object the clicks are
+simulated on is the sampler's forced class (stored label >= fg_label); the restatement is tests/lits3d_clicks_ref.py.
+
 Offline, `input_fn_eval` tiles every case of the validation fold with windows cut as `eval_online` cuts them (window_starts,
 eval_tables) for the sliding-window evaluator, `EvaluateVolume.run_3d` (--eval_in_patches).  Two options
 of that evaluation live here too: the per-axis Gaussian window tables (window_weights, --eval_window_weight gaussian) and
@@ -39,6 +45,11 @@ LABEL_MAPS = (("Liver",), ("Liver", "Tumor"))
 WINDOW_WEIGHTS = ("uniform", "gaussian")
 MIN_WINDOW_WEIGHT = 1e-30          # the smallest weight of a window, gz[0] * gy[0] * gx[0] in float32, may not fall below this
 DEFAULT_BOX_MARGIN = (0, 25, 25)   # (z, y, x): padding_z / padding of the 2-D --eval_in_patches (lits.get_dataset_for_eval_patches)
+CLICKS = (3, 10, 40, 5)            # gen_kernel :492-503: margin, step, N; d = 40 for the background band
+DEFAULT_STDDEV = (1.0, 3.0, 3.0)   # --stddev of nf_3d: (z, y, x)
+STATUS_BITS = ((1, "unetk_lits_pick_voxel: a forced sample's rank was beyond the forced-class count of its slice; the per-slice "
+                   "counts do not match the resident store"),
+               (4, "unetk_lits3d_clicks: a row of click draws was out of range"))
 (COL_BASE, COL_DEPTH, COL_CZ, COL_CY, COL_CX, COL_CH, COL_CW, COL_FLIP_LR, COL_FLIP_UD, COL_FLIP_FB, COL_GAMMA, COL_FORCED,
  COL_K) = range(13)
 
@@ -80,7 +91,24 @@ def check_args(args):
         raise ValueError("--eval_box_margin takes three voxel counts >= 0 (z y x), got {}".format(list(margin)))
     if margin is not DEFAULT_BOX_MARGIN and getattr(args, "eval_box_from", None) is None:       # argparse keeps the default object
         raise ValueError("--eval_box_margin grows the box of --eval_box_from, which is not given")
+    guide_stddev(args)
+    if int(getattr(args, "guide_channel", 2)) not in (1, 2):
+        raise ValueError("--guide_channel must be 1 or 2, got {}".format(args.guide_channel))
+    if getattr(args, "use_spatial", False) and getattr(args, "mode", "train") == "eval":
+        raise NotImplementedError("--mode eval with --use_spatial is not built: the sliding-window evaluator has no clicks")
     return label_map(args.classes)
+
+
+def guide_stddev(args):
+    """--stddev -> (s_z, s_y, s_x), three positive numbers (nf_3d's default 1 3 3)."""
+    sd = getattr(args, "stddev", DEFAULT_STDDEV)
+    try:
+        sd = tuple(float(v) for v in sd)
+    except TypeError:
+        sd = (float(sd),)
+    if len(sd) != 3 or not all(v > 0.0 for v in sd):              # also refuses NaN
+        raise ValueError("--stddev takes three positive numbers (z y x), got {}".format(list(sd)))
+    return sd
 
 
 def label_map(classes):
@@ -200,26 +228,48 @@ def check_status(status, what):
     """Read the pick kernel's status word (one small device -> host copy: call it where the host synchronises anyway) and
     raise if a forced sample's rank lay beyond its slice's count -- per-slice counts that do not match the store.  Such a
     sample is centred on (0, 0), so without this check the bug would only show as a run that never sees its forced class."""
-    if int(status.item()) != 0:
-        raise RuntimeError("unetk_lits_pick_voxel: a forced sample's rank was beyond the forced-class count of its slice ({}); "
-                           "the per-slice counts do not match the resident store".format(what))
+    word = int(status.item())
+    if word != 0:
+        raise RuntimeError("liver_3d ({}): {}".format(what, "; ".join(msg for bit, msg in STATUS_BITS if word & bit) or
+                                                      "status word {}".format(word)))
 
 
-def batches(store, sampler, shape, lab_max, fg_label, status=None):
+def batches(store, sampler, shape, lab_max, fg_label, status=None, guide=None):
     """(features, labels) device batches for ever: features["images"] f32 [bs, D, H, W, 1], features["names"] the case ids,
     labels int32 [bs, D, H, W].  Per batch: one sampler draw, one pinned upload, then `unetk_lits_pick_voxel` (forced
     samples' centres, in the device table) and `unetk_lits_patch3d` on the current stream -- no host synchronisation.
-    status: int32 [1] device word that collects the pick kernel's out-of-range bit; it is NOT read here (that would
-    synchronise): the owner reads it with `check_status` at a point that synchronises anyway (input_fn: every evaluation)."""
+    status: int32 [1] device word that collects the kernels' bits (STATUS_BITS); it is NOT read here (that would
+    synchronise): the owner reads it with `check_status` at a point that synchronises anyway (input_fn: every evaluation).
+    guide: None, or dict(channels, stddev) for --use_spatial (stddev None: the Euclidean guide): the click draws are made
+    after the sampler's and ride in the same upload, `unetk_lits3d_clicks` and `unetk_click_guide3d` follow on the same
+    stream and features["sp_guide"] is f32 [bs, D, H, W, channels]."""
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=store.device)
     while True:
         b = sampler.draw()
-        (tab,) = lits.upload_pinned([sampler.table(b)], store.device)
+        if guide is None:
+            (tab,) = lits.upload_pinned([sampler.table(b)], store.device)
+        else:
+            from . import lits_inter
+            clicks = lits_inter.draw_click_tab(sampler.rng, sampler.bs, CLICKS[3])
+            tab, ctab = lits.upload_pinned([sampler.table(b), clicks.view(np.int32)], store.device)
         if sampler.force:
             ops.lits_pick_voxels(store.lb, tab, fg_label, status, lits.LB_SCALE)
         images, labels = ops.lits_patch3d(store.im, store.lb, tab, shape, sampler.training, lab_max, lits.IM_SCALE, lits.LB_SCALE)
-        yield {"images": images, "names": torch.from_numpy(b["pid"])}, labels
+        feats = {"images": images, "names": torch.from_numpy(b["pid"])}
+        if guide is not None:
+            pts, cnt = ops.lits3d_clicks(store.lb, tab, ctab, shape, status, fg_label, CLICKS, lits.LB_SCALE)
+            feats["sp_guide"] = ops.click_guide3d(tab, pts, cnt, shape, store.im.shape[1:], guide["channels"], guide["stddev"])
+        yield feats, labels
+
+
+def guide_config(args):
+    """None without --use_spatial, else what `batches` renders: dict(channels = --guide_channel, stddev = --stddev with
+    --local_enhance, None for the Euclidean guide)."""
+    if not getattr(args, "use_spatial", False):
+        return None
+    return dict(channels=int(getattr(args, "guide_channel", 2)),
+                stddev=guide_stddev(args) if getattr(args, "local_enhance", False) else None)
 
 
 def input_fn(mode, params):
@@ -260,7 +310,7 @@ def input_fn(mode, params):
     skey = ("lits3d_status", training)
     if skey not in params:
         params[skey] = torch.zeros(1, dtype=torch.int32, device=store.device)
-    gen = batches(store, sampler, shape, lab_max, fg_label, params[skey])
+    gen = batches(store, sampler, shape, lab_max, fg_label, params[skey], guide_config(args))
     if training:
         return gen
     n = int(getattr(args, "eval_num_batches_per_epoch", 100))

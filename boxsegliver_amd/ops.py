@@ -1785,6 +1785,79 @@ def click_guide(sample_tab, pts, cnt, out_hw, src_hw, guide_channel=2, stddev=No
     return guide
 
 
+def lits3d_clicks_desc(seg_slices, n, shape, obj_label=1, clicks=(3, 10, 40, 5), lab_scale=64, guide_channel=2, stddev=None,
+                       euclid_norm=1.0):
+    """The descriptor of unetk_lits3d_clicks and unetk_click_guide3d (include/unetk.h): shape = (D, H, W), clicks = (margin,
+    step, band, max_clicks) -- the reference's 3, 10, 40, 5 (input_pipeline_3d.py:492-503).  stddev None: the Euclidean
+    guide divided by euclid_norm; (s_z, s_y, s_x): the Gaussian of --local_enhance."""
+    d, h, w = (int(v) for v in shape)
+    margin, step, band, max_clicks = (int(v) for v in clicks)
+    sd = (0.0, 0.0, 0.0) if stddev is None else tuple(float(v) for v in stddev)
+    assert len(sd) == 3
+    return _abi.Lits3dClicksDesc(N=int(n), D=d, H=h, W=w, n_slices=seg_slices.shape[0], src_h=seg_slices.shape[1],
+                                 src_w=seg_slices.shape[2], lab_scale=int(lab_scale), obj_label=int(obj_label), margin=margin,
+                                 step=step, band=band, max_clicks=max_clicks, G=int(guide_channel),
+                                 gaussian=0 if stddev is None else 1, stddev=(ctypes.c_float * 3)(*sd),
+                                 euclid_norm=float(euclid_norm))
+
+
+def lits3d_clicks(seg_slices, sample_tab, click_tab, shape, status, obj_label=1, clicks=(3, 10, 40, 5), lab_scale=64):
+    """The simulated 3-D clicks of a batch (unetk_lits3d_clicks; include/unetk.h has the semantics) on the label patches
+    `lits_patch3d` cuts for sample_tab int32 [N, 16], shape = (D, H, W); click_tab uint32-valued int32 [N, 12] = the samples'
+    draws (data/lits_inter.draw_click_tab).  Returns pts int32 [N, 2, 4, 3] = (kind fg / bg, click, (z, y, x) in the crop; -1
+    padding) and cnt int32 [N, 2].  status collects bit 2 (value 4); it is NOT read here.  Current stream."""
+    _require_cuda(seg_slices, sample_tab, click_tab, status)
+    assert seg_slices.dtype == torch.uint8 and seg_slices.dim() == 3 and seg_slices.is_contiguous()
+    n = _inter_tab(sample_tab)
+    assert click_tab.dtype == torch.int32 and tuple(click_tab.shape) == (n, _abi.LITS_CLICK_TAB_COLS) and click_tab.is_contiguous()
+    assert status.dtype == torch.int32 and status.numel() >= 1
+    desc = lits3d_clicks_desc(seg_slices, n, shape, obj_label, clicks, lab_scale)
+    nbytes = int(_abi.lib().unetk_lits3d_clicks_ws_bytes(ctypes.byref(desc)))
+    if nbytes == 0:
+        raise _abi.UnetkError("lits3d_clicks: unsupported parameters {} or depth {} on {} x {} slices".format(
+            tuple(clicks), desc.D, seg_slices.shape[1], seg_slices.shape[2]))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=seg_slices.device)
+    pts = torch.empty((n, 2, _abi.LITS_MAX_CLICKS, 3), dtype=torch.int32, device=seg_slices.device)
+    cnt = torch.empty((n, 2), dtype=torch.int32, device=seg_slices.device)
+    with _timed_hbm("lits3d_clicks", ws, 1):
+        check(_abi.lib().unetk_lits3d_clicks(ctypes.byref(desc), ptr(seg_slices), ptr(sample_tab), ptr(click_tab), ptr(pts),
+                                             ptr(cnt), ptr(status), ptr(ws), nbytes, stream_ptr()), "lits3d_clicks")
+    return pts, cnt
+
+
+def click_guide3d(sample_tab, pts, cnt, shape, src_hw, guide_channel=2, stddev=None, euclid_norm=None):
+    """sp_guide f32 [N, D, H, W, guide_channel] from 3-D clicks (unetk_click_guide3d): pts int32 [N, 2, 4, 3], cnt int32 [N, 2],
+    in the crop boxes and under the three flips of sample_tab; shape = (D, H, W).  stddev None: the Euclidean distance to the
+    nearest click divided by euclid_norm (default: float32(H * sqrt(2) * 0.8), input_pipeline_3d.py:372); (s_z, s_y, s_x):
+    the Gaussian of --local_enhance.  guide_channel 2: (fg, bg); 1: fg - bg.  Current stream."""
+    _require_cuda(sample_tab, pts, cnt)
+    n = _inter_tab(sample_tab)
+    assert pts.dtype == torch.int32 and tuple(pts.shape) == (n, 2, _abi.LITS_MAX_CLICKS, 3) and pts.is_contiguous()
+    assert cnt.dtype == torch.int32 and tuple(cnt.shape) == (n, 2) and cnt.is_contiguous()
+    d, h, w = (int(v) for v in shape)
+    if euclid_norm is None:
+        euclid_norm = click_guide3d_norm(h)
+    # the guide reads the geometry and its own fields; the store's and the simulator's only have to be valid
+    desc = _abi.Lits3dClicksDesc(N=n, D=d, H=h, W=w, n_slices=1, src_h=int(src_hw[0]), src_w=int(src_hw[1]), lab_scale=1,
+                                 obj_label=1, margin=1, step=0, band=1, max_clicks=2, G=int(guide_channel),
+                                 gaussian=0 if stddev is None else 1,
+                                 stddev=(ctypes.c_float * 3)(*((0.0, 0.0, 0.0) if stddev is None else tuple(float(v) for v in stddev))),
+                                 euclid_norm=float(euclid_norm))
+    guide = torch.empty((n, d, h, w, int(guide_channel)), dtype=torch.float32, device=sample_tab.device)
+    with _timed_hbm("click_guide3d", guide, 1):
+        check(_abi.lib().unetk_click_guide3d(ctypes.byref(desc), ptr(sample_tab), ptr(pts), ptr(cnt), ptr(guide), stream_ptr()),
+              "click_guide3d")
+    return guide
+
+
+def click_guide3d_norm(im_height):
+    """The divisor of the Euclidean 3-D guide, float32(im_height * sqrt(2) * 0.8) (input_pipeline_3d.py:372: a python float
+    that TensorFlow converts to the guide's float32)."""
+    import math
+    import numpy as np
+    return float(np.float32(int(im_height) * math.sqrt(2) * 0.8))
+
+
 def adam_step(p, g, m, v, lr_t, beta1, beta2, eps, gscale=1.0, l2=0.0, decoupled_wd=0.0):
     with _timed_hbm("adam_step", p, 7):            # reads p, g, m, v; writes p, m, v
         check(_abi.lib().unetk_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr_t, beta1, beta2, eps, gscale, l2,

@@ -894,6 +894,65 @@ int unetk_lits_clicks(const unetk_lits_inter_desc* d, const uint8_t* seg_slices,
 int unetk_click_guide(const unetk_lits_inter_desc* d, const int32_t* sample_tab, const int32_t* pts, const int32_t* cnt,
                       float* guide, void* stream);
 
+/* ---------------------------------------------------------------- LiTS 3-D click guides  
+ * sp_guide for UNet3D: the clicks of the reference's 3-D pipeline (DataLoader/NF/input_pipeline_3d.py:258-324
+ * inter_simulation as :474-504 gen_kernel calls it) simulated on the label patch of unetk_lits_patch3d, and rendered as
+ * utils/image_ops.py:437-472 create_spatial_guide_3d renders them (:364-398 data_processing).  Additive to ABI 10.
+ *
+ * sample_tab is the LiTS 3-D table and the crop box is unetk_lits_patch3d's, z clamp included: the patch is [D, ch, cw], crop
+ * slices at or beyond the case's depth (or outside the store) are label 0.  The object is seg / lab_scale >= obj_label.
+ * click_tab is unetk_lits_clicks' table (UNETK_LITS_CLICK_TAB_COLS, same columns).  status int32 [1] (zeroed by the caller):
+ *   bit 2 (4): a click_tab row out of range (n_fg outside [1, max_clicks), n_bg outside [0, max_clicks), a strategy other
+ *              than 1 or 3) -- the value is clamped as unetk_lits_clicks clamps it (strategy: 1).
+ * Nothing is read out of bounds for any table content.
+ *
+ * unetk_lits3d_clicks: pts int32 [N][2][UNETK_LITS_MAX_CLICKS][3] = (kind: 0 foreground / 1 background, click, (z, y, x) relative
+ *   to the crop box; -1 padding), cnt int32 [N][2].  Three things differ from unetk_lits_clicks:
+ *   1. The erosion's element is the 3 x 3 square of ONE slice (struct[1] = True), so with dinf the chessboard distance inside
+ *      a slice -- nothing crosses slices:
+ *        foreground candidates {p in obj : dinf(p, non-object of p's slice or outside the crop's (y, x) box) > margin}
+ *        background candidates {p : margin < dinf(p, object of p's slice) <= margin + band}; a slice without an object has none
+ *   2. Candidates are ordered (z, y, x) over the whole patch: a rank pick is i = (r * count) >> 32 in that order, and under
+ *      strategy 3 a later click maximises the minimum squared 3-D distance dz^2 + dy^2 + dx^2 to the clicks so far, the
+ *      first in (z, y, x) order on ties.  After a click only ITS OWN slice loses the candidates with dy^2 + dx^2 <= step^2.
+ *      The kind stops when no candidate is left anywhere.
+ *   3. "Small" (no candidate at all): ONE click at the mean of the kind's mask, rounded half to even per axis in integers
+ *      (q = sum / n, r = sum % n: q if 2r < n, q + 1 if 2r > n, q + (q & 1) if 2r == n).
+ *   The rest is unetk_lits_clicks': the draws, the foreground by rank, no foreground click without an object in the patch, a
+ *   mask without a voxel gives no click (the deviation for an all-object patch).
+ *   margin, band >= 1, step >= 0, margin + band <= 254, 2 <= max_clicks <= UNETK_LITS_MAX_CLICKS + 1, src_h, src_w <= 1024,
+ *   D <= 256, D*src_h*src_w < 2^31, N <= 65535 (else UNETK_E_UNSUPPORTED and a zero ws query).  Integer arithmetic only, no
+ *   atomics on results: two calls give identical bits.  ws (16-byte aligned): per sample three byte fields of D*src_h*src_w
+ *   (rounded up to 16; column distances of both kinds, candidate classes), then int32 [N][D][src_h][8] row records
+ *   (foreground candidates, background candidates, object pixels, sum of the object pixels' x, first and last x of a
+ *   background candidate, two reserved).
+ *
+ * unetk_click_guide3d: guide f32 [N,D,H,W,G] from pts / cnt (plain device arrays: real clicks may be fed) -- same crop box and
+ *   the three flips of unetk_lits_patch3d, so guide and image line up.  create_spatial_guide_3d at crop resolution [D, ch, cw],
+ *   then resize_bilinear(align_corners) per slice, without the intermediate: every output voxel evaluates the guide at its 4
+ *   in-plane bilinear corners and lerps.
+ *   gaussian == 0: sqrt(min_k(dz^2 + dy^2 + dx^2)) / euclid_norm, euclid_norm > 0 formed by the caller (the reference divides by
+ *     float32(im_height * sqrt(2) * 0.8));
+ *   gaussian != 0: max_k exp(-(dz^2 / (2 sz^2) + dy^2 / (2 sy^2) + dx^2 / (2 sx^2))), summed z, y, x; stddev = {sz, sy, sx} > 0.
+ *   A kind without clicks is exactly 0; cnt is clamped into [0, UNETK_LITS_MAX_CLICKS].  G == 2: (fg, bg); G == 1: fg - bg.
+ *   D*H*W < 2^31 (else UNETK_E_UNSUPPORTED).  Reads D, H, W, src_h, src_w, G, gaussian, stddev, euclid_norm of the desc. */
+typedef struct unetk_lits3d_clicks_desc {
+  int32_t N, D, H, W;
+  int32_t n_slices, src_h, src_w; /* extent of the resident store */
+  int32_t lab_scale;              /* LB_SCALE = 64 */
+  int32_t obj_label;              /* object = seg / lab_scale >= obj_label: the sampler's forced class */
+  int32_t margin, step, band, max_clicks; /* the reference passes 3, 10, 40, 5 */
+  int32_t G, gaussian;            /* unetk_click_guide3d */
+  float stddev[3];                /* (z, y, x); --stddev, default 1 3 3 */
+  float euclid_norm;
+} unetk_lits3d_clicks_desc;
+size_t unetk_lits3d_clicks_ws_bytes(const unetk_lits3d_clicks_desc* d);
+int unetk_lits3d_clicks(const unetk_lits3d_clicks_desc* d, const uint8_t* seg_slices, const int32_t* sample_tab,
+                        const uint32_t* click_tab, int32_t* pts, int32_t* cnt, int32_t* status, void* ws, size_t ws_bytes,
+                        void* stream);
+int unetk_click_guide3d(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const int32_t* pts, const int32_t* cnt,
+                        float* guide, void* stream);
+
 /* ---------------------------------------------------------------- optimiser  core/solver.py:204-243
  * tf.train.AdamOptimizer on a flat parameter buffer.  g' = g*gscale + l2*p  (slim.l2_regularizer
  * gradient, base.py:128-135);  m += (1-b1)(g'-m);  v += (1-b2)(g'^2-v);
