@@ -81,6 +81,14 @@ class LitsInterDesc(Structure):
 
 LITS_MAX_CLICKS = 4         # UNETK_LITS_MAX_CLICKS
 LITS_CLICK_TAB_COLS = 12    # UNETK_LITS_CLICK_TAB_COLS
+INTER_MAX_CLICKS = 64       # UNETK_INTER_MAX_CLICKS
+INTER_ROW_COLS = 4          # UNETK_INTER_ROW_COLS
+INTER_TAB_COLS = 16         # UNETK_INTER_TAB_COLS
+
+
+class InterClickDesc(Structure):
+    _fields_ = [("N", c_int32), ("H", c_int32), ("W", c_int32), ("n_slices", c_int32), ("src_h", c_int32), ("src_w", c_int32),
+                ("lab_scale", c_int32), ("obj_label", c_int32), ("K", c_int32), ("vol_base", c_int32), ("vol_depth", c_int32)]
 
 
 
@@ -104,6 +112,9 @@ _SIGNATURES = {
     "unetk_lits_clicks_ws_bytes": (c_size_t, [POINTER(LitsInterDesc)]),
     "unetk_lits_clicks": (c_int, [POINTER(LitsInterDesc), P, P, P, P, P, P, P, c_size_t, P]),
     "unetk_click_guide": (c_int, [POINTER(LitsInterDesc), P, P, P, P, P]),
+    "unetk_click_guide_list": (c_int, [POINTER(LitsInterDesc), P, P, P, c_int, P, P]),
+    "unetk_inter_click_ws_bytes": (c_size_t, [POINTER(InterClickDesc)]),
+    "unetk_inter_click": (c_int, [POINTER(InterClickDesc), P, P, P, P, P, P, P, P, c_size_t, P]),
     "unetk_lits3d_clicks_ws_bytes": (c_size_t, [POINTER(Lits3dClicksDesc)]),
     "unetk_lits3d_clicks": (c_int, [POINTER(Lits3dClicksDesc), P, P, P, P, P, P, P, c_size_t, P]),
     "unetk_click_guide3d": (c_int, [POINTER(Lits3dClicksDesc), P, P, P, P, P]),

@@ -3,6 +3,7 @@
 // transform and the surface-distance sums.  Masks are dense C-order uint8 [D,H,W], non-zero = object; D*H*W < 2^31, so a
 // linear voxel index fits an int32.  Every reduction runs in a fixed order: results are bit-reproducible run to run.
 #include "common.h"
+#include "unionfind.h"   // ld_label, lc_find, lc_union: shared with inter_eval.hip
 
 namespace {
 
@@ -19,11 +20,6 @@ static inline int ev_dims(int D, int H, int W) {
 }
 static inline size_t ev_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// Labels only ever decrease and every value a voxel has held names a member of its own set, so a stale read (an older
-// parent, or a "root" that has since been linked) is still an ancestor: the union below stays correct and terminates, and
-// the reads may come from the CU's own cache (workgroup scope) instead of all hitting the one L2 line of a big root.
-__device__ __forceinline__ int ld_label(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
 // ---------------------------------------------------------------- largest 6-connected component (union-find)
 // label[i] = -1 (background) or a voxel index <= i of the same component; roots have label[i] == i.  A union links the
 // larger root under the smaller one with atomicMin (Playne & Hawick's lock-free union), so each tree's root is the minimum
@@ -37,32 +33,6 @@ __global__ __launch_bounds__(EV_BLOCK) void lc_init_kernel(const uint8_t* __rest
   if (i >= n) return;
   label[i] = mask[i] ? i : -1;
   cnt[i] = 0;
-}
-
-__device__ __forceinline__ int lc_find(const int* label, int p) {
-  int q = ld_label(label + p);
-  while (q != p) {
-    p = q;
-    q = ld_label(label + p);
-  }
-  return p;
-}
-
-__device__ __forceinline__ void lc_union(int* label, int a, int b) {
-  for (;;) {
-    a = lc_find(label, a);
-    b = lc_find(label, b);
-    if (a == b) return;
-    if (a < b) {
-      const int old = atomicMin(label + b, a);
-      if (old == b) return;
-      b = old;
-    } else {
-      const int old = atomicMin(label + a, b);
-      if (old == a) return;
-      a = old;
-    }
-  }
 }
 
 __global__ __launch_bounds__(EV_BLOCK) void lc_merge_kernel(const uint8_t* __restrict__ mask, int D, int H, int W,

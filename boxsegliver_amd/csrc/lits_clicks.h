@@ -79,4 +79,27 @@ __device__ __forceinline__ void clk_col_sweeps(const uint8_t* __restrict__ p, bo
   }
 }
 
+// ------------------------------------------------------------------------------------------------ row pass
+// One block, one row of cw pixels in LDS, NF fields side by side: d(x) = min_x' g(x') + |x - x'|, capped at `cap`, by
+// min-plus doubling (offsets 1, 2, 4, ... compose every |x - x'| below the cap exactly).  The caller has filled buf[0] and
+// synchronised; returns the half of buf that holds the result, synchronised.
+template <int NF>
+__device__ __forceinline__ int clk_row_minplus(int16_t (&buf)[2][NF][CLK_MAX_EXTENT], int cw, int cap) {
+  int cur = 0;
+  for (int o = 1; o < cap; o <<= 1) {
+    for (int x = threadIdx.x; x < cw; x += blockDim.x) {
+#pragma unroll
+      for (int k = 0; k < NF; ++k) {
+        int v = buf[cur][k][x];
+        if (x >= o) v = min(v, buf[cur][k][x - o] + o);
+        if (x + o < cw) v = min(v, buf[cur][k][x + o] + o);
+        buf[cur ^ 1][k][x] = (int16_t)min(v, cap);
+      }
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  return cur;
+}
+
 }  // namespace

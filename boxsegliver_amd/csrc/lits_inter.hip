@@ -9,6 +9,7 @@
 //   unetk_lits_clicks       inter_simulation on the label crop at source resolution: the reference runs it in a pool of host
 //                           processes; the labels live here, so it runs here
 //   unetk_click_guide       create_spatial_guide_2d + resize_bilinear from the clicks, evaluated at the bilinear corners
+//   unetk_click_guide_list  the same kernel on lists of K <= 64 clicks per kind (the interactive evaluator)
 //
 // The click simulator.  binary_erosion(mask, iterations=m) with the default cross is "city-block distance to the nearest 0
 // > m", so both candidate sets come from ONE capped distance transform per kind instead of 3 + 40 erosion sweeps:
@@ -22,7 +23,7 @@
 //                     click is not written back, a candidate is alive while it is farther than `step` from every click so far
 // Everything is integer arithmetic and every reduction has a fixed order (ballots inside a wave, waves by index).
 #include "common.h"
-#include "lits_clicks.h"     // MAXK, CTW, CLS_*, CLK_U, clk_draws, clk_col_sweeps: shared with lits3d_clicks.hip
+#include "lits_clicks.h"     // MAXK, CTW, CLS_*, CLK_U, clk_draws, clk_col_sweeps, clk_row_minplus: shared with the other simulators
 #include "lits_geom.h"
 #include "lits_patch.h"
 
@@ -238,20 +239,7 @@ __global__ __launch_bounds__(256) void clk_rows_kernel(unetk_lits_inter_desc d, 
     buf[0][1][x] = (int16_t)gb[x];
   }
   __syncthreads();
-  int cur = 0;
-  for (int o = 1; o < cap; o <<= 1) {
-    for (int x = threadIdx.x; x < cw; x += 256) {
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        int v = buf[cur][k][x];
-        if (x >= o) v = min(v, buf[cur][k][x - o] + o);
-        if (x + o < cw) v = min(v, buf[cur][k][x + o] + o);
-        buf[cur ^ 1][k][x] = (int16_t)min(v, cap);
-      }
-    }
-    __syncthreads();
-    cur ^= 1;
-  }
+  const int cur = clk_row_minplus<2>(buf, cw, cap);
   for (int x = threadIdx.x; x < cw; x += 256) {
     const int df = buf[cur][0][x], db = buf[cur][1][x];
     cls[x] = (uint8_t)((df > d.margin ? CLS_FG : 0) | ((db > d.margin && db <= d.margin + d.band) ? CLS_BG : 0) |
@@ -473,7 +461,7 @@ __device__ __forceinline__ float cg_at(int py, int px, const int32_t* __restrict
 }
 __global__ __launch_bounds__(256) void click_guide_kernel(unetk_lits_inter_desc d, const int32_t* __restrict__ tab,
                                                           const int32_t* __restrict__ pts, const int32_t* __restrict__ cnt,
-                                                          float* __restrict__ guide) {
+                                                          int K, float* __restrict__ guide) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int area = d.H * d.W;
   if (i >= (int64_t)d.N * area) return;
@@ -488,8 +476,8 @@ __global__ __launch_bounds__(256) void click_guide_kernel(unetk_lits_inter_desc 
   float g[2];
 #pragma unroll
   for (int kind = 0; kind < 2; ++kind) {
-    const int32_t* p = pts + ((int64_t)n * 2 + kind) * MAXK * 2;
-    const int k = min(max(cnt[(int64_t)n * 2 + kind], 0), MAXK);
+    const int32_t* p = pts + ((int64_t)n * 2 + kind) * K * 2;  // K clicks per list: MAXK, or the evaluator's --max_iter
+    const int k = min(max(cnt[(int64_t)n * 2 + kind], 0), K);
     const float tl = cg_at(y0, x0, p, k, gaussian, two_s2), tr = cg_at(y0, tx.i1, p, k, gaussian, two_s2);
     const float bl = cg_at(ty.i1, x0, p, k, gaussian, two_s2), br = cg_at(ty.i1, tx.i1, p, k, gaussian, two_s2);
     g[kind] = lits_bilerp(tl, tr, bl, br, tx.f, ty.f);
@@ -584,15 +572,27 @@ extern "C" int unetk_lits_clicks(const unetk_lits_inter_desc* d, const uint8_t* 
   return UNETK_OK;
 }
 
-extern "C" int unetk_click_guide(const unetk_lits_inter_desc* d, const int32_t* sample_tab, const int32_t* pts,
-                                 const int32_t* cnt, float* guide, void* stream) {
+static int click_guide_run(const unetk_lits_inter_desc* d, const int32_t* sample_tab, const int32_t* pts, const int32_t* cnt,
+                           int K, float* guide, void* stream) {
   UNETK_REQUIRE(ib_valid(d) && sample_tab && pts && cnt && guide && (d->G == 1 || d->G == 2));
   UNETK_REQUIRE(((((uintptr_t)sample_tab) | ((uintptr_t)pts) | ((uintptr_t)cnt) | ((uintptr_t)guide)) & 3u) == 0);
   UNETK_REQUIRE(d->gaussian == 0 || d->stddev > 0.f);
   const int64_t total = (int64_t)d->N * d->H * d->W;
   if ((int64_t)d->H * d->W >= ((int64_t)1 << 31) || (total + 255) / 256 >= ((int64_t)1 << 31)) return UNETK_E_UNSUPPORTED;
   UNETK_LAUNCH(click_guide_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *d, sample_tab, pts,
-               cnt, guide);
+               cnt, K, guide);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
+}
+
+extern "C" int unetk_click_guide(const unetk_lits_inter_desc* d, const int32_t* sample_tab, const int32_t* pts,
+                                 const int32_t* cnt, float* guide, void* stream) {
+  return click_guide_run(d, sample_tab, pts, cnt, MAXK, guide, stream);
+}
+
+// the same guide from lists of K clicks per kind (the interactive evaluator's): one kernel, one arithmetic
+extern "C" int unetk_click_guide_list(const unetk_lits_inter_desc* d, const int32_t* sample_tab, const int32_t* pts,
+                                      const int32_t* cnt, int K, float* guide, void* stream) {
+  UNETK_REQUIRE(K >= 1 && K <= UNETK_INTER_MAX_CLICKS);
+  return click_guide_run(d, sample_tab, pts, cnt, K, guide, stream);
 }

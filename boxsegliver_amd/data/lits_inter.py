@@ -20,7 +20,8 @@ The nets are binary, as on NF: `--classes Liver` makes the object stored label >
 `--classes Tumor` stored label >= 2; labels are {0, 1} and the sampler's forced class is the object.
 
 Not built: --geodesic (GeodisTK), --fp_sample / --sample_neg (false-positive caches of earlier runs), --downsampling,
---use_context, and offline evaluation (--mode eval / infer: the interactive evaluator of evaluators/evaluator_nf.py).
+--use_context, and --mode eval / infer of this sub-command (evaluators/evaluator_nf.py).  The click-guided nets are scored
+offline by entry/main_eval.py, the reference's own script for it.
 Deviations: a crop that is all object gives no background click (the reference fails converting NaN), and a crop without a
 non-zero voxel is all zeros (TensorFlow's moments of an empty tensor are NaN)."""
 import numpy as np
@@ -54,8 +55,8 @@ def object_label(classes):
     return OBJECT_LABEL[classes]
 
 
-def check_args(args):
-    """Refuses what is not built, naming the flag; returns the object label."""
+def refuse_unbuilt_flags(args):
+    """Refuses the flags of the `liver_inter` group that are not built, naming the flag (training and entry.main_eval)."""
     if getattr(args, "geodesic", False):
         raise NotImplementedError("--geodesic is not built: the geodesic guide needs GeodisTK, which is not available")
     if getattr(args, "fp_sample", False):
@@ -66,10 +67,10 @@ def check_args(args):
         raise NotImplementedError("--downsampling is not built: the resident store holds the slices at full resolution")
     if getattr(args, "use_context", False):
         raise NotImplementedError("--use_context is not built for `liver_inter` (the histogram context is `liver`'s, entry.main_g)")
-    mode = getattr(args, "mode", "train")
-    if mode != "train":
-        raise NotImplementedError("`liver_inter` serves --mode train with online evaluation, got --mode {}: the interactive "
-                                  "offline evaluator (evaluators/evaluator_nf.py) is not built yet".format(mode))
+
+
+def check_values(args):
+    """The value checks of the group; returns the object label."""
     c = int(getattr(args, "im_channel", 3))
     if c < 1 or c % 2 == 0 or c > MAX_CHANNELS:
         raise ValueError("--im_channel must be odd and at most {} (the slices cz - C/2 .. cz + C/2), got {}".format(MAX_CHANNELS, c))
@@ -80,6 +81,16 @@ def check_args(args):
     if float(getattr(args, "noise_scale", 0.)) < 0:
         raise ValueError("--noise_scale must be >= 0, got {}".format(args.noise_scale))
     return object_label(args.classes)
+
+
+def check_args(args):
+    """Refuses what is not built, naming the flag; returns the object label."""
+    refuse_unbuilt_flags(args)
+    mode = getattr(args, "mode", "train")
+    if mode != "train":
+        raise NotImplementedError("`liver_inter` serves --mode train with online evaluation, got --mode {}: the interactive "
+                                  "offline evaluator (evaluators/evaluator_nf.py) is not built yet".format(mode))
+    return check_values(args)
 
 
 def draw_click_tab(rng, bs, max_clicks=CLICKS[3]):

@@ -1785,6 +1785,74 @@ def click_guide(sample_tab, pts, cnt, out_hw, src_hw, guide_channel=2, stddev=No
     return guide
 
 
+def click_guide_list(sample_tab, pts, cnt, out_hw, src_hw, guide_channel=2, stddev=None):
+    """click_guide from lists of K clicks per kind (unetk_click_guide_list): pts int32 [N, 2, K, 2] with K <= 64, cnt int32
+    [N, 2].  The same kernel: bit-equal to click_guide where every count is <= 4.  Current stream."""
+    _require_cuda(sample_tab, pts, cnt)
+    n = _inter_tab(sample_tab)
+    assert pts.dtype == torch.int32 and pts.dim() == 4 and pts.shape[0] == n and pts.shape[1] == 2 and pts.shape[3] == 2
+    assert pts.is_contiguous() and cnt.dtype == torch.int32 and tuple(cnt.shape) == (n, 2) and cnt.is_contiguous()
+    k = int(pts.shape[2])
+    h, w = int(out_hw[0]), int(out_hw[1])
+    desc = _abi.LitsInterDesc(N=n, H=h, W=w, C=1, n_slices=1, src_h=int(src_hw[0]), src_w=int(src_hw[1]), im_scale=1, lab_scale=1,
+                              obj_label=1, training=0, seed=0, noise_scale=0.0, margin=1, step=0, band=1, max_clicks=2,
+                              G=int(guide_channel), gaussian=0 if stddev is None else 1,
+                              stddev=0.0 if stddev is None else float(stddev))
+    guide = torch.empty((n, h, w, int(guide_channel)), dtype=torch.float32, device=sample_tab.device)
+    with _timed_hbm("click_guide_list", guide, 1):
+        check(_abi.lib().unetk_click_guide_list(ctypes.byref(desc), ptr(sample_tab), ptr(pts), ptr(cnt), k, ptr(guide),
+                                                stream_ptr()), "click_guide_list")
+    return guide
+
+
+def inter_click_desc(seg_slices, n, pred_hw, k, obj_label=1, lab_scale=64, vol_base=0, vol_depth=0):
+    """The descriptor of unetk_inter_click (include/unetk.h)."""
+    return _abi.InterClickDesc(N=int(n), H=int(pred_hw[0]), W=int(pred_hw[1]), n_slices=seg_slices.shape[0],
+                               src_h=seg_slices.shape[1], src_w=seg_slices.shape[2], lab_scale=int(lab_scale),
+                               obj_label=int(obj_label), K=int(k), vol_base=int(vol_base), vol_depth=int(vol_depth))
+
+
+def inter_click_ws(desc, device):
+    """A workspace of exactly the size unetk_inter_click asks for; raises where the query says unsupported."""
+    nbytes = int(_abi.lib().unetk_inter_click_ws_bytes(ctypes.byref(desc)))
+    if nbytes == 0:
+        raise _abi.UnetkError("inter_click: unsupported ({} sessions, {} x {} slices, predictions {} x {}, K = {})".format(
+            desc.N, desc.src_h, desc.src_w, desc.H, desc.W, desc.K))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def inter_click(seg_slices, rows, pred, pts, cnt, obj_label=1, lab_scale=64, vol=None, vol_base=0, pred_hw=None, table=None,
+                ws=None):
+    """One corrective click for every active session (unetk_inter_click; include/unetk.h has the semantics): rows int32 [N, 4]
+    = (store slice, active, previous click y, x), pred uint8 [N, H, W] or None (all zeros; pred_hw then gives H, W), pts int32
+    [N, 2, K, 2] / cnt int32 [N, 2] the click lists (appended to in place), vol uint8 [depth, src_h, src_w] or None the case's
+    prediction volume starting at store slice vol_base.  Returns the int32 [N, 16] table.  Nothing is read back here.
+    Current stream."""
+    _require_cuda(seg_slices, rows, pts, cnt)
+    assert seg_slices.dtype == torch.uint8 and seg_slices.dim() == 3 and seg_slices.is_contiguous()
+    n = rows.shape[0]
+    assert rows.dtype == torch.int32 and tuple(rows.shape) == (n, _abi.INTER_ROW_COLS) and rows.is_contiguous()
+    assert pts.dtype == torch.int32 and pts.dim() == 4 and pts.shape[0] == n and pts.shape[1] == 2 and pts.shape[3] == 2
+    assert pts.is_contiguous() and cnt.dtype == torch.int32 and tuple(cnt.shape) == (n, 2) and cnt.is_contiguous()
+    if pred is not None:
+        assert pred.is_cuda and pred.dtype == torch.uint8 and pred.dim() == 3 and pred.shape[0] == n and pred.is_contiguous()
+        pred_hw = pred.shape[1:]
+    depth = 0
+    if vol is not None:
+        assert vol.is_cuda and vol.dtype == torch.uint8 and vol.is_contiguous() and tuple(vol.shape[1:]) == tuple(seg_slices.shape[1:])
+        depth = vol.shape[0]
+    desc = inter_click_desc(seg_slices, n, pred_hw, pts.shape[2], obj_label, lab_scale, vol_base, depth)
+    if ws is None:
+        ws = inter_click_ws(desc, seg_slices.device)
+    if table is None:
+        table = torch.empty((n, _abi.INTER_TAB_COLS), dtype=torch.int32, device=seg_slices.device)
+    assert table.dtype == torch.int32 and tuple(table.shape) == (n, _abi.INTER_TAB_COLS) and table.is_contiguous()
+    with _timed_hbm("inter_click", ws, 1):
+        check(_abi.lib().unetk_inter_click(ctypes.byref(desc), ptr(seg_slices), ptr(rows), ptr(pred), ptr(vol), ptr(pts), ptr(cnt),
+                                           ptr(table), ptr(ws), ws.numel(), stream_ptr()), "inter_click")
+    return table
+
+
 def lits3d_clicks_desc(seg_slices, n, shape, obj_label=1, clicks=(3, 10, 40, 5), lab_scale=64, guide_channel=2, stddev=None,
                        euclid_norm=1.0):
     """The descriptor of unetk_lits3d_clicks and unetk_click_guide3d (include/unetk.h): shape = (D, H, W), clicks = (margin,

@@ -894,6 +894,50 @@ int unetk_lits_clicks(const unetk_lits_inter_desc* d, const uint8_t* seg_slices,
 int unetk_click_guide(const unetk_lits_inter_desc* d, const int32_t* sample_tab, const int32_t* pts, const int32_t* cnt,
                       float* guide, void* stream);
 
+/* ---------------------------------------------------------------- interactive evaluation: corrective clicks  
+ * The click step of the reference's entry/main_eval.py (:149-183 inter_simulation_test) for N sessions at once, and the
+ * guide from their click lists.  Additive to ABI 10.
+ *
+ * unetk_click_guide_list: unetk_click_guide from lists of K clicks per kind, pts int32 [N][2][K][2], cnt clamped into
+ *   [0, K], 1 <= K <= UNETK_INTER_MAX_CLICKS.  Same kernel and arithmetic: with every count <= UNETK_LITS_MAX_CLICKS the
+ *   output equals unetk_click_guide's bit for bit.
+ *
+ * unetk_inter_click: rows int32 [N][UNETK_INTER_ROW_COLS] = (slice index in the store, active != 0, previous click y, x; -1 =
+ *   none).  pred uint8 [N][H][W] (non-zero = object) or NULL = all zeros.  vol uint8 [vol_depth][src_h][src_w] or NULL: the
+ *   case's prediction volume, whose first slice is store slice vol_base.  pts int32 [N][2][K][2], cnt int32 [N][2]: the
+ *   sessions' click lists (kind 0 foreground / 1 background), read and appended to.  Per active row:
+ *     pred at source resolution, nearest: pixel (y, x) reads pred[y * H / src_h][x * W / src_w] (integer floor); it is written
+ *       to slice (slice - vol_base) of vol;  ref = stored label >= obj_label * lab_scale;  err = pred xor ref;
+ *     the 4-connected components of err; the largest one, the smallest root (= minimum linear index y * src_w + x) on ties;
+ *     candidate = the component's mean per axis, rounded half to even (exact integers);
+ *     click = the candidate where err is set there (err, not the component); otherwise (fallback) the component's pixel with
+ *       the greatest city-block distance to the nearest non-error pixel, the slice's border counting as non-error, the
+ *       distance capped at 255; ties: the smaller squared Euclidean distance to the candidate, then the smaller linear index;
+ *     kind = ref set at the click ? 0 : 1;  repeat = the click equals the row's previous click;
+ *     the click is appended to the kind's list unless the list holds K clicks already.
+ *   An empty err gives no click (empty flag).  table int32 [N][UNETK_INTER_TAB_COLS]:
+ *     0 n_pred  1 n_ref  2 n_inter (at source resolution)   3 components  4 area  5 root   6, 7 candidate (y, x)
+ *     8, 9 click (y, x)  10 kind (-1 without a click)  11 fallback  12 repeat  13 empty  14 appended
+ *     15 row state: 1 = ran, 0 = inactive, 2 = slice outside the store or the volume.  Rows in state 0 or 2 read and write
+ *     nothing but their (otherwise zero) table row.
+ *   src_h, src_w <= 1024, K <= UNETK_INTER_MAX_CLICKS, H * W < 2^21 (else UNETK_E_UNSUPPORTED and a zero ws query); N <= 65535;
+ *   ws 16-byte aligned.  Integer arithmetic only; sums and maxima are integer atomics: two calls give identical bits. */
+#define UNETK_INTER_MAX_CLICKS 64
+#define UNETK_INTER_ROW_COLS 4
+#define UNETK_INTER_TAB_COLS 16
+typedef struct unetk_inter_click_desc {
+  int32_t N, H, W;                /* sessions; extent of pred */
+  int32_t n_slices, src_h, src_w; /* extent of the resident store */
+  int32_t lab_scale, obj_label;   /* object = seg / lab_scale >= obj_label */
+  int32_t K;                      /* clicks a list holds */
+  int32_t vol_base, vol_depth;    /* vol[z] is store slice vol_base + z */
+} unetk_inter_click_desc;
+int unetk_click_guide_list(const unetk_lits_inter_desc* d, const int32_t* sample_tab, const int32_t* pts, const int32_t* cnt,
+                           int K, float* guide, void* stream);
+size_t unetk_inter_click_ws_bytes(const unetk_inter_click_desc* d);
+int unetk_inter_click(const unetk_inter_click_desc* d, const uint8_t* seg_slices, const int32_t* rows, const uint8_t* pred,
+                      uint8_t* vol, int32_t* pts, int32_t* cnt, int32_t* table, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- LiTS 3-D click guides  
  * sp_guide for UNet3D: the clicks of the reference's 3-D pipeline (DataLoader/NF/input_pipeline_3d.py:258-324
  * inter_simulation as :474-504 gen_kernel calls it) simulated on the label patch of unetk_lits_patch3d, and rendered as
