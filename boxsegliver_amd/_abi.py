@@ -99,6 +99,14 @@ class Lits3dClicksDesc(Structure):
                 ("euclid_norm", c_float)]
 
 
+INTER3D_TAB_COLS = 20       # UNETK_INTER3D_TAB_COLS
+
+
+class InterClick3dDesc(Structure):
+    _fields_ = [("case_base", c_int32), ("depth", c_int32), ("n_slices", c_int32), ("src_h", c_int32), ("src_w", c_int32),
+                ("lab_scale", c_int32), ("obj_label", c_int32), ("K", c_int32), ("dist_cap", c_int32)]
+
+
 P = c_void_p
 _SIGNATURES = {
     "unetk_lits_pick_voxel": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P]),
@@ -118,6 +126,9 @@ _SIGNATURES = {
     "unetk_lits3d_clicks_ws_bytes": (c_size_t, [POINTER(Lits3dClicksDesc)]),
     "unetk_lits3d_clicks": (c_int, [POINTER(Lits3dClicksDesc), P, P, P, P, P, P, P, c_size_t, P]),
     "unetk_click_guide3d": (c_int, [POINTER(Lits3dClicksDesc), P, P, P, P, P]),
+    "unetk_click_guide3d_list": (c_int, [POINTER(Lits3dClicksDesc), P, P, P, c_int, P, P]),
+    "unetk_inter_click3d_ws_bytes": (c_size_t, [POINTER(InterClick3dDesc)]),
+    "unetk_inter_click3d": (c_int, [POINTER(InterClick3dDesc), P, P, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
     "unetk_lits_batch": (c_int, [POINTER(LitsDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "unetk_lits_spatial_guide": (c_int, [POINTER(LitsGuideDesc), P, P, P, P, P]),
     "unetk_lits_context": (c_int, [P, c_int64, c_int, P, c_int, c_int, P, P, P, P]),

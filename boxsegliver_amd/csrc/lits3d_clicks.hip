@@ -444,11 +444,15 @@ struct Guide3 {
 // create_spatial_guide_3d at one crop voxel: min_k sqrt(dz^2 + dy^2 + dx^2) = sqrt(min_k ...) (the squares are exact
 // integers), divided as data_processing :372 divides it; or max_k exp(-(dz^2 / (2 sz^2) + dy^2 / (2 sy^2) + dx^2 / (2 sx^2))),
 // summed z, y, x as image_ops.py:471 sums them
-__device__ __forceinline__ float cg3_at(int pz, int py, int px, const int32_t* __restrict__ p, int n, const Guide3& g) {
+// (oz, oy, ox): what is subtracted from the clicks, in integers, before they are used -- the crop box's origin for clicks in
+// case coordinates (click_guide3d_kernel<true>), 0 for clicks relative to the box
+__device__ __forceinline__ float cg3_at(int pz, int py, int px, const int32_t* __restrict__ p, int n, const Guide3& g, int oz = 0,
+                                        int oy = 0, int ox = 0) {
   if (n == 0) return 0.f;
   float best = g.gaussian ? 0.f : INFINITY;
   for (int k = 0; k < n; ++k) {
-    const float dz = (float)pz - (float)p[3 * k], dy = (float)py - (float)p[3 * k + 1], dx = (float)px - (float)p[3 * k + 2];
+    const float dz = (float)pz - (float)(p[3 * k] - oz), dy = (float)py - (float)(p[3 * k + 1] - oy),
+                dx = (float)px - (float)(p[3 * k + 2] - ox);
     if (g.gaussian)
       best = fmaxf(best, expf(-(dz * dz / g.nz + dy * dy / g.ny + dx * dx / g.nx)));
     else
@@ -456,9 +460,12 @@ __device__ __forceinline__ float cg3_at(int pz, int py, int px, const int32_t* _
   }
   return g.gaussian ? best : sqrtf(best) / g.norm;
 }
+// LIST: ONE pair of click lists for all rows, pts [2][K][3] in case coordinates (z from the case's first slice, y and x in the
+// slice) and cnt [2] (unetk_click_guide3d_list); else pts [N][2][MAXK][3] relative to each row's box and cnt [N][2]
+template <bool LIST>
 __global__ __launch_bounds__(256) void click_guide3d_kernel(unetk_lits3d_clicks_desc d, const int32_t* __restrict__ tab,
                                                             const int32_t* __restrict__ pts, const int32_t* __restrict__ cnt,
-                                                            float* __restrict__ guide) {
+                                                            int K, float* __restrict__ guide) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int area = d.H * d.W, vol = d.D * area;              // < 2^31: checked by the entry point
   if (i >= (int64_t)d.N * vol) return;
@@ -478,10 +485,11 @@ __global__ __launch_bounds__(256) void click_guide3d_kernel(unetk_lits3d_clicks_
   float v[2];
 #pragma unroll
   for (int kind = 0; kind < 2; ++kind) {
-    const int32_t* p = pts + ((int64_t)n * 2 + kind) * MAXK * 3;
-    const int k = min(max(cnt[(int64_t)n * 2 + kind], 0), MAXK);
-    const float tl = cg3_at(z, y0, x0, p, k, g), tr = cg3_at(z, y0, tx.i1, p, k, g);
-    const float bl = cg3_at(z, ty.i1, x0, p, k, g), br = cg3_at(z, ty.i1, tx.i1, p, k, g);
+    const int32_t* p = LIST ? pts + (int64_t)kind * K * 3 : pts + ((int64_t)n * 2 + kind) * MAXK * 3;
+    const int k = min(max(cnt[LIST ? kind : (int64_t)n * 2 + kind], 0), LIST ? K : MAXK);
+    const int oz = LIST ? b.z1 : 0, oy = LIST ? b.y1 : 0, ox = LIST ? b.x1 : 0;
+    const float tl = cg3_at(z, y0, x0, p, k, g, oz, oy, ox), tr = cg3_at(z, y0, tx.i1, p, k, g, oz, oy, ox);
+    const float bl = cg3_at(z, ty.i1, x0, p, k, g, oz, oy, ox), br = cg3_at(z, ty.i1, tx.i1, p, k, g, oz, oy, ox);
     v[kind] = lits_bilerp(tl, tr, bl, br, tx.f, ty.f);
   }
   const int zo = t[9] != 0 ? d.D - 1 - z : z, yo = t[8] != 0 ? d.H - 1 - y : y, xo = t[7] != 0 ? d.W - 1 - x : x;
@@ -531,16 +539,33 @@ extern "C" int unetk_lits3d_clicks(const unetk_lits3d_clicks_desc* d, const uint
   return UNETK_OK;
 }
 
-extern "C" int unetk_click_guide3d(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const int32_t* pts,
-                                   const int32_t* cnt, float* guide, void* stream) {
+namespace {
+// K == 0: unetk_click_guide3d (clicks per row, relative to its box); else unetk_click_guide3d_list
+int click_guide3d_launch(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const int32_t* pts, const int32_t* cnt,
+                         int K, float* guide, void* stream) {
   UNETK_REQUIRE(d && d->N > 0 && d->D > 0 && d->H > 0 && d->W > 0 && d->src_h > 0 && d->src_w > 0 && sample_tab && pts && cnt &&
                 guide && (d->G == 1 || d->G == 2));
   UNETK_REQUIRE(((((uintptr_t)sample_tab) | ((uintptr_t)pts) | ((uintptr_t)cnt) | ((uintptr_t)guide)) & 3u) == 0);
   UNETK_REQUIRE(d->gaussian != 0 ? (d->stddev[0] > 0.f && d->stddev[1] > 0.f && d->stddev[2] > 0.f) : d->euclid_norm > 0.f);
   const int64_t total = (int64_t)d->N * d->D * d->H * d->W;
   if ((int64_t)d->D * d->H * d->W >= ((int64_t)1 << 31) || (total + 255) / 256 >= ((int64_t)1 << 31)) return UNETK_E_UNSUPPORTED;
-  UNETK_LAUNCH(click_guide3d_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *d, sample_tab, pts,
-               cnt, guide);
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (K > 0)
+    UNETK_LAUNCH(click_guide3d_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, *d, sample_tab, pts, cnt, K, guide);
+  else
+    UNETK_LAUNCH(click_guide3d_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, *d, sample_tab, pts, cnt, 0, guide);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
+}
+}  // namespace
+
+extern "C" int unetk_click_guide3d(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const int32_t* pts,
+                                   const int32_t* cnt, float* guide, void* stream) {
+  return click_guide3d_launch(d, sample_tab, pts, cnt, 0, guide, stream);
+}
+
+extern "C" int unetk_click_guide3d_list(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const int32_t* pts,
+                                        const int32_t* cnt, int K, float* guide, void* stream) {
+  UNETK_REQUIRE(K >= 1 && K <= UNETK_INTER_MAX_CLICKS);
+  return click_guide3d_launch(d, sample_tab, pts, cnt, K, guide, stream);
 }

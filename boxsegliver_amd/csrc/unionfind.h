@@ -1,5 +1,6 @@
 // The lock-free union-find that the component kernels share (evalvol.hip: 6- and 18-connected volumes; inter_eval.hip:
-// 4-connected error regions of a slice).  One copy, so the labellings cannot drift.
+// 4-connected error regions of a slice; inter_eval3d.hip: 6-connected error regions of a case).  One copy, so the labellings
+// cannot drift.
 #pragma once
 #include "common.h"
 

@@ -73,6 +73,15 @@ def add_arguments(parser):
 
 
 def check_args(args):
+    check_values(args)
+    if getattr(args, "use_spatial", False) and getattr(args, "mode", "train") == "eval":
+        raise NotImplementedError("--mode eval with --use_spatial is not built: the sliding-window evaluator has no clicks -- real "
+                                  "or simulated clicks per case are the interactive evaluator's job, entry/main_eval_3d.py")
+    return label_map(args.classes)
+
+
+def check_values(args):
+    """The value checks of the flag group, shared with the interactive evaluator (entry/main_eval_3d.py)."""
     if int(getattr(args, "im_channel", 1)) != 1:
         raise ValueError("the LiTS 3-D patches have one channel, got --im_channel {}".format(args.im_channel))
     overlap = float(getattr(args, "eval_overlap", 0.5))
@@ -94,9 +103,6 @@ def check_args(args):
     guide_stddev(args)
     if int(getattr(args, "guide_channel", 2)) not in (1, 2):
         raise ValueError("--guide_channel must be 1 or 2, got {}".format(args.guide_channel))
-    if getattr(args, "use_spatial", False) and getattr(args, "mode", "train") == "eval":
-        raise NotImplementedError("--mode eval with --use_spatial is not built: the sliding-window evaluator has no clicks")
-    return label_map(args.classes)
 
 
 def guide_stddev(args):

@@ -121,6 +121,65 @@ def mirror_plan(config):
 _FLIPS = {0: (False, False), 1: (False, True), 2: (True, False), 3: (True, True)}   # mirror id -> (flip H, flip W)
 
 
+class CaseWindows3D(object):
+    """The body of the sliding-window evaluation of ONE case by UNet3D, shared by EvaluateVolume.run_3d and the interactive
+    evaluator (entry/main_eval_3d.py): per table `add` -- one pinned upload, the windows cut by `unetk_lits_patch3d` as
+    `eval_online` cuts them, one forward, `unetk_eval3d_accumulate[_w]` into the case's accumulator at source resolution --
+    and at the end of the case `finish`, the class volume.  forward(features) -> probabilities [n, D, H, W, C].  The only
+    option is `sp_guide`: a function of the device table that returns the guide feature of its rows."""
+
+    def __init__(self, forward, cfg):
+        from ..data import lits3d
+        self.forward = forward
+        self.shape = (int(cfg.im_depth), int(cfg.im_height), int(cfg.im_width))
+        self.lab_max = len(tuple(cfg.classes))
+        self.gaussian = getattr(cfg, "eval_window_weight", "uniform") == "gaussian"
+        self.boxed = getattr(cfg, "eval_box_from", None) is not None
+        self.host_tables = lits3d.window_weights(self.shape, getattr(cfg, "eval_window_sigma", 0.125)) if self.gaussian else None
+        self.acc = self.cnt = self.tables = None
+
+    def add(self, store, tab, sp_guide=None, before_forward=None):
+        from ..data import lits, lits3d
+        shape = self.shape
+        (dtab,) = lits.upload_pinned([tab], store.device)
+        images, _ = ops.lits_patch3d(store.im, store.lb, dtab, shape, False, self.lab_max, lits.IM_SCALE, lits.LB_SCALE)
+        features = {"images": images}
+        if sp_guide is not None:
+            features["sp_guide"] = sp_guide(dtab)
+        if before_forward is not None:
+            before_forward(features)
+        prob = self.forward(features).contiguous()                      # [n, D, H, W, C]
+        base, depth = int(tab[0, lits3d.COL_BASE]), int(tab[0, lits3d.COL_DEPTH])
+        src_hw = tuple(store.im.shape[1:])
+        if self.acc is None:
+            self.acc = torch.zeros((depth,) + src_hw + (prob.shape[-1],), dtype=torch.float32, device=store.device)
+            self.cnt = torch.zeros((depth,) + src_hw, dtype=torch.float32 if self.gaussian else torch.int32, device=store.device)
+        box = lits3d.table_box(tab, shape, depth, src_hw)
+        if self.gaussian:
+            if self.tables is None:                                     # once per run
+                self.tables = lits.upload_pinned(list(self.host_tables), store.device)
+            ops.eval3d_accumulate_w(prob, dtab, shape, base, depth, box, self.tables, self.acc, self.cnt, store.im, host_tab=tab)
+        else:
+            ops.eval3d_accumulate(prob, dtab, shape, base, depth, box, self.acc, self.cnt, store.im, host_tab=tab)
+
+    def labels(self, store, base, depth):
+        from ..data import lits
+        lb = store.lb[base:base + depth]
+        return torch.clamp(torch.div(lb, lits.LB_SCALE, rounding_mode="floor"), max=self.lab_max).to(torch.uint8)
+
+    def finish(self, box=None):
+        """(class volume uint8 [depth, src_h, src_w], coverage): the coverage volume of the plain path, or the word [1] that
+        `unetk_eval3d_finish` counted the box's voxels without cover into.  The case's accumulator is dropped."""
+        acc, cnt = self.acc, self.cnt
+        self.acc = self.cnt = None
+        if self.gaussian or self.boxed:
+            uncovered = torch.zeros(1, dtype=torch.int32, device=acc.device)
+            whole = (0, acc.shape[0], 0, acc.shape[1], 0, acc.shape[2])
+            return ops.eval3d_finish(acc, cnt, box if box is not None else whole, uncovered), uncovered
+        amax, _ = ops.head_predict(acc.view(-1, acc.shape[-1]), acc.shape[-1], want_preds=False)
+        return amax.view(cnt.shape), cnt
+
+
 class EvaluateVolume(EvaluateBase):
     """Evaluate a model case by case (volume by volume).
 
@@ -488,60 +547,34 @@ class EvaluateVolume(EvaluateBase):
         (the end-of-case item carries it) and everything outside it is class 0.  With either flag `unetk_eval3d_finish` is
         the argmax inside the box (the whole case without --eval_box_from) and counts the box's voxels without cover; the
         count is read where the plain path reads cnt.min()."""
-        from ..data import lits, lits3d
         cfg = self.config
         model = self._model()
         if checkpoint_path and not tf_checkpoint.checkpoint_exists(checkpoint_path):
             raise FileNotFoundError("Missing checkpoint file {} (status_file None)".format(checkpoint_path))
         mode = getattr(cfg, "mode", ModeKeys.EVAL)
-        shape = (int(cfg.im_depth), int(cfg.im_height), int(cfg.im_width))
-        lab_max, _ = lits3d.label_map(cfg.classes)
         params = self.params
-        gaussian = getattr(cfg, "eval_window_weight", "uniform") == "gaussian"
-        boxed = getattr(cfg, "eval_box_from", None) is not None
-        host_tables = lits3d.window_weights(shape, getattr(cfg, "eval_window_sigma", 0.125)) if gaussian else None
+        from ..data import lits3d
+        lits3d.label_map(cfg.classes)                                   # refuses other --classes than the LiTS label maps
+        windows = CaseWindows3D(lambda features: self._forward(model, features), cfg)
+        restored = [False]
+
+        def restore_once(features):
+            if not restored[0]:
+                restored[0] = True
+                if model.params is None:
+                    self._forward(model, features)                      # creates the variables
+                if checkpoint_path and self.estimator is not None:
+                    self.estimator._restore(checkpoint_path, model, None)
 
         def run_pred():
-            restored = False
-            acc = cnt = tables = None
             for tab, end in input_fn(mode, params):
                 store = params[("lits_store", False)][0]            # input_fn_eval made it resident before its first item
                 if tab is not None:
-                    (dtab,) = lits.upload_pinned([tab], store.device)
-                    images, _ = ops.lits_patch3d(store.im, store.lb, dtab, shape, False, lab_max, lits.IM_SCALE, lits.LB_SCALE)
-                    features = {"images": images}
-                    if not restored:
-                        restored = True
-                        if model.params is None:
-                            self._forward(model, features)              # creates the variables
-                        if checkpoint_path and self.estimator is not None:
-                            self.estimator._restore(checkpoint_path, model, None)
-                    prob = self._forward(model, features).contiguous()  # [n, D, H, W, C]
-                    base, depth = int(tab[0, lits3d.COL_BASE]), int(tab[0, lits3d.COL_DEPTH])
-                    src_hw = tuple(store.im.shape[1:])
-                    if acc is None:
-                        acc = torch.zeros((depth,) + src_hw + (prob.shape[-1],), dtype=torch.float32, device=store.device)
-                        cnt = torch.zeros((depth,) + src_hw, dtype=torch.float32 if gaussian else torch.int32, device=store.device)
-                    box = lits3d.table_box(tab, shape, depth, src_hw)
-                    if gaussian:
-                        if tables is None:                              # once per run
-                            tables = lits.upload_pinned(list(host_tables), store.device)
-                        ops.eval3d_accumulate_w(prob, dtab, shape, base, depth, box, tables, acc, cnt, store.im, host_tab=tab)
-                    else:
-                        ops.eval3d_accumulate(prob, dtab, shape, base, depth, box, acc, cnt, store.im, host_tab=tab)
+                    windows.add(store, tab, before_forward=restore_once)
                 else:
-                    if acc is None or end["depth"] != acc.shape[0]:
+                    if windows.acc is None or end["depth"] != windows.acc.shape[0]:
                         raise RuntimeError("case {} ended without windows of its own".format(end["case"]))
-                    lb = end["store"].lb[end["base"]:end["base"] + end["depth"]]
-                    labels = torch.clamp(torch.div(lb, lits.LB_SCALE, rounding_mode="floor"), max=lab_max).to(torch.uint8)
-                    if gaussian or boxed:
-                        uncovered = torch.zeros(1, dtype=torch.int32, device=acc.device)
-                        whole = (0, acc.shape[0], 0, acc.shape[1], 0, acc.shape[2])
-                        yield end["case"], labels, ops.eval3d_finish(acc, cnt, end.get("box", whole), uncovered), uncovered
-                    else:
-                        amax, _ = ops.head_predict(acc.view(-1, acc.shape[-1]), acc.shape[-1], want_preds=False)
-                        yield end["case"], labels, amax.view(cnt.shape), cnt
-                    acc = cnt = None
+                    yield (end["case"], windows.labels(end["store"], end["base"], end["depth"])) + windows.finish(end.get("box"))
 
         n_cases = cases if cases is not None else getattr(cfg, "eval_num", -1)
         return self._run_actual(self._predict_case_3d, run_pred, save, cases=n_cases)

@@ -1893,15 +1893,8 @@ def lits3d_clicks(seg_slices, sample_tab, click_tab, shape, status, obj_label=1,
     return pts, cnt
 
 
-def click_guide3d(sample_tab, pts, cnt, shape, src_hw, guide_channel=2, stddev=None, euclid_norm=None):
-    """sp_guide f32 [N, D, H, W, guide_channel] from 3-D clicks (unetk_click_guide3d): pts int32 [N, 2, 4, 3], cnt int32 [N, 2],
-    in the crop boxes and under the three flips of sample_tab; shape = (D, H, W).  stddev None: the Euclidean distance to the
-    nearest click divided by euclid_norm (default: float32(H * sqrt(2) * 0.8), input_pipeline_3d.py:372); (s_z, s_y, s_x):
-    the Gaussian of --local_enhance.  guide_channel 2: (fg, bg); 1: fg - bg.  Current stream."""
-    _require_cuda(sample_tab, pts, cnt)
-    n = _inter_tab(sample_tab)
-    assert pts.dtype == torch.int32 and tuple(pts.shape) == (n, 2, _abi.LITS_MAX_CLICKS, 3) and pts.is_contiguous()
-    assert cnt.dtype == torch.int32 and tuple(cnt.shape) == (n, 2) and cnt.is_contiguous()
+def _click_guide3d_args(sample_tab, n, shape, src_hw, guide_channel, stddev, euclid_norm):
+    """(descriptor, empty guide [n, D, H, W, guide_channel]) of unetk_click_guide3d and unetk_click_guide3d_list."""
     d, h, w = (int(v) for v in shape)
     if euclid_norm is None:
         euclid_norm = click_guide3d_norm(h)
@@ -1911,11 +1904,79 @@ def click_guide3d(sample_tab, pts, cnt, shape, src_hw, guide_channel=2, stddev=N
                                  gaussian=0 if stddev is None else 1,
                                  stddev=(ctypes.c_float * 3)(*((0.0, 0.0, 0.0) if stddev is None else tuple(float(v) for v in stddev))),
                                  euclid_norm=float(euclid_norm))
-    guide = torch.empty((n, d, h, w, int(guide_channel)), dtype=torch.float32, device=sample_tab.device)
+    return desc, torch.empty((n, d, h, w, int(guide_channel)), dtype=torch.float32, device=sample_tab.device)
+
+
+def click_guide3d(sample_tab, pts, cnt, shape, src_hw, guide_channel=2, stddev=None, euclid_norm=None):
+    """sp_guide f32 [N, D, H, W, guide_channel] from 3-D clicks (unetk_click_guide3d): pts int32 [N, 2, 4, 3], cnt int32 [N, 2],
+    in the crop boxes and under the three flips of sample_tab; shape = (D, H, W).  stddev None: the Euclidean distance to the
+    nearest click divided by euclid_norm (default: float32(H * sqrt(2) * 0.8), input_pipeline_3d.py:372); (s_z, s_y, s_x):
+    the Gaussian of --local_enhance.  guide_channel 2: (fg, bg); 1: fg - bg.  Current stream."""
+    _require_cuda(sample_tab, pts, cnt)
+    n = _inter_tab(sample_tab)
+    assert pts.dtype == torch.int32 and tuple(pts.shape) == (n, 2, _abi.LITS_MAX_CLICKS, 3) and pts.is_contiguous()
+    assert cnt.dtype == torch.int32 and tuple(cnt.shape) == (n, 2) and cnt.is_contiguous()
+    desc, guide = _click_guide3d_args(sample_tab, n, shape, src_hw, guide_channel, stddev, euclid_norm)
     with _timed_hbm("click_guide3d", guide, 1):
         check(_abi.lib().unetk_click_guide3d(ctypes.byref(desc), ptr(sample_tab), ptr(pts), ptr(cnt), ptr(guide), stream_ptr()),
               "click_guide3d")
     return guide
+
+
+def click_guide3d_list(sample_tab, pts, cnt, shape, src_hw, guide_channel=2, stddev=None, euclid_norm=None):
+    """click_guide3d for the rows of sample_tab from ONE pair of click lists in case coordinates (unetk_click_guide3d_list): pts
+    int32 [2, K, 3] with K <= 64 = (kind, click, (z from the case's first slice, y, x)), cnt int32 [2].  Each row subtracts its
+    crop box's origin; the same kernel: bit-equal to click_guide3d fed the clicks relative to the box.  Current stream."""
+    _require_cuda(sample_tab, pts, cnt)
+    n = _inter_tab(sample_tab)
+    assert pts.dtype == torch.int32 and pts.dim() == 3 and pts.shape[0] == 2 and pts.shape[2] == 3 and pts.is_contiguous()
+    assert cnt.dtype == torch.int32 and tuple(cnt.shape) == (2,) and cnt.is_contiguous()
+    desc, guide = _click_guide3d_args(sample_tab, n, shape, src_hw, guide_channel, stddev, euclid_norm)
+    with _timed_hbm("click_guide3d_list", guide, 1):
+        check(_abi.lib().unetk_click_guide3d_list(ctypes.byref(desc), ptr(sample_tab), ptr(pts), ptr(cnt), int(pts.shape[1]),
+                                                  ptr(guide), stream_ptr()), "click_guide3d_list")
+    return guide
+
+
+def inter_click3d_desc(seg_slices, case_base, depth, k, obj_label=1, lab_scale=64, dist_cap=255):
+    """The descriptor of unetk_inter_click3d (include/unetk.h)."""
+    return _abi.InterClick3dDesc(case_base=int(case_base), depth=int(depth), n_slices=seg_slices.shape[0],
+                                 src_h=seg_slices.shape[1], src_w=seg_slices.shape[2], lab_scale=int(lab_scale),
+                                 obj_label=int(obj_label), K=int(k), dist_cap=int(dist_cap))
+
+
+def inter_click3d_ws(desc, device):
+    """A workspace of exactly the size unetk_inter_click3d asks for; raises where the query says unsupported."""
+    nbytes = int(_abi.lib().unetk_inter_click3d_ws_bytes(ctypes.byref(desc)))
+    if nbytes == 0:
+        raise _abi.UnetkError("inter_click3d: unsupported (a case of {} x {} x {}, K = {}, dist_cap = {})".format(
+            desc.depth, desc.src_h, desc.src_w, desc.K, desc.dist_cap))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def inter_click3d(seg_slices, case_base, depth, pred, prev, pts, cnt, obj_label=1, lab_scale=64, dist_cap=255, table=None, ws=None):
+    """One corrective 3-D click for a case (unetk_inter_click3d; include/unetk.h has the semantics): the case is store slices
+    [case_base, case_base + depth); pred uint8 [depth, src_h, src_w] or None (all zeros); prev = the previous click (z, y, x) or
+    None; pts int32 [2, K, 3] / cnt int32 [2] the case's click lists in case coordinates (appended to in place).  Returns the
+    int32 [20] table row.  Nothing is read back here.  Current stream."""
+    _require_cuda(seg_slices, pts, cnt)
+    assert seg_slices.dtype == torch.uint8 and seg_slices.dim() == 3 and seg_slices.is_contiguous()
+    assert pts.dtype == torch.int32 and pts.dim() == 3 and pts.shape[0] == 2 and pts.shape[2] == 3 and pts.is_contiguous()
+    assert cnt.dtype == torch.int32 and tuple(cnt.shape) == (2,) and cnt.is_contiguous()
+    if pred is not None:
+        assert pred.is_cuda and pred.dtype == torch.uint8 and pred.is_contiguous()
+        assert tuple(pred.shape) == (int(depth),) + tuple(seg_slices.shape[1:])
+    desc = inter_click3d_desc(seg_slices, case_base, depth, pts.shape[1], obj_label, lab_scale, dist_cap)
+    if ws is None:
+        ws = inter_click3d_ws(desc, seg_slices.device)
+    if table is None:
+        table = torch.empty(_abi.INTER3D_TAB_COLS, dtype=torch.int32, device=seg_slices.device)
+    assert table.dtype == torch.int32 and table.numel() == _abi.INTER3D_TAB_COLS and table.is_contiguous()
+    pz, py, px = (-1, -1, -1) if prev is None else (int(v) for v in prev)
+    with _timed_hbm("inter_click3d", ws, 1):
+        check(_abi.lib().unetk_inter_click3d(ctypes.byref(desc), ptr(seg_slices), ptr(pred), pz, py, px, ptr(pts), ptr(cnt),
+                                             ptr(table), ptr(ws), ws.numel(), stream_ptr()), "inter_click3d")
+    return table
 
 
 def click_guide3d_norm(im_height):

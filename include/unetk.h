@@ -997,6 +997,51 @@ int unetk_lits3d_clicks(const unetk_lits3d_clicks_desc* d, const uint8_t* seg_sl
 int unetk_click_guide3d(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const int32_t* pts, const int32_t* cnt,
                         float* guide, void* stream);
 
+/* ---------------------------------------------------------------- 3-D interactive evaluation: corrective clicks  
+ * The click step of the reference's entry/main_eval_3d.py (:152-185 inter_simulation_test) for ONE case, and the guide of the
+ * case's windows from its click lists.  Additive to ABI 10.
+ *
+ * unetk_click_guide3d_list: unetk_click_guide3d for the N rows of a LiTS 3-D table from ONE pair of click lists shared by all
+ *   rows: pts int32 [2][K][3] = (kind, click, (z, y, x)) in CASE coordinates -- z from the case's first slice, (y, x) in the
+ *   slice -- and cnt int32 [2], clamped into [0, K]; 1 <= K <= UNETK_INTER_MAX_CLICKS (else UNETK_E_BADARG).  Per row the crop
+ *   box's origin (z1, y1, x1) is subtracted from the clicks in integers; a click outside the box takes part with its true
+ *   (negative or large) offset.  Then the same kernel and arithmetic: unetk_click_guide3d fed the clicks relative to the row's
+ *   box, with counts <= UNETK_LITS_MAX_CLICKS, gives the same output bit for bit.
+ *
+ * unetk_inter_click3d: the case is the `depth` store slices from `case_base`; a voxel's linear index is (z * src_h + y) * src_w
+ *   + x with z from the case's first slice.  pred uint8 [depth][src_h][src_w] (non-zero = object) or NULL = all zeros.
+ *   (prev_z, prev_y, prev_x): the previous click, -1 = none.  pts int32 [2][K][3], cnt int32 [2]: the case's click lists in case
+ *   coordinates (kind 0 foreground / 1 background), read and appended to.
+ *     ref = stored label >= obj_label * lab_scale;  err = pred xor ref;
+ *     the 6-connected components of err; the largest one, the smallest root (= minimum linear index) on ties;
+ *     candidate = the component's mean per axis, rounded half to even (exact integers, the q / r rule of unetk_lits3d_clicks);
+ *     click = the candidate where err is set there (err, not the component); otherwise (fallback) the component's voxel with
+ *       the greatest 3-D city-block distance to the nearest non-error voxel, the case's border counting as non-error, the
+ *       distance capped at dist_cap; ties: the smaller squared Euclidean distance to the candidate, then the smaller index;
+ *     kind = ref set at the click ? 0 : 1;  repeat = the click equals the previous click;
+ *     the click is appended to the kind's list unless the list holds K clicks already.
+ *   An empty err gives no click (empty flag).  table int32 [UNETK_INTER3D_TAB_COLS]:
+ *     0 n_pred  1 n_ref  2 n_inter   3 components  4 area  5 root   6, 7, 8 candidate (z, y, x)   9, 10, 11 click (z, y, x)
+ *     12 kind   13 fallback  14 repeat  15 empty  16 appended   17 row state: 1 = ran, 2 = the case leaves the store (nothing
+ *     but the row is written)   18, 19 zero.  Columns 5 .. 12 are -1 without a click.
+ *   src_h, src_w <= 1024, depth <= 4096 (the fallback's key holds the squared distance to the candidate in 25 bits),
+ *   depth * src_h * src_w < 2^31, K <= UNETK_INTER_MAX_CLICKS (else UNETK_E_UNSUPPORTED and a zero ws query); 1 <= dist_cap <= 255;
+ *   ws 16-byte aligned.  Integer arithmetic only; sums and maxima are integer atomics: two calls give identical bits.  Nothing
+ *   is written beyond pts, cnt, the table row and ws. */
+#define UNETK_INTER3D_TAB_COLS 20
+typedef struct unetk_inter_click3d_desc {
+  int32_t case_base, depth;       /* the case: store slices [case_base, case_base + depth) */
+  int32_t n_slices, src_h, src_w; /* extent of the resident store */
+  int32_t lab_scale, obj_label;   /* object = seg / lab_scale >= obj_label */
+  int32_t K;                      /* clicks a list holds */
+  int32_t dist_cap;               /* cap of the fallback's distance, 1 .. 255 */
+} unetk_inter_click3d_desc;
+int unetk_click_guide3d_list(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const int32_t* pts, const int32_t* cnt,
+                             int K, float* guide, void* stream);
+size_t unetk_inter_click3d_ws_bytes(const unetk_inter_click3d_desc* d);
+int unetk_inter_click3d(const unetk_inter_click3d_desc* d, const uint8_t* seg_slices, const uint8_t* pred, int prev_z, int prev_y,
+                        int prev_x, int32_t* pts, int32_t* cnt, int32_t* table, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- optimiser  core/solver.py:204-243
  * tf.train.AdamOptimizer on a flat parameter buffer.  g' = g*gscale + l2*p  (slim.l2_regularizer
  * gradient, base.py:128-135);  m += (1-b1)(g'-m);  v += (1-b2)(g'^2-v);
