@@ -105,6 +105,21 @@ __global__ __launch_bounds__(256) void p3d_mask_stats_kernel(unetk_lits3d_desc d
 
 // ------------------------------------------------------------------------------------------------ pass 2: the patch
 // Voxel (z, y, x) of the resized, un-flipped patch; the flips are its write address.
+//
+// ROT (unetk_lits_patch3d_rot): a row whose table columns 13 / 14 are not both bit-zero is turned in the
+// plane about the crop's centre.  Its four taps and its label are read from the SLICE (p3d_rot_tap / p3d_rot_label), not
+// from the crop box, so the corners of a turned patch show the tissue that lies there; only what leaves the slice is 0.
+// The row is block-uniform (blockIdx.y); rows that are not rotated run the statements of ROT = false.  x-fastest threads
+// walk a slanted line through the uint16 rows: neighbouring lanes stay within a few 64-byte segments of each other, and the
+// pass is a few MB per sample either way.
+__device__ __forceinline__ float p3d_rot_tap(const uint16_t* __restrict__ sl, int64_t yy, int64_t xx, int src_h, int src_w) {
+  return (yy >= 0 && yy < src_h && xx >= 0 && xx < src_w) ? (float)sl[yy * src_w + xx] : 0.f;
+}
+__device__ __forceinline__ int p3d_rot_label(const uint8_t* __restrict__ sg, int64_t yy, int64_t xx,
+                                             const unetk_lits3d_desc& d) {
+  return (yy >= 0 && yy < d.src_h && xx >= 0 && xx < d.src_w) ? min((int)sg[yy * d.src_w + xx] / d.lab_scale, d.lab_max) : 0;
+}
+template <bool ROT>
 __global__ __launch_bounds__(256) void p3d_patch_kernel(unetk_lits3d_desc d, const uint16_t* __restrict__ slices,
                                                         const uint8_t* __restrict__ segs, const int32_t* __restrict__ tab,
                                                         const float* __restrict__ stat, float* __restrict__ images,
@@ -114,6 +129,8 @@ __global__ __launch_bounds__(256) void p3d_patch_kernel(unetk_lits3d_desc d, con
   const int32_t* t = tab + (int64_t)n * TW;
   const Box3 b = p3d_box(t, d);
   const bool flr = t[7] != 0, fud = t[8] != 0, ffb = t[9] != 0;
+  LitsRot rot = {false, 0.f, 0.f};
+  if (ROT) rot = lits_rot_of(t);
   const float m = stat[(int64_t)n * ST_N + ST_M], den = stat[(int64_t)n * ST_N + ST_S] + 1e-8f;
   const float scale = (float)d.im_scale;
   const float hs = lits_ac_scale(b.ch, d.H), ws = lits_ac_scale(b.cw, d.W);
@@ -131,7 +148,23 @@ __global__ __launch_bounds__(256) void p3d_patch_kernel(unetk_lits3d_desc d, con
     float v = 0.f;
     int l = 0;
     const int64_t s = p3d_slice(b, z, d);
-    if (s >= 0) {
+    if (ROT && rot.on) {
+      const LitsRotAt at = lits_rot_coord(y, x, b.ch, b.cw, hs, ws, rot);
+      if (s >= 0 && at.ok) {
+        const float fy0 = floorf(at.in_y), fx0 = floorf(at.in_x);
+        const int64_t yy = (int64_t)b.y1 + (int)fy0, xx = (int64_t)b.x1 + (int)fx0;
+        const uint16_t* sl = slices + s * plane;
+        float c[4] = {p3d_rot_tap(sl, yy, xx, d.src_h, d.src_w), p3d_rot_tap(sl, yy, xx + 1, d.src_h, d.src_w),
+                      p3d_rot_tap(sl, yy + 1, xx, d.src_h, d.src_w), p3d_rot_tap(sl, yy + 1, xx + 1, d.src_h, d.src_w)};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float cv = c[j] / scale;
+          c[j] = cv > 0.f ? (cv - m) / den : 0.f;
+        }
+        v = lits_bilerp(c[0], c[1], c[2], c[3], at.in_x - fx0, at.in_y - fy0);
+        l = p3d_rot_label(segs + s * plane, (int64_t)b.y1 + (int)roundf(at.in_y), (int64_t)b.x1 + (int)roundf(at.in_x), d);
+      }
+    } else if (s >= 0) {
       const LitsTaps ty = lits_ac_taps(in_y, b.ch), tx = lits_ac_taps(in_x, b.cw);
       const uint16_t* p = slices + s * plane + (int64_t)b.y1 * d.src_w + b.x1;
       // z-score of each corner, then the lerp (data_processing :359 before :381): (img - region mean) / (region sd + 1e-8)
@@ -381,9 +414,10 @@ extern "C" size_t unetk_lits_patch3d_ws_bytes(const unetk_lits3d_desc* d) {
   return (size_t)d->N * p3d_blocks(d) * (3 * sizeof(double) + 2 * sizeof(float)) + (size_t)d->N * ST_N * sizeof(float);
 }
 
-extern "C" int unetk_lits_patch3d(const unetk_lits3d_desc* d, const uint16_t* slices, const uint8_t* seg_slices,
-                                  const int32_t* sample_tab, float* images, int32_t* labels, void* ws, size_t ws_bytes,
-                                  void* stream) {
+// Both patch entry points: the same passes, the patch pass reading the table's rotation columns or not.
+template <bool ROT>
+static int lits_patch3d(const unetk_lits3d_desc* d, const uint16_t* slices, const uint8_t* seg_slices,
+                        const int32_t* sample_tab, float* images, int32_t* labels, void* ws, size_t ws_bytes, void* stream) {
   UNETK_REQUIRE(p3d_valid(d) && slices && seg_slices && sample_tab && images && labels && ws);
   UNETK_REQUIRE((((uintptr_t)slices) & 1u) == 0 && ((((uintptr_t)sample_tab) | ((uintptr_t)images) | ((uintptr_t)labels)) & 3u) == 0);
   UNETK_REQUIRE(unetk_aligned16(ws));
@@ -397,7 +431,7 @@ extern "C" int unetk_lits_patch3d(const unetk_lits3d_desc* d, const uint16_t* sl
   const dim3 grid(P, d->N), fin(d->N);
   UNETK_LAUNCH(p3d_mask_stats_kernel, grid, dim3(256), 0, st, *d, slices, sample_tab, part);
   UNETK_LAUNCH(p3d_finalize_kernel, fin, dim3(64), 0, st, 0, P, (const double*)part, (const float*)minmax, stat);
-  UNETK_LAUNCH(p3d_patch_kernel, grid, dim3(256), 0, st, *d, slices, seg_slices, sample_tab, (const float*)stat, images, labels, part, minmax);
+  UNETK_LAUNCH(p3d_patch_kernel<ROT>, grid, dim3(256), 0, st, *d, slices, seg_slices, sample_tab, (const float*)stat, images, labels, part, minmax);
   if (d->training) {
     const int total = d->D * d->H * d->W;                      // < 2^31: p3d_supported
     UNETK_LAUNCH(p3d_finalize_kernel, fin, dim3(64), 0, st, 1, P, (const double*)part, (const float*)minmax, stat);
@@ -407,4 +441,16 @@ extern "C" int unetk_lits_patch3d(const unetk_lits3d_desc* d, const uint16_t* sl
   }
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
+}
+
+extern "C" int unetk_lits_patch3d(const unetk_lits3d_desc* d, const uint16_t* slices, const uint8_t* seg_slices,
+                                  const int32_t* sample_tab, float* images, int32_t* labels, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  return lits_patch3d<false>(d, slices, seg_slices, sample_tab, images, labels, ws, ws_bytes, stream);
+}
+
+extern "C" int unetk_lits_patch3d_rot(const unetk_lits3d_desc* d, const uint16_t* slices, const uint8_t* seg_slices,
+                                      const int32_t* sample_tab, float* images, int32_t* labels, void* ws, size_t ws_bytes,
+                                      void* stream) {
+  return lits_patch3d<true>(d, slices, seg_slices, sample_tab, images, labels, ws, ws_bytes, stream);
 }

@@ -462,7 +462,11 @@ __device__ __forceinline__ float cg3_at(int pz, int py, int px, const int32_t* _
 }
 // LIST: ONE pair of click lists for all rows, pts [2][K][3] in case coordinates (z from the case's first slice, y and x in the
 // slice) and cnt [2] (unetk_click_guide3d_list); else pts [N][2][MAXK][3] relative to each row's box and cnt [N][2]
-template <bool LIST>
+// ROT (unetk_click_guide3d_rot): ONLY the rows whose table columns 13 / 14 are not both bit-zero; the guide is
+// evaluated at the four UNCLAMPED corners of the turned coordinate (lits_rot_coord, the patch kernel's): it is a function of
+// position, so a corner beyond the crop box is simply evaluated there; an invalid coordinate gives 0.  The rows that are not
+// rotated are left to the plain kernel, which the entry point launches first (click_guide3d_launch says why).
+template <bool LIST, bool ROT>
 __global__ __launch_bounds__(256) void click_guide3d_kernel(unetk_lits3d_clicks_desc d, const int32_t* __restrict__ tab,
                                                             const int32_t* __restrict__ pts, const int32_t* __restrict__ cnt,
                                                             int K, float* __restrict__ guide) {
@@ -474,8 +478,29 @@ __global__ __launch_bounds__(256) void click_guide3d_kernel(unetk_lits3d_clicks_
   const int y = q / d.W, x = q - y * d.W;
   const int32_t* t = tab + (int64_t)n * TW;
   const Box3 b = p3d_box(t, d);
-  const LitsTaps ty = lits_ac_taps(y * lits_ac_scale(b.ch, d.H), b.ch), tx = lits_ac_taps(x * lits_ac_scale(b.cw, d.W), b.cw);
-  const int y0 = min(ty.i0, b.ch - 1), x0 = min(tx.i0, b.cw - 1);
+  LitsTaps ty, tx;
+  int y0, x0;
+  bool ok = true;
+  if (ROT) {
+    const LitsRot rot = lits_rot_of(t);
+    if (!rot.on) return;                                     // the plain kernel has written this row
+    const LitsRotAt at = lits_rot_coord(y, x, b.ch, b.cw, lits_ac_scale(b.ch, d.H), lits_ac_scale(b.cw, d.W), rot);
+    ok = at.ok;
+    const float fy0 = ok ? floorf(at.in_y) : 0.f, fx0 = ok ? floorf(at.in_x) : 0.f;
+    y0 = (int)fy0;
+    x0 = (int)fx0;
+    ty.i0 = y0;
+    ty.i1 = y0 + 1;
+    ty.f = ok ? at.in_y - fy0 : 0.f;
+    tx.i0 = x0;
+    tx.i1 = x0 + 1;
+    tx.f = ok ? at.in_x - fx0 : 0.f;
+  } else {
+    ty = lits_ac_taps(y * lits_ac_scale(b.ch, d.H), b.ch);
+    tx = lits_ac_taps(x * lits_ac_scale(b.cw, d.W), b.cw);
+    y0 = min(ty.i0, b.ch - 1);
+    x0 = min(tx.i0, b.cw - 1);
+  }
   Guide3 g;
   g.gaussian = d.gaussian != 0;
   g.nz = 2.f * d.stddev[0] * d.stddev[0];
@@ -491,6 +516,7 @@ __global__ __launch_bounds__(256) void click_guide3d_kernel(unetk_lits3d_clicks_
     const float tl = cg3_at(z, y0, x0, p, k, g, oz, oy, ox), tr = cg3_at(z, y0, tx.i1, p, k, g, oz, oy, ox);
     const float bl = cg3_at(z, ty.i1, x0, p, k, g, oz, oy, ox), br = cg3_at(z, ty.i1, tx.i1, p, k, g, oz, oy, ox);
     v[kind] = lits_bilerp(tl, tr, bl, br, tx.f, ty.f);
+    if (ROT && !ok) v[kind] = 0.f;
   }
   const int zo = t[9] != 0 ? d.D - 1 - z : z, yo = t[8] != 0 ? d.H - 1 - y : y, xo = t[7] != 0 ? d.W - 1 - x : x;
   const int64_t o = (int64_t)n * vol + ((int64_t)zo * d.H + yo) * d.W + xo;
@@ -540,9 +566,10 @@ extern "C" int unetk_lits3d_clicks(const unetk_lits3d_clicks_desc* d, const uint
 }
 
 namespace {
-// K == 0: unetk_click_guide3d (clicks per row, relative to its box); else unetk_click_guide3d_list
+// K == 0: unetk_click_guide3d (clicks per row, relative to its box), with rot unetk_click_guide3d_rot; else
+// unetk_click_guide3d_list
 int click_guide3d_launch(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const int32_t* pts, const int32_t* cnt,
-                         int K, float* guide, void* stream) {
+                         int K, float* guide, void* stream, bool rot = false) {
   UNETK_REQUIRE(d && d->N > 0 && d->D > 0 && d->H > 0 && d->W > 0 && d->src_h > 0 && d->src_w > 0 && sample_tab && pts && cnt &&
                 guide && (d->G == 1 || d->G == 2));
   UNETK_REQUIRE(((((uintptr_t)sample_tab) | ((uintptr_t)pts) | ((uintptr_t)cnt) | ((uintptr_t)guide)) & 3u) == 0);
@@ -551,9 +578,16 @@ int click_guide3d_launch(const unetk_lits3d_clicks_desc* d, const int32_t* sampl
   if ((int64_t)d->D * d->H * d->W >= ((int64_t)1 << 31) || (total + 255) / 256 >= ((int64_t)1 << 31)) return UNETK_E_UNSUPPORTED;
   const dim3 grid((unsigned)((total + 255) / 256));
   if (K > 0)
-    UNETK_LAUNCH(click_guide3d_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, *d, sample_tab, pts, cnt, K, guide);
+    UNETK_LAUNCH((click_guide3d_kernel<true, false>), grid, dim3(256), 0, (hipStream_t)stream, *d, sample_tab, pts, cnt, K, guide);
   else
-    UNETK_LAUNCH(click_guide3d_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, *d, sample_tab, pts, cnt, 0, guide);
+    UNETK_LAUNCH((click_guide3d_kernel<false, false>), grid, dim3(256), 0, (hipStream_t)stream, *d, sample_tab, pts, cnt, 0, guide);
+  // Rotated rows are written again by a kernel of their own, after the plain kernel has written every row.  One kernel that
+  // branched per row was tried: the compiler contracted the plain statements differently next to the rotated ones (the
+  // fraction y * scale - i0 became a fused multiply-add), and the rows that are not rotated were no longer the bits of
+  // unetk_click_guide3d.  Running the SAME compiled kernel on them makes that equality hold by construction, for the price
+  // of evaluating the rotated rows twice (the guide is the small part of a guided batch: DESIGN.md 7.3.9).
+  if (rot)
+    UNETK_LAUNCH((click_guide3d_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, *d, sample_tab, pts, cnt, 0, guide);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }
@@ -562,6 +596,11 @@ int click_guide3d_launch(const unetk_lits3d_clicks_desc* d, const int32_t* sampl
 extern "C" int unetk_click_guide3d(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const int32_t* pts,
                                    const int32_t* cnt, float* guide, void* stream) {
   return click_guide3d_launch(d, sample_tab, pts, cnt, 0, guide, stream);
+}
+
+extern "C" int unetk_click_guide3d_rot(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const int32_t* pts,
+                                       const int32_t* cnt, float* guide, void* stream) {
+  return click_guide3d_launch(d, sample_tab, pts, cnt, 0, guide, stream, true);
 }
 
 extern "C" int unetk_click_guide3d_list(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const int32_t* pts,

@@ -24,6 +24,11 @@ the sampler's draw so that an unguided run consumes its generator exactly as wit
 :364-398 with utils/image_ops.py:437-472 `create_spatial_guide_3d` -> `unetk_click_guide3d`.  The object the clicks are
 simulated on is the sampler's forced class (stored label >= fg_label); the restatement is tests/lits3d_clicks_ref.py.
 
+With --random_rotate DEG (not a reference flag) training patches are turned in the plane: the sampler draws an
+angle per sample AFTER every other draw of the batch, writes its sin / cos into columns 13 / 14 of the table, and the batches
+go through `unetk_lits_patch3d_rot` and `unetk_click_guide3d_rot`; the restatement is tests/lits3d_rotate_ref.py.  Evaluation
+never rotates.
+
 Offline, `input_fn_eval` tiles every case of the validation fold with windows cut as `eval_online` cuts them (window_starts,
 eval_tables) for the sliding-window evaluator, `EvaluateVolume.run_3d` (--eval_in_patches).  Two options
 of that evaluation live here too: the per-axis Gaussian window tables (window_weights, --eval_window_weight gaussian) and
@@ -52,6 +57,7 @@ STATUS_BITS = ((1, "unetk_lits_pick_voxel: a forced sample's rank was beyond the
                (4, "unetk_lits3d_clicks: a row of click draws was out of range"))
 (COL_BASE, COL_DEPTH, COL_CZ, COL_CY, COL_CX, COL_CH, COL_CW, COL_FLIP_LR, COL_FLIP_UD, COL_FLIP_FB, COL_GAMMA, COL_FORCED,
  COL_K) = range(13)
+COL_SIN, COL_COS = 13, 14          # --random_rotate: float bits, both zero = not rotated
 
 
 def add_arguments(parser):
@@ -62,6 +68,10 @@ def add_arguments(parser):
     parser.add_argument("--seed", type=int, default=1234)
     parser.add_argument("--eval_overlap", type=float, default=0.5,
                         help="--mode eval --eval_in_patches: overlap of neighbouring windows as a share of the window, in [0, 1)")
+    parser.add_argument("--random_rotate", type=float, default=0.0, metavar="DEG",
+                        help="--mode train: turn every patch in the plane by an angle from U(-DEG, DEG) degrees; 0 = off")
+    parser.add_argument("--rotate_prob", type=float, default=1.0, metavar="P",
+                        help="--random_rotate: the probability that a sample is rotated")
     parser.add_argument("--eval_window_weight", type=str, default="uniform", choices=WINDOW_WEIGHTS,
                         help="--eval_in_patches: how a window's voxels count in the average; gaussian weights its centre")
     parser.add_argument("--eval_window_sigma", type=float, default=0.125,
@@ -101,8 +111,19 @@ def check_values(args):
     if margin is not DEFAULT_BOX_MARGIN and getattr(args, "eval_box_from", None) is None:       # argparse keeps the default object
         raise ValueError("--eval_box_margin grows the box of --eval_box_from, which is not given")
     guide_stddev(args)
+    rotation(args)
     if int(getattr(args, "guide_channel", 2)) not in (1, 2):
         raise ValueError("--guide_channel must be 1 or 2, got {}".format(args.guide_channel))
+
+
+def rotation(args):
+    """(--random_rotate in degrees, --rotate_prob): 0 <= DEG <= 180 and 0 <= P <= 1."""
+    deg, prob = float(getattr(args, "random_rotate", 0.0) or 0.0), float(getattr(args, "rotate_prob", 1.0))
+    if not 0.0 <= deg <= 180.0:                           # also refuses NaN
+        raise ValueError("--random_rotate must satisfy 0 <= DEG <= 180, got {}".format(deg))
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError("--rotate_prob must satisfy 0 <= P <= 1, got {}".format(prob))
+    return deg, prob
 
 
 def guide_stddev(args):
@@ -152,13 +173,18 @@ class PatchSampler(object):
       * per sample two zoom factors U(zoom_scale) for y and x, crop = int32(target * zoom) (:589); evaluation: 1.125;
       * training: a coin per flip axis enabled in random_flip (image_ops.py:309-314) and gamma -- with probability 0.3 from
         U(0.7, 1), else from U(1, 1.5) (image_ops.py:344-346 as data_processing :405 calls it).
+      * training with random_rotate > 0 (not in the reference): a draw of its own, `draw_rotation`, made after
+        all of the above (and after a guided run's click draws) -- a coin with probability rotate_prob and an angle from
+        U(-random_rotate, random_rotate) degrees per sample.
     A forced-class voxel is chosen WITHOUT a position table: `slice_counts` (forced-class pixels of every store slice, see
     forced_counts) is cumulated once; a rank below the case's total is drawn, searchsorted on the cumulative counts gives
     the slice z and the rank k inside it, and `unetk_lits_pick_voxel` turns (z, k) into (py, px) on the device."""
 
     def __init__(self, cases, offset, slice_counts, batch_size, shape, src_hw, tumor_percent=0.5, zoom_scale=(1.0, 1.25),
-                 random_flip=0, training=True, seed=None):
+                 random_flip=0, training=True, seed=None, random_rotate=0.0, rotate_prob=1.0):
         self.bs = int(batch_size)
+        self.rotate = float(random_rotate or 0.0) if training else 0.0      # degrees; > 0: draw_rotation draws
+        self.rotate_prob = float(rotate_prob)
         self.depth_out, self.h, self.w = (int(v) for v in shape)
         self.src_h, self.src_w = int(src_hw[0]), int(src_hw[1])
         self.training = bool(training)
@@ -215,10 +241,27 @@ class PatchSampler(object):
         return dict(case=case, pid=self.pid[case], forced=forced, center=center, k=k, crop=crop, flips=flips,
                     gamma=gamma.astype(np.float32))
 
-    def table(self, b=None):
-        """The batch as `unetk_lits_patch3d` takes it: int32 [bs, 16] (include/unetk.h), gamma as float bits."""
-        b = self.draw() if b is None else b
+    def draw_rotation(self):
+        """The rotation draw of one batch, made only when --random_rotate > 0 and AFTER every other draw of
+        the batch (`draw`, and the click draws of a guided run), so that a run without the flag consumes its generator as
+        before: dict(on [bs] bool with probability rotate_prob, deg [bs] from U(-DEG, DEG)), or None."""
+        if not self.rotate > 0.0:
+            return None
+        on = self.rng.random(self.bs) < self.rotate_prob
+        return dict(on=on, deg=self.rng.uniform(-self.rotate, self.rotate, self.bs))
+
+    def table(self, b=None, rot=None):
+        """The batch as `unetk_lits_patch3d` takes it: int32 [bs, 16] (include/unetk.h), gamma as float bits.  rot: what
+        `draw_rotation` gave -- the `on` rows get sin / cos (float64, cast to float32; float bits) in columns 13 / 14 for
+        `unetk_lits_patch3d_rot`, every other row keeps zeros there.  Without b the sampler draws both."""
+        if b is None:
+            b, rot = self.draw(), self.draw_rotation()
         tab = np.zeros((self.bs, _abi.LITS3D_TAB_COLS), dtype=np.int32)
+        if rot is not None:
+            rad = np.deg2rad(np.asarray(rot["deg"], dtype=np.float64))
+            on = np.asarray(rot["on"], dtype=bool)
+            tab[on, COL_SIN] = np.sin(rad).astype(np.float32).view(np.int32)[on]
+            tab[on, COL_COS] = np.cos(rad).astype(np.float32).view(np.int32)[on]
         tab[:, COL_BASE] = self.base[b["case"]]
         tab[:, COL_DEPTH] = self.depth[b["case"]]
         tab[:, COL_CZ:COL_CX + 1] = b["center"]
@@ -254,18 +297,21 @@ def batches(store, sampler, shape, lab_max, fg_label, status=None, guide=None):
     while True:
         b = sampler.draw()
         if guide is None:
-            (tab,) = lits.upload_pinned([sampler.table(b)], store.device)
+            (tab,) = lits.upload_pinned([sampler.table(b, sampler.draw_rotation())], store.device)
         else:
             from . import lits_inter
             clicks = lits_inter.draw_click_tab(sampler.rng, sampler.bs, CLICKS[3])
-            tab, ctab = lits.upload_pinned([sampler.table(b), clicks.view(np.int32)], store.device)
+            tab, ctab = lits.upload_pinned([sampler.table(b, sampler.draw_rotation()), clicks.view(np.int32)], store.device)
         if sampler.force:
             ops.lits_pick_voxels(store.lb, tab, fg_label, status, lits.LB_SCALE)
-        images, labels = ops.lits_patch3d(store.im, store.lb, tab, shape, sampler.training, lab_max, lits.IM_SCALE, lits.LB_SCALE)
+        rotate = sampler.rotate > 0.0                        # --random_rotate: the _rot entries, which read the table's (sin, cos)
+        images, labels = ops.lits_patch3d(store.im, store.lb, tab, shape, sampler.training, lab_max, lits.IM_SCALE, lits.LB_SCALE,
+                                          rotate=rotate)
         feats = {"images": images, "names": torch.from_numpy(b["pid"])}
         if guide is not None:
             pts, cnt = ops.lits3d_clicks(store.lb, tab, ctab, shape, status, fg_label, CLICKS, lits.LB_SCALE)
-            feats["sp_guide"] = ops.click_guide3d(tab, pts, cnt, shape, store.im.shape[1:], guide["channels"], guide["stddev"])
+            feats["sp_guide"] = ops.click_guide3d(tab, pts, cnt, shape, store.im.shape[1:], guide["channels"], guide["stddev"],
+                                                  rotate=rotate)
         yield feats, labels
 
 
@@ -307,9 +353,11 @@ def input_fn(mode, params):
     base_seed = int(getattr(args, "seed", 1234) or 1234)
     training = mode == "train"
     seed = base_seed + 1000 * int(params.get("rank", 0)) if training else base_seed + 500
+    deg, prob = rotation(args)                             # only `train` rotates: the sampler drops it for eval_online
     sampler = PatchSampler(cases, store.offset, params[ckey], bs, shape, store.im.shape[1:],
                            tumor_percent=getattr(args, "tumor_percent", 0.5), zoom_scale=getattr(args, "zoom_scale", (1., 1.25)),
-                           random_flip=getattr(args, "random_flip", 0), training=training, seed=seed)
+                           random_flip=getattr(args, "random_flip", 0), training=training, seed=seed, random_rotate=deg,
+                           rotate_prob=prob)
     # the pick kernel's status words live in `params` (one per mode) so that they outlast the generators: params[("lits3d_status",
     # True)] is the training stream's.  An evaluation synchronises anyway, so both are read there: the training word when
     # the evaluation starts, the evaluation's own after its last batch.

@@ -743,8 +743,8 @@ int unetk_lits_context(float* table, int64_t n_rows, int F, const int32_t* sampl
  *   2 cz     centre slice (within the case)              10 gamma (float bits; training only)
  *   3 cy     centre row                                  11 forced: 1 = (cy, cx) come from unetk_lits_pick_voxel
  *   4 cx     centre column                               12 k: rank of the forced-class pixel in slice cz
- *   5 ch     crop rows    = int32(H * zoom_y)            13..15 reserved (0)
- *   6 cw     crop columns = int32(W * zoom_x)
+ *   5 ch     crop rows    = int32(H * zoom_y)            13, 14 sin, cos (float bits): read by the _rot entries only
+ *   6 cw     crop columns = int32(W * zoom_x)            15 reserved (0)
  *   7 flip_left_right
  *
  * unetk_lits_pick_voxel: for every row with forced != 0, (cy, cx) <- the k-th pixel, in row-major order, of slice
@@ -779,6 +779,26 @@ int unetk_lits_pick_voxel(const uint8_t* seg_slices, int n_slices, int src_h, in
 size_t unetk_lits_patch3d_ws_bytes(const unetk_lits3d_desc* d);
 int unetk_lits_patch3d(const unetk_lits3d_desc* d, const uint16_t* slices, const uint8_t* seg_slices,
                        const int32_t* sample_tab, float* images, int32_t* labels, void* ws, size_t ws_bytes, void* stream);
+
+/* In-plane rotated patches (additive to ABI 10).  unetk_lits_patch3d with two more table columns:
+ *   13 sin, 14 cos of the row's angle (float bits, formed by the host: the device never calls sincosf); 15 stays reserved.
+ * A row whose columns 13 and 14 are BOTH bit-zero is not rotated: it takes the arithmetic of unetk_lits_patch3d and gives
+ * its output bit for bit.  Any other content -- the explicit identity (0, 1) included -- is a rotated row:
+ *   statistics: m, s over the UNROTATED crop box (pass 1 as it is); gamma as it is, on the rotated patch;
+ *   coordinates: voxel (z, y, x) of the un-flipped patch samples crop slice z at, all float32, EVERY operation rounded on its
+ *     own (no fused multiply-add: a numpy float32 restatement forms the same bits),
+ *       hs = (ch - 1) / (H - 1), ws = (cw - 1) / (W - 1)  (0 for an axis of one voxel: align_corners)
+ *       cy0 = 0.5 (ch - 1), cx0 = 0.5 (cw - 1);   u = y hs - cy0, v = x ws - cx0
+ *       in_y = cy0 + (cos u - sin v),   in_x = cx0 + (sin u + cos v)
+ *   image: i0 = floor(in_y), i1 = i0 + 1, f = in_y - i0, x likewise, the second tap NOT clamped; each of the four taps reads
+ *     the SLICE at (y1 + i, x1 + j) where that lies inside [0, src_h) x [0, src_w) -- beyond the crop box there is real
+ *     tissue -- and is 0 outside it; every tap is normalised on the fly as above, then the same lerps;
+ *   labels: roundf of both coordinates; outside the slice 0, else min(seg / lab_scale, lab_max);
+ *   a coordinate that is not finite or whose magnitude is >= 2^24 counts as outside: image 0, label 0.
+ * Crop slices at or beyond the case's depth are zeros, the flips are the write address: as unetk_lits_patch3d.  Nothing is
+ * read out of bounds for any table content.  Same arguments, checks, error codes and workspace query. */
+int unetk_lits_patch3d_rot(const unetk_lits3d_desc* d, const uint16_t* slices, const uint8_t* seg_slices,
+                           const int32_t* sample_tab, float* images, int32_t* labels, void* ws, size_t ws_bytes, void* stream);
 
 /* Whole-volume evaluation in windows.  probs f32 [N,D,H,W,C]: the class probabilities of the N windows that
  * unetk_lits_patch3d(training = 0) cut for sample_tab (same desc, same table, flips included).  acc f32 [depth,src_h,src_w,C],
@@ -996,6 +1016,17 @@ int unetk_lits3d_clicks(const unetk_lits3d_clicks_desc* d, const uint8_t* seg_sl
                         void* stream);
 int unetk_click_guide3d(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const int32_t* pts, const int32_t* cnt,
                         float* guide, void* stream);
+
+/* The guide of in-plane rotated patches (additive to ABI 10): unetk_click_guide3d that reads columns 13 / 14
+ * of the table as unetk_lits_patch3d_rot does.  The clicks stay what unetk_lits3d_clicks simulates on the UNROTATED label crop
+ * (relative to the crop box).  A row with both columns bit-zero gives the output of unetk_click_guide3d bit for bit.  A rotated
+ * row evaluates the guide -- a function of position, defined beyond [0, ch) x [0, cw) too -- at the four unclamped corners
+ * (i0 | i0 + 1, j0 | j0 + 1) of the in_y, in_x of unetk_lits_patch3d_rot (same float32 operations, no fused multiply-add) and
+ * lerps them with the fractions in_y - i0, in_x - j0 as unetk_click_guide3d lerps its corners; where a coordinate is not finite
+ * or its magnitude is >= 2^24 the guide is 0.  Every mode is served: Gaussian and Euclidean, G 1 and 2, the three flips; a
+ * kind without clicks is exactly 0.  Same arguments, checks and error codes. */
+int unetk_click_guide3d_rot(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const int32_t* pts, const int32_t* cnt,
+                            float* guide, void* stream);
 
 /* ---------------------------------------------------------------- 3-D interactive evaluation: corrective clicks  
  * The click step of the reference's entry/main_eval_3d.py (:152-185 inter_simulation_test) for ONE case, and the guide of the
