@@ -113,6 +113,7 @@ _SIGNATURES = {
     "unetk_lits_patch3d_ws_bytes": (c_size_t, [POINTER(Lits3dDesc)]),
     "unetk_lits_patch3d": (c_int, [POINTER(Lits3dDesc), P, P, P, P, P, P, c_size_t, P]),
     "unetk_lits_patch3d_rot": (c_int, [POINTER(Lits3dDesc), P, P, P, P, P, P, c_size_t, P]),
+    "unetk_lits_patch3d_warp": (c_int, [POINTER(Lits3dDesc), P, P, P, P, c_int, P, P, P, c_size_t, P]),
     "unetk_eval3d_accumulate": (c_int, [POINTER(Lits3dDesc), P, P, c_int, c_int64, c_int, POINTER(c_int32), P, P, P]),
     "unetk_eval3d_accumulate_w": (c_int, [POINTER(Lits3dDesc), P, P, c_int, c_int64, c_int, POINTER(c_int32), P, P, P, P, P, P]),
     "unetk_eval3d_finish": (c_int, [P, c_int, c_int, c_int, c_int, P, P, POINTER(c_int32), P, P, P]),
@@ -128,6 +129,7 @@ _SIGNATURES = {
     "unetk_lits3d_clicks": (c_int, [POINTER(Lits3dClicksDesc), P, P, P, P, P, P, P, c_size_t, P]),
     "unetk_click_guide3d": (c_int, [POINTER(Lits3dClicksDesc), P, P, P, P, P]),
     "unetk_click_guide3d_rot": (c_int, [POINTER(Lits3dClicksDesc), P, P, P, P, P]),
+    "unetk_click_guide3d_warp": (c_int, [POINTER(Lits3dClicksDesc), P, P, c_int, P, P, P, P]),
     "unetk_click_guide3d_list": (c_int, [POINTER(Lits3dClicksDesc), P, P, P, c_int, P, P]),
     "unetk_inter_click3d_ws_bytes": (c_size_t, [POINTER(InterClick3dDesc)]),
     "unetk_inter_click3d": (c_int, [POINTER(InterClick3dDesc), P, P, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),

@@ -195,6 +195,84 @@ __global__ __launch_bounds__(256) void p3d_patch_kernel(unetk_lits3d_desc d, con
   }
 }
 
+// WARP (unetk_lits_patch3d_warp): ONLY the rows whose table column 15 is not zero, launched after
+// p3d_patch_kernel<true> has written every row -- the rows that are not deformed keep the bits of that compiled kernel by
+// construction (lits3d_clicks.hip: click_guide3d_launch says why a branch inside one kernel does not give that).  A deformed
+// row is written again, and its block partials with it, from coordinates moved by the row's B-spline lattice in front of
+// the row's own map (lits_warp_coord); taps, label, z-score and flips are p3d_patch_kernel's rotated branch word for word.
+// The field is the same for every slice, so a thread owns output pixels (y, x), evaluates the spline once per pixel and
+// walks the slices; ZC threads share a pixel's slices when the grid has more threads than the patch has pixels.  The
+// lattice (at most 2 * 19 * 19 floats) is staged in LDS: 32 reads per pixel, neighbouring lanes on the same or the next word.
+__global__ __launch_bounds__(256) void p3d_warp_kernel(unetk_lits3d_desc d, const uint16_t* __restrict__ slices,
+                                                       const uint8_t* __restrict__ segs, const int32_t* __restrict__ tab,
+                                                       const float* __restrict__ warp, int G, const float* __restrict__ stat,
+                                                       float* __restrict__ images, int32_t* __restrict__ labels,
+                                                       double* __restrict__ part, float* __restrict__ minmax) {
+  __shared__ float lat[2 * (LITS_WARP_MAX_G + 3) * (LITS_WARP_MAX_G + 3)];
+  const int n = blockIdx.y, P = gridDim.x;
+  const int32_t* t = tab + (int64_t)n * TW;
+  if (t[15] == 0) return;                                    // block-uniform: p3d_patch_kernel<true> has written this row
+  const int cells = (G + 3) * (G + 3);
+  for (int i = threadIdx.x; i < 2 * cells; i += 256) lat[i] = warp[(int64_t)n * 2 * cells + i];
+  __syncthreads();
+  const Box3 b = p3d_box(t, d);
+  const bool flr = t[7] != 0, fud = t[8] != 0, ffb = t[9] != 0;
+  const LitsRot rot = lits_rot_of(t);
+  const float m = stat[(int64_t)n * ST_N + ST_M], den = stat[(int64_t)n * ST_N + ST_S] + 1e-8f;
+  const float scale = (float)d.im_scale;
+  const float hs = lits_ac_scale(b.ch, d.H), ws = lits_ac_scale(b.cw, d.W);
+  const int64_t plane = (int64_t)d.src_h * d.src_w;
+  const int area = d.H * d.W;
+  const int total = d.D * area;                              // < 2^31: checked by the entry point
+  const int ZC = (int)min((int64_t)d.D, max((int64_t)1, ((int64_t)P * 256) / area));
+  float* img = images + (int64_t)n * total;
+  int32_t* lab = labels + (int64_t)n * total;
+  double cnt = 0., sum = 0., sq = 0.;
+  float lo = INFINITY, hi = -INFINITY;
+  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < (int64_t)ZC * area; i += P * 256) {
+    const int zc = (int)(i / area), r = (int)(i - (int64_t)zc * area);
+    const int y = r / d.W, x = r - y * d.W;
+    const LitsSpline sy = lits_warp_spline(y, d.H, G), sx = lits_warp_spline(x, d.W, G);
+    const LitsRotAt at = lits_warp_coord(y, x, lits_warp_disp(lat, G, sy, sx), lits_warp_disp(lat + cells, G, sy, sx), b.ch, b.cw,
+                                         hs, ws, rot);
+    const float fy0 = at.ok ? floorf(at.in_y) : 0.f, fx0 = at.ok ? floorf(at.in_x) : 0.f;
+    const int64_t yy = (int64_t)b.y1 + (int)fy0, xx = (int64_t)b.x1 + (int)fx0;
+    const int64_t ly = (int64_t)b.y1 + (at.ok ? (int)roundf(at.in_y) : 0), lx = (int64_t)b.x1 + (at.ok ? (int)roundf(at.in_x) : 0);
+    const float fx = at.in_x - fx0, fy = at.in_y - fy0;
+    const int yo = fud ? d.H - 1 - y : y, xo = flr ? d.W - 1 - x : x;
+    for (int z = zc; z < d.D; z += ZC) {
+      float v = 0.f;
+      int l = 0;
+      const int64_t s = p3d_slice(b, z, d);
+      if (s >= 0 && at.ok) {
+        const uint16_t* sl = slices + s * plane;
+        float c[4] = {p3d_rot_tap(sl, yy, xx, d.src_h, d.src_w), p3d_rot_tap(sl, yy, xx + 1, d.src_h, d.src_w),
+                      p3d_rot_tap(sl, yy + 1, xx, d.src_h, d.src_w), p3d_rot_tap(sl, yy + 1, xx + 1, d.src_h, d.src_w)};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float cv = c[j] / scale;
+          c[j] = cv > 0.f ? (cv - m) / den : 0.f;
+        }
+        v = lits_bilerp(c[0], c[1], c[2], c[3], fx, fy);
+        l = p3d_rot_label(segs + s * plane, ly, lx, d);
+      }
+      const int zo = ffb ? d.D - 1 - z : z;
+      const int o = (zo * d.H + yo) * d.W + xo;
+      img[o] = v;
+      lab[o] = l;
+      cnt += 1.;
+      sum += (double)v;
+      sq += (double)v * (double)v;
+      lo = fminf(lo, v);
+      hi = fmaxf(hi, v);
+    }
+  }
+  if (d.training) {
+    block_sum3(cnt, sum, sq, part + ((int64_t)n * P + blockIdx.x) * 3);
+    block_minmax(lo, hi, minmax + ((int64_t)n * P + blockIdx.x) * 2);
+  }
+}
+
 // passes 3, 4 (gamma, retain_stats): lits_patch.h
 bool p3d_supported(const unetk_lits3d_desc* d) {
   return (int64_t)d->D * d->H * d->W < ((int64_t)1 << 31) && (int64_t)d->D * d->src_h * d->src_w < ((int64_t)1 << 31);
@@ -414,10 +492,12 @@ extern "C" size_t unetk_lits_patch3d_ws_bytes(const unetk_lits3d_desc* d) {
   return (size_t)d->N * p3d_blocks(d) * (3 * sizeof(double) + 2 * sizeof(float)) + (size_t)d->N * ST_N * sizeof(float);
 }
 
-// Both patch entry points: the same passes, the patch pass reading the table's rotation columns or not.
+// The patch entry points: the same passes, the patch pass reading the table's rotation columns or not; with a lattice
+// (unetk_lits_patch3d_warp: ROT, warp != nullptr) the deformed rows are then written again by p3d_warp_kernel.
 template <bool ROT>
 static int lits_patch3d(const unetk_lits3d_desc* d, const uint16_t* slices, const uint8_t* seg_slices,
-                        const int32_t* sample_tab, float* images, int32_t* labels, void* ws, size_t ws_bytes, void* stream) {
+                        const int32_t* sample_tab, float* images, int32_t* labels, void* ws, size_t ws_bytes, void* stream,
+                        const float* warp = nullptr, int G = 0) {
   UNETK_REQUIRE(p3d_valid(d) && slices && seg_slices && sample_tab && images && labels && ws);
   UNETK_REQUIRE((((uintptr_t)slices) & 1u) == 0 && ((((uintptr_t)sample_tab) | ((uintptr_t)images) | ((uintptr_t)labels)) & 3u) == 0);
   UNETK_REQUIRE(unetk_aligned16(ws));
@@ -432,6 +512,8 @@ static int lits_patch3d(const unetk_lits3d_desc* d, const uint16_t* slices, cons
   UNETK_LAUNCH(p3d_mask_stats_kernel, grid, dim3(256), 0, st, *d, slices, sample_tab, part);
   UNETK_LAUNCH(p3d_finalize_kernel, fin, dim3(64), 0, st, 0, P, (const double*)part, (const float*)minmax, stat);
   UNETK_LAUNCH(p3d_patch_kernel<ROT>, grid, dim3(256), 0, st, *d, slices, seg_slices, sample_tab, (const float*)stat, images, labels, part, minmax);
+  if (warp)
+    UNETK_LAUNCH(p3d_warp_kernel, grid, dim3(256), 0, st, *d, slices, seg_slices, sample_tab, warp, G, (const float*)stat, images, labels, part, minmax);
   if (d->training) {
     const int total = d->D * d->H * d->W;                      // < 2^31: p3d_supported
     UNETK_LAUNCH(p3d_finalize_kernel, fin, dim3(64), 0, st, 1, P, (const double*)part, (const float*)minmax, stat);
@@ -453,4 +535,11 @@ extern "C" int unetk_lits_patch3d_rot(const unetk_lits3d_desc* d, const uint16_t
                                       const int32_t* sample_tab, float* images, int32_t* labels, void* ws, size_t ws_bytes,
                                       void* stream) {
   return lits_patch3d<true>(d, slices, seg_slices, sample_tab, images, labels, ws, ws_bytes, stream);
+}
+
+extern "C" int unetk_lits_patch3d_warp(const unetk_lits3d_desc* d, const uint16_t* slices, const uint8_t* seg_slices,
+                                       const int32_t* sample_tab, const float* warp, int G, float* images, int32_t* labels,
+                                       void* ws, size_t ws_bytes, void* stream) {
+  UNETK_REQUIRE(warp && (((uintptr_t)warp) & 3u) == 0 && G >= 1 && G <= LITS_WARP_MAX_G);
+  return lits_patch3d<true>(d, slices, seg_slices, sample_tab, images, labels, ws, ws_bytes, stream, warp, G);
 }

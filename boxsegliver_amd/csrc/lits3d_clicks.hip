@@ -528,6 +528,59 @@ __global__ __launch_bounds__(256) void click_guide3d_kernel(unetk_lits3d_clicks_
   }
 }
 
+// WARP (unetk_click_guide3d_warp): ONLY the rows whose table column 15 is not zero, after the plain kernel
+// and the rotated rows' kernel have written every row (so the rows that are not deformed keep those kernels' bits).  The
+// guide is evaluated at the four unclamped corners of the coordinate p3d_warp_kernel (lits3d.hip) samples the slice at --
+// lits_warp_coord, the same float32 operations -- exactly as ROT evaluates it at the turned coordinate.  One thread per
+// voxel, as above: the spline is re-evaluated per slice (32 cached lattice reads beside up to 4 * 2 * MAXK expf), which keeps
+// the grid and the write order of click_guide3d_kernel.
+__global__ __launch_bounds__(256) void click_guide3d_warp_kernel(unetk_lits3d_clicks_desc d, const int32_t* __restrict__ tab,
+                                                                 const float* __restrict__ warp, int WG,
+                                                                 const int32_t* __restrict__ pts, const int32_t* __restrict__ cnt,
+                                                                 float* __restrict__ guide) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int area = d.H * d.W, vol = d.D * area;              // < 2^31: checked by the entry point
+  if (i >= (int64_t)d.N * vol) return;
+  const int n = (int)(i / vol), r = (int)(i - (int64_t)n * vol);
+  const int32_t* t = tab + (int64_t)n * TW;
+  if (t[15] == 0) return;                                    // the kernels before this one have written the row
+  const int z = r / area, q = r - z * area;
+  const int y = q / d.W, x = q - y * d.W;
+  const Box3 b = p3d_box(t, d);
+  const int cells = (WG + 3) * (WG + 3);
+  const float* lat = warp + (int64_t)n * 2 * cells;
+  const LitsSpline sy = lits_warp_spline(y, d.H, WG), sx = lits_warp_spline(x, d.W, WG);
+  const LitsRotAt at = lits_warp_coord(y, x, lits_warp_disp(lat, WG, sy, sx), lits_warp_disp(lat + cells, WG, sy, sx), b.ch, b.cw,
+                                       lits_ac_scale(b.ch, d.H), lits_ac_scale(b.cw, d.W), lits_rot_of(t));
+  const bool ok = at.ok;
+  const float fy0 = ok ? floorf(at.in_y) : 0.f, fx0 = ok ? floorf(at.in_x) : 0.f;
+  const int y0 = (int)fy0, x0 = (int)fx0;
+  const float fy = ok ? at.in_y - fy0 : 0.f, fx = ok ? at.in_x - fx0 : 0.f;
+  Guide3 g;
+  g.gaussian = d.gaussian != 0;
+  g.nz = 2.f * d.stddev[0] * d.stddev[0];
+  g.ny = 2.f * d.stddev[1] * d.stddev[1];
+  g.nx = 2.f * d.stddev[2] * d.stddev[2];
+  g.norm = d.euclid_norm;
+  float v[2];
+#pragma unroll
+  for (int kind = 0; kind < 2; ++kind) {
+    const int32_t* p = pts + ((int64_t)n * 2 + kind) * MAXK * 3;
+    const int k = min(max(cnt[(int64_t)n * 2 + kind], 0), MAXK);
+    const float tl = cg3_at(z, y0, x0, p, k, g), tr = cg3_at(z, y0, x0 + 1, p, k, g);
+    const float bl = cg3_at(z, y0 + 1, x0, p, k, g), br = cg3_at(z, y0 + 1, x0 + 1, p, k, g);
+    v[kind] = ok ? lits_bilerp(tl, tr, bl, br, fx, fy) : 0.f;
+  }
+  const int zo = t[9] != 0 ? d.D - 1 - z : z, yo = t[8] != 0 ? d.H - 1 - y : y, xo = t[7] != 0 ? d.W - 1 - x : x;
+  const int64_t o = (int64_t)n * vol + ((int64_t)zo * d.H + yo) * d.W + xo;
+  if (d.G == 2) {
+    guide[o * 2 + 0] = v[0];
+    guide[o * 2 + 1] = v[1];
+  } else {
+    guide[o] = v[0] - v[1];
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 bool clk3_valid(const unetk_lits3d_clicks_desc* d) {
   return d && d->N > 0 && d->N <= 65535 && d->D > 0 && d->H > 0 && d->W > 0 && d->n_slices > 0 && d->src_h > 0 && d->src_w > 0 &&
@@ -568,8 +621,9 @@ extern "C" int unetk_lits3d_clicks(const unetk_lits3d_clicks_desc* d, const uint
 namespace {
 // K == 0: unetk_click_guide3d (clicks per row, relative to its box), with rot unetk_click_guide3d_rot; else
 // unetk_click_guide3d_list
+// warp != nullptr (implies rot): unetk_click_guide3d_warp
 int click_guide3d_launch(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const int32_t* pts, const int32_t* cnt,
-                         int K, float* guide, void* stream, bool rot = false) {
+                         int K, float* guide, void* stream, bool rot = false, const float* warp = nullptr, int WG = 0) {
   UNETK_REQUIRE(d && d->N > 0 && d->D > 0 && d->H > 0 && d->W > 0 && d->src_h > 0 && d->src_w > 0 && sample_tab && pts && cnt &&
                 guide && (d->G == 1 || d->G == 2));
   UNETK_REQUIRE(((((uintptr_t)sample_tab) | ((uintptr_t)pts) | ((uintptr_t)cnt) | ((uintptr_t)guide)) & 3u) == 0);
@@ -588,6 +642,9 @@ int click_guide3d_launch(const unetk_lits3d_clicks_desc* d, const int32_t* sampl
   // of evaluating the rotated rows twice (the guide is the small part of a guided batch: DESIGN.md 7.3.9).
   if (rot)
     UNETK_LAUNCH((click_guide3d_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, *d, sample_tab, pts, cnt, 0, guide);
+  // and the deformed rows once more, for the same reason
+  if (warp)
+    UNETK_LAUNCH(click_guide3d_warp_kernel, grid, dim3(256), 0, (hipStream_t)stream, *d, sample_tab, warp, WG, pts, cnt, guide);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }
@@ -601,6 +658,12 @@ extern "C" int unetk_click_guide3d(const unetk_lits3d_clicks_desc* d, const int3
 extern "C" int unetk_click_guide3d_rot(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const int32_t* pts,
                                        const int32_t* cnt, float* guide, void* stream) {
   return click_guide3d_launch(d, sample_tab, pts, cnt, 0, guide, stream, true);
+}
+
+extern "C" int unetk_click_guide3d_warp(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const float* warp, int G,
+                                        const int32_t* pts, const int32_t* cnt, float* guide, void* stream) {
+  UNETK_REQUIRE(warp && (((uintptr_t)warp) & 3u) == 0 && G >= 1 && G <= LITS_WARP_MAX_G);
+  return click_guide3d_launch(d, sample_tab, pts, cnt, 0, guide, stream, true, warp, G);
 }
 
 extern "C" int unetk_click_guide3d_list(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const int32_t* pts,

@@ -29,6 +29,12 @@ angle per sample AFTER every other draw of the batch, writes its sin / cos into 
 go through `unetk_lits_patch3d_rot` and `unetk_click_guide3d_rot`; the restatement is tests/lits3d_rotate_ref.py.  Evaluation
 never rotates.
 
+With --random_deform PX (not a reference flag) training patches are deformed elastically in the plane: after
+the rotation draw the sampler draws, per sample, a coin and a lattice of (G + 3)^2 control displacements from U(-PX, PX) for
+each of dy and dx (--deform_grid G cells per axis, a uniform cubic B-spline).  Column 15 of the table marks the deformed rows,
+the lattices ride in the batch's one upload, and the batches go through `unetk_lits_patch3d_warp` and
+`unetk_click_guide3d_warp`, which serve rotation too; the restatement is tests/lits3d_deform_ref.py.  Evaluation never deforms.
+
 Offline, `input_fn_eval` tiles every case of the validation fold with windows cut as `eval_online` cuts them (window_starts,
 eval_tables) for the sliding-window evaluator, `EvaluateVolume.run_3d` (--eval_in_patches).  Two options
 of that evaluation live here too: the per-axis Gaussian window tables (window_weights, --eval_window_weight gaussian) and
@@ -58,6 +64,9 @@ STATUS_BITS = ((1, "unetk_lits_pick_voxel: a forced sample's rank was beyond the
 (COL_BASE, COL_DEPTH, COL_CZ, COL_CY, COL_CX, COL_CH, COL_CW, COL_FLIP_LR, COL_FLIP_UD, COL_FLIP_FB, COL_GAMMA, COL_FORCED,
  COL_K) = range(13)
 COL_SIN, COL_COS = 13, 14          # --random_rotate: float bits, both zero = not rotated
+COL_WARP = 15                      # --random_deform: 0 = not deformed, else the row's lattice applies
+DEFORM_MAX_GRID = 16               # the _warp entries' largest lattice: G + 3 <= 19 control points per axis
+DEFORM_FOLD_CAP = 0.4              # largest control displacement as a share of the control spacing (no folding: 7.3.10)
 
 
 def add_arguments(parser):
@@ -72,6 +81,13 @@ def add_arguments(parser):
                         help="--mode train: turn every patch in the plane by an angle from U(-DEG, DEG) degrees; 0 = off")
     parser.add_argument("--rotate_prob", type=float, default=1.0, metavar="P",
                         help="--random_rotate: the probability that a sample is rotated")
+    parser.add_argument("--random_deform", type=float, default=0.0, metavar="PX",
+                        help="--mode train: deform every patch in the plane by a smooth random field; PX = the largest "
+                             "displacement of a control point, in pixels of the patch; 0 = off")
+    parser.add_argument("--deform_grid", type=int, default=4, metavar="G",
+                        help="--random_deform: control cells across the patch on each in-plane axis, 1..16")
+    parser.add_argument("--deform_prob", type=float, default=1.0, metavar="P",
+                        help="--random_deform: the probability that a sample is deformed")
     parser.add_argument("--eval_window_weight", type=str, default="uniform", choices=WINDOW_WEIGHTS,
                         help="--eval_in_patches: how a window's voxels count in the average; gaussian weights its centre")
     parser.add_argument("--eval_window_sigma", type=float, default=0.125,
@@ -112,6 +128,7 @@ def check_values(args):
         raise ValueError("--eval_box_margin grows the box of --eval_box_from, which is not given")
     guide_stddev(args)
     rotation(args)
+    deformation(args)
     if int(getattr(args, "guide_channel", 2)) not in (1, 2):
         raise ValueError("--guide_channel must be 1 or 2, got {}".format(args.guide_channel))
 
@@ -124,6 +141,33 @@ def rotation(args):
     if not 0.0 <= prob <= 1.0:
         raise ValueError("--rotate_prob must satisfy 0 <= P <= 1, got {}".format(prob))
     return deg, prob
+
+
+def deform_cap(hw, grid):
+    """The largest --random_deform for an H x W patch and G cells: 0.4 of the control spacing (min(H, W) - 1) / G.  Both
+    displacement components of a cubic B-spline stay below their largest control value, so below 0.4 of the spacing -- under
+    the 2-D injectivity bound spacing / 2.046 of Choi & Lee (2000): the deformed patch does not fold."""
+    return DEFORM_FOLD_CAP * (min(int(hw[0]), int(hw[1])) - 1) / int(grid)
+
+
+def deformation(args):
+    """(--random_deform in pixels, --deform_grid, --deform_prob): PX finite and 0 <= PX <= deform_cap, 1 <= G <= 16 and
+    0 <= P <= 1."""
+    px = float(getattr(args, "random_deform", 0.0) or 0.0)
+    grid, prob = int(getattr(args, "deform_grid", 4)), float(getattr(args, "deform_prob", 1.0))
+    if not 0.0 <= px < float("inf"):                      # also refuses NaN
+        raise ValueError("--random_deform must be a finite number of pixels >= 0, got {}".format(px))
+    if not 1 <= grid <= DEFORM_MAX_GRID:
+        raise ValueError("--deform_grid must satisfy 1 <= G <= {}, got {}".format(DEFORM_MAX_GRID, grid))
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError("--deform_prob must satisfy 0 <= P <= 1, got {}".format(prob))
+    if px > 0.0:
+        cap = deform_cap((getattr(args, "im_height"), getattr(args, "im_width")), grid)
+        if px > cap:
+            raise ValueError("--random_deform {} would let the patch fold: with --deform_grid {} on a {} x {} patch the largest "
+                             "allowed value is {!r} (0.4 of the control spacing)".format(px, grid, args.im_height, args.im_width,
+                                                                                         cap))
+    return px, grid, prob
 
 
 def guide_stddev(args):
@@ -176,13 +220,19 @@ class PatchSampler(object):
       * training with random_rotate > 0 (not in the reference): a draw of its own, `draw_rotation`, made after
         all of the above (and after a guided run's click draws) -- a coin with probability rotate_prob and an angle from
         U(-random_rotate, random_rotate) degrees per sample.
+      * training with random_deform > 0 (not in the reference): `draw_deform`, made after `draw_rotation` --
+        a coin with probability deform_prob and 2 (G + 3)^2 control displacements from U(-random_deform, random_deform) per sample.
     A forced-class voxel is chosen WITHOUT a position table: `slice_counts` (forced-class pixels of every store slice, see
     forced_counts) is cumulated once; a rank below the case's total is drawn, searchsorted on the cumulative counts gives
     the slice z and the rank k inside it, and `unetk_lits_pick_voxel` turns (z, k) into (py, px) on the device."""
 
     def __init__(self, cases, offset, slice_counts, batch_size, shape, src_hw, tumor_percent=0.5, zoom_scale=(1.0, 1.25),
-                 random_flip=0, training=True, seed=None, random_rotate=0.0, rotate_prob=1.0):
+                 random_flip=0, training=True, seed=None, random_rotate=0.0, rotate_prob=1.0, random_deform=0.0, deform_grid=4,
+                 deform_prob=1.0):
         self.bs = int(batch_size)
+        self.deform = float(random_deform or 0.0) if training else 0.0      # pixels; > 0: draw_deform draws
+        self.deform_grid = int(deform_grid)
+        self.deform_prob = float(deform_prob)
         self.rotate = float(random_rotate or 0.0) if training else 0.0      # degrees; > 0: draw_rotation draws
         self.rotate_prob = float(rotate_prob)
         self.depth_out, self.h, self.w = (int(v) for v in shape)
@@ -250,13 +300,27 @@ class PatchSampler(object):
         on = self.rng.random(self.bs) < self.rotate_prob
         return dict(on=on, deg=self.rng.uniform(-self.rotate, self.rotate, self.bs))
 
-    def table(self, b=None, rot=None):
+    def draw_deform(self):
+        """The deformation draw of one batch, made only when --random_deform > 0 and AFTER `draw_rotation`
+        (so after every other draw of the batch): dict(on [bs] bool with probability deform_prob, ctl float32
+        [bs, 2, G + 3, G + 3] from U(-PX, PX), component 0 = dy and 1 = dx), or None."""
+        if not self.deform > 0.0:
+            return None
+        on = self.rng.random(self.bs) < self.deform_prob
+        g = self.deform_grid + 3
+        return dict(on=on, ctl=self.rng.uniform(-self.deform, self.deform, (self.bs, 2, g, g)).astype(np.float32))
+
+    def table(self, b=None, rot=None, warp=None):
         """The batch as `unetk_lits_patch3d` takes it: int32 [bs, 16] (include/unetk.h), gamma as float bits.  rot: what
         `draw_rotation` gave -- the `on` rows get sin / cos (float64, cast to float32; float bits) in columns 13 / 14 for
-        `unetk_lits_patch3d_rot`, every other row keeps zeros there.  Without b the sampler draws both."""
+        `unetk_lits_patch3d_rot`, every other row keeps zeros there.  warp: what `draw_deform` gave -- the `on` rows get 1 in
+        column 15 for `unetk_lits_patch3d_warp`, which takes warp["ctl"] beside the table.  Without b the sampler draws the
+        batch and the rotation (a deformation comes with its lattices, so its draw is the caller's)."""
         if b is None:
             b, rot = self.draw(), self.draw_rotation()
         tab = np.zeros((self.bs, _abi.LITS3D_TAB_COLS), dtype=np.int32)
+        if warp is not None:
+            tab[:, COL_WARP] = np.asarray(warp["on"], dtype=bool)
         if rot is not None:
             rad = np.deg2rad(np.asarray(rot["deg"], dtype=np.float64))
             on = np.asarray(rot["on"], dtype=bool)
@@ -296,22 +360,27 @@ def batches(store, sampler, shape, lab_max, fg_label, status=None, guide=None):
         status = torch.zeros(1, dtype=torch.int32, device=store.device)
     while True:
         b = sampler.draw()
-        if guide is None:
-            (tab,) = lits.upload_pinned([sampler.table(b, sampler.draw_rotation())], store.device)
-        else:
+        parts = []
+        if guide is not None:
             from . import lits_inter
-            clicks = lits_inter.draw_click_tab(sampler.rng, sampler.bs, CLICKS[3])
-            tab, ctab = lits.upload_pinned([sampler.table(b, sampler.draw_rotation()), clicks.view(np.int32)], store.device)
+            parts.append(lits_inter.draw_click_tab(sampler.rng, sampler.bs, CLICKS[3]).view(np.int32))
+        rot = sampler.draw_rotation()
+        deform = sampler.draw_deform()                       # --random_deform: the last draw; the lattices ride in the same upload
+        if deform is not None:
+            parts.append(deform["ctl"].view(np.int32))
+        dev = lits.upload_pinned([sampler.table(b, rot, deform)] + parts, store.device)
+        tab, ctab = dev[0], dev[1] if guide is not None else None
+        warp, grid = (dev[-1].view(torch.float32), sampler.deform_grid) if deform is not None else (None, 0)
         if sampler.force:
             ops.lits_pick_voxels(store.lb, tab, fg_label, status, lits.LB_SCALE)
         rotate = sampler.rotate > 0.0                        # --random_rotate: the _rot entries, which read the table's (sin, cos)
         images, labels = ops.lits_patch3d(store.im, store.lb, tab, shape, sampler.training, lab_max, lits.IM_SCALE, lits.LB_SCALE,
-                                          rotate=rotate)
+                                          rotate=rotate, warp=warp, grid=grid)
         feats = {"images": images, "names": torch.from_numpy(b["pid"])}
         if guide is not None:
             pts, cnt = ops.lits3d_clicks(store.lb, tab, ctab, shape, status, fg_label, CLICKS, lits.LB_SCALE)
             feats["sp_guide"] = ops.click_guide3d(tab, pts, cnt, shape, store.im.shape[1:], guide["channels"], guide["stddev"],
-                                                  rotate=rotate)
+                                                  rotate=rotate, warp=warp, grid=grid)
         yield feats, labels
 
 
@@ -354,10 +423,11 @@ def input_fn(mode, params):
     training = mode == "train"
     seed = base_seed + 1000 * int(params.get("rank", 0)) if training else base_seed + 500
     deg, prob = rotation(args)                             # only `train` rotates: the sampler drops it for eval_online
+    px, grid, dprob = deformation(args)                    # likewise
     sampler = PatchSampler(cases, store.offset, params[ckey], bs, shape, store.im.shape[1:],
                            tumor_percent=getattr(args, "tumor_percent", 0.5), zoom_scale=getattr(args, "zoom_scale", (1., 1.25)),
                            random_flip=getattr(args, "random_flip", 0), training=training, seed=seed, random_rotate=deg,
-                           rotate_prob=prob)
+                           rotate_prob=prob, random_deform=px, deform_grid=grid, deform_prob=dprob)
     # the pick kernel's status words live in `params` (one per mode) so that they outlast the generators: params[("lits3d_status",
     # True)] is the training stream's.  An evaluation synchronises anyway, so both are read there: the training word when
     # the evaluation starts, the evaluation's own after its last batch.

@@ -1589,12 +1589,28 @@ def lits3d_desc(slices, n, shape, training, lab_max=2, im_scale=64, lab_scale=64
                            int(lab_max), 1 if training else 0)
 
 
-def lits_patch3d(slices, seg_slices, sample_tab, shape, training, lab_max=2, im_scale=64, lab_scale=64, rotate=False):
+def _warp_lattice(warp, grid, n, device):
+    """The checks of a `warp=` argument: f32 [n, 2, G + 3, G + 3] on the table's device, 1 <= G <= 16 -> G."""
+    g = int(grid)
+    if not 1 <= g <= 16:
+        raise ValueError("grid must satisfy 1 <= G <= 16, got {}".format(grid))
+    _require_cuda(warp)
+    assert warp.dtype == torch.float32 and tuple(warp.shape) == (n, 2, g + 3, g + 3) and warp.is_contiguous(), \
+        (warp.dtype, tuple(warp.shape), (n, 2, g + 3, g + 3))
+    assert warp.device == device
+    return g
+
+
+def lits_patch3d(slices, seg_slices, sample_tab, shape, training, lab_max=2, im_scale=64, lab_scale=64, rotate=False, warp=None,
+                 grid=0):
     """One UNet3D batch from the device-resident slice store (unetk_lits_patch3d; include/unetk.h has the table layout):
     slices uint16 / seg_slices uint8 [n, src_h, src_w] (stored as int16 / uint8 tensors), sample_tab int32 [N, 16],
     shape = (D, H, W).  Returns images f32 [N, D, H, W, 1], labels int32 [N, D, H, W].  training: gamma augmentation with
     the table's per-sample gamma.  rotate: unetk_lits_patch3d_rot, which turns the rows whose columns 13 / 14 hold (sin, cos)
-    in the plane; without it the columns are ignored.  Current stream; no host synchronisation."""
+    in the plane; without it the columns are ignored.  warp f32 [N, 2, grid + 3, grid + 3]:
+    unetk_lits_patch3d_warp, which also deforms the rows whose column 15 is not zero by their B-spline lattice of `grid` cells
+    per axis and reads the rotation columns whatever `rotate` says.  Current stream; no host
+    synchronisation."""
     _require_cuda(slices, seg_slices, sample_tab)
     assert slices.dtype in (torch.int16, torch.uint16) and seg_slices.dtype == torch.uint8
     assert slices.is_contiguous() and seg_slices.is_contiguous() and slices.shape == seg_slices.shape and slices.dim() == 3
@@ -1611,10 +1627,11 @@ def lits_patch3d(slices, seg_slices, sample_tab, shape, training, lab_max=2, im_
     labels = torch.empty((n, desc.D, desc.H, desc.W), dtype=torch.int32, device=slices.device)
     # algorithmic bytes: the image written once (training: + the two gamma passes' read and write) and the labels; the crop
     # reads depend on the table's zoom and are left out
-    name = "lits_patch3d_rot" if rotate else "lits_patch3d"
+    name = "lits_patch3d_warp" if warp is not None else "lits_patch3d_rot" if rotate else "lits_patch3d"
+    lattice = () if warp is None else (ptr(warp), _warp_lattice(warp, grid, n, sample_tab.device))
     with _timed_hbm(name, images, 5 if training else 1, labels.numel() * 4):
-        check(getattr(_abi.lib(), "unetk_" + name)(ctypes.byref(desc), ptr(slices), ptr(seg_slices), ptr(sample_tab), ptr(images),
-                                                   ptr(labels), ptr(ws), nbytes, stream_ptr()), name)
+        check(getattr(_abi.lib(), "unetk_" + name)(ctypes.byref(desc), ptr(slices), ptr(seg_slices), ptr(sample_tab), *lattice,
+                                                   ptr(images), ptr(labels), ptr(ws), nbytes, stream_ptr()), name)
     return images, labels
 
 
@@ -1641,6 +1658,9 @@ def _eval3d_accumulate_args(name, probs, sample_tab, shape, case_base, case_dept
         if bool((rows[:, 13:15] != 0).any()):
             raise ValueError("{}: a row carries a rotation (columns 13 / 14 of the table): a rotated window cannot be "
                              "accumulated back into its case".format(name))
+        if bool((rows[:, 15] != 0).any()):
+            raise ValueError("{}: a row is deformed (column 15 of the table): a deformed window cannot be accumulated back "
+                             "into its case".format(name))
     desc = lits3d_desc(slices, n, shape, False)
     cbox = (ctypes.c_int32 * 6)(*(int(v) for v in box))
     return desc, c, cbox, (cbox[1] - cbox[0]) * (cbox[3] - cbox[2]) * (cbox[5] - cbox[4])
@@ -1912,20 +1932,23 @@ def _click_guide3d_args(sample_tab, n, shape, src_hw, guide_channel, stddev, euc
     return desc, torch.empty((n, d, h, w, int(guide_channel)), dtype=torch.float32, device=sample_tab.device)
 
 
-def click_guide3d(sample_tab, pts, cnt, shape, src_hw, guide_channel=2, stddev=None, euclid_norm=None, rotate=False):
+def click_guide3d(sample_tab, pts, cnt, shape, src_hw, guide_channel=2, stddev=None, euclid_norm=None, rotate=False, warp=None,
+                  grid=0):
     """sp_guide f32 [N, D, H, W, guide_channel] from 3-D clicks (unetk_click_guide3d): pts int32 [N, 2, 4, 3], cnt int32 [N, 2],
     in the crop boxes and under the three flips of sample_tab; shape = (D, H, W).  stddev None: the Euclidean distance to the
     nearest click divided by euclid_norm (default: float32(H * sqrt(2) * 0.8), input_pipeline_3d.py:372); (s_z, s_y, s_x):
     the Gaussian of --local_enhance.  guide_channel 2: (fg, bg); 1: fg - bg.  rotate: unetk_click_guide3d_rot, the guide of
-    the patches `lits_patch3d(..., rotate=True)` cuts.  Current stream."""
+    the patches `lits_patch3d(..., rotate=True)` cuts.  warp, grid: unetk_click_guide3d_warp, the guide of
+    the patches `lits_patch3d(..., warp=warp, grid=grid)` cuts.  Current stream."""
     _require_cuda(sample_tab, pts, cnt)
     n = _inter_tab(sample_tab)
     assert pts.dtype == torch.int32 and tuple(pts.shape) == (n, 2, _abi.LITS_MAX_CLICKS, 3) and pts.is_contiguous()
     assert cnt.dtype == torch.int32 and tuple(cnt.shape) == (n, 2) and cnt.is_contiguous()
     desc, guide = _click_guide3d_args(sample_tab, n, shape, src_hw, guide_channel, stddev, euclid_norm)
-    name = "click_guide3d_rot" if rotate else "click_guide3d"
+    name = "click_guide3d_warp" if warp is not None else "click_guide3d_rot" if rotate else "click_guide3d"
+    lattice = () if warp is None else (ptr(warp), _warp_lattice(warp, grid, n, sample_tab.device))
     with _timed_hbm(name, guide, 1):
-        check(getattr(_abi.lib(), "unetk_" + name)(ctypes.byref(desc), ptr(sample_tab), ptr(pts), ptr(cnt), ptr(guide),
+        check(getattr(_abi.lib(), "unetk_" + name)(ctypes.byref(desc), ptr(sample_tab), *lattice, ptr(pts), ptr(cnt), ptr(guide),
                                                    stream_ptr()), name)
     return guide
 

@@ -743,8 +743,8 @@ int unetk_lits_context(float* table, int64_t n_rows, int F, const int32_t* sampl
  *   2 cz     centre slice (within the case)              10 gamma (float bits; training only)
  *   3 cy     centre row                                  11 forced: 1 = (cy, cx) come from unetk_lits_pick_voxel
  *   4 cx     centre column                               12 k: rank of the forced-class pixel in slice cz
- *   5 ch     crop rows    = int32(H * zoom_y)            13, 14 sin, cos (float bits): read by the _rot entries only
- *   6 cw     crop columns = int32(W * zoom_x)            15 reserved (0)
+ *   5 ch     crop rows    = int32(H * zoom_y)            13, 14 sin, cos (float bits): read by the _rot / _warp entries only
+ *   6 cw     crop columns = int32(W * zoom_x)            15 warp: != 0 = deformed; read by the _warp entries only
  *   7 flip_left_right
  *
  * unetk_lits_pick_voxel: for every row with forced != 0, (cy, cx) <- the k-th pixel, in row-major order, of slice
@@ -799,6 +799,29 @@ int unetk_lits_patch3d(const unetk_lits3d_desc* d, const uint16_t* slices, const
  * read out of bounds for any table content.  Same arguments, checks, error codes and workspace query. */
 int unetk_lits_patch3d_rot(const unetk_lits3d_desc* d, const uint16_t* slices, const uint8_t* seg_slices,
                            const int32_t* sample_tab, float* images, int32_t* labels, void* ws, size_t ws_bytes, void* stream);
+
+/* Elastically deformed patches (additive to ABI 10).  unetk_lits_patch3d_rot with one more table column and
+ * one more input:
+ *   15 warp: 0 = the row is not deformed; anything else = it is, by its lattice;
+ *   warp f32 [N][2][G + 3][G + 3]: per row the control displacements (0 = dy, 1 = dx, in pixels of the OUTPUT patch) of a
+ *     uniform cubic B-spline with G x G cells across the patch, 1 <= G <= 16.  Rows with column 15 == 0 never read theirs.
+ * A row with column 15 == 0 gives the output of unetk_lits_patch3d_rot bit for bit (and so, with columns 13 / 14 zero too, that of
+ * unetk_lits_patch3d).  A deformed row, rotated or not -- all float32, EVERY operation rounded on its own:
+ *   gy = H > 1 ? (float)G / (float)(H - 1) : 0;  t = y gy;  i = min((int)floor(t), G - 1);  f = t - i   (x: W, j, fx)
+ *   g = 1 - f;  k6 = 1.f / 6.f
+ *   w0 = ((g g) g) k6                               w1 = ((((3 f) - 6) f) f + 4) k6
+ *   w2 = (((((-3 f) + 3) f + 3) f) + 1) k6          w3 = ((f f) f) k6
+ *   dy = sum_a wy[a] (sum_b wx[b] warp[n][0][i + a][j + b]),  dx likewise from warp[n][1]; both sums left to right from term 0
+ *   y' = y + dy,  x' = x + dx                       (the field is the same for every slice)
+ *   not rotated: in_y = y' hs, in_x = x' ws;   rotated: u = y' hs - cy0, v = x' ws - cx0 and the sums of unetk_lits_patch3d_rot.
+ * Everything else is the rotated row of unetk_lits_patch3d_rot: unclamped second tap, taps and label read from the SLICE and 0
+ * outside it, labels roundf, m and s of the axis-aligned crop, gamma on the result, flips the write address, a coordinate that
+ * is not finite or >= 2^24 in magnitude image 0 and label 0.  Nothing is read out of bounds for any table or lattice content.
+ * warp NULL or misaligned, G outside [1, 16]: UNETK_E_BADARG.  Otherwise the arguments, checks, error codes and workspace query
+ * of unetk_lits_patch3d_rot. */
+int unetk_lits_patch3d_warp(const unetk_lits3d_desc* d, const uint16_t* slices, const uint8_t* seg_slices,
+                            const int32_t* sample_tab, const float* warp, int G, float* images, int32_t* labels,
+                            void* ws, size_t ws_bytes, void* stream);
 
 /* Whole-volume evaluation in windows.  probs f32 [N,D,H,W,C]: the class probabilities of the N windows that
  * unetk_lits_patch3d(training = 0) cut for sample_tab (same desc, same table, flips included).  acc f32 [depth,src_h,src_w,C],
@@ -1027,6 +1050,16 @@ int unetk_click_guide3d(const unetk_lits3d_clicks_desc* d, const int32_t* sample
  * kind without clicks is exactly 0.  Same arguments, checks and error codes. */
 int unetk_click_guide3d_rot(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const int32_t* pts, const int32_t* cnt,
                             float* guide, void* stream);
+
+/* The guide of elastically deformed patches (additive to ABI 10): unetk_click_guide3d_rot that reads column 15
+ * of the table and the lattices warp f32 [N][2][G + 3][G + 3] as unetk_lits_patch3d_warp does.  The clicks stay what
+ * unetk_lits3d_clicks simulates on the UNDEFORMED label crop.  A row with column 15 == 0 gives the output of
+ * unetk_click_guide3d_rot bit for bit.  A deformed row evaluates the guide at the four unclamped corners of the in_y, in_x of
+ * unetk_lits_patch3d_warp (same float32 operations) and lerps them as unetk_click_guide3d_rot does; an invalid coordinate
+ * gives 0.  warp NULL or misaligned, G (the lattice's; the descriptor's G is the guide's channels) outside [1, 16]:
+ * UNETK_E_BADARG.  Otherwise the arguments, checks and error codes of unetk_click_guide3d_rot. */
+int unetk_click_guide3d_warp(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const float* warp, int G,
+                             const int32_t* pts, const int32_t* cnt, float* guide, void* stream);
 
 /* ---------------------------------------------------------------- 3-D interactive evaluation: corrective clicks  
  * The click step of the reference's entry/main_eval_3d.py (:152-185 inter_simulation_test) for ONE case, and the guide of the
