@@ -531,6 +531,15 @@ CONV3D_ROWS = [
     # The workspace query has to size the slabs of the launches that run, not of a launch over every plane.
     ("first_layer_resplit", (1, 8, 96, 96, 1, 32, 3, 1, 1), 0, 0, None, ("conv3x3_direct_kernel<1, float>",), None,
      ("conv3x3_wgrad_c3_kernel<32>",)),
+    # the input gradient's fallback for dy planes the four-class kernel refuses (the end of unetk_conv3d_dgrad): dy zero-dilated
+    # into the workspace, dx zeroed, one accumulating stride-1 launch per depth tap -- dy planes 8 x 80, 4 x 112 and 2 x 1
+    ("dgrad_dilated_w80", (1, 2, 16, 160, 32, 64, 1, 1, 2), 32, 64, None, (IGEMM + "4, 1, 1, 2, 2, 1, 0>",),
+     ("dilate2_kernel", IGEMM + "4, 1, 2, 1, 1, 1, 0>"), (WG_S2,)),
+    ("dgrad_dilated_w112_kd3", (1, 3, 8, 224, 64, 64, 3, 1, 2), 0, 0, None, (IGEMM + "4, 1, 1, 2, 2, 1, 0>",),
+     ("dilate2_kernel", IGEMM + "4, 1, 1, 2, 1, 1, 1>"), (WG_S2,)),
+    ("dgrad_dilated_2x1_sd2", (1, 4, 4, 2, 64, 64, 3, 2, 2), 32, 0, None, (IGEMM + "4, 1, 1, 2, 2, 1, 0>",),
+     ("dilate2_kernel", "zero_slice_kernel", LIN + "4, 1, 1, 2, false, false, false, true, false, false>",
+      IGEMM + "4, 1, 1, 2, 1, 1, 1>"), (WG_S2,)),
 ]
 
 

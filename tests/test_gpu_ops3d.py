@@ -45,6 +45,12 @@ CASES = [
     # D = 1: depth taps 0 and 2 have no input plane (forward / input gradient: the middle tap alone; dw[0] = dw[2] = 0)
     (1, 1, 8, 16, 64, 64, 3, (1, 1, 1)),       # one filter-gradient tile: one split, dw written in place
     (3, 1, 6, 6, 64, 64, 3, (1, 1, 1)),        # three one-plane samples side by side, stacked-plane filter gradient
+    # stride-2 input gradient on dy planes the four-class linear-pixel kernel refuses (unetk_conv_lin_gen_ok: the padded rows
+    # of a pixel block pass its LDS bound): dy zero-dilated into the workspace, dx zeroed, one accumulating stride-1 launch
+    # per depth tap onto depth-strided dx planes (the end of unetk_conv3d_dgrad)
+    (1, 2, 16, 160, 32, 64, 1, (1, 2, 2)),     # dy 8 x 80: the first stride-2 layer of a 12 x 160 x 160 patch
+    (1, 3, 8, 224, 64, 64, 3, (1, 2, 2)),      # dy 4 x 112: 224-wide patches, three depth taps
+    (1, 4, 4, 2, 64, 64, 3, (2, 2, 2)),        # dy 2 x 1: a plane narrower than any tile, depth stride 2
 ]
 
 
@@ -255,6 +261,15 @@ EXACT_TRACES = {
     13: (['conv3x3_igemm_kernel<4,1,1,2,1,1,1>'],
         ['conv3x3_igemm_kernel<4,1,1,2,1,1,1>'],
         ['conv3x3_wgrad_kernel<64,64,false,20,6,true,1,1>', 'slab_reduce_kernel<1>']),
+    14: (['conv3x3_igemm_kernel<4,1,1,2,2,1,0>'],
+        ['dilate2_kernel', 'conv3x3_igemm_kernel<4,1,2,1,1,1,0>'],
+        ['conv3x3_wgrad_kernel<32,64,false,4,16,false,2,1>', 'slab_reduce_kernel<4>']),
+    15: (['conv3x3_igemm_kernel<4,1,1,2,2,1,0>'],
+        ['dilate2_kernel', 'conv3x3_igemm_kernel<4,1,1,2,1,1,1>', 'conv3x3_igemm_kernel<4,1,1,2,1,1,1>', 'conv3x3_igemm_kernel<4,1,1,2,1,1,1>'],
+        ['conv3x3_wgrad_kernel<32,64,false,4,16,false,2,1>', 'slab_reduce_kernel<4>']),
+    16: (['conv3x3_igemm_kernel<4,1,1,2,2,1,0>'],
+        ['dilate2_kernel', 'conv3x3_igemm_lin_kernel<4,1,1,2,false,false,false,true,false,false>', 'conv3x3_igemm_lin_kernel<4,1,1,2,false,false,false,true,false,false>', 'conv3x3_igemm_kernel<4,1,1,2,1,1,1>'],
+        ['conv3x3_wgrad_kernel<32,64,false,4,16,false,2,1>', 'slab_reduce_kernel<1>']),
 }
 EXACT_LIVE_TRACES = {
     0: (['conv3x3_igemm_lin_kernel<2,2,2,2,false,false,true,false,false,false>', 'lin_sk_fixup_kernel<128,128>'],
