@@ -124,6 +124,11 @@ _SIGNATURES = {
     "unetk_click_guide": (c_int, [POINTER(LitsInterDesc), P, P, P, P, P]),
     "unetk_click_guide_list": (c_int, [POINTER(LitsInterDesc), P, P, P, c_int, P, P]),
     "unetk_inter_click_ws_bytes": (c_size_t, [POINTER(InterClickDesc)]),
+    "unetk_lits_inter_center_ws_bytes": (c_size_t, [POINTER(LitsInterDesc)]),
+    "unetk_lits_inter_center": (c_int, [POINTER(LitsInterDesc), P, P, P, P, P, c_size_t, P]),
+    "unetk_click_geodesic_path": (c_int, [POINTER(LitsInterDesc)]),
+    "unetk_click_geodesic_ws_bytes": (c_size_t, [POINTER(LitsInterDesc)]),
+    "unetk_click_geodesic": (c_int, [POINTER(LitsInterDesc), P, P, P, P, c_int, P, P, P, P, c_size_t, P]),
     "unetk_inter_click": (c_int, [POINTER(InterClickDesc), P, P, P, P, P, P, P, P, c_size_t, P]),
     "unetk_lits3d_clicks_ws_bytes": (c_size_t, [POINTER(Lits3dClicksDesc)]),
     "unetk_lits3d_clicks": (c_int, [POINTER(Lits3dClicksDesc), P, P, P, P, P, P, P, c_size_t, P]),

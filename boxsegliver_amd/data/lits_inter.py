@@ -9,7 +9,13 @@ pipeline for them.  The semantics here are that pipeline's, the volumes are the 
   * :435-527 `data_processing`, DataLoader/misc.py:108-129 `img_crop` -> `unetk_lits_inter_batch` (csrc/lits_inter.hip);
   * :346-412 `inter_simulation` as :530-561 `gen_kernel` calls it (a pool of host processes in the reference) ->
     `unetk_lits_clicks`, from per-sample draws made here (`draw_click_tab`);
-  * utils/image_ops.py:396-434 `create_spatial_guide_2d` + the resize -> `unetk_click_guide`.
+  * utils/image_ops.py:396-434 `create_spatial_guide_2d` + the resize -> `unetk_click_guide`;
+  * :471-496 the geodesic guide -> `--geodesic_guide`: `unetk_lits_inter_center` (the half-resolution centre channel) and
+    `unetk_click_geodesic` (csrc/lits_geodesic.hip), one workgroup per (sample, kind) relaxing to convergence in one launch.
+    The reference grows it with GeodisTK on the host; here the distance is builder-defined (include/unetk.h, DESIGN.md 7.3.7.1:
+    the float32 shortest path on the 8-connected grid, restated in tests/lits_geodesic_ref.py), so it has a flag of its own
+    and `--geodesic`, which promises GeodisTK's numbers, stays refused.  It needs --use_spatial; --local_enhance and --stddev
+    are ignored under it, as the reference ignores them under --geodesic (:447, :471).
 TensorFlow does not run here: the arithmetic is pinned by the restatement in tests/lits_inter_ref.py, which cites the same
 lines and uses scipy's `binary_erosion` literally ("parity unpinned").
 
@@ -19,7 +25,7 @@ batch path reads from the device.  The kernels' status word is read where an eva
 The nets are binary, as on NF: `--classes Liver` makes the object stored label >= 1 (tumour counting as liver),
 `--classes Tumor` stored label >= 2; labels are {0, 1} and the sampler's forced class is the object.
 
-Not built: --geodesic (GeodisTK), --fp_sample / --sample_neg (false-positive caches of earlier runs), --downsampling,
+Not built: --geodesic (GeodisTK's own numbers; see --geodesic_guide), --fp_sample / --sample_neg (false-positive caches of earlier runs), --downsampling,
 --use_context, and --mode eval / infer of this sub-command (evaluators/evaluator_nf.py).  The click-guided nets are scored
 offline by entry/main_eval.py, the reference's own script for it.
 Deviations: a crop that is all object gives no background click (the reference fails converting NaN), and a crop without a
@@ -36,7 +42,8 @@ OBJECT_LABEL = {("Liver",): 1, ("Tumor",): 2}
 MAX_CHANNELS = 7
 STATUS_BITS = ((1, "a forced sample's rank was beyond the object count of its slice (the per-slice counts do not match the store)"),
                (2, "a sample's centre slice lay outside its case"),
-               (4, "a row of click draws was out of range"))
+               (4, "a row of click draws was out of range"),
+               (8, "a geodesic guide reached its sweep bound before it converged"))
 
 
 def add_arguments(parser):
@@ -45,6 +52,9 @@ def add_arguments(parser):
     flagsets.add_arguments(parser, "liver_inter")
     parser.add_argument("--lits_root", type=str, default="data/LiTS", help="where png/, meta.json and k_folds.txt live")
     parser.add_argument("--seed", type=int, default=1234)
+    parser.add_argument("--geodesic_guide", action="store_true",
+                        help="With --use_spatial: the guide is the geodesic distance from the clicks through the half-resolution "
+                             "centre channel (this project's float32 shortest-path definition, not GeodisTK's)")
 
 
 def object_label(classes):
@@ -58,7 +68,8 @@ def object_label(classes):
 def refuse_unbuilt_flags(args):
     """Refuses the flags of the `liver_inter` group that are not built, naming the flag (training and entry.main_eval)."""
     if getattr(args, "geodesic", False):
-        raise NotImplementedError("--geodesic is not built: the geodesic guide needs GeodisTK, which is not available")
+        raise NotImplementedError("--geodesic is not built: the geodesic guide needs GeodisTK, which is not available; see --geodesic_guide "
+                                  "for this project's own definition of it")
     if getattr(args, "fp_sample", False):
         raise NotImplementedError("--fp_sample is not built: it samples clicks from the false positives of an earlier run's predictions")
     if float(getattr(args, "sample_neg", 0.) or 0.) > 0:
@@ -80,6 +91,8 @@ def check_values(args):
         raise ValueError("--stddev must be > 0, got {}".format(args.stddev))
     if float(getattr(args, "noise_scale", 0.)) < 0:
         raise ValueError("--noise_scale must be >= 0, got {}".format(args.noise_scale))
+    if getattr(args, "geodesic_guide", False) and not getattr(args, "use_spatial", False):
+        raise ValueError("--geodesic_guide needs --use_spatial: it chooses the kind of guide the clicks are rendered into")
     return object_label(args.classes)
 
 
@@ -118,7 +131,8 @@ def batches(store, sampler, args, obj_label, status=None):
     """(features, labels) device batches for ever: features["images"] f32 [bs, H, W, C], features["names"] the case ids,
     with --use_spatial features["sp_guide"] f32 [bs, H, W, guide_channel]; labels int32 [bs, H, W] in {0, 1}.  Per batch:
     one sampler draw, one pinned upload, then `unetk_lits_pick_voxel`, `unetk_lits_inter_batch`, `unetk_lits_clicks` and
-    `unetk_click_guide` on the current stream -- no host synchronisation.  status: int32 [1] device word, NOT read here."""
+    `unetk_click_guide` -- under --geodesic_guide `unetk_lits_inter_center` and `unetk_click_geodesic` in its place -- on the
+    current stream: no host synchronisation.  status: int32 [1] device word, NOT read here."""
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=store.device)
     shape = (sampler.depth_out, sampler.h, sampler.w)
@@ -126,6 +140,7 @@ def batches(store, sampler, args, obj_label, status=None):
     spatial = bool(getattr(args, "use_spatial", False))
     stddev = float(getattr(args, "stddev", 3.)) if getattr(args, "local_enhance", False) else None
     channels = int(getattr(args, "guide_channel", 2))
+    geodesic = spatial and bool(getattr(args, "geodesic_guide", False))
     while True:
         b = sampler.draw()
         clicks = draw_click_tab(sampler.rng, sampler.bs)
@@ -138,7 +153,12 @@ def batches(store, sampler, args, obj_label, status=None):
         feats = {"images": images, "names": torch.from_numpy(b["pid"])}
         if spatial:
             pts, cnt = ops.lits_clicks(store.lb, tab, ctab, status, obj_label, CLICKS, lits.LB_SCALE)
-            feats["sp_guide"] = ops.click_guide(tab, pts, cnt, shape[1:], store.im.shape[1:], channels, stddev)
+            if geodesic:
+                base = ops.lits_inter_center(store.im, tab, shape, status, lits.IM_SCALE)
+                feats["sp_guide"] = ops.click_geodesic(tab, base, pts, cnt, shape[1:], channels, status=status,
+                                                       src_hw=store.im.shape[1:])
+            else:
+                feats["sp_guide"] = ops.click_guide(tab, pts, cnt, shape[1:], store.im.shape[1:], channels, stddev)
         yield feats, labels
 
 

@@ -11,7 +11,8 @@ finished sessions are refilled from the next slices of the same case.  One ROUND
   unetk_inter_click      the prediction of the last forward at source resolution into the case's volume, its counts against
                          the label, and the next click at the centre of the largest error region (inter_simulation_test)
   ONE host read          the int32 [batch, 16] table: the float64 Dice, the stop decisions and the slot refill happen here
-  unetk_click_guide_list the guide from all clicks so far (update_guide's running max / min)
+  unetk_click_guide_list the guide from all clicks so far (update_guide's running max / min); under --geodesic_guide
+                         unetk_click_geodesic on the half-resolution centre channel, computed once per fresh table (:205-220)
   the net                with mirror averaging (run_TTA), arg-max
 Per session the order is the reference's (:335-358): click -- stop if it repeats the previous one -- guide, forward -- Dice --
 stop if Dice > --inter_thresh or fg + bg clicks >= --max_iter.  The Dice of a forward is read together with the next click,
@@ -225,10 +226,11 @@ class NetPredictor(object):
         self.spatial = bool(getattr(args, "use_spatial", False))
         self.stddev = float(getattr(args, "stddev", 3.)) if getattr(args, "local_enhance", False) else None
         self.channels = int(getattr(args, "guide_channel", 2))
+        self.geodesic = self.spatial and bool(getattr(args, "geodesic_guide", False))
         self.plan = mirror_plan(args)
         self.status = torch.zeros(1, dtype=torch.int32, device=store.device)
         self.case = None                                                          # (base, depth) of the case being scored
-        self.tab = self.images = None
+        self.tab = self.images = self.base = None
 
     def forward(self, feats):
         self.model(feats, ModeKeys.EVAL, *self.model_args, **self.kwargs)
@@ -264,8 +266,13 @@ class NetPredictor(object):
             self.tab, = lits.upload_pinned([tab], self.store.device)
             self.images, _ = ops.lits_inter_batch(self.store.im, self.store.lb, self.tab, self.shape, False, self.status,
                                                   self.obj_label, 0.0, 0, lits.IM_SCALE, lits.LB_SCALE)
+            if self.geodesic:
+                self.base = ops.lits_inter_center(self.store.im, self.tab, self.shape, self.status, lits.IM_SCALE)
         feats = {"images": self.images}
-        if self.spatial:
+        if self.geodesic:
+            feats["sp_guide"] = ops.click_geodesic(self.tab, self.base, pts, cnt, self.shape[1:], self.channels, status=self.status,
+                                                   src_hw=(src_h, src_w))
+        elif self.spatial:
             feats["sp_guide"] = ops.click_guide_list(self.tab, pts, cnt, self.shape[1:], (src_h, src_w), self.channels, self.stddev)
         prob = self.probability(feats)
         amax, _ = ops.head_predict(prob.contiguous(), prob.shape[-1], want_preds=False)

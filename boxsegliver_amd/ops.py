@@ -1830,6 +1830,78 @@ def click_guide_list(sample_tab, pts, cnt, out_hw, src_hw, guide_channel=2, stdd
     return guide
 
 
+def lits_inter_center(slices, sample_tab, shape, status, im_scale=64):
+    """The base field of the geodesic guide (unetk_lits_inter_center): f32 [N, (H + 1) // 2, (W + 1) // 2], the value
+    lits_inter_batch(training=False) writes at [:, ::2, ::2, C // 2] with the table's flips ignored, bit for bit.  shape = (C, H,
+    W); status collects bit 1; it is NOT read here.  Current stream."""
+    _require_cuda(slices, sample_tab, status)
+    assert slices.dtype in (torch.int16, torch.uint16) and slices.is_contiguous() and slices.dim() == 3
+    assert status.dtype == torch.int32 and status.numel() >= 1
+    n = _inter_tab(sample_tab)
+    desc = lits_inter_desc(slices, n, shape, im_scale=im_scale)
+    nbytes = int(_abi.lib().unetk_lits_inter_center_ws_bytes(ctypes.byref(desc)))
+    if nbytes == 0:
+        raise _abi.UnetkError("lits_inter_center: unsupported shape {} (C odd, <= 7) from {} x {} slices".format(
+            tuple(shape), slices.shape[1], slices.shape[2]))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=slices.device)
+    base = torch.empty((n, (desc.H + 1) // 2, (desc.W + 1) // 2), dtype=torch.float32, device=slices.device)
+    with _timed_hbm("lits_inter_center", base, 1):
+        check(_abi.lib().unetk_lits_inter_center(ctypes.byref(desc), ptr(slices), ptr(sample_tab), ptr(base), ptr(status), ptr(ws),
+                                                 nbytes, stream_ptr()), "lits_inter_center")
+    return base
+
+
+def click_geodesic_desc(n, out_hw, src_hw, guide_channel=2):
+    """The descriptor of unetk_click_geodesic: it reads the geometry and G; the store's and the simulator's fields only have
+    to be valid."""
+    return _abi.LitsInterDesc(N=int(n), H=int(out_hw[0]), W=int(out_hw[1]), C=1, n_slices=1, src_h=int(src_hw[0]), src_w=int(src_hw[1]),
+                              im_scale=1, lab_scale=1, obj_label=1, training=0, seed=0, noise_scale=0.0, margin=1, step=0, band=1,
+                              max_clicks=2, G=int(guide_channel), gaussian=0, stddev=0.0)
+
+
+def click_geodesic_path(out_hw, src_hw=(1, 1)):
+    """Where unetk_click_geodesic keeps a grid of this output size: 0 unsupported, 1 LDS, 2 workspace."""
+    return int(_abi.lib().unetk_click_geodesic_path(ctypes.byref(click_geodesic_desc(1, out_hw, src_hw))))
+
+
+def click_geodesic(sample_tab, base, pts, cnt, out_hw, guide_channel=2, want_dist=False, status=None, src_hw=None,
+                   want_sweeps=False):
+    """sp_guide f32 [N, H, W, guide_channel] of --geodesic_guide (unetk_click_geodesic; include/unetk.h has the definition):
+    base f32 [N, hh, hw] (lits_inter_center's, or any field), pts int32 [N, 2, K, 2] with K <= 64 and cnt int32 [N, 2] in the
+    crop boxes and under the flips of sample_tab.  guide_channel 2: (fg, bg); 1: fg - bg.  want_dist: also the raw distances
+    f32 [N, 2, hh, hw]; want_sweeps: also the int32 [N, 2] sweeps each solve ran.  status int32 [1] collects bit 3 (a solve hit
+    its sweep bound); it is NOT read here (None: a word of its own).  src_hw: the store's slice extent, which clamps the
+    table's crop sizes as every kernel on the table clamps them (None: 16384 x 16384).  Current stream."""
+    _require_cuda(sample_tab, base, pts, cnt)
+    n = _inter_tab(sample_tab)
+    assert pts.dtype == torch.int32 and pts.dim() == 4 and pts.shape[0] == n and pts.shape[1] == 2 and pts.shape[3] == 2
+    assert pts.is_contiguous() and cnt.dtype == torch.int32 and tuple(cnt.shape) == (n, 2) and cnt.is_contiguous()
+    k = int(pts.shape[2])
+    h, w = int(out_hw[0]), int(out_hw[1])
+    hh, hw = (h + 1) // 2, (w + 1) // 2
+    assert base.dtype == torch.float32 and tuple(base.shape) == (n, hh, hw) and base.is_contiguous()
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=sample_tab.device)
+    assert status.dtype == torch.int32 and status.numel() >= 1
+    desc = click_geodesic_desc(n, (h, w), src_hw if src_hw is not None else (1 << 14, 1 << 14), guide_channel)
+    nbytes = int(_abi.lib().unetk_click_geodesic_ws_bytes(ctypes.byref(desc)))
+    if nbytes == 0:
+        raise _abi.UnetkError("click_geodesic: unsupported output {} x {} (the half-resolution grid holds at most 2^18 pixels)".format(h, w))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=sample_tab.device)
+    guide = torch.empty((n, h, w, int(guide_channel)), dtype=torch.float32, device=sample_tab.device)
+    dist = torch.empty((n, 2, hh, hw), dtype=torch.float32, device=sample_tab.device) if want_dist else None
+    with _timed_hbm("click_geodesic", guide, 1):
+        check(_abi.lib().unetk_click_geodesic(ctypes.byref(desc), ptr(sample_tab), ptr(base), ptr(pts), ptr(cnt), k, ptr(guide),
+                                              ptr(dist) if want_dist else None, ptr(status), ptr(ws), nbytes, stream_ptr()),
+              "click_geodesic")
+    out = (guide,)
+    if want_dist:
+        out += (dist,)
+    if want_sweeps:
+        out += (ws[:n * 8].view(torch.int32).view(n, 2),)
+    return out[0] if len(out) == 1 else out
+
+
 def inter_click_desc(seg_slices, n, pred_hw, k, obj_label=1, lab_scale=64, vol_base=0, vol_depth=0):
     """The descriptor of unetk_inter_click (include/unetk.h)."""
     return _abi.InterClickDesc(N=int(n), H=int(pred_hw[0]), W=int(pred_hw[1]), n_slices=seg_slices.shape[0],

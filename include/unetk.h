@@ -981,6 +981,47 @@ size_t unetk_inter_click_ws_bytes(const unetk_inter_click_desc* d);
 int unetk_inter_click(const unetk_inter_click_desc* d, const uint8_t* seg_slices, const int32_t* rows, const uint8_t* pred,
                       uint8_t* vol, int32_t* pts, int32_t* cnt, int32_t* table, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- geodesic click guides  
+ * The third guide kind of the click-guided nets (--geodesic_guide): the geodesic distance from the clicks through the image,
+ * grown on the half-resolution centre channel (DataLoader/NF/input_pipeline_g_simply.py:471-496, entry/main_eval.py:205-220;
+ * the reference calls GeodisTK's fast marching on the host).  Builder-defined, parity unpinned: the definition below is this
+ * library's own.  Additive to ABI 10; unetk_lits_inter_desc is unchanged.  With hh = (H + 1) / 2, hw = (W + 1) / 2:
+ *
+ * unetk_lits_inter_center: the base field, base f32 [N][hh][hw].  base[n][i][j] is the value unetk_lits_inter_batch writes at
+ *   pixel (2i, 2j) of channel C / 2 of sample n with training = 0 and the row's flip columns ignored -- img[::2, ::2, C // 2]
+ *   of :484 -- bit for bit (same partial blocks, same expression).  Reads N, H, W, C, n_slices, src_h, src_w, im_scale of the
+ *   desc; the checks, limits and status bit 1 (2) of unetk_lits_inter_batch.
+ *
+ * unetk_click_geodesic: guide f32 [N][H][W][G] from base (a plain device array: any field may be fed), the sample table (crop
+ *   box and flips) and click lists pts int32 [N][2][K][2] = (kind, click, (y, x) relative to the crop box), cnt int32 [N][2]
+ *   clamped into [0, K], 1 <= K <= UNETK_INTER_MAX_CLICKS.  Per sample and kind:
+ *     seeds: gy = (int)(((float)y / (float)ch) * (float)H / 2.0f), gx likewise with cw and W (:483); each operation rounded to
+ *       float32, truncation toward zero, the result clamped into the grid; duplicates are fine;
+ *     D f32 [hh][hw]: the shortest-path distance on the 8-connected grid from the nearest seed under the step cost
+ *       c(p, q) = sqrtf(s2 + (I[p] - I[q])^2), s2 = 1 for an axial step and 2 for a diagonal one, a path's length being the
+ *       left-to-right float32 sum of its step costs from the seed; every operation is rounded to float32 on its own (no
+ *       contraction), the square root correctly rounded.  Equivalently the fixed point with D = 0 at the seeds reached from
+ *       +inf elsewhere under D[q] = min(D[q], min over the 8 neighbours p of fl(D[p] + c(p, q))): float addition is monotone and
+ *       c >= 1, so every relaxation order ends at the same bits, those of a heap Dijkstra with the same operations;
+ *     guide: resize_bilinear(align_corners) of D from hh x hw to H x W (:487), written through the row's flips; a kind without
+ *       clicks is exactly 0;  G == 2: (fg, bg), G == 1: fg - bg; not normalised.
+ *   dist f32 [N][2][hh][hw] or NULL receives the raw D (zeros for a kind without clicks).
+ *   One workgroup solves one (sample, kind) from start to convergence inside one launch; no workgroup waits on another.
+ *   unetk_click_geodesic_path: 0 = unsupported, 1 = I and D in LDS (at least 128 x 128 grids), 2 = I and D in the workspace
+ *   (hh * hw <= 2^18); beyond that UNETK_E_UNSUPPORTED and a zero ws query.  The loop ends when a whole sweep lowers nothing and
+ *   is bounded at hh * hw sweeps (Bellman-Ford: no order needs more); reaching the bound sets status bit 3 (8) and the launch
+ *   ends normally.  The first N * 2 int32 words of ws hold the sweeps each solve ran (0 for a kind without clicks).
+ *   Nothing is read or written out of bounds for any table or click content; two calls give identical bits.
+ *   Reads N, H, W, src_h, src_w, G of the desc (the rest only has to be valid).  ws 16-byte aligned. */
+size_t unetk_lits_inter_center_ws_bytes(const unetk_lits_inter_desc* d);
+int unetk_lits_inter_center(const unetk_lits_inter_desc* d, const uint16_t* slices, const int32_t* sample_tab, float* base,
+                            int32_t* status, void* ws, size_t ws_bytes, void* stream);
+int unetk_click_geodesic_path(const unetk_lits_inter_desc* d);
+size_t unetk_click_geodesic_ws_bytes(const unetk_lits_inter_desc* d);
+int unetk_click_geodesic(const unetk_lits_inter_desc* d, const int32_t* sample_tab, const float* base, const int32_t* pts,
+                         const int32_t* cnt, int K, float* guide, float* dist, int32_t* status, void* ws, size_t ws_bytes,
+                         void* stream);
+
 /* ---------------------------------------------------------------- LiTS 3-D click guides  
  * sp_guide for UNet3D: the clicks of the reference's 3-D pipeline (DataLoader/NF/input_pipeline_3d.py:258-324
  * inter_simulation as :474-504 gen_kernel calls it) simulated on the label patch of unetk_lits_patch3d, and rendered as
