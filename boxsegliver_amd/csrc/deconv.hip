@@ -810,48 +810,35 @@ __global__ void pack_deconv_bf16_kernel(const float* __restrict__ w, int Cin, in
     unetk_pack::deconv_bf16(w, Cin, Cout, wp_fwd, wp_dgrad, perm, i);  // csrc/pack.h
 }
 
-template <int MODE, int WM, int WN, int TM, int TN, bool BS = false>
-int launch_pw_bf16(const PwParams& p, hipStream_t st) {
-  constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-  constexpr size_t lds = (size_t)(2 * BM * PSQ + 2 * (CKB / 8) * BN) * 16;
-  const int n_mtiles = (p.M + BM - 1) / BM;
-  UNETK_LAUNCH((pw_gemm_bf16_kernel<MODE, WM, WN, TM, TN, BS>), dim3(n_mtiles * p.n_ntiles), dim3(WM * WN * 64), lds, st,
-                     p);
-  UNETK_LAUNCH_CHECK();
-  return UNETK_OK;
-}
+// The planned GEMM of a forward / input-gradient launch (deconv_plan below): the tile <WM, WN, TM, TN> of pw_gemm_kernel /
+// pw_gemm_bf16_kernel, which of the two (and its bf16-storage variant) being the call's precision, PwParams::bf16.
+enum PwTile { PW_128, PW_256, PW_64 };          // <2,2,2,2> 128 rows x 128 columns, <2,2,4,2> 256 x 128 (fp32 only), <4,1,1,2> 128 x 64
+struct PwPlan { int tile, n_ntiles, grid; };  // PwTile, column tiles (PwParams::n_ntiles), blocks = row tiles x column tiles
 
 template <int MODE, int WM, int WN, int TM, int TN>
-int launch_pw(const PwParams& p, hipStream_t st) {
+int launch_pw_tile(const PwParams& p, int grid, hipStream_t st) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   constexpr size_t lds = (size_t)(2 * BM * PS + 2 * CK * BN) * sizeof(float);
-  const int n_mtiles = (p.M + BM - 1) / BM;
-  UNETK_LAUNCH((pw_gemm_kernel<MODE, WM, WN, TM, TN>), dim3(n_mtiles * p.n_ntiles), dim3(WM * WN * 64), lds, st, p);
+  constexpr size_t lds_bf16 = (size_t)(2 * BM * PSQ + 2 * (CKB / 8) * BN) * 16;
+  if (p.bf16 == UNETK_FP32) UNETK_LAUNCH((pw_gemm_kernel<MODE, WM, WN, TM, TN>), dim3(grid), dim3(WM * WN * 64), lds, st, p);
+  if constexpr (TM != 4) {                      // the bf16 kernels have no 256-row tile
+    if (p.bf16 == UNETK_BF16)
+      UNETK_LAUNCH((pw_gemm_bf16_kernel<MODE, WM, WN, TM, TN, false>), dim3(grid), dim3(WM * WN * 64), lds_bf16, st, p);
+    if (p.bf16 == UNETK_BF16S)
+      UNETK_LAUNCH((pw_gemm_bf16_kernel<MODE, WM, WN, TM, TN, true>), dim3(grid), dim3(WM * WN * 64), lds_bf16, st, p);
+  }
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }
 
+// instantiates what the plan says (p.n_ntiles = g.n_ntiles is the caller's): no shape rule, no refusal
 template <int MODE>
-int run_pw(PwParams& p, hipStream_t st) {
-  if (p.bf16 == UNETK_BF16S) {
-    if (p.accumulate || p.Ncols % 64 != 0) return UNETK_E_UNSUPPORTED;
-    if (p.Ncols % 128 == 0) {
-      p.n_ntiles = p.Ncols / 128;
-      return launch_pw_bf16<MODE, 2, 2, 2, 2, true>(p, st);
-    }
-    p.n_ntiles = p.Ncols / 64;
-    return launch_pw_bf16<MODE, 4, 1, 1, 2, true>(p, st);
+int launch_pw(const PwParams& p, const PwPlan& g, hipStream_t st) {
+  switch (g.tile) {
+    case PW_256: return launch_pw_tile<MODE, 2, 2, 4, 2>(p, g.grid, st);
+    case PW_64: return launch_pw_tile<MODE, 4, 1, 1, 2>(p, g.grid, st);
+    default: return launch_pw_tile<MODE, 2, 2, 2, 2>(p, g.grid, st);
   }
-  if (p.Ncols % 128 == 0) {
-    p.n_ntiles = p.Ncols / 128;
-    // fp32, long K: 256-row tiles while they still give two blocks per CU -- half the filter-panel staging per MFMA
-    // (conv_igemm.hip).  Measured at bs 32: K = 1024 forward 0.335 -> 0.277 ms, K = 1024 input gradient -0.045 ms; K <= 512
-    // is 5-10 % SLOWER (eight to thirty-two steps do not amortise the four-fragment prologue / epilogue).
-    if (!p.bf16 && p.K >= 1024 && (int64_t)((p.M + 255) / 256) * p.n_ntiles >= 512) return launch_pw<MODE, 2, 2, 4, 2>(p, st);
-    return p.bf16 ? launch_pw_bf16<MODE, 2, 2, 2, 2>(p, st) : launch_pw<MODE, 2, 2, 2, 2>(p, st);
-  }
-  p.n_ntiles = p.Ncols / 64;
-  return p.bf16 ? launch_pw_bf16<MODE, 4, 1, 1, 2>(p, st) : launch_pw<MODE, 4, 1, 1, 2>(p, st);
 }
 
 // fp32 filter gradient of ALL FOUR output sub-pixels (a, b) of an input pixel in one block: the x tile is staged once and
@@ -951,66 +938,95 @@ __global__ __launch_bounds__(256) void deconv_wgrad4_kernel(DwParams p) {
   }
 }
 
-bool deconv_desc_ok(const unetk_deconv3d_desc* d) {
-  return d && d->N > 0 && d->D > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && (d->kd == 1 || d->kd == 2) &&
-         d->out_coff >= 0 && d->out_stride >= d->out_coff + d->Cout &&
-         (d->precision == UNETK_FP32 || d->precision == UNETK_BF16 || d->precision == UNETK_BF16S);
-}
-
-// The backward's shape rules (UNETK_E_UNSUPPORTED / a zero workspace query).  Cout <= 1024: relu_bwd_bias_kernel maps a block's
-// 256 threads to Cout / 4 channel quads (unetk_colmap), and dw_plan divides by the rows that leaves per block -- none beyond.
-bool deconv_bwd_ok(const unetk_deconv3d_desc* d) {
-  if (d->Cin % 64 != 0 || d->Cout % 32 != 0 || d->Cout > 1024 || d->out_stride % 4 != 0 || d->out_coff % 4 != 0) return false;
-  if (d->precision == UNETK_BF16S && (d->kd != 1 || d->Cout % 64 != 0)) return false;
-  return true;
-}
-
-struct DwPlan {
-  int S, m_per_split, nblk_bias;
+// ---- one decision per transposed-conv call, as ConvPlan / WgPlan (common.h).  deconv_plan (pure host arithmetic, no HIP calls)
+// derives from the descriptor alone what the forward, the backward and the workspace query do: the refusals, both GEMMs, the
+// filter-gradient kernel and its splits, the bias-gradient grid and the workspace layout.  The entry points validate, plan,
+// launch; nothing below the plan chooses a tile, refuses a shape or computes an offset.
+enum DwFamily { DW_FP32_4, DW_BF16, DW_BF16S, DW_BF16S4 };          // deconv_wgrad4_kernel, deconv_wgrad_kernel<true>,
+                                                                   // deconv_wgrad_bf16s_kernel, deconv_wgrad_bf16s4_kernel
+struct DeconvPlan {
+  int fwd_rc, bwd_rc;                           // UNETK_OK, UNETK_E_BADARG (the descriptor) or UNETK_E_UNSUPPORTED (the shape)
+  int M;                                        // input pixels N D H W
+  PwPlan fwd, dgrad;                            // forward: [M x Cin] . [Cin x 4 Cout]; input gradient: [M x 4 Cout] . [4 Cout x Cin]
+  int dw_family, S, m_per_split, n_co_tiles, n_ci_tiles, dw_grid, dw_threads;      // filter gradient: DwFamily, pixel splits
+  size_t dw_lds;                                // ... its dynamic LDS bytes
+  int nblk_bias, cq_n, rows_per_iter;           // relu_bwd_bias_kernel: blocks, unetk_colmap(Cout)
+  int64_t dplane;                               // one depth plane of dpre, 4 H W Cout
+  ImgAddr da;                                   // dpre plane of input plane nn (depth tap a: + a * dplane)
+  // The backward's workspace, in floats from its start: dpre (the masked, re-laid gradient) at 0, the bias-gradient partials, the
+  // row reduction's scratch, a dbias sink for callers that pass NULL, and -- 4-float aligned -- the filter gradient's slabs.
+  size_t bpart, btmp, bsink, slab, ws_bytes;
 };
-inline bool dw_bf16s4(const unetk_deconv3d_desc* d) {
-  return d->precision == UNETK_BF16S && d->kd == 1 && d->Cin % 128 == 0 && d->Cout % 64 == 0;
+
+PwPlan pw_plan(int prec, int M, int K, int Ncols) {
+  PwPlan g;
+  g.tile = Ncols % 128 != 0 ? PW_64 : PW_128;
+  g.n_ntiles = Ncols / (g.tile == PW_64 ? 64 : 128);
+  // fp32, long K: 256-row tiles while they still give two blocks per CU -- half the filter-panel staging per MFMA
+  // (conv_igemm.hip).  Measured at bs 32: K = 1024 forward 0.335 -> 0.277 ms, K = 1024 input gradient -0.045 ms; K <= 512
+  // is 5-10 % SLOWER (eight to thirty-two steps do not amortise the four-fragment prologue / epilogue).
+  if (g.tile == PW_128 && prec == UNETK_FP32 && K >= 1024 && (int64_t)((M + 255) / 256) * g.n_ntiles >= 512) g.tile = PW_256;
+  const int bm = g.tile == PW_256 ? 256 : 128;
+  g.grid = (M + bm - 1) / bm * g.n_ntiles;
+  return g;
 }
-DwPlan dw_plan(const unetk_deconv3d_desc* d) {
-  DwPlan pl{};
-  const int M = d->N * d->D * d->H * d->W;
-  int want, mt;         // wanted splits, pixels per tile
-  if (dw_bf16s4(d)) {   // deconv_wgrad_bf16s4_kernel: 64-pixel tiles, (Cout / 64) x (Cin / 128) panels, one block per CU and more
-    const int panels = (d->Cin / 128) * (d->Cout / 64);
-    want = (256 + panels - 1) / panels;
-    mt = 64;
+
+DeconvPlan deconv_plan(const unetk_deconv3d_desc* d) {
+  DeconvPlan pl{};
+  pl.fwd_rc = pl.bwd_rc = UNETK_E_BADARG;
+  if (!(d && d->N > 0 && d->D > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && (d->kd == 1 || d->kd == 2) &&
+        d->out_coff >= 0 && d->out_stride >= d->out_coff + d->Cout &&
+        (d->precision == UNETK_FP32 || d->precision == UNETK_BF16 || d->precision == UNETK_BF16S)))
+    return pl;
+  const int prec = d->precision, Cin = d->Cin, Cout = d->Cout, M = d->N * d->D * d->H * d->W;
+  const bool bs = prec == UNETK_BF16S;
+  // ---- the shape rules, both filled before anything is divided.  Every column count that passes is a multiple of 64, the GEMMs'
+  // narrowest tile.  UNETK_BF16S is 2-D only: a second depth tap would accumulate into dx, which its GEMM cannot.
+  pl.fwd_rc = pl.bwd_rc = UNETK_OK; pl.M = M;
+  if (Cin % CK != 0 || Cout % 16 != 0) pl.fwd_rc = UNETK_E_UNSUPPORTED;
+  if (prec == UNETK_BF16 && (Cin % CKB != 0 || Cout % 32 != 0)) pl.fwd_rc = UNETK_E_UNSUPPORTED;
+  if (bs && (d->kd != 1 || Cin % 64 != 0 || Cout % 64 != 0 || d->out_stride % 2 != 0 || d->out_coff % 2 != 0))
+    pl.fwd_rc = UNETK_E_UNSUPPORTED;
+  // Cout <= 1024: relu_bwd_bias_kernel maps a block's 256 threads to Cout / 4 channel quads (unetk_colmap), and the bias grid
+  // below divides by the rows that leaves per block -- none beyond.
+  if (Cin % 64 != 0 || Cout % 32 != 0 || Cout > 1024 || d->out_stride % 4 != 0 || d->out_coff % 4 != 0)
+    pl.bwd_rc = UNETK_E_UNSUPPORTED;
+  if (bs && (d->kd != 1 || Cout % 64 != 0)) pl.bwd_rc = UNETK_E_UNSUPPORTED;
+  if (pl.fwd_rc == UNETK_OK) pl.fwd = pw_plan(prec, M, Cin, 4 * Cout);
+  if (pl.bwd_rc != UNETK_OK) return pl;
+  pl.dgrad = pw_plan(prec, M, 4 * Cout, Cin);
+  // ---- filter gradient: `sub` blocks per (co, ci) panel, `budget` blocks wanted, `mt` pixels per tile.  The bf16 kernels take
+  // one sub-pixel per block -- ~1024 blocks
+  int sub = 4, budget = 1024, mt = 128;
+  pl.n_co_tiles = (Cout + 63) / 64; pl.n_ci_tiles = Cin / 64; pl.dw_threads = 256;
+  if (prec == UNETK_FP32) {     // one block takes all four sub-pixels of its (co, ci) panel -- ~768 blocks of 40 KB LDS
+    pl.dw_family = DW_FP32_4; sub = 1; budget = 768; pl.dw_lds = 0;
+  } else if (bs && d->kd == 1 && Cin % 128 == 0 && Cout % 64 == 0) {
+    // 64-pixel tiles, (Cout / 64) x (Cin / 128) panels, one block per CU and more
+    pl.dw_family = DW_BF16S4; sub = 1; budget = 256; mt = 64;
+    pl.n_ci_tiles = Cin / 128; pl.dw_threads = 512; pl.dw_lds = (size_t)6 * 64 * 128;
+  } else if (bs) {
+    pl.dw_family = DW_BF16S; pl.dw_lds = (size_t)2 * 128 * 128;
   } else {
-    // fp32: one block takes all four sub-pixels of its (co, ci) panel (deconv_wgrad4_kernel) -- ~768 blocks of 40 KB LDS;
-    // the bf16 kernels take one sub-pixel per block -- ~1024 blocks
-    const bool four = d->precision == UNETK_FP32;
-    const int panels = (four ? 1 : 4) * (d->Cin / 64) * ((d->Cout + 63) / 64);
-    want = ((four ? 768 : 1024) + panels - 1) / panels;
-    mt = 128;
+    pl.dw_family = DW_BF16; pl.dw_lds = (size_t)2 * 128 * 64 * sizeof(float);
   }
-  const SplitK sk = unetk_split((M + mt - 1) / mt, want);
-  pl.S = sk.S;
-  pl.m_per_split = sk.per * mt;
-  const ColMap m = unetk_colmap(d->Cout);
-  int64_t g = ((int64_t)4 * d->kd * M + m.rows_per_iter - 1) / m.rows_per_iter;
-  if (g > UNETK_COL_BLOCKS) g = UNETK_COL_BLOCKS;
-  pl.nblk_bias = (int)g;
+  const int panels = sub * pl.n_co_tiles * pl.n_ci_tiles;
+  const SplitK sk = unetk_split((M + mt - 1) / mt, (budget + panels - 1) / panels);
+  pl.S = sk.S; pl.m_per_split = sk.per * mt; pl.dw_grid = sk.S * panels;
+  // ---- ReLU backward + bias gradient
+  const ColMap m = unetk_colmap(Cout);
+  pl.cq_n = m.cq_n; pl.rows_per_iter = m.rows_per_iter;
+  const int64_t g = ((int64_t)4 * d->kd * M + m.rows_per_iter - 1) / m.rows_per_iter;
+  pl.nblk_bias = (int)(g > UNETK_COL_BLOCKS ? UNETK_COL_BLOCKS : g);
+  pl.dplane = (int64_t)4 * d->H * d->W * Cout;
+  pl.da.group = d->D; pl.da.img_stride = d->kd * pl.dplane; pl.da.group_stride = (int64_t)d->kd * d->D * pl.dplane;
+  // ---- workspace
+  pl.bpart = (size_t)4 * d->kd * M * Cout;
+  pl.btmp = pl.bpart + (size_t)pl.nblk_bias * Cout;
+  pl.bsink = pl.btmp + unetk_rows_reduce_tmp_floats(1, pl.nblk_bias, Cout);
+  pl.slab = (pl.bsink + (size_t)Cout + 3) & ~(size_t)3;
+  pl.ws_bytes = (pl.slab + (size_t)pl.S * 4 * Cin * Cout) * sizeof(float);
   return pl;
-}
-
-// The backward's workspace, in floats from its start: dpre (the masked, re-laid gradient), the bias-gradient partials, the row
-// reduction's scratch, a dbias sink for callers that pass NULL, and -- 4-float aligned -- the filter gradient's slabs.
-struct BwdLayout {
-  size_t bpart, btmp, bsink, slab, total;
-};
-BwdLayout bwd_layout(const unetk_deconv3d_desc* d, const DwPlan& pl) {
-  BwdLayout l;
-  const size_t M = (size_t)d->N * d->D * d->H * d->W;
-  l.bpart = 4 * d->kd * M * d->Cout;
-  l.btmp = l.bpart + (size_t)pl.nblk_bias * d->Cout;
-  l.bsink = l.btmp + unetk_rows_reduce_tmp_floats(1, pl.nblk_bias, d->Cout);
-  l.slab = (l.bsink + (size_t)d->Cout + 3) & ~(size_t)3;
-  l.total = l.slab + (size_t)pl.S * 4 * d->Cin * d->Cout;
-  return l;
 }
 
 unetk_deconv3d_desc from2d(const unetk_deconv_desc* d) {
@@ -1083,30 +1099,90 @@ extern "C" int unetk_deconv3d_fwd(const unetk_deconv3d_desc* d, const void* xv, 
   const float* x = (const float*)xv;
   const float* wp_fwd = (const float*)wpv;
   float* out = (float*)outv;
-  UNETK_REQUIRE(deconv_desc_ok(d) && x && wp_fwd && out);
+  const DeconvPlan pl = deconv_plan(d);
+  UNETK_REQUIRE(pl.fwd_rc != UNETK_E_BADARG && x && wp_fwd && out);
   UNETK_REQUIRE(unetk_aligned16(x) && unetk_aligned16(wp_fwd));
-  if (d->Cin % CK != 0 || d->Cout % 16 != 0) return UNETK_E_UNSUPPORTED;
-  if (d->precision == UNETK_BF16 && (d->Cin % CKB != 0 || d->Cout % 32 != 0)) return UNETK_E_UNSUPPORTED;
-  if (d->precision == UNETK_BF16S && (d->kd != 1 || d->Cin % 64 != 0 || d->Cout % 64 != 0 || d->out_stride % 2 != 0 ||
-                                      d->out_coff % 2 != 0))
-    return UNETK_E_UNSUPPORTED;
+  if (pl.fwd_rc != UNETK_OK) return pl.fwd_rc;
   const int64_t plane = (int64_t)4 * d->H * d->W * d->out_stride;      // one output depth plane
   for (int a = 0; a < d->kd; ++a) {
     PwParams p{};
     p.bf16 = d->precision;
     p.a = x; p.wp = tap_panel(wp_fwd, a, d); p.bias = bias; p.out = out + a * plane;
-    p.M = d->N * d->D * d->H * d->W; p.K = d->Cin; p.Ncols = 4 * d->Cout;
+    p.M = pl.M; p.K = d->Cin; p.Ncols = 4 * d->Cout; p.n_ntiles = pl.fwd.n_ntiles;
     p.H = d->H; p.W = d->W; p.Cout = d->Cout; p.out_stride = d->out_stride; p.out_coff = d->out_coff;
     p.oa.group = d->D; p.oa.img_stride = d->kd * plane; p.oa.group_stride = (int64_t)d->kd * d->D * plane;
-    int rc = run_pw<0>(p, (hipStream_t)stream);
+    int rc = launch_pw<0>(p, pl.fwd, (hipStream_t)stream);
     if (rc != UNETK_OK) return rc;
   }
   return UNETK_OK;
 }
 
 extern "C" size_t unetk_deconv3d_bwd_ws_bytes(const unetk_deconv3d_desc* d) {
-  if (!deconv_desc_ok(d) || !deconv_bwd_ok(d)) return 0;
-  return bwd_layout(d, dw_plan(d)).total * sizeof(float);
+  const DeconvPlan pl = deconv_plan(d);
+  return pl.bwd_rc == UNETK_OK ? pl.ws_bytes : 0;
+}
+
+// ---- the backward's three steps; `ws` is the workspace = dpre, the other regions at the plan's offsets
+// 1. ReLU backward over the whole up half + bias-grad partials, reduced into dbias
+static int bwd_relu_bias(const unetk_deconv3d_desc* d, const DeconvPlan& pl, const float* cat, const float* dcat, float* dbias,
+                         float* ws, hipStream_t st) {
+  const size_t lds = (size_t)pl.rows_per_iter * d->Cout * sizeof(float);
+  const int64_t npix = (int64_t)4 * d->kd * pl.M;
+  if (d->precision == UNETK_BF16S)     // dpre is bf16 in the same workspace region (half of it used)
+    UNETK_LAUNCH(relu_bwd_bias_kernel<bf16_t>, dim3(pl.nblk_bias), dim3(256), lds, st, (const bf16_t*)cat, (const bf16_t*)dcat,
+                 d->out_stride, d->out_coff, (bf16_t*)ws, ws + pl.bpart, npix, d->Cout, pl.cq_n, pl.rows_per_iter);
+  else
+    UNETK_LAUNCH(relu_bwd_bias_kernel<float>, dim3(pl.nblk_bias), dim3(256), lds, st, cat, dcat, d->out_stride, d->out_coff, ws,
+                 ws + pl.bpart, npix, d->Cout, pl.cq_n, pl.rows_per_iter);
+  UNETK_LAUNCH_CHECK();
+  return unetk_rows_reduce(ws + pl.bpart, 1, pl.nblk_bias, d->Cout, dbias ? dbias : ws + pl.bsink, ws + pl.btmp, st);
+}
+
+// 2. input gradient of depth tap a: [M x 4Cout] . [4Cout x Cin], accumulated over depth taps
+static int bwd_dgrad_tap(const unetk_deconv3d_desc* d, const DeconvPlan& pl, int a, const float* wp_dgrad, float* dx,
+                         const float* ws, hipStream_t st) {
+  PwParams p{};
+  p.bf16 = d->precision;
+  p.a = ws + a * pl.dplane; p.wp = tap_panel(wp_dgrad, a, d); p.bias = nullptr; p.out = dx;
+  p.M = pl.M; p.K = 4 * d->Cout; p.Ncols = d->Cin; p.n_ntiles = pl.dgrad.n_ntiles; p.H = d->H; p.W = d->W; p.Cout = d->Cout;
+  p.oa = pl.da; p.accumulate = a > 0 ? 1 : 0;
+  return launch_pw<1>(p, pl.dgrad, st);
+}
+
+// a kernel's dynamic LDS limit, raised once per process; the latch stands next to the one launch that needs it
+static int dyn_lds_once(bool* done, const void* kern, size_t bytes) {
+  if (*done) return UNETK_OK;
+  const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  *done = e == hipSuccess;
+  return (int)e;
+}
+
+// 3. filter gradient of depth tap a: the planned kernel's slabs, reduced into dw[a]
+static int bwd_wgrad_tap(const unetk_deconv3d_desc* d, const DeconvPlan& pl, int a, const float* x, float* dw, float* ws,
+                         hipStream_t st) {
+  DwParams q{};
+  q.bf16 = d->precision == UNETK_BF16;
+  q.x = x; q.dpre = ws + a * pl.dplane; q.slab = ws + pl.slab; q.M = pl.M; q.H = d->H; q.W = d->W; q.Cin = d->Cin; q.Cout = d->Cout;
+  q.m_per_split = pl.m_per_split; q.n_co_tiles = pl.n_co_tiles; q.n_ci_tiles = pl.n_ci_tiles; q.da = pl.da;
+  const dim3 grid(pl.dw_grid), block(pl.dw_threads);
+  switch (pl.dw_family) {
+    case DW_FP32_4: UNETK_LAUNCH(deconv_wgrad4_kernel, grid, block, pl.dw_lds, st, q); break;
+    case DW_BF16S: UNETK_LAUNCH(deconv_wgrad_bf16s_kernel, grid, block, pl.dw_lds, st, q); break;
+    case DW_BF16S4: {
+      static bool latch = false;
+      if (int rc = dyn_lds_once(&latch, (const void*)deconv_wgrad_bf16s4_kernel, pl.dw_lds)) return rc;
+      UNETK_LAUNCH(deconv_wgrad_bf16s4_kernel, grid, block, pl.dw_lds, st, q);
+      break;
+    }
+    default: {    // DW_BF16
+      static bool latch = false;
+      if (int rc = dyn_lds_once(&latch, (const void*)deconv_wgrad_kernel<true>, pl.dw_lds)) return rc;
+      UNETK_LAUNCH(deconv_wgrad_kernel<true>, grid, block, pl.dw_lds, st, q);
+    }
+  }
+  UNETK_LAUNCH_CHECK();
+  const int64_t n = (int64_t)4 * d->Cin * d->Cout;
+  return unetk_launch_slab_reduce(ws + pl.slab, pl.S, n, dw + a * n, st);
 }
 
 extern "C" int unetk_deconv3d_bwd(const unetk_deconv3d_desc* d, const void* xv, const void* wpv,
@@ -1122,96 +1198,19 @@ extern "C" int unetk_deconv3d_bwd(const unetk_deconv3d_desc* d, const void* xv, 
 extern "C" int unetk_deconv3d_bwd_parts(const unetk_deconv3d_desc* d, const void* xv, const void* wpv,
                                         const void* catv, const void* dcatv, void* dxv, float* dw, float* dbias, void* ws,
                                         size_t ws_bytes, int parts, void* stream) {
-  const float* x = (const float*)xv;
-  const float* wp_dgrad = (const float*)wpv;
-  const float* cat = (const float*)catv;
-  const float* dcat = (const float*)dcatv;
-  float* dx = (float*)dxv;
-  UNETK_REQUIRE(deconv_desc_ok(d) && x && wp_dgrad && cat && dcat && dx && dw && ws && parts >= 1 && parts <= 3);
-  const bool bs = d->precision == UNETK_BF16S;
-  if (!deconv_bwd_ok(d)) return UNETK_E_UNSUPPORTED;
-  UNETK_REQUIRE(unetk_aligned16(x) && unetk_aligned16(wp_dgrad) && unetk_aligned16(cat) && unetk_aligned16(dcat) &&
-                unetk_aligned16(dx) && unetk_aligned16(dw) && unetk_aligned16(ws));
-  if (ws_bytes < unetk_deconv3d_bwd_ws_bytes(d)) return UNETK_E_WORKSPACE;
+  const DeconvPlan pl = deconv_plan(d);
+  UNETK_REQUIRE(pl.bwd_rc != UNETK_E_BADARG && xv && wpv && catv && dcatv && dxv && dw && ws && parts >= 1 && parts <= 3);
+  if (pl.bwd_rc != UNETK_OK) return pl.bwd_rc;
+  UNETK_REQUIRE(unetk_aligned16(xv) && unetk_aligned16(wpv) && unetk_aligned16(catv) && unetk_aligned16(dcatv) &&
+                unetk_aligned16(dxv) && unetk_aligned16(dw) && unetk_aligned16(ws));
+  if (ws_bytes < pl.ws_bytes) return UNETK_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const DwPlan pl = dw_plan(d);
-  const int M = d->N * d->D * d->H * d->W;
-  const BwdLayout lay = bwd_layout(d, pl);
-  float* dpre = (float*)ws;
-  float *bpart = dpre + lay.bpart, *btmp = dpre + lay.btmp, *bsink = dpre + lay.bsink, *slab = dpre + lay.slab;
-
-  int rc = UNETK_OK;
-  if (parts & 1) {
-  // 1. ReLU backward over the whole up half + bias-grad partials
-  const ColMap cm = unetk_colmap(d->Cout);
-  if (bs)     // dpre is bf16 in the same workspace region (half of it used)
-    UNETK_LAUNCH(relu_bwd_bias_kernel<bf16_t>, dim3(pl.nblk_bias), dim3(256),
-                       (size_t)cm.rows_per_iter * d->Cout * sizeof(float), st, (const bf16_t*)catv, (const bf16_t*)dcatv,
-                       d->out_stride, d->out_coff, (bf16_t*)dpre, bpart, (int64_t)4 * d->kd * M, d->Cout, cm.cq_n,
-                       cm.rows_per_iter);
-  else
-    UNETK_LAUNCH(relu_bwd_bias_kernel<float>, dim3(pl.nblk_bias), dim3(256),
-                       (size_t)cm.rows_per_iter * d->Cout * sizeof(float), st, cat, dcat, d->out_stride, d->out_coff, dpre,
-                       bpart, (int64_t)4 * d->kd * M, d->Cout, cm.cq_n, cm.rows_per_iter);
-  UNETK_LAUNCH_CHECK();
-  rc = unetk_rows_reduce(bpart, 1, pl.nblk_bias, d->Cout, dbias ? dbias : bsink, btmp, st);
-  if (rc != UNETK_OK) return rc;
+  int rc = (parts & 1) ? bwd_relu_bias(d, pl, (const float*)catv, (const float*)dcatv, dbias, (float*)ws, st) : UNETK_OK;
+  for (int a = 0; a < d->kd && rc == UNETK_OK; ++a) {
+    if (parts & 1) rc = bwd_dgrad_tap(d, pl, a, (const float*)wpv, (float*)dxv, (float*)ws, st);
+    if ((parts & 2) && rc == UNETK_OK) rc = bwd_wgrad_tap(d, pl, a, (const float*)xv, dw, (float*)ws, st);
   }
-
-  const int64_t plane = (int64_t)4 * d->H * d->W * d->Cout;            // one dpre depth plane
-  ImgAddr da;
-  da.group = d->D; da.img_stride = d->kd * plane; da.group_stride = (int64_t)d->kd * d->D * plane;
-  for (int a = 0; a < d->kd; ++a) {
-    // 2. input gradient: [M x 4Cout] . [4Cout x Cin], accumulated over depth taps
-    if (parts & 1) {
-    PwParams p{};
-    p.bf16 = d->precision;
-    p.a = dpre + a * plane; p.wp = tap_panel(wp_dgrad, a, d); p.bias = nullptr; p.out = dx;
-    p.M = M; p.K = 4 * d->Cout; p.Ncols = d->Cin; p.H = d->H; p.W = d->W; p.Cout = d->Cout;
-    p.oa = da; p.accumulate = a > 0 ? 1 : 0;
-    rc = run_pw<1>(p, st);
-    if (rc != UNETK_OK) return rc;
-    }
-    if (!(parts & 2)) continue;
-
-    // 3. filter gradient of this depth tap
-    DwParams q{};
-    q.bf16 = d->precision == UNETK_BF16;
-    q.x = x; q.dpre = dpre + a * plane; q.slab = slab; q.M = M; q.H = d->H; q.W = d->W; q.Cin = d->Cin; q.Cout = d->Cout;
-    q.m_per_split = pl.m_per_split; q.n_co_tiles = (d->Cout + 63) / 64; q.n_ci_tiles = d->Cin / 64; q.da = da;
-    const int grid = pl.S * 4 * q.n_co_tiles * q.n_ci_tiles;
-    if (d->precision == UNETK_FP32) {
-      UNETK_LAUNCH(deconv_wgrad4_kernel, dim3(pl.S * q.n_co_tiles * q.n_ci_tiles), dim3(256), 0, st, q);
-      UNETK_LAUNCH_CHECK();
-      rc = unetk_launch_slab_reduce(slab, pl.S, (int64_t)4 * d->Cin * d->Cout, dw + (int64_t)a * 4 * d->Cin * d->Cout, st);
-      if (rc != UNETK_OK) return rc;
-      continue;
-    }
-    static bool attr_done = false;
-    if (!attr_done) {
-      hipError_t e = hipFuncSetAttribute((const void*)deconv_wgrad_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         2 * 128 * 64 * (int)sizeof(float));
-      if (e != hipSuccess) return (int)e;
-      attr_done = true;
-    }
-    if (dw_bf16s4(d)) {
-      static bool attr4 = false;
-      if (!attr4) {
-        hipError_t e = hipFuncSetAttribute((const void*)deconv_wgrad_bf16s4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 6 * 64 * 128);
-        if (e != hipSuccess) return (int)e;
-        attr4 = true;
-      }
-      q.n_ci_tiles = d->Cin / 128;
-      UNETK_LAUNCH(deconv_wgrad_bf16s4_kernel, dim3(pl.S * q.n_co_tiles * q.n_ci_tiles), dim3(512), (size_t)6 * 64 * 128, st, q);
-    } else if (bs)
-      UNETK_LAUNCH(deconv_wgrad_bf16s_kernel, dim3(grid), dim3(256), (size_t)2 * 128 * 128, st, q);
-    else      // UNETK_BF16 (deconv_desc_ok admits no fourth precision)
-      UNETK_LAUNCH(deconv_wgrad_kernel<true>, dim3(grid), dim3(256), (size_t)2 * 128 * 64 * sizeof(float), st, q);
-    UNETK_LAUNCH_CHECK();
-    rc = unetk_launch_slab_reduce(slab, pl.S, (int64_t)4 * d->Cin * d->Cout, dw + (int64_t)a * 4 * d->Cin * d->Cout, st);
-    if (rc != UNETK_OK) return rc;
-  }
-  return UNETK_OK;
+  return rc;
 }
 
 // ---- 2-D entry points (UNet / GUNet): depth 1, one depth tap

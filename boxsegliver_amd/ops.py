@@ -955,7 +955,7 @@ def deconv2x2_fwd(x, wp_fwd, bias, cat, coff, cout, bf16=False):
 SIDE_DECONV = os.environ.get("UNETK_SIDE_DECONV", "1") == "1"
 
 
-def _deconv_bwd_call(fn_parts, fn_whole, d, nbytes, args, side_ok, x, tag, what):
+def _deconv_bwd_call(fn_parts, fn_whole, d, nbytes, args, side_ok, what):
     """args = (x, wp_dgrad, cat, dcat, dx, dw, db) pointers' owners; returns nothing (dx / dw / db are filled)."""
     xx, wp, cat, dcat, dx, dw, db = args
     if not (side_ok and SIDE_DECONV and not _Side.paused):
@@ -987,7 +987,7 @@ def deconv2x2_bwd(x, wp_dgrad, cat, dcat, coff, cout, bf16=False, out_w=None, ou
     with _timed(lambda: "deconv2x2_bwd{}(relu_bwd+pw_gemm<dgrad>+deconv_wgrad)".format({0: "", 1: "<bf16>", 2: "<bf16s>"}[prec]),
                 16.0 * n * h * w * cin * cout, "{}x{}x{} {}->{}", (n, h, w, cin, cout)):
         _deconv_bwd_call(_abi.lib().unetk_deconv2x2_bwd_parts, _abi.lib().unetk_deconv2x2_bwd, d, nbytes,
-                         (x, wp_dgrad, cat, dcat, dx, dw, db), side_ok, x, None, "deconv2x2_bwd")
+                         (x, wp_dgrad, cat, dcat, dx, dw, db), side_ok, "deconv2x2_bwd")
     return dx, dw, db
 
 
@@ -1052,7 +1052,7 @@ def deconv3d_bwd(x, wp_dgrad, cat, dcat, coff, cout, kd, want_dbias, out_w=None,
     side_ok = out_w is not None and DEBUG_CAPTURE is None and _Side.enabled and SIDE_WGRAD3D_VOXELS > 0
     with _Timed("deconv3d_bwd", 16.0 * kd * n * dd * h * w * cin * cout, "kd{} {}".format(kd, tuple(x.shape))):
         _deconv_bwd_call(_abi.lib().unetk_deconv3d_bwd_parts, _abi.lib().unetk_deconv3d_bwd, d, nbytes,
-                         (x, wp_dgrad, cat, dcat, dx, dw, db), side_ok, x, None, "deconv3d_bwd")
+                         (x, wp_dgrad, cat, dcat, dx, dw, db), side_ok, "deconv3d_bwd")
     return dx, dw, db
 
 

@@ -15,7 +15,7 @@ that it has ties under a non-zero dcat.
 
 Each row of ROWS names the kernels it exists to reach: the GEMM tile of the forward and of the input gradient ("128" =
 <2,2,2,2>, "256" = <2,2,4,2>, "64" = <4,1,1,2>; UNETK_BF16 / UNETK_BF16S have no 256-row tile) and the slab reducer of the
-filter gradient per precision, written out by hand from run_pw, dw_plan, unetk_launch_slab_reduce and unetk_rows_reduce.  The
+filter gradient per precision, written out by hand from pw_plan, deconv_plan, unetk_launch_slab_reduce and unetk_rows_reduce.  The
 library's launch trace must show exactly those kernels in order (pack kernels excluded).  test_plans_are_as_stated ties the
 splits S, tiles per split and bias-partial blocks of PLANS to the library through unetk_deconv*_bwd_ws_bytes, whose value is
 a function of exactly those numbers.
@@ -109,7 +109,7 @@ ROWS = [
 ]
 BY_ID = {r.id: r for r in ROWS}
 
-# dw_plan per row and precision: (splits S, pixel tiles per split, blocks of relu_bwd_bias_kernel), written out by hand; tiles are
+# deconv_plan per row and precision: (splits S, pixel tiles per split, blocks of relu_bwd_bias_kernel), written out by hand; tiles are
 # 128 pixels, 64 for deconv_wgrad_bf16s4_kernel.  test_plans_are_as_stated checks them against the workspace query.
 PLANS = {
     ("g128_small", FP32): (1, 1, 16),             # S = 1: one tile
@@ -230,7 +230,7 @@ def bf16s4(row, prec):
 
 
 def plan(row, prec):
-    """dw_plan restated: (S, tiles per split, bias-partial blocks)."""
+    """deconv_plan's filter-gradient splits and bias grid restated: (S, tiles per split, bias-partial blocks)."""
     M = npix(row)
     rpi = 256 // (row.cout // 4)
     nblk = min(_cd(4 * row.kd * M, rpi), COL_BLOCKS)
@@ -542,13 +542,13 @@ RUN_IDS = ["{}-{}".format(r.id, PREC_NAME[q]) for r, q in RUNS]
 
 
 def test_table_is_consistent_with_the_dispatch_rules():
-    """CPU-side checks of the table against the restated predicates of run_pw and the entry points."""
+    """CPU-side checks of the table against the restated predicates of pw_plan and deconv_plan."""
     assert len(BY_ID) == len(ROWS)
     for row in ROWS:
         M = npix(row)
         assert row.bf16 == fwd_ok(row, BF16) and row.bf16s == fwd_ok(row, BF16S), row.id
         assert (row.dgrad is not None) == bwd_ok(row, FP32), row.id
-        # run_pw, forward: N = 4 Cout columns, K = Cin
+        # pw_plan, forward: N = 4 Cout columns, K = Cin
         ncols, K = 4 * row.cout, row.cin
         want = "64" if ncols % 128 else ("256" if K >= 1024 and _cd(M, 256) * (ncols // 128) >= 512 else "128")
         assert row.fwd == want, (row.id, row.fwd, want)
