@@ -243,6 +243,8 @@ _SIGNATURES = {
     "unetk_mask_counts": (c_int, [P, P, c_int, c_int, c_int, P, P, c_size_t, P]),
     "unetk_slice_hist_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "unetk_slice_hist": (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, c_int, P, P, c_size_t, P]),
+    "unetk_glcm_features_ws_bytes": (c_size_t, [c_int, c_int]),
+    "unetk_glcm_features": (c_int, [P, c_int64, P, c_int, P, c_int, c_int, P, P, P, c_size_t, P]),
     "unetk_guide_components_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "unetk_guide_components": (c_int, [P, P, c_int, c_int, c_int, P, P, c_size_t, P]),
     "unetk_guide_render": (c_int, [P, c_int, c_int, c_int, c_float, P, P]),

@@ -128,6 +128,121 @@ def dump_hist_feature(in_path, out_path, mode, bins=100, xrng=HIST_RANGE, device
     return written
 
 
+GLCM_GRAY = (-250, 300)         # extract.py's own GRAY_MIN / GRAY_MAX: the window the uint8 levels of the glcm patches come from
+GLCM_FILTER_SIZE = 20           # run_dump_glcm_feature_for_{train,eval}: tumours on a slice smaller than this are skipped
+GLCM_AVERAGE_NUM = 3            # ... and at least this many patches are averaged per row
+
+
+def _glcm_patch(image, loop):
+    """The patch of zoom loop `loop` (0 = plain) as the reference makes it: ndi.zoom(order=1) by 1 + 0.1 loop, then
+    ndi.gaussian_filter(., 0.5) ON THE uint8 ARRAY -- scipy rounds back to uint8 after each axis, which the levels depend on."""
+    import warnings
+    if loop > 0:
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            image = ndi.zoom(image, (1. + loop * .1,) * 2, order=1)
+    return np.ascontiguousarray(ndi.gaussian_filter(image, 0.5))
+
+
+def glcm_patches(volume, case, mode, filter_size=GLCM_FILTER_SIZE, average_num=GLCM_AVERAGE_NUM):
+    """The smoothed uint8 patches of one case and how the rows are made of them (extract.py:465-512 for "train", :607-643
+    for "eval"): (patches, groups), groups = [(z1, z2, [patch indices])] -- the float64 mean of a group's feature vectors
+    goes to rows [z1, z2) (train: one slice, assigned; eval: a tumour's z-extent, accumulated and counted).  volume: uint8
+    [depth, H, W]; case: its meta.json record."""
+    from .lits import _maybe_json
+    index = list(_maybe_json(case["tumor_slices_index"]))
+    from_to = _maybe_json(case["tumor_slices_from_to"])
+    areas = _maybe_json(case["tumor_slices_areas"])
+    boxes = _maybe_json(case["tumor_slices"])
+    patches, groups = [], []
+
+    def add(k, j, loop):
+        y1, x1, y2, x2 = boxes[j]
+        patches.append(_glcm_patch(volume[k, y1:y2, x1:x2], loop))
+        return len(patches) - 1
+
+    if mode == "train":
+        for k in range(volume.shape[0]):
+            if k not in index:
+                continue
+            ind = index.index(k)
+            js = [j for j in range(from_to[ind], from_to[ind + 1]) if areas[j] >= filter_size]
+            if not js:
+                continue                      # every tumour of the slice is below filter_size: the row stays zero
+            members = [add(k, j, 0) for j in js]
+            loop = 1
+            while len(members) < average_num:
+                members += [add(k, j, loop) for j in js]
+                loop += 1
+            groups.append((k, k + 1, members))
+        return patches, groups
+    tids = _maybe_json(case["tumor_slices_tid"])
+    for tid, (z1, _, _, z2, _, _) in enumerate(_maybe_json(case["tumors"])):
+        middle = (z2 - z1 - 1) // 2 + z1
+        ind = index.index(middle)
+        for j in range(from_to[ind], from_to[ind + 1]):
+            if tids[j] == tid:
+                if areas[j] >= filter_size:   # only the first record of the tumour on its middle slice is looked at
+                    groups.append((z1, z2, [add(middle, j, loop) for loop in range(average_num)]))
+                break
+    return patches, groups
+
+
+def glcm_rows(feats, groups, depth, mode):
+    """float32 [depth, F] rows from the float64 [n, F] feature vectors of glcm_patches' patches, in the reference's dtypes:
+    train rows are the float64 mean stored as float32; eval rows accumulate the float64 means into float32 and are divided
+    by max(count, 1) in float64."""
+    width = feats.shape[1] if feats.ndim == 2 else 0
+    rows = np.zeros((depth, width), dtype=np.float32)
+    counter = np.zeros((depth,), dtype=np.int32)
+    for z1, z2, members in groups:
+        mean = np.mean([feats[m] for m in members], axis=0)
+        if mode == "train":
+            rows[z1] = mean
+        else:
+            rows[z1:z2] += np.tile(mean[None], (z2 - z1, 1))
+            counter[z1:z2] += 1
+    if mode != "train":
+        rows /= np.clip(counter, 1, np.inf)[:, None]
+    return rows
+
+
+def dump_glcm_feature(in_path, out_path, mode, meta, device=None):
+    """extract.py:377-661 (`dump_glcm_feature_for_train` / `dump_glcm_feature_for_eval` as run_dump_glcm_feature_for_* call
+    them: all 8 properties, distances 1 2 3, angles 0 45 90 135, filter_size 20, average_num 3, norm_levels): for every
+    volume-<PID>.nii[.gz] of in_path the float32 [depth, 96] rows -> <out_path>/glcm/<mode>/<PID:03d>.npy, the files the
+    guided pipeline reads with --use_context --glcm --context_list ... glcm 96.  meta: the meta.json records (a list, or the
+    path of the file).  Cutting, zooming and smoothing the tumour boxes stays on the host (scipy's own uint8 rounding is part
+    of the result); every patch of a case goes to the device in ONE ops.glcm_features call.  Returns the written paths."""
+    from .. import ops
+    if mode not in ("train", "eval"):
+        raise ValueError("mode must be `train` or `eval`, got {}".format(mode))
+    if isinstance(meta, (str, Path)):
+        with Path(meta).open() as f:
+            meta = json.load(f)
+    meta = {int(case["PID"]): case for case in meta}
+    src = Path(in_path)
+    dst = Path(out_path) / "glcm" / mode
+    dst.mkdir(parents=True, exist_ok=True)
+    files = sorted(list(src.glob("volume-*.nii")) + list(src.glob("volume-*.nii.gz")),
+                   key=lambda x: int(x.name.split(".")[0].split("-")[-1]))
+    width = 8 * len(ops.glcm_offsets())
+    written = []
+    for vol_case in files:
+        pid = int(vol_case.name.split(".")[0].split("-")[-1])
+        if pid not in meta:
+            raise KeyError("case {} has no record in the meta file".format(pid))
+        _, volume = nii_kits.read_lits(pid, "vol", vol_case)
+        lo, hi = GLCM_GRAY
+        volume = ((np.clip(volume, lo, hi) - lo) * (255. / (hi - lo))).astype(np.uint8)
+        patches, groups = glcm_patches(volume, meta[pid], mode)
+        feats = ops.glcm_features(patches, norm_levels=True, device=device) if patches else np.zeros((0, width))
+        out = dst / "{:03d}.npy".format(pid)
+        np.save(out, glcm_rows(feats.reshape(-1, width), groups, volume.shape[0], mode))
+        written.append(out)
+    return written
+
+
 def simulate_user_prior(meta):
     """extract.py:664-717 `simulate_user_prior` on a list of meta.json records: for every 3-D tumour (z1, y1, x1, z2, y2,
     x2) its middle slice (z2 - z1 - 1) // 2 + z1 receives {"z": [z1, z2], "center", "stddev"} of that tumour's 2-D record
@@ -166,6 +281,7 @@ def write_user_prior(lits_root):
 def main(argv=None):
     """python -m boxsegliver_amd.data.extract png <nii_dir> <lits_root>/png
        python -m boxsegliver_amd.data.extract hist <nii_dir> <lits_root>/feat [--mode train eval]
+       python -m boxsegliver_amd.data.extract glcm <nii_dir> <lits_root>/feat --meta <lits_root>/meta.json [--mode train eval]
        python -m boxsegliver_amd.data.extract prior <lits_root>"""
     import argparse
     parser = argparse.ArgumentParser(prog="python -m boxsegliver_amd.data.extract", description=__doc__.split("\n")[0])
@@ -178,6 +294,12 @@ def main(argv=None):
     h.add_argument("nii_dir")
     h.add_argument("feat_dir")
     h.add_argument("--mode", nargs="+", choices=("train", "eval"), default=["train", "eval"])
+    g = sub.add_parser("glcm", help="NIfTI volumes + meta.json -> per-slice co-occurrence texture context features "
+                                    "<out>/glcm/<mode>/<PID>.npy")
+    g.add_argument("nii_dir")
+    g.add_argument("feat_dir")
+    g.add_argument("--meta", required=True, help="the meta.json of the `png` sub-command")
+    g.add_argument("--mode", nargs="+", choices=("train", "eval"), default=["train", "eval"])
     r = sub.add_parser("prior", help="<lits_root>/meta.json -> <lits_root>/prior.json, the simulated user prior of the "
                                      "propagated evaluation")
     r.add_argument("lits_root")
@@ -186,6 +308,10 @@ def main(argv=None):
         nii_3d_to_png(a.nii_dir, a.out_dir, a.only_meta)
     elif a.cmd == "prior":
         print(write_user_prior(a.lits_root))
+    elif a.cmd == "glcm":
+        for mode in a.mode:
+            for path in dump_glcm_feature(a.nii_dir, a.feat_dir, mode, a.meta):
+                print(path)
     else:
         for mode in a.mode:
             for path in dump_hist_feature(a.nii_dir, a.feat_dir, mode):

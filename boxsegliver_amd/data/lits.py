@@ -20,6 +20,7 @@ of the reference's unseeded global generators.
 """
 import copy
 import json
+import logging
 import math
 import random
 import struct
@@ -541,22 +542,60 @@ def render_guide(tab, obj_ptr, obj, config, channels, src_hw):
                                   channels, src_hw, RENDER_MIN_STD)
 
 
-CONTEXT_FEATURES = ("hist",)           # glcm / ct_conv contexts are not built
+CONTEXT_FEATURES = ("hist",)           # always served; `glcm` only with --glcm; the ct_conv context is not built
+GLCM_LENGTH = 96                       # 8 properties x 3 distances x 4 angles (data/extract.py dump_glcm_feature)
+GLCM_DEFAULTS = {"glcm_features": ["contrast", "dissimilarity", "homogeneity", "energy", "entropy", "correlation",
+                                   "cluster_shade", "cluster_prominence"],
+                 "glcm_distance": [1, 2, 3], "glcm_angle": [0., math.pi * 0.25, math.pi * 0.5, math.pi * 0.75]}
 
 
-def parse_context_list(context_list):
-    """--context_list name length [name length ...] -> [(name, length)] (input_pipeline_g.py:264-271)."""
+def parse_context_list(context_list, glcm=False):
+    """--context_list name length [name length ...] -> [(name, length)] (input_pipeline_g.py:264-271).  `glcm` (--glcm): the
+    co-occurrence texture rows are accepted too, 96 numbers per slice."""
     items = list(context_list or [])
     if not items:
         raise ValueError("--use_context needs --context_list, e.g. --context_list hist 200")
     if len(items) % 2 != 0:
         raise ValueError("context_list is not paired: {}".format(items))
     pairs = [(str(items[2 * i]), int(items[2 * i + 1])) for i in range(len(items) // 2)]
-    for name, _ in pairs:
-        if name not in CONTEXT_FEATURES:
+    for name, f_len in pairs:
+        if name == "glcm" and glcm:
+            if f_len != GLCM_LENGTH:
+                raise ValueError("context feature `glcm` has {} numbers per slice, got length {}".format(GLCM_LENGTH, f_len))
+        elif name == "glcm":
+            raise ValueError("context feature `glcm` is not supported without --glcm; the LiTS pipeline builds {}".format(
+                ", ".join(CONTEXT_FEATURES + ("glcm",))))
+        elif name not in CONTEXT_FEATURES:
             raise ValueError("context feature `{}` is not supported; the LiTS pipeline builds {}".format(
                 name, ", ".join(CONTEXT_FEATURES)))
     return pairs
+
+
+_GLCM_NOISE_LOGGED = False
+
+
+def context_list_from_args(args):
+    """parse_context_list of the run's flags.  With --glcm the feature files hold the reference's one layout, so
+    --glcm_features / --glcm_distance / --glcm_angle (commented out in the reference) must keep their defaults; --glcm_noise
+    has no effect, as in the reference's LiTS pipeline (input_pipeline_g.py:276-291 fills the hist kwargs only)."""
+    global _GLCM_NOISE_LOGGED
+    glcm = bool(getattr(args, "glcm", False))
+    if glcm:
+        for flag, default in GLCM_DEFAULTS.items():
+            value = getattr(args, flag, None)
+            if value is not None and list(value) != default:
+                raise ValueError("--{} {} is not supported: the glcm feature files hold {}".format(
+                    flag, " ".join(str(v) for v in value), " ".join(str(v) for v in default)))
+        if getattr(args, "glcm_noise", False) and not _GLCM_NOISE_LOGGED:
+            _GLCM_NOISE_LOGGED = True
+            logging.getLogger(__name__).warning("--glcm_noise has no effect: the LiTS pipeline adds noise to the hist columns only")
+    return parse_context_list(getattr(args, "context_list", None), glcm=glcm)
+
+
+def context_noise_scale(context_list, hist_noise_scale):
+    """float64 [F]: the per-column scale of the training noise -- hist_noise_scale on `hist` columns, 0 on `glcm` columns."""
+    return np.concatenate([np.full(n, float(hist_noise_scale) if name == "hist" else 0., dtype=np.float64)
+                           for name, n in context_list])
 
 
 def hist_preprocess(feat, hist_scale):
@@ -584,19 +623,23 @@ def load_context_rows(lits_root, cases, offset, n_rows, context_list, mode_dir, 
                 raise ValueError("{}: feature length mismatch {} vs {}".format(path, feat.shape[1:], f_len))
             if feat.shape[0] != depth:
                 raise ValueError("{}: {} rows for a case of {} slices".format(path, feat.shape[0], depth))
-            rows[offset[pid]:offset[pid] + depth, col:col + f_len] = hist_preprocess(feat, hist_scale)
+            # feature_ops: hist_preprocess scales; glcm_preprocess is the cast alone (--hist_scale is for hist columns only)
+            rows[offset[pid]:offset[pid] + depth, col:col + f_len] = \
+                hist_preprocess(feat, hist_scale) if name == "hist" else feat.astype(np.float32)
             col += f_len
     return rows
 
 
 class ContextGuide(object):
     """The context guide of one pipeline: the host copy of its table (load_context_rows), the coin's spatial_random and,
-    in training with --hist_noise, the noise scale.  `fresh(device)` uploads a new resident table -- one per generator,
+    in training with --hist_noise, the noise scale (a float, or a per-column float64 vector: context_noise_scale).
+    `fresh(device)` uploads a new resident table -- one per generator,
     as the reference caches per generator -- which `unetk_lits_context` reads and, under noise, updates in place."""
 
     def __init__(self, rows, spatial_random=1., noise_scale=None):
         self.rows, self.spatial_random = rows, float(spatial_random)
-        self.noise_scale = None if noise_scale is None else float(noise_scale)
+        self.noise_scale = None if noise_scale is None else \
+            (float(noise_scale) if np.ndim(noise_scale) == 0 else np.asarray(noise_scale, dtype=np.float64))
 
     def fresh(self, device):
         return torch.from_numpy(self.rows).to(device)
@@ -662,6 +705,8 @@ def batches(store, data_list, config, training, seed=1234, liver_percent=0., tum
             noise = None
             if training and context.noise_scale is not None:
                 noise = sampler.noise_rng.normal(0., 1., (bs, table.shape[1])) * context.noise_scale
+                if np.ndim(context.noise_scale) == 1:
+                    noise[:, context.noise_scale == 0.] = -0.        # x + -0. keeps every bit of x, a row's -0. included
             sp, feats["context"] = guides(tab_d, coin, obj_ptr, obj, noise, table, config, c, store.im.shape[1:])
             if sp is not None:
                 feats["sp_guide"] = sp
@@ -756,7 +801,7 @@ def input_fn(mode, params):
     context = None
     if use_context:
         # the context table: train rows for training, eval rows for both eval_online modes (input_pipeline_g.py:734, :815)
-        context_list = parse_context_list(getattr(args, "context_list", None))
+        context_list = context_list_from_args(args)
         hist_scale = float(getattr(args, "hist_scale", 20.))
         ckey = ("lits_context", mode == "train", tuple(context_list), hist_scale)
         if ckey not in params:
@@ -765,6 +810,8 @@ def input_fn(mode, params):
         rows = params[ckey]
         if mode == "train":
             noise = float(getattr(args, "hist_noise_scale", 0.002)) if getattr(args, "hist_noise", False) else None
+            if noise is not None and any(name != "hist" for name, _ in context_list):
+                noise = context_noise_scale(context_list, noise)
             context = ContextGuide(rows, sr, noise)
         else:
             context = ContextGuide(rows, 0. if sr < 1. else sr)
@@ -798,7 +845,7 @@ def input_fn_eval(mode, params):
     context = None
     if getattr(args, "use_context", False) and not getattr(args, "use_spatial", False):
         # input_pipeline_g.py:910-980 (get_dataset_for_eval_image): every slab carries its slices' eval context rows
-        context = EvalContext(params["lits_root"], parse_context_list(getattr(args, "context_list", None)),
+        context = EvalContext(params["lits_root"], context_list_from_args(args),
                               float(getattr(args, "hist_scale", 20.)), params.get("device"))
     fixed = None
     if getattr(args, "use_spatial", False) and getattr(args, "eval_no_sp", False):
@@ -830,7 +877,7 @@ def eval_no_sp_features(args, device=None):
     fixed = {"sp_guide": torch.full((bs, int(args.im_height), int(args.im_width), 1), 0.5, dtype=torch.float32,
                                     device=device)}
     if getattr(args, "use_context", False):
-        width = sum(n for _, n in parse_context_list(getattr(args, "context_list", None)))
+        width = sum(n for _, n in context_list_from_args(args))
         fixed["context"] = torch.zeros((bs, width), dtype=torch.float32, device=device)
     return fixed
 

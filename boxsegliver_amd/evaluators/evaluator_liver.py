@@ -625,7 +625,7 @@ class EvaluateVolume(EvaluateBase):
             raise ValueError("No valid dataset found!")
         context = None
         if getattr(cfg, "use_context", False):
-            context = lits.EvalContext(root, lits.parse_context_list(getattr(cfg, "context_list", None)),
+            context = lits.EvalContext(root, lits.context_list_from_args(cfg),
                                        float(getattr(cfg, "hist_scale", 20.)), self.params.get("device"))
         prior = propagate.load_prior(root, getattr(cfg, "real_sp", None))
         state = propagate.Propagation(prior, float(getattr(cfg, "min_std", 2.)), float(getattr(cfg, "eval_discount", 0.85)),

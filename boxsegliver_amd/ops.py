@@ -1262,6 +1262,58 @@ def slice_hist(vol, lab, mode, bins=100, xrng=(-200, 250)):
     return out
 
 
+GLCM_PROPERTIES = ("contrast", "dissimilarity", "homogeneity", "energy", "entropy", "correlation", "cluster_shade",
+                   "cluster_prominence")
+
+
+def glcm_offsets(distances=(1, 2, 3), angles=(0, 1, 2, 3)):
+    """int32 [len(distances) * len(angles), 2] = (dr, dc) of skimage's greycomatrix for the angles a * pi / 4:
+    (round(sin(a pi / 4) d), round(cos(a pi / 4) d)), in the order distance-major, the reference's [d][a] layout."""
+    import math
+    import numpy as np
+    return np.array([[int(round(math.sin(a * math.pi / 4) * d)), int(round(math.cos(a * math.pi / 4) * d))]
+                     for d in distances for a in angles], dtype=np.int32).reshape(-1, 2)
+
+
+def glcm_features(patches, offsets=None, norm_levels=True, want_counts=False, device=None):
+    """float64 numpy [n, 8 K] texture features of n uint8 patches (unetk_glcm_features; include/unetk.h has the definition):
+    column = property * K + offset index, the reference's np.array([ff[fe] for fe in feat_list]).reshape(-1) with
+    K = distances x angles.  patches: 2-D uint8 numpy arrays of any sizes up to 4096 x 4096; they are packed back to back
+    into one pinned buffer and uploaded in one copy.  offsets: int [K, 2] (default glcm_offsets()).  want_counts: also the
+    uint32 [n, K, 256, 256] symmetric count matrices."""
+    import numpy as np
+    offs = np.ascontiguousarray(glcm_offsets() if offsets is None else offsets, dtype=np.int32).reshape(-1, 2)
+    n, k = len(patches), offs.shape[0]
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    tab = np.zeros((max(n, 1), 3), dtype=np.int32)
+    total = 0
+    for i, a in enumerate(patches):
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 2:
+            raise ValueError("patch {}: a 2-D uint8 numpy array expected".format(i))
+        tab[i] = (total, a.shape[0], a.shape[1])
+        total += a.size
+    lib = _abi.lib()
+    nbytes = int(lib.unetk_glcm_features_ws_bytes(n, k))
+    if nbytes == 0 or total >= 1 << 31:
+        raise _abi.UnetkError("glcm_features: unsupported request ({} patches, {} offsets, {} bytes)".format(n, k, total))
+    host = torch.empty(max(total, 16), dtype=torch.uint8, pin_memory=True)
+    hv = host.numpy()
+    for a, (o, _, _) in zip(patches, tab):
+        hv[o:o + a.size] = a.reshape(-1)
+    pix = host.to(device, non_blocking=True)
+    out = torch.empty((n, 8, k), dtype=torch.float64, device=device)
+    counts = torch.empty((n, k, 256, 256), dtype=torch.int32, device=device) if want_counts else None
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        check(lib.unetk_glcm_features(ptr(pix), total, tab.ctypes.data_as(ctypes.c_void_p), n,
+                                      offs.ctypes.data_as(ctypes.c_void_p), k, 1 if norm_levels else 0, ptr(out), ptr(counts),
+                                      ptr(ws), nbytes, stream_ptr()), "glcm_features")
+        feats = out.cpu().numpy().reshape(n, 8 * k)          # also ends the library's read of the host table
+    if want_counts:
+        return feats, counts.cpu().numpy().view(np.uint32)
+    return feats
+
+
 def mask_counts_async(a, b):
     """int64 device tensor {|A|, |B|, |A and B|, |A or B|} of two same-shape masks (no host read)."""
     a, b = _mask3d(a), _mask3d(b)

@@ -608,6 +608,24 @@ int unetk_surface_dist(const uint8_t* surf, const double* dist2, int D, int H, i
 size_t unetk_slice_hist_ws_bytes(int D, int H, int W, int bins, int mode);
 int unetk_slice_hist(const int16_t* vol, const uint8_t* lab, int D, int H, int W, int mode, const int32_t* lut, int lut_lo,
                      int lut_n, const double* db, int bins, float* out, void* ws, size_t ws_bytes, void* stream);
+/* Grey-level co-occurrence texture features of uint8 patches, the `glcm` context rows (DataLoader/Liver/extract.py:377-661 ->
+ * utils/array_kits.py:1140-1232 glcm_features / greycoprops on skimage's greycomatrix(levels=256, symmetric, normed)).
+ * pix: device bytes; patch p is the row-major h x w uint8 image at pix + patch_tab[p][0] (any byte alignment).  patch_tab int32
+ * [n][3] = (byte offset, h, w) and offsets int32 [K][2] = (dr, dc) are HOST arrays: they are checked before anything is
+ * launched and the table is copied into the workspace on `stream`.  For patch p and offset k every pixel (r, c) whose partner
+ * (r + dr, c + dc) lies inside the patch counts once at [img[r, c]][img[r + dr, c + dc]]; S = C + C^T, P = S / sum(S) (sum
+ * taken as 1 when there is no pair, so P = 0).  out f64 [n][8][K], property order contrast, dissimilarity, homogeneity, energy,
+ * entropy (-sum P log(P + 1e-16)), correlation (exactly 1 when a standard deviation is below 1e-15; centred two-pass form),
+ * cluster_shade, cluster_prominence; norm_levels != 0 applies glcm_features' scaling for 256 levels (contrast / 4096,
+ * dissimilarity / 64, homogeneity x 2, energy x 2, entropy / 8, shade / 64^3, prominence / 64^4).  counts_out (nullable) u32
+ * [n][K][256][256] receives S.  Counts are integer LDS atomics and the fp64 sums run in a fixed order: bit-reproducible.
+ * One workgroup per (p, k) with S's upper triangle in 131,584 B of LDS.
+ * UNETK_E_UNSUPPORTED (and a workspace query of 0): n < 1, K < 1, K > 16, n > 2^24; also h or w outside [1, 4096] and
+ * pix_bytes >= 2^31.  UNETK_E_BADARG: null pix / patch_tab / offsets / out / ws, patch_tab or offsets or counts_out not 4-byte,
+ * out not 8-byte, ws not 16-byte aligned, a patch reaching past pix_bytes.  UNETK_E_WORKSPACE: ws_bytes below the query. */
+size_t unetk_glcm_features_ws_bytes(int n, int K);
+int unetk_glcm_features(const uint8_t* pix, int64_t pix_bytes, const int32_t* patch_tab, int n, const int32_t* offsets, int K,
+                        int norm_levels, double* out, uint32_t* counts_out, void* ws, size_t ws_bytes, void* stream);
 
 /* Spatial-guide propagation of the guided volume evaluation (DataLoader/Liver/input_pipeline_g.py:1179-1513,
  * EvalImage3DLoader), one slice at a time; the matching itself stays on the host.
