@@ -100,6 +100,7 @@ class Lits3dClicksDesc(Structure):
 
 
 INTER3D_TAB_COLS = 20       # UNETK_INTER3D_TAB_COLS
+SLICE_PRIOR_BOUNDARY, SLICE_PRIOR_BINARY = 0, 1     # UNETK_SLICE_PRIOR_*
 
 
 class InterClick3dDesc(Structure):
@@ -136,6 +137,9 @@ _SIGNATURES = {
     "unetk_click_guide3d_rot": (c_int, [POINTER(Lits3dClicksDesc), P, P, P, P, P]),
     "unetk_click_guide3d_warp": (c_int, [POINTER(Lits3dClicksDesc), P, P, c_int, P, P, P, P]),
     "unetk_click_guide3d_list": (c_int, [POINTER(Lits3dClicksDesc), P, P, P, c_int, P, P]),
+    "unetk_slice_prior_ws_bytes": (c_size_t, [POINTER(Lits3dClicksDesc)]),
+    "unetk_slice_prior_field": (c_int, [POINTER(Lits3dClicksDesc), P, P, P, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
+    "unetk_slice_prior_render": (c_int, [POINTER(Lits3dClicksDesc), P, P, P, P, c_int, c_int, P, P]),
     "unetk_inter_click3d_ws_bytes": (c_size_t, [POINTER(InterClick3dDesc)]),
     "unetk_inter_click3d": (c_int, [POINTER(InterClick3dDesc), P, P, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
     "unetk_lits_batch": (c_int, [POINTER(LitsDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -10,7 +10,7 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -I$ROOT/include -I$HERE -Wall -Wno-unused-function ${UNETK_EXTRA_FLAGS:-}"
 objs=()
 pids=()
-for src in evalvol evalio conv_igemm conv_igemm_lin conv_igemm_bf16 conv_igemm_bf16s conv_wgrad conv_wgrad_bf16s conv3d deconv norm reduce pool head weights lits lits3d lits3d_clicks lits_inter lits_geodesic glcm inter_eval inter_eval3d fc conv1d pack optim prof; do
+for src in evalvol evalio conv_igemm conv_igemm_lin conv_igemm_bf16 conv_igemm_bf16s conv_wgrad conv_wgrad_bf16s conv3d deconv norm reduce pool head weights lits lits3d lits3d_clicks slice_prior lits_inter lits_geodesic glcm inter_eval inter_eval3d fc conv1d pack optim prof; do
   o="$OBJ/$src.o"
   if [[ ! -f "$o" || "$HERE/$src.hip" -nt "$o" || "$HERE/common.h" -nt "$o" || "$HERE/pack.h" -nt "$o" || "$HERE/lits_geom.h" -nt "$o" || "$HERE/lits_patch.h" -nt "$o" || "$HERE/lits_clicks.h" -nt "$o" || "$HERE/lits_inter_px.h" -nt "$o" || "$HERE/unionfind.h" -nt "$o" || "$ROOT/include/unetk.h" -nt "$o" ]]; then
     rm -f "$o"                                  # a failed compile must not leave a stale object for the link

@@ -35,6 +35,14 @@ each of dy and dx (--deform_grid G cells per axis, a uniform cubic B-spline).  C
 the lattices ride in the batch's one upload, and the batches go through `unetk_lits_patch3d_warp` and
 `unetk_click_guide3d_warp`, which serve rotation too; the restatement is tests/lits3d_deform_ref.py.  Evaluation never deforms.
 
+With --slice_prior boundary | binary (the reference's --use_cascade [--cascade_binary] without --use_2d,
+:505-533 gen_kernel and :411-471 data_processing_2c) a guided run feeds a second IMAGE channel: the object on the slice of the
+first foreground click -- exp(-dist / 25) of the exact Euclidean distance to its inner boundary, or the mask itself on that
+slice.  After `unetk_lits3d_clicks`, `unetk_slice_prior_field` and `unetk_slice_prior_render` follow on the same stream and
+features["images"] is [bs, D, H, W, 2] (--im_channel 2); the prior consumes no random draw and the host never sees the click.
+Training sees only the boundary pixels inside the crop box, the interactive evaluator (entry/main_eval_3d.py) the whole slice
+-- the difference the reference has too.  The restatement is tests/slice_prior_ref.py.
+
 Offline, `input_fn_eval` tiles every case of the validation fold with windows cut as `eval_online` cuts them (window_starts,
 eval_tables) for the sliding-window evaluator, `EvaluateVolume.run_3d` (--eval_in_patches).  Two options
 of that evaluation live here too: the per-axis Gaussian window tables (window_weights, --eval_window_weight gaussian) and
@@ -67,6 +75,7 @@ COL_SIN, COL_COS = 13, 14          # --random_rotate: float bits, both zero = no
 COL_WARP = 15                      # --random_deform: 0 = not deformed, else the row's lattice applies
 DEFORM_MAX_GRID = 16               # the _warp entries' largest lattice: G + 3 <= 19 control points per axis
 DEFORM_FOLD_CAP = 0.4              # largest control displacement as a share of the control spacing (no folding: 7.3.10)
+SLICE_PRIORS = ("off", "boundary", "binary")     # --slice_prior
 
 
 def add_arguments(parser):
@@ -88,6 +97,10 @@ def add_arguments(parser):
                         help="--random_deform: control cells across the patch on each in-plane axis, 1..16")
     parser.add_argument("--deform_prob", type=float, default=1.0, metavar="P",
                         help="--random_deform: the probability that a sample is deformed")
+    parser.add_argument("--slice_prior", type=str, default="off", choices=SLICE_PRIORS,
+                        help="--use_spatial: a second image channel (--im_channel 2) from the object on the slice of the first "
+                             "foreground click: boundary = exp(-distance to its inner boundary / 25) (the reference's "
+                             "--use_cascade), binary = the mask on that slice (--use_cascade --cascade_binary)")
     parser.add_argument("--eval_window_weight", type=str, default="uniform", choices=WINDOW_WEIGHTS,
                         help="--eval_in_patches: how a window's voxels count in the average; gaussian weights its centre")
     parser.add_argument("--eval_window_sigma", type=float, default=0.125,
@@ -108,8 +121,12 @@ def check_args(args):
 
 def check_values(args):
     """The value checks of the flag group, shared with the interactive evaluator (entry/main_eval_3d.py)."""
-    if int(getattr(args, "im_channel", 1)) != 1:
+    prior = slice_prior(args)
+    if prior is None and int(getattr(args, "im_channel", 1)) != 1:
         raise ValueError("the LiTS 3-D patches have one channel, got --im_channel {}".format(args.im_channel))
+    if prior is not None and int(getattr(args, "im_channel", 1)) != 2:
+        raise ValueError("--slice_prior {} is a second image channel: pass --im_channel 2, got --im_channel {}".format(
+            prior, getattr(args, "im_channel", 1)))
     overlap = float(getattr(args, "eval_overlap", 0.5))
     if not 0.0 <= overlap < 1.0:                          # also refuses NaN
         raise ValueError("--eval_overlap must satisfy 0 <= v < 1, got {}".format(overlap))
@@ -127,10 +144,26 @@ def check_values(args):
     if margin is not DEFAULT_BOX_MARGIN and getattr(args, "eval_box_from", None) is None:       # argparse keeps the default object
         raise ValueError("--eval_box_margin grows the box of --eval_box_from, which is not given")
     guide_stddev(args)
-    rotation(args)
-    deformation(args)
+    deg, _ = rotation(args)
+    px, _, _ = deformation(args)
+    if prior is not None and (deg > 0.0 or px > 0.0):
+        raise ValueError("--slice_prior {} is not served together with --random_rotate > 0 or --random_deform > 0: the field is "
+                         "not defined beyond the crop box".format(prior))
     if int(getattr(args, "guide_channel", 2)) not in (1, 2):
         raise ValueError("--guide_channel must be 1 or 2, got {}".format(args.guide_channel))
+
+
+def slice_prior(args):
+    """--slice_prior -> None (off) | "boundary" | "binary"; a prior needs --use_spatial: the first foreground click names the
+    slice."""
+    mode = getattr(args, "slice_prior", "off") or "off"
+    if mode not in SLICE_PRIORS:
+        raise ValueError("--slice_prior must be one of {}, got {}".format(", ".join(SLICE_PRIORS), mode))
+    if mode == "off":
+        return None
+    if not getattr(args, "use_spatial", False):
+        raise ValueError("--slice_prior {} needs --use_spatial: the slice is the first foreground click's".format(mode))
+    return mode
 
 
 def rotation(args):
@@ -347,7 +380,7 @@ def check_status(status, what):
                                                       "status word {}".format(word)))
 
 
-def batches(store, sampler, shape, lab_max, fg_label, status=None, guide=None):
+def batches(store, sampler, shape, lab_max, fg_label, status=None, guide=None, prior=None):
     """(features, labels) device batches for ever: features["images"] f32 [bs, D, H, W, 1], features["names"] the case ids,
     labels int32 [bs, D, H, W].  Per batch: one sampler draw, one pinned upload, then `unetk_lits_pick_voxel` (forced
     samples' centres, in the device table) and `unetk_lits_patch3d` on the current stream -- no host synchronisation.
@@ -355,7 +388,12 @@ def batches(store, sampler, shape, lab_max, fg_label, status=None, guide=None):
     synchronise): the owner reads it with `check_status` at a point that synchronises anyway (input_fn: every evaluation).
     guide: None, or dict(channels, stddev) for --use_spatial (stddev None: the Euclidean guide): the click draws are made
     after the sampler's and ride in the same upload, `unetk_lits3d_clicks` and `unetk_click_guide3d` follow on the same
-    stream and features["sp_guide"] is f32 [bs, D, H, W, channels]."""
+    stream and features["sp_guide"] is f32 [bs, D, H, W, channels].
+    prior: None, or "boundary" / "binary" for --slice_prior (needs guide): `unetk_slice_prior_field` on the clicks just simulated
+    and `unetk_slice_prior_render` follow on the same stream, features["images"] is f32 [bs, D, H, W, 2] with channel 0 the
+    one-channel patch bit for bit.  No draw, no upload and no synchronisation is added."""
+    if prior is not None and guide is None:
+        raise ValueError("a slice prior needs the simulated clicks of a guided run")
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=store.device)
     while True:
@@ -381,6 +419,9 @@ def batches(store, sampler, shape, lab_max, fg_label, status=None, guide=None):
             pts, cnt = ops.lits3d_clicks(store.lb, tab, ctab, shape, status, fg_label, CLICKS, lits.LB_SCALE)
             feats["sp_guide"] = ops.click_guide3d(tab, pts, cnt, shape, store.im.shape[1:], guide["channels"], guide["stddev"],
                                                   rotate=rotate, warp=warp, grid=grid)
+            if prior is not None:
+                field, z0 = ops.slice_prior_field(store.lb, tab, pts, cnt, shape, fg_label, prior, lab_scale=lits.LB_SCALE)
+                feats["images"] = ops.slice_prior_render(tab, images, field, z0, shape, store.im.shape[1:], prior)
         yield feats, labels
 
 
@@ -434,7 +475,7 @@ def input_fn(mode, params):
     skey = ("lits3d_status", training)
     if skey not in params:
         params[skey] = torch.zeros(1, dtype=torch.int32, device=store.device)
-    gen = batches(store, sampler, shape, lab_max, fg_label, params[skey], guide_config(args))
+    gen = batches(store, sampler, shape, lab_max, fg_label, params[skey], guide_config(args), slice_prior(args))
     if training:
         return gen
     n = int(getattr(args, "eval_num_batches_per_epoch", 100))

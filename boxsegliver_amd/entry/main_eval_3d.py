@@ -22,6 +22,15 @@ stop if Dice > --inter_thresh or fg + bg clicks >= --max_iter.  The Dice of a fo
 a session that stops by its Dice or by --max_iter has had one more click computed than it uses; that click is not counted.
 Without --use_spatial: one pass and no clicks (:386-389).
 
+With --slice_prior boundary | binary (the reference's --use_cascade [--cascade_binary] without --use_2d,
+:348-369) the windows' images carry a second channel: the object on the slice of the session's FIRST foreground click.  Its
+field is built ONCE per session (the reference's `pred_2d_added`), by unetk_slice_prior_field over the whole slice of pts[0][0]
+read on the device, before the first forward; every window table of every later round renders it through
+unetk_slice_prior_render's shared form, however many clicks follow.  Round 0 starts from an empty prediction, so every error
+voxel is an object voxel and its click is a foreground click: the field always has its slice.  Were there none, the channel
+would be zeros (the reference's `len(pos_col[0]) == 0` branch).  --use_cascade and --cascade_binary themselves stay refused as
+before; the variant that feeds a 2-D net's prediction (--use_2d, infer_2d.py) needs a second checkpoint and is not built.
+
 Deviations: the net runs in windows of its training depth in place of one forward over the whole case
 (--im_depth <= 0 is refused); the guide is rendered as in training, at crop resolution and resized with align_corners (the
 reference zooms a source-resolution guide with ndi.zoom); the images go through unetk_lits_patch3d(training = 0); where the
@@ -42,8 +51,10 @@ from .main_eval import _setup_logging, dice
 log = logging.getLogger("boxsegliver_amd")
 
 NF_3D_ONLY = [name for name in flagsets.PIPELINES["nf_3d"][0] if name not in flagsets.PIPELINES["liver_3d"][0]]
-NOT_BUILT = (("use_cascade", "--use_cascade", "the cascade feeds a 2-D net's prediction as a second image channel"),
-             ("cascade_binary", "--cascade_binary", "the cascade feeds a 2-D net's prediction as a second image channel"),
+NOT_BUILT = (("use_cascade", "--use_cascade", "the cascade feeds a 2-D net's prediction as a second image channel; the prior "
+                                             "built from the label is --slice_prior boundary"),
+             ("cascade_binary", "--cascade_binary", "the cascade feeds a 2-D net's prediction as a second image channel; the "
+                                                    "prior built from the label is --slice_prior binary"),
              ("downsampling", "--downsampling", "the resident store holds the slices at full resolution"),
              ("test", "--test", "it scores the reference's private NF test set"),
              ("save_predict", "--save_predict", "the interactive evaluator writes no volumes"))
@@ -175,6 +186,9 @@ class NetPredictor(object):
         self.store, self.args = store, args
         self.shape = (int(args.im_depth), int(args.im_height), int(args.im_width))
         self.guide = lits3d.guide_config(args)
+        self.prior = lits3d.slice_prior(args)                                     # None | "boundary" | "binary"
+        self.obj_label = object_label(args.classes)
+        self.field = None                                                         # (field, z0) of the session, built once
         self.n_classes = len(tuple(args.classes))
         self.variants = lits3d.mirror_variants(args)
         self.windows = CaseWindows3D(self.forward, args)
@@ -196,18 +210,29 @@ class NetPredictor(object):
         self.tables = list(lits3d.eval_tables(case, store, self.shape, float(getattr(a, "eval_overlap", 0.5)), self.variants,
                                               int(a.batch_size), self.box))
         self.coverage = None
+        self.field = None                                                         # a new session: a new first click
 
     def classes(self, pts=None, cnt=None):
         """The case's class volume uint8 [depth, src_h, src_w] under the click lists (None: no guide)."""
         from .. import ops
-        sp_guide = None
+        sp_guide = prior = None
+        src_hw = tuple(self.store.im.shape[1:])
+        if self.prior is not None:
+            from ..data import lits
+            if self.field is None:                                                # once per session, from the first click
+                (row,) = lits.upload_pinned([self.tables[0][:1]], self.store.device)
+                self.field = ops.slice_prior_field(self.store.lb, row, pts, cnt, self.shape, self.obj_label, self.prior,
+                                                   whole=True, lab_scale=lits.LB_SCALE)
+            field, z0 = self.field
+
+            def prior(dtab, images):
+                return ops.slice_prior_render(dtab, images, field, z0, self.shape, src_hw, self.prior, shared=True)
         if self.guide is not None:
-            src_hw = tuple(self.store.im.shape[1:])
 
             def sp_guide(dtab):
                 return ops.click_guide3d_list(dtab, pts, cnt, self.shape, src_hw, self.guide["channels"], self.guide["stddev"])
         for tab in self.tables:
-            self.windows.add(self.store, tab, sp_guide=sp_guide)
+            self.windows.add(self.store, tab, sp_guide=sp_guide, prior=prior)
         volume, self.coverage = self.windows.finish(self.box)
         return volume
 
@@ -258,7 +283,7 @@ def run(args, dataset_params=None, trace=None, trace_preds=False, restore=True, 
         net = NetPredictor(model, mparams.get("model_args", ()), mparams.get("model_kwargs", {}), store, args)
         spatial = net.guide is not None
         if model.params is None:                                   # a forward on zeros creates the variables
-            feats = {"images": torch.zeros((1,) + net.shape + (1,), dtype=torch.float32, device=device)}
+            feats = {"images": torch.zeros((1,) + net.shape + (int(args.im_channel),), dtype=torch.float32, device=device)}
             if spatial:
                 feats["sp_guide"] = torch.zeros((1,) + net.shape + (net.guide["channels"],), dtype=torch.float32, device=device)
             net.forward(feats)

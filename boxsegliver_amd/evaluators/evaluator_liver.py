@@ -125,8 +125,9 @@ class CaseWindows3D(object):
     """The body of the sliding-window evaluation of ONE case by UNet3D, shared by EvaluateVolume.run_3d and the interactive
     evaluator (entry/main_eval_3d.py): per table `add` -- one pinned upload, the windows cut by `unetk_lits_patch3d` as
     `eval_online` cuts them, one forward, `unetk_eval3d_accumulate[_w]` into the case's accumulator at source resolution --
-    and at the end of the case `finish`, the class volume.  forward(features) -> probabilities [n, D, H, W, C].  The only
-    option is `sp_guide`: a function of the device table that returns the guide feature of its rows."""
+    and at the end of the case `finish`, the class volume.  forward(features) -> probabilities [n, D, H, W, C].  The options
+    are `sp_guide`: a function of the device table that returns the guide feature of its rows, and `prior`: a function of the
+    device table and its one-channel images that returns the images the net is fed (--slice_prior: the second channel)."""
 
     def __init__(self, forward, cfg):
         from ..data import lits3d
@@ -138,12 +139,12 @@ class CaseWindows3D(object):
         self.host_tables = lits3d.window_weights(self.shape, getattr(cfg, "eval_window_sigma", 0.125)) if self.gaussian else None
         self.acc = self.cnt = self.tables = None
 
-    def add(self, store, tab, sp_guide=None, before_forward=None):
+    def add(self, store, tab, sp_guide=None, before_forward=None, prior=None):
         from ..data import lits, lits3d
         shape = self.shape
         (dtab,) = lits.upload_pinned([tab], store.device)
         images, _ = ops.lits_patch3d(store.im, store.lb, dtab, shape, False, self.lab_max, lits.IM_SCALE, lits.LB_SCALE)
-        features = {"images": images}
+        features = {"images": images if prior is None else prior(dtab, images)}
         if sp_guide is not None:
             features["sp_guide"] = sp_guide(dtab)
         if before_forward is not None:

@@ -2092,6 +2092,66 @@ def click_guide3d_list(sample_tab, pts, cnt, shape, src_hw, guide_channel=2, std
     return guide
 
 
+SLICE_PRIOR_MODES = {"boundary": _abi.SLICE_PRIOR_BOUNDARY, "binary": _abi.SLICE_PRIOR_BINARY}
+
+
+def slice_prior_field(seg_slices, sample_tab, pts, cnt, shape, obj_label=1, mode="boundary", whole=False, lab_scale=64):
+    """The slice-prior field of every row of sample_tab int32 [N, 16] (unetk_slice_prior_field; include/unetk.h has the rule):
+    (field int32 [N, src_h * src_w], z0 int32 [N]).  pts int32 [N, 2, 4, 3] / cnt int32 [N, 2]: the rows' own clicks
+    (`lits3d_clicks`), or pts int32 [2, K, 3] / cnt int32 [2]: ONE pair of lists for all rows; z0 = the first foreground
+    click's slice, read on the device.  whole=False: the box is the row's crop box, stored densely (pitch cw) at the start of
+    its plane, z0 relative to the box; whole=True: the whole slice, z0 from the case's first slice.  mode "boundary": the
+    exact squared Euclidean distance to the inner boundary of the object on that slice, -1 everywhere where there is none;
+    "binary": the 0 / 1 mask.  Current stream; nothing is read back."""
+    _require_cuda(seg_slices, sample_tab, pts, cnt)
+    assert seg_slices.dtype == torch.uint8 and seg_slices.dim() == 3 and seg_slices.is_contiguous()
+    n = _inter_tab(sample_tab)
+    assert pts.dtype == torch.int32 and cnt.dtype == torch.int32 and pts.is_contiguous() and cnt.is_contiguous()
+    if pts.dim() == 4:
+        assert tuple(pts.shape) == (n, 2, _abi.LITS_MAX_CLICKS, 3) and tuple(cnt.shape) == (n, 2)
+        k = 0
+    else:
+        assert pts.dim() == 3 and pts.shape[0] == 2 and pts.shape[2] == 3 and tuple(cnt.shape) == (2,)
+        k = int(pts.shape[1])
+    desc = lits3d_clicks_desc(seg_slices, n, shape, obj_label, lab_scale=lab_scale)
+    nbytes = int(_abi.lib().unetk_slice_prior_ws_bytes(ctypes.byref(desc)))
+    if nbytes == 0:
+        raise _abi.UnetkError("slice_prior_field: unsupported slices of {} x {}".format(seg_slices.shape[1], seg_slices.shape[2]))
+    binary = SLICE_PRIOR_MODES[mode] == _abi.SLICE_PRIOR_BINARY
+    ws = None if binary else torch.empty(nbytes, dtype=torch.uint8, device=seg_slices.device)     # binary: the row pass alone
+    field = torch.empty((n, seg_slices.shape[1] * seg_slices.shape[2]), dtype=torch.int32, device=seg_slices.device)
+    z0 = torch.empty(n, dtype=torch.int32, device=seg_slices.device)
+    with _timed_hbm("slice_prior_field", field, 1 if binary else 3):
+        check(_abi.lib().unetk_slice_prior_field(ctypes.byref(desc), ptr(seg_slices), ptr(sample_tab), ptr(pts), ptr(cnt), k,
+                                                 1 if whole else 0, SLICE_PRIOR_MODES[mode], ptr(field), ptr(z0),
+                                                 ptr(ws), 0 if binary else nbytes, stream_ptr()),
+              "slice_prior_field")
+    return field, z0
+
+
+def slice_prior_render(sample_tab, images, field, z0, shape, src_hw, mode="boundary", shared=False):
+    """images f32 [N, D, H, W, 2] (unetk_slice_prior_render): channel 0 = images [N, D, H, W, 1] of `lits_patch3d` for the same
+    table, bit for bit; channel 1 = the prior rendered from `slice_prior_field`'s (field, z0) in the rows' crop boxes and under
+    their flips.  shared: ONE whole-slice field [1, src_h * src_w] and z0 [1] in case coordinates for all rows (a window table of
+    one case).  Current stream."""
+    _require_cuda(sample_tab, images, field, z0)
+    n = _inter_tab(sample_tab)
+    d, h, w = (int(v) for v in shape)
+    plane = int(src_hw[0]) * int(src_hw[1])
+    assert images.dtype == torch.float32 and tuple(images.shape) == (n, d, h, w, 1) and images.is_contiguous()
+    assert field.dtype == torch.int32 and field.is_contiguous() and z0.dtype == torch.int32 and z0.is_contiguous()
+    assert tuple(field.shape) == ((1 if shared else n), plane) and z0.numel() == (1 if shared else n), (tuple(field.shape), z0.shape)
+    desc = _abi.Lits3dClicksDesc(N=n, D=d, H=h, W=w, n_slices=1, src_h=int(src_hw[0]), src_w=int(src_hw[1]), lab_scale=1,
+                                 obj_label=1, margin=1, step=0, band=1, max_clicks=2, G=2, gaussian=0,
+                                 stddev=(ctypes.c_float * 3)(0.0, 0.0, 0.0), euclid_norm=1.0)
+    out = torch.empty((n, d, h, w, 2), dtype=torch.float32, device=images.device)
+    with _timed_hbm("slice_prior_render", out, 1, images.numel() * 4):
+        check(_abi.lib().unetk_slice_prior_render(ctypes.byref(desc), ptr(sample_tab), ptr(images), ptr(field), ptr(z0),
+                                                  1 if shared else 0, SLICE_PRIOR_MODES[mode], ptr(out), stream_ptr()),
+              "slice_prior_render")
+    return out
+
+
 def inter_click3d_desc(seg_slices, case_base, depth, k, obj_label=1, lab_scale=64, dist_cap=255):
     """The descriptor of unetk_inter_click3d (include/unetk.h)."""
     return _abi.InterClick3dDesc(case_base=int(case_base), depth=int(depth), n_slices=seg_slices.shape[0],

@@ -1165,6 +1165,70 @@ size_t unetk_inter_click3d_ws_bytes(const unetk_inter_click3d_desc* d);
 int unetk_inter_click3d(const unetk_inter_click3d_desc* d, const uint8_t* seg_slices, const uint8_t* pred, int prev_z, int prev_y,
                         int prev_x, int32_t* pts, int32_t* cnt, int32_t* table, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- slice prior of click-guided UNet3D  
+ * The second image channel of the reference's --use_cascade without --use_2d (DataLoader/NF/input_pipeline_3d.py:505-533
+ * gen_kernel, :411-471 data_processing_2c; entry/main_eval_3d.py:348-369): what the object looks like on the slice z0 of the
+ * first foreground click.  Additive to ABI 10.  The descriptor is unetk_lits3d_clicks_desc, of which N, D, H, W, the store's
+ * extent, lab_scale and obj_label are read, sample_tab the LiTS 3-D table, the object seg / lab_scale >= obj_label.
+ *
+ * unetk_slice_prior_field: per table row n an int32 field over a box of ONE store slice, and z0 int32 [N].
+ *   z0: K == 0: pts int32 [N][2][UNETK_LITS_MAX_CLICKS][3], cnt int32 [N][2] (what unetk_lits3d_clicks gives):
+ *         z0[n] = cnt[n][0] > 0 ? pts[n][0][0][0] : -1;
+ *       1 <= K <= UNETK_INTER_MAX_CLICKS: ONE pair of lists pts int32 [2][K][3], cnt int32 [2] (unetk_inter_click3d's): every
+ *         row takes z0 = cnt[0] > 0 ? pts[0][0][0] : -1.  The value is written to z0[n] as read.
+ *   box: whole == 0: the row's crop box of unetk_lits_patch3d, bh x bw = ch x cw at (y1, x1), and z0 counts from the box's
+ *         first slice z1 -- the slice is crop slice z0 where 0 <= z0 < D;
+ *       whole != 0: the whole slice, bh x bw = src_h x src_w at (0, 0), and z0 counts from the case's first slice.
+ *     Without a click, with z0 outside that range, on a crop slice at or beyond the case's depth or outside the store, the mask
+ *     is all background.  Otherwise mask(i, j) = object at (y1 + i, x1 + j) of that slice.
+ *   field int32 [N][src_h * src_w]: row n's box is stored densely at the start of its plane, pixel (i, j) at i * bw + j; the
+ *     rest of the plane is not written.
+ *   mode UNETK_SLICE_PRIOR_BINARY: field = mask (0 / 1).
+ *   mode UNETK_SLICE_PRIOR_BOUNDARY: a foreground pixel is BOUNDARY when at least one of its 4-neighbours INSIDE the box is
+ *     background; the border of the box does not count as background.  (skimage find_boundaries(mode="inner"): dilation !=
+ *     erosion under the cross footprint, ANDed with the foreground -- a neighbour beyond the border never changes a pixel's
+ *     own value under either border rule skimage has used, minimum / maximum padding or reflection.)
+ *     field = D2(i, j) = min over boundary pixels (i', j') of (i - i')^2 + (j - j')^2, exact integers -- the squared Euclidean
+ *     distance transform, in two separable passes: g(i, j) = distance along row i to its nearest boundary pixel (capped at
+ *     32768 where the row has none), then D2(i, j) = min over i' of (i - i')^2 + g(i', j)^2.  With src_h, src_w <= 4096
+ *     (else UNETK_E_UNSUPPORTED and a zero ws query) nothing exceeds 2^30 + 4111^2 < 2^31.
+ *     Because every seed of the reference's 3-D transform lies in slice z0, its distance is exactly sqrt(dz^2 + D2).
+ *   SENTINEL: a box without a boundary pixel -- no click, no object on the slice, or an object that fills the box -- gets
+ *     field = -1 everywhere, which renders as exactly 0.  Deviation 1 from the scipy / skimage corner cases: the reference feeds
+ *     zeros only for "no click"; with an empty boundary it calls distance_transform_edt on an array without a seed, whose
+ *     answer is an artefact of scipy's implementation -- here the rule is: no boundary, no prior.  Deviation 2: a crop slice
+ *     at or beyond the case's depth (a case shallower than D is padded with label-0 slices, as unetk_lits_patch3d pads it) is
+ *     background, where the reference's crop would have indexed from a negative start.
+ *   ws (16-byte aligned, boundary mode only; NULL is fine for binary): int32 [N][src_h * src_w], the g^2 of the row pass.
+ *   Integer arithmetic, no atomics: two calls give identical bits.  Nothing is read out of bounds for any table or click
+ *   content.  N <= 65535.
+ *
+ * unetk_slice_prior_render: images2 f32 [N,D,H,W,2] (8-byte aligned) from images f32 [N,D,H,W,1] = what unetk_lits_patch3d
+ *   wrote for the same table, and field / z0 as above.
+ *   channel 0 = images, copied bit for bit (so no concat pass follows);
+ *   channel 1 = the prior: create-then-resize as unetk_click_guide3d -- the value at crop resolution is v(z, i, j), evaluated
+ *     at the four in-plane corners (i0 | i1, j0 | j1) of resize_bilinear(align_corners) from ch x cw to H x W and lerped,
+ *       in_y = y * ((ch - 1) / (H - 1)), i0 = min(floor(in_y), ch - 1), i1 = min(floor(in_y) + 1, ch - 1), ly = in_y - floor(in_y)
+ *       top = tl + (tr - tl) lx,  bot = bl + (br - bl) lx,  out = top + (bot - top) ly
+ *     in float32 with EVERY operation rounded on its own (no fused multiply-add: a float32 restatement forms the same taps);
+ *     boundary: v = D2[i][j] < 0 ? 0 : expf(-sqrtf((float)(dz dz + D2[i][j])) / 25.f)     binary: v = dz == 0 ? mask[i][j] : 0
+ *     the three flips of the table are the write address, as for the image.  No z-score, no gamma, no noise touches channel 1:
+ *     data_processing_2c splits the prior off before the z-score and re-attaches it after the gamma.
+ *   shared == 0: field [N][src_h * src_w] per row over its crop box (whole == 0 above), z0 [N], dz = z - z0[n].
+ *   shared != 0: ONE field over the whole slice (whole != 0 above, the plane of row 0) and ONE z0 [1], both in case coordinates,
+ *     for all N rows of a window table: each row reads pixel (y1 + i, x1 + j) and dz = z1 + z - z0[0] -- its box origin
+ *     subtracted in integers; dz may be negative or exceed D.  Fed the crop of the same field, the per-row form gives the
+ *     same bits.
+ *   D*H*W < 2^31 (else UNETK_E_UNSUPPORTED). */
+#define UNETK_SLICE_PRIOR_BOUNDARY 0
+#define UNETK_SLICE_PRIOR_BINARY 1
+size_t unetk_slice_prior_ws_bytes(const unetk_lits3d_clicks_desc* d);
+int unetk_slice_prior_field(const unetk_lits3d_clicks_desc* d, const uint8_t* seg_slices, const int32_t* sample_tab,
+                            const int32_t* pts, const int32_t* cnt, int K, int whole, int mode, int32_t* field, int32_t* z0,
+                            void* ws, size_t ws_bytes, void* stream);
+int unetk_slice_prior_render(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const float* images,
+                             const int32_t* field, const int32_t* z0, int shared, int mode, float* images2, void* stream);
+
 /* ---------------------------------------------------------------- optimiser  core/solver.py:204-243
  * tf.train.AdamOptimizer on a flat parameter buffer.  g' = g*gscale + l2*p  (slim.l2_regularizer
  * gradient, base.py:128-135);  m += (1-b1)(g'-m);  v += (1-b2)(g'^2-v);
