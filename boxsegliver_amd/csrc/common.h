@@ -3,8 +3,16 @@
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "unetk.h"
+
+// A measurement switch: the integer value of the environment variable `name`, dflt where it is unset.  A site that reads its
+// switch once keeps it in a `static const int`.
+inline int unetk_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
 
 // Every kernel launch of the library.  With the kernel trace on (prof.hip, unetk_prof_enable: bench.py's roofline block) the
 // dispatch carries a start / stop event pair bound to the kernel itself, so its duration is the GPU's own begin -> end

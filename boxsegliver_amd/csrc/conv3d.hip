@@ -14,8 +14,6 @@
 //     parity-plane variant was measured and dropped: it stages the same bytes, which is what bounds that kernel).
 #include "common.h"
 
-#include <stdlib.h>
-
 namespace {
 
 struct Geo3 {
@@ -60,6 +58,9 @@ bool desc_ok(const unetk_conv3d_desc* d) {
          !(d->kd == 1 && d->sd != 1) && d->x_stride >= d->Cin && d->y_stride >= d->Cout;
 }
 
+// blocks of 256 threads for a grid-stride loop over `work` elements
+inline int ew_grid(int64_t work) { return work > (int64_t)8192 * 256 ? 8192 : (int)((work + 255) / 256); }
+
 // zero the C channels of npix pixels at pixel stride `stride`: an output that is a channel slice of a concat buffer must leave
 // the channels beside it alone (a dense output is one memset)
 __global__ __launch_bounds__(256) void zero_slice_kernel(float* __restrict__ p, int64_t npix, int C, int stride) {
@@ -75,9 +76,7 @@ int zero_pixels(float* p, int64_t npix, int C, int stride, hipStream_t st) {
     const hipError_t e = hipMemsetAsync(p, 0, (size_t)npix * C * sizeof(float), st);
     return e == hipSuccess ? UNETK_OK : (int)e;
   }
-  int64_t grid = (npix * C + 255) / 256;
-  if (grid > 8192) grid = 8192;
-  UNETK_LAUNCH(zero_slice_kernel, dim3((int)grid), dim3(256), 0, st, p, npix, C, stride);
+  UNETK_LAUNCH(zero_slice_kernel, dim3(ew_grid(npix * C)), dim3(256), 0, st, p, npix, C, stride);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }
@@ -178,18 +177,22 @@ ConvPlan plane_plan(int np, int H, int W, int Cin, int Cout, int spg, int klive 
 }
 bool is_lin(const ConvPlan& pl) { return pl.family == CONV_LIN || pl.family == CONV_LIN_SK; }
 
-// A strided conv whose OUTPUT planes are small (W < 32: the linear-pixel kernel's range) and whose input extents are even
-// (SAME padding then puts the one pad row / column / plane behind the data): forward = space-to-depth + grouped taps.
-// UNETK_S2LIN=0 (measurement): the tiled stride-2 kernel as before.
-bool s2lin_ok(const unetk_conv3d_desc* d, const Geo3& g) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("UNETK_S2LIN"); on = e ? atoi(e) : 1; }
-  if (!on || d->shw != 2 || (d->H & 1) || (d->W & 1) || d->Cin % 16 != 0) return false;
-  if (d->sd == 2 && ((d->D & 1) || d->kd != 3)) return false;
-  return is_lin(plane_plan(d->N * g.Do, g.Ho, g.Wo, d->Cin, d->Cout, g.Do));
+// The plane-launch fields of ConvParams: np planes of H x W in samples of spg planes, x -> y at pixel strides xs / ys
+ConvParams plane_params(const float* x, const float* wp, float* y, int np, int H, int W, int Cin, int Cout, int xs, int ys,
+                        const ImgAddr& xa, const ImgAddr& ya, int spg) {
+  ConvParams p{};
+  p.x = x; p.wp = wp; p.y = y;
+  p.N = np; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.xs = xs; p.ys = ys;
+  p.xa = xa; p.ya = ya; p.spg = spg;
+  return p;
 }
-inline size_t s2lin_xs_floats(const unetk_conv3d_desc* d, const Geo3& g) {
-  return ((size_t)d->N * g.Do * g.Ho * g.Wo * (d->sd == 2 ? 8 : 4) * d->Cin + 63) & ~(size_t)63;
+
+// UNETK_KSKIP (measurement; read once): bit 0 = skip the dead 16-channel chunks of a channel-padded contraction axis
+// (unetk_conv3d_desc.cin_live8 / cout_live8), bit 1 = half the MFMAs on a chunk whose upper 8 channels are padding.  Default 3.
+int kskip() { static const int v = unetk_env_int("UNETK_KSKIP", 3); return v; }
+int live_k(const uint32_t live8[2], int K) { return (kskip() & 1) ? 16 * unetk_live_chunks(live8, K) : K; }
+void set_live(ConvParams& p, const uint32_t live8[2], int K) {
+  if (kskip() & 1) unetk_set_klive(p, live8, K, (kskip() & 2) != 0);
 }
 
 // The filter-gradient launches of a layer, decided once: the workspace queries size for exactly these (wg_runs_bytes) and the
@@ -242,6 +245,403 @@ size_t wg_runs_bytes(const WgRuns& r) {
   }
   return bytes ? r.zf * sizeof(float) + bytes : 0;
 }
+
+// ---- one decision per 3-D conv layer, as ConvPlan / WgPlan (common.h) and DeconvPlan (deconv.hip).  conv3d_plan (pure host
+// arithmetic, no HIP calls) derives from the descriptor and the precision the route of each op, the rows of the launch that
+// writes the statistics, the workspace and every refusal the descriptor decides; the queries return its fields and the entry
+// points launch what it says, so the five cannot disagree.
+enum FwdRoute {
+  FWD_TAPS,              // one stride-1 launch per depth tap, accumulating when kd == 3
+  FWD_FUSED_LIN,         // small planes, stride 1: the three depth taps inside ONE linear-pixel launch
+  FWD_S2D,               // stride 2, small even planes: space-to-depth copy + ONE grouped-tap linear-pixel launch
+  FWD_S2_TAPS,           // native stride-2 tiles, kd == 1
+  FWD_S2_FUSED,          // native stride-2 tiles, the three depth taps inside ONE launch
+  FWD_SUB,               // stride 2 without a strided kernel: FWD_TAPS into a scratch tensor + subsample
+  FWD_BF16               // UNETK_BF16: ONE launch, the depth taps fused into its K loop
+};
+enum DgradRoute {
+  DGRAD_NONE,            // refused
+  DGRAD_GEN_DPAR,        // stride 2, four parity classes from the undilated dy: both depth parities of a (2,2,2) layer in ONE launch
+  DGRAD_GEN_FUSED,       // ... the three depth taps of a (1,2,2) layer in ONE launch
+  DGRAD_GEN_TAPS,        // ... one accumulating launch per depth tap
+  DGRAD_FUSED_LIN,       // small planes, stride 1: as FWD_FUSED_LIN
+  DGRAD_TAPS,            // one stride-1 launch per depth tap
+  DGRAD_DILATED,         // stride 2 fallback: DGRAD_TAPS on the zero-dilated dy
+  DGRAD_BF16             // as FWD_BF16
+};
+struct Tap { int dt, lo, hi; };      // depth tap dt reaches the output planes lo .. hi
+struct Conv3dPlan {
+  int rc;                // the layer itself: UNETK_E_BADARG (descriptor), UNETK_E_UNSUPPORTED (bf16 outside the layer rule)
+  Geo3 g;
+  int fwd, dgrad;        // FwdRoute, DgradRoute
+  // what the descriptor decides against one op (`admit` below): UNETK_E_BADARG = a stride or channel multiple the route needs,
+  // UNETK_E_UNSUPPORTED = no kernel for the channel counts (the route of a refused input gradient is DGRAD_NONE)
+  int fwd_rc, dgrad_rc, wgrad_rc;
+  Tap tap[3];            // the forward's per-tap routes: the launches in order, the full-coverage tap last (it emits the
+  int ntaps;             // statistics); each is planned at its own plane count N * (hi - lo + 1), unetk_split is not monotone
+  int stat_rows;         // rows of the launch that writes the statistics; rc where the layer is refused (bf16: or its launch's)
+  WgRuns wg;             // the filter gradient's launches
+  int klive_f, klive_b;  // live channels of the contraction axis, forward / input gradient (the stream-K cut is sized by them)
+  // workspace.  Forward: FWD_SUB's stride-1 result in the first scratch_f floats; FWD_S2D's copy of x in the first xs_f, its
+  // stream-K slab behind.  Input gradient: DGRAD_DILATED's dy in the first scratch_f floats; the fused-tap linear routes of
+  // both directions take the whole workspace as slab.  Filter gradient: the dilated dy in the first wg.zf floats, the slabs
+  // of the splits behind.
+  size_t scratch_f, xs_f;
+  size_t ws_bytes;
+};
+
+Conv3dPlan conv3d_plan(const unetk_conv3d_desc* d, int prec) {
+  static const int s2lin = unetk_env_int("UNETK_S2LIN", 1);      // 0 (measurement): the routes before the s2d copy / dpar launch
+  Conv3dPlan pl{};
+  pl.rc = pl.stat_rows = UNETK_E_BADARG;
+  if (!desc_ok(d)) return pl;
+  const Geo3 g = pl.g = geo3(d);
+  const bool s4 = d->x_stride % 4 == 0 && d->y_stride % 4 == 0;
+  const int np = d->N * g.Do;
+  if (prec == UNETK_BF16) {
+    pl.rc = pl.stat_rows = UNETK_E_UNSUPPORTED;      // the layer rule (include/unetk.h)
+    if (d->sd != 1 || d->shw != 1 || d->Cin % 32 != 0 || d->Cout % 32 != 0) return pl;
+    pl.rc = UNETK_OK;
+    pl.fwd = FWD_BF16; pl.dgrad = DGRAD_BF16;
+    pl.fwd_rc = pl.dgrad_rc = pl.wgrad_rc = s4 ? UNETK_OK : UNETK_E_BADARG;
+    const ConvPlan cp = plane_plan(np, d->H, d->W, d->Cin, d->Cout, d->D, 0, 0, 0, 1, UNETK_BF16);
+    pl.stat_rows = cp.stat_rows > 0 ? cp.stat_rows : cp.rc;
+    pl.wg = wg_runs(d, g, UNETK_BF16);
+    pl.ws_bytes = wg_runs_bytes(pl.wg);
+    return pl;
+  }
+  pl.rc = UNETK_OK;
+  const bool s2 = d->shw == 2, taps3 = d->kd == 3 && d->sd == 1;      // taps3: every plane receives all three depth taps
+  pl.klive_f = live_k(d->cin_live8, d->Cin);
+  pl.klive_b = live_k(d->cout_live8, d->Cout);
+  // ---- forward.  `out` = one launch over every output plane: its family admits the two linear-pixel routes, and its rows
+  // are those of the per-tap routes' last launch (the full-coverage tap)
+  const ConvPlan out = plane_plan(np, g.Ho, g.Wo, d->Cin, d->Cout, g.Do);
+  pl.fwd_rc = d->y_stride % 4 == 0 ? UNETK_OK : UNETK_E_BADARG;
+  pl.stat_rows = out.stat_rows;
+  if (!s2 && taps3 && is_lin(out)) {
+    pl.fwd = FWD_FUSED_LIN;
+  } else if (s2lin && s2 && !(d->H & 1) && !(d->W & 1) && d->Cin % 16 == 0 && (d->sd == 1 || (!(d->D & 1) && d->kd == 3)) &&
+             is_lin(out)) {
+    // OUTPUT planes in the linear-pixel kernel's range (W < 32) and even input extents: SAME padding then puts the one pad
+    // row / column / plane behind the data
+    pl.fwd = FWD_S2D;
+    pl.xs_f = ((size_t)np * g.Ho * g.Wo * (d->sd == 2 ? 8 : 4) * d->Cin + 63) & ~(size_t)63;
+    if (d->x_stride % 4 != 0) pl.fwd_rc = UNETK_E_BADARG;
+  } else if (s2 && unetk_conv_stride2_ok(d->Cin, d->Cout)) {
+    pl.fwd = d->kd == 3 ? FWD_S2_FUSED : FWD_S2_TAPS;
+    pl.stat_rows = plane_plan(np, g.Ho, g.Wo, d->Cin, d->Cout, g.Do, 0, 0, 0, 2).stat_rows;
+  } else if (s2) {
+    pl.fwd = FWD_SUB;
+    pl.stat_rows = d->N * SUB_BPS;
+    if (d->Cout % 4 != 0) pl.fwd_rc = UNETK_E_BADARG;
+    else if (d->Cout > 1024 && pl.fwd_rc == UNETK_OK) pl.fwd_rc = UNETK_E_UNSUPPORTED;      // subsample2_stats_kernel's thread map
+  } else {
+    pl.fwd = FWD_TAPS;
+  }
+  if (pl.fwd == FWD_TAPS || pl.fwd == FWD_S2_TAPS || pl.fwd == FWD_SUB) {
+    Tap full{-1, 0, 0};
+    for (int dt = 0; dt < d->kd; ++dt) {
+      Tap t{dt, 0, 0};
+      tap_range(d, g, dt, &t.lo, &t.hi);
+      if (full.dt < 0 && t.lo == 0 && t.hi == g.Do - 1) full = t;
+      else if (t.hi >= t.lo) pl.tap[pl.ntaps++] = t;
+    }
+    if (full.dt >= 0) pl.tap[pl.ntaps++] = full;
+    else if (pl.fwd_rc == UNETK_OK) pl.fwd_rc = UNETK_E_UNSUPPORTED;
+  }
+  // ---- input gradient: the conv of dy with Cin and Cout swapped
+  if (!s4 || d->Cout % 4 != 0) pl.dgrad_rc = UNETK_E_BADARG;
+  else if (d->Cout % 16 != 0 || d->Cin % 32 != 0) pl.dgrad_rc = UNETK_E_UNSUPPORTED;      // the MFMA kernels' K and N granularity
+  else if (s2 && unetk_conv_lin_gen_ok(g.Ho, g.Wo, d->Cout, d->Cin))
+    pl.dgrad = s2lin && d->kd == 3 && d->sd == 2 && !(d->D & 1) && g.pb_d == 0 ? DGRAD_GEN_DPAR
+               : taps3                                                       ? DGRAD_GEN_FUSED
+                                                                             : DGRAD_GEN_TAPS;
+  else if (s2) pl.dgrad = DGRAD_DILATED;
+  else pl.dgrad = taps3 && is_lin(plane_plan(np, d->H, d->W, d->Cout, d->Cin, d->D)) ? DGRAD_FUSED_LIN : DGRAD_TAPS;
+  // ---- filter gradient
+  pl.wg = wg_runs(d, g, UNETK_FP32);
+  pl.wgrad_rc = d->y_stride % 4 == 0 ? UNETK_OK : UNETK_E_BADARG;
+  // ---- workspace: one size serves the three ops
+  if (s2) pl.scratch_f = ((size_t)np * d->H * d->W * d->Cout + 63) & ~(size_t)63;      // stride-1 result / dilated dy
+  pl.ws_bytes = pl.scratch_f * sizeof(float);
+  auto at_least = [&pl](size_t bytes) { if (bytes > pl.ws_bytes) pl.ws_bytes = bytes; };
+  at_least(wg_runs_bytes(pl.wg));
+  if (pl.fwd == FWD_S2D)
+    at_least(pl.xs_f * sizeof(float) + plane_plan(np, g.Ho, g.Wo, d->Cin, d->Cout, g.Do, pl.klive_f, 0, d->kd * 4).ws_bytes);
+  if (!s2 && d->sd == 1) {      // stream-K slabs of the small-plane kernel, forward and input gradient
+    at_least(plane_plan(np, d->H, d->W, d->Cin, d->Cout, d->D, pl.klive_f, d->kd).ws_bytes);
+    at_least(plane_plan(np, d->H, d->W, d->Cout, d->Cin, d->D, pl.klive_b, d->kd).ws_bytes);
+  }
+  return pl;
+}
+
+// The refusals of a call in the one order every entry point keeps: the layer, the arguments of the call and the multiples the
+// op's route needs (UNETK_E_BADARG), the workspace where the route takes one, then the channel counts no kernel takes.
+int admit(const Conv3dPlan& pl, bool args_ok, int op_rc, bool needs_ws, const void* ws, size_t ws_bytes) {
+  if (pl.rc != UNETK_OK) return pl.rc;
+  if (!args_ok || op_rc == UNETK_E_BADARG) return UNETK_E_BADARG;
+  if (needs_ws) {
+    if (!ws || !unetk_aligned16(ws)) return UNETK_E_BADARG;
+    if (ws_bytes < pl.ws_bytes) return UNETK_E_WORKSPACE;
+  }
+  return op_rc;
+}
+
+// ---------------------------------------------------------------- the launchers
+// A stride-1 layer in ONE launch over all its planes, forward (in = x, out = y) or input gradient (in = dy, out = dx, the
+// channels swapped), the three depth taps inside the K loop -- no memset, no read-modify-write of the output per tap:
+//   y[o] = sum_dt x[o - 1 + dt] w[dt],  dx[i] = sum_dt dy[i + 1 - dt] w'[dt]     (SAME pad-before of a (3,.,.) kernel is 1)
+// fp32 (FWD / DGRAD_FUSED_LIN): the linear-pixel kernel on small planes (UNet3D's 24^2 / 12^2 / 6^2 levels), K = 27 Cin over
+// the live channels, the whole workspace on offer as stream-K slab.  UNETK_BF16 (FWD / DGRAD_BF16): conv3x3_igemm_bf16_kernel,
+// kd = 1 included
+int run_fused(const unetk_conv3d_desc* d, int prec, bool fwd, const float* in, const float* wp, float* out, float* stat, void* ws,
+              size_t ws_bytes, hipStream_t st) {
+  const int Cin = fwd ? d->Cin : d->Cout, Cout = fwd ? d->Cout : d->Cin, is = fwd ? d->x_stride : d->y_stride;
+  const int os = fwd ? d->y_stride : d->x_stride, HWi = d->H * d->W * is;
+  ConvParams p = plane_params(in, wp, out, d->N * d->D, d->H, d->W, Cin, Cout, is, os, planes(HWi, d->D, 1, d->D),
+                              planes(d->H * d->W * os, d->D, 1, d->D), d->D);
+  p.stat = stat;
+  if (d->kd == 3) { p.kd = 3; p.dshift0 = fwd ? -1 : 1; p.dstep = fwd ? 1 : -1; }
+  if (prec == UNETK_BF16) {
+    p.bf16 = UNETK_BF16;
+    if (d->kd == 3) { p.dsd = 1; p.din = d->D; p.dplane = HWi; }
+  } else {
+    set_live(p, fwd ? d->cin_live8 : d->cout_live8, Cin);
+    if (ws && unetk_aligned16(ws)) { p.sk_slab = (float*)ws; p.sk_slab_bytes = ws_bytes; }
+  }
+  return unetk_conv_run(p, st);
+}
+
+// The tap groups of a strided conv over the space-to-depth copy of its input (ConvParams::ng): group = (depth tap, in-plane class)
+void set_s2d_groups(ConvParams& p, const unetk_conv3d_desc* d, const Geo3& g) {
+  int ng = 0;
+  for (int kd_ = 0; kd_ < d->kd; ++kd_) {
+    const int cd = d->sd == 2 ? (kd_ & 1) : 0;
+    const int dz = d->sd == 2 ? (kd_ >> 1) : kd_ - g.pb_d;      // depth stride 1: input plane = do + kd - pb
+    for (int ph = 0; ph < 2; ++ph)
+      for (int pw = 0; pw < 2; ++pw, ++ng) {
+        p.g_chan[ng] = ((cd * 2 + ph) * 2 + pw) * d->Cin;
+        p.g_dz[ng] = dz;
+        int nt = 0;
+        for (int kh = ph; kh < 3; kh += 2)
+          for (int kw = pw; kw < 3; kw += 2, ++nt) {
+            p.g_off[ng][nt] = 4 * ((kh >> 1) + 1) + ((kw >> 1) + 1);      // output o reads class k & 1 at o + (k >> 1)
+            p.g_panel[ng][nt] = kd_ * 9 + kh * 3 + kw;
+          }
+        p.g_ntaps[ng] = nt;
+      }
+  }
+  p.ng = ng;
+}
+
+// Small OUTPUT planes behind a stride-2 layer: space-to-depth copy of x into the workspace, then ONE launch of the linear-pixel
+// kernel over kd x 4 tap groups (K = kd x 9 x Cin, every MFMA row an output pixel, stream-K in the workspace behind the copy)
+int fwd_s2d(const unetk_conv3d_desc* d, const Conv3dPlan& pl, const float* x, const float* wp, float* y, float* stat, void* ws,
+            size_t ws_bytes, hipStream_t st) {
+  const Geo3& g = pl.g;
+  float* XS = (float*)ws;
+  const int ncls = d->sd == 2 ? 8 : 4;
+  const int64_t npix_out = (int64_t)d->N * g.Do * g.Ho * g.Wo;
+  UNETK_LAUNCH(s2d_kernel, dim3(ew_grid(npix_out * ncls * (d->Cin / 4))), dim3(256), 0, st, x, d->x_stride, XS, npix_out, g.Do, d->D,
+               d->H, d->W, g.Ho, g.Wo, d->Cin, d->sd);
+  UNETK_LAUNCH_CHECK();
+  ConvParams p = plane_params(XS, wp, y, d->N * g.Do, g.Ho, g.Wo, d->Cin, d->Cout, ncls * d->Cin, d->y_stride,
+                              planes(g.Ho * g.Wo * ncls * d->Cin, g.Do, 1, g.Do), planes(g.Ho * g.Wo * d->y_stride, g.Do, 1, g.Do), g.Do);
+  p.stat = stat;
+  set_s2d_groups(p, d, g);
+  set_live(p, d->cin_live8, d->Cin);
+  p.sk_slab = XS + pl.xs_f; p.sk_slab_bytes = ws_bytes - pl.xs_f * sizeof(float);
+  return unetk_conv_run(p, st);
+}
+
+// Natively strided (3,3,3) conv (UNet3D's (1,2,2) and (2,2,2) down-sampling layers): the three depth taps are contracted inside
+// ONE launch of the tiled stride-2 kernel (K = 27 Cin; a tap whose input plane falls outside the sample is skipped per block) --
+// no memset, no read-modify-write of y per tap, one prologue / epilogue instead of three
+int fwd_s2_fused(const unetk_conv3d_desc* d, const Conv3dPlan& pl, const float* x, const float* wp, float* y, float* stat, hipStream_t st) {
+  const Geo3& g = pl.g;
+  const int HWx = d->H * d->W * d->x_stride;
+  ConvParams p = plane_params(x, wp, y, d->N * g.Do, g.Ho, g.Wo, d->Cin, d->Cout, d->x_stride, d->y_stride,
+                              planes(HWx, g.Do, d->sd, d->D), planes(g.Ho * g.Wo * d->y_stride, g.Do, 1, g.Do), g.Do);
+  p.stat = stat;
+  p.stride = 2; p.Hin = d->H; p.Win = d->W; p.pbh = 1 - g.off_h; p.pbw = 1 - g.off_w;
+  p.kd = 3; p.dshift0 = -g.pb_d; p.dstep = 1; p.dsd = d->sd; p.din = d->D; p.dplane = HWx;
+  return unetk_conv_run(p, st);
+}
+
+// One launch per depth tap of pl.tap over the planes the tap reaches.  FWD_S2_TAPS: the tiled stride-2 kernel; FWD_SUB: the
+// stride-1 result goes to the workspace, and the subsample kernel writes y and the statistics from it
+int fwd_taps(const unetk_conv3d_desc* d, const Conv3dPlan& pl, const float* x, const float* wp, float* y, float* stat, void* ws,
+             hipStream_t st) {
+  const Geo3& g = pl.g;
+  const bool native = pl.fwd == FWD_S2_TAPS, sub = pl.fwd == FWD_SUB;
+  float* T = sub ? (float*)ws : y;
+  const int ts = sub ? d->Cout : d->y_stride;
+  const int Hp = native ? g.Ho : d->H, Wp = native ? g.Wo : d->W;      // the planes the launches write
+  const int HWx = d->H * d->W * d->x_stride, HWt = Hp * Wp * ts;
+  if (d->kd > 1) {
+    const int zr = zero_pixels(T, (int64_t)d->N * g.Do * Hp * Wp, d->Cout, ts, st);
+    if (zr != UNETK_OK) return zr;
+  }
+  for (int i = 0; i < pl.ntaps; ++i) {
+    const Tap& t = pl.tap[i];
+    const int n = t.hi - t.lo + 1;
+    ConvParams p = plane_params(x + (int64_t)(t.lo * d->sd - g.pb_d + t.dt) * HWx, wp + (int64_t)t.dt * 9 * d->Cin * d->Cout,
+                                T + (int64_t)t.lo * HWt, d->N * n, Hp, Wp, d->Cin, d->Cout, d->x_stride, ts,
+                                planes(HWx, n, d->sd, d->D), planes(HWt, n, 1, g.Do), n);
+    p.stat = (i == pl.ntaps - 1 && !sub) ? stat : nullptr;
+    p.accumulate = d->kd > 1 ? 1 : 0;
+    if (native) { p.stride = 2; p.Hin = d->H; p.Win = d->W; p.pbh = 1 - g.off_h; p.pbw = 1 - g.off_w; }
+    const int rc = unetk_conv_run(p, st);
+    if (rc != UNETK_OK) return rc;
+  }
+  if (sub) {
+    const ColMap m = unetk_colmap(d->Cout);
+    const size_t lds = stat ? (size_t)2 * m.rows_per_iter * d->Cout * sizeof(float) : 0;
+    UNETK_LAUNCH(subsample2_stats_kernel, dim3(d->N * SUB_BPS), dim3(256), lds, st, T, y, stat, g.Do, d->H, d->W, g.Ho, g.Wo, d->Cout,
+                 d->y_stride, g.off_h, g.off_w, m.cq_n, m.rows_per_iter, SUB_BPS, d->N * SUB_BPS);
+    UNETK_LAUNCH_CHECK();
+  }
+  return UNETK_OK;
+}
+
+// wp: the fp32 pack, or the bf16 pack of the bf16 entry points
+int conv3d_fwd(const unetk_conv3d_desc* d, int prec, const float* x, const float* wp, float* y, float* stat, void* ws, size_t ws_bytes,
+               void* stream) {
+  const Conv3dPlan pl = conv3d_plan(d, prec);
+  const int rc = admit(pl, x && wp && y && unetk_aligned16(x) && unetk_aligned16(wp) && unetk_aligned16(y), pl.fwd_rc,
+                       pl.fwd == FWD_SUB || pl.fwd == FWD_S2D || pl.fwd == FWD_BF16, ws, ws_bytes);
+  if (rc != UNETK_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  switch (pl.fwd) {
+    case FWD_FUSED_LIN:
+    case FWD_BF16: return run_fused(d, prec, true, x, wp, y, stat, ws, ws_bytes, st);
+    case FWD_S2D: return fwd_s2d(d, pl, x, wp, y, stat, ws, ws_bytes, st);
+    case FWD_S2_FUSED: return fwd_s2_fused(d, pl, x, wp, y, stat, st);
+    default: return fwd_taps(d, pl, x, wp, y, stat, ws, st);
+  }
+}
+
+// dy -> (Z, stride) usable by the stride-1 backward kernels: dy itself, or (dilate) its zero-dilated copy in the first floats of ws
+int dilated_dy(const unetk_conv3d_desc* d, const Geo3& g, bool dilate, const float* dy, void* ws, hipStream_t st, const float** z,
+               int* zs) {
+  *z = dy;
+  *zs = d->y_stride;
+  if (!dilate) return UNETK_OK;
+  float* Z = (float*)ws;
+  const size_t n = (size_t)d->N * g.Do * d->H * d->W * d->Cout;
+  hipError_t e = hipMemsetAsync(Z, 0, n * sizeof(float), st);
+  if (e != hipSuccess) return (int)e;
+  const int64_t npix_out = (int64_t)d->N * g.Do * g.Ho * g.Wo;
+  UNETK_LAUNCH(dilate2_kernel, dim3(ew_grid(npix_out * (d->Cout / 4))), dim3(256), 0, st, dy, d->y_stride, Z, npix_out, d->H, d->W,
+               g.Ho, g.Wo, d->Cout, g.off_h, g.off_w);
+  UNETK_LAUNCH_CHECK();
+  *z = Z;
+  *zs = d->Cout;
+  return UNETK_OK;
+}
+
+// dx = 0 before the accumulating launches of a per-tap input gradient
+int zero_dx(const unetk_conv3d_desc* d, float* dx, hipStream_t st) {
+  return zero_pixels(dx, (int64_t)d->N * d->D * d->H * d->W, d->Cin, d->x_stride, st);
+}
+
+// The four output-parity classes of a stride-2 conv's input gradient (conv_igemm_lin.hip GEN), pbh / pbw = SAME pad-before:
+//   dx[hi] = sum_{kh = ph, ph+2} dy[a - (kh - ph)/2] w[kh],  ph = (hi + pbh) & 1,  a = (hi + pbh - ph) / 2
+// class q = 2 ph + pw contracts the undilated dy over its 4 / 2 / 2 / 1 taps
+void set_parity_taps(ConvParams& p, int pbh, int pbw) {
+  for (int ph = 0; ph < 2; ++ph)
+    for (int pw = 0; pw < 2; ++pw) {
+      const int q = ph * 2 + pw;
+      p.ooh[q] = ph - pbh;
+      p.oow[q] = pw - pbw;
+      p.ntaps[q] = 0;
+      for (int kh = ph; kh < 3; kh += 2)
+        for (int kw = pw; kw < 3; kw += 2) {
+          p.tap_off[q][p.ntaps[q]] = 4 * ((ph - kh) / 2 + 1) + ((pw - kw) / 2 + 1);
+          p.tap_panel[q][p.ntaps[q]] = 8 - (kh * 3 + kw);
+          ++p.ntaps[q];
+        }
+    }
+}
+
+// The three four-class routes.  DGRAD_GEN_FUSED (depth stride 1, UNet3D's (1,2,2) layers): every dx plane receives all three
+// depth taps, contracted in ONE launch (K = 3 x taps x Cout) -- no memset, no accumulation passes.  DGRAD_GEN_DPAR (the (2,2,2)
+// bridge): dx plane di = 2 do + dt (pad-before 0 for an even depth), so the EVEN dx planes receive the taps dt = 0 (do = di / 2)
+// and dt = 2 (do = di / 2 - 1), the ODD ones dt = 1 alone -- both parities in ONE launch that writes every plane once.
+// DGRAD_GEN_TAPS: one launch per depth tap, accumulating into a zeroed dx where more than one tap reaches a plane
+int dgrad_gen(const unetk_conv3d_desc* d, const Conv3dPlan& pl, const float* dy, const float* wp, float* dx, hipStream_t st) {
+  const Geo3& g = pl.g;
+  const int HWx = d->H * d->W * d->x_stride, HWy = g.Ho * g.Wo * d->y_stride;
+  const bool dpar = pl.dgrad == DGRAD_GEN_DPAR, fused = pl.dgrad == DGRAD_GEN_FUSED;
+  const bool multi = pl.dgrad == DGRAD_GEN_TAPS && (d->kd > 1 || d->sd > 1);
+  int rc = UNETK_OK;
+  if (multi && (rc = zero_dx(d, dx, st)) != UNETK_OK) return rc;
+  for (int dt = 0; dt < (dpar || fused ? 1 : d->kd); ++dt) {
+    int lo = 0, hi = g.Do - 1;
+    if (pl.dgrad == DGRAD_GEN_TAPS) tap_range(d, g, dt, &lo, &hi);
+    if (hi < lo) continue;
+    const int n = hi - lo + 1;
+    ConvParams p = plane_params(dy + (int64_t)lo * HWy, wp + (int64_t)dt * 9 * d->Cin * d->Cout,
+                                dx + (int64_t)(dpar || fused ? 0 : lo * d->sd - g.pb_d + dt) * HWx, d->N * n, g.Ho, g.Wo, d->Cout, d->Cin,
+                                d->y_stride, d->x_stride, planes(HWy, n, 1, g.Do), planes(HWx, n, d->sd, d->D), n);
+    p.accumulate = multi ? 1 : 0;
+    if (fused) { p.kd = 3; p.dshift0 = g.pb_d; p.dstep = -1; }      // dx[di] = sum_dt dy[di + pb - dt] * w[dt]
+    if (dpar) {
+      p.dshift0 = 0; p.dstep = -1;            // even planes: dy plane do = di / 2 - dt' for the fused taps dt' = 0, 1 (dt = 0, 2)
+      p.dpar = 1; p.dpar_yoff = HWx;          // odd planes: one plane further
+    }
+    set_live(p, d->cout_live8, d->Cout);
+    p.os = 2; p.Hd = d->H; p.Wd = d->W;
+    set_parity_taps(p, 1 - g.off_h, 1 - g.off_w);
+    if ((rc = unetk_conv_run_lin_gen(p, st)) != UNETK_OK) return rc;
+  }
+  return UNETK_OK;
+}
+
+// DGRAD_TAPS / DGRAD_DILATED: one stride-1 launch per depth tap, dy planes lo .. hi -> dx planes di = do * sd - pb + dt
+int dgrad_taps(const unetk_conv3d_desc* d, const Conv3dPlan& pl, const float* dy, const float* wp, float* dx, void* ws, hipStream_t st) {
+  const Geo3& g = pl.g;
+  const float* Z;
+  int zs;
+  int rc = dilated_dy(d, g, pl.dgrad == DGRAD_DILATED, dy, ws, st, &Z, &zs);
+  if (rc != UNETK_OK) return rc;
+  const int HWx = d->H * d->W * d->x_stride, HWz = d->H * d->W * zs;
+  const bool multi = d->kd > 1 || d->sd > 1;
+  if (multi && (rc = zero_dx(d, dx, st)) != UNETK_OK) return rc;
+  for (int dt = 0; dt < d->kd; ++dt) {
+    int lo, hi;
+    tap_range(d, g, dt, &lo, &hi);
+    if (hi < lo) continue;
+    const int n = hi - lo + 1;
+    ConvParams p = plane_params(Z + (int64_t)lo * HWz, wp + (int64_t)dt * 9 * d->Cin * d->Cout,
+                                dx + (int64_t)(lo * d->sd - g.pb_d + dt) * HWx, d->N * n, d->H, d->W, d->Cout, d->Cin, zs, d->x_stride,
+                                planes(HWz, n, 1, g.Do), planes(HWx, n, d->sd, d->D), n);
+    p.accumulate = multi ? 1 : 0;
+    rc = unetk_conv_run(p, st);
+    if (rc != UNETK_OK) return rc;
+  }
+  return UNETK_OK;
+}
+
+int conv3d_dgrad(const unetk_conv3d_desc* d, int prec, const float* dy, const float* wp, float* dx, void* ws, size_t ws_bytes,
+                 void* stream) {
+  const Conv3dPlan pl = conv3d_plan(d, prec);
+  const int rc = admit(pl, dy && wp && dx && unetk_aligned16(dy) && unetk_aligned16(wp) && unetk_aligned16(dx), pl.dgrad_rc,
+                       pl.dgrad == DGRAD_DILATED || pl.dgrad == DGRAD_BF16, ws, ws_bytes);
+  if (rc != UNETK_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  switch (pl.dgrad) {
+    case DGRAD_GEN_DPAR:
+    case DGRAD_GEN_FUSED:
+    case DGRAD_GEN_TAPS: return dgrad_gen(d, pl, dy, wp, dx, st);
+    case DGRAD_FUSED_LIN:
+    case DGRAD_BF16: return run_fused(d, prec, false, dy, wp, dx, nullptr, ws, ws_bytes, st);
+    default: return dgrad_taps(d, pl, dy, wp, dx, ws, st);
+  }
+}
+
+// ---------------------------------------------------------------- filter gradient
 // Z, zs: dy and its pixel stride (dilated where r.zf); ws: behind the dilated dy
 int run_wgrad(const unetk_conv3d_desc* d, const Geo3& g, const WgRuns& r, const float* x, const float* Z, int zs, float* dw,
               void* ws, size_t ws_bytes, hipStream_t st) {
@@ -274,6 +674,18 @@ int run_wgrad(const unetk_conv3d_desc* d, const Geo3& g, const WgRuns& r, const 
   return UNETK_OK;
 }
 
+int conv3d_wgrad(const unetk_conv3d_desc* d, int prec, const float* x, const float* dy, float* dw, void* ws, size_t ws_bytes,
+                 void* stream) {
+  const Conv3dPlan pl = conv3d_plan(d, prec);
+  int rc = admit(pl, x && dy && dw && unetk_aligned16(x) && unetk_aligned16(dy) && unetk_aligned16(dw), pl.wgrad_rc, true, ws, ws_bytes);
+  if (rc != UNETK_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const float* Z;
+  int zs;
+  if ((rc = dilated_dy(d, pl.g, pl.wg.zf != 0, dy, ws, st, &Z, &zs)) != UNETK_OK) return rc;
+  return run_wgrad(d, pl.g, pl.wg, x, Z, zs, dw, (float*)ws + pl.wg.zf, ws_bytes - pl.wg.zf * sizeof(float), st);
+}
+
 }  // namespace
 
 extern "C" int unetk_conv3d_pack(const float* w, int kd, int Cin, int Cout, float* wp_fwd, float* wp_dgrad,
@@ -288,398 +700,35 @@ extern "C" int unetk_conv3d_pack(const float* w, int kd, int Cin, int Cout, floa
 }
 
 extern "C" int unetk_conv3d_out_dims(const unetk_conv3d_desc* d, int* Do, int* Ho, int* Wo) {
-  if (!desc_ok(d)) return UNETK_E_BADARG;
-  const Geo3 g = geo3(d);
-  if (Do) *Do = g.Do;
-  if (Ho) *Ho = g.Ho;
-  if (Wo) *Wo = g.Wo;
+  const Conv3dPlan pl = conv3d_plan(d, UNETK_FP32);
+  if (pl.rc != UNETK_OK) return pl.rc;
+  if (Do) *Do = pl.g.Do;
+  if (Ho) *Ho = pl.g.Ho;
+  if (Wo) *Wo = pl.g.Wo;
   return UNETK_OK;
 }
 
-extern "C" int unetk_conv3d_stat_rows(const unetk_conv3d_desc* d) {
-  if (!desc_ok(d)) return UNETK_E_BADARG;
-  const Geo3 g = geo3(d);
-  if (d->shw == 2) {
-    if (s2lin_ok(d, g)) return plane_plan(d->N * g.Do, g.Ho, g.Wo, d->Cin, d->Cout, g.Do).stat_rows;
-    if (unetk_conv_stride2_ok(d->Cin, d->Cout)) return plane_plan(d->N * g.Do, g.Ho, g.Wo, d->Cin, d->Cout, g.Do, 0, 0, 0, 2).stat_rows;
-    return d->N * SUB_BPS;
-  }
-  return plane_plan(d->N * g.Do, d->H, d->W, d->Cin, d->Cout, g.Do).stat_rows;
-}
-
-// UNETK_KSKIP (measurement; read once): bit 0 = skip the dead 16-channel chunks of a channel-padded contraction axis
-// (unetk_conv3d_desc.cin_live8 / cout_live8), bit 1 = half the MFMAs on a chunk whose upper 8 channels are padding.  Default 3.
-static int kskip() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("UNETK_KSKIP"); v = e ? atoi(e) : 3; }
-  return v;
-}
-static int live_k(const uint32_t live8[2], int K) { return (kskip() & 1) ? 16 * unetk_live_chunks(live8, K) : K; }
-static void set_live(ConvParams& p, const uint32_t live8[2], int K) {
-  if (kskip() & 1) unetk_set_klive(p, live8, K, (kskip() & 2) != 0);
-}
-
-extern "C" size_t unetk_conv3d_ws_bytes(const unetk_conv3d_desc* d) {
-  if (!desc_ok(d)) return 0;
-  const Geo3 g = geo3(d);
-  size_t f = 0;
-  if (d->shw == 2) f += (size_t)d->N * g.Do * d->H * d->W * d->Cout;          // stride-1 result / dilated dy
-  f = (f + 63) & ~(size_t)63;
-  size_t bytes = f * sizeof(float);
-  const size_t wb = wg_runs_bytes(wg_runs(d, g, UNETK_FP32));     // the filter gradient's launches (behind the dilated dy)
-  if (wb > bytes) bytes = wb;
-  if (s2lin_ok(d, g)) {              // space-to-depth copy of x + the stream-K slab of the grouped-tap forward
-    const size_t sb = s2lin_xs_floats(d, g) * sizeof(float) +
-                      plane_plan(d->N * g.Do, g.Ho, g.Wo, d->Cin, d->Cout, g.Do, live_k(d->cin_live8, d->Cin), 0, d->kd * 4).ws_bytes;
-    if (sb > bytes) bytes = sb;
-  }
-  if (d->shw == 1 && d->sd == 1) {   // stream-K slabs of the small-plane kernel, forward and input gradient
-    const size_t kf = plane_plan(d->N * d->D, d->H, d->W, d->Cin, d->Cout, d->D, live_k(d->cin_live8, d->Cin), d->kd).ws_bytes;
-    const size_t kb = plane_plan(d->N * d->D, d->H, d->W, d->Cout, d->Cin, d->D, live_k(d->cout_live8, d->Cout), d->kd).ws_bytes;
-    if (kf > bytes) bytes = kf;
-    if (kb > bytes) bytes = kb;
-  }
-  return bytes;
-}
+extern "C" int unetk_conv3d_stat_rows(const unetk_conv3d_desc* d) { return conv3d_plan(d, UNETK_FP32).stat_rows; }
+extern "C" size_t unetk_conv3d_ws_bytes(const unetk_conv3d_desc* d) { return conv3d_plan(d, UNETK_FP32).ws_bytes; }
 
 extern "C" int unetk_conv3d_fwd(const unetk_conv3d_desc* d, const float* x, const float* wp, float* y,
                                 float* stat_partials, void* ws, size_t ws_bytes, void* stream) {
-  UNETK_REQUIRE(desc_ok(d) && x && wp && y);
-  UNETK_REQUIRE(unetk_aligned16(x) && unetk_aligned16(wp) && unetk_aligned16(y) && d->y_stride % 4 == 0);
-  hipStream_t st = (hipStream_t)stream;
-  const Geo3 g = geo3(d);
-  // stride (.,2,2): natively strided tiles when the MFMA kernel covers the channel counts, else stride-1 + subsample
-  const bool native = d->shw == 2 && unetk_conv_stride2_ok(d->Cin, d->Cout);
-  const bool strided = d->shw == 2 && !native;
-  float* T = y;
-  int ts = d->y_stride;
-  if (strided) {
-    UNETK_REQUIRE(ws && unetk_aligned16(ws) && d->Cout % 4 == 0);
-    if (ws_bytes < unetk_conv3d_ws_bytes(d)) return UNETK_E_WORKSPACE;
-    T = (float*)ws;
-    ts = d->Cout;
-  }
-  const int HWx = d->H * d->W * d->x_stride, HWt = (native ? g.Ho * g.Wo : d->H * d->W) * ts;
-  if (d->kd == 3 && d->sd == 1 && d->shw == 1 && is_lin(plane_plan(d->N * d->D, d->H, d->W, d->Cin, d->Cout, d->D))) {
-    // small planes, depth stride 1 (UNet3D's 24^2 / 12^2 / 6^2 levels): the three depth taps are contracted inside ONE
-    // launch of the linear-pixel kernel (K = 27 Cin) -- no memset, no read-modify-write of y per tap
-    ConvParams p{};
-    p.x = x; p.wp = wp; p.y = y; p.stat = stat_partials;
-    p.N = d->N * d->D; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout;
-    p.xs = d->x_stride; p.ys = d->y_stride;
-    p.xa = planes(HWx, d->D, 1, d->D);
-    p.ya = planes(d->H * d->W * d->y_stride, d->D, 1, d->D);
-    p.spg = d->D;
-    p.kd = 3; p.dshift0 = -g.pb_d; p.dstep = 1;
-    set_live(p, d->cin_live8, d->Cin);
-    if (ws && unetk_aligned16(ws)) { p.sk_slab = (float*)ws; p.sk_slab_bytes = ws_bytes; }
-    return unetk_conv_run(p, st);
-  }
-  if (s2lin_ok(d, g)) {
-    // small OUTPUT planes (UNet3D's 24^2 / 12^2 / 6^2 levels behind a stride-2 layer): space-to-depth copy of x, then ONE
-    // launch of the linear-pixel kernel over kd x 4 tap groups (K = kd x 9 x Cin, every MFMA row an output pixel, stream-K).
-    // The copy lives in ws, and unetk_conv3d_stat_rows counts this kernel's rows: no silent fall-back to the tiled kernel
-    // (it writes more rows) when ws is missing or short
-    UNETK_REQUIRE(ws && unetk_aligned16(ws) && d->x_stride % 4 == 0);
-    if (ws_bytes < unetk_conv3d_ws_bytes(d)) return UNETK_E_WORKSPACE;
-    float* XS = (float*)ws;
-    const int ncls = d->sd == 2 ? 8 : 4;
-    const int64_t npix_out = (int64_t)d->N * g.Do * g.Ho * g.Wo;
-    int64_t grid = (npix_out * ncls * (d->Cin / 4) + 255) / 256;
-    if (grid > 8192) grid = 8192;
-    UNETK_LAUNCH(s2d_kernel, dim3((int)grid), dim3(256), 0, st, x, d->x_stride, XS, npix_out, g.Do, d->D, d->H, d->W, g.Ho, g.Wo,
-                 d->Cin, d->sd);
-    UNETK_LAUNCH_CHECK();
-    ConvParams p{};
-    p.x = XS; p.wp = wp; p.y = y; p.stat = stat_partials;
-    p.N = d->N * g.Do; p.H = g.Ho; p.W = g.Wo; p.Cin = d->Cin; p.Cout = d->Cout;
-    p.xs = ncls * d->Cin; p.ys = d->y_stride;
-    p.xa = planes(g.Ho * g.Wo * ncls * d->Cin, g.Do, 1, g.Do);
-    p.ya = planes(g.Ho * g.Wo * d->y_stride, g.Do, 1, g.Do);
-    p.spg = g.Do;
-    int ng = 0;
-    for (int kd_ = 0; kd_ < d->kd; ++kd_) {
-      const int cd = d->sd == 2 ? (kd_ & 1) : 0;
-      const int dz = d->sd == 2 ? (kd_ >> 1) : kd_ - g.pb_d;      // depth stride 1: input plane = do + kd - pb
-      for (int ph = 0; ph < 2; ++ph)
-        for (int pw = 0; pw < 2; ++pw, ++ng) {
-          p.g_chan[ng] = ((cd * 2 + ph) * 2 + pw) * d->Cin;
-          p.g_dz[ng] = dz;
-          int nt = 0;
-          for (int kh = ph; kh < 3; kh += 2)
-            for (int kw = pw; kw < 3; kw += 2, ++nt) {
-              p.g_off[ng][nt] = 4 * ((kh >> 1) + 1) + ((kw >> 1) + 1);      // output o reads class k & 1 at o + (k >> 1)
-              p.g_panel[ng][nt] = kd_ * 9 + kh * 3 + kw;
-            }
-          p.g_ntaps[ng] = nt;
-        }
-    }
-    p.ng = ng;
-    set_live(p, d->cin_live8, d->Cin);
-    const size_t xsb = s2lin_xs_floats(d, g) * sizeof(float);
-    p.sk_slab = (float*)((char*)ws + xsb); p.sk_slab_bytes = ws_bytes - xsb;
-    return unetk_conv_run(p, st);
-  }
-  if (native && d->kd == 3) {
-    // natively strided (3,3,3) conv (UNet3D's (1,2,2) and (2,2,2) down-sampling layers): the three depth taps are contracted
-    // inside ONE launch of the tiled stride-2 kernel (K = 27 Cin; a tap whose input plane falls outside the sample is
-    // skipped per block) -- no memset, no read-modify-write of y per tap, one prologue / epilogue instead of three
-    ConvParams p{};
-    p.x = x; p.wp = wp; p.y = y; p.stat = stat_partials;
-    p.N = d->N * g.Do; p.H = g.Ho; p.W = g.Wo; p.Cin = d->Cin; p.Cout = d->Cout;
-    p.xs = d->x_stride; p.ys = d->y_stride;
-    p.xa = planes(HWx, g.Do, d->sd, d->D);
-    p.ya = planes(g.Ho * g.Wo * d->y_stride, g.Do, 1, g.Do);
-    p.spg = g.Do;
-    p.stride = 2; p.Hin = d->H; p.Win = d->W; p.pbh = 1 - g.off_h; p.pbw = 1 - g.off_w;
-    p.kd = 3; p.dshift0 = -g.pb_d; p.dstep = 1; p.dsd = d->sd; p.din = d->D; p.dplane = HWx;
-    return unetk_conv_run(p, st);
-  }
-  // order: partial-coverage taps first, a full-coverage tap last (it emits the statistics)
-  int order[3], n_taps = 0, full = -1;
-  for (int dt = 0; dt < d->kd; ++dt) {
-    int lo, hi;
-    tap_range(d, g, dt, &lo, &hi);
-    if (lo == 0 && hi == g.Do - 1 && full < 0) full = dt;
-  }
-  if (full < 0) return UNETK_E_UNSUPPORTED;
-  for (int dt = 0; dt < d->kd; ++dt)
-    if (dt != full) order[n_taps++] = dt;
-  order[n_taps++] = full;
-  if (d->kd > 1) {
-    const int zr = zero_pixels(T, (int64_t)d->N * g.Do * (HWt / ts), d->Cout, ts, st);
-    if (zr != UNETK_OK) return zr;
-  }
-  for (int i = 0; i < n_taps; ++i) {
-    const int dt = order[i];
-    int lo, hi;
-    tap_range(d, g, dt, &lo, &hi);
-    if (hi < lo) continue;
-    ConvParams p{};
-    p.x = x + (int64_t)(lo * d->sd - g.pb_d + dt) * HWx;
-    p.wp = wp + (int64_t)dt * 9 * d->Cin * d->Cout;
-    p.y = T + (int64_t)lo * HWt;
-    p.stat = (i == n_taps - 1 && !strided) ? stat_partials : nullptr;
-    p.N = d->N * (hi - lo + 1); p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout;
-    p.xs = d->x_stride; p.ys = ts;
-    p.xa = planes(HWx, hi - lo + 1, d->sd, d->D);
-    p.ya = planes(HWt, hi - lo + 1, 1, g.Do);
-    p.accumulate = d->kd > 1 ? 1 : 0;
-    p.spg = hi - lo + 1;
-    if (native) {
-      p.stride = 2;
-      p.H = g.Ho; p.W = g.Wo; p.Hin = d->H; p.Win = d->W;
-      p.pbh = 1 - g.off_h; p.pbw = 1 - g.off_w;
-    }
-    int rc = unetk_conv_run(p, st);
-    if (rc != UNETK_OK) return rc;
-  }
-  if (strided) {
-    const ColMap m = unetk_colmap(d->Cout);
-    if (d->Cout > 1024) return UNETK_E_UNSUPPORTED;
-    const size_t lds = stat_partials ? (size_t)2 * m.rows_per_iter * d->Cout * sizeof(float) : 0;
-    UNETK_LAUNCH(subsample2_stats_kernel, dim3(d->N * SUB_BPS), dim3(256), lds, st, T, y, stat_partials, g.Do,
-                       d->H, d->W, g.Ho, g.Wo, d->Cout, d->y_stride, g.off_h, g.off_w, m.cq_n, m.rows_per_iter, SUB_BPS,
-                       d->N * SUB_BPS);
-    UNETK_LAUNCH_CHECK();
-  }
-  return UNETK_OK;
+  return conv3d_fwd(d, UNETK_FP32, x, wp, y, stat_partials, ws, ws_bytes, stream);
 }
-
-namespace {
-// dy -> (Z, stride) usable by the stride-1 backward kernels
-int dilated_dy(const unetk_conv3d_desc* d, const Geo3& g, const float* dy, void* ws, hipStream_t st, const float** z,
-               int* zs) {
-  if (d->shw == 1) {
-    *z = dy;
-    *zs = d->y_stride;
-    return UNETK_OK;
-  }
-  float* Z = (float*)ws;
-  const size_t n = (size_t)d->N * g.Do * d->H * d->W * d->Cout;
-  hipError_t e = hipMemsetAsync(Z, 0, n * sizeof(float), st);
-  if (e != hipSuccess) return (int)e;
-  const int64_t npix_out = (int64_t)d->N * g.Do * g.Ho * g.Wo;
-  int64_t grid = (npix_out * (d->Cout / 4) + 255) / 256;
-  if (grid > 8192) grid = 8192;
-  UNETK_LAUNCH(dilate2_kernel, dim3((int)grid), dim3(256), 0, st, dy, d->y_stride, Z, npix_out, d->H, d->W, g.Ho,
-                     g.Wo, d->Cout, g.off_h, g.off_w);
-  UNETK_LAUNCH_CHECK();
-  *z = Z;
-  *zs = d->Cout;
-  return UNETK_OK;
-}
-}  // namespace
-
 extern "C" int unetk_conv3d_dgrad(const unetk_conv3d_desc* d, const float* dy, const float* wp_dgrad, float* dx,
                                   void* ws, size_t ws_bytes, void* stream) {
-  UNETK_REQUIRE(desc_ok(d) && dy && wp_dgrad && dx);
-  UNETK_REQUIRE(unetk_aligned16(dy) && unetk_aligned16(wp_dgrad) && unetk_aligned16(dx));
-  UNETK_REQUIRE(d->x_stride % 4 == 0 && d->y_stride % 4 == 0 && d->Cout % 4 == 0);
-  if (d->Cout % 16 != 0 || d->Cin % 32 != 0) return UNETK_E_UNSUPPORTED;   // the MFMA kernels' K and N granularity
-  hipStream_t st = (hipStream_t)stream;
-  const Geo3 g = geo3(d);
-  if (d->shw == 2 && unetk_conv_lin_gen_ok(g.Ho, g.Wo, d->Cout, d->Cin)) {
-    // native: one launch per output-parity class of dx, each contracting the undilated dy over its 4 / 2 / 2 / 1 taps
-    //   dx[hi] = sum_{kh = ph, ph+2} dy[a - (kh - ph)/2] w[kh],  ph = (hi + pbh) & 1,  a = (hi + pbh - ph) / 2
-    const int pbh = 1 - g.off_h, pbw = 1 - g.off_w;
-    const int HWx = d->H * d->W * d->x_stride, HWy = g.Ho * g.Wo * d->y_stride;
-    // depth stride 1 with three depth taps (UNet3D's (1,2,2) layers): every dx plane receives all three taps, so they are
-    // contracted in ONE launch (K = 3 x taps x Cout) -- no memset, no accumulation passes
-    const bool fuse_d = d->kd == 3 && d->sd == 1 && d->Cin % 32 == 0;
-    // depth stride 2 (the (2,2,2) bridge; round 5): dx plane di = 2 do + dt (pad-before 0 for an even depth), so the EVEN dx
-    // planes receive the taps dt = 0 (do = di / 2) and dt = 2 (do = di / 2 - 1), the ODD ones dt = 1 alone -- two launches that
-    // each write their planes once (fused taps; no memset, no read-modify-write of dx: three accumulating launches before)
-    static int s2d_on = -1;
-    if (s2d_on < 0) { const char* e = getenv("UNETK_S2LIN"); s2d_on = e ? atoi(e) : 1; }
-    if (s2d_on && d->kd == 3 && d->sd == 2 && (d->D & 1) == 0 && g.pb_d == 0 && d->Cin % 32 == 0) {
-      ConvParams p{};
-      p.x = dy; p.wp = wp_dgrad; p.y = dx;
-      p.N = d->N * g.Do; p.H = g.Ho; p.W = g.Wo; p.Cin = d->Cout; p.Cout = d->Cin;
-      p.xs = d->y_stride; p.ys = d->x_stride;
-      p.xa = planes(HWy, g.Do, 1, g.Do);
-      p.ya = planes(HWx, g.Do, 2, d->D);
-      p.spg = g.Do;
-      p.dshift0 = 0; p.dstep = -1;           // even planes: dy plane do = di / 2 - dt' for the fused taps dt' = 0, 1 (dt = 0, 2)
-      p.dpar = 1; p.dpar_yoff = HWx;          // odd planes: one plane further
-      set_live(p, d->cout_live8, d->Cout);
-      p.os = 2; p.Hd = d->H; p.Wd = d->W;
-      for (int ph = 0; ph < 2; ++ph)
-        for (int pw = 0; pw < 2; ++pw) {
-          const int q = ph * 2 + pw;
-          p.ooh[q] = ph - pbh;
-          p.oow[q] = pw - pbw;
-          for (int kh = ph; kh < 3; kh += 2)
-            for (int kw = pw; kw < 3; kw += 2) {
-              p.tap_off[q][p.ntaps[q]] = 4 * ((ph - kh) / 2 + 1) + ((pw - kw) / 2 + 1);
-              p.tap_panel[q][p.ntaps[q]] = 8 - (kh * 3 + kw);
-              ++p.ntaps[q];
-            }
-        }
-      return unetk_conv_run_lin_gen(p, st);
-    }
-    const bool multi = !fuse_d && (d->kd > 1 || d->sd > 1);
-    if (multi) {
-      const int zr = zero_pixels(dx, (int64_t)d->N * d->D * d->H * d->W, d->Cin, d->x_stride, st);
-      if (zr != UNETK_OK) return zr;
-    }
-    for (int dt = 0; dt < (fuse_d ? 1 : d->kd); ++dt) {
-      int lo, hi;
-      tap_range(d, g, dt, &lo, &hi);
-      if (fuse_d) { lo = 0; hi = g.Do - 1; }
-      if (hi < lo) continue;
-      ConvParams p{};
-      p.x = dy + (int64_t)lo * HWy;
-      p.wp = wp_dgrad + (int64_t)dt * 9 * d->Cin * d->Cout;
-      p.y = dx + (int64_t)(fuse_d ? 0 : lo * d->sd - g.pb_d + dt) * HWx;
-      p.N = d->N * (hi - lo + 1); p.H = g.Ho; p.W = g.Wo; p.Cin = d->Cout; p.Cout = d->Cin;
-      p.xs = d->y_stride; p.ys = d->x_stride;
-      p.xa = planes(HWy, hi - lo + 1, 1, g.Do);
-      p.ya = planes(HWx, hi - lo + 1, d->sd, d->D);
-      p.accumulate = multi ? 1 : 0;
-      p.spg = hi - lo + 1;
-      if (fuse_d) { p.kd = 3; p.dshift0 = g.pb_d; p.dstep = -1; }   // dx[di] = sum_dt dy[di + pb - dt] * w[dt]
-      set_live(p, d->cout_live8, d->Cout);
-      p.os = 2; p.Hd = d->H; p.Wd = d->W;
-      for (int ph = 0; ph < 2; ++ph)
-        for (int pw = 0; pw < 2; ++pw) {
-          const int q = ph * 2 + pw;
-          p.ooh[q] = ph - pbh;
-          p.oow[q] = pw - pbw;
-          for (int kh = ph; kh < 3; kh += 2)
-            for (int kw = pw; kw < 3; kw += 2) {
-              p.tap_off[q][p.ntaps[q]] = 4 * ((ph - kh) / 2 + 1) + ((pw - kw) / 2 + 1);
-              p.tap_panel[q][p.ntaps[q]] = 8 - (kh * 3 + kw);
-              ++p.ntaps[q];
-            }
-        }
-      int rc = unetk_conv_run_lin_gen(p, st);
-      if (rc != UNETK_OK) return rc;
-    }
-    return UNETK_OK;
-  }
-  if (d->shw == 2) {
-    UNETK_REQUIRE(ws && unetk_aligned16(ws));
-    if (ws_bytes < unetk_conv3d_ws_bytes(d)) return UNETK_E_WORKSPACE;
-  }
-  if (d->kd == 3 && d->sd == 1 && d->shw == 1 && is_lin(plane_plan(d->N * d->D, d->H, d->W, d->Cout, d->Cin, d->D))) {
-    // fused depth taps (see unetk_conv3d_fwd): dx[di] = sum_dt dy[di + pb - dt] * w[dt]
-    ConvParams p{};
-    p.x = dy; p.wp = wp_dgrad; p.y = dx; p.stat = nullptr;
-    p.N = d->N * d->D; p.H = d->H; p.W = d->W; p.Cin = d->Cout; p.Cout = d->Cin;
-    p.xs = d->y_stride; p.ys = d->x_stride;
-    p.xa = planes(d->H * d->W * d->y_stride, d->D, 1, d->D);
-    p.ya = planes(d->H * d->W * d->x_stride, d->D, 1, d->D);
-    p.spg = d->D;
-    p.kd = 3; p.dshift0 = g.pb_d; p.dstep = -1;
-    set_live(p, d->cout_live8, d->Cout);
-    if (ws && unetk_aligned16(ws)) { p.sk_slab = (float*)ws; p.sk_slab_bytes = ws_bytes; }
-    return unetk_conv_run(p, st);
-  }
-  const float* Z;
-  int zs;
-  int rc = dilated_dy(d, g, dy, ws, st, &Z, &zs);
-  if (rc != UNETK_OK) return rc;
-  const int HWx = d->H * d->W * d->x_stride, HWz = d->H * d->W * zs;
-  const bool multi = d->kd > 1 || d->sd > 1;
-  if (multi) {
-    const int zr = zero_pixels(dx, (int64_t)d->N * d->D * d->H * d->W, d->Cin, d->x_stride, st);
-    if (zr != UNETK_OK) return zr;
-  }
-  for (int dt = 0; dt < d->kd; ++dt) {
-    int lo, hi;
-    tap_range(d, g, dt, &lo, &hi);
-    if (hi < lo) continue;
-    ConvParams p{};
-    p.x = Z + (int64_t)lo * HWz;                                              // input of the dgrad conv = dy planes
-    p.wp = wp_dgrad + (int64_t)dt * 9 * d->Cin * d->Cout;
-    p.y = dx + (int64_t)(lo * d->sd - g.pb_d + dt) * HWx;                      // output = dx planes di = do*sd - pb + dt
-    p.stat = nullptr;
-    p.N = d->N * (hi - lo + 1); p.H = d->H; p.W = d->W; p.Cin = d->Cout; p.Cout = d->Cin;
-    p.xs = zs; p.ys = d->x_stride;
-    p.xa = planes(HWz, hi - lo + 1, 1, g.Do);
-    p.ya = planes(HWx, hi - lo + 1, d->sd, d->D);
-    p.accumulate = multi ? 1 : 0;
-    p.spg = hi - lo + 1;
-    rc = unetk_conv_run(p, st);
-    if (rc != UNETK_OK) return rc;
-  }
-  return UNETK_OK;
+  return conv3d_dgrad(d, UNETK_FP32, dy, wp_dgrad, dx, ws, ws_bytes, stream);
 }
-
 extern "C" int unetk_conv3d_wgrad(const unetk_conv3d_desc* d, const float* x, const float* dy, float* dw, void* ws,
                                   size_t ws_bytes, void* stream) {
-  UNETK_REQUIRE(desc_ok(d) && x && dy && dw && ws && unetk_aligned16(ws));
-  UNETK_REQUIRE(unetk_aligned16(x) && unetk_aligned16(dy) && unetk_aligned16(dw) && d->y_stride % 4 == 0);
-  if (ws_bytes < unetk_conv3d_ws_bytes(d)) return UNETK_E_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const Geo3 g = geo3(d);
-  const WgRuns r = wg_runs(d, g, UNETK_FP32);
-  const float* Z = dy;
-  int zs = d->y_stride;
-  if (r.zf) {
-    const int rc = dilated_dy(d, g, dy, ws, st, &Z, &zs);
-    if (rc != UNETK_OK) return rc;
-  }
-  return run_wgrad(d, g, r, x, Z, zs, dw, (float*)ws + r.zf, ws_bytes - r.zf * sizeof(float), st);
+  return conv3d_wgrad(d, UNETK_FP32, x, dy, dw, ws, ws_bytes, stream);
 }
 
 // ---------------------------------------------------------------- UNETK_BF16: the stride-1 3-D convs on the bf16 matrix cores
 // (include/unetk.h: the layer rule).  Forward / input gradient: ONE launch of conv3x3_igemm_bf16_kernel per conv, the kd depth
 // taps fused into its K loop (FT); filter gradient: ONE launch of the bf16 conv3x3_wgrad_kernel with WgParams::kd = kd, fixed
-// splits + fixed-order slab reduction.
-namespace {
-bool bf16_rule_ok(const unetk_conv3d_desc* d) {
-  return d->sd == 1 && d->shw == 1 && (d->kd == 1 || d->kd == 3) && d->Cin % 32 == 0 && d->Cout % 32 == 0;
-}
-// every bf16 entry point takes the workspace of unetk_conv3d_ws_bytes_bf16 and refuses a missing, misaligned or short one
-int bf16_ws_check(const unetk_conv3d_desc* d, const void* ws, size_t ws_bytes) {
-  if (!ws || !unetk_aligned16(ws)) return UNETK_E_BADARG;
-  if (ws_bytes < unetk_conv3d_ws_bytes_bf16(d)) return UNETK_E_WORKSPACE;
-  return UNETK_OK;
-}
-}  // namespace
-
+// splits + fixed-order slab reduction.  Every entry point takes the workspace of unetk_conv3d_ws_bytes_bf16 and refuses a
+// missing, misaligned or short one.
 extern "C" int unetk_conv3d_pack_bf16(const float* w, int kd, int Cin, int Cout, void* wp_fwd, void* wp_dgrad, void* stream) {
   UNETK_REQUIRE(w && (kd == 1 || kd == 3) && Cin > 0 && Cout > 0 && (wp_fwd || wp_dgrad));
   if (Cin % 32 != 0 || Cout % 32 != 0) return UNETK_E_UNSUPPORTED;
@@ -693,68 +742,18 @@ extern "C" int unetk_conv3d_pack_bf16(const float* w, int kd, int Cin, int Cout,
   return UNETK_OK;
 }
 
-extern "C" int unetk_conv3d_stat_rows_bf16(const unetk_conv3d_desc* d) {
-  if (!desc_ok(d)) return UNETK_E_BADARG;
-  if (!bf16_rule_ok(d)) return UNETK_E_UNSUPPORTED;
-  const ConvPlan pl = plane_plan(d->N * d->D, d->H, d->W, d->Cin, d->Cout, d->D, 0, 0, 0, 1, UNETK_BF16);
-  return pl.stat_rows > 0 ? pl.stat_rows : pl.rc;
-}
-
-extern "C" size_t unetk_conv3d_ws_bytes_bf16(const unetk_conv3d_desc* d) {
-  if (!desc_ok(d) || !bf16_rule_ok(d)) return 0;
-  return wg_runs_bytes(wg_runs(d, geo3(d), UNETK_BF16));
-}
+extern "C" int unetk_conv3d_stat_rows_bf16(const unetk_conv3d_desc* d) { return conv3d_plan(d, UNETK_BF16).stat_rows; }
+extern "C" size_t unetk_conv3d_ws_bytes_bf16(const unetk_conv3d_desc* d) { return conv3d_plan(d, UNETK_BF16).ws_bytes; }
 
 extern "C" int unetk_conv3d_fwd_bf16(const unetk_conv3d_desc* d, const float* x, const void* wp_fwd, float* y,
                                      float* stat_partials, void* ws, size_t ws_bytes, void* stream) {
-  if (!desc_ok(d)) return UNETK_E_BADARG;
-  if (!bf16_rule_ok(d)) return UNETK_E_UNSUPPORTED;
-  UNETK_REQUIRE(x && wp_fwd && y && unetk_aligned16(x) && unetk_aligned16(wp_fwd) && unetk_aligned16(y));
-  UNETK_REQUIRE(d->x_stride % 4 == 0 && d->y_stride % 4 == 0);
-  const int rc = bf16_ws_check(d, ws, ws_bytes);
-  if (rc != UNETK_OK) return rc;
-  const int HWx = d->H * d->W * d->x_stride;
-  ConvParams p{};
-  p.bf16 = UNETK_BF16;
-  p.x = x; p.wp = (const float*)wp_fwd; p.y = y; p.stat = stat_partials;
-  p.N = d->N * d->D; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout;
-  p.xs = d->x_stride; p.ys = d->y_stride;
-  p.xa = planes(HWx, d->D, 1, d->D);
-  p.ya = planes(d->H * d->W * d->y_stride, d->D, 1, d->D);
-  p.spg = d->D;
-  if (d->kd == 3) { p.kd = 3; p.dsd = 1; p.dshift0 = -1; p.dstep = 1; p.din = d->D; p.dplane = HWx; }   // y[o] = sum_dt x[o - 1 + dt] w[dt]
-  return unetk_conv_run(p, (hipStream_t)stream);
+  return conv3d_fwd(d, UNETK_BF16, x, (const float*)wp_fwd, y, stat_partials, ws, ws_bytes, stream);
 }
-
 extern "C" int unetk_conv3d_dgrad_bf16(const unetk_conv3d_desc* d, const float* dy, const void* wp_dgrad, float* dx,
                                        void* ws, size_t ws_bytes, void* stream) {
-  if (!desc_ok(d)) return UNETK_E_BADARG;
-  if (!bf16_rule_ok(d)) return UNETK_E_UNSUPPORTED;
-  UNETK_REQUIRE(dy && wp_dgrad && dx && unetk_aligned16(dy) && unetk_aligned16(wp_dgrad) && unetk_aligned16(dx));
-  UNETK_REQUIRE(d->x_stride % 4 == 0 && d->y_stride % 4 == 0);
-  const int rc = bf16_ws_check(d, ws, ws_bytes);
-  if (rc != UNETK_OK) return rc;
-  const int HWy = d->H * d->W * d->y_stride;
-  ConvParams p{};
-  p.bf16 = UNETK_BF16;
-  p.x = dy; p.wp = (const float*)wp_dgrad; p.y = dx; p.stat = nullptr;
-  p.N = d->N * d->D; p.H = d->H; p.W = d->W; p.Cin = d->Cout; p.Cout = d->Cin;
-  p.xs = d->y_stride; p.ys = d->x_stride;
-  p.xa = planes(HWy, d->D, 1, d->D);
-  p.ya = planes(d->H * d->W * d->x_stride, d->D, 1, d->D);
-  p.spg = d->D;
-  if (d->kd == 3) { p.kd = 3; p.dsd = 1; p.dshift0 = 1; p.dstep = -1; p.din = d->D; p.dplane = HWy; }   // dx[i] = sum_dt dy[i + 1 - dt] w'[dt]
-  return unetk_conv_run(p, (hipStream_t)stream);
+  return conv3d_dgrad(d, UNETK_BF16, dy, (const float*)wp_dgrad, dx, ws, ws_bytes, stream);
 }
-
 extern "C" int unetk_conv3d_wgrad_bf16(const unetk_conv3d_desc* d, const float* x, const float* dy, float* dw, void* ws,
                                        size_t ws_bytes, void* stream) {
-  if (!desc_ok(d)) return UNETK_E_BADARG;
-  if (!bf16_rule_ok(d)) return UNETK_E_UNSUPPORTED;
-  UNETK_REQUIRE(x && dy && dw && unetk_aligned16(x) && unetk_aligned16(dy) && unetk_aligned16(dw));
-  UNETK_REQUIRE(d->x_stride % 4 == 0 && d->y_stride % 4 == 0);
-  const int rc = bf16_ws_check(d, ws, ws_bytes);
-  if (rc != UNETK_OK) return rc;
-  const Geo3 g = geo3(d);
-  return run_wgrad(d, g, wg_runs(d, g, UNETK_BF16), x, dy, d->y_stride, dw, ws, ws_bytes, (hipStream_t)stream);
+  return conv3d_wgrad(d, UNETK_BF16, x, dy, dw, ws, ws_bytes, stream);
 }

@@ -564,11 +564,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bf16s_kernel(ConvParams p) {
 // (cache-resident), 16 = no barriers in the main loop, 32 = no tile epilogue, 64 = the waits of a tile's first chunk never
 // cover the previous tile's stores, 128 = no output stores, 256 = no halo requests, 512 = no filter-panel requests.
 static int v3_flags() {
-  static int f = -1;
-  if (f < 0) {
-    const char* e = getenv("UNETK_V3_FLAGS");
-    f = e ? atoi(e) : 0;
-  }
+  static const int f = unetk_env_int("UNETK_V3_FLAGS", 0);
   return f;
 }
 

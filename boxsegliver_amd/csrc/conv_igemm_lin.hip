@@ -706,11 +706,7 @@ constexpr int LIN_BM = 128;
 // 512 K pieces instead of 256 whole tiles of 64 x 128) 93 -> 107 TFLOP/s, step 370.3 -> 373.3 slices/s in two interleaved runs;
 // 2 alone 372.3, 14 373.2, bit 0 on top (15) 366.6 (profiles/r05_gunet_lin2d_ab.txt).
 static int lin_2d() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("UNETK_LIN_2D");
-    v = e ? atoi(e) : 6;
-  }
+  static const int v = unetk_env_int("UNETK_LIN_2D", 6);
   return v;
 }
 
@@ -738,11 +734,7 @@ static bool lin_ok(int N, int H, int W, int Cin, int Cout, int spg) {
 // and with every tile cut into K pieces the block count no longer has to fit the CU count.)  Applied to 3-D layers (spg > 1)
 // first; round 5 gave the 2-D nets' starved small planes bits 0 + 1 as well (lin_2d() above).
 static int lin_tune(int N, int H, int W, int spg) {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("UNETK_LIN_TUNE");
-    v = e ? atoi(e) : 7;
-  }
+  static const int v = unetk_env_int("UNETK_LIN_TUNE", 7);
   if (spg > 1) return v;
   // 2-D planes: only those the tiled kernel would FILL (they are here because its grid starves the chip, lin_ok) --
   // with at least 16 blocks of 128 pixels (8 slices of 16 x 16), where the change was measured.  The badly filled small planes

@@ -576,8 +576,7 @@ constexpr int STH = 10, STW = 12;   // stacked-plane tile
 constexpr int S2TH = 4;             // stride-2 tile: 4 x 16 (or 4 x 12, 4 x 6) output pixels, 32-channel ci panels
 
 int wg_s2w6() {        // UNETK_WG_S2W6=0: measurement switch for the 6-wide stride-2 tile (read once)
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("UNETK_WG_S2W6"); v = e ? atoi(e) : 1; }
+  static const int v = unetk_env_int("UNETK_WG_S2W6", 1);
   return v;
 }
 
@@ -770,7 +769,7 @@ int unetk_wgrad_run(WgParams p, float* dw, void* ws, size_t ws_bytes, hipStream_
   // probe build only (tools/probe_v3.sh; WRONG results, timing) of conv3x3_wgrad_bf16s_kernel: 4 = no staging requests, 16 = no
   // barriers, 32 = no epilogue (LDS exchange, slab store, slab_reduce), 2048 = one request behind each of the first five MFMA
   // groups instead of five in a row
-  if (pl.family == WG_BF16S || pl.family == WG_BF16S_C3) { const char* e = getenv("UNETK_V3_FLAGS"); p.dbg = e ? atoi(e) : 0; }
+  if (pl.family == WG_BF16S || pl.family == WG_BF16S_C3) p.dbg = unetk_env_int("UNETK_V3_FLAGS", 0);
 #endif
   const int rc = launch_plan(pl, p, st);
   if (rc != UNETK_OK || pl.S == 1) return rc;

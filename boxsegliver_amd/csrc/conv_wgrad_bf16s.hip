@@ -523,8 +523,8 @@ int unetk_wgrad_launch_bf16s(const WgPlan& pl, const WgParams& p, hipStream_t st
     if (e != hipSuccess) return (int)e;
     attr_done = true;
   }
-  static int deep = -1;          // UNETK_WGRAD_DEEP=1 (measurement): three tiles of load flight, first fragments behind the barrier
-  if (deep < 0) { const char* e = getenv("UNETK_WGRAD_DEEP"); deep = e ? atoi(e) : 0; }
+  // UNETK_WGRAD_DEEP=1 (measurement): three tiles of load flight, first fragments behind the barrier
+  static const int deep = unetk_env_int("UNETK_WGRAD_DEEP", 0);
   if (deep) UNETK_LAUNCH(conv3x3_wgrad_bf16s_kernel<false>, dim3(pl.grid), dim3(512), LDS_B, st, p);
   else UNETK_LAUNCH(conv3x3_wgrad_bf16s_kernel<true>, dim3(pl.grid), dim3(512), LDS_B, st, p);
   UNETK_LAUNCH_CHECK();

@@ -3,11 +3,11 @@ test_gpu_conv3d_sweep.py: the grid of cases, the two exact input kinds, and a re
 
 conv3d.hip builds every UNet3D convolution out of 2-D kernels and sends the forward, the input gradient and the filter gradient
 down one of about a dozen branches chosen by extents, parities and channel counts.  The index arithmetic of those branches
-(tap_range, the SAME pads, the space-to-depth and parity classes, WgRun::lo / hi, the ImgAddr plane strides) is the kind that
+(tap_range, the SAME pads, the space-to-depth and parity classes, Tap / WgRun::lo / hi, the ImgAddr plane strides) is the kind that
 breaks at one residue and not the next, so the sweep runs every branch over a dense grid of small and odd extents with inputs
 for which fp32 arithmetic is exact in any summation order, and compares bit for bit with float64.
 
-branch(case) restates the predicates of conv3d.hip (s2lin_ok, the fused-tap tests, tap_range, wg_runs), conv_igemm_lin.hip
+branch(case) restates the predicates of conv3d.hip (the route tests of conv3d_plan, tap_range, wg_runs), conv_igemm_lin.hip
 (lin_ok, lin_rows_bound, unetk_conv_lin_gen_ok), conv_igemm.hip (unetk_conv_stride2_ok) and conv_wgrad.hip (the channel rule of
 unetk_wgrad_plan at stride 2) with the default switches; decode(case, op, launches) names the branch a traced launch list shows.
 The device test asserts that the two agree for every case, so a change of the dispatch cannot quietly move the cases elsewhere.
@@ -160,6 +160,7 @@ def stride2_ok(cin, cout):
 
 
 def s2lin_ok(c):
+    """conv3d_plan's test for FWD_S2D (at the default UNETK_S2LIN)."""
     g = geo(c)
     if c.stride[1] != 2 or c.h % 2 or c.w % 2 or c.cin % 16:
         return False
@@ -190,7 +191,7 @@ BRANCHES = (F_TAP_TILED, F_TAP_LIN, F_FUSED_LIN, F_S2D, F_S2_KD1, F_S2_KD3, F_SU
 
 
 def _full_tap(c):
-    """The depth tap the forward launches last (conv3d.hip: the first tap that covers every output plane)."""
+    """The depth tap the forward launches last (conv3d.hip Conv3dPlan::tap: the first tap that covers every output plane)."""
     g = geo(c)
     return next(dt for dt in range(c.kd) if tap_range(c, dt) == (0, g.do - 1))
 

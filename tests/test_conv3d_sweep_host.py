@@ -1,7 +1,7 @@
 """No GPU: the sweep of tests/conv3d_sweep_cases.py is what test_gpu_conv3d_sweep.py needs it to be.
 
   * every branch of the composition has grid cases under the restatement of the dispatch, and the input gradient's dilated
-    fallback (conv3d.hip, the end of unetk_conv3d_dgrad) has at least 100 in each stride-2 family;
+    fallback (conv3d.hip, DGRAD_DILATED) has at least 100 in each stride-2 family;
   * every case is in the exact regime of its input kind, from its own float64 reference: fp32 sums are exact in any order, so the
     device test may ask for bit equality;
   * the host-callable queries of the library (pure host arithmetic) hold their contracts at every extent up to 40.

@@ -531,7 +531,7 @@ CONV3D_ROWS = [
     # The workspace query has to size the slabs of the launches that run, not of a launch over every plane.
     ("first_layer_resplit", (1, 8, 96, 96, 1, 32, 3, 1, 1), 0, 0, None, ("conv3x3_direct_kernel<1, float>",), None,
      ("conv3x3_wgrad_c3_kernel<32>",)),
-    # the input gradient's fallback for dy planes the four-class kernel refuses (the end of unetk_conv3d_dgrad): dy zero-dilated
+    # the input gradient's fallback for dy planes the four-class kernel refuses (conv3d.hip DGRAD_DILATED): dy zero-dilated
     # into the workspace, dx zeroed, one accumulating stride-1 launch per depth tap -- dy planes 8 x 80, 4 x 112 and 2 x 1
     ("dgrad_dilated_w80", (1, 2, 16, 160, 32, 64, 1, 1, 2), 32, 64, None, (IGEMM + "4, 1, 1, 2, 2, 1, 0>",),
      ("dilate2_kernel", IGEMM + "4, 1, 2, 1, 1, 1, 0>"), (WG_S2,)),

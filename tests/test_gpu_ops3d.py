@@ -47,7 +47,7 @@ CASES = [
     (3, 1, 6, 6, 64, 64, 3, (1, 1, 1)),        # three one-plane samples side by side, stacked-plane filter gradient
     # stride-2 input gradient on dy planes the four-class linear-pixel kernel refuses (unetk_conv_lin_gen_ok: the padded rows
     # of a pixel block pass its LDS bound): dy zero-dilated into the workspace, dx zeroed, one accumulating stride-1 launch
-    # per depth tap onto depth-strided dx planes (the end of unetk_conv3d_dgrad)
+    # per depth tap onto depth-strided dx planes (conv3d.hip DGRAD_DILATED)
     (1, 2, 16, 160, 32, 64, 1, (1, 2, 2)),     # dy 8 x 80: the first stride-2 layer of a 12 x 160 x 160 patch
     (1, 3, 8, 224, 64, 64, 3, (1, 2, 2)),      # dy 4 x 112: 224-wide patches, three depth taps
     (1, 4, 4, 2, 64, 64, 3, (2, 2, 2)),        # dy 2 x 1: a plane narrower than any tile, depth stride 2
