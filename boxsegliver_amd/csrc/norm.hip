@@ -21,6 +21,9 @@
 // norm), else 1; a launch group indexes the statistics with stride sst (C or 0).
 #include "common.h"
 
+#include <algorithm>
+#include <initializer_list>
+
 namespace {
 
 constexpr int MAXG = 4;   // guide channels
@@ -40,27 +43,23 @@ constexpr int MAXG = 4;   // guide channels
 #define UNETK_NORM_RGROUPS_BF 2
 #endif
 
-struct NormGeom {
-  int Ns;        // statistic groups (1 for batch norm, N for instance norm)
-  int64_t Ps;    // pixels per statistic group
+// Statistics geometry: any C > 0.  The finalise entry points and their query use nothing else.
+struct StatGeom { int Ns; int64_t Ps; };   // statistic groups (1 for batch norm, N for instance norm), pixels per group
+StatGeom stat_geom(const unetk_norm_desc* d) {
+  return {d->per_sample ? d->N : 1, d->per_sample ? (int64_t)d->HW : (int64_t)d->N * d->HW};
+}
+
+// Launch geometry: only once C % 4 == 0 && C <= 1024 is established (unetk_colmap divides by C / 4, then 256 by the quotient).
+struct LaunchGeom {
   int L;         // launch groups
   int64_t P;     // pixels per launch group
   int sst;       // statistics stride of a launch group (C or 0)
-  int C, cq_n, rpi;
+  int cq_n, rpi;
 };
-
-NormGeom geom(const unetk_norm_desc* d, bool density) {
-  NormGeom g;
-  g.Ns = d->per_sample ? d->N : 1;
-  g.Ps = d->per_sample ? (int64_t)d->HW : (int64_t)d->N * d->HW;
-  g.L = (d->per_sample || density) ? d->N : 1;
-  g.P = g.L > 1 ? (int64_t)d->HW : (int64_t)d->N * d->HW;
-  g.sst = d->per_sample ? d->C : 0;
-  g.C = d->C;
+LaunchGeom launch_geom(const unetk_norm_desc* d, bool per_sample_groups) {
+  const int L = (d->per_sample || per_sample_groups) ? d->N : 1;
   const ColMap m = unetk_colmap(d->C);
-  g.cq_n = m.cq_n;
-  g.rpi = m.rows_per_iter;
-  return g;
+  return {L, L > 1 ? (int64_t)d->HW : (int64_t)d->N * d->HW, d->per_sample ? d->C : 0, m.cq_n, m.rows_per_iter};
 }
 
 // The batch statistics come in one pass, var = E[y^2] - E[y]^2 from fp32 partials: three fp32 roundings (the epilogue's row
@@ -843,29 +842,46 @@ bool norm_desc_ok(const unetk_norm_desc* d) {
 }
 bool norm_supported(const unetk_norm_desc* d) { return d->C % 4 == 0 && d->C <= 1024; }
 
-int bwd_blocks(const NormGeom& g) {
-  int64_t b = (g.P + g.rpi - 1) / g.rpi;
+int bwd_blocks(const LaunchGeom& g) {
+  const int64_t b = (g.P + g.rpi - 1) / g.rpi;
   // per launch group; few groups (instance norm at batch 1-2: UNet3D's 96^3 tensors) need more blocks each to fill the GPU
   const int64_t cap = g.L > 1 ? (2048 / g.L > 64 ? 2048 / g.L : 64) : UNETK_COL_BLOCKS;
-  if (b > cap) b = cap;
-  return (int)b;
+  return (int)(b > cap ? cap : b);
 }
 
-#define G_DISPATCH(G_, CALL) \
+// blocks of an apply pass, per launch group, over `pixels` rows of work (P, or the P / 4 windows of the pool pair)
+int apply_grid(int64_t pixels, const LaunchGeom& g) {
+  const int64_t b = (pixels + g.rpi - 1) / g.rpi;
+  const int64_t cap = g.L > 1 ? (4096 + g.L - 1) / g.L : 4096;
+  return (int)(b > cap ? cap : b);
+}
+
+// the tensors of a call are float (16-byte accesses) or bf16_t (8-byte); no other storage has kernels
+bool norm_storage_ok(int storage, std::initializer_list<const void*> tensors) {
+  bool ok = storage == UNETK_FP32 || storage == UNETK_BF16S;
+  for (const void* p : tensors) ok = ok && (storage == UNETK_BF16S ? unetk_aligned8(p) : unetk_aligned16(p));
+  return ok;
+}
+
+// a guide comes with its weights and its gb block (columns gw_coff .. gw_coff + C of rows gw_stride wide); gb alone is a bare shift
+bool guide_operands_ok(const unetk_norm_desc* d, const float* guide, const float* gw, const float* gb) {
+  if (d->guide_ch > 0 &&
+      !(guide && gw && gb && d->gw_stride >= d->gw_coff + d->C && d->gw_stride % 4 == 0 && unetk_aligned16(gw)))
+    return false;
+  return !gb || (d->gw_coff % 4 == 0 && d->gw_coff >= 0 && unetk_aligned16(gb));
+}
+
+// the call is the variadic part: once expanded, its commas stand outside parentheses
+#define GL_DISPATCH(G_, ...) \
   switch (G_) {              \
-    case 0: { constexpr int GG = 0; CALL; } break; \
-    case 1: { constexpr int GG = 1; CALL; } break; \
-    case 2: { constexpr int GG = 2; CALL; } break; \
-    case 3: { constexpr int GG = 3; CALL; } break; \
-    default: { constexpr int GG = 4; CALL; } break; \
+    case 1: { constexpr int GG = 1; __VA_ARGS__; } break; \
+    case 2: { constexpr int GG = 2; __VA_ARGS__; } break; \
+    case 3: { constexpr int GG = 3; __VA_ARGS__; } break; \
+    default: { constexpr int GG = 4; __VA_ARGS__; } break; \
   }
-#define GL_DISPATCH(G_, CALL) \
-  switch (G_) {              \
-    case 1: { constexpr int GG = 1; CALL; } break; \
-    case 2: { constexpr int GG = 2; CALL; } break; \
-    case 3: { constexpr int GG = 3; CALL; } break; \
-    default: { constexpr int GG = 4; CALL; } break; \
-  }
+#define G_DISPATCH(G_, ...)                              \
+  if (G_ == 0) { constexpr int GG = 0; __VA_ARGS__; } \
+  else GL_DISPATCH(G_, __VA_ARGS__)
 #define GD_DISPATCH_T(TT, G_, D_, L_, KERN, ...)                                               \
   if (L_ && D_) { GL_DISPATCH(G_, UNETK_LAUNCH((KERN<GG, true, true, TT>), __VA_ARGS__)); } \
   else if (L_) { GL_DISPATCH(G_, UNETK_LAUNCH((KERN<GG, false, true, TT>), __VA_ARGS__)); }   \
@@ -875,6 +891,10 @@ int bwd_blocks(const NormGeom& g) {
 #define GD_DISPATCH(S_, G_, D_, L_, KERN, ...)                      \
   if (S_) { GD_DISPATCH_T(bf16_t, G_, D_, L_, KERN, __VA_ARGS__) } \
   else { GD_DISPATCH_T(float, G_, D_, L_, KERN, __VA_ARGS__) }
+// CALL for the storage type of the tensors, which it names TT (the kernels that GD_DISPATCH does not cover)
+#define T_DISPATCH(S_, CALL)             \
+  if (S_) { using TT = bf16_t; CALL; } \
+  else { using TT = float; CALL; }
 
 // ---- plain unit whose activation feeds a 2 x 2 max-pool AND the skip connection (UNet.py:80-81,93: every encoder level's
 // second conv): the pool's backward is folded into both passes.  dz of pixel i of a window = dskip_i + (i is the window's
@@ -998,17 +1018,147 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_pool_kernel(BwdArgs a, Poo
     });
 }
 
+// ---- one decision per apply / backward / side-pass call, as ConvPlan / WgPlan / DeconvPlan / Conv3dPlan.  norm_plan (pure host
+// arithmetic, no HIP calls) derives from the descriptor, the kind of call and WHICH optional operands are present everything the
+// entry points and unetk_norm_bwd_ws_bytes do: refusals, launch geometry, template variant, both grids, the route of the dy
+// formula's sums, the tail launches, the workspace layout.  The entry points validate pointers, plan, launch; nothing below the
+// plan refuses a shape, chooses a grid or computes an offset.  Return codes: the first rule a call breaks decides, in one order:
+//   1. BADARG, entry point: the descriptor's ranges (norm_desc_ok), a missing required pointer, a stride below C
+//   2. UNSUPPORTED, plan: C % 4, C > 1024, stride % 4; the pool pair's guide / leaky / dropout and W / HW rules; drop_pool's affine_only
+//   3. BADARG, plan: the keep range (0, 1] of the two dropout side passes; the storage.  `shaped` from here on (the geometry is
+//      defined); the pool pair and the side passes have no further plan rule
+//   4. BADARG, entry point: alignment, the guide's operands and strides, den without dden, gb without dgb
+//   5. WORKSPACE, entry point (backward): ws_bytes below the query -- which is 0 where 6a or 6c refuses: those keep their code
+//   6. plan, `unit` calls: a. leaky without a guide (UNSUPPORTED)  b. post without density or gb, or with pre_partials (UNSUPPORTED)
+//      c. dropout_keep outside [0, 1] (BADARG)  d. backward: dropout with a guide or gb but neither density nor leaky (UNSUPPORTED:
+//      the guide-bias sum needs the density variant, pass den = 1)  e. guide_per_sample with one launch group (UNSUPPORTED)
+//      f. pre_partials with guide, density, gb, dropout or affine_only (UNSUPPORTED)  g. pre_rows no multiple of L > 0 (BADARG)
+enum NormCall { NORM_APPLY, NORM_BWD, NORM_POOL_APPLY, NORM_POOL_BWD, NORM_SE_ADD, NORM_SE_ADD_DROP, NORM_DROP_POOL };
+struct NormOperands { bool den, gb, dgb, pre; int pre_rows; };   // which optional operands the call was given
+enum { WS_PARTIAL, WS_SUMS, WS_PSUM, WS_TMP1, WS_TMP2, WS_END };
+struct NormWs { size_t at[WS_END + 1]; };   // the backward's workspace in floats from its start; at[WS_END] = its size
+struct NormPlan {
+  int rc;
+  bool shaped;                   // rules 2 and 3 passed
+  StatGeom s;
+  LaunchGeom g;
+  int G, K;                      // guide channels; rows of the reduce pass
+  bool D, leaky, post, gps, bs;  // density, leaky guide, guide_leaky == 3, per-sample guide weights, bf16 storage
+  bool simple;                   // K = 2 and no dgb: d beta / d gamma ARE the two totals, written by the last reduction launch
+  size_t lds;                    // [K][rpi][C] floats of the reduce pass (and of unetk_norm_drop_pool)
+  int gw_ns, gb_ns;              // per-sample strides of gw / gb
+  float alpha;
+  int nblk, gx, pre_rows;        // per launch group: blocks of the reduce pass, of the apply pass; pre_partials rows
+  int tot;                       // WS_ index of the sums over all launch groups: the per-group sums themselves when L == 1
+  int ksum, kst, krow;           // the dy formula's sums: WS_ index, stride per launch group, offset of the second row
+  int kb, groups;                // gps: the guide-bias row of the per-group sums; post: groups of the dgb block
+  size_t dden;                   // D: float offset of the density-gradient rows [N][C]
+  NormWs ws;
+};
+
+NormWs bwd_ws_layout(int K, int L, int nblk, int C) {
+  NormWs w;
+  w.at[WS_PARTIAL] = 0;                                                   // [K][L][nblk][C]
+  w.at[WS_SUMS] = (size_t)K * L * nblk * C;                               // [K][L][C]: sums per launch group
+  w.at[WS_PSUM] = w.at[WS_SUMS] + (size_t)K * L * C;                      // [K][C]: sums over groups
+  w.at[WS_TMP1] = w.at[WS_PSUM] + (size_t)K * C;                          // pre-computed partials may have any row count
+  w.at[WS_TMP2] = w.at[WS_TMP1] + unetk_rows_reduce_tmp_floats(K * L, UNETK_RR_DIRECT_ROWS + 1, C);
+  w.at[WS_END] = w.at[WS_TMP2] + unetk_rows_reduce_tmp_floats(K, L, C);
+  return w;
+}
+
+NormPlan norm_plan(const unetk_norm_desc* d, NormCall call, int stride, int W, NormOperands p) {
+  NormPlan pl{};
+  const bool pool = call == NORM_POOL_APPLY || call == NORM_POOL_BWD;
+  const bool unit = call == NORM_APPLY || call == NORM_BWD;
+  pl.rc = UNETK_E_UNSUPPORTED;
+  if (!norm_supported(d) || stride % 4 != 0) return pl;
+  if (pool && (d->guide_ch > 0 || d->guide_leaky || d->dropout_keep > 0.f)) return pl;
+  if (pool && (W < 2 || (W & 1) || d->HW % W != 0 || ((d->HW / W) & 1))) return pl;
+  if (call == NORM_DROP_POOL && d->affine_only) return pl;
+  pl.rc = UNETK_E_BADARG;
+  if ((call == NORM_SE_ADD_DROP || call == NORM_DROP_POOL) && !(d->dropout_keep > 0.f && d->dropout_keep <= 1.f)) return pl;
+  if (!norm_storage_ok(d->storage, {})) return pl;
+  pl.shaped = true;
+  pl.s = stat_geom(d);
+  pl.g = launch_geom(d, p.den || !(unit || pool));       // a side pass: one launch group per sample
+  pl.G = d->guide_ch; pl.D = p.den; pl.leaky = d->guide_leaky != 0; pl.gps = d->guide_per_sample != 0;
+  pl.post = d->guide_leaky == 3;                         // gb and dgb are then blocks: [4][C] ([N][4][C] per sample)
+  pl.bs = d->storage == UNETK_BF16S;
+  if (unit) {
+    const bool drop = d->dropout_keep > 0.f;
+    pl.rc = UNETK_E_UNSUPPORTED;
+    if (pl.leaky && pl.G < 1) return pl;
+    if (pl.post && (!p.den || !p.gb || p.pre)) return pl;
+    if (d->dropout_keep < 0.f || d->dropout_keep > 1.f) { pl.rc = UNETK_E_BADARG; return pl; }
+    if (call == NORM_BWD && drop && (p.gb || pl.G > 0) && !pl.D && !pl.leaky) return pl;
+    if (pl.gps && pl.g.L != d->N) return pl;
+    if (p.pre && (pl.G > 0 || pl.D || pl.leaky || p.gb || drop || d->affine_only)) return pl;
+    if (p.pre && !(p.pre_rows > 0 && p.pre_rows % pl.g.L == 0)) { pl.rc = UNETK_E_BADARG; return pl; }
+  }
+  pl.rc = UNETK_OK;
+  pl.K = unit ? 2 + pl.G + (pl.D ? 2 : (pl.leaky ? 1 : 0)) + (pl.post ? 1 : 0) : 2;
+  pl.simple = pl.G == 0 && !pl.D && !pl.leaky && !p.dgb;
+  pl.lds = (size_t)pl.K * pl.g.rpi * d->C * sizeof(float);
+  pl.gw_ns = pl.gps ? pl.G * d->gw_stride : 0; pl.gb_ns = pl.gps ? (pl.post ? 4 : 1) * d->gw_stride : 0;
+  pl.alpha = d->guide_leaky == 2 ? d->guide_alpha : 0.2f;
+  pl.nblk = bwd_blocks(pl.g);
+  pl.gx = apply_grid(pool ? pl.g.P >> 2 : pl.g.P, pl.g);
+  pl.pre_rows = p.pre ? p.pre_rows / pl.g.L : 0;
+  // the statistics sums of the dy formula: per launch group when the statistics are per sample, else the batch totals
+  pl.tot = pl.g.L == 1 ? WS_SUMS : WS_PSUM;
+  pl.ksum = d->per_sample ? WS_SUMS : pl.tot; pl.kst = d->per_sample ? d->C : 0; pl.krow = d->per_sample ? pl.g.L * d->C : d->C;
+  pl.kb = (pl.D || pl.leaky) ? 2 + pl.G : 0; pl.groups = pl.gps ? d->N : 1;
+  pl.ws = bwd_ws_layout(pl.K, pl.g.L, pl.nblk, d->C);
+  pl.dden = pl.ws.at[WS_SUMS] + (size_t)(3 + pl.G) * pl.g.L * d->C;     // the per-sample row sum du * t
+  return pl;
+}
+
+// what the plain and the pool-fused apply pass share (the pool kernel reads neither density, guide nor dropout fields)
+ApplyArgs apply_args(const unetk_norm_desc* d, const NormPlan& pl, const void* y, const float* scale, const float* shift,
+                     const float* den, const float* guide, const float* gw, const float* gb, void* z) {
+  return ApplyArgs{y, scale, shift, den, guide, gw, gb, z, pl.g.P, d->C, d->z_stride, pl.g.cq_n, pl.g.rpi, d->gw_stride,
+                   d->gw_coff, pl.g.sst, pl.gw_ns, pl.gb_ns, pl.post ? 1 : 0, pl.alpha, d->dropout_keep, d->dropout_seed};
+}
+
+// both passes of a backward, plain or pool-fused (dz = dskip there)
+BwdArgs bwd_args(const unetk_norm_desc* d, const NormPlan& pl, float* ws, const void* y, const void* dz, int dz_stride,
+                 const float* scale, const float* shift, const float* mean, const float* rstd, const float* den,
+                 const float* guide, const float* gw, const float* gb, void* dy) {
+  BwdArgs a{};
+  a.y = y; a.dz = dz; a.scale = scale; a.shift = shift; a.mean = mean; a.rstd = rstd; a.den = den;
+  a.guide = guide; a.gw = gw; a.gb = gb; a.partial = ws + pl.ws.at[WS_PARTIAL]; a.dy = dy;
+  a.ksum = ws + pl.ws.at[pl.ksum]; a.kst = pl.kst; a.krow = pl.krow;
+  a.P = pl.g.P; a.inv_ps = 1.0f / (float)pl.s.Ps; a.C = d->C; a.dzs = dz_stride; a.cq_n = pl.g.cq_n; a.rpi = pl.g.rpi;
+  a.gw_stride = d->gw_stride; a.gw_coff = d->gw_coff; a.L = pl.g.L; a.plain = d->affine_only; a.sst = pl.g.sst;
+  a.gw_ns = pl.gw_ns; a.gb_ns = pl.gb_ns; a.alpha = pl.alpha; a.keep = d->dropout_keep; a.seed = d->dropout_seed;
+  a.post = pl.post ? 1 : 0;
+  return a;
+}
+
+// src[K L][rows][C] (the reduce pass's partials, or pre_partials) -> sums[K][L][C] -> (L > 1) psum[K][C].  A simple plan's two
+// totals are d beta / d gamma: the last launch writes them as well.
+int bwd_sums(const NormPlan& pl, int C, const float* src, int rows, float* ws, float* dbeta, float* dgamma, hipStream_t st) {
+  float *const al0 = pl.simple ? dbeta : nullptr, *const al1 = pl.simple ? dgamma : nullptr;
+  const bool last1 = pl.g.L == 1;
+  float* sums = ws + pl.ws.at[WS_SUMS];
+  const int rc = unetk_rows_reduce_alias(src, pl.K * pl.g.L, rows, C, sums, ws + pl.ws.at[WS_TMP1], last1 ? al0 : nullptr,
+                                         last1 ? al1 : nullptr, st);
+  if (rc != UNETK_OK || last1) return rc;
+  return unetk_rows_reduce_alias(sums, pl.K, pl.g.L, C, ws + pl.ws.at[WS_PSUM], ws + pl.ws.at[WS_TMP2], al0, al1, st);
+}
+
 }  // namespace
 
 // bytes of the first part of the workspace (sums, first-level row sums), rounded up to 16: the refinement scratch follows
-size_t finalize_ws_base(const unetk_norm_desc* d, const NormGeom& g, int stat_rows) {
+size_t finalize_ws_base(const unetk_norm_desc* d, const StatGeom& g, int stat_rows) {
   const size_t f = 2 * (size_t)g.Ns * d->C + unetk_rows_reduce_tmp_floats(2 * g.Ns, stat_rows / g.Ns, d->C);
   return (f * sizeof(float) + 15) / 16 * 16;
 }
 
 extern "C" size_t unetk_norm_finalize_ws_bytes(const unetk_norm_desc* d, int stat_rows) {
   if (!norm_desc_ok(d) || stat_rows <= 0) return 0;
-  const NormGeom g = geom(d, false);
+  const StatGeom g = stat_geom(d);
   const size_t cblocks = (d->C + 15) / 16;
   // refinement (unetk_norm_finalize_y): part[Ns][cblocks][PB][2][16] and one[Ns][C][2] doubles, flags[Ns][C],
   // counters[Ns][cblocks]
@@ -1030,49 +1180,44 @@ extern "C" int unetk_norm_finalize_y(const unetk_norm_desc* d, const float* stat
                                      float* scale_out, float* shift_out, void* ws, size_t ws_bytes, void* stream) {
   UNETK_REQUIRE(norm_desc_ok(d) && mean_out && rstd_out && scale_out && shift_out);
   hipStream_t st = (hipStream_t)stream;
-  const NormGeom g = geom(d, false);
-  const int use_moving = (!d->per_sample && !training) ? 1 : 0;
-  float* sums = nullptr;
-  if (!use_moving) {
-    UNETK_REQUIRE(stat_partials && stat_rows > 0 && ws && stat_rows % g.Ns == 0);
-    UNETK_REQUIRE(!y || (d->storage == UNETK_FP32 && norm_supported(d) && unetk_aligned16(y) && unetk_aligned16(mean_out)));
-    if (ws_bytes < unetk_norm_finalize_ws_bytes(d, stat_rows)) return UNETK_E_WORKSPACE;
-    sums = (float*)ws;
-    // partials are [2][stat_rows][C] with each image's tiles contiguous -> [2*Ns][rows_per_group][C]
-    const float* src = stat_partials;
-    int rows = stat_rows / g.Ns;
-    if (rows > UNETK_RR_DIRECT_ROWS) {   // first level: 64 row blocks per (statistic, group)
-      int rc = unetk_rows_reduce_l1(stat_partials, 2 * g.Ns, rows, d->C, sums + 2 * g.Ns * d->C, st);
-      if (rc != UNETK_OK) return rc;
-      src = sums + 2 * g.Ns * d->C;
-      rows = 64;
-    }
-    const int update_moving = (!d->per_sample && training && moving_mean && moving_var) ? 1 : 0;
-    const int cblocks = (d->C + 15) / 16, PB = refine_blocks(g.Ps);
-    double* part = (double*)((char*)ws + finalize_ws_base(d, g, stat_rows));
-    double* one = part + (size_t)g.Ns * cblocks * PB * 32;
-    int* flags = y ? (int*)(one + (size_t)g.Ns * d->C * 2) : nullptr;
-    unsigned* counters = y ? (unsigned*)(flags + (size_t)g.Ns * d->C) : nullptr;
-    UNETK_LAUNCH(norm_reduce_finalize_kernel, dim3(cblocks * g.Ns), dim3(256), 0, st, src, rows, g.Ns, d->C,
-                       (double)g.Ps, gamma, beta, eps, decay, update_moving, moving_mean, moving_var, mean_out, rstd_out,
-                       scale_out, shift_out, flags, counters, one);
-    UNETK_LAUNCH_CHECK();
-    if (y) {
-      UNETK_LAUNCH(norm_refine_kernel, dim3(PB * cblocks * g.Ns), dim3(256), 0, st, y, g.Ps, g.Ns, d->C, PB, (double)g.Ps,
-                   gamma, beta, eps, decay, update_moving, moving_mean, moving_var, mean_out, rstd_out, scale_out,
-                   shift_out, flags, counters, part, one);
-      UNETK_LAUNCH_CHECK();
-    }
-    return UNETK_OK;
-  } else {
+  const StatGeom g = stat_geom(d);
+  if (!d->per_sample && !training) {   // batch norm at inference: the moving statistics
     UNETK_REQUIRE(moving_mean && moving_var);
+    UNETK_LAUNCH(norm_finalize_kernel, dim3((g.Ns * d->C + 255) / 256), dim3(256), 0, st, (const float*)nullptr, g.Ns, d->C,
+                       (double)g.Ps, gamma, beta, eps, decay, 1, 0, moving_mean, moving_var, mean_out, rstd_out, scale_out,
+                       shift_out);
+    UNETK_LAUNCH_CHECK();
+    return UNETK_OK;
+  }
+  UNETK_REQUIRE(stat_partials && stat_rows > 0 && ws && stat_rows % g.Ns == 0);
+  UNETK_REQUIRE(!y || (d->storage == UNETK_FP32 && norm_supported(d) && unetk_aligned16(y) && unetk_aligned16(mean_out)));
+  if (ws_bytes < unetk_norm_finalize_ws_bytes(d, stat_rows)) return UNETK_E_WORKSPACE;
+  float* sums = (float*)ws;
+  // partials are [2][stat_rows][C] with each image's tiles contiguous -> [2*Ns][rows_per_group][C]
+  const float* src = stat_partials;
+  int rows = stat_rows / g.Ns;
+  if (rows > UNETK_RR_DIRECT_ROWS) {   // first level: 64 row blocks per (statistic, group)
+    int rc = unetk_rows_reduce_l1(stat_partials, 2 * g.Ns, rows, d->C, sums + 2 * g.Ns * d->C, st);
+    if (rc != UNETK_OK) return rc;
+    src = sums + 2 * g.Ns * d->C;
+    rows = 64;
   }
   const int update_moving = (!d->per_sample && training && moving_mean && moving_var) ? 1 : 0;
-  const int total = g.Ns * d->C;
-  UNETK_LAUNCH(norm_finalize_kernel, dim3((total + 255) / 256), dim3(256), 0, st, sums, g.Ns, d->C, (double)g.Ps,
-                     gamma, beta, eps, decay, use_moving, update_moving, moving_mean, moving_var, mean_out, rstd_out,
-                     scale_out, shift_out);
+  const int cblocks = (d->C + 15) / 16, PB = refine_blocks(g.Ps);
+  double* part = (double*)((char*)ws + finalize_ws_base(d, g, stat_rows));
+  double* one = part + (size_t)g.Ns * cblocks * PB * 32;
+  int* flags = y ? (int*)(one + (size_t)g.Ns * d->C * 2) : nullptr;
+  unsigned* counters = y ? (unsigned*)(flags + (size_t)g.Ns * d->C) : nullptr;
+  UNETK_LAUNCH(norm_reduce_finalize_kernel, dim3(cblocks * g.Ns), dim3(256), 0, st, src, rows, g.Ns, d->C, (double)g.Ps, gamma,
+                     beta, eps, decay, update_moving, moving_mean, moving_var, mean_out, rstd_out, scale_out, shift_out, flags,
+                     counters, one);
   UNETK_LAUNCH_CHECK();
+  if (y) {
+    UNETK_LAUNCH(norm_refine_kernel, dim3(PB * cblocks * g.Ns), dim3(256), 0, st, y, g.Ps, g.Ns, d->C, PB, (double)g.Ps, gamma,
+                 beta, eps, decay, update_moving, moving_mean, moving_var, mean_out, rstd_out, scale_out, shift_out, flags,
+                 counters, part, one);
+    UNETK_LAUNCH_CHECK();
+  }
   return UNETK_OK;
 }
 
@@ -1080,32 +1225,13 @@ extern "C" int unetk_norm_apply_relu(const unetk_norm_desc* d, const void* y, co
                                      const float* den, const float* guide, const float* gw, const float* gb, void* z,
                                      void* stream) {
   UNETK_REQUIRE(norm_desc_ok(d) && y && scale && shift && z && d->z_stride >= d->C);
-  if (!norm_supported(d) || d->z_stride % 4 != 0) return UNETK_E_UNSUPPORTED;
-  const bool bs = d->storage == UNETK_BF16S;
-  UNETK_REQUIRE(d->storage == UNETK_FP32 || bs);
-  UNETK_REQUIRE(bs ? (unetk_aligned8(y) && unetk_aligned8(z)) : (unetk_aligned16(y) && unetk_aligned16(z)));
-  UNETK_REQUIRE(unetk_aligned16(scale) && unetk_aligned16(shift));
-  UNETK_REQUIRE(!den || unetk_aligned16(den));
-  if (d->guide_ch > 0) {
-    UNETK_REQUIRE(guide && gw && gb && d->gw_stride >= d->gw_coff + d->C);
-    UNETK_REQUIRE(d->gw_stride % 4 == 0 && unetk_aligned16(gw));
-  }
-  UNETK_REQUIRE(!gb || (d->gw_coff % 4 == 0 && d->gw_coff >= 0 && unetk_aligned16(gb)));
-  const NormGeom g = geom(d, den != nullptr);
-  if (d->dropout_keep < 0.f || d->dropout_keep > 1.f) return UNETK_E_BADARG;
-  if (d->guide_per_sample && g.L != d->N) return UNETK_E_UNSUPPORTED;      // needs one launch group per sample
-  ApplyArgs a{y, scale, shift, den, guide, gw, gb, z, g.P, d->C, d->z_stride, g.cq_n, g.rpi, d->gw_stride, d->gw_coff, g.sst,
-              d->guide_per_sample ? d->guide_ch * d->gw_stride : 0,
-              d->guide_per_sample ? (d->guide_leaky == 3 ? 4 : 1) * d->gw_stride : 0, d->guide_leaky == 3 ? 1 : 0,
-              d->guide_leaky == 2 ? d->guide_alpha : 0.2f,
-              d->dropout_keep, d->dropout_seed};
-  int64_t gx = (g.P + g.rpi - 1) / g.rpi;
-  const int64_t cap = g.L > 1 ? (4096 + g.L - 1) / g.L : 4096;
-  if (gx > cap) gx = cap;
-  const bool leaky = d->guide_leaky != 0;
-  if (leaky && d->guide_ch < 1) return UNETK_E_UNSUPPORTED;
-  if (d->guide_leaky == 3 && (den == nullptr || gb == nullptr)) return UNETK_E_UNSUPPORTED;     // post vectors: with density gains only
-  GD_DISPATCH(bs, d->guide_ch, den != nullptr, leaky, norm_apply_relu_kernel, dim3((int)gx, g.L), dim3(256), 0, (hipStream_t)stream, a);
+  const NormPlan pl = norm_plan(d, NORM_APPLY, d->z_stride, 0, {den != nullptr, gb != nullptr, false, false, 0});
+  if (!pl.shaped) return pl.rc;
+  UNETK_REQUIRE(norm_storage_ok(d->storage, {y, z}) && unetk_aligned16(scale) && unetk_aligned16(shift));
+  UNETK_REQUIRE((!den || unetk_aligned16(den)) && guide_operands_ok(d, guide, gw, gb));
+  if (pl.rc != UNETK_OK) return pl.rc;
+  const ApplyArgs a = apply_args(d, pl, y, scale, shift, den, guide, gw, gb, z);
+  GD_DISPATCH(pl.bs, pl.G, pl.D, pl.leaky, norm_apply_relu_kernel, dim3(pl.gx, pl.g.L), dim3(256), 0, (hipStream_t)stream, a);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }
@@ -1115,47 +1241,28 @@ extern "C" int unetk_norm_apply_relu(const unetk_norm_desc* d, const void* y, co
 extern "C" int unetk_norm_apply_relu_pool(const unetk_norm_desc* d, int W, const void* y, const float* scale, const float* shift,
                                           void* z, void* pooled, void* stream) {
   UNETK_REQUIRE(norm_desc_ok(d) && y && scale && shift && z && pooled && d->z_stride >= d->C);
-  if (!norm_supported(d) || d->z_stride % 4 != 0) return UNETK_E_UNSUPPORTED;
-  if (d->guide_ch > 0 || d->guide_leaky || d->dropout_keep > 0.f) return UNETK_E_UNSUPPORTED;
-  if (W < 2 || (W & 1) || d->HW % W != 0 || ((d->HW / W) & 1)) return UNETK_E_UNSUPPORTED;
-  const bool bs = d->storage == UNETK_BF16S;
-  UNETK_REQUIRE(d->storage == UNETK_FP32 || bs);
-  UNETK_REQUIRE(bs ? (unetk_aligned8(y) && unetk_aligned8(z) && unetk_aligned8(pooled))
-                   : (unetk_aligned16(y) && unetk_aligned16(z) && unetk_aligned16(pooled)));
-  UNETK_REQUIRE(unetk_aligned16(scale) && unetk_aligned16(shift));
-  const NormGeom g = geom(d, false);
-  ApplyArgs a{};
-  a.y = y; a.scale = scale; a.shift = shift; a.z = z; a.P = g.P; a.C = d->C; a.zs = d->z_stride; a.cq_n = g.cq_n; a.rpi = g.rpi;
-  a.sst = g.sst;
-  int64_t gx = ((g.P >> 2) + g.rpi - 1) / g.rpi;
-  const int64_t cap = g.L > 1 ? (4096 + g.L - 1) / g.L : 4096;
-  if (gx > cap) gx = cap;
-  if (bs) UNETK_LAUNCH(norm_apply_relu_pool_kernel<bf16_t>, dim3((int)gx, g.L), dim3(256), 0, (hipStream_t)stream, a, pooled,
-                             d->HW / W, W, g.L);
-  else UNETK_LAUNCH(norm_apply_relu_pool_kernel<float>, dim3((int)gx, g.L), dim3(256), 0, (hipStream_t)stream, a, pooled,
-                          d->HW / W, W, g.L);
+  const NormPlan pl = norm_plan(d, NORM_POOL_APPLY, d->z_stride, W, {});
+  if (pl.rc != UNETK_OK) return pl.rc;
+  UNETK_REQUIRE(norm_storage_ok(d->storage, {y, z, pooled}) && unetk_aligned16(scale) && unetk_aligned16(shift));
+  const ApplyArgs a = apply_args(d, pl, y, scale, shift, nullptr, nullptr, nullptr, nullptr, z);
+  T_DISPATCH(pl.bs, UNETK_LAUNCH(norm_apply_relu_pool_kernel<TT>, dim3(pl.gx, pl.g.L), dim3(256), 0, (hipStream_t)stream, a,
+                                 pooled, d->HW / W, W, pl.g.L));
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }
 
 extern "C" size_t unetk_norm_bwd_ws_bytes(const unetk_norm_desc* d) {
-  if (!norm_desc_ok(d) || !norm_supported(d)) return 0;
-  // what the backward refuses on the descriptor alone has no workspace either
-  if (d->storage != UNETK_FP32 && d->storage != UNETK_BF16S) return 0;
-  if (d->dropout_keep < 0.f || d->dropout_keep > 1.f) return 0;
-  if (d->guide_leaky != 0 && d->guide_ch < 1) return 0;
-  // sized for the density variant (K + 2 rows, N launch groups): a superset of every other case
-  const NormGeom g = geom(d, true);
-  const int K = 5 + d->guide_ch;          // density + leaky guide + post-shift row: the largest variant
-  NormGeom g1 = geom(d, false);
-  int nblk = bwd_blocks(g);
-  const int nblk1 = bwd_blocks(g1);
-  size_t f = (size_t)K * ((size_t)g.L * nblk > (size_t)g1.L * nblk1 ? (size_t)g.L * nblk : (size_t)g1.L * nblk1) * d->C;
-  f += (size_t)K * g.L * d->C;                                       // sums per launch group
-  f += (size_t)K * d->C;                                             // sums over groups
-  if (nblk1 > nblk) nblk = nblk1;
-  f += unetk_rows_reduce_tmp_floats(K * g.L, UNETK_RR_DIRECT_ROWS + 1, d->C);              // always: pre-computed partials may have any row count
-  f += unetk_rows_reduce_tmp_floats(K, g.L, d->C);
+  if (!norm_desc_ok(d)) return 0;
+  // planned with density and a gb block: no rule refuses BECAUSE one of them is there, so what this plan refuses, every plan of
+  // the descriptor refuses -- and has no workspace.  Else one size for every variant: each segment as long as its longest, which
+  // is K = 5 + G rows (density + leaky guide + post-shift row) over the density and the plain geometry.
+  const NormPlan pl = norm_plan(d, NORM_BWD, d->C, 0, {true, true, true, false, 0});
+  if (pl.rc != UNETK_OK) return 0;
+  const int K = 5 + d->guide_ch;
+  const LaunchGeom g1 = launch_geom(d, false);
+  const NormWs a = bwd_ws_layout(K, pl.g.L, pl.nblk, d->C), b = bwd_ws_layout(K, g1.L, bwd_blocks(g1), d->C);
+  size_t f = 0;
+  for (int i = 0; i < WS_END; ++i) f += std::max(a.at[i + 1] - a.at[i], b.at[i + 1] - b.at[i]);
   return f * sizeof(float);
 }
 
@@ -1177,106 +1284,51 @@ extern "C" int unetk_norm_relu_bwd_pre(const unetk_norm_desc* d, const void* y, 
                                        float* dgamma, float* dbeta, float* dden, float* dgw, float* dgb,
                                        const float* pre_partials, int pre_rows, void* ws, size_t ws_bytes, void* stream) {
   UNETK_REQUIRE(norm_desc_ok(d) && y && dz && scale && shift && mean && rstd && dy && ws && dz_stride >= d->C);
-  if (!norm_supported(d) || dz_stride % 4 != 0) return UNETK_E_UNSUPPORTED;
-  const bool bs = d->storage == UNETK_BF16S;
-  UNETK_REQUIRE(d->storage == UNETK_FP32 || bs);
-  UNETK_REQUIRE(bs ? (unetk_aligned8(y) && unetk_aligned8(dz) && unetk_aligned8(dy))
-                   : (unetk_aligned16(y) && unetk_aligned16(dz) && unetk_aligned16(dy)));
-  UNETK_REQUIRE(unetk_aligned16(ws));
-  const int G = d->guide_ch;
-  const bool D = den != nullptr;
-  UNETK_REQUIRE(!D || (dden && unetk_aligned16(den)));
-  if (G > 0) {
-    UNETK_REQUIRE(guide && gw && gb && dgw && d->gw_stride >= d->gw_coff + d->C);
-    UNETK_REQUIRE(d->gw_stride % 4 == 0 && unetk_aligned16(gw));
-  }
-  UNETK_REQUIRE(!gb || (dgb && d->gw_coff % 4 == 0 && d->gw_coff >= 0 && unetk_aligned16(gb)));
+  const NormPlan pl = norm_plan(d, NORM_BWD, dz_stride, 0,
+                                {den != nullptr, gb != nullptr, dgb != nullptr, pre_partials != nullptr, pre_rows});
+  if (!pl.shaped) return pl.rc;
+  UNETK_REQUIRE(norm_storage_ok(d->storage, {y, dz, dy}) && unetk_aligned16(ws));
+  UNETK_REQUIRE(!den || (dden && unetk_aligned16(den)));
+  UNETK_REQUIRE(guide_operands_ok(d, guide, gw, gb) && (pl.G == 0 || dgw) && (!gb || dgb));
   if (ws_bytes < unetk_norm_bwd_ws_bytes(d)) return UNETK_E_WORKSPACE;
+  if (pl.rc != UNETK_OK) return pl.rc;
   hipStream_t st = (hipStream_t)stream;
-  const NormGeom g = geom(d, D);
-  const bool leaky = d->guide_leaky != 0;
-  if (leaky && G < 1) return UNETK_E_UNSUPPORTED;
-  const bool post = d->guide_leaky == 3;     // dgb is then the gradient of the whole gb block: [4][C] ([N][4][C] per sample)
-  if (post && (!D || !gb || pre_partials != nullptr)) return UNETK_E_UNSUPPORTED;
-  const int K = 2 + G + (D ? 2 : (leaky ? 1 : 0)) + (post ? 1 : 0);
-  const int nblk = bwd_blocks(g);
-  float* partial = (float*)ws;
-  float* sums = partial + (size_t)K * g.L * nblk * d->C;
-  float* psum = sums + (size_t)K * g.L * d->C;
-  float* tmp1 = psum + (size_t)K * d->C;
-  float* tmp2 = tmp1 + unetk_rows_reduce_tmp_floats(K * g.L, UNETK_RR_DIRECT_ROWS + 1, d->C);
-  BwdArgs a{};
-  a.y = y; a.dz = dz; a.scale = scale; a.shift = shift; a.mean = mean; a.rstd = rstd; a.den = den;
-  a.guide = guide; a.gw = gw; a.gb = gb; a.partial = partial; a.dy = dy;
-  a.P = g.P; a.inv_ps = 1.0f / (float)g.Ps; a.C = d->C; a.dzs = dz_stride; a.cq_n = g.cq_n; a.rpi = g.rpi;
-  a.gw_stride = d->gw_stride; a.gw_coff = d->gw_coff; a.L = g.L; a.plain = d->affine_only; a.sst = g.sst;
-  if (d->dropout_keep < 0.f || d->dropout_keep > 1.f) return UNETK_E_BADARG;
-  if (d->dropout_keep > 0.f && (gb || G > 0) && !D && !leaky) return UNETK_E_UNSUPPORTED;   // the guide-bias sum needs the density variant (pass den = 1)
-  if (d->guide_per_sample && g.L != d->N) return UNETK_E_UNSUPPORTED;
-  a.gw_ns = d->guide_per_sample ? G * d->gw_stride : 0; a.gb_ns = d->guide_per_sample ? (post ? 4 : 1) * d->gw_stride : 0;
-  a.alpha = d->guide_leaky == 2 ? d->guide_alpha : 0.2f; a.keep = d->dropout_keep; a.seed = d->dropout_seed;
-  a.post = post ? 1 : 0;
-  // the statistics sums of the dy formula: per launch group when the statistics are per sample, else the batch totals
-  if (d->per_sample) { a.ksum = sums; a.kst = d->C; a.krow = g.L * d->C; }
-  else if (g.L == 1) { a.ksum = sums; a.kst = 0; a.krow = d->C; }
-  else { a.ksum = psum; a.kst = 0; a.krow = d->C; }
-  const size_t lds = (size_t)K * g.rpi * d->C * sizeof(float);
-  int rc;
-  // plain unit (K = 2: sum du, sum du * xhat): d beta / d gamma ARE the two totals, written by the last reduction launch
-  const bool simple = G == 0 && !D && !leaky && dgb == nullptr;
-  float* const al0 = simple ? dbeta : nullptr;
-  float* const al1 = simple ? dgamma : nullptr;
-  const bool last1 = g.L == 1;
-  if (pre_partials != nullptr) {
-    if (G > 0 || D || leaky || gb || d->dropout_keep > 0.f || d->affine_only) return UNETK_E_UNSUPPORTED;
-    UNETK_REQUIRE(pre_rows > 0 && pre_rows % g.L == 0);
-    rc = unetk_rows_reduce_alias(pre_partials, K * g.L, pre_rows / g.L, d->C, sums, tmp1, last1 ? al0 : nullptr,
-                                 last1 ? al1 : nullptr, st);   // -> sums[K][L][C]
-  } else {
-    if (post) {
-      if (bs) { GL_DISPATCH(G, UNETK_LAUNCH((norm_bwd_reduce_kernel<GG, true, true, bf16_t, true>), dim3(nblk, g.L), dim3(256), lds, st, a)); }
-      else { GL_DISPATCH(G, UNETK_LAUNCH((norm_bwd_reduce_kernel<GG, true, true, float, true>), dim3(nblk, g.L), dim3(256), lds, st, a)); }
+  float* const wsf = (float*)ws;
+  const BwdArgs a = bwd_args(d, pl, wsf, y, dz, dz_stride, scale, shift, mean, rstd, den, guide, gw, gb, dy);
+  const int G = pl.G;
+  int rc = pre_partials ? bwd_sums(pl, d->C, pre_partials, pl.pre_rows, wsf, dbeta, dgamma, st) : UNETK_OK;
+  if (!pre_partials) {
+    if (pl.post) {
+      T_DISPATCH(pl.bs, GL_DISPATCH(G, UNETK_LAUNCH((norm_bwd_reduce_kernel<GG, true, true, TT, true>), dim3(pl.nblk, pl.g.L),
+                                                    dim3(256), pl.lds, st, a)));
     } else {
-      GD_DISPATCH(bs, G, D, leaky, norm_bwd_reduce_kernel, dim3(nblk, g.L), dim3(256), lds, st, a);
+      GD_DISPATCH(pl.bs, G, pl.D, pl.leaky, norm_bwd_reduce_kernel, dim3(pl.nblk, pl.g.L), dim3(256), pl.lds, st, a);
     }
     UNETK_LAUNCH_CHECK();
-    rc = unetk_rows_reduce_alias(partial, K * g.L, nblk, d->C, sums, tmp1, last1 ? al0 : nullptr, last1 ? al1 : nullptr,
-                                 st);                          // -> sums[K][L][C]
+    rc = bwd_sums(pl, d->C, a.partial, pl.nblk, wsf, dbeta, dgamma, st);
   }
   if (rc != UNETK_OK) return rc;
-  if (g.L == 1) {
-    psum = sums;                                                               // one launch group: nothing to add up
-  } else {
-    rc = unetk_rows_reduce_alias(sums, K, g.L, d->C, psum, tmp2, al0, al1, st);   // -> psum[K][C]
-    if (rc != UNETK_OK) return rc;
-  }
-  const bool gps = d->guide_per_sample != 0;
-  if (!simple) {
-    UNETK_LAUNCH(norm_bwd_params_kernel, dim3((d->C + 255) / 256), dim3(256), 0, st, psum, d->C, gps ? 0 : G,
-                       (D || leaky) ? 1 : 0, dgamma, dbeta, gps ? nullptr : dgw, (gps || post) ? nullptr : dgb);
+  const float *sums = wsf + pl.ws.at[WS_SUMS], *tot = wsf + pl.ws.at[pl.tot];
+  if (!pl.simple) {
+    UNETK_LAUNCH(norm_bwd_params_kernel, dim3((d->C + 255) / 256), dim3(256), 0, st, tot, d->C, pl.gps ? 0 : G,
+                       (pl.D || pl.leaky) ? 1 : 0, dgamma, dbeta, pl.gps ? nullptr : dgw, (pl.gps || pl.post) ? nullptr : dgb);
     UNETK_LAUNCH_CHECK();
   }
-  if (gps) {   // dgw [N][G][C], dgb [N][C]: the per-launch-group sums, not their total
-    const int kb = (D || leaky) ? 2 + G : 0;
-    UNETK_LAUNCH(norm_bwd_guide_ps_kernel, dim3((d->N * d->C + 255) / 256), dim3(256), 0, st, sums, d->N, d->C, G, kb, dgw,
-                       post ? nullptr : dgb);
+  if (pl.gps) {   // dgw [N][G][C], dgb [N][C]: the per-launch-group sums, not their total
+    UNETK_LAUNCH(norm_bwd_guide_ps_kernel, dim3((d->N * d->C + 255) / 256), dim3(256), 0, st, sums, d->N, d->C, G, pl.kb, dgw,
+                       pl.post ? nullptr : dgb);
     UNETK_LAUNCH_CHECK();
   }
-  if (post) {  // gradient of the gb block: bias row = sum dg, slope rows = 0 (constants of the fold's sign), post-shift row = sum du
-    const int groups = gps ? d->N : 1;
-    UNETK_LAUNCH(norm_bwd_post_block_kernel, dim3((groups * d->C + 255) / 256), dim3(256), 0, st, gps ? sums : psum, groups,
-                       d->C, G, dgb);
+  if (pl.post) {  // gradient of the gb block: bias row = sum dg, slope rows = 0 (constants of the fold's sign), post-shift row = sum du
+    UNETK_LAUNCH(norm_bwd_post_block_kernel, dim3((pl.groups * d->C + 255) / 256), dim3(256), 0, st, pl.gps ? sums : tot,
+                       pl.groups, d->C, G, dgb);
     UNETK_LAUNCH_CHECK();
   }
-  if (D) {   // density gradient: the per-sample row sum du * t
-    hipError_t e = hipMemcpyAsync(dden, sums + (size_t)(3 + G) * g.L * d->C, (size_t)d->N * d->C * sizeof(float),
-                                  hipMemcpyDeviceToDevice, st);
+  if (pl.D) {   // density gradient
+    hipError_t e = hipMemcpyAsync(dden, wsf + pl.dden, (size_t)d->N * d->C * sizeof(float), hipMemcpyDeviceToDevice, st);
     if (e != hipSuccess) return (int)e;
   }
-  int64_t gx = (g.P + g.rpi - 1) / g.rpi;
-  const int64_t cap = g.L > 1 ? (4096 + g.L - 1) / g.L : 4096;
-  if (gx > cap) gx = cap;
-  GD_DISPATCH(bs, G, D, leaky, norm_bwd_apply_kernel, dim3((int)gx, g.L), dim3(256), 0, st, a);
+  GD_DISPATCH(pl.bs, G, pl.D, pl.leaky, norm_bwd_apply_kernel, dim3(pl.gx, pl.g.L), dim3(256), 0, st, a);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }
@@ -1289,47 +1341,19 @@ extern "C" int unetk_norm_relu_bwd_pool(const unetk_norm_desc* d, int W, const v
                                         const float* rstd, void* dy, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
                                         void* stream) {
   UNETK_REQUIRE(norm_desc_ok(d) && y && dskip && dp && scale && shift && mean && rstd && dy && ws && dskip_stride >= d->C);
-  if (!norm_supported(d) || dskip_stride % 4 != 0) return UNETK_E_UNSUPPORTED;
-  if (d->guide_ch > 0 || d->guide_leaky || d->dropout_keep > 0.f) return UNETK_E_UNSUPPORTED;
-  if (W < 2 || (W & 1) || d->HW % W != 0 || ((d->HW / W) & 1)) return UNETK_E_UNSUPPORTED;
-  const bool bs = d->storage == UNETK_BF16S;
-  UNETK_REQUIRE(d->storage == UNETK_FP32 || bs);
-  UNETK_REQUIRE(bs ? (unetk_aligned8(y) && unetk_aligned8(dskip) && unetk_aligned8(dp) && unetk_aligned8(dy))
-                   : (unetk_aligned16(y) && unetk_aligned16(dskip) && unetk_aligned16(dp) && unetk_aligned16(dy)));
-  UNETK_REQUIRE(unetk_aligned16(ws));
+  const NormPlan pl = norm_plan(d, NORM_POOL_BWD, dskip_stride, W, {});
+  if (pl.rc != UNETK_OK) return pl.rc;
+  UNETK_REQUIRE(norm_storage_ok(d->storage, {y, dskip, dp, dy}) && unetk_aligned16(ws));
   if (ws_bytes < unetk_norm_bwd_ws_bytes(d)) return UNETK_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const NormGeom g = geom(d, false);
-  const int K = 2;
-  const int nblk = bwd_blocks(g);
-  float* partial = (float*)ws;
-  float* sums = partial + (size_t)K * g.L * nblk * d->C;
-  float* psum = sums + (size_t)K * g.L * d->C;
-  float* tmp1 = psum + (size_t)K * d->C;
-  float* tmp2 = tmp1 + unetk_rows_reduce_tmp_floats(K * g.L, UNETK_RR_DIRECT_ROWS + 1, d->C);
-  BwdArgs a{};
-  a.y = y; a.dz = dskip; a.scale = scale; a.shift = shift; a.mean = mean; a.rstd = rstd; a.partial = partial; a.dy = dy;
-  a.P = g.P; a.inv_ps = 1.0f / (float)g.Ps; a.C = d->C; a.dzs = dskip_stride; a.cq_n = g.cq_n; a.rpi = g.rpi;
-  a.L = g.L; a.plain = d->affine_only; a.sst = g.sst;
-  if (d->per_sample) { a.ksum = sums; a.kst = d->C; a.krow = g.L * d->C; }
-  else { a.ksum = sums; a.kst = 0; a.krow = d->C; }                 // batch statistics: one launch group
-  PoolArgs pa{dp, d->HW / W, W};
-  const size_t lds = (size_t)K * g.rpi * d->C * sizeof(float);
-  const bool last1 = g.L == 1;
-  if (bs) UNETK_LAUNCH(norm_bwd_reduce_pool_kernel<bf16_t>, dim3(nblk, g.L), dim3(256), lds, st, a, pa);
-  else UNETK_LAUNCH(norm_bwd_reduce_pool_kernel<float>, dim3(nblk, g.L), dim3(256), lds, st, a, pa);
+  float* const wsf = (float*)ws;
+  const BwdArgs a = bwd_args(d, pl, wsf, y, dskip, dskip_stride, scale, shift, mean, rstd, nullptr, nullptr, nullptr, nullptr, dy);
+  const PoolArgs pa{dp, d->HW / W, W};
+  T_DISPATCH(pl.bs, UNETK_LAUNCH(norm_bwd_reduce_pool_kernel<TT>, dim3(pl.nblk, pl.g.L), dim3(256), pl.lds, st, a, pa));
   UNETK_LAUNCH_CHECK();
-  int rc = unetk_rows_reduce_alias(partial, K * g.L, nblk, d->C, sums, tmp1, last1 ? dbeta : nullptr, last1 ? dgamma : nullptr, st);
+  const int rc = bwd_sums(pl, d->C, a.partial, pl.nblk, wsf, dbeta, dgamma, st);
   if (rc != UNETK_OK) return rc;
-  if (!last1) {
-    rc = unetk_rows_reduce_alias(sums, K, g.L, d->C, psum, tmp2, dbeta, dgamma, st);
-    if (rc != UNETK_OK) return rc;
-  }
-  int64_t gx = ((g.P >> 2) + g.rpi - 1) / g.rpi;
-  const int64_t cap = g.L > 1 ? (4096 + g.L - 1) / g.L : 4096;
-  if (gx > cap) gx = cap;
-  if (bs) UNETK_LAUNCH(norm_bwd_apply_pool_kernel<bf16_t>, dim3((int)gx, g.L), dim3(256), 0, st, a, pa);
-  else UNETK_LAUNCH(norm_bwd_apply_pool_kernel<float>, dim3((int)gx, g.L), dim3(256), 0, st, a, pa);
+  T_DISPATCH(pl.bs, UNETK_LAUNCH(norm_bwd_apply_pool_kernel<TT>, dim3(pl.gx, pl.g.L), dim3(256), 0, st, a, pa));
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }
@@ -1339,19 +1363,11 @@ extern "C" int unetk_norm_relu_bwd_pool(const unetk_norm_desc* d, int W, const v
 extern "C" int unetk_norm_drop_pool(const unetk_norm_desc* d, const void* y, const float* mean, const float* rstd, float* sums,
                                     void* stream) {
   UNETK_REQUIRE(norm_desc_ok(d) && y && mean && rstd && sums);
-  if (!norm_supported(d) || d->affine_only) return UNETK_E_UNSUPPORTED;
-  if (!(d->dropout_keep > 0.f && d->dropout_keep <= 1.f)) return UNETK_E_BADARG;
-  const bool bs = d->storage == UNETK_BF16S;
-  UNETK_REQUIRE(d->storage == UNETK_FP32 || bs);
-  UNETK_REQUIRE(bs ? unetk_aligned8(y) : unetk_aligned16(y));
-  const NormGeom g = geom(d, true);            // one launch group per sample
-  const size_t lds = (size_t)2 * g.rpi * d->C * sizeof(float);
-  if (bs)
-    UNETK_LAUNCH(norm_drop_pool_kernel<bf16_t>, dim3(d->N), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)y, mean, rstd,
-                       sums, g.P, d->C, g.cq_n, g.rpi, g.sst, d->N, d->dropout_keep, d->dropout_seed);
-  else
-    UNETK_LAUNCH(norm_drop_pool_kernel<float>, dim3(d->N), dim3(256), lds, (hipStream_t)stream, (const float*)y, mean, rstd,
-                       sums, g.P, d->C, g.cq_n, g.rpi, g.sst, d->N, d->dropout_keep, d->dropout_seed);
+  const NormPlan pl = norm_plan(d, NORM_DROP_POOL, d->C, 0, {});
+  if (pl.rc != UNETK_OK) return pl.rc;
+  UNETK_REQUIRE(norm_storage_ok(d->storage, {y}));
+  T_DISPATCH(pl.bs, UNETK_LAUNCH(norm_drop_pool_kernel<TT>, dim3(d->N), dim3(256), pl.lds, (hipStream_t)stream, (const TT*)y, mean,
+                                 rstd, sums, pl.g.P, d->C, pl.g.cq_n, pl.g.rpi, pl.g.sst, d->N, d->dropout_keep, d->dropout_seed));
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }
@@ -1360,23 +1376,14 @@ extern "C" int unetk_norm_drop_pool(const unetk_norm_desc* d, const void* y, con
 extern "C" int unetk_norm_se_bwd_add_drop(const unetk_norm_desc* d, const void* y, void* dy, const float* mean, const float* rstd,
                                           const float* scale, const float* E, const float* k1, const float* k2, void* stream) {
   UNETK_REQUIRE(norm_desc_ok(d) && y && dy && mean && rstd && scale && E && k1 && k2);
-  if (!norm_supported(d)) return UNETK_E_UNSUPPORTED;
-  if (!(d->dropout_keep > 0.f && d->dropout_keep <= 1.f)) return UNETK_E_BADARG;
-  const bool bs = d->storage == UNETK_BF16S;
-  UNETK_REQUIRE(d->storage == UNETK_FP32 || bs);
-  UNETK_REQUIRE(bs ? (unetk_aligned8(y) && unetk_aligned8(dy)) : (unetk_aligned16(y) && unetk_aligned16(dy)));
+  const NormPlan pl = norm_plan(d, NORM_SE_ADD_DROP, d->C, 0, {});
+  if (pl.rc != UNETK_OK) return pl.rc;
+  UNETK_REQUIRE(norm_storage_ok(d->storage, {y, dy}));
   UNETK_REQUIRE(unetk_aligned16(E) && unetk_aligned16(k1) && unetk_aligned16(k2) && unetk_aligned16(mean) && unetk_aligned16(rstd) &&
                 unetk_aligned16(scale));
-  NormGeom g = geom(d, true);
-  int64_t gx = (g.P + g.rpi - 1) / g.rpi;
-  const int64_t cap = (4096 + g.L - 1) / g.L;
-  if (gx > cap) gx = cap;
-  if (bs)
-    UNETK_LAUNCH(norm_se_bwd_add_drop_kernel<bf16_t>, dim3((int)gx, g.L), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)y,
-                       (bf16_t*)dy, mean, rstd, scale, E, k1, k2, g.P, d->C, g.cq_n, g.rpi, g.sst, d->dropout_keep, d->dropout_seed);
-  else
-    UNETK_LAUNCH(norm_se_bwd_add_drop_kernel<float>, dim3((int)gx, g.L), dim3(256), 0, (hipStream_t)stream, (const float*)y,
-                       (float*)dy, mean, rstd, scale, E, k1, k2, g.P, d->C, g.cq_n, g.rpi, g.sst, d->dropout_keep, d->dropout_seed);
+  T_DISPATCH(pl.bs, UNETK_LAUNCH(norm_se_bwd_add_drop_kernel<TT>, dim3(pl.gx, pl.g.L), dim3(256), 0, (hipStream_t)stream,
+                                 (const TT*)y, (TT*)dy, mean, rstd, scale, E, k1, k2, pl.g.P, d->C, pl.g.cq_n, pl.g.rpi, pl.g.sst,
+                                 d->dropout_keep, d->dropout_seed));
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }
@@ -1384,21 +1391,12 @@ extern "C" int unetk_norm_se_bwd_add_drop(const unetk_norm_desc* d, const void* 
 extern "C" int unetk_norm_se_bwd_add(const unetk_norm_desc* d, const void* y, void* dy, const float* mean, const float* rstd,
                                      const float* scale, const float* A, const float* k2, void* stream) {
   UNETK_REQUIRE(norm_desc_ok(d) && y && dy && mean && rstd && scale && A && k2);
-  if (!norm_supported(d)) return UNETK_E_UNSUPPORTED;
-  const bool bs = d->storage == UNETK_BF16S;
-  UNETK_REQUIRE(d->storage == UNETK_FP32 || bs);
-  UNETK_REQUIRE(bs ? (unetk_aligned8(y) && unetk_aligned8(dy)) : (unetk_aligned16(y) && unetk_aligned16(dy)));
+  const NormPlan pl = norm_plan(d, NORM_SE_ADD, d->C, 0, {});      // one launch group per sample: A is per (sample, channel)
+  if (pl.rc != UNETK_OK) return pl.rc;
+  UNETK_REQUIRE(norm_storage_ok(d->storage, {y, dy}));
   UNETK_REQUIRE(unetk_aligned16(A) && unetk_aligned16(k2) && unetk_aligned16(mean) && unetk_aligned16(rstd) && unetk_aligned16(scale));
-  NormGeom g = geom(d, true);            // one launch group per sample: A is per (sample, channel)
-  int64_t gx = (g.P + g.rpi - 1) / g.rpi;
-  const int64_t cap = (4096 + g.L - 1) / g.L;
-  if (gx > cap) gx = cap;
-  if (bs)
-    UNETK_LAUNCH(norm_se_bwd_add_kernel<bf16_t>, dim3((int)gx, g.L), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)y,
-                       (bf16_t*)dy, mean, rstd, scale, A, k2, g.P, d->C, g.cq_n, g.rpi, g.sst);
-  else
-    UNETK_LAUNCH(norm_se_bwd_add_kernel<float>, dim3((int)gx, g.L), dim3(256), 0, (hipStream_t)stream, (const float*)y,
-                       (float*)dy, mean, rstd, scale, A, k2, g.P, d->C, g.cq_n, g.rpi, g.sst);
+  T_DISPATCH(pl.bs, UNETK_LAUNCH(norm_se_bwd_add_kernel<TT>, dim3(pl.gx, pl.g.L), dim3(256), 0, (hipStream_t)stream, (const TT*)y,
+                                 (TT*)dy, mean, rstd, scale, A, k2, pl.g.P, d->C, pl.g.cq_n, pl.g.rpi, pl.g.sst));
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }

@@ -773,6 +773,13 @@ def norm_apply_relu(d, y, aff, z, guide=None, gw=None, gb=None, den=None):
     return z
 
 
+def _norm_refused(op, d):
+    """unetk_norm_bwd_ws_bytes(d) == 0: the backward refuses the descriptor whatever operands come with it (NormPlan, norm.hip)."""
+    return ("{}: the norm descriptor is refused (N {} HW {} C {} guide_ch {} guide_leaky {} storage {} dropout_keep {}): the backward "
+            "needs N, HW > 0, C % 4 == 0, C <= 1024, guide_ch in 0..4, fp32 or bf16 storage, dropout_keep in [0, 1] and a guide "
+            "under guide_leaky").format(op, d.N, d.HW, d.C, d.guide_ch, d.guide_leaky, d.storage, d.dropout_keep)
+
+
 def norm_relu_bwd(d, y, dz, aff, has_gamma, has_beta, guide=None, gw=None, gb=None, den=None, out_gamma=None,
                   out_beta=None, pre=None):
     dev = y.device
@@ -791,7 +798,7 @@ def norm_relu_bwd(d, y, dz, aff, has_gamma, has_beta, guide=None, gw=None, gb=No
         dgb = torch.empty(blk + (d.C,), dtype=torch.float32, device=dev) if (d.guide_ch or gb is not None) else None
     nbytes = _abi.lib().unetk_norm_bwd_ws_bytes(ctypes.byref(d))
     if nbytes == 0:
-        raise _abi.UnetkError("norm_relu_bwd: unsupported channel count {}".format(d.C))
+        raise _abi.UnetkError(_norm_refused("norm_relu_bwd", d))
     ws = WORKSPACE.get(nbytes, dev)
     pre_part, pre_rows = pre if pre is not None else (None, 0)
     # reduction pass reads (dz, y) unless its partials came from the producing kernel; the apply pass reads (dz, y), writes dy
@@ -828,7 +835,7 @@ def norm_relu_bwd_pool(d, y, dskip, dp, aff, has_gamma, has_beta, out_gamma=None
     dbeta = (out_beta if out_beta is not None else torch.empty((d.C,), dtype=torch.float32, device=dev)) if has_beta else None
     nbytes = _abi.lib().unetk_norm_bwd_ws_bytes(ctypes.byref(d))
     if nbytes == 0:
-        raise _abi.UnetkError("norm_relu_bwd_pool: unsupported channel count {}".format(d.C))
+        raise _abi.UnetkError(_norm_refused("norm_relu_bwd_pool", d))
     ws = WORKSPACE.get(nbytes, dev)
     # both passes read (y, dskip) and a quarter-size dp; the apply pass writes dy
     with _timed_hbm("norm_relu_bwd_pool(reduce+apply)", y, 5.5):

@@ -1,6 +1,10 @@
 """The table of tests/test_gpu_norm_paths.py (csrc/norm.hip: apply, backward, pool-fused, SE / dropout passes), the Python
 restatement of the host dispatch it is checked against (tests/test_norm_paths_host.py, no GPU) and the inputs of both tiers.
 
+What is restated is norm.hip's NormPlan: `geom` = stat_geom + launch_geom, `bwd_blocks`, `apply_grid`, `k_rows` = NormPlan::K,
+`ws_bytes` = unetk_norm_bwd_ws_bytes (the segment-wise maximum of bwd_ws_layout), `plan` = norm_plan's geometry and grids of a
+row.  tests/test_norm_plan_host.py holds the library's two queries to `ws_bytes` and to recorded values without a GPU.
+
 A row names, by hand from the dispatch code of norm.hip, the template arguments of the kernels it must reach (`tmpl`: G, D, L as
 GD_DISPATCH instantiates them) and the reducer launches behind unetk_rows_reduce_alias (`red`: "w" = rows_reduce_final_wide_kernel,
 "l1" = rows_reduce_l1_kernel, "n" = rows_reduce_final_kernel); `xdy` marks the rows whose dy is compared bit for bit (the

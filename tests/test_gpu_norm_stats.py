@@ -293,3 +293,51 @@ def test_unit_forward_backward_at_large_ratio(ops, unit, kind, ratio):
     z2 = step()
     grads2 = torch.autograd.grad(z2, (xd, wd, gd, bd), dz)
     assert torch.equal(z, z2) and all(torch.equal(a, b) for a, b in zip(grads, grads2))
+
+
+@pytest.mark.parametrize("kind", ["batch_norm", "instance_norm"])
+def test_finalize_two_channels(ops, kind):
+    """unetk_norm_finalize at C = 2 (N = 2, HW = 16, two stat rows per group): the finalise kernels take any C > 0 and have no
+    thread map, so the host path there must not compute one -- C / 4 = 0 channel quads is a division by zero.  Partials of small
+    integers (exact in fp32), against their float64 moments at check_stats' bounds."""
+    import ctypes
+    from boxsegliver_amd import _abi
+    per_sample = kind == "instance_norm"
+    eps, decay, n, hw, c = (1e-6 if per_sample else 1e-3), 0.5, 2, 16, 2
+    groups = n if per_sample else 1
+    g = torch.Generator().manual_seed(11)
+    y = torch.randint(-4, 5, (n, hw, c), generator=g).double() + torch.tensor([3.0, -1.0], dtype=torch.float64)
+    tiles = y.reshape(2 * groups, -1, c)                             # two tiles per statistics group, each group's contiguous
+    rows = tiles.shape[0]
+    stats = torch.stack([tiles.sum(1), (tiles * tiles).sum(1)]).float().cuda().contiguous()      # [2][rows][C], exact
+    gamma = torch.tensor([1.5, -0.75], device="cuda")
+    beta = torch.tensor([0.25, -0.5], device="cuda")
+    mm, mv = torch.zeros(c, device="cuda"), torch.zeros(c, device="cuda")
+    out = torch.full((4, groups, c), float("nan"), device="cuda")
+    d = ops.norm_desc((n, hw, c), per_sample)
+    L = _abi.lib()
+    nbytes = L.unetk_norm_finalize_ws_bytes(ctypes.byref(d), rows)
+    assert nbytes > 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    rc, names = _trace(ops, lambda: L.unetk_norm_finalize(
+        ctypes.byref(d), p(stats), rows, p(gamma), p(beta), eps, decay, 1, p(mm), p(mv), p(out[0]), p(out[1]), p(out[2]),
+        p(out[3]), p(ws), nbytes, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    assert rc == 0, rc
+    assert _has(names, "norm_reduce_finalize_kernel(") and not _has(names, "norm_refine_kernel("), names
+    y64 = y.reshape(groups, -1, c).cuda()
+    m64, v64 = y64.mean(1), y64.var(1, unbiased=False)
+    s64, r64, cnt = v64.sqrt(), 1.0 / torch.sqrt(v64 + eps), y64.shape[1]
+    mean, rstd, scale, shift = (out[i].double() for i in range(4))
+    assert (s64 > 0).all()
+    assert ((mean - m64).abs() <= 2.0 ** -22 * m64.abs() + 1e-6 * s64).all(), (mean, m64)
+    assert ((rstd - r64).abs() / r64).max().item() <= 1e-5
+    sc64 = gamma.double() * r64
+    assert ((scale - sc64).abs() <= 1e-5 * sc64.abs()).all()
+    assert ((shift - (beta.double() - m64 * sc64)).abs() <= 1e-5 * (beta.double().abs() + (m64 * sc64).abs())).all()
+    if per_sample:
+        assert (mm == 0).all() and (mv == 0).all()               # instance norm keeps no moving statistics
+    else:
+        ref_mv, ref_mm = decay * v64[0] * cnt / (cnt - 1), decay * m64[0]
+        assert ((mv.double() - ref_mv).abs() <= 1e-5 * ref_mv).all()
+        assert ((mm.double() - ref_mm).abs() <= 2.0 ** -21 * ref_mm.abs() + 1e-6 * s64[0]).all()
