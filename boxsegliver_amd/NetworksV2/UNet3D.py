@@ -3,7 +3,9 @@
 nnU-Net-like topology (UNet3D.py:31-91,123-186): anisotropic kernels (1,3,3) at the two finest levels, (3,3,3)
 below, STRIDED convs instead of pooling (TF SAME: 0 before / 1 after at stride 2 on even sizes), channels
 30 -> 60 -> 120 -> 240 -> 320 (cap), decoder conv3d_transpose(kernel == stride, no bias) + ReLU, concat(skip, up),
-1x1x1 logits + bias; weighted cross-entropy only (:188-202).
+1x1x1 logits + bias; weighted cross-entropy only (:188-202).  --loss_weight_type boundary, which the reference's
+_compute_weights cannot build for 5-D tensors, weights the voxels by the 3-D boundary distance of the label patch
+(unetk_boundary_weights3d).
 
 MI355X decisions: NDHWC fp32; every conv3d is a composition of the 2-D fp32-MFMA conv kernel over depth-tap
 plane views (csrc/conv3d.hip); variables are channel-padded to the 32-wide MFMA tile on the device
@@ -18,7 +20,7 @@ transposed convs run on the bf16 pipe; the first conv (Cin = 1) and the four str
 import torch
 
 from .. import ops
-from ..loss_metrics import build_head_desc, metrics_from_sums
+from ..loss_metrics import build_head_desc, metrics_from_sums, pixel_weights
 from ..utils import distribution_utils
 from . import base
 from .base import ModeKeys
@@ -211,11 +213,16 @@ class UNet3D(base.BaseNet):
                 labels = labels.to(torch.int32).contiguous()
             nvox = dd * h * w
             pcl = x.shape[-1]
-            desc = build_head_desc(self.args, n, nvox, pcl, self.num_classes) if labels is not None else \
+            # --loss_weight_type boundary (not in the reference) or a caller's map; else None and no launch
+            pixel_w = pixel_weights(self.args, self._inputs, labels)
+            if pixel_w is not None:
+                pixel_w = pixel_w.reshape(n, nvox)
+            desc = build_head_desc(self.args, n, nvox, pcl, self.num_classes,
+                                   explicit_map=pixel_w is not None) if labels is not None else \
                 ops.head_desc(n, nvox, pcl, self.num_classes)
             want_probs = bool(self.ret_prob or self.ret_pred or self.mode != ModeKeys.TRAIN)
             xent, dice, logits, probs, result = ops.HeadLoss.apply(
-                x.reshape(n, nvox, 1, pcl), p[nm + "/logits/weights"], p[nm + "/logits/biases"], labels, None, desc,
+                x.reshape(n, nvox, 1, pcl), p[nm + "/logits/weights"], p[nm + "/logits/biases"], labels, pixel_w, desc,
                 want_probs)
             self._head = (xent, dice, result)
             self._layers["logits"] = logits.view(n, dd, h, w, self.num_classes)

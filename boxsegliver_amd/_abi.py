@@ -240,6 +240,8 @@ _SIGNATURES = {
     "unetk_sumsq": (c_int, [P, c_int64, P, P, c_size_t, P]),
     "unetk_boundary_weights_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "unetk_boundary_weights": (c_int, [P, c_int, c_int, c_int, P, P, c_size_t, P]),
+    "unetk_boundary_weights3d_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "unetk_boundary_weights3d": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "unetk_largest_component_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "unetk_largest_component": (c_int, [P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "unetk_component_mask": (c_int, [P, c_int, c_int, c_int, c_int32, P, P]),

@@ -102,6 +102,164 @@ __global__ __launch_bounds__(256) void edt_normalise_kernel(float* __restrict__ 
     M[i] *= scale;
 }
 
+
+// ------------------------------------------------------------------------------------------------ 3-D
+// The same map over a label PATCH [N, D, H, W] with an integer z scale K (include/unetk.h has the full statement): the ring is the
+// 3x3x3 one, d2 = min over ring voxels of (K dz)^2 + dy^2 + dx^2.  Three separable passes over int32 fields:
+//   b3_x_kernel          a wave per line (n, z, y): ring detection, one bit per voxel in LDS, 64 voxels per ballot; every voxel finds the
+//                        nearest set bit to its left and right word by word -> g1 = gx^2, or B3_NONE on a line without a ring voxel
+//   b3_axis_kernel<0>    y: g2(y) = min over y' of (y - y')^2 + g1(y'), brute force, a 64-column strip staged through LDS
+//   b3_axis_kernel<1>    z: d2(z) = min over z' of K^2 (z - z')^2 + g2(z'), the same loop along the other axis, then sqrt / expf and a
+//                        block's sum of the weights in double, tree-reduced in a fixed order
+//   b3_normalise_kernel  every block adds the sample's block sums in the same order, then scales its share of the map
+// A sample without a ring voxel keeps B3_NONE through every minimum: its voxels get w = 1 and d2 = -1, with no flag to consult.
+// Integer arithmetic up to the sqrt, no atomics: two calls give identical bits.
+constexpr int B3_MAX_D = 1024, B3_MAX_HW = 4096, B3_MAX_K = 16;
+constexpr int B3_NONE = 1 << 30;          // "no ring voxel on this line": 2^30 + 16^2 * (1023 + 15)^2 < 2^31, and every real d2 is
+                                          // <= 16^2 * 1023^2 + 2 * 4095^2 < 2^30
+constexpr int B3_LINES = 4;               // lines of a block of b3_x_kernel: one per wave
+constexpr int B3_STAGE = 128;             // rows of a 64-column strip staged at a time: 32 KiB of LDS
+constexpr int B3_T = 16;                  // outputs along the axis of a block of b3_axis_kernel: four per thread
+
+__global__ __launch_bounds__(256) void b3_x_kernel(const int32_t* __restrict__ lab, int D, int H, int W, int64_t lines,
+                                                   int32_t* __restrict__ g1) {
+  __shared__ unsigned long long bits[B3_LINES][B3_MAX_HW / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t line = (int64_t)blockIdx.x * B3_LINES + wave;   // (n * D + z) * H + y
+  const bool live = line < lines;                               // wave-uniform
+  const int64_t l = live ? line : 0;
+  const int y = (int)(l % H), z = (int)((l / H) % D);
+  const int64_t plane = (int64_t)H * W;
+  // the nine rows of the neighbourhood; one outside the SAMPLE's volume is replaced by the nearest one inside, which is a row of
+  // the neighbourhood too (a neighbour that changes nothing)
+  const int32_t* row = lab + l * W;
+  const int32_t* nb[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const int cz = min(max(z + k / 3 - 1, 0), D - 1), cy = min(max(y + k % 3 - 1, 0), H - 1);
+    nb[k] = row + (int64_t)(cz - z) * plane + (int64_t)(cy - y) * W;
+  }
+  for (int x0 = 0; x0 < W; x0 += 64) {                          // block-uniform trip count: the ballots see whole waves
+    const int x = x0 + lane;
+    bool ring = false;
+    if (live && x < W) {
+      const int32_t own = row[x];
+      const int xl = max(x - 1, 0), xr = min(x + 1, W - 1);
+#pragma unroll
+      for (int k = 0; k < 9; ++k) ring |= nb[k][xl] != own || nb[k][x] != own || nb[k][xr] != own;
+    }
+    const unsigned long long w = __ballot(ring);
+    if (lane == 0) bits[wave][x0 >> 6] = w;
+  }
+  __syncthreads();
+  if (!live) return;
+  const unsigned long long* b = bits[wave];
+  const int nwords = (W + 63) >> 6;
+  int32_t* o = g1 + l * W;
+  for (int x = lane; x < W; x += 64) {
+    const int w = x >> 6;                                       // lane == x & 63
+    int g = -1;
+    unsigned long long m = b[w] & (~0ull >> (63 - lane));       // the nearest ring voxel at or left of x
+    int ww = w;
+    while (m == 0 && ww > 0) m = b[--ww];
+    if (m != 0) g = x - (ww * 64 + 63 - __clzll((long long)m));
+    m = b[w] & (~0ull << lane);                                 // at or right of x
+    ww = w;
+    while (m == 0 && ww + 1 < nwords) m = b[++ww];
+    if (m != 0) {
+      const int r = ww * 64 + __ffsll((long long)m) - 1 - x;
+      g = g < 0 ? r : min(g, r);
+    }
+    o[x] = g < 0 ? B3_NONE : g * g;
+  }
+}
+
+// out(i) = min over j of scale * (i - j)^2 + in(j) along one axis of length L and element stride `stride`, for the W columns of a
+// slab (consecutive in memory).  Slab s starts at (s / sps) * sample + (s % sps) * slab_stride: the y pass walks the planes of a
+// sample (sps = D, slab_stride = H * W, stride = W), the z pass its rows (sps = H, slab_stride = W, stride = H * W).  No slab
+// spans two samples, so no sample sees another's ring.
+template <bool FINAL>
+__global__ __launch_bounds__(256) void b3_axis_kernel(const int32_t* __restrict__ in, int L, int64_t stride, int W, int nxb, int sps,
+                                                      int64_t sample, int64_t slab_stride, int scale, int32_t* __restrict__ out,
+                                                      float* __restrict__ wmap, int32_t* __restrict__ d2_out,
+                                                      double* __restrict__ block_sums) {
+  __shared__ int stage[B3_STAGE][64];
+  const int slab = blockIdx.x / nxb, xb = (blockIdx.x - slab * nxb) * 64, t0 = blockIdx.y * B3_T;
+  const int n = slab / sps;
+  const int64_t base = (int64_t)n * sample + (int64_t)(slab - n * sps) * slab_stride;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int x = xb + lane, i0 = t0 + wave * 4;                  // the thread's outputs: i0 .. i0 + 3 along the axis, column x
+  int best[4] = {B3_NONE, B3_NONE, B3_NONE, B3_NONE};
+  for (int c0 = 0; c0 < L; c0 += B3_STAGE) {
+    const int rows = min(B3_STAGE, L - c0);
+    if (c0 > 0) __syncthreads();                                // the chunk before has been read
+    for (int r = wave; r < rows; r += 4) stage[r][lane] = x < W ? in[base + (int64_t)(c0 + r) * stride + x] : B3_NONE;
+    __syncthreads();
+    for (int r = 0; r < rows; ++r) {
+      const int v = stage[r][lane], di = i0 - (c0 + r);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) best[k] = min(best[k], scale * (di + k) * (di + k) + v);
+    }
+  }
+  if (!FINAL) {
+    if (x >= W) return;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (i0 + k < L) out[base + (int64_t)(i0 + k) * stride + x] = min(best[k], B3_NONE);
+    return;
+  }
+  __shared__ double red[256];
+  double part = 0.0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (x >= W || i0 + k >= L) continue;
+    const int64_t o = base + (int64_t)(i0 + k) * stride + x;
+    const bool has = best[k] < B3_NONE;
+    float v = 1.f;
+    if (has) {
+      const float d = (float)sqrt((double)best[k]);
+      v = expf(-d / 25.f) + 1.f;
+    }
+    wmap[o] = v;
+    if (d2_out) d2_out[o] = has ? best[k] : -1;
+    part += (double)v;
+  }
+  red[threadIdx.x] = part;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  // the sample's sums are consecutive: [n][blockIdx.y][the sample's share of blockIdx.x]
+  const int per = sps * nxb;
+  if (threadIdx.x == 0) block_sums[((int64_t)n * gridDim.y + blockIdx.y) * per + (blockIdx.x - n * per)] = red[0];
+}
+
+__global__ __launch_bounds__(256) void b3_normalise_kernel(float* __restrict__ wmap, const double* __restrict__ block_sums, int per_sample,
+                                                           int64_t vox) {
+  __shared__ double red[256];
+  const int n = blockIdx.y;
+  double s = 0.0;
+  for (int i = threadIdx.x; i < per_sample; i += 256) s += block_sums[(int64_t)n * per_sample + i];   // the same order in every block
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int k = 128; k > 0; k >>= 1) {
+    if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+    __syncthreads();
+  }
+  const float scale = (float)((double)vox / red[0]);
+  float* M = wmap + (int64_t)n * vox;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < vox; i += (int64_t)gridDim.x * blockDim.x) M[i] *= scale;
+}
+
+bool b3_valid(int N, int D, int H, int W) { return N > 0 && N <= 65535 && D > 0 && H > 0 && W > 0; }
+bool b3_supported(int N, int D, int H, int W) {
+  if (D > B3_MAX_D || H > B3_MAX_HW || W > B3_MAX_HW) return false;
+  // every launch's grid.x: lines / 4, planes x strips, rows x strips
+  return (int64_t)N * D * H * ((W + 63) / 64) < ((int64_t)1 << 31);
+}
+int64_t b3_sums_per_sample(int D, int H, int W) { return (int64_t)H * ((W + 63) / 64) * ((D + B3_T - 1) / B3_T); }
+
 }  // namespace
 
 extern "C" size_t unetk_boundary_weights_ws_bytes(int N, int H, int W) {
@@ -126,6 +284,34 @@ extern "C" int unetk_boundary_weights(const int32_t* labels, int N, int H, int W
   UNETK_LAUNCH_CHECK();
   const int gx = (int)min((int64_t)1024, ((int64_t)H * W + 255) / 256);
   UNETK_LAUNCH(edt_normalise_kernel, dim3(gx, N), dim3(256), 0, st, wmap, row_sums, N, H, W);
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
+extern "C" size_t unetk_boundary_weights3d_ws_bytes(int N, int D, int H, int W) {
+  if (!b3_valid(N, D, H, W) || !b3_supported(N, D, H, W)) return 0;
+  return (size_t)N * b3_sums_per_sample(D, H, W) * sizeof(double) + (size_t)N * D * H * W * sizeof(int32_t);
+}
+
+extern "C" int unetk_boundary_weights3d(const int32_t* labels, int N, int D, int H, int W, int z_scale, float* wmap, int32_t* d2_out,
+                                        void* ws, size_t ws_bytes, void* stream) {
+  UNETK_REQUIRE(labels && wmap && ws && b3_valid(N, D, H, W));
+  UNETK_REQUIRE(((((uintptr_t)labels) | ((uintptr_t)wmap) | ((uintptr_t)d2_out)) & 3u) == 0 && unetk_aligned16(ws));
+  if (z_scale < 1 || z_scale > B3_MAX_K || !b3_supported(N, D, H, W)) return UNETK_E_UNSUPPORTED;
+  if (ws_bytes < unetk_boundary_weights3d_ws_bytes(N, D, H, W)) return UNETK_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int per = (int)b3_sums_per_sample(D, H, W), nxb = (W + 63) / 64;
+  const int64_t plane = (int64_t)H * W, vox = plane * D, lines = (int64_t)N * D * H;
+  double* block_sums = static_cast<double*>(ws);
+  int32_t* g2 = reinterpret_cast<int32_t*>(block_sums + (size_t)N * per);
+  int32_t* g1 = reinterpret_cast<int32_t*>(wmap);               // the map's own storage holds the x pass until the z pass writes it
+  UNETK_LAUNCH(b3_x_kernel, dim3((unsigned)((lines + B3_LINES - 1) / B3_LINES)), dim3(256), 0, st, labels, D, H, W, lines, g1);
+  UNETK_LAUNCH(b3_axis_kernel<false>, dim3((unsigned)(N * D * nxb), (H + B3_T - 1) / B3_T), dim3(256), 0, st, (const int32_t*)g1, H,
+               (int64_t)W, W, nxb, D, vox, plane, 1, g2, (float*)nullptr, (int32_t*)nullptr, (double*)nullptr);
+  UNETK_LAUNCH(b3_axis_kernel<true>, dim3((unsigned)(N * H * nxb), (D + B3_T - 1) / B3_T), dim3(256), 0, st, (const int32_t*)g2, D,
+               plane, W, nxb, H, vox, (int64_t)W, z_scale * z_scale, (int32_t*)nullptr, wmap, d2_out, block_sums);
+  const int gx = (int)min((int64_t)1024, (vox + 255) / 256);
+  UNETK_LAUNCH(b3_normalise_kernel, dim3(gx, N), dim3(256), 0, st, wmap, (const double*)block_sums, per, vox);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }

@@ -76,6 +76,7 @@ COL_WARP = 15                      # --random_deform: 0 = not deformed, else the
 DEFORM_MAX_GRID = 16               # the _warp entries' largest lattice: G + 3 <= 19 control points per axis
 DEFORM_FOLD_CAP = 0.4              # largest control displacement as a share of the control spacing (no folding: 7.3.10)
 SLICE_PRIORS = ("off", "boundary", "binary")     # --slice_prior
+BOUNDARY_MAX_Z_SCALE = 16          # --boundary_z_scale: the cap of unetk_boundary_weights3d
 
 
 def add_arguments(parser):
@@ -101,6 +102,10 @@ def add_arguments(parser):
                         help="--use_spatial: a second image channel (--im_channel 2) from the object on the slice of the first "
                              "foreground click: boundary = exp(-distance to its inner boundary / 25) (the reference's "
                              "--use_cascade), binary = the mask on that slice (--use_cascade --cascade_binary)")
+    parser.add_argument("--boundary_z_scale", type=int, default=1, metavar="K",
+                        help="--loss_weight_type boundary: the slice spacing in units of the in-plane spacing, an integer in "
+                             "1..{}; the distance to a label interface counts K per slice (the patches are not resampled "
+                             "along z)".format(BOUNDARY_MAX_Z_SCALE))
     parser.add_argument("--eval_window_weight", type=str, default="uniform", choices=WINDOW_WEIGHTS,
                         help="--eval_in_patches: how a window's voxels count in the average; gaussian weights its centre")
     parser.add_argument("--eval_window_sigma", type=float, default=0.125,
@@ -151,6 +156,19 @@ def check_values(args):
                          "not defined beyond the crop box".format(prior))
     if int(getattr(args, "guide_channel", 2)) not in (1, 2):
         raise ValueError("--guide_channel must be 1 or 2, got {}".format(args.guide_channel))
+    boundary_z_scale(args)
+
+
+def boundary_z_scale(args):
+    """--boundary_z_scale: 1 <= K <= 16, and K != 1 only with --loss_weight_type boundary (elsewhere it would do nothing)."""
+    k = int(getattr(args, "boundary_z_scale", 1))
+    if not 1 <= k <= BOUNDARY_MAX_Z_SCALE:
+        raise ValueError("--boundary_z_scale must satisfy 1 <= K <= {}, got {}".format(BOUNDARY_MAX_Z_SCALE, k))
+    w_type = (getattr(args, "loss_weight_type", "none") or "none").lower()
+    if k != 1 and w_type != "boundary":
+        raise ValueError("--boundary_z_scale {} scales the distances of --loss_weight_type boundary, got --loss_weight_type "
+                         "{}".format(k, w_type))
+    return k
 
 
 def slice_prior(args):

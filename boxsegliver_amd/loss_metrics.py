@@ -55,20 +55,24 @@ def build_head_desc(args, n, hw, c, ncls, explicit_map=False):
         return ops.head_desc(n, hw, c, ncls, "proportion", proportion_decay=decay if decay > 0 else 0.0)
     if w_type == "boundary":
         # resolved by pixel_weights() below into an explicit map (the reference round-trips to scipy on the host,
-        # loss_metrics.py:149-159); reaching this line means 3-D labels, which the reference cannot handle either
+        # loss_metrics.py:149-159; 3-D patches: unetk_boundary_weights3d); reaching this line means a caller that came
+        # without that map
         raise ValueError("loss_weight_type `boundary` is defined for 2-D labels only")
     raise ValueError("Not supported weight type: " + w_type)
 
 
 def pixel_weights(args, inputs, labels):
     """Explicit per-pixel loss weights: a caller-provided inputs["pixel_weights"] map, or the `boundary` map
-    (loss_metrics.py:149-165) computed on the device from the labels; None for the table-driven weight types."""
+    (loss_metrics.py:149-165) computed on the device from the labels -- [bs, H, W] as in the reference, or [bs, D, H, W] with
+    --boundary_z_scale; None for the table-driven weight types."""
     explicit = inputs.get("pixel_weights")
     if explicit is not None or labels is None:
         return explicit
     w_type = (getattr(args, "loss_weight_type", "none") or "none").lower()
     if w_type == "boundary" and labels.dim() == 3:
         return ops.boundary_weights(labels)
+    if w_type == "boundary" and labels.dim() == 4:           # UNet3D's [bs, D, H, W] patches (DESIGN.md 7.3.12)
+        return ops.boundary_weights3d(labels, getattr(args, "boundary_z_scale", 1))
     return None
 
 

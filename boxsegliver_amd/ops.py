@@ -1133,6 +1133,24 @@ def boundary_weights(labels):
     return wmap
 
 
+def boundary_weights3d(labels, z_scale=1, want_d2=False):
+    """--loss_weight_type boundary for UNet3D: labels int32 [N,D,H,W] -> normalised weight map f32
+    [N,D,H,W]; z_scale = the slice spacing in units of the in-plane spacing (an integer, 1..16).  want_d2: also the exact
+    squared distances int32 [N,D,H,W] (-1 throughout a sample without a ring voxel, whose weights are all 1)."""
+    _require_cuda(labels)
+    if labels.dim() != 4:
+        raise ValueError("boundary_weights3d takes [bs, D, H, W] labels, got shape {}".format(tuple(labels.shape)))
+    labels = labels.to(torch.int32).contiguous()
+    n, d, h, w = labels.shape
+    wmap = torch.empty((n, d, h, w), dtype=torch.float32, device=labels.device)
+    d2 = torch.empty((n, d, h, w), dtype=torch.int32, device=labels.device) if want_d2 else None
+    nbytes = _abi.lib().unetk_boundary_weights3d_ws_bytes(n, d, h, w)
+    ws = WORKSPACE.get(nbytes, labels.device)
+    check(_abi.lib().unetk_boundary_weights3d(ptr(labels), n, d, h, w, int(z_scale), ptr(wmap), ptr(d2), ptr(ws), nbytes,
+                                              stream_ptr()), "boundary_weights3d")
+    return (wmap, d2) if want_d2 else wmap
+
+
 # ----------------------------------------------------------------------------- volume evaluation (csrc/evalvol.hip)
 def _mask3d(t):
     """A [D, H, W] device mask as a dense uint8 tensor (non-zero = object)."""

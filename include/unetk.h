@@ -552,6 +552,30 @@ size_t unetk_boundary_weights_ws_bytes(int N, int H, int W);
 int unetk_boundary_weights(const int32_t* labels, int N, int H, int W, float* wmap, void* ws,
                            size_t ws_bytes, void* stream);
 
+/* --loss_weight_type boundary for UNet3D (a project extension: the reference's _compute_weights reshapes a 4-D
+ * one-hot tensor and fails on 5-D).  For labels int32 [N, D, H, W], an integer z scale K >= 1 (the slice spacing in units of the
+ * in-plane spacing), and each sample on its own:
+ *   ring(z,y,x)  some in-bounds voxel of the 3x3x3 neighbourhood carries a label different from the voxel's own.  This equals
+ *                sum_c (clip(conv3d(onehot_c, ones(3,3,3), SAME), 0, 1) - onehot_c) > 0, the 3-D form of the reference's 2-D ring.
+ *   d2(z,y,x)  = min over ring voxels (K (z - z'))^2 + (y - y')^2 + (x - x')^2.  This is an exact integer.
+ *   d          = (float) sqrt((double) d2).  This is bit for bit what
+ *                scipy.ndimage.distance_transform_edt(~ring, sampling=(K,1,1)).astype(float32) returns.
+ *   w          = expf(-d / 25) + 1, then w * (D H W) / sum(w) per sample.  The sum is taken in a fixed order, so two runs give
+ *                identical bits.
+ * A sample without any ring voxel (a single-label patch) gets w = 1 everywhere and d2 = -1.  This is a rule of this project:
+ * scipy's answer for an input without zeros is an artefact, and the 2-D entry's reproduction of that artefact is not carried
+ * into 3-D.
+ * wmap f32 [N, D, H, W] feeds unetk_head_fwd/bwd as UNETK_W_PIXELMAP with HW = D H W; it also serves as scratch during the call.
+ * d2_out int32 [N, D, H, W] is nullable: when it is null, nothing extra is written.
+ * Limits: 1 <= z_scale <= 16, D <= 1024, H, W <= 4096 and N D H ceil(W / 64) < 2^31, else UNETK_E_UNSUPPORTED (under these caps
+ * d2 < 2^31, and no intermediate overflows int32); N <= 65535 and 4-byte aligned labels / wmap / d2_out, else UNETK_E_BADARG.
+ * Workspace (16-byte aligned, else UNETK_E_BADARG; short: UNETK_E_WORKSPACE; the query returns 0 for extents the entry refuses):
+ *   8 * N * H * ceil(W / 64) * ceil(D / 16)   one double per block of the z pass, the sums of the weights
+ * + 4 * N * D * H * W                         the int32 field between the y and the z pass */
+size_t unetk_boundary_weights3d_ws_bytes(int N, int D, int H, int W);
+int unetk_boundary_weights3d(const int32_t* labels, int N, int D, int H, int W, int z_scale, float* wmap,
+                             int32_t* d2_out /* nullable, [N,D,H,W] */, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- volume evaluation
  * evaluators/evaluator_liver.py:680-702,906-996 (_postprocess, _run_actual) and loss_metrics.py:342-452 (metric_3d), which
  * the reference runs on the host with scipy.  Masks are dense C-order uint8 [D,H,W], non-zero = object.  D, H, W > 0
