@@ -7,27 +7,25 @@
 // The field is therefore ONE slice of int32 per row, in two separable passes:
 //   sp_rows_kernel   block per (box row, table row): the object mask and its inner boundary (a foreground pixel with a background
 //                    4-neighbour INSIDE the box) as one bit per pixel in LDS, 64 pixels per ballot; every pixel then finds the
-//                    nearest set bit to its left and to its right word by word -> g(y, x)^2, g capped at SP_G_CAP (no boundary
-//                    pixel in the row).  Binary mode writes the mask itself and stops here.
-//   sp_cols_kernel   block per 64 columns x 16 rows of the box: D2(y, x) = min over y' of (y - y')^2 + g(y', x)^2 by brute force,
-//                    the strip's g^2 staged through LDS SP_STAGE rows at a time (a lane per column: each LDS row is read
-//                    conflict-free, and one read serves the thread's four output rows).  A box without a boundary pixel has
-//                    g = SP_G_CAP everywhere, which the minimum shows: such a pixel gets the sentinel -1.
+//                    nearest set bit of its row (edt_int.h) -> g(y, x)^2, or IEDT_NONE in a row without a boundary pixel.
+//                    Binary mode writes the mask itself and stops here.
+//   sp_cols_kernel   block per 64 columns x 16 rows of the box: D2(y, x) = min over y' of (y - y')^2 + g(y', x)^2 by brute force
+//                    (edt_int.h).  A box without a boundary pixel has IEDT_NONE everywhere, which the minimum shows: such a
+//                    pixel gets the sentinel -1.
 //   sp_render_kernel thread per output voxel: channel 0 copies the one-channel patch, channel 1 evaluates
 //                    exp(-sqrt(dz^2 + D2) / 25) at the four in-plane bilinear corners and lerps (create, then resize, as
 //                    click_guide3d_kernel); the three flips are the write address.
 // Integer arithmetic up to the render, no atomics: two calls give identical bits.
 #include "common.h"
+#include "edt_int.h"
 #include "lits_geom.h"
 #include "lits_patch.h"      // TW, Box3, p3d_box, p3d_slice
 
 namespace {
 
-constexpr int SP_MAX_EXTENT = 4096;       // src_h, src_w: (y - y')^2 <= 4095^2 and the bit row of sp_rows_kernel holds 64 words
-constexpr int SP_G_CAP = 32768;           // "no boundary pixel in this row": SP_G_CAP^2 + 4095^2 < 2^31
-constexpr int SP_NONE = SP_G_CAP * SP_G_CAP;   // 2^30: every real D2 is <= 2 * 4095^2 < 2^30
-constexpr int SP_STAGE = 128;             // rows of a 64-column strip staged at a time: 32 KiB of LDS
-constexpr int SP_TY = 16;                 // output rows of a block of sp_cols_kernel: four per thread
+constexpr int SP_MAX_EXTENT = IEDT_MAX_BITS;   // src_h, src_w: a box row is one bit row of sp_rows_kernel
+static_assert(iedt_fits(1, SP_MAX_EXTENT), "sp_cols_kernel overflows int32");
+static_assert(2 * (int64_t)(SP_MAX_EXTENT - 1) * (SP_MAX_EXTENT - 1) < IEDT_NONE, "a real D2 reaches the sentinel");
 constexpr int MAXK = UNETK_LITS_MAX_CLICKS;
 
 // The box a row's field covers and the store slice it reads: the row's crop box with z0 relative to it, or (whole) the whole
@@ -98,19 +96,9 @@ __global__ __launch_bounds__(256) void sp_rows_kernel(unetk_lits3d_clicks_desc d
   }
   if (binary) return;
   __syncthreads();
-  const int nwords = (bw + 63) >> 6;
   for (int x = threadIdx.x; x < bw; x += 256) {
-    const int w = x >> 6, l = x & 63;
-    int g = SP_G_CAP;
-    unsigned long long m = bits[w] & (~0ull >> (63 - l));    // the nearest boundary pixel at or left of x
-    int ww = w;
-    while (m == 0 && ww > 0) m = bits[--ww];
-    if (m != 0) g = x - (ww * 64 + 63 - __clzll((long long)m));
-    m = bits[w] & (~0ull << l);                              // at or right of x
-    ww = w;
-    while (m == 0 && ww + 1 < nwords) m = bits[++ww];
-    if (m != 0) g = min(g, ww * 64 + __ffsll((long long)m) - 1 - x);
-    o[x] = g * g;
+    const int g = iedt_nearest_bit(bits, (bw + 63) >> 6, x);
+    o[x] = g < 0 ? IEDT_NONE : g * g;
   }
 }
 
@@ -118,33 +106,21 @@ __global__ __launch_bounds__(256) void sp_rows_kernel(unetk_lits3d_clicks_desc d
 __global__ __launch_bounds__(256) void sp_cols_kernel(unetk_lits3d_clicks_desc d, const int32_t* __restrict__ tab,
                                                       const int32_t* __restrict__ z0s, int whole,
                                                       const int32_t* __restrict__ gsq, int32_t* __restrict__ field) {
-  __shared__ int stage[SP_STAGE][64];
+  __shared__ int stage[IEDT_STAGE][64];
   const int n = blockIdx.z;
   const PriorBox p = sp_box(tab + (int64_t)n * TW, d, whole, z0s[n]);
-  const int xb = blockIdx.x * 64, yb = blockIdx.y * SP_TY;
+  const int xb = blockIdx.x * 64, yb = blockIdx.y * IEDT_T;
   if (xb >= p.bw || yb >= p.bh) return;                      // block-uniform
   const int bw = p.bw, bh = p.bh;
   const int64_t plane = (int64_t)d.src_h * d.src_w;
-  const int32_t* g = gsq + (int64_t)n * plane;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int x = xb + lane, y0 = yb + wave * 4;               // the thread's outputs: rows y0 .. y0 + 3 of column x
-  int best[4] = {SP_NONE, SP_NONE, SP_NONE, SP_NONE};
-  for (int c0 = 0; c0 < bh; c0 += SP_STAGE) {
-    const int rows = min(SP_STAGE, bh - c0);
-    if (c0 > 0) __syncthreads();                             // the chunk before has been read
-    for (int r = wave; r < rows; r += 4) stage[r][lane] = x < bw ? g[(int64_t)(c0 + r) * bw + x] : SP_NONE;
-    __syncthreads();
-    for (int r = 0; r < rows; ++r) {
-      const int v = stage[r][lane], dy = y0 - (c0 + r);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) best[k] = min(best[k], (dy + k) * (dy + k) + v);
-    }
-  }
+  const int x = xb + (threadIdx.x & 63), y0 = yb + (threadIdx.x >> 6) * 4;   // the thread's outputs: rows y0 .. y0 + 3 of column x
+  int best[4];
+  iedt_axis_min(stage, gsq + (int64_t)n * plane + x, x < bw, bw, bh, y0, 1, best);
   if (x >= bw) return;
   int32_t* f = field + (int64_t)n * plane;
 #pragma unroll
   for (int k = 0; k < 4; ++k)
-    if (y0 + k < bh) f[(int64_t)(y0 + k) * bw + x] = best[k] < SP_NONE ? best[k] : -1;
+    if (y0 + k < bh) f[(int64_t)(y0 + k) * bw + x] = best[k] < IEDT_NONE ? best[k] : -1;
 }
 
 // ------------------------------------------------------------------------------------------------ render
@@ -221,7 +197,7 @@ extern "C" int unetk_slice_prior_field(const unetk_lits3d_clicks_desc* d, const 
   UNETK_LAUNCH(sp_rows_kernel, dim3(d->src_h, d->N), dim3(256), 0, st, *d, seg_slices, sample_tab, pts, cnt, K, whole != 0 ? 1 : 0,
                binary, binary ? field : gsq, z0);
   if (!binary)
-    UNETK_LAUNCH(sp_cols_kernel, dim3((d->src_w + 63) / 64, (d->src_h + SP_TY - 1) / SP_TY, d->N), dim3(256), 0, st, *d, sample_tab,
+    UNETK_LAUNCH(sp_cols_kernel, dim3((d->src_w + 63) / 64, (d->src_h + IEDT_T - 1) / IEDT_T, d->N), dim3(256), 0, st, *d, sample_tab,
                  (const int32_t*)z0, whole != 0 ? 1 : 0, (const int32_t*)gsq, field);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;

@@ -11,6 +11,7 @@
 // sqrt((h+1)^2 + w^2), which is reproduced so that such slices weigh as they do in the reference.
 // HBM-bound and tiny next to the network (one int32 read + a few float passes over [N,H,W]).
 #include "common.h"
+#include "edt_int.h"
 
 namespace {
 
@@ -107,19 +108,30 @@ __global__ __launch_bounds__(256) void edt_normalise_kernel(float* __restrict__ 
 // The same map over a label PATCH [N, D, H, W] with an integer z scale K (include/unetk.h has the full statement): the ring is the
 // 3x3x3 one, d2 = min over ring voxels of (K dz)^2 + dy^2 + dx^2.  Three separable passes over int32 fields:
 //   b3_x_kernel          a wave per line (n, z, y): ring detection, one bit per voxel in LDS, 64 voxels per ballot; every voxel finds the
-//                        nearest set bit to its left and right word by word -> g1 = gx^2, or B3_NONE on a line without a ring voxel
-//   b3_axis_kernel<0>    y: g2(y) = min over y' of (y - y')^2 + g1(y'), brute force, a 64-column strip staged through LDS
+//                        nearest set bit of its line (edt_int.h) -> g1 = gx^2, or IEDT_NONE on a line without a ring voxel
+//   b3_axis_kernel<0>    y: g2(y) = min over y' of (y - y')^2 + g1(y'), brute force over a 64-column strip (edt_int.h)
 //   b3_axis_kernel<1>    z: d2(z) = min over z' of K^2 (z - z')^2 + g2(z'), the same loop along the other axis, then sqrt / expf and a
 //                        block's sum of the weights in double, tree-reduced in a fixed order
 //   b3_normalise_kernel  every block adds the sample's block sums in the same order, then scales its share of the map
-// A sample without a ring voxel keeps B3_NONE through every minimum: its voxels get w = 1 and d2 = -1, with no flag to consult.
+// A sample without a ring voxel keeps IEDT_NONE through every minimum: its voxels get w = 1 and d2 = -1, with no flag to consult.
 // Integer arithmetic up to the sqrt, no atomics: two calls give identical bits.
-constexpr int B3_MAX_D = 1024, B3_MAX_HW = 4096, B3_MAX_K = 16;
-constexpr int B3_NONE = 1 << 30;          // "no ring voxel on this line": 2^30 + 16^2 * (1023 + 15)^2 < 2^31, and every real d2 is
-                                          // <= 16^2 * 1023^2 + 2 * 4095^2 < 2^30
+constexpr int B3_MAX_D = 1024, B3_MAX_HW = IEDT_MAX_BITS, B3_MAX_K = 16;
+static_assert(iedt_fits(1, B3_MAX_HW) && iedt_fits(B3_MAX_K * B3_MAX_K, B3_MAX_D), "b3_axis_kernel overflows int32");
+static_assert((int64_t)B3_MAX_K * B3_MAX_K * (B3_MAX_D - 1) * (B3_MAX_D - 1) + 2 * (int64_t)(B3_MAX_HW - 1) * (B3_MAX_HW - 1) < IEDT_NONE,
+              "a real d2 reaches the sentinel");
 constexpr int B3_LINES = 4;               // lines of a block of b3_x_kernel: one per wave
-constexpr int B3_STAGE = 128;             // rows of a 64-column strip staged at a time: 32 KiB of LDS
-constexpr int B3_T = 16;                  // outputs along the axis of a block of b3_axis_kernel: four per thread
+
+// the sum of the block's 256 `part`s, paired s = 128, 64, .., 1: the order is part of the map's bits
+__device__ __forceinline__ double b3_block_sum(double part) {
+  __shared__ double red[256];
+  red[threadIdx.x] = part;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  return red[0];
+}
 
 __global__ __launch_bounds__(256) void b3_x_kernel(const int32_t* __restrict__ lab, int D, int H, int W, int64_t lines,
                                                    int32_t* __restrict__ g1) {
@@ -157,20 +169,8 @@ __global__ __launch_bounds__(256) void b3_x_kernel(const int32_t* __restrict__ l
   const int nwords = (W + 63) >> 6;
   int32_t* o = g1 + l * W;
   for (int x = lane; x < W; x += 64) {
-    const int w = x >> 6;                                       // lane == x & 63
-    int g = -1;
-    unsigned long long m = b[w] & (~0ull >> (63 - lane));       // the nearest ring voxel at or left of x
-    int ww = w;
-    while (m == 0 && ww > 0) m = b[--ww];
-    if (m != 0) g = x - (ww * 64 + 63 - __clzll((long long)m));
-    m = b[w] & (~0ull << lane);                                 // at or right of x
-    ww = w;
-    while (m == 0 && ww + 1 < nwords) m = b[++ww];
-    if (m != 0) {
-      const int r = ww * 64 + __ffsll((long long)m) - 1 - x;
-      g = g < 0 ? r : min(g, r);
-    }
-    o[x] = g < 0 ? B3_NONE : g * g;
+    const int g = iedt_nearest_bit(b, nwords, x);
+    o[x] = g < 0 ? IEDT_NONE : g * g;
   }
 }
 
@@ -183,38 +183,26 @@ __global__ __launch_bounds__(256) void b3_axis_kernel(const int32_t* __restrict_
                                                       int64_t sample, int64_t slab_stride, int scale, int32_t* __restrict__ out,
                                                       float* __restrict__ wmap, int32_t* __restrict__ d2_out,
                                                       double* __restrict__ block_sums) {
-  __shared__ int stage[B3_STAGE][64];
-  const int slab = blockIdx.x / nxb, xb = (blockIdx.x - slab * nxb) * 64, t0 = blockIdx.y * B3_T;
+  __shared__ int stage[IEDT_STAGE][64];
+  const int slab = blockIdx.x / nxb, xb = (blockIdx.x - slab * nxb) * 64, t0 = blockIdx.y * IEDT_T;
   const int n = slab / sps;
   const int64_t base = (int64_t)n * sample + (int64_t)(slab - n * sps) * slab_stride;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int x = xb + lane, i0 = t0 + wave * 4;                  // the thread's outputs: i0 .. i0 + 3 along the axis, column x
-  int best[4] = {B3_NONE, B3_NONE, B3_NONE, B3_NONE};
-  for (int c0 = 0; c0 < L; c0 += B3_STAGE) {
-    const int rows = min(B3_STAGE, L - c0);
-    if (c0 > 0) __syncthreads();                                // the chunk before has been read
-    for (int r = wave; r < rows; r += 4) stage[r][lane] = x < W ? in[base + (int64_t)(c0 + r) * stride + x] : B3_NONE;
-    __syncthreads();
-    for (int r = 0; r < rows; ++r) {
-      const int v = stage[r][lane], di = i0 - (c0 + r);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) best[k] = min(best[k], scale * (di + k) * (di + k) + v);
-    }
-  }
+  const int x = xb + (threadIdx.x & 63), i0 = t0 + (threadIdx.x >> 6) * 4;   // the thread's outputs: i0 .. i0 + 3 along the axis, column x
+  int best[4];
+  iedt_axis_min(stage, in + base + x, x < W, stride, L, i0, scale, best);
   if (!FINAL) {
     if (x >= W) return;
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      if (i0 + k < L) out[base + (int64_t)(i0 + k) * stride + x] = min(best[k], B3_NONE);
+      if (i0 + k < L) out[base + (int64_t)(i0 + k) * stride + x] = best[k];
     return;
   }
-  __shared__ double red[256];
   double part = 0.0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     if (x >= W || i0 + k >= L) continue;
     const int64_t o = base + (int64_t)(i0 + k) * stride + x;
-    const bool has = best[k] < B3_NONE;
+    const bool has = best[k] < IEDT_NONE;
     float v = 1.f;
     if (has) {
       const float d = (float)sqrt((double)best[k]);
@@ -224,30 +212,18 @@ __global__ __launch_bounds__(256) void b3_axis_kernel(const int32_t* __restrict_
     if (d2_out) d2_out[o] = has ? best[k] : -1;
     part += (double)v;
   }
-  red[threadIdx.x] = part;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
+  const double sum = b3_block_sum(part);
   // the sample's sums are consecutive: [n][blockIdx.y][the sample's share of blockIdx.x]
   const int per = sps * nxb;
-  if (threadIdx.x == 0) block_sums[((int64_t)n * gridDim.y + blockIdx.y) * per + (blockIdx.x - n * per)] = red[0];
+  if (threadIdx.x == 0) block_sums[((int64_t)n * gridDim.y + blockIdx.y) * per + (blockIdx.x - n * per)] = sum;
 }
 
 __global__ __launch_bounds__(256) void b3_normalise_kernel(float* __restrict__ wmap, const double* __restrict__ block_sums, int per_sample,
                                                            int64_t vox) {
-  __shared__ double red[256];
   const int n = blockIdx.y;
   double s = 0.0;
   for (int i = threadIdx.x; i < per_sample; i += 256) s += block_sums[(int64_t)n * per_sample + i];   // the same order in every block
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int k = 128; k > 0; k >>= 1) {
-    if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-    __syncthreads();
-  }
-  const float scale = (float)((double)vox / red[0]);
+  const float scale = (float)((double)vox / b3_block_sum(s));
   float* M = wmap + (int64_t)n * vox;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < vox; i += (int64_t)gridDim.x * blockDim.x) M[i] *= scale;
 }
@@ -258,7 +234,7 @@ bool b3_supported(int N, int D, int H, int W) {
   // every launch's grid.x: lines / 4, planes x strips, rows x strips
   return (int64_t)N * D * H * ((W + 63) / 64) < ((int64_t)1 << 31);
 }
-int64_t b3_sums_per_sample(int D, int H, int W) { return (int64_t)H * ((W + 63) / 64) * ((D + B3_T - 1) / B3_T); }
+int64_t b3_sums_per_sample(int D, int H, int W) { return (int64_t)H * ((W + 63) / 64) * ((D + IEDT_T - 1) / IEDT_T); }
 
 }  // namespace
 
@@ -306,9 +282,9 @@ extern "C" int unetk_boundary_weights3d(const int32_t* labels, int N, int D, int
   int32_t* g2 = reinterpret_cast<int32_t*>(block_sums + (size_t)N * per);
   int32_t* g1 = reinterpret_cast<int32_t*>(wmap);               // the map's own storage holds the x pass until the z pass writes it
   UNETK_LAUNCH(b3_x_kernel, dim3((unsigned)((lines + B3_LINES - 1) / B3_LINES)), dim3(256), 0, st, labels, D, H, W, lines, g1);
-  UNETK_LAUNCH(b3_axis_kernel<false>, dim3((unsigned)(N * D * nxb), (H + B3_T - 1) / B3_T), dim3(256), 0, st, (const int32_t*)g1, H,
+  UNETK_LAUNCH(b3_axis_kernel<false>, dim3((unsigned)(N * D * nxb), (H + IEDT_T - 1) / IEDT_T), dim3(256), 0, st, (const int32_t*)g1, H,
                (int64_t)W, W, nxb, D, vox, plane, 1, g2, (float*)nullptr, (int32_t*)nullptr, (double*)nullptr);
-  UNETK_LAUNCH(b3_axis_kernel<true>, dim3((unsigned)(N * H * nxb), (D + B3_T - 1) / B3_T), dim3(256), 0, st, (const int32_t*)g2, D,
+  UNETK_LAUNCH(b3_axis_kernel<true>, dim3((unsigned)(N * H * nxb), (D + IEDT_T - 1) / IEDT_T), dim3(256), 0, st, (const int32_t*)g2, D,
                plane, W, nxb, H, vox, (int64_t)W, z_scale * z_scale, (int32_t*)nullptr, wmap, d2_out, block_sums);
   const int gx = (int)min((int64_t)1024, (vox + 255) / 256);
   UNETK_LAUNCH(b3_normalise_kernel, dim3(gx, N), dim3(256), 0, st, wmap, (const double*)block_sums, per, vox);

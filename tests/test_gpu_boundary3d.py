@@ -8,6 +8,8 @@ multiplication by the float32 scale of a sum that is taken in double.  Measured 
 map and 6.2e-8 on a sample's mean (the tests print every row's figure before they assert)."""
 import argparse
 import ctypes
+import importlib.util
+import os
 
 import numpy as np
 import pytest
@@ -21,11 +23,12 @@ pytestmark = pytest.mark.gpu
 BOUNDARY_RTOL = 2e-6
 E_BADARG, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3
 KERNELS = ["b3_x_kernel", "b3_axis_kernel<false>", "b3_axis_kernel<true>", "b3_normalise_kernel"]
-# the issue's volumes, then one per block / tile size of the kernels with the extent just past it:
+# the issue's volumes, then one per block / tile size of the kernels with the extent just past it (the sizes
+# of the two shared passes are the constants of csrc/edt_int.h):
 #   (3, 9, 65)   W = 65: a second ballot word of b3_x_kernel and a second 64-column strip of b3_axis_kernel; 27 lines per sample,
-#                no multiple of the 4 lines of a block of b3_x_kernel
-#   (5, 17, 6)   H = 17 and (17, 5, 6) D = 17: a second block of 16 outputs along the axis of b3_axis_kernel
-#   (3, 129, 4)  H = 129 and (129, 3, 4) D = 129: a second staging chunk of 128 rows
+#                no multiple of the 4 lines of a block of b3_x_kernel (B3_LINES of csrc/weights.hip)
+#   (5, 17, 6)   H = 17 and (17, 5, 6) D = 17: a second block of 16 outputs along the axis of b3_axis_kernel (IEDT_T)
+#   (3, 129, 4)  H = 129 and (129, 3, 4) D = 129: a second staging chunk of 128 rows (IEDT_STAGE)
 VOLUMES = [(6, 20, 24), (10, 32, 40), (4, 70, 9), (1, 33, 65), (3, 5, 300), (2, 300, 5), (70, 6, 7), (5, 1, 70), (1, 1, 1), (2, 1, 1),
            (3, 9, 65), (5, 17, 6), (17, 5, 6), (3, 129, 4), (129, 3, 4)]
 SCALES = (1, 3)
@@ -163,6 +166,31 @@ def test_without_d2_out_and_through_the_wrapper(ops):
     assert torch.equal(ops.boundary_weights3d(t.long(), z_scale=3), wmap)       # int64 labels, as the input pipeline's
     with pytest.raises(ValueError):
         ops.boundary_weights3d(t[0])
+
+
+# ------------------------------------------------------------------------------------------------- the bits before the shared core
+def _load_generator():
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_edt_fixture.py")
+    spec = importlib.util.spec_from_file_location("make_edt_fixture", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_map_bits_are_those_before_the_shared_edt_core(ops):
+    """tests/golden/edt_maps_before.npz holds the map's float32 bits as weights.hip computed them with its own copy of the two
+    integer passes and of the tree sum (recorded by tests/golden/make_edt_fixture.py on an MI355X): moving onto csrc/edt_int.h
+    and b3_block_sum changed no bit -- not the minima, not the order of the double sums."""
+    G = _load_generator()
+    z = np.load(G.OUT)
+    assert sorted(z.files) == sorted(G.key(s, k) for s in G.SHAPES for k in G.SCALES), "the fixture was recorded for other cases"
+    for shape in G.SHAPES:
+        for k in G.SCALES:
+            got, want = G.record(ops, shape, k), z[G.key(shape, k)]
+            assert want.dtype == np.uint32 and want.shape == (2,) + shape
+            bad = got != want
+            assert np.array_equal(got, want), "{} K={}: {} of {} words differ, first at {}".format(
+                shape, k, int(bad.sum()), bad.size, np.argwhere(bad)[:3].tolist())
 
 
 # ------------------------------------------------------------------------------------------------- batch isolation

@@ -21,7 +21,7 @@ import slice_prior_ref as sref
 pytestmark = pytest.mark.gpu
 
 IDENTITY_TOL, RESIZE_TOL = 5e-7, 1e-6
-STAGE = 128                                     # SP_STAGE of csrc/slice_prior.hip: rows of a strip staged at a time
+STAGE = 128                                     # IEDT_STAGE of csrc/edt_int.h: rows of a strip staged at a time
 SRC_A = (40, 80)
 D = 4
 
