@@ -12,7 +12,7 @@ objs=()
 pids=()
 for src in evalvol evalio conv_igemm conv_igemm_lin conv_igemm_bf16 conv_igemm_bf16s conv_wgrad conv_wgrad_bf16s conv3d deconv norm reduce pool head weights lits lits3d lits3d_clicks slice_prior lits_inter lits_geodesic glcm inter_eval inter_eval3d fc conv1d pack optim prof; do
   o="$OBJ/$src.o"
-  if [[ ! -f "$o" || "$HERE/$src.hip" -nt "$o" || "$HERE/common.h" -nt "$o" || "$HERE/pack.h" -nt "$o" || "$HERE/lits_geom.h" -nt "$o" || "$HERE/lits_patch.h" -nt "$o" || "$HERE/lits_clicks.h" -nt "$o" || "$HERE/lits_inter_px.h" -nt "$o" || "$HERE/unionfind.h" -nt "$o" || "$HERE/edt_int.h" -nt "$o" || "$ROOT/include/unetk.h" -nt "$o" ]]; then
+  if [[ ! -f "$o" || "$HERE/$src.hip" -nt "$o" || "$HERE/common.h" -nt "$o" || "$HERE/pack.h" -nt "$o" || "$HERE/lits_geom.h" -nt "$o" || "$HERE/lits_patch.h" -nt "$o" || "$HERE/lits_clicks.h" -nt "$o" || "$HERE/lits_inter_px.h" -nt "$o" || "$HERE/unionfind.h" -nt "$o" || "$HERE/edt_int.h" -nt "$o" || "$HERE/inter_click.h" -nt "$o" || "$ROOT/include/unetk.h" -nt "$o" ]]; then
     rm -f "$o"                                  # a failed compile must not leave a stale object for the link
     "$HIPCC" $FLAGS -c "$HERE/$src.hip" -o "$o" &
     pids+=("$!")

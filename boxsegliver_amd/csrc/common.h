@@ -125,6 +125,34 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
+// exact integer reductions (counts, coordinate sums, arg-max keys): any order gives the same bits
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long other = __shfl_xor(v, o);
+    v = other > v ? other : v;
+  }
+  return v;
+}
+
+// np.mean(...).round(0) of integers: s / a rounded half to even.  (Spelt before as "2r > a, 2r == a, else" and as "2r < a,
+// 2r > a, else": both compare twice the remainder with the divisor and send the tie to the even quotient.)
+__device__ __forceinline__ int unetk_round_div_even(unsigned long long s, unsigned long long a) {
+  const unsigned long long q = s / a, r2 = 2 * (s - q * a);
+  return (int)(r2 < a ? q : (r2 > a ? q + 1 : q + (q & 1ull)));
+}
+
+// An arg-max key under an unsigned 64-bit max: the larger `hi32` wins, then the SMALLER index (np.argmax's first maximum
+// in row-major order).  i < 2^32 - 1, so no element gives 0, which stands for "none".
+__device__ __forceinline__ unsigned long long unetk_first_key(unsigned int hi32, unsigned int i) {
+  return ((unsigned long long)hi32 << 32) | (unsigned long long)(0xffffffffu - i);
+}
+__device__ __forceinline__ int unetk_key_index(unsigned long long key) { return (int)(0xffffffffu - (unsigned int)key); }
 
 // ---- internal cross-file helpers (not part of the C ABI)
 // Operand of the 2-D conv kernels.  "Images" are (n, d) planes of an N(D)HWC tensor: image i lives at

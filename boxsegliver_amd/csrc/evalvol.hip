@@ -3,7 +3,7 @@
 // transform and the surface-distance sums.  Masks are dense C-order uint8 [D,H,W], non-zero = object; D*H*W < 2^31, so a
 // linear voxel index fits an int32.  Every reduction runs in a fixed order: results are bit-reproducible run to run.
 #include "common.h"
-#include "unionfind.h"   // ld_label, lc_find, lc_union: shared with inter_eval.hip
+#include "unionfind.h"   // lc_find, lc_union, lc_union_back6, lc_flatten: shared with inter_eval.hip and inter_eval3d.hip
 
 namespace {
 
@@ -40,31 +40,12 @@ __global__ __launch_bounds__(EV_BLOCK) void lc_merge_kernel(const uint8_t* __res
   const int n = D * H * W;
   const int i = blockIdx.x * EV_BLOCK + threadIdx.x;
   if (i >= n || !mask[i]) return;
-  const int x = i % W, y = (i / W) % H, z = i / (H * W);
-  if (x > 0 && mask[i - 1]) lc_union(label, i, i - 1);
-  if (y > 0 && mask[i - W]) lc_union(label, i, i - W);
-  if (z > 0 && mask[i - H * W]) lc_union(label, i, i - H * W);
+  lc_union_back6(mask, label, i, i % W, (i / W) % H, i / (H * W), W, H * W);
 }
 
-// every voxel points straight at its root; component sizes by integer atomics at the root's slot, one per wave for the
-// lanes that share the wave's first root (the big component would otherwise take one atomic per voxel on one address)
+// every voxel points straight at its root; component sizes at the roots' slots
 __global__ __launch_bounds__(EV_BLOCK) void lc_flatten_kernel(int n, int* __restrict__ label, int* __restrict__ cnt) {
-  const int i = blockIdx.x * EV_BLOCK + threadIdx.x;
-  int r = -1;
-  if (i < n) {
-    const int l = label[i];
-    if (l >= 0) {
-      r = lc_find(label, l);
-      label[i] = r;
-    }
-  }
-  const int lead = __builtin_amdgcn_readfirstlane(r >= 0 ? r : 0x7fffffff);
-  const unsigned long long same = __ballot(r == lead);
-  if (r < 0) return;
-  if (r != lead)
-    atomicAdd(cnt + r, 1);
-  else if ((int)__lane_id() == __ffsll((long long)same) - 1)
-    atomicAdd(cnt + r, __popcll(same));
+  lc_flatten_count(label, cnt, (int)(blockIdx.x * EV_BLOCK + threadIdx.x), n);
 }
 
 // best = max over roots of (size << 32 | root): the largest component, the larger root (= scipy's larger label id) on ties
@@ -419,21 +400,9 @@ __global__ __launch_bounds__(EV_BLOCK) void sh_merge18_kernel(const uint8_t* __r
 // holds their largest z: consecutive lanes are consecutive voxels)
 __global__ __launch_bounds__(EV_BLOCK) void sh_flatten_kernel(int n, int HW, int* __restrict__ label, int* __restrict__ zmax) {
   const int i = blockIdx.x * EV_BLOCK + threadIdx.x;
-  int r = -1;
-  if (i < n) {
-    const int l = label[i];
-    if (l >= 0) {
-      r = lc_find(label, l);
-      label[i] = r;
-    }
-  }
-  const int lead = __builtin_amdgcn_readfirstlane(r >= 0 ? r : 0x7fffffff);
-  const unsigned long long same = __ballot(r == lead);
-  if (r < 0) return;
-  if (r != lead)
-    atomicMax(zmax + r, i / HW);
-  else if ((int)__lane_id() == 63 - __clzll((long long)same))
-    atomicMax(zmax + r, i / HW);
+  const LcFlat f = lc_flatten(label, i, n);
+  if (f.r < 0) return;
+  if (f.r != f.lead || (int)__lane_id() == 63 - __clzll((long long)f.same)) atomicMax(zmax + f.r, i / HW);
 }
 
 // array_kits.guide_pixel_list(middle, tile_guide): the voxels of component c on its middle slice m add their bins to
@@ -591,7 +560,7 @@ __global__ __launch_bounds__(EV_BLOCK) void gc_accum_kernel(int n, int H, int W,
         k = c;
         y = i / W;
         x = i - y * W;
-        key = ((unsigned long long)gc_order_bits(guide[i]) << 32) | (unsigned long long)(0xffffffffu - (unsigned int)i);
+        key = unetk_first_key(gc_order_bits(guide[i]), (unsigned int)i);
       }
     }
   }
@@ -600,12 +569,7 @@ __global__ __launch_bounds__(EV_BLOCK) void gc_accum_kernel(int n, int H, int W,
   const unsigned long long same = __ballot(k >= 0 && ry == lead);
   const int kl = __builtin_amdgcn_readfirstlane(k >= 0 ? k : 0x7fffffff);
   const bool in_lead = k >= 0 && k == kl;
-  unsigned long long m = in_lead ? key : 0ull;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long other = __shfl_xor(m, o);
-    m = other > m ? other : m;
-  }
+  const unsigned long long m = wave_max(in_lead ? key : 0ull);
   const int first = __ffsll((long long)__ballot(in_lead)) - 1;
   if (k < 0) return;
   if (ry != lead)
@@ -676,7 +640,7 @@ __global__ __launch_bounds__(EV_BLOCK) void gc_final_kernel(int H, int W, int ca
   row[3] = x0;
   row[4] = y1;
   row[5] = x1;
-  row[6] = (int32_t)(0xffffffffu - (unsigned int)(p & 0xffffffffull));
+  row[6] = unetk_key_index(p);
   row[7] = __float_as_int(gc_order_float((unsigned int)(p >> 32)));
   row[8] = __float_as_int(cy);
   row[9] = __float_as_int(cx);

@@ -13,24 +13,23 @@
 //                     smaller linear index
 //   ic_finish_kernel  the click's kind, the append to the session's lists, the table row
 // Integer arithmetic only.  The sums and maxima are integer atomics, which commute exactly: two calls give identical bits.
-#include "common.h"
-#include "lits_clicks.h"     // CLK_MAX_EXTENT, clk_col_sweeps, clk_row_minplus
-#include "unionfind.h"
+// The kernels' bodies from pick to far are inter_click.h's, shared with inter_eval3d.hip; here: which sessions run, the
+// resize of the prediction, the addresses of a session's planes, the finish kernel.
+#include "inter_click.h"
 
 namespace {
 
-constexpr int IC_BLOCK = 256;
-constexpr int IC_PER_THREAD = 8;         // pixels a thread of the reducing kernels walks
-constexpr int IC_CAP = 255;              // the distance cap: a byte
+constexpr int IC_CAP = 255;              // the distance cap: a byte (clk_col_sweeps wants <= 255, the key holds 8 bits)
 constexpr int IC_TW = UNETK_INTER_TAB_COLS, IC_RW = UNETK_INTER_ROW_COLS;
-enum { HD_NPRED = 0, HD_NREF, HD_NINTER, HD_NCOMP, HD_BEST, HD_SY, HD_SX, HD_FAR, HD_N };
-enum { IF_CY = 0, IF_CX, IF_FALLBACK, IF_ROOT, IF_AREA, IF_N = 8 };
+static_assert(IC_CAP <= 255, "a distance is a byte");
+using Ic = IcDim<2>;
+using Sl = IcSlots<2>;                   // header [HD_N]: HD_SUM + 0 / 1 = the y / x sums; info [IF_N]: IF_C + 0 / 1 = the candidate's y / x
 
 inline size_t ic_align(size_t b) { return (b + 255) & ~(size_t)255; }
 inline int ic_blocks(int plane) { return (plane + IC_BLOCK * IC_PER_THREAD - 1) / (IC_BLOCK * IC_PER_THREAD); }
 
 struct IcWs {
-  unsigned long long* hdr;   // [N][HD_N]
+  unsigned long long* hdr;   // [N][Sl::HD_N]
   int32_t* info;             // [N][IF_N]
   uint8_t *err, *gf, *dist;  // [N][plane]
   int *label, *cnt;          // [N][plane]
@@ -44,7 +43,7 @@ inline IcLayout ic_layout(const unetk_inter_click_desc* d) {
   IcLayout l;
   size_t o = 0;
   l.hdr = o;
-  o += ic_align(n * HD_N * 8);
+  o += ic_align(n * Sl::HD_N * 8);
   l.info = o;
   o += ic_align(n * IF_N * 4);
   l.zero = o;
@@ -83,20 +82,6 @@ __device__ __forceinline__ int ic_state(const unetk_inter_click_desc& d, const i
   return 1;
 }
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long other = __shfl_xor(v, o);
-    v = other > v ? other : v;
-  }
-  return v;
-}
-
 // ------------------------------------------------------------------------------------------------ err, counts, label init
 __global__ __launch_bounds__(IC_BLOCK) void ic_err_kernel(unetk_inter_click_desc d, const uint8_t* __restrict__ segs,
                                                           const int32_t* __restrict__ rows, const uint8_t* __restrict__ pred,
@@ -111,34 +96,19 @@ __global__ __launch_bounds__(IC_BLOCK) void ic_err_kernel(unetk_inter_click_desc
   uint8_t* err = w.err + (int64_t)n * plane;
   int* label = w.label + (int64_t)n * plane;
   int* cnt = w.cnt + (int64_t)n * plane;
-  unsigned long long np = 0, nr = 0, ni = 0;
-  const int base = blockIdx.x * IC_BLOCK * IC_PER_THREAD;
+  IcTally t;
 #pragma unroll
   for (int u = 0; u < IC_PER_THREAD; ++u) {
-    const int i = base + u * IC_BLOCK + threadIdx.x;
+    const int i = ic_strided<2>(u);
     if (i < plane) {
       const int y = i / d.src_w, x = i - y * d.src_w;
       const int p = pr ? (pr[(y * d.H / d.src_h) * d.W + x * d.W / d.src_w] != 0 ? 1 : 0) : 0;   // y * H < 2^31: ic_supported
       const int r = (int)seg[i] >= thr ? 1 : 0;
       if (vo) vo[i] = (uint8_t)p;
-      const int e = p ^ r;
-      err[i] = (uint8_t)e;
-      label[i] = e ? i : -1;
-      cnt[i] = 0;
-      np += p;
-      nr += r;
-      ni += p & r;
+      ic_mark(t, p, r, i, err, label, cnt);
     }
   }
-  np = wave_sum(np);
-  nr = wave_sum(nr);
-  ni = wave_sum(ni);
-  if ((threadIdx.x & 63) == 0) {
-    unsigned long long* h = w.hdr + (int64_t)n * HD_N;
-    if (np) atomicAdd(h + HD_NPRED, np);
-    if (nr) atomicAdd(h + HD_NREF, nr);
-    if (ni) atomicAdd(h + HD_NINTER, ni);
-  }
+  ic_tally(t, w.hdr + (int64_t)n * Sl::HD_N);
 }
 
 // ------------------------------------------------------------------------------------------------ components
@@ -150,121 +120,45 @@ __global__ __launch_bounds__(IC_BLOCK) void ic_merge_kernel(unetk_inter_click_de
   const uint8_t* err = w.err + (int64_t)n * plane;
   int* label = w.label + (int64_t)n * plane;
   if (i >= plane || !err[i]) return;
-  const int y = i / d.src_w, x = i - y * d.src_w;
-  if (x > 0 && err[i - 1]) lc_union(label, i, i - 1);
-  if (y > 0 && err[i - d.src_w]) lc_union(label, i, i - d.src_w);
+  const int y = i / d.src_w;
+  lc_union_back6(err, label, i, i - y * d.src_w, y, 0, d.src_w, plane);
 }
 
-// every pixel points straight at its root; sizes by integer atomics at the root's slot, one per wave for the lanes that
-// share the wave's first root (evalvol.hip's lc_flatten_kernel, per session)
 __global__ __launch_bounds__(IC_BLOCK) void ic_flatten_kernel(unetk_inter_click_desc d, const int32_t* __restrict__ rows,
                                                               bool has_vol, IcWs w) {
   const int n = blockIdx.y;
   if (ic_state(d, rows, n, has_vol) != 1) return;
-  const int plane = d.src_h * d.src_w, i = blockIdx.x * IC_BLOCK + threadIdx.x;
-  int* label = w.label + (int64_t)n * plane;
-  int* cnt = w.cnt + (int64_t)n * plane;
-  int r = -1;
-  if (i < plane) {
-    const int l = label[i];
-    if (l >= 0) {
-      r = lc_find(label, l);
-      label[i] = r;
-    }
-  }
-  const int lead = __builtin_amdgcn_readfirstlane(r >= 0 ? r : 0x7fffffff);
-  const unsigned long long same = __ballot(r == lead);
-  if (r < 0) return;
-  if (r != lead)
-    atomicAdd(cnt + r, 1);
-  else if ((int)__lane_id() == __ffsll((long long)same) - 1)
-    atomicAdd(cnt + r, __popcll(same));
+  const int plane = d.src_h * d.src_w;
+  lc_flatten_count(w.label + (int64_t)n * plane, w.cnt + (int64_t)n * plane, (int)(blockIdx.x * IC_BLOCK + threadIdx.x), plane);
 }
 
-// best = max over roots of (size << 32 | ~root): the largest component, the smaller root on ties
 __global__ __launch_bounds__(IC_BLOCK) void ic_pick_kernel(unetk_inter_click_desc d, const int32_t* __restrict__ rows,
                                                            bool has_vol, IcWs w) {
   const int n = blockIdx.y;
   if (ic_state(d, rows, n, has_vol) != 1) return;
   const int plane = d.src_h * d.src_w;
-  const int* label = w.label + (int64_t)n * plane;
-  const int* cnt = w.cnt + (int64_t)n * plane;
-  unsigned long long key = 0ull, roots = 0ull;
-  const int base = blockIdx.x * IC_BLOCK * IC_PER_THREAD;
-#pragma unroll
-  for (int u = 0; u < IC_PER_THREAD; ++u) {
-    const int i = base + u * IC_BLOCK + threadIdx.x;
-    if (i < plane && label[i] == i) {
-      const unsigned long long k = ((unsigned long long)(unsigned)cnt[i] << 32) | (unsigned long long)(0xffffffffu - (unsigned)i);
-      key = k > key ? k : key;
-      roots += 1;
-    }
-  }
-  key = wave_max(key);
-  roots = wave_sum(roots);
-  if ((threadIdx.x & 63) == 0 && roots) {
-    unsigned long long* h = w.hdr + (int64_t)n * HD_N;
-    atomicMax(h + HD_BEST, key);
-    atomicAdd(h + HD_NCOMP, roots);
-  }
+  ic_pick<2>(w.label + (int64_t)n * plane, w.cnt + (int64_t)n * plane, plane, w.hdr + (int64_t)n * Sl::HD_N);
 }
 
 __global__ __launch_bounds__(IC_BLOCK) void ic_mean_kernel(unetk_inter_click_desc d, const int32_t* __restrict__ rows,
                                                            bool has_vol, IcWs w) {
   const int n = blockIdx.y;
   if (ic_state(d, rows, n, has_vol) != 1) return;
-  unsigned long long* h = w.hdr + (int64_t)n * HD_N;
-  const unsigned long long best = h[HD_BEST];
-  if (best == 0ull) return;                                  // no error pixel
-  const int root = (int)(0xffffffffu - (unsigned)(best & 0xffffffffull));
   const int plane = d.src_h * d.src_w;
-  const int* label = w.label + (int64_t)n * plane;
-  unsigned long long sy = 0, sx = 0;
-  const int base = blockIdx.x * IC_BLOCK * IC_PER_THREAD;
-#pragma unroll
-  for (int u = 0; u < IC_PER_THREAD; ++u) {
-    const int i = base + u * IC_BLOCK + threadIdx.x;
-    if (i < plane && label[i] == root) {
-      const int y = i / d.src_w;
-      sy += (unsigned long long)y;
-      sx += (unsigned long long)(i - y * d.src_w);
-    }
-  }
-  sy = wave_sum(sy);
-  sx = wave_sum(sx);
-  if ((threadIdx.x & 63) == 0) {
-    if (sy) atomicAdd(h + HD_SY, sy);
-    if (sx) atomicAdd(h + HD_SX, sx);
-  }
+  ic_mean<2>(w.label + (int64_t)n * plane, plane, d.src_w, plane, w.hdr + (int64_t)n * Sl::HD_N);
 }
 
-// np.mean(...).round(0) of integers: s / a rounded half to even (the rule unetk_lits3d_clicks documents)
-__device__ __forceinline__ int ic_round_div(unsigned long long s, unsigned long long a) {
-  const unsigned long long q = s / a, r = s - q * a;
-  if (2 * r > a) return (int)q + 1;
-  if (2 * r == a) return (int)(q + (q & 1ull));
-  return (int)q;
-}
 __global__ void ic_cand_kernel(unetk_inter_click_desc d, const int32_t* __restrict__ rows, bool has_vol, IcWs w) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= d.N || ic_state(d, rows, n, has_vol) != 1) return;
-  const unsigned long long* h = w.hdr + (int64_t)n * HD_N;
-  int32_t* f = w.info + (int64_t)n * IF_N;
-  const unsigned long long best = h[HD_BEST];
-  if (best == 0ull) return;                                  // info stays zero: no fallback
-  const unsigned long long area = best >> 32;
-  const int cy = ic_round_div(h[HD_SY], area), cx = ic_round_div(h[HD_SX], area);   // inside the slice: a mean of its pixels
-  f[IF_CY] = cy;
-  f[IF_CX] = cx;
-  f[IF_ROOT] = (int)(0xffffffffu - (unsigned)(best & 0xffffffffull));
-  f[IF_AREA] = (int)area;
-  f[IF_FALLBACK] = w.err[(int64_t)n * d.src_h * d.src_w + (int64_t)cy * d.src_w + cx] ? 0 : 1;
+  const int plane = d.src_h * d.src_w;
+  ic_cand<2>(w.hdr + (int64_t)n * Sl::HD_N, w.info + (int64_t)n * IF_N, w.err + (int64_t)n * plane, d.src_w, plane);
 }
 
 // ------------------------------------------------------------------------------------------------ fallback: distances
 __global__ __launch_bounds__(64) void ic_cols_kernel(unetk_inter_click_desc d, IcWs w) {
   const int n = blockIdx.y, x = blockIdx.x * 64 + threadIdx.x;
-  if (w.info[(int64_t)n * IF_N + IF_FALLBACK] == 0 || x >= d.src_w) return;   // zero for rows that do not run
+  if (w.info[(int64_t)n * IF_N + Sl::IF_FALLBACK] == 0 || x >= d.src_w) return;   // zero for rows that do not run
   const int64_t plane = (int64_t)d.src_h * d.src_w;
   // the sweep's second field (distance to the nearest error pixel) is not used: it lands in `dist`, which the row pass rewrites
   clk_col_sweeps(w.err + n * plane + x, true, d.src_w, d.src_h, d.src_w, 1, IC_CAP, w.gf + n * plane + x, w.dist + n * plane + x);
@@ -273,39 +167,15 @@ __global__ __launch_bounds__(64) void ic_cols_kernel(unetk_inter_click_desc d, I
 __global__ __launch_bounds__(IC_BLOCK) void ic_rows_kernel(unetk_inter_click_desc d, IcWs w) {
   __shared__ int16_t buf[2][1][CLK_MAX_EXTENT];
   const int n = blockIdx.y, y = blockIdx.x;
-  if (w.info[(int64_t)n * IF_N + IF_FALLBACK] == 0) return;  // block-uniform
-  const int64_t plane = (int64_t)d.src_h * d.src_w;
-  const int cw = d.src_w;
-  const uint8_t* gf = w.gf + n * plane + (int64_t)y * cw;
-  uint8_t* dist = w.dist + n * plane + (int64_t)y * cw;
-  for (int x = threadIdx.x; x < cw; x += IC_BLOCK) buf[0][0][x] = (int16_t)min((int)gf[x], min(x + 1, cw - x));   // the slice's border
-  __syncthreads();
-  const int cur = clk_row_minplus<1>(buf, cw, IC_CAP);
-  for (int x = threadIdx.x; x < cw; x += IC_BLOCK) dist[x] = (uint8_t)buf[cur][0][x];
+  if (w.info[(int64_t)n * IF_N + Sl::IF_FALLBACK] == 0) return;  // block-uniform
+  const int64_t o = n * ((int64_t)d.src_h * d.src_w) + (int64_t)y * d.src_w;
+  ic_row_pass(buf, w.gf + o, w.dist + o, d.src_w, IC_CAP);
 }
 
-// key = distance (8 bits) | 2^21 - 1 - squared distance to the mean (21 bits: < 2 * 1023^2) | 2^20 - 1 - index (20 bits)
 __global__ __launch_bounds__(IC_BLOCK) void ic_far_kernel(unetk_inter_click_desc d, IcWs w) {
-  const int n = blockIdx.y;
-  const int32_t* f = w.info + (int64_t)n * IF_N;
-  if (f[IF_FALLBACK] == 0) return;
-  const int plane = d.src_h * d.src_w, root = f[IF_ROOT], cy = f[IF_CY], cx = f[IF_CX];
-  const int* label = w.label + (int64_t)n * plane;
-  const uint8_t* dist = w.dist + (int64_t)n * plane;
-  unsigned long long key = 0ull;
-  const int base = blockIdx.x * IC_BLOCK * IC_PER_THREAD;
-#pragma unroll
-  for (int u = 0; u < IC_PER_THREAD; ++u) {
-    const int i = base + u * IC_BLOCK + threadIdx.x;
-    if (i < plane && label[i] == root) {
-      const int y = i / d.src_w, x = i - y * d.src_w;
-      const unsigned long long d2 = (unsigned long long)((y - cy) * (y - cy) + (x - cx) * (x - cx));
-      const unsigned long long k = ((unsigned long long)dist[i] << 41) | ((0x1fffffull - d2) << 20) | (unsigned long long)(0xfffff - i);
-      key = k > key ? k : key;
-    }
-  }
-  key = wave_max(key);
-  if ((threadIdx.x & 63) == 0 && key) atomicMax(w.hdr + (int64_t)n * HD_N + HD_FAR, key);
+  const int n = blockIdx.y, plane = d.src_h * d.src_w;
+  ic_far<2>(w.label + (int64_t)n * plane, w.dist + (int64_t)n * plane, plane, d.src_w, plane, w.info + (int64_t)n * IF_N,
+            w.hdr + (int64_t)n * Sl::HD_N);
 }
 
 // ------------------------------------------------------------------------------------------------ click, lists, table
@@ -322,7 +192,7 @@ __global__ void ic_finish_kernel(unetk_inter_click_desc d, const uint8_t* __rest
   out[8] = out[9] = out[10] = -1;
   out[15] = state;
   if (state == 1) {
-    const unsigned long long* h = w.hdr + (int64_t)n * HD_N;
+    const unsigned long long* h = w.hdr + (int64_t)n * Sl::HD_N;
     const int32_t* f = w.info + (int64_t)n * IF_N;
     const int32_t* r = rows + (int64_t)n * IC_RW;
     out[0] = (int)h[HD_NPRED];
@@ -333,13 +203,13 @@ __global__ void ic_finish_kernel(unetk_inter_click_desc d, const uint8_t* __rest
       out[5] = out[6] = out[7] = -1;
       out[13] = 1;                                            // nothing to correct: no click
     } else {
-      int y = f[IF_CY], x = f[IF_CX];
-      out[4] = f[IF_AREA];
-      out[5] = f[IF_ROOT];
+      int y = f[IF_C], x = f[IF_C + 1];
+      out[4] = f[Sl::IF_AREA];
+      out[5] = f[Sl::IF_ROOT];
       out[6] = y;
       out[7] = x;
-      if (f[IF_FALLBACK]) {
-        const int i = 0xfffff - (int)(h[HD_FAR] & 0xfffffull);  // the component has a pixel: the key is not zero
+      if (f[Sl::IF_FALLBACK]) {
+        const int i = ic_far_index<Ic::D2_BITS, Ic::IDX_BITS>(h[Sl::HD_FAR]);   // the component has a pixel: the key is not zero
         y = i / d.src_w;
         x = i - y * d.src_w;
         out[11] = 1;

@@ -172,11 +172,6 @@ __device__ __forceinline__ unsigned int clk3_far_bound(int z, int y, int xa, int
   }
   return ub;
 }
-// np.round of sum / n for integers: half to even
-__device__ __forceinline__ int clk3_round_mean(unsigned long long sum, unsigned long long n) {
-  const unsigned long long q = sum / n, r2 = 2 * (sum - q * n);
-  return (int)(r2 < n ? q : (r2 > n ? q + 1 : q + (q & 1)));
-}
 
 __global__ __launch_bounds__(1024) void clk3_select_kernel(unetk_lits3d_clicks_desc d, const int32_t* __restrict__ tab,
                                                            const uint32_t* __restrict__ click_tab,
@@ -224,13 +219,10 @@ __global__ __launch_bounds__(1024) void clk3_select_kernel(unetk_lits3d_clicks_d
     for (int o = 32; o > 0; o >>= 1) cand += __shfl_xor(cand, o);
     if (lane == 0) scnt[z] = cand;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    nmask += __shfl_xor(nmask, o);
-    sz += __shfl_xor(sz, o);
-    sy += __shfl_xor(sy, o);
-    sx += __shfl_xor(sx, o);
-  }
+  nmask = wave_sum(nmask);
+  sz = wave_sum(sz);
+  sy = wave_sum(sy);
+  sx = wave_sum(sx);
   if (lane == 0) {
     red[wave][0] = nmask;
     red[wave][1] = sz;
@@ -255,9 +247,9 @@ __global__ __launch_bounds__(1024) void clk3_select_kernel(unetk_lits3d_clicks_d
   if (nmask == 0 || want == 0) {
     // no voxel to click on (deviation: the reference fails on an all-object patch), or no click drawn
   } else if (alive == 0) {                                   // "small": one click at the mask's mean, rounded half to even
-    c.z[0] = clk3_round_mean(sz, nmask);
-    c.y[0] = clk3_round_mean(sy, nmask);
-    c.x[0] = clk3_round_mean(sx, nmask);
+    c.z[0] = unetk_round_div_even(sz, nmask);
+    c.y[0] = unetk_round_div_even(sy, nmask);
+    c.x[0] = unetk_round_div_even(sx, nmask);
     c.n = 1;
   } else {
     int zl = -1;                                             // the slice whose per-wave counts wcnt holds (the last click's)
@@ -382,7 +374,7 @@ __global__ __launch_bounds__(1024) void clk3_select_kernel(unetk_lits3d_clicks_d
                 const int dz = z - c.z[m], dy = y - c.y[m], dx = x - c.x[m];
                 d2 = m < c.n ? min(d2, (unsigned int)(dz * dz + dy * dy + dx * dx)) : d2;
               }
-              const unsigned long long key = ((unsigned long long)d2 << 32) | (unsigned long long)(0xffffffffu - (unsigned int)i);
+              const unsigned long long key = unetk_first_key(d2, (unsigned int)i);
               best = key > best ? key : best;
             }
             ++i;
@@ -395,16 +387,12 @@ __global__ __launch_bounds__(1024) void clk3_select_kernel(unetk_lits3d_clicks_d
             }
           }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-          const unsigned long long other = __shfl_xor(best, o);
-          best = other > best ? other : best;
-        }
+        best = wave_max(best);
         if (lane == 0) wbest[wave] = best;
         __syncthreads();
         if (threadIdx.x == 0) {
           for (int w = 0; w < 16; ++w) best = wbest[w] > best ? wbest[w] : best;
-          const int i = (int)(0xffffffffu - (unsigned int)(best & 0xffffffffull));
+          const int i = unetk_key_index(best);
           const int z = i / area, r = i - z * area;
           pick[0] = z;
           pick[1] = r / cw;

@@ -246,12 +246,9 @@ __global__ __launch_bounds__(1024) void clk_select_kernel(unetk_lits_inter_desc 
       }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    nmask += __shfl_xor(nmask, o);
-    sy += __shfl_xor(sy, o);
-    sx += __shfl_xor(sx, o);
-  }
+  nmask = wave_sum(nmask);
+  sy = wave_sum(sy);
+  sx = wave_sum(sx);
   if (lane == 0) {
     wcnt[wave] = ncand;
     red[wave][0] = nmask;
@@ -342,20 +339,16 @@ __global__ __launch_bounds__(1024) void clk_select_kernel(unetk_lits_inter_desc 
               const int dy = y - c.y[j], dx = x - c.x[j];
               d2 = j < c.n ? min(d2, (unsigned int)(dy * dy + dx * dx)) : d2;
             }
-            const unsigned long long key = ((unsigned long long)d2 << 32) | (unsigned long long)(0xffffffffu - (unsigned int)i);
+            const unsigned long long key = unetk_first_key(d2, (unsigned int)i);
             best = key > best ? key : best;
           }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-          const unsigned long long other = __shfl_xor(best, o);
-          best = other > best ? other : best;
-        }
+        best = wave_max(best);
         if (lane == 0) wbest[wave] = best;
         __syncthreads();
         if (threadIdx.x == 0) {
           for (int w = 0; w < 16; ++w) best = wbest[w] > best ? wbest[w] : best;
-          const int i = (int)(0xffffffffu - (unsigned int)(best & 0xffffffffull));
+          const int i = unetk_key_index(best);
           pick[0] = i / cw;
           pick[1] = i - (i / cw) * cw;
         }
