@@ -261,6 +261,10 @@ _SIGNATURES = {
     "unetk_zoom_nearest3d": (c_int, [P, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, P, P]),
     "unetk_nii_compose": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                   P, P]),
+    "unetk_nii_ingest": (c_int, [P, c_int, c_int, c_int, c_int, c_double, c_double, c_int, c_int, c_int, c_int, c_int, c_int,
+                                 c_int, P, P]),
+    "unetk_eval3d_prob": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, POINTER(c_int32), c_int, c_int, c_int, c_int, P,
+                                  P]),
     "unetk_surface3d": (c_int, [P, c_int, c_int, c_int, P, P, c_int, P]),
     "unetk_edt3d_sq_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "unetk_edt3d_sq": (c_int, [P, c_int, c_int, c_int, P, c_double, c_double, c_double, P, P, c_size_t, P]),

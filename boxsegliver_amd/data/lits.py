@@ -3,7 +3,8 @@ DataLoader/Liver/input_pipeline.py (dataset collection :73-198, sampler `gen_tra
 `data_processing_train` :243-284) and DataLoader/misc.py (`read_or_create_k_folds` :45-74).
 
 On-disk format (the reference's own): `<root>/png/volume-<PID>/<slice:03d>_im.png` 16-bit grayscale = (HU clipped to
-[-200, 250] + 200) * IM_SCALE, `<slice:03d>_lb.png` 8-bit = label * LB_SCALE (IM_SCALE = LB_SCALE = 64, :47-48);
+[-250, 300] + 250) * IM_SCALE (DataLoader/Liver/extract.py:32-35,72; the evaluation window [-200, 250] of input_pipeline.py:45-46
+is the stored range [50, 500] * IM_SCALE), `<slice:03d>_lb.png` 8-bit = label * LB_SCALE (IM_SCALE = LB_SCALE = 64, :47-48);
 `meta.json` (shipped with the reference: 131 cases) and `k_folds.txt` ("Fold i:pid pid ...").
 
 Design: the reference feeds the GPU from tf.data CPU threads (PNG decode + crop + resize per sample per step).  An

@@ -46,7 +46,11 @@ Training sees only the boundary pixels inside the crop box, the interactive eval
 Offline, `input_fn_eval` tiles every case of the validation fold with windows cut as `eval_online` cuts them (window_starts,
 eval_tables) for the sliding-window evaluator, `EvaluateVolume.run_3d` (--eval_in_patches).  Two options
 of that evaluation live here too: the per-axis Gaussian window tables (window_weights, --eval_window_weight gaussian) and
-the box of a saved coarse prediction to which the windows are restricted (prediction_box, --eval_box_from)."""
+the box of a saved coarse prediction to which the windows are restricted (prediction_box, --eval_box_from).
+
+--mode infer (`input_fn_infer`) serves the same windows over NIfTI volumes that are not in the store: per file
+the voxel block goes into pinned memory (VolumeReader: one thread, one case ahead), is uploaded as it lies in the file, and
+`unetk_nii_ingest` writes the store's slices on the device (CaseStore)."""
 import math
 from pathlib import Path
 
@@ -114,9 +118,22 @@ def add_arguments(parser):
                         help="--eval_in_patches: tile only the box of predict-<case>.nii.gz in DIR (a --save_predict output)")
     parser.add_argument("--eval_box_margin", type=int, nargs=3, default=DEFAULT_BOX_MARGIN, metavar=("Z", "Y", "X"),
                         help="voxels the --eval_box_from box is grown by on each side, per axis")
+    parser.add_argument("--infer_volumes", type=str, nargs="+", default=None, metavar="FILE",
+                        help="--mode infer: the NIfTI volumes (.nii / .nii.gz) to segment, instead of the validation fold's")
+    parser.add_argument("--infer_dir", type=str, default=None, metavar="DIR",
+                        help="--mode infer: segment every *.nii / *.nii.gz of DIR, sorted by name")
 
 
 def check_args(args):
+    mode = getattr(args, "mode", "train")
+    if mode != "infer" and (getattr(args, "infer_volumes", None) or getattr(args, "infer_dir", None) is not None):
+        raise ValueError("--infer_volumes / --infer_dir name the volumes of --mode infer, got --mode {}".format(mode))
+    if mode == "infer" and (getattr(args, "slice_prior", "off") or "off") != "off":
+        raise NotImplementedError("--mode infer with --slice_prior is not built: a prior needs the clicks of the interactive "
+                                  "evaluator, entry/main_eval_3d.py")
+    if mode == "infer" and getattr(args, "use_spatial", False):
+        raise NotImplementedError("--mode infer with --use_spatial is not built: the sliding-window evaluator has no clicks -- "
+                                  "real or simulated clicks per case are the interactive evaluator's job, entry/main_eval_3d.py")
     check_values(args)
     if getattr(args, "use_spatial", False) and getattr(args, "mode", "train") == "eval":
         raise NotImplementedError("--mode eval with --use_spatial is not built: the sliding-window evaluator has no clicks -- real "
@@ -563,18 +580,22 @@ def window_weights(shape, sigma):
     return tuple(tables)
 
 
-def prediction_box(directory, case, depth, src_hw, margin=DEFAULT_BOX_MARGIN):
+def prediction_box(directory, case, depth, src_hw, margin=DEFAULT_BOX_MARGIN, special=None):
     """--eval_box_from: (z0, z1, y0, y1, x0, x1), the box of the foreground of `<directory>/predict-<PID>.nii.gz` (what
     --save_predict writes, voxel for voxel on the case's volume file), grown by margin = (z, y, x) and clamped to the case.
     The file is read with the volume's mirror rule (nii_kits.read_lits("vol"): cases 28..47), so the array lines up with
     the resident store.  A missing file, another shape than (depth, src_h, src_w) or an empty mask raise: there is no
     fallback to the whole volume."""
     from . import nii_kits
-    pid = int(case["PID"]) if isinstance(case, dict) else int(case)
+    if special is None:
+        pid = int(case["PID"]) if isinstance(case, dict) else int(case)
+        special = 28 <= pid < 48
+    else:                                                  # --mode infer: the case's id and mirror rule are the input file's
+        pid = str(case)
     path = Path(directory) / "predict-{}.nii.gz".format(pid)
     if not path.exists():
         raise FileNotFoundError("--eval_box_from: {} does not exist".format(path))
-    _, mask = nii_kits.read_nii(path, out_dtype=np.uint8, special=28 <= pid < 48)
+    _, mask = nii_kits.read_nii(path, out_dtype=np.uint8, special=special)
     want = (int(depth), int(src_hw[0]), int(src_hw[1]))
     if tuple(mask.shape) != want:
         raise ValueError("--eval_box_from: {} holds a volume of shape {}, case {} has {}".format(path, tuple(mask.shape), pid, want))
@@ -653,11 +674,16 @@ def input_fn_eval(mode, params):
     restricted to (prediction_box).  Labels never leave the device: the evaluator takes them from store.lb.
     Without the flag: the reference's other way, one forward over the whole case (entry/main_eval_3d.py), which is not built."""
     args = params["args"]
+    # NIfTI volumes in, --eval_in_patches implied (DESIGN.md 7.3.15) -- for arguments of --mode infer: the flags of that mode
+    # (which volumes, whether labels exist) are the arguments', so a mode that disagrees with them is served by nobody
+    if mode == "infer" and getattr(args, "mode", mode) == "infer":
+        return input_fn_infer(mode, params)
     if not getattr(args, "eval_in_patches", False):
         raise NotImplementedError("whole-volume 3-D evaluation of UNet3D on LiTS in ONE forward is not built; pass "
                                   "--eval_in_patches for the sliding-window evaluator")
     if mode != "eval":
-        raise NotImplementedError("`liver_3d` serves --mode train and --mode eval --eval_in_patches, got --mode {}".format(mode))
+        raise NotImplementedError("`liver_3d` serves --mode train, --mode eval --eval_in_patches and --mode infer with arguments "
+                                  "of that mode, got mode {} with --mode {}".format(mode, getattr(args, "mode", None)))
     check_args(args)
     return _eval_cases(args, params)
 
@@ -688,3 +714,217 @@ def _eval_cases(args, params):
         for tab in eval_tables(case, store, shape, float(getattr(args, "eval_overlap", 0.5)), variants, bs, box):
             yield tab, None
         yield None, end
+
+
+# ------------------------------------------------------------------------------------------------- NIfTI volumes in (--mode infer)
+NII_SUFFIXES = (".nii.gz", ".nii")
+
+
+def infer_case_id(path):
+    """(id, special) of an input volume: the file name without .nii[.gz]; `volume-<N>` is LiTS case N -- id "<N>", read with
+    read_lits's rule (x-mirrored for 28 <= N < 48, lits._load_lits_volume's distinction), so its slices equal the stored ones.
+    Any other name is read plainly."""
+    import re
+    name = Path(path).name
+    for suffix in NII_SUFFIXES:
+        if name.endswith(suffix):
+            name = name[:-len(suffix)]
+            break
+    else:
+        raise ValueError("{}: a .nii or .nii.gz file expected".format(path))
+    m = re.fullmatch(r"volume-(\d+)", name)
+    if m:
+        return str(int(m.group(1))), 28 <= int(m.group(1)) < 48
+    return name, False
+
+
+def infer_files(args, params):
+    """The volumes of --mode infer, in order: --infer_volumes as given, then --infer_dir's *.nii / *.nii.gz sorted by name;
+    with neither flag the `vol_case` files of the validation fold (meta.json under params["lits_root"], paths relative to
+    params["proj_root"]), as the 2-D --mode infer takes them.  A missing file raises FileNotFoundError naming it."""
+    volumes, directory = getattr(args, "infer_volumes", None), getattr(args, "infer_dir", None)
+    files = [Path(v) for v in (volumes or [])]
+    if directory is not None:
+        if not Path(directory).is_dir():
+            raise FileNotFoundError("--infer_dir: {} is not a directory".format(directory))
+        files += sorted((p for p in Path(directory).iterdir() if p.name.endswith(NII_SUFFIXES)), key=lambda p: p.name)
+    if not volumes and directory is None:
+        cases = lits.collect_datasets(params["lits_root"], args.test_fold, "val", filter_tumor_size=getattr(args, "filter_size", 0))
+        for case in cases:
+            if not case.get("vol_case"):
+                raise ValueError("--mode infer: case {} of meta.json names no vol_case; pass --infer_volumes or "
+                                 "--infer_dir".format(case["PID"]))
+            files.append(Path(params.get("proj_root", ".")) / case["vol_case"])
+    if not files:
+        raise ValueError("No valid dataset found!")
+    for f in files:
+        if not f.exists():
+            raise FileNotFoundError("--mode infer: the volume {} does not exist".format(f))
+    ids = [infer_case_id(f)[0] for f in files]
+    if len(set(ids)) != len(ids):
+        raise ValueError("--mode infer: two volumes share a case id (their outputs would share a file name): {}".format(ids))
+    return files
+
+
+def infer_plan(path):
+    """What unetk_nii_ingest needs of one file, from its header alone: dict(header, case, special, dtype, file_shape, nbytes,
+    trans_bk, flips, shape = (d, h, w)).  Big-endian files, other than 3-D data and oblique affines are refused."""
+    from . import nii_kits
+    header = nii_kits.load_header(path)
+    if header.endian != "<":
+        raise ValueError("{}: big-endian NIfTI files are not supported".format(path))
+    if len(header.shape) != 3 or min(header.shape) < 1:
+        raise ValueError("{}: a 3-D volume expected, the file holds shape {}".format(path, header.shape))
+    if header.dtype.name not in ops.NII_INGEST_CODES:
+        raise ValueError("{}: unsupported NIfTI datatype {}".format(path, header.dtype))
+    case, special = infer_case_id(path)
+    try:
+        trans_bk, flips = nii_kits.file_orientation(header, special)
+    except ValueError as e:
+        raise ValueError("{}: {}".format(path, e))
+    return dict(header=header, case=case, special=special, dtype=header.dtype, file_shape=tuple(header.shape),
+                nbytes=int(np.prod(header.shape)) * header.dtype.itemsize, trans_bk=trans_bk, flips=flips,
+                shape=nii_kits.data_shape(header))
+
+
+def read_voxel_block(path, header, view):
+    """The file's voxel block (what lies behind vox_offset) straight into `view`, a writable byte buffer of exactly the
+    block's size; a .gz is inflated with readinto -- no intermediate copy of the volume exists.  Every failure names the file."""
+    import zlib
+    from . import nii_kits
+    view = memoryview(view).cast("B")
+    try:
+        with nii_kits._open(path, "rb") as f:
+            skip = int(header.vox_offset)
+            if len(f.read(skip)) != skip:
+                raise ValueError("ends inside its header")
+            got = 0
+            while got < len(view):
+                n = f.readinto(view[got:])
+                if not n:
+                    break
+                got += n
+            if got == len(view):
+                f.read(1)                                  # a .gz whose stream ends here checks its CRC now, not never
+        if got != len(view):
+            raise ValueError("holds {} of the {} bytes of its voxel block".format(got, len(view)))
+    except (OSError, EOFError, ValueError, zlib.error) as e:
+        if isinstance(e, FileNotFoundError):
+            raise FileNotFoundError("--mode infer: the volume {} does not exist".format(path))
+        raise ValueError("{}: {}".format(path, e))
+
+
+class VolumeReader(object):
+    """The host side of --mode infer: header, then the voxel block into one of two staging buffers (pinned on a GPU run, grown
+    to the largest case seen).  With ahead=True ONE background thread reads and inflates file i + 1 while the caller works on
+    file i -- at most one case ahead; what the thread met is re-raised by `get`.  Headers are read and buffers grown in the
+    caller's thread; the thread does file I/O and zlib only (both release the interpreter lock)."""
+
+    def __init__(self, files, device, ahead=True):
+        import concurrent.futures
+        self.files, self.pin = list(files), torch.device(device).type == "cuda"
+        self.bufs, self.uploaded = [None, None], [None, None]
+        self.pool = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix="volume-reader") if ahead else None
+        self.jobs = {}
+
+    def _start(self, i):
+        plan = infer_plan(self.files[i])
+        slot = i & 1
+        if self.uploaded[slot] is not None:                # the upload that last used this buffer has left it
+            self.uploaded[slot].synchronize()
+            self.uploaded[slot] = None
+        if self.bufs[slot] is None or self.bufs[slot].numel() < plan["nbytes"]:
+            self.bufs[slot] = torch.empty(plan["nbytes"], dtype=torch.uint8, pin_memory=self.pin)
+        view = self.bufs[slot].numpy()[:plan["nbytes"]]
+        job = self.pool.submit(read_voxel_block, self.files[i], plan["header"], view) if self.pool is not None else None
+        self.jobs[i] = (plan, job, view)
+
+    def prefetch(self, i):
+        """Start on file i (no-op past the end, when it is started already, or without the thread)."""
+        if self.pool is not None and i < len(self.files) and i not in self.jobs:
+            self._start(i)
+
+    def get(self, i):
+        """(plan, block): file i's infer_plan and its voxel block, a uint8 host tensor in the staging buffer."""
+        if i not in self.jobs:
+            self._start(i)
+        plan, job, view = self.jobs.pop(i)
+        if job is not None:
+            job.result()                                   # re-raises the thread's exception, which names the file
+        else:
+            read_voxel_block(self.files[i], plan["header"], view)
+        return plan, self.bufs[i & 1][:plan["nbytes"]]
+
+    def sent(self, i):
+        """The caller has queued the upload of file i's block on the current stream."""
+        if self.pin:
+            self.uploaded[i & 1] = torch.cuda.Event()
+            self.uploaded[i & 1].record()
+
+    def close(self):
+        if self.pool is not None:
+            self.pool.shutdown(wait=True)
+            self.pool = None
+
+
+class CaseStore(object):
+    """One ingested volume as the windows' kernels see a store (the duck type of lits.SliceStore): `im` the int16-typed storage
+    of the uint16 pixels [d, h, w], `lb` zeros of the same shape, the case at offset 0."""
+
+    def __init__(self, im, lb, device):
+        self.im, self.lb, self.offset, self.device = im, lb, {0: 0}, device
+
+
+def input_fn_infer(mode, params):
+    """`liver_3d --mode infer`: per input volume (infer_files) the header is read, the voxel block goes
+    through VolumeReader into staging memory, is uploaded as it lies in the file and `unetk_nii_ingest` turns it into the
+    store's slices on the device -- a CaseStore per case, slices of any one size.  Then exactly what `_eval_cases` yields: the
+    case's window tables (here with dict(store=...) beside them, there is no fold-wide store) and the end-of-case item, which
+    also carries `header` and `special` for the saver.  --eval_overlap, --eval_mirror, --eval_window_weight and --eval_box_from
+    (the box of DIR/predict-<case>.nii.gz) apply unchanged; --eval_in_patches is implied.
+    params["infer_read_ahead"] = False reads every file in the caller's thread (measurements)."""
+    args = params["args"]
+    if mode != "infer" or getattr(args, "mode", "infer") != "infer":
+        raise ValueError("lits3d.input_fn_infer serves --mode infer, got {} / --mode {}".format(mode, getattr(args, "mode", None)))
+    check_args(args)
+    files = infer_files(args, params)
+    files = files[int(getattr(args, "eval_skip_num", 0) or 0):]
+    if int(getattr(args, "eval_num", -1)) > 0:
+        files = files[:int(args.eval_num)]
+    return _infer_cases(args, params, files)
+
+
+def _infer_cases(args, params, files):
+    device = params.get("device") or torch.device("cuda", torch.cuda.current_device())
+    bs = distribution_utils.per_device_batch_size(args.batch_size, args.num_gpus)
+    shape = (int(args.im_depth), int(args.im_height), int(args.im_width))
+    variants = mirror_variants(args)
+    box_from = getattr(args, "eval_box_from", None)
+    reader = VolumeReader(files, device, ahead=bool(params.get("infer_read_ahead", True)))
+    zeros = None                                           # the labels of every case: zeroed once, grown to the largest case
+    try:
+        for i in range(len(files)):
+            plan, block = reader.get(i)
+            dev_block = torch.empty(block.numel(), dtype=torch.uint8, device=device)
+            dev_block.copy_(block, non_blocking=True)
+            reader.sent(i)
+            reader.prefetch(i + 1)
+            header = plan["header"]
+            im = ops.nii_ingest(dev_block, plan["dtype"], plan["file_shape"], plan["trans_bk"], plan["flips"], header.scl_slope,
+                                header.scl_inter)
+            del dev_block
+            depth, src_h, src_w = plan["shape"]
+            if zeros is None or zeros.numel() < im.numel():
+                zeros = torch.zeros(im.numel(), dtype=torch.uint8, device=device)
+            store = CaseStore(im, zeros[:im.numel()].view(im.shape), device)
+            case = {"PID": 0, "size": [depth, src_h, src_w]}                   # the one case of its store, at offset 0
+            end = dict(case=plan["case"], base=0, depth=depth, store=store, header=header, special=plan["special"])
+            box = None
+            if box_from is not None:
+                box = end["box"] = prediction_box(box_from, plan["case"], depth, (src_h, src_w),
+                                                  getattr(args, "eval_box_margin", DEFAULT_BOX_MARGIN), special=plan["special"])
+            for tab in eval_tables(case, store, shape, float(getattr(args, "eval_overlap", 0.5)), variants, bs, box):
+                yield tab, {"store": store}
+            yield None, end
+    finally:
+        reader.close()

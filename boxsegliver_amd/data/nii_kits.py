@@ -310,6 +310,19 @@ def to_file_order(data, header, special=False, out_dtype=np.int16):
     return np.transpose(data, trans_bk).astype(out_dtype).reshape(-1, order="F")
 
 
+PROB_LEVELS = 255           # --pred_type prob of the 3-D path: probabilities are stored as uint8 q = rint(255 p), scl_slope 1 / 255
+
+
+def prob_header(header):
+    """The header of a saved probability volume: `header`'s geometry with datatype uint8, scl_slope = 1 / 255 and
+    scl_inter = 0, so any NIfTI reader (`load` included) returns q / 255 in [0, 1]."""
+    import copy
+    out = copy.copy(header)
+    out.dtype = np.dtype(np.uint8)
+    out.scl_slope, out.scl_inter = 1.0 / PROB_LEVELS, 0.0
+    return out
+
+
 def header_from_meta(size, spacing, dtype=np.int16):
     """A header for a case known only from meta.json (size = [d, h, w], spacing = [z, y, x]): pixdim (sx, sy, sz) and
     sform diag(-sx, -sy, +sz) with zero offsets -- the orientation read_nii returns unflipped, so the array index of the

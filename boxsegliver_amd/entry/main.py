@@ -103,6 +103,9 @@ def run(args, sub, pipe, guided=False, dataset_params=None):
     if sub == "liver_inter":                             # refused flags and modes raise before anything is loaded
         from ..data import lits_inter
         lits_inter.check_args(args)
+    if sub == "liver_3d":                                # likewise: --infer_volumes / --infer_dir outside --mode infer, clicks in it
+        from ..data import lits3d
+        lits3d.check_args(args)
     _setup_logging(args)
     log.debug(args)
     if args.num_gpus < 2:
@@ -183,7 +186,9 @@ def run(args, sub, pipe, guided=False, dataset_params=None):
                 args.model_dir, args.load_status_file if not args.eval_final else None))
         if propagated:                                   # entry/main_g.py:218-228: guide propagation (EvaluateVolume.run_g)
             return evaluator.run_g(input_fn_eval, checkpoint_path=ckpt, save=args.save_predict)
-        if sub == "liver_3d" and args.mode == ModeKeys.EVAL:      # UNet3D on LiTS: sliding windows (EvaluateVolume.run_3d)
+        if sub == "liver_3d":                            # UNet3D on LiTS: sliding windows (EvaluateVolume.run_3d); --mode infer
+            if args.mode == ModeKeys.PREDICT:            # takes NIfTI volumes (lits3d.input_fn_infer) and implies the windows
+                args.eval_in_patches = True
             return evaluator.run_3d(input_fn_eval, checkpoint_path=ckpt, save=args.save_predict)
         return evaluator.run(input_fn_eval, checkpoint_path=ckpt, save=args.save_predict)
 

@@ -37,7 +37,9 @@ With --use_spatial, `run_g` (evaluator_liver.py:768-917) evaluates by guide prop
 state machine, `_GuidedLoop` the per-slice device work (one forward, unetk_guide_components, one table copy, unetk_guide_render).
 
 UNet3D on LiTS (`liver_3d --eval_in_patches`) is scored by `run_3d`: sliding windows from data/lits3d.input_fn_eval, one forward per
-batch, `unetk_eval3d_accumulate` into the case at source resolution, then the same scoring.
+batch, `unetk_eval3d_accumulate` into the case at source resolution, then the same scoring.  With --mode infer
+the cases are NIfTI volumes ingested on the device (data/lits3d.input_fn_infer): no labels, no metrics, and the
+saved files carry the input's header; --pred_type prob saves `prob-<case>-<Class>.nii.gz` from the accumulator (`unetk_eval3d_prob`).
 """
 import json
 import logging
@@ -137,7 +139,7 @@ class CaseWindows3D(object):
         self.gaussian = getattr(cfg, "eval_window_weight", "uniform") == "gaussian"
         self.boxed = getattr(cfg, "eval_box_from", None) is not None
         self.host_tables = lits3d.window_weights(self.shape, getattr(cfg, "eval_window_sigma", 0.125)) if self.gaussian else None
-        self.acc = self.cnt = self.tables = None
+        self.acc = self.cnt = self.tables = self.kept = None
 
     def add(self, store, tab, sp_guide=None, before_forward=None, prior=None):
         from ..data import lits, lits3d
@@ -168,11 +170,13 @@ class CaseWindows3D(object):
         lb = store.lb[base:base + depth]
         return torch.clamp(torch.div(lb, lits.LB_SCALE, rounding_mode="floor"), max=self.lab_max).to(torch.uint8)
 
-    def finish(self, box=None):
+    def finish(self, box=None, keep=False):
         """(class volume uint8 [depth, src_h, src_w], coverage): the coverage volume of the plain path, or the word [1] that
-        `unetk_eval3d_finish` counted the box's voxels without cover into.  The case's accumulator is dropped."""
+        `unetk_eval3d_finish` counted the box's voxels without cover into.  The case's accumulator is dropped, or with keep
+        (--pred_type prob) handed back in `self.kept` = (acc, weight) for `unetk_eval3d_prob`."""
         acc, cnt = self.acc, self.cnt
         self.acc = self.cnt = None
+        self.kept = (acc, cnt) if keep else None
         if self.gaussian or self.boxed:
             uncovered = torch.zeros(1, dtype=torch.int32, device=acc.device)
             whole = (0, acc.shape[0], 0, acc.shape[1], 0, acc.shape[2])
@@ -567,15 +571,28 @@ class EvaluateVolume(EvaluateBase):
                 if checkpoint_path and self.estimator is not None:
                     self.estimator._restore(checkpoint_path, model, None)
 
+        do_eval = mode not in ("predict", ModeKeys.PREDICT)
+        want_prob = getattr(cfg, "pred_type", "pred") == "prob"
+
         def run_pred():
             for tab, end in input_fn(mode, params):
-                store = params[("lits_store", False)][0]            # input_fn_eval made it resident before its first item
                 if tab is not None:
+                    # --mode infer: the table's own one-case store; else the fold's, resident before input_fn_eval's first item
+                    store = end["store"] if end is not None else params[("lits_store", False)][0]
                     windows.add(store, tab, before_forward=restore_once)
                 else:
                     if windows.acc is None or end["depth"] != windows.acc.shape[0]:
                         raise RuntimeError("case {} ended without windows of its own".format(end["case"]))
-                    yield (end["case"], windows.labels(end["store"], end["base"], end["depth"])) + windows.finish(end.get("box"))
+                    if self._saver is not None and end.get("header") is not None:
+                        self._saver.given[str(end["case"])] = (end["header"], bool(end.get("special", False)))
+                    # --mode infer makes no label request: there is nothing to score
+                    labels = windows.labels(end["store"], end["base"], end["depth"]) if do_eval else None
+                    volume, cover = windows.finish(end.get("box"), keep=want_prob)
+                    probs = None
+                    if want_prob:
+                        probs = windows.kept + (end.get("box"),)
+                        windows.kept = None
+                    yield end["case"], labels, volume, cover, probs
 
         n_cases = cases if cases is not None else getattr(cfg, "eval_num", -1)
         return self._run_actual(self._predict_case_3d, run_pred, save, cases=n_cases)
@@ -583,17 +600,22 @@ class EvaluateVolume(EvaluateBase):
     def _predict_case_3d(self, predicts, cases=-1, dtype="pred", save_path=None):
         """A case of run_3d for _run_actual: (case, device labels, device class volume uint8 [depth, src_h, src_w], False).
         The coverage is read here, where the scoring that follows synchronises anyway.  With save_path the volume is saved as
-        in _predict_case, its box being the whole case at source resolution."""
-        if dtype != "pred":
-            raise NotImplementedError("the sliding-window 3-D evaluation scores class predictions (--pred_type pred)")
+        in _predict_case, its box being the whole case at source resolution.  --pred_type prob: the class volume is still what
+        is yielded (and scored in --mode eval); what is saved is one `prob-<case>-<Class>.nii.gz` per foreground class instead
+        (`unetk_eval3d_prob` on the case's accumulator, _CaseSaver.save_prob)."""
         counter = 0
-        for case, labels, volume, cnt in predicts:
+        for case, labels, volume, cnt, probs in predicts:
             # cnt: the coverage volume [depth, src_h, src_w] of the plain path, or the word [1] eval3d_finish counted into
             if (int(cnt.item()) != 0) if cnt.dim() == 1 else (int(cnt.min().item()) <= 0):
                 raise RuntimeError("--eval_in_patches: windows do not cover every voxel of case {}".format(case))
             depth, src_h, src_w = (int(v) for v in volume.shape)
-            yield (case, labels) + self._maybe_save_case(case, volume, (0, 0, 0, src_w - 1, src_h - 1, depth - 1), dtype,
-                                                         save_path)
+            if dtype != "pred":
+                if save_path is not None and self._saver is not None:
+                    self._saver.save_prob(str(case), *probs)
+                yield case, labels, volume, False
+            else:
+                yield (case, labels) + self._maybe_save_case(case, volume, (0, 0, 0, src_w - 1, src_h - 1, depth - 1), dtype,
+                                                             save_path)
             counter += 1
             if 0 < cases <= counter:
                 break
@@ -810,7 +832,8 @@ class _CaseSaver(object):
     path (np.pad, write_nii's flips and transpose) runs in the writer thread.  Both write the same bytes.  The files are
     written by utils/volume_writer.VolumeWriter behind the evaluation of the next case.
 
-    Header: the case's `vol_case` of meta.json under params["proj_root"], read header-only; when the entry or the file is
+    Header: what the input function handed in for the case (`given`: liver_3d --mode infer, the input file's own), else the
+    case's `vol_case` of meta.json under params["proj_root"], read header-only; when the entry or the file is
     missing (the PNG store of liver_3d needs no NIfTI), nii_kits.header_from_meta of its `size` and `spacing`, logged once.
     Unlike the reference, which calls write_nii without `special`, the write inverts the read: cases 28..47 are x-mirrored
     as read_lits("vol") mirrors them, so voxel (i, j, k) of the written file is voxel (i, j, k) of the volume file."""
@@ -821,6 +844,7 @@ class _CaseSaver(object):
         self.writer = VolumeWriter()
         self._meta = None
         self._told_fallback = False
+        self.given = {}                 # case -> (header, special) handed in by the input function (liver_3d --mode infer)
 
     def abandon(self):
         """The way out of an exception: stop the thread; what it met is second to the exception under way."""
@@ -842,6 +866,8 @@ class _CaseSaver(object):
         """(header, special) of a case; special = the x mirror of read_lits("vol")."""
         from ..data import nii_kits
         from ..data.lits import _maybe_json
+        if str(case) in self.given:                                   # the input file's own header comes first
+            return self.given[str(case)]
         pid = int(case)
         meta = self._case_meta(pid)
         if meta is None:
@@ -857,6 +883,23 @@ class _CaseSaver(object):
             log.info("--save_predict: no volume file for case %s (vol_case %r); headers are built from meta.json's size and "
                      "spacing", case, vol_case)
         return nii_kits.header_from_meta(_maybe_json(meta["size"]), _maybe_json(meta["spacing"])), special
+
+    def save_prob(self, case, acc, weight, box=None):
+        """--pred_type prob of the sliding-window 3-D path: one `prob-<case>-<Class>.nii.gz` per foreground class, uint8
+        q = rint(255 p) in the case's file order with scl_slope = 1 / 255 (nii_kits.prob_header), composed on the device by
+        `unetk_eval3d_prob` from the case's accumulator and written by the same thread."""
+        from ..data import nii_kits
+        header, special = self.header(case)
+        case_shape = nii_kits.data_shape(header)
+        if tuple(acc.shape[:3]) != tuple(case_shape):
+            raise ValueError("--save_predict: the accumulator of case {} has shape {}, its volume {}".format(
+                case, tuple(acc.shape[:3]), case_shape))
+        trans_bk, flips = nii_kits.file_orientation(header, special)
+        file_shape = tuple(case_shape[axis] for axis in trans_bk)
+        out_header = nii_kits.prob_header(header)
+        for i, cls in enumerate(self.ev.classes):
+            flat = ops.eval3d_prob(acc, weight, i + 1, box, trans_bk, flips)
+            self.writer.submit(self.save_path / "prob-{}-{}.nii.gz".format(case, cls), out_header, file_shape, flat)
 
     def save(self, case, volume, bbox, dtype):
         from ..data import nii_kits

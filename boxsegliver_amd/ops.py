@@ -1527,6 +1527,46 @@ def nii_compose(liver, tumor, origin, case_shape, trans_bk=(2, 1, 0), flips=(Fal
     return out
 
 
+NII_INGEST_CODES = {"uint8": 2, "int16": 4, "int32": 8, "float32": 16, "float64": 64, "int8": 256, "uint16": 512, "uint32": 768}
+STORE_WINDOW = (-250, 300, 64)      # (lo, hi, scale) of the slice store's pixels: DataLoader/Liver/extract.py:32-35
+
+
+def nii_ingest(block, dtype, file_shape, trans_bk=(2, 1, 0), flips=(False, False, False), slope=0.0, inter=0.0, out=None,
+               window=STORE_WINDOW):
+    """A NIfTI file's voxel block as store slices (unetk_nii_ingest): block = the file's bytes behind
+    vox_offset on the device (a dense uint8 tensor of at least prod(file_shape) * itemsize bytes, little-endian), dtype its
+    numpy datatype name, file_shape = (n0, n1, n2) with axis 0 fastest; trans_bk and flips = (flip_x, flip_y, flip_z) are
+    nii_kits.file_orientation's.  slope / inter: the header's scl_slope / scl_inter (applied when the slope is neither 0 nor
+    NaN).  Returns the int16-typed storage [d, h, w] of the uint16 pixels (clip(int16(v), lo, hi) - lo) * scale, bit for bit
+    what nii_kits.read_nii and the store's encoding give.  out: a dense int16 [d, h, w] tensor to write into."""
+    _require_cuda(block)
+    name = str(getattr(dtype, "name", dtype))
+    if name not in NII_INGEST_CODES:
+        raise ValueError("unsupported NIfTI datatype {}".format(dtype))
+    item = {2: 1, 256: 1, 4: 2, 512: 2, 8: 4, 16: 4, 768: 4, 64: 8}[NII_INGEST_CODES[name]]
+    n0, n1, n2 = (int(v) for v in file_shape)
+    if block.dtype != torch.uint8 or block.dim() != 1 or not block.is_contiguous() or block.numel() < n0 * n1 * n2 * item:
+        raise ValueError("a dense 1-D uint8 tensor of at least {} bytes expected".format(n0 * n1 * n2 * item))
+    tb = tuple(int(v) for v in trans_bk)
+    if sorted(tb) != [0, 1, 2]:
+        raise ValueError("trans_bk must be a permutation of (0, 1, 2), got {}".format(trans_bk))
+    zyx = [0, 0, 0]
+    for k, axis in enumerate(tb):
+        zyx[axis] = (n0, n1, n2)[k]
+    fx, fy, fz = (bool(f) for f in flips)
+    lo, hi, scale = (int(v) for v in window)
+    if out is None:
+        out = torch.empty(tuple(zyx), dtype=torch.int16, device=block.device)
+    _require_cuda(out)
+    if out.dtype != torch.int16 or tuple(out.shape) != tuple(zyx) or not out.is_contiguous():
+        raise ValueError("out must be a dense int16 {} tensor".format(tuple(zyx)))
+    with _timed_hbm("nii_ingest", out, 1, n0 * n1 * n2 * item):        # the block read once, the slices written once
+        check(_abi.lib().unetk_nii_ingest(ptr(block), NII_INGEST_CODES[name], n0, n1, n2, float(slope), float(inter), tb[0], tb[1],
+                                          tb[2], int(fx) | int(fy) << 1 | int(fz) << 2, lo, hi, scale, ptr(out), stream_ptr()),
+              "nii_ingest")
+    return out
+
+
 def _mask_bytes(t):
     """A [D, H, W] device mask as dense bytes, values kept (bool -> 0 / 1)."""
     _require_cuda(t)
@@ -1798,6 +1838,34 @@ def eval3d_finish(acc, weight, box, uncovered):
                                              None if is_w else ptr(weight), cbox, ptr(pred), ptr(uncovered), stream_ptr()),
               "eval3d_finish")
     return pred
+
+
+def eval3d_prob(acc, weight, cls, box=None, trans_bk=(2, 1, 0), flips=(False, False, False), out=None):
+    """The probability of class `cls` of a sliding-window case as a saved volume (unetk_eval3d_prob): acc, weight and box as
+    eval3d_finish takes them (box None: the whole case).  Returns the flat uint8 device tensor of depth * src_h * src_w
+    elements in NIfTI file order (trans_bk, flips = (flip_x, flip_y, flip_z): nii_kits.file_orientation), q = rint(255 * acc /
+    weight) clamped to 0..255, and 0 where the weight is not positive or outside the box.  Current stream."""
+    _require_cuda(acc, weight)
+    assert acc.dtype == torch.float32 and acc.dim() == 4 and acc.is_contiguous()
+    assert weight.dtype in (torch.float32, torch.int32) and tuple(weight.shape) == tuple(acc.shape[:3]) and weight.is_contiguous()
+    depth, src_h, src_w, c = (int(v) for v in acc.shape)
+    tb = tuple(int(v) for v in trans_bk)
+    if sorted(tb) != [0, 1, 2]:
+        raise ValueError("trans_bk must be a permutation of (0, 1, 2), got {}".format(trans_bk))
+    fx, fy, fz = (bool(f) for f in flips)
+    if out is None:
+        out = torch.empty(depth * src_h * src_w, dtype=torch.uint8, device=acc.device)
+    _require_cuda(out)
+    if out.dtype != torch.uint8 or out.numel() != depth * src_h * src_w or not out.is_contiguous():
+        raise ValueError("out must be a dense uint8 tensor of {} elements".format(depth * src_h * src_w))
+    cbox = (ctypes.c_int32 * 6)(*(int(v) for v in (box if box is not None else (0, depth, 0, src_h, 0, src_w))))
+    is_w = weight.dtype == torch.float32
+    # algorithmic bytes: one class of acc and the weight read once, the volume written
+    with _timed_hbm("eval3d_prob", weight, 2, out.numel()):
+        check(_abi.lib().unetk_eval3d_prob(ptr(acc), c, int(cls), depth, src_h, src_w, ptr(weight) if is_w else None,
+                                           None if is_w else ptr(weight), cbox, tb[0], tb[1], tb[2],
+                                           int(fx) | int(fy) << 1 | int(fz) << 2, ptr(out), stream_ptr()), "eval3d_prob")
+    return out
 
 
 def lits_inter_desc(slices, n, shape, training=False, obj_label=1, im_scale=64, lab_scale=64, noise_scale=0.0, seed=0,

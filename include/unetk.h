@@ -722,6 +722,25 @@ int unetk_zoom_nearest3d(const uint8_t* src, int d, int h, int w, const int32_t*
  * non-positive size, a box outside the case, (t0, t1, t2) not a permutation; UNETK_E_UNSUPPORTED: d * h * w >= 2^31. */
 int unetk_nii_compose(const uint8_t* liver, const uint8_t* tumor, int bd, int bh, int bw, int z1, int y1, int x1, int d, int h,
                       int w, int t0, int t1, int t2, int flips, int16_t* dst, void* stream);
+/* A NIfTI volume into store slices (nii_kits.py:33-50 `read_nii` and DataLoader/Liver/extract.py:72): the
+ * inverse walk of unetk_nii_compose.  src: the file's voxel block as it lies in the file behind vox_offset (little-endian), on
+ * the device, n0 * n1 * n2 elements of NIfTI `datatype` (2 uint8, 4 int16, 8 int32, 16 float32, 64 float64, 256 int8,
+ * 512 uint16, 768 uint32), file axis 0 fastest.  (t0, t1, t2) and `flips` in unetk_nii_compose's convention: file axis k runs
+ * along data axis t_k (0 = z, 1 = y, 2 = x), backwards along the data axes whose bit of `flips` is set (bit 0 = x, 1 = y,
+ * 2 = z).  dst uint16 [d,h,w] dense in (z, y, x) order (the int16-typed storage of a slice store), d, h, w = the n_k of the
+ * file axes along z, y, x; every element is written exactly once by plain stores; no workspace.
+ * Value, bit for bit the host's: v = (double)raw, and v * scl_slope + scl_inter (product and sum rounded on their own) when
+ * scl_slope is neither 0 nor NaN; v16 = v cast to int16 by truncation toward zero -- where numpy leaves the cast undefined this
+ * library defines it: NaN gives 0, values beyond [-32768, 32767] saturate; dst = (min(max(v16, lo), hi) - lo) * scale.  The
+ * store's encoding is lo = -250, hi = 300, scale = 64 (extract.py:32-35).
+ * t0 == 2 (every LiTS file): int16 without scaling from a 16-byte aligned src moves in 16-byte loads and, where the row's place
+ * in dst is 16-byte aligned, 16-byte stores, reversed in the registers under an x flip; any other datatype, a scaled source or
+ * a src that is not 16-byte aligned goes one element per thread.  t0 != 2: a tiled transpose through LDS, reads and writes
+ * both coalesced.  UNETK_E_BADARG (nothing is written): src or dst NULL, dst not 2-byte aligned, src not aligned for its
+ * datatype, an unknown datatype, a non-positive size or scale, (t0, t1, t2) not a permutation, flips outside 0..7, lo > hi,
+ * (hi - lo) * scale > 65535; UNETK_E_UNSUPPORTED: n0 * n1 * n2 >= 2^31. */
+int unetk_nii_ingest(const void* src, int datatype, int n0, int n1, int n2, double scl_slope, double scl_inter, int t0, int t1,
+                     int t2, int flips, int lo, int hi, int scale, uint16_t* dst, void* stream);
 
 /* ---------------------------------------------------------------- LiTS training batch  
  * DataLoader/Liver/input_pipeline.py:243-284 `data_processing_train` for a whole batch, gathering from decoded slices
@@ -898,6 +917,18 @@ int unetk_eval3d_accumulate_w(const unetk_lits3d_desc* d, const int32_t* sample_
  * 1 <= C <= 8; depth * src_h * src_w < 2^31 (UNETK_E_UNSUPPORTED). */
 int unetk_eval3d_finish(const float* acc, int C, int depth, int src_h, int src_w, const float* wsum, const int32_t* cnt,
                         const int32_t box[6], uint8_t* pred, int32_t* uncovered, void* stream);
+
+/* The probability of ONE class of a sliding-window case as a saved volume (--pred_type prob; additive to ABI 10): acc, wsum / cnt
+ * and box as unetk_eval3d_finish takes them, 0 <= c < C.  Per voxel p = acc[z,y,x,c] / weight in f32 (IEEE division, cnt
+ * converted to f32), q = rint(255 * p) (ties to even) clamped to 0..255, and q = 0 where the weight is not > 0 or the voxel lies
+ * outside box.  dst uint8 [depth * src_h * src_w] in NIfTI file order, (t0, t1, t2, flips) in unetk_nii_compose's convention;
+ * every element is written exactly once, no workspace, two calls give identical bits.  One thread per file element: the stores
+ * are consecutive bytes for every orientation; with t0 == 2 the reads walk consecutive voxels too (coalesced), for the other
+ * orientations they are a plain per-element gather.  UNETK_E_BADARG: a NULL or misaligned pointer, both or neither weight,
+ * C outside [1, 8], c outside [0, C), a box that is empty or leaves the volume, (t0, t1, t2) not a permutation;
+ * UNETK_E_UNSUPPORTED: depth * src_h * src_w >= 2^31. */
+int unetk_eval3d_prob(const float* acc, int C, int c, int depth, int src_h, int src_w, const float* wsum, const int32_t* cnt,
+                      const int32_t box[6], int t0, int t1, int t2, int flips, uint8_t* dst, void* stream);
 
 /* ---------------------------------------------------------------- LiTS click-guided 2-D batches  
  * Batches for the nets that take concat(images, sp_guide) (UNetInter, SmallUNet, InterUNet, LGNet), cropped from the resident
