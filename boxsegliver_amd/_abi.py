@@ -111,6 +111,7 @@ class InterClick3dDesc(Structure):
 P = c_void_p
 _SIGNATURES = {
     "unetk_lits_pick_voxel": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P]),
+    "unetk_lits_pick_voxel_rows": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P]),
     "unetk_lits_patch3d_ws_bytes": (c_size_t, [POINTER(Lits3dDesc)]),
     "unetk_lits_patch3d": (c_int, [POINTER(Lits3dDesc), P, P, P, P, P, P, c_size_t, P]),
     "unetk_lits_patch3d_rot": (c_int, [POINTER(Lits3dDesc), P, P, P, P, P, P, c_size_t, P]),
@@ -133,6 +134,7 @@ _SIGNATURES = {
     "unetk_inter_click": (c_int, [POINTER(InterClickDesc), P, P, P, P, P, P, P, P, c_size_t, P]),
     "unetk_lits3d_clicks_ws_bytes": (c_size_t, [POINTER(Lits3dClicksDesc)]),
     "unetk_lits3d_clicks": (c_int, [POINTER(Lits3dClicksDesc), P, P, P, P, P, P, P, c_size_t, P]),
+    "unetk_lits3d_clicks_neg": (c_int, [POINTER(Lits3dClicksDesc), P, P, P, P, P, P, P, P, c_size_t, P]),
     "unetk_click_guide3d": (c_int, [POINTER(Lits3dClicksDesc), P, P, P, P, P]),
     "unetk_click_guide3d_rot": (c_int, [POINTER(Lits3dClicksDesc), P, P, P, P, P]),
     "unetk_click_guide3d_warp": (c_int, [POINTER(Lits3dClicksDesc), P, P, c_int, P, P, P, P]),
@@ -244,6 +246,8 @@ _SIGNATURES = {
     "unetk_boundary_weights3d": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "unetk_largest_component_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "unetk_largest_component": (c_int, [P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
+    "unetk_fp_mask3d_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "unetk_fp_mask3d": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
     "unetk_component_mask": (c_int, [P, c_int, c_int, c_int, c_int32, P, P]),
     "unetk_mask_counts_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "unetk_mask_counts": (c_int, [P, P, c_int, c_int, c_int, P, P, c_size_t, P]),

@@ -101,6 +101,65 @@ __global__ __launch_bounds__(EV_BLOCK) void lc_write_kernel(int n, const int* __
   out[i] = label[i] == root ? 1 : 0;
 }
 
+// ---------------------------------------------------------------- false-positive components (unetk_fp_mask3d)
+// The mining rule of hard-negative training: the 6-connected components of pred >= pred_label that hold at
+// least min_size voxels and share no voxel with the labelled object.  `out` serves as the 0/1 mask of the union-find first and
+// is rewritten by fp_write_kernel; cnt[root] = the component's size, with FP_HIT set once a voxel of it lies on the object.
+constexpr int FP_HIT = (int)0x80000000u;                   // a size is < 2^31: the sign bit is free
+
+__global__ __launch_bounds__(EV_BLOCK) void fp_init_kernel(const uint8_t* __restrict__ pred, int n, int D, int pred_label,
+                                                           uint8_t* __restrict__ mask, int* __restrict__ label,
+                                                           int* __restrict__ cnt, int32_t* __restrict__ slice_counts,
+                                                           int32_t* __restrict__ head) {
+  const int i = blockIdx.x * EV_BLOCK + threadIdx.x;
+  if (i < 4) head[i] = 0;
+  if (i < D) slice_counts[i] = 0;                            // D <= n
+  if (i >= n) return;
+  const bool m = (int)pred[i] >= pred_label;
+  mask[i] = m ? 1 : 0;
+  label[i] = m ? i : -1;
+  cnt[i] = 0;
+}
+
+// after the flatten: a predicted voxel on the labelled object marks its root.  The flag only ever goes from clear to set, so the
+// plain read that spares a big component its millions of atomics on one address cannot change the result.
+__global__ __launch_bounds__(EV_BLOCK) void fp_overlap_kernel(const uint8_t* __restrict__ lab, int n, int thr,
+                                                              const int* __restrict__ label, int* __restrict__ cnt) {
+  const int i = blockIdx.x * EV_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const int r = label[i];
+  if (r < 0 || (int)lab[i] < thr) return;
+  if (__hip_atomic_load(cnt + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 0) atomicOr(cnt + r, FP_HIT);
+}
+
+// out, the per-slice counts and head = {components, kept components, kept voxels, 0}: integer atomics, one per wave and slice
+// where the wave lies inside one slice (HW >= 64 mostly), else one per kept voxel
+__global__ __launch_bounds__(EV_BLOCK) void fp_write_kernel(int n, int HW, const int* __restrict__ label,
+                                                            const int* __restrict__ cnt, int min_size, int out_value,
+                                                            uint8_t* __restrict__ out, int32_t* __restrict__ slice_counts,
+                                                            int32_t* __restrict__ head) {
+  const int i = blockIdx.x * EV_BLOCK + threadIdx.x;
+  const int r = i < n ? label[i] : -1;
+  const int c = r >= 0 ? cnt[r] : 0;                         // negative with FP_HIT
+  const bool kept = r >= 0 && c >= min_size;
+  const bool root = r == i && i < n;
+  if (i < n) out[i] = kept ? (uint8_t)out_value : 0;
+  const unsigned long long mk = __ballot(kept), mr = __ballot(root), mkr = __ballot(root && kept);
+  const int lane = threadIdx.x & 63;
+  const int first = i - lane, last = min(first + 63, n - 1);
+  const bool one_slice = first < n && first / HW == last / HW;   // wave-uniform
+  if (one_slice) {
+    if (lane == 0 && mk) atomicAdd(slice_counts + first / HW, __popcll(mk));
+  } else if (kept) {
+    atomicAdd(slice_counts + i / HW, 1);
+  }
+  if (lane == 0) {
+    if (mr) atomicAdd(head + 0, __popcll(mr));
+    if (mkr) atomicAdd(head + 1, __popcll(mkr));
+    if (mk) atomicAdd(head + 2, __popcll(mk));
+  }
+}
+
 // ---------------------------------------------------------------- counts |A|, |B|, |A and B|, |A or B|
 __global__ __launch_bounds__(EV_BLOCK) void counts_partial_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
                                                                   int n, long long* __restrict__ part) {
@@ -929,6 +988,40 @@ extern "C" int unetk_component_mask(const void* ws, int D, int H, int W, int32_t
   const int* cnt = (const int*)((const char*)ws + ev_align((size_t)n * 4));
   UNETK_LAUNCH(lc_write_kernel, dim3(ev_grid1(n)), dim3(EV_BLOCK), 0, st, n, label, cnt, (const unsigned long long*)nullptr, root,
                out, (int32_t*)nullptr);
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
+extern "C" size_t unetk_fp_mask3d_ws_bytes(int D, int H, int W) {
+  if (ev_dims(D, H, W) != UNETK_OK) return 0;
+  return 2 * ev_align((size_t)D * H * W * 4);
+}
+
+extern "C" int unetk_fp_mask3d(const uint8_t* pred, const uint8_t* lab, int D, int H, int W, int pred_label, int lab_scale,
+                               int obj_label, int min_size, int out_value, uint8_t* out, int32_t* slice_counts, int32_t* head,
+                               void* ws, size_t ws_bytes, void* stream) {
+  const int dims = ev_dims(D, H, W);
+  if (dims != UNETK_OK) return dims;
+  UNETK_REQUIRE(pred && lab && out && slice_counts && head && ws && unetk_aligned16(ws));
+  UNETK_REQUIRE(((((uintptr_t)slice_counts) | ((uintptr_t)head)) & 3u) == 0);
+  UNETK_REQUIRE(pred_label >= 1 && lab_scale >= 1 && obj_label >= 1 && (int64_t)lab_scale * obj_label < ((int64_t)1 << 31) &&
+                min_size >= 1 && out_value >= 1 && out_value <= 255);
+  if (ws_bytes < unetk_fp_mask3d_ws_bytes(D, H, W)) return UNETK_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int n = D * H * W;
+  int* label = (int*)ws;
+  int* cnt = (int*)((char*)ws + ev_align((size_t)n * 4));
+  const int g = ev_grid1(n);
+  UNETK_LAUNCH(fp_init_kernel, dim3(g), dim3(EV_BLOCK), 0, st, pred, n, D, pred_label, out, label, cnt, slice_counts, head);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(lc_merge_kernel, dim3(g), dim3(EV_BLOCK), 0, st, (const uint8_t*)out, D, H, W, label);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(lc_flatten_kernel, dim3(g), dim3(EV_BLOCK), 0, st, n, label, cnt);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(fp_overlap_kernel, dim3(g), dim3(EV_BLOCK), 0, st, lab, n, lab_scale * obj_label, (const int*)label, cnt);
+  UNETK_LAUNCH_CHECK();
+  UNETK_LAUNCH(fp_write_kernel, dim3(g), dim3(EV_BLOCK), 0, st, n, H * W, (const int*)label, (const int*)cnt, min_size, out_value,
+               out, slice_counts, head);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }

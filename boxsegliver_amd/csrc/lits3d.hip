@@ -25,10 +25,12 @@ inline int p3d_blocks(const unetk_lits3d_desc* d) { return p3d_blocks_for((int64
 // One block per sample; thread t owns the contiguous pixels [t L, (t + 1) L) of the slice, so a block-wide exclusive
 // prefix of the per-thread counts orders the forced-class pixels row-major.
 __global__ __launch_bounds__(1024) void lits_pick_voxel_kernel(const uint8_t* __restrict__ segs, int n_slices, int src_h, int src_w,
-                                                              int thr, int32_t* __restrict__ tab, int32_t* __restrict__ status) {
+                                                              int thr, int only, int32_t* __restrict__ tab,
+                                                              int32_t* __restrict__ status) {
   __shared__ int wtot[16];
   int32_t* t = tab + (int64_t)blockIdx.x * TW;
   if (t[11] == 0) return;                                    // uniform sample: keeps the (cy, cx) the host drew
+  if (only != 0 && t[11] != only) return;                    // unetk_lits_pick_voxel_rows: another plane's row
   const int64_t s = (int64_t)t[0] + t[2];
   const int k = t[12];
   const bool ok = s >= 0 && s < n_slices && k >= 0;          // block-uniform
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(1024) void lits_pick_voxel_kernel(const uint8_t* __
   if (threadIdx.x == 0 && (!ok || k >= total)) {             // a caller bug: flagged, and a centre that is always valid
     t[3] = 0;
     t[4] = 0;
-    atomicOr(status, 1);
+    atomicOr(status, only > 1 ? 3 : 1);                      // bit 1 (2) beside bit 0: the rank was one of another plane's rows
   }
 }
 
@@ -482,7 +484,18 @@ extern "C" int unetk_lits_pick_voxel(const uint8_t* seg_slices, int n_slices, in
   UNETK_REQUIRE((int64_t)src_h * src_w < ((int64_t)1 << 30) && (int64_t)lab_scale * fg_label < ((int64_t)1 << 31));
   UNETK_REQUIRE(((((uintptr_t)sample_tab) | ((uintptr_t)status)) & 3u) == 0);
   UNETK_LAUNCH(lits_pick_voxel_kernel, dim3(N), dim3(1024), 0, (hipStream_t)stream, seg_slices, n_slices, src_h, src_w,
-               lab_scale * fg_label, sample_tab, status);      // seg / lab_scale >= fg  <=>  seg >= fg * lab_scale
+               lab_scale * fg_label, 0, sample_tab, status);   // seg / lab_scale >= fg  <=>  seg >= fg * lab_scale
+  UNETK_LAUNCH_CHECK();
+  return UNETK_OK;
+}
+
+extern "C" int unetk_lits_pick_voxel_rows(const uint8_t* seg_slices, int n_slices, int src_h, int src_w, int lab_scale, int fg_label,
+                                          int32_t* sample_tab, int N, int32_t* status, int forced_value, void* stream) {
+  UNETK_REQUIRE(seg_slices && sample_tab && status && n_slices > 0 && src_h > 0 && src_w > 0 && N > 0 && lab_scale > 0 && fg_label > 0);
+  UNETK_REQUIRE((int64_t)src_h * src_w < ((int64_t)1 << 30) && (int64_t)lab_scale * fg_label < ((int64_t)1 << 31));
+  UNETK_REQUIRE(((((uintptr_t)sample_tab) | ((uintptr_t)status)) & 3u) == 0 && forced_value > 0);
+  UNETK_LAUNCH(lits_pick_voxel_kernel, dim3(N), dim3(1024), 0, (hipStream_t)stream, seg_slices, n_slices, src_h, src_w,
+               lab_scale * fg_label, forced_value, sample_tab, status);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }

@@ -55,10 +55,14 @@ __global__ __launch_bounds__(64) void clk3_cols_kernel(unetk_lits3d_clicks_desc 
 }
 
 // ------------------------------------------------------------------------------------------------ row pass, classes
+// NEG (unetk_lits3d_clicks_neg): the row of the `neg` plane under the crop adds the class bit CLS_NEG and the
+// row record's slot 6, the row's false-positive voxels; everything else is the plain kernel's.
+template <bool NEG>
 __global__ __launch_bounds__(256) void clk3_rows_kernel(unetk_lits3d_clicks_desc d, const int32_t* __restrict__ tab,
-                                                        uint8_t* __restrict__ ws, int32_t* __restrict__ rowrec) {
+                                                        const uint8_t* __restrict__ negs, uint8_t* __restrict__ ws,
+                                                        int32_t* __restrict__ rowrec) {
   __shared__ int16_t buf[2][3][CLK_MAX_EXTENT];
-  __shared__ int red[4][6];
+  __shared__ int red[4][7];
   const int n = blockIdx.z, z = blockIdx.y, y = blockIdx.x;
   const Box3 b = p3d_box(tab + (int64_t)n * TW, d);
   if (y >= b.ch) return;                                     // block-uniform
@@ -90,12 +94,16 @@ __global__ __launch_bounds__(256) void clk3_rows_kernel(unetk_lits3d_clicks_desc
     __syncthreads();
     cur ^= 1;
   }
-  int nf = 0, nb = 0, no = 0, so = 0, bfirst = cw, blast = -1;
+  int nf = 0, nb = 0, no = 0, so = 0, bfirst = cw, blast = -1, nn = 0;
+  const int64_t nsl = NEG ? p3d_slice(b, z, d) : -1;         // a slice beyond the case holds no false positive
+  const uint8_t* ng = NEG && nsl >= 0 ? negs + (nsl * d.src_h + b.y1 + y) * (int64_t)d.src_w + b.x1 : nullptr;
   for (int x = threadIdx.x; x < cw; x += 256) {
     const bool fg = buf[cur][0][x] > d.margin;
     const bool bg = buf[cur][1][x] > d.margin && !(buf[cur][2][x] > outer);
     const bool ob = gf[x] > 0;
-    cls[x] = (uint8_t)((fg ? CLS_FG : 0) | (bg ? CLS_BG : 0) | (ob ? CLS_OBJ : 0));
+    const bool ng1 = NEG && ng != nullptr && (int)ng[x] >= d.lab_scale;      // the plane's encoding: label 1
+    cls[x] = (uint8_t)((fg ? CLS_FG : 0) | (bg ? CLS_BG : 0) | (ob ? CLS_OBJ : 0) | (ng1 ? CLS_NEG : 0));
+    nn += ng1;
     nf += fg;
     nb += bg;
     no += ob;
@@ -111,9 +119,11 @@ __global__ __launch_bounds__(256) void clk3_rows_kernel(unetk_lits3d_clicks_desc
     so += __shfl_xor(so, o);
     bfirst = min(bfirst, __shfl_xor(bfirst, o));
     blast = max(blast, __shfl_xor(blast, o));
+    if (NEG) nn += __shfl_xor(nn, o);
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) {
+    red[wave][6] = nn;
     red[wave][0] = nf;
     red[wave][1] = nb;
     red[wave][2] = no;
@@ -127,7 +137,8 @@ __global__ __launch_bounds__(256) void clk3_rows_kernel(unetk_lits3d_clicks_desc
   if (t < 4) rec[t] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
   if (t == 4) rec[4] = min(min(red[0][4], red[1][4]), min(red[2][4], red[3][4]));
   if (t == 5) rec[5] = max(max(red[0][5], red[1][5]), max(red[2][5], red[3][5]));
-  if (t == 6 || t == 7) rec[t] = 0;
+  if (t == 6) rec[6] = NEG ? red[0][6] + red[1][6] + red[2][6] + red[3][6] : 0;
+  if (t == 7) rec[7] = 0;
 }
 
 // ------------------------------------------------------------------------------------------------ selection
@@ -173,12 +184,16 @@ __device__ __forceinline__ unsigned int clk3_far_bound(int z, int y, int xa, int
   return ub;
 }
 
+// NEG: a background kind whose crop holds false-positive voxels (row records' slot 6) runs the reference's strategy 4: the
+// candidates are the CLS_NEG voxels, every click is a rank pick, there is no "small" click; any other row runs as without NEG.
+template <bool NEG>
 __global__ __launch_bounds__(1024) void clk3_select_kernel(unetk_lits3d_clicks_desc d, const int32_t* __restrict__ tab,
                                                            const uint32_t* __restrict__ click_tab,
                                                            const uint8_t* __restrict__ ws, const int32_t* __restrict__ rowrec,
                                                            int32_t* __restrict__ pts, int32_t* __restrict__ cnt,
                                                            int32_t* __restrict__ status) {
-  __shared__ int scnt[CLK3_MAX_D];                           // candidates alive per slice
+  __shared__ int sband[CLK3_MAX_D];                          // candidates alive per slice
+  __shared__ int sneg[NEG ? CLK3_MAX_D : 1];                 // NEG: ... of the false positives
   __shared__ unsigned long long red[16][4];
   __shared__ unsigned long long wbest[16];
   __shared__ int wcnt[16];
@@ -194,21 +209,24 @@ __global__ __launch_bounds__(1024) void clk3_select_kernel(unetk_lits3d_clicks_d
   const int total = D * area;                                // < 2^31: checked by the entry point
   const int chunk = ((area + 15) / 16 + 63) / 64 * 64;       // pixels of a wave in one slice: a multiple of 64, row-major across waves
   const int lo = min(wave * chunk, area), hi = min(lo + chunk, area);
-  const int bit = kind == 0 ? CLS_FG : CLS_BG, step2 = d.step * d.step;
+  int bit = kind == 0 ? CLS_FG : CLS_BG;
+  const int step2 = d.step * d.step;
   const float rcw = 1.f / (float)cw;                         // i / cw through unetk_fdiv: i < 2^20 + 512
   const uint32_t* ct = click_tab + (int64_t)n * CTW;
   const ClkDraws dr = clk_draws(ct, kind, d.max_clicks);
-  const int want = dr.want, strategy = dr.strategy;
+  const int want = dr.want;
+  int strategy = dr.strategy;
   if (threadIdx.x == 0 && dr.bad) atomicOr(status, 4);
 
   // pass 0, from the row records: candidates per slice; the mask's voxel count and coordinate sums.  Wave w takes the
   // slices w, w + 16, ...
   unsigned long long nmask = 0, sz = 0, sy = 0, sx = 0;
   for (int z = wave; z < D; z += 16) {
-    int cand = 0;
+    int cand = 0, cneg = 0;
     for (int y = lane; y < ch; y += 64) {
       const int4 r = *reinterpret_cast<const int4*>(rec + ((int64_t)z * d.src_h + y) * CLK3_REC);
       cand += kind == 0 ? r.x : r.y;
+      if (NEG) cneg += rec[((int64_t)z * d.src_h + y) * CLK3_REC + 6];
       const unsigned long long m = (unsigned long long)(kind == 0 ? r.z : cw - r.z);
       nmask += m;
       sz += m * (unsigned long long)z;
@@ -216,8 +234,14 @@ __global__ __launch_bounds__(1024) void clk3_select_kernel(unetk_lits3d_clicks_d
       sx += (unsigned long long)(kind == 0 ? r.w : cw * (cw - 1) / 2 - r.w);
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cand += __shfl_xor(cand, o);
-    if (lane == 0) scnt[z] = cand;
+    for (int o = 32; o > 0; o >>= 1) {
+      cand += __shfl_xor(cand, o);
+      if (NEG) cneg += __shfl_xor(cneg, o);
+    }
+    if (lane == 0) {
+      sband[z] = cand;
+      if (NEG) sneg[z] = cneg;
+    }
   }
   nmask = wave_sum(nmask);
   sz = wave_sum(sz);
@@ -237,6 +261,17 @@ __global__ __launch_bounds__(1024) void clk3_select_kernel(unetk_lits3d_clicks_d
     sy += red[w][2];
     sx += red[w][3];
   }
+  bool useneg = false;                                       // block-uniform
+  if (NEG && kind == 1) {
+    int t = 0;
+    for (int z = 0; z < D; ++z) t += sneg[z];
+    useneg = t > 0;
+  }
+  int* scnt = useneg ? sneg : sband;
+  if (useneg) {
+    bit = CLS_NEG;
+    strategy = 1;
+  }
   int alive = 0;
   for (int z = 0; z < D; ++z) alive += scnt[z];
 
@@ -244,7 +279,7 @@ __global__ __launch_bounds__(1024) void clk3_select_kernel(unetk_lits3d_clicks_d
   c.n = 0;
 #pragma unroll
   for (int k = 0; k < MAXK; ++k) c.z[k] = c.y[k] = c.x[k] = 0;
-  if (nmask == 0 || want == 0) {
+  if ((nmask == 0 && !useneg) || want == 0) {
     // no voxel to click on (deviation: the reference fails on an all-object patch), or no click drawn
   } else if (alive == 0) {                                   // "small": one click at the mask's mean, rounded half to even
     c.z[0] = unetk_round_div_even(sz, nmask);
@@ -587,10 +622,11 @@ extern "C" size_t unetk_lits3d_clicks_ws_bytes(const unetk_lits3d_clicks_desc* d
   return (size_t)d->N * 3 * (size_t)clk3_field(*d) + (size_t)d->N * d->D * d->src_h * CLK3_REC * sizeof(int32_t);
 }
 
-extern "C" int unetk_lits3d_clicks(const unetk_lits3d_clicks_desc* d, const uint8_t* seg_slices, const int32_t* sample_tab,
-                                   const uint32_t* click_tab, int32_t* pts, int32_t* cnt, int32_t* status, void* ws,
-                                   size_t ws_bytes, void* stream) {
-  UNETK_REQUIRE(clk3_valid(d) && seg_slices && sample_tab && click_tab && pts && cnt && status && ws);
+namespace {
+template <bool NEG>
+int clk3_launch(const unetk_lits3d_clicks_desc* d, const uint8_t* seg_slices, const uint8_t* neg_slices, const int32_t* sample_tab,
+                const uint32_t* click_tab, int32_t* pts, int32_t* cnt, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  UNETK_REQUIRE(clk3_valid(d) && seg_slices && (!NEG || neg_slices) && sample_tab && click_tab && pts && cnt && status && ws);
   UNETK_REQUIRE(((((uintptr_t)sample_tab) | ((uintptr_t)click_tab) | ((uintptr_t)pts) | ((uintptr_t)cnt) | ((uintptr_t)status)) & 3u) == 0);
   UNETK_REQUIRE(unetk_aligned16(ws));
   if (!clk3_supported(d)) return UNETK_E_UNSUPPORTED;
@@ -599,11 +635,24 @@ extern "C" int unetk_lits3d_clicks(const unetk_lits3d_clicks_desc* d, const uint
   uint8_t* w = static_cast<uint8_t*>(ws);
   int32_t* rowrec = reinterpret_cast<int32_t*>(w + (size_t)d->N * 3 * (size_t)clk3_field(*d));
   UNETK_LAUNCH(clk3_cols_kernel, dim3((d->src_w + 63) / 64, d->D, d->N), dim3(64), 0, st, *d, seg_slices, sample_tab, w);
-  UNETK_LAUNCH(clk3_rows_kernel, dim3(d->src_h, d->D, d->N), dim3(256), 0, st, *d, sample_tab, w, rowrec);
-  UNETK_LAUNCH(clk3_select_kernel, dim3(2, d->N), dim3(1024), 0, st, *d, sample_tab, click_tab, (const uint8_t*)w,
+  UNETK_LAUNCH(clk3_rows_kernel<NEG>, dim3(d->src_h, d->D, d->N), dim3(256), 0, st, *d, sample_tab, neg_slices, w, rowrec);
+  UNETK_LAUNCH(clk3_select_kernel<NEG>, dim3(2, d->N), dim3(1024), 0, st, *d, sample_tab, click_tab, (const uint8_t*)w,
                (const int32_t*)rowrec, pts, cnt, status);
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
+}
+}  // namespace
+
+extern "C" int unetk_lits3d_clicks(const unetk_lits3d_clicks_desc* d, const uint8_t* seg_slices, const int32_t* sample_tab,
+                                   const uint32_t* click_tab, int32_t* pts, int32_t* cnt, int32_t* status, void* ws,
+                                   size_t ws_bytes, void* stream) {
+  return clk3_launch<false>(d, seg_slices, nullptr, sample_tab, click_tab, pts, cnt, status, ws, ws_bytes, stream);
+}
+
+extern "C" int unetk_lits3d_clicks_neg(const unetk_lits3d_clicks_desc* d, const uint8_t* seg_slices, const uint8_t* neg_slices,
+                                       const int32_t* sample_tab, const uint32_t* click_tab, int32_t* pts, int32_t* cnt,
+                                       int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  return clk3_launch<true>(d, seg_slices, neg_slices, sample_tab, click_tab, pts, cnt, status, ws, ws_bytes, stream);
 }
 
 namespace {

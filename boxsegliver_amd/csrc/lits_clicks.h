@@ -9,7 +9,7 @@ namespace {
 constexpr int MAXK = UNETK_LITS_MAX_CLICKS;
 constexpr int CTW = UNETK_LITS_CLICK_TAB_COLS;
 constexpr int CLK_MAX_EXTENT = 1024;     // rows / columns of a slice the simulators take (their row buffers live in LDS)
-enum { CLS_FG = 1, CLS_BG = 2, CLS_OBJ = 4 };
+enum { CLS_FG = 1, CLS_BG = 2, CLS_OBJ = 4, CLS_NEG = 8 };   // CLS_NEG: lits3d_clicks.hip with a `neg` plane only
 constexpr int CLK_U = 8;                  // pixels a thread loads before it works on them (column sweeps, selection)
 
 // ------------------------------------------------------------------------------------------------ the draws of one kind

@@ -278,8 +278,87 @@ def write_user_prior(lits_root):
     return out
 
 
+NEG_DIR = "neg3d"              # <lits_root>/neg3d/neg-<PID>.npz: what liver_3d --hard_neg_from reads
+NEG_MIN_SIZE = 6               # load_neg drops components of size <= 5 (input_pipeline_3d.py:216)
+
+
+def save_neg(path, mask, slice_counts, kept, components):
+    """One case's false-positive mask as `mine_false_positives` writes it: `bits` = np.packbits of the 0/1 mask in (z, y, x)
+    order, `shape`, `slice_counts` int64 [depth], `kept` and `components`."""
+    mask = np.ascontiguousarray(np.asarray(mask) != 0)
+    np.savez(path, bits=np.packbits(mask.reshape(-1)), shape=np.asarray(mask.shape, dtype=np.int64),
+             slice_counts=np.asarray(slice_counts, dtype=np.int64), kept=np.int64(kept), components=np.int64(components))
+
+
+def load_neg(path):
+    """dict(bits uint8 [ceil(n / 8)], shape (d, h, w), slice_counts int64 [d], kept, components) of a neg-<PID>.npz; a file that
+    does not hold these, or whose parts disagree in size, is an error naming it."""
+    try:
+        with np.load(path) as f:
+            rec = dict(bits=np.ascontiguousarray(f["bits"], dtype=np.uint8), shape=tuple(int(v) for v in f["shape"]),
+                       slice_counts=np.asarray(f["slice_counts"], dtype=np.int64), kept=int(f["kept"]),
+                       components=int(f["components"]))
+    except (KeyError, ValueError, OSError) as e:
+        if isinstance(e, FileNotFoundError):
+            raise
+        raise ValueError("{}: not a neg-<PID>.npz of `extract neg3d`: {}".format(path, e))
+    n = int(np.prod(rec["shape"])) if len(rec["shape"]) == 3 else -1
+    if n < 0 or rec["bits"].shape != ((n + 7) // 8,) or rec["slice_counts"].shape != (rec["shape"][0],):
+        raise ValueError("{}: bits / slice_counts do not fit the shape {}".format(path, rec["shape"]))
+    return rec
+
+
+def unpack_neg(rec):
+    """The 0/1 uint8 mask [d, h, w] of a load_neg record (host)."""
+    n = int(np.prod(rec["shape"]))
+    return np.unpackbits(rec["bits"])[:n].reshape(rec["shape"])
+
+
+def mine_false_positives(pred_dir, lits_root, classes=("Liver", "Tumor"), min_size=NEG_MIN_SIZE, device=None):
+    """DataLoader/NF/input_pipeline_3d.py:187-219 `load_neg` for LiTS, on the device: for every
+    predict-<PID>.nii.gz of pred_dir (what --save_predict writes) whose PID is in <lits_root>/meta.json, the 6-connected
+    components of the predicted object class that hold >= min_size voxels and touch no labelled voxel of that class
+    (ops.fp_mask3d) -> <lits_root>/neg3d/neg-<PID>.npz.  The object class is lits3d.label_map's fg_label: the tumour where it
+    is a class, else the liver.  The prediction is read with the volume's mirror rule (as lits3d.prediction_box reads it), the
+    labels come from the PNG store.  Returns [(pid, path, components, kept, voxels)]."""
+    import torch
+
+    from .. import ops
+    from . import lits, lits3d
+    _, fg_label = lits3d.label_map(classes)
+    if int(min_size) < 1:
+        raise ValueError("--min_size must be >= 1, got {}".format(min_size))
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    root = Path(lits_root)
+    with (root / "meta.json").open() as f:
+        meta = {int(c["PID"]): c for c in json.load(f)}
+    dst = root / NEG_DIR
+    dst.mkdir(parents=True, exist_ok=True)
+    files = []
+    for p in Path(pred_dir).glob("predict-*.nii.gz"):
+        stem = p.name[len("predict-"):-len(".nii.gz")]
+        if stem.isdigit() and int(stem) in meta:
+            files.append((int(stem), p))
+    done = []
+    for pid, path in sorted(files):
+        _, pred = nii_kits.read_nii(path, out_dtype=np.uint8, special=28 <= pid < 48)
+        want = tuple(int(v) for v in lits._maybe_json(meta[pid]["size"]))
+        if tuple(pred.shape) != want:
+            raise ValueError("{} holds a volume of shape {}, case {} has {}".format(path, tuple(pred.shape), pid, want))
+        store = lits.SliceStore(root, [{"PID": pid, "size": list(want)}], device)
+        out, counts, head = ops.fp_mask3d(torch.from_numpy(np.ascontiguousarray(pred)).to(device), store.lb, fg_label, fg_label,
+                                          min_size=min_size, out_value=1, lab_scale=LB_SCALE)
+        components, kept, voxels, _ = head.tolist()
+        target = dst / "neg-{}.npz".format(pid)
+        save_neg(target, out.cpu().numpy(), counts.cpu().numpy(), kept, components)
+        del store, out
+        done.append((pid, target, components, kept, voxels))
+    return done
+
+
 def main(argv=None):
     """python -m boxsegliver_amd.data.extract png <nii_dir> <lits_root>/png
+       python -m boxsegliver_amd.data.extract neg3d <pred_dir> <lits_root> [--classes Liver Tumor] [--min_size 6]
        python -m boxsegliver_amd.data.extract hist <nii_dir> <lits_root>/feat [--mode train eval]
        python -m boxsegliver_amd.data.extract glcm <nii_dir> <lits_root>/feat --meta <lits_root>/meta.json [--mode train eval]
        python -m boxsegliver_amd.data.extract prior <lits_root>"""
@@ -303,9 +382,18 @@ def main(argv=None):
     r = sub.add_parser("prior", help="<lits_root>/meta.json -> <lits_root>/prior.json, the simulated user prior of the "
                                      "propagated evaluation")
     r.add_argument("lits_root")
+    n = sub.add_parser("neg3d", help="saved predictions predict-<PID>.nii.gz -> their false-positive objects "
+                                     "<lits_root>/neg3d/neg-<PID>.npz, for liver_3d --hard_neg_from")
+    n.add_argument("pred_dir")
+    n.add_argument("lits_root")
+    n.add_argument("--classes", nargs="+", default=["Liver", "Tumor"])
+    n.add_argument("--min_size", type=int, default=NEG_MIN_SIZE, help="the smallest component that is kept, in voxels")
     a = parser.parse_args(argv)
     if a.cmd == "png":
         nii_3d_to_png(a.nii_dir, a.out_dir, a.only_meta)
+    elif a.cmd == "neg3d":
+        for pid, path, components, kept, voxels in mine_false_positives(a.pred_dir, a.lits_root, a.classes, a.min_size):
+            print("case {}: {} components, {} kept, {} voxels -> {}".format(pid, components, kept, voxels, path))
     elif a.cmd == "prior":
         print(write_user_prior(a.lits_root))
     elif a.cmd == "glcm":

@@ -50,7 +50,14 @@ the box of a saved coarse prediction to which the windows are restricted (predic
 
 --mode infer (`input_fn_infer`) serves the same windows over NIfTI volumes that are not in the store: per file
 the voxel block goes into pinned memory (VolumeReader: one thread, one case ahead), is uploaded as it lies in the file, and
-`unetk_nii_ingest` writes the store's slices on the device (CaseStore)."""
+`unetk_nii_ingest` writes the store's slices on the device (CaseStore).
+
+With --hard_neg_from DIR (the reference's --sample_neg / --fp_sample of nf_3d, :187-219 load_neg, :559-605
+gen_batch, :486-504 gen_kernel, inter_simulation strategy 4) training uses the false positives of an earlier run, mined by
+`python -m boxsegliver_amd.data.extract neg3d` into DIR/neg-<PID>.npz: they are expanded into a `neg` plane beside store.lb
+(load_neg_plane).  --hard_neg_patches P centres ceil(bs P) rows of every batch on a false-positive voxel
+(PatchSampler.draw_hard_neg -> `unetk_lits_pick_voxel_rows`), --hard_neg_clicks draws the background clicks inside the false
+positives of the crop (`unetk_lits3d_clicks_neg`).  eval_online never sees the plane; the restatement is tests/hard_neg_ref.py."""
 import math
 from pathlib import Path
 
@@ -72,6 +79,8 @@ CLICKS = (3, 10, 40, 5)            # gen_kernel :492-503: margin, step, N; d = 4
 DEFAULT_STDDEV = (1.0, 3.0, 3.0)   # --stddev of nf_3d: (z, y, x)
 STATUS_BITS = ((1, "unetk_lits_pick_voxel: a forced sample's rank was beyond the forced-class count of its slice; the per-slice "
                    "counts do not match the resident store"),
+               (2, "unetk_lits_pick_voxel_rows: that rank was a hard-negative row's, beyond the false-positive count of its slice "
+                   "of the `neg` plane; the per-slice counts of --hard_neg_from do not match the plane"),
                (4, "unetk_lits3d_clicks: a row of click draws was out of range"))
 (COL_BASE, COL_DEPTH, COL_CZ, COL_CY, COL_CX, COL_CH, COL_CW, COL_FLIP_LR, COL_FLIP_UD, COL_FLIP_FB, COL_GAMMA, COL_FORCED,
  COL_K) = range(13)
@@ -81,6 +90,7 @@ DEFORM_MAX_GRID = 16               # the _warp entries' largest lattice: G + 3 <
 DEFORM_FOLD_CAP = 0.4              # largest control displacement as a share of the control spacing (no folding: 7.3.10)
 SLICE_PRIORS = ("off", "boundary", "binary")     # --slice_prior
 BOUNDARY_MAX_Z_SCALE = 16          # --boundary_z_scale: the cap of unetk_boundary_weights3d
+FORCED_LABEL, FORCED_NEG = 1, 2    # COL_FORCED: the centre is picked on store.lb / on the `neg` plane
 
 
 def add_arguments(parser):
@@ -118,6 +128,15 @@ def add_arguments(parser):
                         help="--eval_in_patches: tile only the box of predict-<case>.nii.gz in DIR (a --save_predict output)")
     parser.add_argument("--eval_box_margin", type=int, nargs=3, default=DEFAULT_BOX_MARGIN, metavar=("Z", "Y", "X"),
                         help="voxels the --eval_box_from box is grown by on each side, per axis")
+    parser.add_argument("--hard_neg_from", type=str, default=None, metavar="DIR",
+                        help="--mode train: the neg-<PID>.npz files of `python -m boxsegliver_amd.data.extract neg3d`, the false "
+                             "positives of an earlier run's saved predictions; needs --hard_neg_patches or --hard_neg_clicks")
+    parser.add_argument("--hard_neg_patches", type=float, default=0.0, metavar="P",
+                        help="--hard_neg_from: ceil(batch_size_per_device * P) samples of every training batch are centred on a "
+                             "false-positive voxel (the reference's --sample_neg of nf_3d)")
+    parser.add_argument("--hard_neg_clicks", action="store_true",
+                        help="--hard_neg_from --use_spatial: background clicks of training are drawn from the false positives "
+                             "inside the crop (the reference's --fp_sample of nf_3d)")
     parser.add_argument("--infer_volumes", type=str, nargs="+", default=None, metavar="FILE",
                         help="--mode infer: the NIfTI volumes (.nii / .nii.gz) to segment, instead of the validation fold's")
     parser.add_argument("--infer_dir", type=str, default=None, metavar="DIR",
@@ -126,6 +145,9 @@ def add_arguments(parser):
 
 def check_args(args):
     mode = getattr(args, "mode", "train")
+    hard = hard_negatives(args)                            # first: --hard_neg_clicks comes with --use_spatial, refused below
+    if hard is not None and mode in ("eval", "infer"):
+        raise ValueError("{} serve --mode train, got --mode {}".format(" / ".join(hard["flags"]), mode))
     if mode != "infer" and (getattr(args, "infer_volumes", None) or getattr(args, "infer_dir", None) is not None):
         raise ValueError("--infer_volumes / --infer_dir name the volumes of --mode infer, got --mode {}".format(mode))
     if mode == "infer" and (getattr(args, "slice_prior", "off") or "off") != "off":
@@ -174,6 +196,37 @@ def check_values(args):
     if int(getattr(args, "guide_channel", 2)) not in (1, 2):
         raise ValueError("--guide_channel must be 1 or 2, got {}".format(args.guide_channel))
     boundary_z_scale(args)
+
+
+def hard_negatives(args):
+    """--hard_neg_from / --hard_neg_patches / --hard_neg_clicks -> None without any of them, else dict(directory, patches = P,
+    clicks, flags = the ones given).  ValueError naming the flag: a training flag without --hard_neg_from, --hard_neg_from
+    without one, --hard_neg_clicks without --use_spatial, P outside [0, 1] (or NaN), and more forced rows than the batch has:
+    ceil(bs tumor_percent) + ceil(bs P) > bs."""
+    directory = getattr(args, "hard_neg_from", None)
+    share = float(getattr(args, "hard_neg_patches", 0.0) or 0.0)
+    clicks = bool(getattr(args, "hard_neg_clicks", False))
+    if not 0.0 <= share <= 1.0:                           # also refuses NaN
+        raise ValueError("--hard_neg_patches must satisfy 0 <= P <= 1, got {}".format(share))
+    flags = [name for name, on in (("--hard_neg_from", directory is not None), ("--hard_neg_patches", share > 0.0),
+                                   ("--hard_neg_clicks", clicks)) if on]
+    if not flags:
+        return None
+    if directory is None:
+        raise ValueError("{} needs --hard_neg_from DIR, the neg-<PID>.npz files of `extract neg3d`".format(flags[0]))
+    if len(flags) == 1:
+        raise ValueError("--hard_neg_from {} is read by --hard_neg_patches P > 0 or --hard_neg_clicks, and neither is "
+                         "given".format(directory))
+    if clicks and not getattr(args, "use_spatial", False):
+        raise ValueError("--hard_neg_clicks needs --use_spatial: it draws the background clicks of the guide")
+    if share > 0.0 and getattr(args, "batch_size", None) is not None:
+        bs = distribution_utils.per_device_batch_size(args.batch_size, getattr(args, "num_gpus", 1))
+        force = int(math.ceil(bs * float(getattr(args, "tumor_percent", 0.5))))
+        force_fp = int(math.ceil(bs * share))
+        if force + force_fp > bs:
+            raise ValueError("--hard_neg_patches {}: ceil(bs * tumor_percent) + ceil(bs * P) = {} + {} rows are forced, a batch has "
+                             "{}".format(share, force, force_fp, bs))
+    return dict(directory=directory, patches=share, clicks=clicks, flags=flags)
 
 
 def boundary_z_scale(args):
@@ -270,6 +323,40 @@ def forced_counts(store, fg_label):
     return torch.cat(parts).cpu().numpy().astype(np.int64)
 
 
+def load_neg_plane(store, cases, directory):
+    """The `neg` plane of hard-negative training: uint8 [n_slices, src_h, src_w] beside store.lb and in its
+    encoding -- lits.LB_SCALE on the false-positive voxels of DIR/neg-<PID>.npz, else 0 -- so the kernels read it with label 1.
+    Per case the PACKED bits are uploaded (1/8 byte per voxel) and expanded on the device.  A case without a file, or a file of
+    another shape than the case, is an error naming both: there is no silent zero plane.  Returns (plane, counts int64
+    [n_slices] = the files' per-slice counts), checked ONCE against the plane as forced_counts counts it: one transfer."""
+    from . import extract
+    n, src_h, src_w = store.lb.shape
+    plane = torch.zeros((n, src_h, src_w), dtype=torch.uint8, device=store.device)
+    counts = np.zeros(n, dtype=np.int64)
+    shifts = torch.arange(7, -1, -1, dtype=torch.uint8, device=store.device)         # np.packbits: the first voxel in bit 7
+    for case in cases:
+        pid, depth = int(case["PID"]), int(case["size"][0])
+        path = Path(directory) / "neg-{}.npz".format(pid)
+        if not path.exists():
+            raise FileNotFoundError("--hard_neg_from: training case {} has no false-positive file {}; run `python -m "
+                                    "boxsegliver_amd.data.extract neg3d` over that case's prediction".format(pid, path))
+        rec = extract.load_neg(path)
+        if rec["shape"] != (depth, src_h, src_w):
+            raise ValueError("--hard_neg_from: {} holds a mask of shape {}, case {} has {}".format(path, rec["shape"], pid,
+                                                                                                   (depth, src_h, src_w)))
+        base, vox = int(store.offset[pid]), depth * src_h * src_w
+        bits = torch.from_numpy(rec["bits"]).to(store.device)
+        flat = ((bits[:, None] >> shifts[None, :]) & 1).reshape(-1)[:vox]
+        plane[base:base + depth] = (flat * lits.LB_SCALE).view(depth, src_h, src_w)
+        counts[base:base + depth] = rec["slice_counts"]
+    have = forced_counts(type("Plane", (object,), {"lb": plane})(), 1)
+    if not np.array_equal(have, counts):
+        bad = int(np.flatnonzero(have != counts)[0])
+        raise ValueError("--hard_neg_from {}: the slice_counts of the files do not match their masks (store slice {}: {} counted, "
+                         "{} recorded)".format(directory, bad, int(have[bad]), int(counts[bad])))
+    return plane, counts
+
+
 def crop_shape(target_hw, zoom):
     """gen_batch :589: (float32 target * python floats).astype(int32) -- a float64 product, truncated."""
     return (np.asarray(target_hw, dtype=np.float32).astype(np.float64) * np.asarray(zoom, dtype=np.float64)).astype(np.int32)
@@ -296,7 +383,7 @@ class PatchSampler(object):
 
     def __init__(self, cases, offset, slice_counts, batch_size, shape, src_hw, tumor_percent=0.5, zoom_scale=(1.0, 1.25),
                  random_flip=0, training=True, seed=None, random_rotate=0.0, rotate_prob=1.0, random_deform=0.0, deform_grid=4,
-                 deform_prob=1.0):
+                 deform_prob=1.0, hard_neg_patches=0.0, neg_counts=None):
         self.bs = int(batch_size)
         self.deform = float(random_deform or 0.0) if training else 0.0      # pixels; > 0: draw_deform draws
         self.deform_grid = int(deform_grid)
@@ -324,14 +411,36 @@ class PatchSampler(object):
         if self.bs - self.force > len(cases) - self.force:
             raise ValueError("too few cases: the {} samples beside the forced ones are drawn without replacement from the "
                              "{} other cases".format(self.bs - self.force, len(cases) - self.force))
+        # --hard_neg_patches (training only): rows [force, force + force_fp) are re-targeted by draw_hard_neg
+        self.force_fp = int(math.ceil(self.bs * float(hard_neg_patches or 0.0))) if training else 0
+        if self.force_fp:
+            if neg_counts is None:
+                raise ValueError("--hard_neg_patches needs the per-slice counts of the `neg` plane")
+            if self.force + self.force_fp > self.bs:
+                raise ValueError("--hard_neg_patches: ceil(bs * tumor_percent) + ceil(bs * P) = {} + {} rows are forced, a batch "
+                                 "has {}".format(self.force, self.force_fp, self.bs))
+            if self.force_fp > len(self.fg_cases):
+                raise ValueError("--hard_neg_patches: too few cases with forced-class voxels: {} are drawn without replacement, "
+                                 "{} have any".format(self.force_fp, len(self.fg_cases)))
+            self.neg_cum = np.concatenate(([0], np.cumsum(np.asarray(neg_counts, dtype=np.int64))))
+            if len(self.neg_cum) != len(self.cum):
+                raise ValueError("the `neg` plane has {} slices, the store {}".format(len(self.neg_cum) - 1, len(self.cum) - 1))
+            self.neg_total = self.neg_cum[self.base + self.depth] - self.neg_cum[self.base]
 
     def locate(self, case, rank):
         """Rank `rank` (< case_total) among the forced-class voxels of case index `case` -> (z within the case, k within
         slice z), element-wise, through the cumulative slice counts."""
+        return self._locate(self.cum, case, rank)
+
+    def _locate(self, cum, case, rank):
         case, rank = np.asarray(case, dtype=np.int64), np.asarray(rank, dtype=np.int64)
-        target = self.cum[self.base[case]] + rank
-        s = np.searchsorted(self.cum, target, side="right") - 1                 # the store slice holding that voxel
-        return s - self.base[case], target - self.cum[s]
+        target = cum[self.base[case]] + rank
+        s = np.searchsorted(cum, target, side="right") - 1                      # the store slice holding that voxel
+        return s - self.base[case], target - cum[s]
+
+    def locate_neg(self, case, rank):
+        """`locate` on the `neg` plane: rank (< neg_total) among the false-positive voxels of case index `case` -> (z, k)."""
+        return self._locate(self.neg_cum, case, rank)
 
     def draw(self):
         """One batch: dict(case [bs] index into the case list, pid, forced [bs] bool, center [bs, 3] = (z, y, x) with (y, x)
@@ -358,6 +467,36 @@ class PatchSampler(object):
             gamma = np.ones(bs)
         return dict(case=case, pid=self.pid[case], forced=forced, center=center, k=k, crop=crop, flips=flips,
                     gamma=gamma.astype(np.float32))
+
+    def draw_hard_neg(self, b):
+        """--hard_neg_patches (gen_batch :577-579, :594-600): re-targets rows [force, force + force_fp) of the
+        batch `draw` gave, in place; made right after `draw` and only when force_fp > 0, so a run without the flag consumes its
+        generator as before.  force_fp cases from fg_cases without replacement -- a draw of its own, independent of the forced
+        one (:578).  A case with false positives: a rank below its total -> (z, k) through the cumulative per-slice counts of
+        the plane, forced = FORCED_NEG, and `unetk_lits_pick_voxel_rows` picks (y, x) on the plane.  A case without any: a
+        uniform centre in its own extents, forced = 0.  Both draws are made for every row, whichever applies.  b["forced"]
+        becomes the int column 11 of the table."""
+        fp, rng = self.force_fp, self.rng
+        if not fp:
+            return b
+        rows = np.arange(self.force, self.force + fp)
+        case = rng.choice(self.fg_cases, size=fp, replace=False).astype(np.int64)
+        total = self.neg_total[case]
+        rank = rng.integers(0, np.maximum(total, 1))
+        u = rng.random((fp, 3))
+        uniform = np.floor(u * np.stack([self.depth[case], np.full(fp, self.src_h), np.full(fp, self.src_w)], axis=1)).astype(np.int64)
+        has = total > 0
+        z, k = self.locate_neg(case[has], rank[has])
+        forced = np.asarray(b["forced"]).astype(np.int64)
+        forced[rows] = np.where(has, FORCED_NEG, 0)
+        b["case"][rows], b["pid"][rows] = case, self.pid[case]
+        b["center"][rows] = uniform
+        b["center"][rows[has], 0] = z
+        b["center"][rows[has], 1:] = 0
+        b["k"][rows] = 0
+        b["k"][rows[has]] = k
+        b["forced"] = forced
+        return b
 
     def draw_rotation(self):
         """The rotation draw of one batch, made only when --random_rotate > 0 and AFTER every other draw of
@@ -415,7 +554,7 @@ def check_status(status, what):
                                                       "status word {}".format(word)))
 
 
-def batches(store, sampler, shape, lab_max, fg_label, status=None, guide=None, prior=None):
+def batches(store, sampler, shape, lab_max, fg_label, status=None, guide=None, prior=None, neg_clicks=False):
     """(features, labels) device batches for ever: features["images"] f32 [bs, D, H, W, 1], features["names"] the case ids,
     labels int32 [bs, D, H, W].  Per batch: one sampler draw, one pinned upload, then `unetk_lits_pick_voxel` (forced
     samples' centres, in the device table) and `unetk_lits_patch3d` on the current stream -- no host synchronisation.
@@ -426,13 +565,23 @@ def batches(store, sampler, shape, lab_max, fg_label, status=None, guide=None, p
     stream and features["sp_guide"] is f32 [bs, D, H, W, channels].
     prior: None, or "boundary" / "binary" for --slice_prior (needs guide): `unetk_slice_prior_field` on the clicks just simulated
     and `unetk_slice_prior_render` follow on the same stream, features["images"] is f32 [bs, D, H, W, 2] with channel 0 the
-    one-channel patch bit for bit.  No draw, no upload and no synchronisation is added."""
+    one-channel patch bit for bit.  No draw, no upload and no synchronisation is added.
+    Hard negatives need store.neg, the plane of load_neg_plane: a sampler with force_fp > 0 re-targets rows
+    (draw_hard_neg, right after draw) and the centres are picked per plane by `unetk_lits_pick_voxel_rows`; neg_clicks: the
+    clicks come from `unetk_lits3d_clicks_neg`.  Without either the calls are exactly those of a run without the flags."""
+    hard_rows = getattr(sampler, "force_fp", 0) > 0
+    if (hard_rows or neg_clicks) and getattr(store, "neg", None) is None:
+        raise ValueError("hard negatives need the store's `neg` plane (load_neg_plane)")
+    if neg_clicks and guide is None:
+        raise ValueError("--hard_neg_clicks needs the simulated clicks of a guided run")
     if prior is not None and guide is None:
         raise ValueError("a slice prior needs the simulated clicks of a guided run")
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=store.device)
     while True:
         b = sampler.draw()
+        if hard_rows:
+            b = sampler.draw_hard_neg(b)
         parts = []
         if guide is not None:
             from . import lits_inter
@@ -444,14 +593,19 @@ def batches(store, sampler, shape, lab_max, fg_label, status=None, guide=None, p
         dev = lits.upload_pinned([sampler.table(b, rot, deform)] + parts, store.device)
         tab, ctab = dev[0], dev[1] if guide is not None else None
         warp, grid = (dev[-1].view(torch.float32), sampler.deform_grid) if deform is not None else (None, 0)
-        if sampler.force:
+        if hard_rows:                                        # one call per plane, each serving its own rows
+            if sampler.force:
+                ops.lits_pick_voxel_rows(store.lb, tab, FORCED_LABEL, status, fg_label, lits.LB_SCALE)
+            ops.lits_pick_voxel_rows(store.neg, tab, FORCED_NEG, status, 1, lits.LB_SCALE)
+        elif sampler.force:
             ops.lits_pick_voxels(store.lb, tab, fg_label, status, lits.LB_SCALE)
         rotate = sampler.rotate > 0.0                        # --random_rotate: the _rot entries, which read the table's (sin, cos)
         images, labels = ops.lits_patch3d(store.im, store.lb, tab, shape, sampler.training, lab_max, lits.IM_SCALE, lits.LB_SCALE,
                                           rotate=rotate, warp=warp, grid=grid)
         feats = {"images": images, "names": torch.from_numpy(b["pid"])}
         if guide is not None:
-            pts, cnt = ops.lits3d_clicks(store.lb, tab, ctab, shape, status, fg_label, CLICKS, lits.LB_SCALE)
+            pts, cnt = ops.lits3d_clicks(store.lb, tab, ctab, shape, status, fg_label, CLICKS, lits.LB_SCALE,
+                                         neg_slices=store.neg if neg_clicks else None)
             feats["sp_guide"] = ops.click_guide3d(tab, pts, cnt, shape, store.im.shape[1:], guide["channels"], guide["stddev"],
                                                   rotate=rotate, warp=warp, grid=grid)
             if prior is not None:
@@ -500,7 +654,12 @@ def input_fn(mode, params):
     seed = base_seed + 1000 * int(params.get("rank", 0)) if training else base_seed + 500
     deg, prob = rotation(args)                             # only `train` rotates: the sampler drops it for eval_online
     px, grid, dprob = deformation(args)                    # likewise
+    hard = hard_negatives(args) if training else None      # eval_online never uses the plane (gen_batch: `train and ...`)
+    if hard is not None and getattr(store, "neg", None) is None:
+        store.neg, params[("lits3d_neg_counts",)] = load_neg_plane(store, cases, hard["directory"])
     sampler = PatchSampler(cases, store.offset, params[ckey], bs, shape, store.im.shape[1:],
+                           hard_neg_patches=hard["patches"] if hard is not None else 0.0,
+                           neg_counts=params[("lits3d_neg_counts",)] if hard is not None else None,
                            tumor_percent=getattr(args, "tumor_percent", 0.5), zoom_scale=getattr(args, "zoom_scale", (1., 1.25)),
                            random_flip=getattr(args, "random_flip", 0), training=training, seed=seed, random_rotate=deg,
                            rotate_prob=prob, random_deform=px, deform_grid=grid, deform_prob=dprob)
@@ -510,7 +669,8 @@ def input_fn(mode, params):
     skey = ("lits3d_status", training)
     if skey not in params:
         params[skey] = torch.zeros(1, dtype=torch.int32, device=store.device)
-    gen = batches(store, sampler, shape, lab_max, fg_label, params[skey], guide_config(args), slice_prior(args))
+    gen = batches(store, sampler, shape, lab_max, fg_label, params[skey], guide_config(args), slice_prior(args),
+                  neg_clicks=hard is not None and hard["clicks"])
     if training:
         return gen
     n = int(getattr(args, "eval_num_batches_per_epoch", 100))

@@ -1193,6 +1193,28 @@ def largest_component3d(mask):
     return out
 
 
+def fp_mask3d(pred, lab, pred_label, obj_label, min_size=6, out_value=64, lab_scale=64):
+    """The false-positive objects of a predicted volume (unetk_fp_mask3d; include/unetk.h has the rule): pred, lab uint8
+    [D, H, W] on the device, lab in the store's encoding.  Returns (out uint8 [D, H, W] = out_value on the 6-connected
+    components of pred >= pred_label with >= min_size voxels and no voxel on lab / lab_scale >= obj_label, slice_counts int32
+    [D], head int32 [4] = {components, kept components, kept voxels, 0}), all on the device.  Current stream."""
+    _require_cuda(pred, lab)
+    assert pred.dtype == torch.uint8 and pred.dim() == 3 and pred.is_contiguous()
+    assert lab.dtype == torch.uint8 and lab.shape == pred.shape and lab.is_contiguous()
+    d, h, w = pred.shape
+    lib = _abi.lib()
+    nbytes = int(lib.unetk_fp_mask3d_ws_bytes(d, h, w))
+    if nbytes == 0:
+        raise _abi.UnetkError("fp_mask3d: a volume of {} x {} x {} voxels is not supported".format(d, h, w))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
+    out = torch.empty_like(pred)
+    counts = torch.empty(d, dtype=torch.int32, device=pred.device)
+    head = torch.empty(4, dtype=torch.int32, device=pred.device)
+    check(lib.unetk_fp_mask3d(ptr(pred), ptr(lab), d, h, w, int(pred_label), int(lab_scale), int(obj_label), int(min_size),
+                              int(out_value), ptr(out), ptr(counts), ptr(head), ptr(ws), nbytes, stream_ptr()), "fp_mask3d")
+    return out, counts, head
+
+
 def component_overlaps_table(res, ref, cap_obj=65536, cap_pair=262144, table=None, ws=None):
     """unetk_component_overlaps as the kernel leaves it: the int32 device table [4 + 4 cap_obj + 3 cap_pair] (include/unetk.h)
     of the 6-connected components of two same-shape masks and of the pairs that share voxels.  No host read."""
@@ -1700,6 +1722,21 @@ def lits_pick_voxels(seg_slices, sample_tab, fg_label, status, lab_scale=64):
     return sample_tab
 
 
+def lits_pick_voxel_rows(plane, sample_tab, forced_value, status, fg_label=1, lab_scale=64):
+    """`lits_pick_voxels` for the rows whose column 11 equals forced_value only (unetk_lits_pick_voxel_rows): one table serves
+    rows centred on the label plane (value 1) and rows centred on the `neg` plane (value 2, label 1), one call per plane.  A
+    rank beyond the slice's count sets status bit 0, and bit 1 too when forced_value > 1.  Current stream."""
+    _require_cuda(plane, sample_tab, status)
+    assert plane.dtype == torch.uint8 and plane.dim() == 3 and plane.is_contiguous()
+    assert sample_tab.dtype == torch.int32 and sample_tab.dim() == 2 and sample_tab.shape[1] == _abi.LITS3D_TAB_COLS
+    assert sample_tab.is_contiguous() and status.dtype == torch.int32 and status.numel() >= 1
+    with _timed_hbm("lits_pick_voxel_rows", plane[0], sample_tab.shape[0]):
+        check(_abi.lib().unetk_lits_pick_voxel_rows(ptr(plane), plane.shape[0], plane.shape[1], plane.shape[2], int(lab_scale),
+                                                    int(fg_label), ptr(sample_tab), sample_tab.shape[0], ptr(status),
+                                                    int(forced_value), stream_ptr()), "lits_pick_voxel_rows")
+    return sample_tab
+
+
 def lits3d_desc(slices, n, shape, training, lab_max=2, im_scale=64, lab_scale=64):
     d, h, w = (int(v) for v in shape)
     return _abi.Lits3dDesc(int(n), d, h, w, slices.shape[0], slices.shape[1], slices.shape[2], int(im_scale), int(lab_scale),
@@ -2111,13 +2148,18 @@ def lits3d_clicks_desc(seg_slices, n, shape, obj_label=1, clicks=(3, 10, 40, 5),
                                  euclid_norm=float(euclid_norm))
 
 
-def lits3d_clicks(seg_slices, sample_tab, click_tab, shape, status, obj_label=1, clicks=(3, 10, 40, 5), lab_scale=64):
+def lits3d_clicks(seg_slices, sample_tab, click_tab, shape, status, obj_label=1, clicks=(3, 10, 40, 5), lab_scale=64, neg_slices=None):
     """The simulated 3-D clicks of a batch (unetk_lits3d_clicks; include/unetk.h has the semantics) on the label patches
     `lits_patch3d` cuts for sample_tab int32 [N, 16], shape = (D, H, W); click_tab uint32-valued int32 [N, 12] = the samples'
     draws (data/lits_inter.draw_click_tab).  Returns pts int32 [N, 2, 4, 3] = (kind fg / bg, click, (z, y, x) in the crop; -1
-    padding) and cnt int32 [N, 2].  status collects bit 2 (value 4); it is NOT read here.  Current stream."""
+    padding) and cnt int32 [N, 2].  status collects bit 2 (value 4); it is NOT read here.  Current stream.
+    neg_slices: the `neg` plane of hard-negative training, uint8 of seg_slices' shape -> unetk_lits3d_clicks_neg: the
+    background clicks of a row whose crop holds false positives are rank picks among them."""
     _require_cuda(seg_slices, sample_tab, click_tab, status)
     assert seg_slices.dtype == torch.uint8 and seg_slices.dim() == 3 and seg_slices.is_contiguous()
+    if neg_slices is not None:
+        _require_cuda(neg_slices)
+        assert neg_slices.dtype == torch.uint8 and neg_slices.shape == seg_slices.shape and neg_slices.is_contiguous()
     n = _inter_tab(sample_tab)
     assert click_tab.dtype == torch.int32 and tuple(click_tab.shape) == (n, _abi.LITS_CLICK_TAB_COLS) and click_tab.is_contiguous()
     assert status.dtype == torch.int32 and status.numel() >= 1
@@ -2130,8 +2172,13 @@ def lits3d_clicks(seg_slices, sample_tab, click_tab, shape, status, obj_label=1,
     pts = torch.empty((n, 2, _abi.LITS_MAX_CLICKS, 3), dtype=torch.int32, device=seg_slices.device)
     cnt = torch.empty((n, 2), dtype=torch.int32, device=seg_slices.device)
     with _timed_hbm("lits3d_clicks", ws, 1):
-        check(_abi.lib().unetk_lits3d_clicks(ctypes.byref(desc), ptr(seg_slices), ptr(sample_tab), ptr(click_tab), ptr(pts),
-                                             ptr(cnt), ptr(status), ptr(ws), nbytes, stream_ptr()), "lits3d_clicks")
+        if neg_slices is None:
+            check(_abi.lib().unetk_lits3d_clicks(ctypes.byref(desc), ptr(seg_slices), ptr(sample_tab), ptr(click_tab), ptr(pts),
+                                                 ptr(cnt), ptr(status), ptr(ws), nbytes, stream_ptr()), "lits3d_clicks")
+        else:
+            check(_abi.lib().unetk_lits3d_clicks_neg(ctypes.byref(desc), ptr(seg_slices), ptr(neg_slices), ptr(sample_tab),
+                                                     ptr(click_tab), ptr(pts), ptr(cnt), ptr(status), ptr(ws), nbytes,
+                                                     stream_ptr()), "lits3d_clicks_neg")
     return pts, cnt
 
 

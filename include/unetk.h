@@ -607,6 +607,20 @@ size_t unetk_largest_component_ws_bytes(int D, int H, int W);
 int unetk_largest_component(const uint8_t* mask, int D, int H, int W, uint8_t* out, int32_t* info, void* ws,
                             size_t ws_bytes, void* stream);
 int unetk_component_mask(const void* ws, int D, int H, int W, int32_t root, uint8_t* out, void* stream);
+/* unetk_fp_mask3d (additive to ABI 10): the false-positive objects of a saved prediction, mined for
+ *   hard-negative training -- DataLoader/NF/input_pipeline_3d.py:187-219 load_neg.  pred, lab, out uint8 [D,H,W]; lab in the
+ *   store's encoding.  Predicted object: pred >= pred_label; labelled object: lab / lab_scale >= obj_label.  The components of
+ *   the predicted object are 6-connected (the union-find of unetk_largest_component).  A component is KEPT when it holds at
+ *   least min_size voxels and shares no voxel with the labelled object (the reference drops sizes <= 5: min_size 6; it tests
+ *   the overlap against any non-zero label, its labels being binary).  out = out_value on kept components, 0 elsewhere (every
+ *   voxel is written; out may be pred itself); slice_counts int32 [D] = kept voxels per slice; head int32 [4] = {components,
+ *   kept components, kept voxels, 0}.  Integer arithmetic and integer atomics only, whose order cannot change a result: two
+ *   calls give identical bits.  pred_label, lab_scale, obj_label, min_size >= 1, 1 <= out_value <= 255 (else UNETK_E_BADARG).
+ *   ws (16-byte aligned): int32 label[n], then int32 size[n] at offset (4n + 255) & ~255. */
+size_t unetk_fp_mask3d_ws_bytes(int D, int H, int W);
+int unetk_fp_mask3d(const uint8_t* pred, const uint8_t* lab, int D, int H, int W, int pred_label, int lab_scale, int obj_label,
+                    int min_size, int out_value, uint8_t* out, int32_t* slice_counts, int32_t* head, void* ws, size_t ws_bytes,
+                    void* stream);
 size_t unetk_mask_counts_ws_bytes(int D, int H, int W);
 int unetk_mask_counts(const uint8_t* a, const uint8_t* b, int D, int H, int W, int64_t* counts, void* ws,
                       size_t ws_bytes, void* stream);
@@ -837,6 +851,13 @@ typedef struct unetk_lits3d_desc {
 } unetk_lits3d_desc;
 int unetk_lits_pick_voxel(const uint8_t* seg_slices, int n_slices, int src_h, int src_w, int lab_scale, int fg_label,
                           int32_t* sample_tab, int N, int32_t* status, void* stream);
+/* unetk_lits_pick_voxel_rows (additive to ABI 10): unetk_lits_pick_voxel for the rows whose column 11 EQUALS
+ * forced_value (> 0) only, every other row is left alone -- so one table can hold rows centred on the label plane (value 1)
+ * and rows centred on a second plane of the same extents and encoding (value 2: the `neg` plane of hard-negative training),
+ * one call per plane.  A rank outside its slice's count writes (0, 0) and sets status[0] |= 1, and |= 2 as well when
+ * forced_value > 1.  No other kernel reads column 11. */
+int unetk_lits_pick_voxel_rows(const uint8_t* seg_slices, int n_slices, int src_h, int src_w, int lab_scale, int fg_label,
+                               int32_t* sample_tab, int N, int32_t* status, int forced_value, void* stream);
 size_t unetk_lits_patch3d_ws_bytes(const unetk_lits3d_desc* d);
 int unetk_lits_patch3d(const unetk_lits3d_desc* d, const uint16_t* slices, const uint8_t* seg_slices,
                        const int32_t* sample_tab, float* images, int32_t* labels, void* ws, size_t ws_bytes, void* stream);
@@ -1151,6 +1172,20 @@ size_t unetk_lits3d_clicks_ws_bytes(const unetk_lits3d_clicks_desc* d);
 int unetk_lits3d_clicks(const unetk_lits3d_clicks_desc* d, const uint8_t* seg_slices, const int32_t* sample_tab,
                         const uint32_t* click_tab, int32_t* pts, int32_t* cnt, int32_t* status, void* ws, size_t ws_bytes,
                         void* stream);
+/* unetk_lits3d_clicks_neg (additive to ABI 10): unetk_lits3d_clicks with background clicks on false positives
+ *   -- inter_simulation(strategy=4, neg_patch) as gen_kernel calls it under cfg.fp_sample.  neg_slices uint8
+ *   [n_slices][src_h][src_w], a plane beside seg_slices in its encoding: a voxel is a false positive where neg / lab_scale >= 1;
+ *   crop slices at or beyond the case's depth hold none.
+ *   A row whose crop box holds no false positive is bit for bit a row of unetk_lits3d_clicks.  In a row whose crop holds one,
+ *   the BACKGROUND kind's candidates are the crop's false-positive voxels -- no erosion, no band, whatever the label says there;
+ *   n_bg clicks, EVERY one a rank pick i = (draw * count) >> 32 in (z, y, x) order over the candidates left; after a click only
+ *   its own slice loses the candidates with dy^2 + dx^2 <= step^2; the kind stops when none is left.  No "small" click, and the
+ *   row's strategy column is not used (an out-of-range value still sets bit 2).  The foreground kind is unchanged.  Limits,
+ *   status bits, workspace (the query is unetk_lits3d_clicks_ws_bytes; the class bytes carry bit 3 and the row records' slot 6
+ *   the row's false positives) and determinism as unetk_lits3d_clicks. */
+int unetk_lits3d_clicks_neg(const unetk_lits3d_clicks_desc* d, const uint8_t* seg_slices, const uint8_t* neg_slices,
+                            const int32_t* sample_tab, const uint32_t* click_tab, int32_t* pts, int32_t* cnt, int32_t* status,
+                            void* ws, size_t ws_bytes, void* stream);
 int unetk_click_guide3d(const unetk_lits3d_clicks_desc* d, const int32_t* sample_tab, const int32_t* pts, const int32_t* cnt,
                         float* guide, void* stream);
 
