@@ -118,6 +118,10 @@ _SIGNATURES = {
     "unetk_lits_patch3d_warp": (c_int, [POINTER(Lits3dDesc), P, P, P, P, c_int, P, P, P, c_size_t, P]),
     "unetk_eval3d_accumulate": (c_int, [POINTER(Lits3dDesc), P, P, c_int, c_int64, c_int, POINTER(c_int32), P, P, P]),
     "unetk_eval3d_accumulate_w": (c_int, [POINTER(Lits3dDesc), P, P, c_int, c_int64, c_int, POINTER(c_int32), P, P, P, P, P, P]),
+    "unetk_lits_patch3d_z": (c_int, [POINTER(Lits3dDesc), P, P, P, P, c_int, P, P, P, c_size_t, P]),
+    "unetk_eval3d_accumulate_z": (c_int, [POINTER(Lits3dDesc), P, P, c_int, P, c_int, c_int64, c_int, POINTER(c_int32), P, P, P]),
+    "unetk_eval3d_accumulate_wz": (c_int, [POINTER(Lits3dDesc), P, P, c_int, P, c_int, c_int64, c_int, POINTER(c_int32), P, P, P, P,
+                                           P, P]),
     "unetk_eval3d_finish": (c_int, [P, c_int, c_int, c_int, c_int, P, P, POINTER(c_int32), P, P, P]),
     "unetk_lits_inter_batch_ws_bytes": (c_size_t, [POINTER(LitsInterDesc)]),
     "unetk_lits_inter_batch": (c_int, [POINTER(LitsInterDesc), P, P, P, P, P, P, P, c_size_t, P]),

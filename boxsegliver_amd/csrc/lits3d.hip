@@ -275,9 +275,122 @@ __global__ __launch_bounds__(256) void p3d_warp_kernel(unetk_lits3d_desc d, cons
   }
 }
 
+// ZSPACE (unetk_lits_patch3d_z): ONLY the rows whose crop depth cd differs from D, each launched after the
+// kernel of the same pass has served every row as unetk_lits_patch3d serves it -- the rows with cd == D keep the bits of those
+// compiled kernels by construction, as the rows p3d_warp_kernel leaves alone.  A resampled row's mask partials and then its
+// voxels and patch partials are written again, same grid and block partition.  The mask pass walks cd slices in place of D.
+__global__ __launch_bounds__(256) void p3d_mask_stats_z_kernel(unetk_lits3d_desc d, const uint16_t* __restrict__ slices,
+                                                               const int32_t* __restrict__ tab, const int32_t* __restrict__ zcrop,
+                                                               int zcrop_max, double* __restrict__ part) {
+  const int n = blockIdx.y, P = gridDim.x;
+  const int cd = p3d_zcrop(zcrop, n, zcrop_max);
+  if (cd == d.D) return;                                     // block-uniform: p3d_mask_stats_kernel has served this row
+  const Box3 b = p3d_box_z(tab + (int64_t)n * TW, d, cd);
+  const int64_t plane = (int64_t)d.src_h * d.src_w;
+  const int area = b.ch * b.cw;
+  const int total = cd * area;                               // < 2^31: zcrop_max * src_h * src_w, checked by the entry point
+  const float scale = (float)d.im_scale;
+  double cnt = 0., sum = 0., sq = 0.;
+  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < total; i += P * 256) {
+    const int z = (int)(i / area), r = (int)(i - (int64_t)z * area);
+    const int y = r / b.cw, x = r - y * b.cw;
+    const int64_t s = p3d_slice(b, z, d);
+    if (s < 0) continue;
+    const float v = (float)slices[s * plane + (int64_t)(b.y1 + y) * d.src_w + b.x1 + x] / scale;
+    if (v > 0.f) {
+      cnt += 1.;
+      sum += (double)v;
+      sq += (double)v * (double)v;
+    }
+  }
+  block_sum3(cnt, sum, sq, part + ((int64_t)n * P + blockIdx.x) * 3);
+}
+
+// The patch pass of a resampled row: the 3-D crop-and-resize.  Output slice z samples crop slices i0, i1 = the align_corners taps
+// of in_z = z (cd - 1) / (D - 1); each slice's in-plane value is p3d_patch_kernel's (corners z-scored on the fly, lits_bilerp),
+// a slice outside the case 0, then the lerp along z; the label is the nearest crop slice's nearest pixel.  8 taps per voxel, both
+// slices' taps in one thread, x-fastest threads: each slice is read in the row segments the plain kernel reads.  The second
+// slice is not read where fz == 0 (v0 + 0 (v1 - v0) = v0).
+__device__ __forceinline__ float p3d_plane_value(const uint16_t* __restrict__ p, int src_w, const LitsTaps& ty, const LitsTaps& tx,
+                                                 float scale, float m, float den) {
+  float c[4] = {(float)p[(int64_t)ty.i0 * src_w + tx.i0], (float)p[(int64_t)ty.i0 * src_w + tx.i1],
+                (float)p[(int64_t)ty.i1 * src_w + tx.i0], (float)p[(int64_t)ty.i1 * src_w + tx.i1]};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float cv = c[j] / scale;
+    c[j] = cv > 0.f ? (cv - m) / den : 0.f;
+  }
+  return lits_bilerp(c[0], c[1], c[2], c[3], tx.f, ty.f);
+}
+__global__ __launch_bounds__(256) void p3d_patch_z_kernel(unetk_lits3d_desc d, const uint16_t* __restrict__ slices,
+                                                          const uint8_t* __restrict__ segs, const int32_t* __restrict__ tab,
+                                                          const int32_t* __restrict__ zcrop, int zcrop_max,
+                                                          const float* __restrict__ stat, float* __restrict__ images,
+                                                          int32_t* __restrict__ labels, double* __restrict__ part,
+                                                          float* __restrict__ minmax) {
+  const int n = blockIdx.y, P = gridDim.x;
+  const int cd = p3d_zcrop(zcrop, n, zcrop_max);
+  if (cd == d.D) return;                                     // block-uniform: p3d_patch_kernel has written this row
+  const int32_t* t = tab + (int64_t)n * TW;
+  const Box3 b = p3d_box_z(t, d, cd);
+  const bool flr = t[7] != 0, fud = t[8] != 0, ffb = t[9] != 0;
+  const float m = stat[(int64_t)n * ST_N + ST_M], den = stat[(int64_t)n * ST_N + ST_S] + 1e-8f;
+  const float scale = (float)d.im_scale;
+  const float zs = lits_ac_scale(cd, d.D), hs = lits_ac_scale(b.ch, d.H), ws = lits_ac_scale(b.cw, d.W);
+  const int64_t plane = (int64_t)d.src_h * d.src_w;
+  const int64_t corner = (int64_t)b.y1 * d.src_w + b.x1;
+  const int area = d.H * d.W;
+  const int total = d.D * area;                              // < 2^31: checked by the entry point
+  float* img = images + (int64_t)n * total;
+  int32_t* lab = labels + (int64_t)n * total;
+  double cnt = 0., sum = 0., sq = 0.;
+  float lo = INFINITY, hi = -INFINITY;
+  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < total; i += P * 256) {
+    const int z = (int)(i / area), r = (int)(i - (int64_t)z * area);
+    const int y = r / d.W, x = r - y * d.W;
+    const float in_y = y * hs, in_x = x * ws;
+    float in_z;
+    {                                                        // the product rounded on its own, never fused into the fraction or the
+#pragma clang fp contract(off)                               // label's rounding: slice ratios put many coordinates near a tie
+      in_z = (float)z * zs;
+    }
+    const LitsTaps tz = lits_ac_taps(in_z, cd), ty = lits_ac_taps(in_y, b.ch), tx = lits_ac_taps(in_x, b.cw);
+    const int64_t s0 = p3d_slice(b, tz.i0, d);
+    float v = s0 >= 0 ? p3d_plane_value(slices + s0 * plane + corner, d.src_w, ty, tx, scale, m, den) : 0.f;
+    if (tz.f != 0.f) {
+      const int64_t s1 = p3d_slice(b, tz.i1, d);
+      const float v1 = s1 >= 0 ? p3d_plane_value(slices + s1 * plane + corner, d.src_w, ty, tx, scale, m, den) : 0.f;
+      v = v + tz.f * (v1 - v);
+    }
+    int l = 0;
+    const int64_t sl = p3d_slice(b, lits_ac_nearest(in_z, cd), d);
+    if (sl >= 0) {
+      const int ny = lits_ac_nearest(in_y, b.ch), nx = lits_ac_nearest(in_x, b.cw);
+      l = min((int)segs[sl * plane + (int64_t)(b.y1 + ny) * d.src_w + b.x1 + nx] / d.lab_scale, d.lab_max);
+    }
+    const int zo = ffb ? d.D - 1 - z : z, yo = fud ? d.H - 1 - y : y, xo = flr ? d.W - 1 - x : x;
+    const int o = (zo * d.H + yo) * d.W + xo;
+    img[o] = v;
+    lab[o] = l;
+    cnt += 1.;
+    sum += (double)v;
+    sq += (double)v * (double)v;
+    lo = fminf(lo, v);
+    hi = fmaxf(hi, v);
+  }
+  if (d.training) {
+    block_sum3(cnt, sum, sq, part + ((int64_t)n * P + blockIdx.x) * 3);
+    block_minmax(lo, hi, minmax + ((int64_t)n * P + blockIdx.x) * 2);
+  }
+}
+
 // passes 3, 4 (gamma, retain_stats): lits_patch.h
 bool p3d_supported(const unetk_lits3d_desc* d) {
   return (int64_t)d->D * d->H * d->W < ((int64_t)1 << 31) && (int64_t)d->D * d->src_h * d->src_w < ((int64_t)1 << 31);
+}
+// the _z entries: the deepest crop must index like a D-deep one, and its slice coordinates must be exact in float32
+bool p3d_z_supported(const unetk_lits3d_desc* d, int zcrop_max) {
+  return (int64_t)zcrop_max * d->src_h * d->src_w < ((int64_t)1 << 31) && zcrop_max < (1 << 24);
 }
 bool p3d_valid(const unetk_lits3d_desc* d) {
   return d && d->N > 0 && d->N <= 65535 && d->D > 0 && d->H > 0 && d->W > 0 && d->n_slices > 0 && d->src_h > 0 && d->src_w > 0 &&
@@ -374,6 +487,90 @@ __global__ __launch_bounds__(256) void eval3d_accumulate_kernel(unetk_lits3d_des
     cnt[vox] += hits;
 }
 
+// ZSPACE (unetk_eval3d_accumulate_z / _wz): the way back of p3d_patch_z_kernel, a kernel of its own so that the
+// instantiations above stay the compiled code they are.  A row's window holds case slices [z1, z1 + cd) (p3d_box_z); case slice
+// zw of it lies at window coordinate zw (D - 1) / (cd - 1), and the hit is the lerp along z of the in-plane bilerps of window
+// slices i0 and i1, each read through the row's flips.  Contraction is off for the whole kernel and every fused multiply-add is
+// spelled out, in the forms of the WEIGHTED branch above -- which are the forms the compiler gives the unweighted one -- so a
+// row with cd == D (in_z == zw, fz == 0, hit == the first bilerp) adds the bits either instantiation above adds.  The second
+// window slice is not read where fz == 0.
+template <int C, bool WEIGHTED>
+__global__ __launch_bounds__(256) void eval3d_accumulate_z_kernel(unetk_lits3d_desc d, const int32_t* __restrict__ tab,
+                                                                  const int32_t* __restrict__ zcrop, int zcrop_max,
+                                                                  const float* __restrict__ probs, int64_t case_base,
+                                                                  int case_depth, EvalBox e, float* __restrict__ acc,
+                                                                  int32_t* __restrict__ cnt, float* __restrict__ wsum,
+                                                                  const float* __restrict__ gz, const float* __restrict__ gy,
+                                                                  const float* __restrict__ gx) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t area = (int64_t)e.bh * e.bw;
+  if (i >= area * e.bd) return;
+  const int zb = (int)(i / area), r = (int)(i - zb * area);
+  const int yb = r / e.bw;
+  const int z = e.z0 + zb, y = e.y0 + yb, x = e.x0 + (r - yb * e.bw);
+  const int64_t vox = ((int64_t)z * d.src_h + y) * d.src_w + x;
+  float* a = acc + vox * C;
+  float sum[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) sum[c] = a[c];
+  int hits = 0;
+  float wtot = 0.f;
+  if constexpr (WEIGHTED) wtot = wsum[vox];
+  const int win = d.D * d.H * d.W * C;                       // < 2^31: checked by the entry point
+  for (int n = 0; n < d.N; ++n) {
+    const int32_t* t = tab + (int64_t)n * TW;
+    const int cd = p3d_zcrop(zcrop, n, zcrop_max);           // wave-uniform, as the table row
+    const Box3 b = p3d_box_z(t, d, cd);
+    if (b.base != case_base || b.depth != case_depth) continue;          // not this case's row: rejected on the host
+    const int zw = z - b.z1, yw = y - b.y1, xw = x - b.x1;
+    if (zw < 0 || zw >= cd || yw < 0 || yw >= b.ch || xw < 0 || xw >= b.cw) continue;
+    if (p3d_slice(b, zw, d) < 0) continue;                               // the window's zero slices below a shallow case
+    // the inverse resize: D x H x W -> cd x ch x cw, taps in the un-flipped window; the flips are the read address
+    const float sz = lits_ac_scale(d.D, cd), sy = lits_ac_scale(d.H, b.ch), sx = lits_ac_scale(d.W, b.cw);
+    const LitsTaps tz = lits_ac_taps((float)zw * sz, d.D), ty = lits_ac_taps((float)yw * sy, d.H), tx = lits_ac_taps((float)xw * sx, d.W);
+    const bool flr = t[7] != 0, fud = t[8] != 0, ffb = t[9] != 0;
+    const int z0 = min(tz.i0, d.D - 1), y0 = min(ty.i0, d.H - 1), x0 = min(tx.i0, d.W - 1);
+    const float fz = (float)zw * sz - (float)tz.i0;
+    const float fy = __builtin_fmaf((float)yw, sy, -(float)ty.i0), fx = (float)xw * sx - (float)tx.i0;
+    const int za = ffb ? d.D - 1 - z0 : z0, zc = ffb ? d.D - 1 - tz.i1 : tz.i1;
+    const int ya = fud ? d.H - 1 - y0 : y0, yb2 = fud ? d.H - 1 - ty.i1 : ty.i1;
+    const int xa = flr ? d.W - 1 - x0 : x0, xb = flr ? d.W - 1 - tx.i1 : tx.i1;
+    const float* p = probs + (int64_t)n * win;
+    const int ra = (za * d.H + ya) * d.W, rb = (za * d.H + yb2) * d.W;
+    const float *tl = p + (ra + xa) * C, *tr = p + (ra + xb) * C, *bl = p + (rb + xa) * C, *br = p + (rb + xb) * C;
+    float hit[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) hit[c] = eval3d_bilerp_fma(tl[c], tr[c], bl[c], br[c], fx, fy);
+    if (fz != 0.f) {
+      const int step = (zc - za) * d.H * d.W * C;                        // to the same taps of window slice i1
+#pragma unroll
+      for (int c = 0; c < C; ++c)
+        hit[c] = __builtin_fmaf(eval3d_bilerp_fma(tl[step + c], tr[step + c], bl[step + c], br[step + c], fx, fy) - hit[c], fz, hit[c]);
+    }
+    if constexpr (WEIGHTED) {
+      // the weight: lits_bilerp's lerp form a + f (b - a) on every axis, the tap itself at fraction 0
+      const float wz = gz[z0] + (gz[tz.i1] - gz[z0]) * fz;
+      const float wy = gy[y0] + (gy[ty.i1] - gy[y0]) * fy, wx = gx[x0] + (gx[tx.i1] - gx[x0]) * fx;
+      const float w = wz * wy * wx;
+#pragma unroll
+      for (int c = 0; c < C; ++c) sum[c] = __builtin_fmaf(w, hit[c], sum[c]);
+      wtot += w;
+    } else {
+#pragma unroll
+      for (int c = 0; c < C; ++c) sum[c] = sum[c] + hit[c];
+    }
+    ++hits;
+  }
+  if (hits == 0) return;
+#pragma unroll
+  for (int c = 0; c < C; ++c) a[c] = sum[c];
+  if constexpr (WEIGHTED)
+    wsum[vox] = wtot;
+  else
+    cnt[vox] += hits;
+}
+
 // The end of a case (unetk_eval3d_finish): one thread per voxel of the volume.  A voxel is covered when its weight (wsum or
 // cnt) is positive; a covered voxel of the box `e` gets the argmax of its C sums, strict > so that the lowest index wins ties
 // (as head_predict_kernel, csrc/head.hip), every other voxel class 0.  Voxels of `e` without cover are counted: one integer
@@ -413,10 +610,13 @@ __global__ __launch_bounds__(256) void eval3d_finish_kernel(const float* __restr
 }  // namespace
 
 // Both accumulate entry points: cnt for the plain one, wsum and the three tables for the weighted one.
+// zspace: the _z / _wz entries, which take the rows' crop depths (zcrop, zcrop_max) and launch eval3d_accumulate_z_kernel.
 static int eval3d_accumulate(const unetk_lits3d_desc* d, const int32_t* sample_tab, const float* probs, int C, int64_t case_base,
                              int case_depth, const int32_t box[6], float* acc, int32_t* cnt, float* wsum, const float* gz,
-                             const float* gy, const float* gx, void* stream) {
+                             const float* gy, const float* gx, void* stream, bool zspace = false, const int32_t* zcrop = nullptr,
+                             int zcrop_max = 0) {
   const bool weighted = cnt == nullptr;
+  UNETK_REQUIRE(!zspace || (zcrop && (((uintptr_t)zcrop) & 3u) == 0 && zcrop_max >= 1));
   UNETK_REQUIRE(p3d_valid(d) && sample_tab && probs && box && acc && C >= 1 && C <= 8);
   UNETK_REQUIRE(((((uintptr_t)sample_tab) | ((uintptr_t)probs) | ((uintptr_t)acc) | ((uintptr_t)cnt)) & 3u) == 0);
   UNETK_REQUIRE(!weighted || (wsum && gz && gy && gx &&
@@ -425,11 +625,21 @@ static int eval3d_accumulate(const unetk_lits3d_desc* d, const int32_t* sample_t
   UNETK_REQUIRE(0 <= box[0] && box[0] < box[1] && box[1] <= case_depth && 0 <= box[2] && box[2] < box[3] && box[3] <= d->src_h &&
                 0 <= box[4] && box[4] < box[5] && box[5] <= d->src_w);
   if (!p3d_supported(d) || (int64_t)d->D * d->H * d->W * C >= ((int64_t)1 << 31)) return UNETK_E_UNSUPPORTED;
+  if (zspace && !p3d_z_supported(d, zcrop_max)) return UNETK_E_UNSUPPORTED;
   const EvalBox e = {box[0], box[2], box[4], box[1] - box[0], box[3] - box[2], box[5] - box[4]};
   const int64_t blocks = ((int64_t)e.bd * e.bh * e.bw + 255) / 256;
   if (blocks >= ((int64_t)1 << 31)) return UNETK_E_UNSUPPORTED;
   const dim3 grid((unsigned)blocks);
   hipStream_t st = (hipStream_t)stream;
+#define EVAL3D_CASE_Z(c)                                                                                                    \
+  case c:                                                                                                                   \
+    if (weighted)                                                                                                           \
+      UNETK_LAUNCH((eval3d_accumulate_z_kernel<c, true>), grid, dim3(256), 0, st, *d, sample_tab, zcrop, zcrop_max, probs,   \
+                   case_base, case_depth, e, acc, cnt, wsum, gz, gy, gx);                                                    \
+    else                                                                                                                    \
+      UNETK_LAUNCH((eval3d_accumulate_z_kernel<c, false>), grid, dim3(256), 0, st, *d, sample_tab, zcrop, zcrop_max, probs,  \
+                   case_base, case_depth, e, acc, cnt, wsum, gz, gy, gx);                                                    \
+    break;
 #define EVAL3D_CASE(c)                                                                                                      \
   case c:                                                                                                                   \
     if (weighted)                                                                                                           \
@@ -439,10 +649,17 @@ static int eval3d_accumulate(const unetk_lits3d_desc* d, const int32_t* sample_t
       UNETK_LAUNCH((eval3d_accumulate_kernel<c, false>), grid, dim3(256), 0, st, *d, sample_tab, probs, case_base, case_depth, e, \
                    acc, cnt, wsum, gz, gy, gx);                                                                             \
     break;
-  switch (C) {
-    EVAL3D_CASE(1) EVAL3D_CASE(2) EVAL3D_CASE(3) EVAL3D_CASE(4) EVAL3D_CASE(5) EVAL3D_CASE(6) EVAL3D_CASE(7) EVAL3D_CASE(8)
+  if (zspace) {
+    switch (C) {
+      EVAL3D_CASE_Z(1) EVAL3D_CASE_Z(2) EVAL3D_CASE_Z(3) EVAL3D_CASE_Z(4) EVAL3D_CASE_Z(5) EVAL3D_CASE_Z(6) EVAL3D_CASE_Z(7) EVAL3D_CASE_Z(8)
+    }
+  } else {
+    switch (C) {
+      EVAL3D_CASE(1) EVAL3D_CASE(2) EVAL3D_CASE(3) EVAL3D_CASE(4) EVAL3D_CASE(5) EVAL3D_CASE(6) EVAL3D_CASE(7) EVAL3D_CASE(8)
+    }
   }
 #undef EVAL3D_CASE
+#undef EVAL3D_CASE_Z
   UNETK_LAUNCH_CHECK();
   return UNETK_OK;
 }
@@ -460,6 +677,23 @@ extern "C" int unetk_eval3d_accumulate_w(const unetk_lits3d_desc* d, const int32
                                          const float* gy, const float* gx, float* acc, float* wsum, void* stream) {
   UNETK_REQUIRE(wsum && gz && gy && gx);
   return eval3d_accumulate(d, sample_tab, probs, C, case_base, case_depth, box, acc, nullptr, wsum, gz, gy, gx, stream);
+}
+
+extern "C" int unetk_eval3d_accumulate_z(const unetk_lits3d_desc* d, const int32_t* sample_tab, const int32_t* zcrop, int zcrop_max,
+                                         const float* probs, int C, int64_t case_base, int case_depth, const int32_t box[6],
+                                         float* acc, int32_t* cnt, void* stream) {
+  UNETK_REQUIRE(cnt);
+  return eval3d_accumulate(d, sample_tab, probs, C, case_base, case_depth, box, acc, cnt, nullptr, nullptr, nullptr, nullptr,
+                           stream, true, zcrop, zcrop_max);
+}
+
+extern "C" int unetk_eval3d_accumulate_wz(const unetk_lits3d_desc* d, const int32_t* sample_tab, const int32_t* zcrop,
+                                          int zcrop_max, const float* probs, int C, int64_t case_base, int case_depth,
+                                          const int32_t box[6], const float* gz, const float* gy, const float* gx, float* acc,
+                                          float* wsum, void* stream) {
+  UNETK_REQUIRE(wsum && gz && gy && gx);
+  return eval3d_accumulate(d, sample_tab, probs, C, case_base, case_depth, box, acc, nullptr, wsum, gz, gy, gx, stream, true,
+                           zcrop, zcrop_max);
 }
 
 extern "C" int unetk_eval3d_finish(const float* acc, int C, int depth, int src_h, int src_w, const float* wsum,
@@ -506,15 +740,19 @@ extern "C" size_t unetk_lits_patch3d_ws_bytes(const unetk_lits3d_desc* d) {
 }
 
 // The patch entry points: the same passes, the patch pass reading the table's rotation columns or not; with a lattice
-// (unetk_lits_patch3d_warp: ROT, warp != nullptr) the deformed rows are then written again by p3d_warp_kernel.
+// (unetk_lits_patch3d_warp: ROT, warp != nullptr) the deformed rows are then written again by p3d_warp_kernel.  zspace
+// (unetk_lits_patch3d_z): the rows whose crop depth is not D get their mask partials and then their voxels written again, by
+// p3d_mask_stats_z_kernel and p3d_patch_z_kernel.
 template <bool ROT>
 static int lits_patch3d(const unetk_lits3d_desc* d, const uint16_t* slices, const uint8_t* seg_slices,
                         const int32_t* sample_tab, float* images, int32_t* labels, void* ws, size_t ws_bytes, void* stream,
-                        const float* warp = nullptr, int G = 0) {
+                        const float* warp = nullptr, int G = 0, bool zspace = false, const int32_t* zcrop = nullptr,
+                        int zcrop_max = 0) {
   UNETK_REQUIRE(p3d_valid(d) && slices && seg_slices && sample_tab && images && labels && ws);
+  UNETK_REQUIRE(!zspace || (zcrop && (((uintptr_t)zcrop) & 3u) == 0 && zcrop_max >= 1));
   UNETK_REQUIRE((((uintptr_t)slices) & 1u) == 0 && ((((uintptr_t)sample_tab) | ((uintptr_t)images) | ((uintptr_t)labels)) & 3u) == 0);
   UNETK_REQUIRE(unetk_aligned16(ws));
-  if (!p3d_supported(d)) return UNETK_E_UNSUPPORTED;
+  if (!p3d_supported(d) || (zspace && !p3d_z_supported(d, zcrop_max))) return UNETK_E_UNSUPPORTED;
   if (ws_bytes < unetk_lits_patch3d_ws_bytes(d)) return UNETK_E_WORKSPACE;
   const int P = p3d_blocks(d);
   double* part = static_cast<double*>(ws);
@@ -523,8 +761,12 @@ static int lits_patch3d(const unetk_lits3d_desc* d, const uint16_t* slices, cons
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(P, d->N), fin(d->N);
   UNETK_LAUNCH(p3d_mask_stats_kernel, grid, dim3(256), 0, st, *d, slices, sample_tab, part);
+  if (zspace)
+    UNETK_LAUNCH(p3d_mask_stats_z_kernel, grid, dim3(256), 0, st, *d, slices, sample_tab, zcrop, zcrop_max, part);
   UNETK_LAUNCH(p3d_finalize_kernel, fin, dim3(64), 0, st, 0, P, (const double*)part, (const float*)minmax, stat);
   UNETK_LAUNCH(p3d_patch_kernel<ROT>, grid, dim3(256), 0, st, *d, slices, seg_slices, sample_tab, (const float*)stat, images, labels, part, minmax);
+  if (zspace)
+    UNETK_LAUNCH(p3d_patch_z_kernel, grid, dim3(256), 0, st, *d, slices, seg_slices, sample_tab, zcrop, zcrop_max, (const float*)stat, images, labels, part, minmax);
   if (warp)
     UNETK_LAUNCH(p3d_warp_kernel, grid, dim3(256), 0, st, *d, slices, seg_slices, sample_tab, warp, G, (const float*)stat, images, labels, part, minmax);
   if (d->training) {
@@ -542,6 +784,13 @@ extern "C" int unetk_lits_patch3d(const unetk_lits3d_desc* d, const uint16_t* sl
                                   const int32_t* sample_tab, float* images, int32_t* labels, void* ws, size_t ws_bytes,
                                   void* stream) {
   return lits_patch3d<false>(d, slices, seg_slices, sample_tab, images, labels, ws, ws_bytes, stream);
+}
+
+extern "C" int unetk_lits_patch3d_z(const unetk_lits3d_desc* d, const uint16_t* slices, const uint8_t* seg_slices,
+                                    const int32_t* sample_tab, const int32_t* zcrop, int zcrop_max, float* images,
+                                    int32_t* labels, void* ws, size_t ws_bytes, void* stream) {
+  return lits_patch3d<false>(d, slices, seg_slices, sample_tab, images, labels, ws, ws_bytes, stream, nullptr, 0, true, zcrop,
+                             zcrop_max);
 }
 
 extern "C" int unetk_lits_patch3d_rot(const unetk_lits3d_desc* d, const uint16_t* slices, const uint8_t* seg_slices,

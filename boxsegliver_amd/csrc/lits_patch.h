@@ -40,6 +40,17 @@ __device__ __forceinline__ Box3 p3d_box(const int32_t* __restrict__ t, const Des
   b.x1 = min(max(t[4] - b.cw / 2, 0), d.src_w - b.cw);
   return b;
 }
+// Rows resampled along z (the _z entries of lits3d.hip): the crop is cd slices deep, cd from zcrop[n] clamped
+// into [1, zcrop_max]; the box is p3d_box's with cd in place of D.  cd is not clamped to the case: p3d_slice gives -1 beyond it.
+__device__ __forceinline__ int p3d_zcrop(const int32_t* __restrict__ zcrop, int n, int zcrop_max) {
+  return min(max(zcrop[n], 1), zcrop_max);
+}
+template <class Desc>
+__device__ __forceinline__ Box3 p3d_box_z(const int32_t* __restrict__ t, const Desc& d, int cd) {
+  Box3 b = p3d_box(t, d);
+  b.z1 = (int)min(max((int64_t)t[2] - cd / 2, (int64_t)0), (int64_t)max(b.depth - cd, 0));
+  return b;
+}
 // store index of crop slice z, or -1 where the crop leaves the case (or the store): zeros, label 0
 template <class Desc>
 __device__ __forceinline__ int64_t p3d_slice(const Box3& b, int z, const Desc& d) {

@@ -57,7 +57,14 @@ gen_batch, :486-504 gen_kernel, inter_simulation strategy 4) training uses the f
 `python -m boxsegliver_amd.data.extract neg3d` into DIR/neg-<PID>.npz: they are expanded into a `neg` plane beside store.lb
 (load_neg_plane).  --hard_neg_patches P centres ceil(bs P) rows of every batch on a false-positive voxel
 (PatchSampler.draw_hard_neg -> `unetk_lits_pick_voxel_rows`), --hard_neg_clicks draws the background clicks inside the false
-positives of the crop (`unetk_lits3d_clicks_neg`).  eval_online never sees the plane; the restatement is tests/hard_neg_ref.py."""
+positives of the crop (`unetk_lits3d_clicks_neg`).  eval_online never sees the plane; the restatement is tests/hard_neg_ref.py.
+
+With --z_spacing MM (not a reference flag) the D output slices of a patch are MM millimetres apart in every case:
+a case of slice spacing sz is cropped cd = int(round((D - 1) MM / sz)) + 1 stored slices deep (crop_depth) and resized along z on
+the device.  Nothing is drawn for it; the rows' crop depths ride beside the table in the batch's one upload and the batches go
+through `unetk_lits_patch3d_z`, the windows of the offline evaluation and of --mode infer are cd slices deep and come back through
+`unetk_eval3d_accumulate_z` / `_wz`.  Clicks, rotation and deformation are refused with it; the restatement is
+tests/lits3d_zspace_ref.py."""
 import math
 from pathlib import Path
 
@@ -93,10 +100,16 @@ BOUNDARY_MAX_Z_SCALE = 16          # --boundary_z_scale: the cap of unetk_bounda
 FORCED_LABEL, FORCED_NEG = 1, 2    # COL_FORCED: the centre is picked on store.lb / on the `neg` plane
 
 
-def add_arguments(parser):
+def add_arguments(parser, z_spacing=True):
     """The flags of DataLoader/NF/input_pipeline_3d.py:53-67 that apply (names / defaults verbatim, data/flagsets.py) +
-    --lits_root and --seed as the 2-D LiTS sub-commands add them."""
+    --lits_root and --seed as the 2-D LiTS sub-commands add them.  z_spacing=False: without --z_spacing (the interactive
+    evaluator, which needs the clicks the flag refuses)."""
     flagsets.add_arguments(parser, "liver_3d")
+    if z_spacing:
+        parser.add_argument("--z_spacing", type=float, default=None, metavar="MM",
+                            help="--mode train / eval --eval_in_patches / infer: the --im_depth output slices of a patch are MM "
+                                 "millimetres apart in every case: int(round((im_depth - 1) * MM / slice spacing)) + 1 stored "
+                                 "slices are resized along z; default: im_depth consecutive stored slices")
     parser.add_argument("--lits_root", type=str, default="data/LiTS", help="where png/, meta.json and k_folds.txt live")
     parser.add_argument("--seed", type=int, default=1234)
     parser.add_argument("--eval_overlap", type=float, default=0.5,
@@ -143,9 +156,69 @@ def add_arguments(parser):
                         help="--mode infer: segment every *.nii / *.nii.gz of DIR, sorted by name")
 
 
+Z_SPACING_REFUSED = (       # (is the flag given?, its name, why): each needs z-resampling in a kernel of its own
+    (lambda a: (getattr(a, "slice_prior", "off") or "off") != "off", "--slice_prior",
+     "the prior's field is built on the crop's stored slices"),
+    (lambda a: bool(getattr(a, "hard_neg_clicks", False)), "--hard_neg_clicks", "the clicks are simulated on the crop's stored slices"),
+    (lambda a: bool(getattr(a, "use_spatial", False)), "--use_spatial",
+     "the clicks and the guide are simulated and rendered on the crop's stored slices"),
+    (lambda a: float(getattr(a, "random_rotate", 0.0) or 0.0) > 0.0, "--random_rotate", "the rotated rows have a patch kernel of their own"),
+    (lambda a: float(getattr(a, "random_deform", 0.0) or 0.0) > 0.0, "--random_deform", "the deformed rows have a patch kernel of their own"))
+
+
+def z_spacing(args):
+    """--z_spacing -> None (off) or MM > 0, finite.  Refused by name with the flags whose kernels do not resample along z."""
+    mm = getattr(args, "z_spacing", None)
+    if mm is None:
+        return None
+    mm = float(mm)
+    if not 0.0 < mm < float("inf"):                       # also refuses NaN
+        raise ValueError("--z_spacing must be a finite number of millimetres > 0, got {}".format(mm))
+    for given, flag, why in Z_SPACING_REFUSED:
+        if given(args):
+            raise NotImplementedError("--z_spacing with {} is not built: {}, which is not resampled along z".format(flag, why))
+    return mm
+
+
+def crop_depth(depth_out, mm, sz):
+    """Stored slices that --im_depth output slices MM millimetres apart span in a case of slice spacing sz:
+    int(round((D - 1) * MM / sz)) + 1, at least 1; sz == MM gives D.  Not clamped to the case's depth."""
+    return max(int(round((int(depth_out) - 1) * float(mm) / float(sz))) + 1, 1)
+
+
+def case_spacing(case):
+    """The slice spacing of a meta.json case, case["spacing"][0]; missing or not a positive finite number: ValueError naming it."""
+    spacing = case.get("spacing") if isinstance(case, dict) else None
+    try:
+        sz = float(spacing[0])
+    except (TypeError, ValueError, IndexError, KeyError):
+        sz = float("nan")
+    if not 0.0 < sz < float("inf"):
+        raise ValueError("--z_spacing: case {} has no positive slice spacing in meta.json (spacing = {!r})".format(
+            case.get("PID") if isinstance(case, dict) else case, spacing))
+    return sz
+
+
+def crop_depths(cases, depth_out, mm, src_hw):
+    """int32 [len(cases)]: crop_depth per case from its meta.json spacing.  Raises before anything is launched when the deepest
+    crop cannot be indexed in 31 bits (max(cd) * src_h * src_w >= 2^31, the kernels' limit)."""
+    cd = np.array([crop_depth(depth_out, mm, case_spacing(c)) for c in cases], dtype=np.int64)
+    check_crop_limit(cd, src_hw, [c.get("PID") for c in cases])
+    return cd.astype(np.int32)
+
+
+def check_crop_limit(cd, src_hw, names=None):
+    cd = np.atleast_1d(np.asarray(cd, dtype=np.int64))
+    if len(cd) and int(cd.max()) * int(src_hw[0]) * int(src_hw[1]) >= 1 << 31:
+        worst = int(np.argmax(cd))
+        raise ValueError("--z_spacing: case {} needs a crop of {} slices of {} x {}, beyond 31-bit indexing (>= 2^31 voxels)".format(
+            names[worst] if names is not None else worst, int(cd.max()), int(src_hw[0]), int(src_hw[1])))
+
+
 def check_args(args):
     mode = getattr(args, "mode", "train")
-    hard = hard_negatives(args)                            # first: --hard_neg_clicks comes with --use_spatial, refused below
+    z_spacing(args)                                        # first: its refusals name the flag, whatever else is wrong with it
+    hard = hard_negatives(args)                          # first: --hard_neg_clicks comes with --use_spatial, refused below
     if hard is not None and mode in ("eval", "infer"):
         raise ValueError("{} serve --mode train, got --mode {}".format(" / ".join(hard["flags"]), mode))
     if mode != "infer" and (getattr(args, "infer_volumes", None) or getattr(args, "infer_dir", None) is not None):
@@ -383,7 +456,7 @@ class PatchSampler(object):
 
     def __init__(self, cases, offset, slice_counts, batch_size, shape, src_hw, tumor_percent=0.5, zoom_scale=(1.0, 1.25),
                  random_flip=0, training=True, seed=None, random_rotate=0.0, rotate_prob=1.0, random_deform=0.0, deform_grid=4,
-                 deform_prob=1.0, hard_neg_patches=0.0, neg_counts=None):
+                 deform_prob=1.0, hard_neg_patches=0.0, neg_counts=None, z_spacing=None):
         self.bs = int(batch_size)
         self.deform = float(random_deform or 0.0) if training else 0.0      # pixels; > 0: draw_deform draws
         self.deform_grid = int(deform_grid)
@@ -397,6 +470,9 @@ class PatchSampler(object):
         self.flip = int(random_flip or 0) if training else 0
         self.rng = np.random.default_rng(seed)
         cases = list(cases)
+        # --z_spacing: the crop depth of every case; no draw depends on it (`crop_depth_rows` reads the batch)
+        self.zcrop = crop_depths(cases, shape[0], z_spacing, src_hw) if z_spacing is not None else None
+        self.zcrop_max = int(self.zcrop.max()) if self.zcrop is not None and len(self.zcrop) else 0
         self.pid = np.array([int(c["PID"]) for c in cases], dtype=np.int64)
         self.depth = np.array([int(c["size"][0]) for c in cases], dtype=np.int64)
         self.base = np.array([int(offset[int(p)]) for p in self.pid], dtype=np.int64)
@@ -517,6 +593,11 @@ class PatchSampler(object):
         g = self.deform_grid + 3
         return dict(on=on, ctl=self.rng.uniform(-self.deform, self.deform, (self.bs, 2, g, g)).astype(np.float32))
 
+    def crop_depth_rows(self, b):
+        """--z_spacing: int32 [bs], the crop depth of every row's case, for the batch `draw` (and `draw_hard_neg`) gave; None
+        without the flag.  It travels BESIDE the table (all 16 columns are taken) in the batch's one upload and draws nothing."""
+        return None if self.zcrop is None else np.ascontiguousarray(self.zcrop[np.asarray(b["case"])], dtype=np.int32)
+
     def table(self, b=None, rot=None, warp=None):
         """The batch as `unetk_lits_patch3d` takes it: int32 [bs, 16] (include/unetk.h), gamma as float bits.  rot: what
         `draw_rotation` gave -- the `on` rows get sin / cos (float64, cast to float32; float bits) in columns 13 / 14 for
@@ -568,7 +649,9 @@ def batches(store, sampler, shape, lab_max, fg_label, status=None, guide=None, p
     one-channel patch bit for bit.  No draw, no upload and no synchronisation is added.
     Hard negatives need store.neg, the plane of load_neg_plane: a sampler with force_fp > 0 re-targets rows
     (draw_hard_neg, right after draw) and the centres are picked per plane by `unetk_lits_pick_voxel_rows`; neg_clicks: the
-    clicks come from `unetk_lits3d_clicks_neg`.  Without either the calls are exactly those of a run without the flags."""
+    clicks come from `unetk_lits3d_clicks_neg`.  Without either the calls are exactly those of a run without the flags.
+    --z_spacing (a sampler built with z_spacing): the rows' crop depths, int32 [bs], ride beside the table in the
+    same upload and the batch goes through `unetk_lits_patch3d_z`; nothing is drawn for it."""
     hard_rows = getattr(sampler, "force_fp", 0) > 0
     if (hard_rows or neg_clicks) and getattr(store, "neg", None) is None:
         raise ValueError("hard negatives need the store's `neg` plane (load_neg_plane)")
@@ -576,6 +659,9 @@ def batches(store, sampler, shape, lab_max, fg_label, status=None, guide=None, p
         raise ValueError("--hard_neg_clicks needs the simulated clicks of a guided run")
     if prior is not None and guide is None:
         raise ValueError("a slice prior needs the simulated clicks of a guided run")
+    zspace = getattr(sampler, "zcrop", None) is not None
+    if zspace and (guide is not None or sampler.rotate > 0.0 or sampler.deform > 0.0):
+        raise ValueError("--z_spacing is not served together with --use_spatial, --random_rotate or --random_deform")
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=store.device)
     while True:
@@ -590,9 +676,13 @@ def batches(store, sampler, shape, lab_max, fg_label, status=None, guide=None, p
         deform = sampler.draw_deform()                       # --random_deform: the last draw; the lattices ride in the same upload
         if deform is not None:
             parts.append(deform["ctl"].view(np.int32))
+        zrows = sampler.crop_depth_rows(b) if zspace else None                   # --z_spacing: no draw; rides in the same upload
+        if zspace:
+            parts.insert(0, zrows)
         dev = lits.upload_pinned([sampler.table(b, rot, deform)] + parts, store.device)
         tab, ctab = dev[0], dev[1] if guide is not None else None
         warp, grid = (dev[-1].view(torch.float32), sampler.deform_grid) if deform is not None else (None, 0)
+        zkw = dict(zcrop=dev[1], zcrop_max=sampler.zcrop_max) if zspace else {}
         if hard_rows:                                        # one call per plane, each serving its own rows
             if sampler.force:
                 ops.lits_pick_voxel_rows(store.lb, tab, FORCED_LABEL, status, fg_label, lits.LB_SCALE)
@@ -601,7 +691,7 @@ def batches(store, sampler, shape, lab_max, fg_label, status=None, guide=None, p
             ops.lits_pick_voxels(store.lb, tab, fg_label, status, lits.LB_SCALE)
         rotate = sampler.rotate > 0.0                        # --random_rotate: the _rot entries, which read the table's (sin, cos)
         images, labels = ops.lits_patch3d(store.im, store.lb, tab, shape, sampler.training, lab_max, lits.IM_SCALE, lits.LB_SCALE,
-                                          rotate=rotate, warp=warp, grid=grid)
+                                          rotate=rotate, warp=warp, grid=grid, **zkw)
         feats = {"images": images, "names": torch.from_numpy(b["pid"])}
         if guide is not None:
             pts, cnt = ops.lits3d_clicks(store.lb, tab, ctab, shape, status, fg_label, CLICKS, lits.LB_SCALE,
@@ -662,7 +752,7 @@ def input_fn(mode, params):
                            neg_counts=params[("lits3d_neg_counts",)] if hard is not None else None,
                            tumor_percent=getattr(args, "tumor_percent", 0.5), zoom_scale=getattr(args, "zoom_scale", (1., 1.25)),
                            random_flip=getattr(args, "random_flip", 0), training=training, seed=seed, random_rotate=deg,
-                           rotate_prob=prob, random_deform=px, deform_grid=grid, deform_prob=dprob)
+                           rotate_prob=prob, random_deform=px, deform_grid=grid, deform_prob=dprob, z_spacing=z_spacing(args))
     # the pick kernel's status words live in `params` (one per mode) so that they outlast the generators: params[("lits3d_status",
     # True)] is the training stream's.  An evaluation synchronises anyway, so both are read there: the training word when
     # the evaluation starts, the evaluation's own after its last batch.
@@ -711,11 +801,12 @@ def mirror_variants(args):
     return [(m & 1, (m >> 1) & 1, (m >> 2) & 1) for m in variants]
 
 
-def eval_windows(src_hw, shape):
+def eval_windows(src_hw, shape, cd=None):
     """(D, ch, cw): a window's extent in the case -- im_depth slices (fewer exist in a shallower case) and the
-    `eval_online` crop int32((H, W) * EVAL_ZOOM) clamped to the slice, as the kernels' crop box clamps it."""
+    `eval_online` crop int32((H, W) * EVAL_ZOOM) clamped to the slice, as the kernels' crop box clamps it.  cd: the case's crop
+    depth with --z_spacing (crop_depth), which takes the place of D: (cd, ch, cw)."""
     ch, cw = (int(v) for v in crop_shape(shape[1:], (EVAL_ZOOM, EVAL_ZOOM)))
-    return int(shape[0]), min(max(ch, 1), int(src_hw[0])), min(max(cw, 1), int(src_hw[1]))
+    return int(shape[0] if cd is None else cd), min(max(ch, 1), int(src_hw[0])), min(max(cw, 1), int(src_hw[1]))
 
 
 def window_weights(shape, sigma):
@@ -780,16 +871,18 @@ def box_starts(extent, window, overlap, lo, hi):
     return [lo + s for s in window_starts(hi - lo, window, overlap)]
 
 
-def eval_tables(case, store, shape, overlap, variants, batch_size, box=None):
+def eval_tables(case, store, shape, overlap, variants, batch_size, box=None, cd=None):
     """The sample tables (PatchSampler.table's layout, int32 [n, 16]) that tile ONE case with windows, in batches of
     `batch_size` rows, the last one short.  Windows are cut as `eval_online` cuts them (zoom EVAL_ZOOM, no gamma, not
     forced) and cover the whole volume -- not the ground-truth liver box: no label information enters the prediction --
     or, with box = (z0, z1, y0, y1, x0, x1) (prediction_box), that box: box_starts per axis.
     A window that starts at `a` is centred on a + window // 2, from which the kernels' volume_crop clamp gives back `a`.
-    Every window is followed by its mirror variants: the same row with the flip columns set."""
+    Every window is followed by its mirror variants: the same row with the flip columns set.
+    cd: the case's crop depth with --z_spacing (crop_depth): the windows are cd stored slices deep, tiled with window_starts(depth,
+    cd, overlap), and the rows' crop depths (all cd) go beside each table to the _z entries."""
     pid, depth = int(case["PID"]), int(case["size"][0])
     src_h, src_w = int(store.im.shape[1]), int(store.im.shape[2])
-    d, ch, cw = eval_windows((src_h, src_w), shape)
+    d, ch, cw = eval_windows((src_h, src_w), shape, cd)
     if box is None:
         box = (0, depth, 0, src_h, 0, src_w)
     elif not (0 <= box[0] < box[1] <= depth and 0 <= box[2] < box[3] <= src_h and 0 <= box[4] < box[5] <= src_w):
@@ -812,11 +905,12 @@ def eval_tables(case, store, shape, overlap, variants, batch_size, box=None):
         yield tab[i:i + bs]
 
 
-def table_box(tab, shape, depth, src_hw):
+def table_box(tab, shape, depth, src_hw, cd=None):
     """(z0, z1, y0, y1, x0, x1): the union box of a table's crop boxes inside the case (the voxels
-    `unetk_eval3d_accumulate` visits), computed as the kernels' crop box (p3d_box, csrc/lits3d.hip) computes them."""
+    `unetk_eval3d_accumulate` visits), computed as the kernels' crop box (p3d_box, csrc/lits3d.hip) computes them.  cd: the
+    rows' crop depth with --z_spacing, in place of D (p3d_box_z)."""
     tab = np.asarray(tab).astype(np.int64)
-    d, depth = int(shape[0]), int(depth)
+    d, depth = int(shape[0] if cd is None else cd), int(depth)
     ch = np.clip(tab[:, COL_CH], 1, int(src_hw[0]))
     cw = np.clip(tab[:, COL_CW], 1, int(src_hw[1]))
     z1 = np.minimum(np.maximum(tab[:, COL_CZ] - d // 2, 0), max(depth - d, 0))
@@ -865,14 +959,18 @@ def _eval_cases(args, params):
     shape = (int(args.im_depth), int(args.im_height), int(args.im_width))
     variants = mirror_variants(args)
     box_from = getattr(args, "eval_box_from", None)
-    for case in cases:
+    mm = z_spacing(args)
+    # --z_spacing: every case's crop depth, checked for all of them before the first window is cut
+    depths = crop_depths(cases, shape[0], mm, store.im.shape[1:]) if mm is not None else None
+    for i, case in enumerate(cases):
         pid, depth = int(case["PID"]), int(case["size"][0])
         end = dict(case=str(pid), base=int(store.offset[pid]), depth=depth, store=store)
         box = None
         if box_from is not None:
             box = end["box"] = prediction_box(box_from, case, depth, store.im.shape[1:], getattr(args, "eval_box_margin", DEFAULT_BOX_MARGIN))
-        for tab in eval_tables(case, store, shape, float(getattr(args, "eval_overlap", 0.5)), variants, bs, box):
-            yield tab, None
+        cd = int(depths[i]) if depths is not None else None
+        for tab in eval_tables(case, store, shape, float(getattr(args, "eval_overlap", 0.5)), variants, bs, box, cd=cd):
+            yield tab, ({"zcrop": cd} if cd is not None else None)
         yield None, end
 
 
@@ -945,6 +1043,19 @@ def infer_plan(path):
     return dict(header=header, case=case, special=special, dtype=header.dtype, file_shape=tuple(header.shape),
                 nbytes=int(np.prod(header.shape)) * header.dtype.itemsize, trans_bk=trans_bk, flips=flips,
                 shape=nii_kits.data_shape(header))
+
+
+def infer_spacing(path, plan):
+    """--z_spacing in --mode infer: the slice spacing of an input volume = the pixdim of whichever FILE axis the ingest maps to
+    the store's z axis (plan["trans_bk"][i] == 0), not pixdim[3] of a transposed file.  Not a positive finite number: ValueError
+    naming the file."""
+    axis = [int(a) for a in plan["trans_bk"]].index(0)
+    pixdim = tuple(plan["header"].pixdim)
+    sz = float(pixdim[axis]) if axis < len(pixdim) else float("nan")
+    if not 0.0 < sz < float("inf"):
+        raise ValueError("--z_spacing: {} (case {}) has no positive slice spacing: pixdim[{}] = {!r}".format(
+            path, plan["case"], axis + 1, pixdim[axis] if axis < len(pixdim) else None))
+    return sz
 
 
 def read_voxel_block(path, header, view):
@@ -1060,6 +1171,7 @@ def _infer_cases(args, params, files):
     shape = (int(args.im_depth), int(args.im_height), int(args.im_width))
     variants = mirror_variants(args)
     box_from = getattr(args, "eval_box_from", None)
+    mm = z_spacing(args)
     reader = VolumeReader(files, device, ahead=bool(params.get("infer_read_ahead", True)))
     zeros = None                                           # the labels of every case: zeroed once, grown to the largest case
     try:
@@ -1083,8 +1195,12 @@ def _infer_cases(args, params, files):
             if box_from is not None:
                 box = end["box"] = prediction_box(box_from, plan["case"], depth, (src_h, src_w),
                                                   getattr(args, "eval_box_margin", DEFAULT_BOX_MARGIN), special=plan["special"])
-            for tab in eval_tables(case, store, shape, float(getattr(args, "eval_overlap", 0.5)), variants, bs, box):
-                yield tab, {"store": store}
+            cd = None
+            if mm is not None:                             # --z_spacing: the pixdim of the file axis that became the store's z
+                cd = crop_depth(shape[0], mm, infer_spacing(files[i], plan))
+                check_crop_limit([cd], (src_h, src_w), [plan["case"]])
+            for tab in eval_tables(case, store, shape, float(getattr(args, "eval_overlap", 0.5)), variants, bs, box, cd=cd):
+                yield tab, ({"store": store, "zcrop": cd} if cd is not None else {"store": store})
             yield None, end
     finally:
         reader.close()

@@ -66,7 +66,7 @@ def build_parser():
     config.add_arguments(parser)
     models.add_arguments(parser)
     loss_metrics.add_arguments(parser)
-    lits3d.add_arguments(parser)
+    lits3d.add_arguments(parser, z_spacing=False)                            # the sessions need --use_spatial, which the flag refuses
     group = parser.add_argument_group(title="Input Pipeline Arguments (nf_3d only)")
     for name in NF_3D_ONLY:                                                  # input_pipeline_3d.py:53-80, names / defaults verbatim
         kw = dict(flagsets.FLAGS[name])

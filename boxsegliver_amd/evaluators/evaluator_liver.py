@@ -141,11 +141,18 @@ class CaseWindows3D(object):
         self.host_tables = lits3d.window_weights(self.shape, getattr(cfg, "eval_window_sigma", 0.125)) if self.gaussian else None
         self.acc = self.cnt = self.tables = self.kept = None
 
-    def add(self, store, tab, sp_guide=None, before_forward=None, prior=None):
+    def add(self, store, tab, sp_guide=None, before_forward=None, prior=None, zcrop=None):
+        """zcrop: the crop depth of the table's windows with --z_spacing (one case, so one value): it rides
+        beside the table in the same upload as int32 [n], and the _z entries cut the windows and take them back."""
         from ..data import lits, lits3d
         shape = self.shape
-        (dtab,) = lits.upload_pinned([tab], store.device)
-        images, _ = ops.lits_patch3d(store.im, store.lb, dtab, shape, False, self.lab_max, lits.IM_SCALE, lits.LB_SCALE)
+        zkw = {}
+        if zcrop is None:
+            (dtab,) = lits.upload_pinned([tab], store.device)
+        else:
+            dtab, dz = lits.upload_pinned([tab, np.full(len(tab), int(zcrop), dtype=np.int32)], store.device)
+            zkw = dict(zcrop=dz, zcrop_max=int(zcrop))
+        images, _ = ops.lits_patch3d(store.im, store.lb, dtab, shape, False, self.lab_max, lits.IM_SCALE, lits.LB_SCALE, **zkw)
         features = {"images": images if prior is None else prior(dtab, images)}
         if sp_guide is not None:
             features["sp_guide"] = sp_guide(dtab)
@@ -157,13 +164,14 @@ class CaseWindows3D(object):
         if self.acc is None:
             self.acc = torch.zeros((depth,) + src_hw + (prob.shape[-1],), dtype=torch.float32, device=store.device)
             self.cnt = torch.zeros((depth,) + src_hw, dtype=torch.float32 if self.gaussian else torch.int32, device=store.device)
-        box = lits3d.table_box(tab, shape, depth, src_hw)
+        box = lits3d.table_box(tab, shape, depth, src_hw, cd=zcrop)
         if self.gaussian:
             if self.tables is None:                                     # once per run
                 self.tables = lits.upload_pinned(list(self.host_tables), store.device)
-            ops.eval3d_accumulate_w(prob, dtab, shape, base, depth, box, self.tables, self.acc, self.cnt, store.im, host_tab=tab)
+            ops.eval3d_accumulate_w(prob, dtab, shape, base, depth, box, self.tables, self.acc, self.cnt, store.im, host_tab=tab,
+                                    **zkw)
         else:
-            ops.eval3d_accumulate(prob, dtab, shape, base, depth, box, self.acc, self.cnt, store.im, host_tab=tab)
+            ops.eval3d_accumulate(prob, dtab, shape, base, depth, box, self.acc, self.cnt, store.im, host_tab=tab, **zkw)
 
     def labels(self, store, base, depth):
         from ..data import lits
@@ -578,8 +586,9 @@ class EvaluateVolume(EvaluateBase):
             for tab, end in input_fn(mode, params):
                 if tab is not None:
                     # --mode infer: the table's own one-case store; else the fold's, resident before input_fn_eval's first item
-                    store = end["store"] if end is not None else params[("lits_store", False)][0]
-                    windows.add(store, tab, before_forward=restore_once)
+                    # --z_spacing: the item beside a table carries the case's crop depth
+                    store = end["store"] if end is not None and "store" in end else params[("lits_store", False)][0]
+                    windows.add(store, tab, before_forward=restore_once, zcrop=end.get("zcrop") if end is not None else None)
                 else:
                     if windows.acc is None or end["depth"] != windows.acc.shape[0]:
                         raise RuntimeError("case {} ended without windows of its own".format(end["case"]))

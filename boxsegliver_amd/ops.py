@@ -1755,16 +1755,33 @@ def _warp_lattice(warp, grid, n, device):
     return g
 
 
+def _zcrop_args(name, zcrop, zcrop_max, n, device, slices):
+    """The checks of a `zcrop=` argument: int32 [n] on the table's device and zcrop_max, the largest crop
+    depth the host put there -> int(zcrop_max); zcrop_max * src_h * src_w must index in 31 bits."""
+    _require_cuda(zcrop)
+    assert zcrop.dtype == torch.int32 and tuple(zcrop.shape) == (n,) and zcrop.is_contiguous() and zcrop.device == device
+    zmax = int(zcrop_max)
+    if zmax < 1:
+        raise ValueError("{}: zcrop_max must be >= 1, got {}".format(name, zcrop_max))
+    if zmax * int(slices.shape[1]) * int(slices.shape[2]) >= 1 << 31 or zmax >= 1 << 24:
+        raise _abi.UnetkError("{}: a crop of {} slices of {} x {} is beyond 31-bit indexing".format(name, zmax, slices.shape[1],
+                                                                                                 slices.shape[2]))
+    return zmax
+
+
 def lits_patch3d(slices, seg_slices, sample_tab, shape, training, lab_max=2, im_scale=64, lab_scale=64, rotate=False, warp=None,
-                 grid=0):
+                 grid=0, zcrop=None, zcrop_max=0):
     """One UNet3D batch from the device-resident slice store (unetk_lits_patch3d; include/unetk.h has the table layout):
     slices uint16 / seg_slices uint8 [n, src_h, src_w] (stored as int16 / uint8 tensors), sample_tab int32 [N, 16],
     shape = (D, H, W).  Returns images f32 [N, D, H, W, 1], labels int32 [N, D, H, W].  training: gamma augmentation with
     the table's per-sample gamma.  rotate: unetk_lits_patch3d_rot, which turns the rows whose columns 13 / 14 hold (sin, cos)
     in the plane; without it the columns are ignored.  warp f32 [N, 2, grid + 3, grid + 3]:
     unetk_lits_patch3d_warp, which also deforms the rows whose column 15 is not zero by their B-spline lattice of `grid` cells
-    per axis and reads the rotation columns whatever `rotate` says.  Current stream; no host
-    synchronisation."""
+    per axis and reads the rotation columns whatever `rotate` says.  zcrop int32 [N] with zcrop_max, its
+    largest entry: unetk_lits_patch3d_z, which resizes min(max(zcrop[n], 1), zcrop_max) crop slices of row n to the D output
+    slices (not together with rotate / warp).  Current stream; no host synchronisation."""
+    if zcrop is not None and (rotate or warp is not None):
+        raise ValueError("lits_patch3d: zcrop is not served together with rotate or warp (DESIGN.md 7.3.17)")
     _require_cuda(slices, seg_slices, sample_tab)
     assert slices.dtype in (torch.int16, torch.uint16) and seg_slices.dtype == torch.uint8
     assert slices.is_contiguous() and seg_slices.is_contiguous() and slices.shape == seg_slices.shape and slices.dim() == 3
@@ -1783,6 +1800,8 @@ def lits_patch3d(slices, seg_slices, sample_tab, shape, training, lab_max=2, im_
     # reads depend on the table's zoom and are left out
     name = "lits_patch3d_warp" if warp is not None else "lits_patch3d_rot" if rotate else "lits_patch3d"
     lattice = () if warp is None else (ptr(warp), _warp_lattice(warp, grid, n, sample_tab.device))
+    if zcrop is not None:
+        name, lattice = "lits_patch3d_z", (ptr(zcrop), _zcrop_args("lits_patch3d", zcrop, zcrop_max, n, sample_tab.device, slices))
     with _timed_hbm(name, images, 5 if training else 1, labels.numel() * 4):
         check(getattr(_abi.lib(), "unetk_" + name)(ctypes.byref(desc), ptr(slices), ptr(seg_slices), ptr(sample_tab), *lattice,
                                                    ptr(images), ptr(labels), ptr(ws), nbytes, stream_ptr()), name)
@@ -1820,16 +1839,26 @@ def _eval3d_accumulate_args(name, probs, sample_tab, shape, case_base, case_dept
     return desc, c, cbox, (cbox[1] - cbox[0]) * (cbox[3] - cbox[2]) * (cbox[5] - cbox[4])
 
 
-def eval3d_accumulate(probs, sample_tab, shape, case_base, case_depth, box, acc, cnt, slices, host_tab=None):
+def eval3d_accumulate(probs, sample_tab, shape, case_base, case_depth, box, acc, cnt, slices, host_tab=None, zcrop=None,
+                      zcrop_max=0):
     """Window probabilities back into ONE case at source resolution (unetk_eval3d_accumulate): probs f32
     [N, D, H, W, C] of the windows `lits_patch3d(..., training=False)` cut for sample_tab int32 [N, 16]; acc f32
     [depth, src_h, src_w, C] and cnt int32 [depth, src_h, src_w] are updated IN PLACE (the caller zeroes them before the
     case's first batch); box = (z0, z1, y0, y1, x0, x1), the union of the rows' crop boxes; slices: the resident store the
     windows were cut from (its extent enters the crop box).  host_tab: the table's host copy, when the caller has it -- the
     rows' (base, depth) are then checked against the case here (a device table is not read back), and a row with a rotation
-    in columns 13 / 14 raises ValueError (the kernels ignore those columns).  Current stream; no host synchronisation."""
+    in columns 13 / 14 raises ValueError (the kernels ignore those columns).  zcrop int32 [N] with zcrop_max: the windows
+    `lits_patch3d(..., zcrop=zcrop, zcrop_max=zcrop_max)` cut (unetk_eval3d_accumulate_z), box the union of
+    their cd-deep crop boxes.  Current stream; no host synchronisation."""
     desc, c, cbox, nvox = _eval3d_accumulate_args("eval3d_accumulate", probs, sample_tab, shape, case_base, case_depth, box, acc,
                                                   cnt, torch.int32, slices, host_tab)
+    if zcrop is not None:
+        zmax = _zcrop_args("eval3d_accumulate", zcrop, zcrop_max, sample_tab.shape[0], sample_tab.device, slices)
+        with _timed_hbm("eval3d_accumulate_z", probs, 1, nvox * 8 * (c + 1)):
+            check(_abi.lib().unetk_eval3d_accumulate_z(ctypes.byref(desc), ptr(sample_tab), ptr(zcrop), zmax, ptr(probs), c,
+                                                       int(case_base), int(case_depth), cbox, ptr(acc), ptr(cnt), stream_ptr()),
+                  "eval3d_accumulate_z")
+        return acc, cnt
     # algorithmic bytes: the windows read once, the box of acc read and written, the box of cnt read and written
     with _timed_hbm("eval3d_accumulate", probs, 1, nvox * 8 * (c + 1)):
         check(_abi.lib().unetk_eval3d_accumulate(ctypes.byref(desc), ptr(sample_tab), ptr(probs), c, int(case_base),
@@ -1837,16 +1866,24 @@ def eval3d_accumulate(probs, sample_tab, shape, case_base, case_depth, box, acc,
     return acc, cnt
 
 
-def eval3d_accumulate_w(probs, sample_tab, shape, case_base, case_depth, box, tables, acc, wsum, slices, host_tab=None):
+def eval3d_accumulate_w(probs, sample_tab, shape, case_base, case_depth, box, tables, acc, wsum, slices, host_tab=None, zcrop=None,
+                        zcrop_max=0):
     """eval3d_accumulate with centre-weighted windows (unetk_eval3d_accumulate_w; --eval_window_weight gaussian): tables =
     (gz f32 [D], gy f32 [H], gx f32 [W]) device vectors (data/lits3d.window_weights); wsum f32 [depth, src_h, src_w] takes
-    the place of cnt and collects the weights.  Everything else as eval3d_accumulate."""
+    the place of cnt and collects the weights.  Everything else as eval3d_accumulate (zcrop: unetk_eval3d_accumulate_wz)."""
     desc, c, cbox, nvox = _eval3d_accumulate_args("eval3d_accumulate_w", probs, sample_tab, shape, case_base, case_depth, box, acc,
                                                   wsum, torch.float32, slices, host_tab)
     gz, gy, gx = tables
     _require_cuda(gz, gy, gx)
     for g, n in zip((gz, gy, gx), shape):
         assert g.dtype == torch.float32 and tuple(g.shape) == (int(n),) and g.is_contiguous()
+    if zcrop is not None:
+        zmax = _zcrop_args("eval3d_accumulate_w", zcrop, zcrop_max, sample_tab.shape[0], sample_tab.device, slices)
+        with _timed_hbm("eval3d_accumulate_wz", probs, 1, nvox * 8 * (c + 1) + 4 * (gz.numel() + gy.numel() + gx.numel())):
+            check(_abi.lib().unetk_eval3d_accumulate_wz(ctypes.byref(desc), ptr(sample_tab), ptr(zcrop), zmax, ptr(probs), c,
+                                                        int(case_base), int(case_depth), cbox, ptr(gz), ptr(gy), ptr(gx), ptr(acc),
+                                                        ptr(wsum), stream_ptr()), "eval3d_accumulate_wz")
+        return acc, wsum
     # algorithmic bytes: as eval3d_accumulate with wsum for cnt, and the three tables once
     with _timed_hbm("eval3d_accumulate_w", probs, 1, nvox * 8 * (c + 1) + 4 * (gz.numel() + gy.numel() + gx.numel())):
         check(_abi.lib().unetk_eval3d_accumulate_w(ctypes.byref(desc), ptr(sample_tab), ptr(probs), c, int(case_base),

@@ -905,6 +905,28 @@ int unetk_lits_patch3d_warp(const unetk_lits3d_desc* d, const uint16_t* slices, 
                             const int32_t* sample_tab, const float* warp, int G, float* images, int32_t* labels,
                             void* ws, size_t ws_bytes, void* stream);
 
+/* Patches at a fixed slice spacing (additive to ABI 10).  unetk_lits_patch3d with one more input:
+ *   zcrop int32 [N] (device memory, 4-byte aligned), zcrop_max (host int, >= 1): per row cd = min(max(zcrop[n], 1), zcrop_max)
+ *   crop slices are resized to the D output slices -- a true 3-D crop-and-resize.
+ * Per row:
+ *   crop box: as unetk_lits_patch3d with cd in place of D, z1 = min(max(cz - cd/2, 0), max(depth - cd, 0)); cd is NOT clamped
+ *     to the case: crop slices at or beyond `depth` read as zeros with label 0;
+ *   mask statistics over the cd x ch x cw source crop (fp64 partials per block, summed by index);
+ *   voxel (z, y, x) of the un-flipped patch: zs = (cd - 1) / (D - 1) (0 when D == 1), in_z = z zs (float32),
+ *     i0 = floor(in_z), i1 = min(i0 + 1, cd - 1), fz = in_z - i0  -- the taps of y and x, align_corners;
+ *   image: v0, v1 = the in-plane value of crop slices i0, i1, each computed exactly as unetk_lits_patch3d computes it (every
+ *     corner normalised on the fly, then the two lerps; a slice outside the case gives 0), v = v0 + fz (v1 - v0);
+ *     no anti-aliasing when cd > D, as in the plane;
+ *   labels: crop slice min(roundf(in_z), cd - 1) at the in-plane nearest pixel;
+ *   flips, patch moments and gamma as unetk_lits_patch3d, on the D x H x W result, same block partition.
+ * A row with cd == D gives the output of unetk_lits_patch3d bit for bit (training != 0 included), whatever the other rows hold.
+ * Nothing is read out of bounds for any content of zcrop.  zcrop NULL or misaligned, zcrop_max < 1: UNETK_E_BADARG;
+ * zcrop_max * src_h * src_w >= 2^31: UNETK_E_UNSUPPORTED.  Otherwise the arguments, checks, error codes and workspace query of
+ * unetk_lits_patch3d. */
+int unetk_lits_patch3d_z(const unetk_lits3d_desc* d, const uint16_t* slices, const uint8_t* seg_slices,
+                         const int32_t* sample_tab, const int32_t* zcrop, int zcrop_max, float* images, int32_t* labels,
+                         void* ws, size_t ws_bytes, void* stream);
+
 /* Whole-volume evaluation in windows.  probs f32 [N,D,H,W,C]: the class probabilities of the N windows that
  * unetk_lits_patch3d(training = 0) cut for sample_tab (same desc, same table, flips included).  acc f32 [depth,src_h,src_w,C],
  * cnt int32 [depth,src_h,src_w]: ONE case, zeroed by the caller before its first batch.  All rows must carry this case's
@@ -929,6 +951,21 @@ int unetk_eval3d_accumulate(const unetk_lits3d_desc* d, const int32_t* sample_ta
 int unetk_eval3d_accumulate_w(const unetk_lits3d_desc* d, const int32_t* sample_tab, const float* probs, int C,
                               int64_t case_base, int case_depth, const int32_t box[6], const float* gz, const float* gy,
                               const float* gx, float* acc, float* wsum, void* stream);
+
+/* The way back of unetk_lits_patch3d_z (additive to ABI 10): the two gathers above for windows cut with the
+ * same zcrop / zcrop_max pair.  A case voxel z lies in a row's window when 0 <= zw = z - z1 < cd (z1 with cd in place of D).
+ * The inverse resize along z: in_z = zw (D - 1) / (cd - 1) (0 when cd == 1), i0 = floor(in_z), i1 = min(i0 + 1, D - 1),
+ * fz = in_z - i0; the hit is p0 + fz (p1 - p0) of the in-plane bilerps p0, p1 of window slices i0 and i1, read through the row's
+ * front/back flip.  _wz scales a hit by (gz[i0] + (gz[i1] - gz[i0]) fz) * wy * wx.  Rows in index order, one writer per
+ * (voxel, class), no atomics; cnt and wsum as above.  When every row has cd == D the outputs equal those of
+ * unetk_eval3d_accumulate / _w bit for bit.  zcrop NULL or misaligned, zcrop_max < 1: UNETK_E_BADARG; zcrop_max * src_h * src_w
+ * >= 2^31: UNETK_E_UNSUPPORTED; nothing is read out of bounds for any content of zcrop. */
+int unetk_eval3d_accumulate_z(const unetk_lits3d_desc* d, const int32_t* sample_tab, const int32_t* zcrop, int zcrop_max,
+                              const float* probs, int C, int64_t case_base, int case_depth, const int32_t box[6], float* acc,
+                              int32_t* cnt, void* stream);
+int unetk_eval3d_accumulate_wz(const unetk_lits3d_desc* d, const int32_t* sample_tab, const int32_t* zcrop, int zcrop_max,
+                               const float* probs, int C, int64_t case_base, int case_depth, const int32_t box[6],
+                               const float* gz, const float* gy, const float* gx, float* acc, float* wsum, void* stream);
 
 /* The end of a case: acc f32 [depth,src_h,src_w,C] and EXACTLY ONE of wsum (f32) / cnt (int32) [depth,src_h,src_w], the other
  * NULL -> pred uint8 [depth,src_h,src_w].  box = {z0, z1, y0, y1, x0, x1} (host memory, inside the volume, not empty): the part
